@@ -12,6 +12,12 @@ the poses are gathered with one RCCL all_gather per step.
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times `--steps` steps and prints the headline (`value`, `ms_per_step`) with what the timed
+steps themselves yield (5-NN launch times, the roofline of that kernel).  `--full` adds everything else, measured after
+the timed region: per-kernel times of fit / solve / index build and their roofs, the 5-NN candidate count, the
+steady-state companion, the pinned-host-memory leg, the CPU oracle baseline with the pose check, and `stages`.
+`--dump-outputs DIR` writes what the last timed step returned (poses, statuses) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -266,6 +272,25 @@ def host_buffer_rate(h, inp, B, reps=5):
     return B / dt, 1e3 * dt, int(c.nbytes + s.nbytes + g.nbytes), [1e3 * t for t in ts], B / (sum(ts) / len(ts))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """arrays: {name: (n, ...) array with one row per scan} -> path/<name>.npy in float64 (f32 stays f32).  Above 64 MB in all,
+    the same fixed, seeded sample of rows of every array, and its row numbers as path/sample_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.asarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    n = len(next(iter(out.values())))
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, int(n * DUMP_LIMIT_BYTES // (total + 8 * n)))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        out = {k: a[rows] for k, a in out.items()}
+        out["sample_rows"] = rows.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -289,7 +314,14 @@ def main():
     ap.add_argument("--stage-slam-scans", type=int, default=100, help="scans of the SLAM-step replay in `stages` (0 disables it)")
     ap.add_argument("--features", choices=["product", "direct"], default="product",
                     help="product: features from the GPU extraction + voxel kernels; direct: from ray-cast hit kinds")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline (per-kernel timing steps, 5-NN candidate count, --steady-steps, "
+                         "value_incl_h2d, cpu_baseline, stages); the --no-* / --cpu-sample / --steady-steps options shape these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the poses (f64) and statuses of the last timed step as DIR/<name>.npy (rank 0; strong scaling: the whole job)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -400,25 +432,31 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     timing = h.get_timing(reset=True)
-    h.set_timing(1)
-    for _ in range(3):
+    # what the last timed step returned: the --full legs below run the step again
+    poses_gpu = d_poses[:B].cpu().numpy()
+    status_gpu = d_status[:B].cpu().numpy()
+    timing_all = None
+    knn_first = knn_seeded = knn_candidates = None
+    steady_steps = args.steady_steps if args.full else 0
+    elapsed_steady = None
+    if args.full:
+        h.set_timing(1)
+        for _ in range(3):
+            step()
+        barrier()
+        timing_all = h.get_timing(reset=True)
+        # one more step with the counting 5-NN instantiation: map points whose distance was evaluated (SURVEY.md 8d's
+        # secondary figure; the HBM roofline is not what binds this kernel)
+        h.set_timing(3)
+        h.get_timing(reset=True)
         step()
-    barrier()
-    timing_all = h.get_timing(reset=True)
-    # one more step with the counting 5-NN instantiation: map points whose distance was evaluated (SURVEY.md 8d's
-    # secondary figure; the HBM roofline is not what binds this kernel)
-    h.set_timing(3)
-    h.get_timing(reset=True)
-    step()
-    barrier()
-    t_knn = h.get_timing(reset=True)
-    knn_first, knn_seeded = t_knn.knn_candidates, t_knn.knn_candidates_seeded
-    knn_candidates = knn_first + knn_seeded
+        barrier()
+        t_knn = h.get_timing(reset=True)
+        knn_first, knn_seeded = t_knn.knn_candidates, t_knn.knn_candidates_seeded
+        knn_candidates = knn_first + knn_seeded
     h.set_timing(0)
     # steady-state companion: the timed region above is `--steps` steps from wherever the clocks were after the
     # warm-up (the driver's 20 steps sit on the ramp, profiles/r04_step_ramp.json); 200 more steps, same bracket, never `value`
-    steady_steps = args.steady_steps
-    elapsed_steady = None
     if steady_steps > 0:
         barrier()
         t0 = time.perf_counter()
@@ -442,9 +480,8 @@ def main():
             dist.all_gather(every, t)
             elapsed_steady = max(float(e.item()) for e in every)
 
-    poses_gpu = d_poses[:B].cpu().numpy()
-    status_gpu = d_status[:B].cpu().numpy()
     poses_sha1 = None
+    dump = {"poses": poses_gpu, "status": status_gpu}
     if strong:
         # every rank's block back in scan order (one more gather, outside the timed region): the job's result must not
         # depend on how many ranks shared it
@@ -452,10 +489,13 @@ def main():
         if use_dist and (world_size > 1 or force_coll):
             t_p = torch.from_numpy(poses_gpu).to(dev if not shared_gpu else "cpu"); t_s = torch.from_numpy(status_gpu).to(dev if not shared_gpu else "cpu")
             all_p, all_s = mdist.gather_ragged(t_p, t_s, total_scans, force=force_coll)
-            all_p = all_p.cpu().numpy()
+            all_p, all_s = all_p.cpu().numpy(), all_s.cpu().numpy()
         else:
-            all_p = poses_gpu
+            all_p, all_s = poses_gpu, status_gpu
         poses_sha1 = hashlib.sha1(np.ascontiguousarray(all_p).tobytes()).hexdigest()
+        dump = {"poses": all_p, "status": all_s}
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dump)
 
     if rank == 0:
         from msf_loam_amd import synth
@@ -467,8 +507,11 @@ def main():
         # + the map read once per batch, split over the n_outer launches + one pose per scan.
         alg_bytes_assoc = F_total * 96 + (n_mc + n_ms) * 16 / n_outer + B * 56
         assoc_ms = timing.ms_assoc / max(timing.launches_assoc, 1)
-        solve_ms = timing_all.ms_solve / max(timing_all.launches_solve, 1)
-        index_ms = timing_all.ms_index / 3.0          # per STEP (both maps): the three extra steps above; round 6: one timed span per msfl_set_map (pair build), two before
+        fit_ms = solve_ms = index_ms = None           # --full only: timed in the three extra steps
+        if timing_all is not None:
+            fit_ms = timing_all.ms_fit / max(timing_all.launches_fit, 1)
+            solve_ms = timing_all.ms_solve / max(timing_all.launches_solve, 1)
+            index_ms = timing_all.ms_index / 3.0          # per STEP (both maps): the three extra steps above; round 6: one timed span per msfl_set_map (pair build), two before
         achieved = alg_bytes_assoc / (assoc_ms * 1e-3) / 1e9 if assoc_ms > 0 else 0.0
         # HBM traffic of the dominant kernel: PMC counters cannot be sampled from inside this process, so
         # the figure comes from the committed rocprofv3 --pmc profile of this same command
@@ -505,26 +548,28 @@ def main():
                                        "kernel is nearer to: its working set is L2-resident (traffic < algorithmic bytes) and its VALU issue "
                                        "fraction (`valu.frac`) is the larger one; `vmem.ta_busy_frac` is the second resource at ~0.8: a "
                                        "multi-dword load instruction costs the CU's texture addresser ~16 clocks whatever it fetches (profiles/r04b_vmem_rate.md)",
-                         "kernels": (kernel_roofs({ASSOC_KERNEL_PREFIX: assoc_ms, "fit_scan2map": timing_all.ms_fit / max(timing_all.launches_fit, 1),
+                         "kernels": (kernel_roofs({ASSOC_KERNEL_PREFIX: assoc_ms, "fit_scan2map": fit_ms,
                                                    "lm_solve_kernel": solve_ms},
                                                   {ASSOC_KERNEL_PREFIX: alg_bytes_assoc, "fit_scan2map": F_total * (5 * 16 + 20 + 40),
                                                    "lm_solve_kernel": F_total * 48})
-                                     if (B == 1024 and args.map_points == 200000) else None),
+                                     if (B == 1024 and args.map_points == 200000 and timing_all is not None) else None),
                          "step": {"algorithmic_bytes_per_step": alg_bytes_step, "achieved": alg_bytes_step / step_s / 1e9,
                                   "unit": "GB/s", "frac": alg_bytes_step / step_s / 1e9 / HBM_PEAK_GBS}},
             "kernels_ms": {"assoc": assoc_ms,
                            "assoc_pass1": (timing.ms_assoc - timing.ms_assoc_seeded) / max(timing.launches_assoc - timing.launches_assoc_seeded, 1),
-                           "assoc_pass2": timing.ms_assoc_seeded / max(timing.launches_assoc_seeded, 1) if timing.launches_assoc_seeded else None, "fit": timing_all.ms_fit / max(timing_all.launches_fit, 1), "solve": solve_ms,
+                           "assoc_pass2": timing.ms_assoc_seeded / max(timing.launches_assoc_seeded, 1) if timing.launches_assoc_seeded else None, "fit": fit_ms, "solve": solve_ms,
                            "index_build": index_ms,
-                           "note": "assoc: HIP events inside the timed region; fit / solve / index_build: 3 extra steps after it; per launch, index_build per step (both maps)",
-                           "launches": {"assoc": timing.launches_assoc, "solve": timing_all.launches_solve,
-                                        "index": timing_all.launches_index}},
-            "knn": {"candidates_per_launch": knn_candidates // 2, "candidates_per_query": knn_candidates / 2 / max(F_total, 1),
+                           "note": "assoc: HIP events inside the timed region; fit / solve / index_build: 3 extra steps after it (--full); per launch, index_build per step (both maps)",
+                           "launches": {"assoc": timing.launches_assoc, "solve": None if timing_all is None else timing_all.launches_solve,
+                                        "index": None if timing_all is None else timing_all.launches_index}},
+            "knn": None if knn_candidates is None else {
+                    "candidates_per_launch": knn_candidates // 2, "candidates_per_query": knn_candidates / 2 / max(F_total, 1),
                     "candidates_per_query_pass1": knn_first / max(F_total, 1), "candidates_per_query_pass2": knn_seeded / max(F_total, 1),
                     "pass2_seeded": os.environ.get("MSFL_KNN_SEED", "0") == "1",
                     "distance_evals_per_s": (knn_candidates / 2) / (assoc_ms * 1e-3) if assoc_ms > 0 else 0.0,
                     "note": "map points whose f32 distance one launch evaluates (counting instantiation, one extra step); "
                             "rate = count / the timed launches' average duration"},
+            "full": args.full,
             "prep_s": t_prep,
             "n_failed": int((status_gpu != 0).sum()),
         }
@@ -539,14 +584,14 @@ def main():
         except OSError:
             out["roofline"]["lm_instantiations"] = None
         out["value_incl_h2d"] = None               # N=1 only: the host-buffer call is a separate, untimed-for-`value` leg
-        if world_size == 1 and not args.no_h2d:
+        if args.full and world_size == 1 and not args.no_h2d:
             v, ms, nbytes, ms_calls, v_mean = host_buffer_rate(h, inp, B)
             out["value_incl_h2d"] = {"value": v, "value_is": "median call", "value_mean_of_calls": v_mean, "unit": "registrations/s", "ms_per_batch": ms,
                                      "ms_per_call": ms_calls, "host_bytes_in": nbytes,
                                      "note": "`value` = the MEDIAN of the listed calls (rounds 1-3 reported the mean: `value_mean_of_calls`); same batch with features, guesses and results in pinned host memory (PCIe "
                                              "staging inside the call), map resident and indexed; never `value`"}
         out["cpu_baseline"] = None                 # timed on rank 0 at N=1 only (the other ranks would idle behind it)
-        if args.cpu_sample > 0 and world_size == 1:
+        if args.full and args.cpu_sample > 0 and world_size == 1:
             cores = os.cpu_count() or 1
             cb = cpu_baseline(inp, args.cpu_sample, cores)
             dts, drs = zip(*[synth.pose_error(poses_gpu[i], cb["poses"][i]) for i in range(cb["n"])])
@@ -576,7 +621,7 @@ def main():
         # the other stages of the hot path (the raw-scan pipeline, configs[2]'s per-scan step): measured on
         # this batch's own raw scans AFTER everything that feeds `value`, each spot-checked against the oracle (checker use only)
         out["stages"] = None
-        if world_size == 1 and not args.no_stages and not strong and inp.get("raw"):
+        if args.full and world_size == 1 and not args.no_stages and not strong and inp.get("raw"):
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_stages
             checker = None

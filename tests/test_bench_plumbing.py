@@ -25,6 +25,30 @@ def test_pmc_traffic_fails_loudly_on_a_missing_kernel():
         bench.pmc_traffic("no_such_kernel")
 
 
+def test_dump_outputs_writes_floats_and_samples_rows_above_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: f64 (f32 kept) .npy per output; above the size limit the same seeded rows of every array, and their numbers."""
+    import bench
+    import numpy as np
+    poses = np.arange(1000 * 7, dtype=np.float64).reshape(1000, 7)
+    status = (np.arange(1000) % 3).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "all"), {"poses": poses, "status": status})
+    assert sorted(os.listdir(tmp_path / "all")) == ["poses.npy", "status.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "poses.npy"), poses)
+    s = np.load(tmp_path / "all" / "status.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, status)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"poses": poses, "status": status})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["poses.npy", "sample_rows.npy", "status.npy"]
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in files) <= 20000
+    rows = np.load(tmp_path / "a" / "sample_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 1000 and np.array_equal(np.load(tmp_path / "a" / "poses.npy"), poses[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "status.npy"), status[rows])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
 def test_plain_gpus_2_launches_two_ranks():
     """No GPU here: every rank must get as far as bench.py's own "needs a GPU" exit, i.e. the plain
     `python bench.py --gpus 2` form launched ranks instead of refusing to run."""

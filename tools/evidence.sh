@@ -7,8 +7,8 @@ O=$R/gpurun_out/${TAG}; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -q -m gpu -x 2>&1 | tail -4 > $O/gpu_tests.txt
 [ -n "${FUZZ:-}" ] && (MSFL_FUZZ_SEEDS=$FUZZ timeout 1500 python -m pytest tests/test_gpu_extract.py tests/test_gpu_scan2map.py tests/test_gpu_scan2scan.py tests/test_grid_store.py tests/test_deskew.py -q -m gpu 2>&1 | tail -4 > $O/fuzz.txt)
-timeout 600 python bench.py --steps 200 --warmup 10 > $O/bench.json 2> $O/bench.err
-timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver_shape.json 2>> $O/bench.err
+timeout 600 python bench.py --full --steps 200 --warmup 10 > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_shape.json 2>> $O/bench.err
 # (before the PMC passes: counter collection leaves the device in its profiling clock state, which cost the pipelined replays 20-25 %)
 # round 5b: the step with the 64-beam sensor and in the other worlds: per-stream timelines + 60-scan replays of this build
 for c in "room 40 64" "outdoor 40 64" "corridor 80 16" "outdoor 80 16"; do

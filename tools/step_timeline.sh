@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -o t -- python $ROOT/bench.py --steps 12 --warmup 3 --no-h2d --no-stages --no-worlds --cpu-sample 0 --steady-steps 0 --no-kernel-timing > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -o t -- python $ROOT/bench.py --full --steps 12 --warmup 3 --no-h2d --no-stages --no-worlds --cpu-sample 0 --steady-steps 0 --no-kernel-timing > $OUT/log.txt 2>&1
 K=$(find $OUT -name "*kernel_trace.csv" | head -1); M=$(find $OUT -name "*memory_copy_trace.csv" | head -1)
 python - "$K" "$M" > $OUT/step_timeline.md <<'PY'
 import csv, sys
