@@ -145,9 +145,6 @@ struct msfl_handle_s {
   bool voxel_force_global = false;        // MSFL_VOXEL_GLOBAL=1: the batched voxel filter keeps the device-wide radix-sort form (A/B testing)
   long long odom_wave_max_targets = -1;   // MSFL_ODOM_WAVE_MAX_TARGETS: previous-scan points up to which a small batch takes the one-wavefront-per-query kernel (default 4096 per pair)
   bool odom_force_brute = false;          // MSFL_ODOM_BRUTE=1: stage B plane queries stay on the brute-force kernel (A/B testing)
-  bool nn_by_feature = false;             // numbering of `nn` left by the last association pass (s_launch_assoc)
-  bool knn_seed = false;                  // MSFL_KNN_SEED=1: the second outer iteration's 5-NN search starts from the bound the first one's neighbours give
-                                          // (exact; measured slower, docs/rejected_experiments.md: -16 % candidates, +13 % launch time)
   int knn_form = 0;                       // MSFL_KNN_FORM: 0 auto (row-parallel latency form for launches of <= kKnnRowsMaxRecords queries),
                                           // 1 "lane" (one lane per query always), 2 "rows" (row-parallel always); results are identical
 
@@ -162,8 +159,6 @@ struct msfl_handle_s {
   DevBuf ex[16];
   DevBuf od[20];
   DevBuf vb[14];  // batched voxel filter
-  DevBuf fit_fallback;                    // two {count, record numbers} lists of the whole-batch fit kernel's deferred pivoted-QR planes
-  size_t fit_fallback_words = 0; int fit_fallback_parity = 0;
   DevBuf vox_big_scratch, vox_big_list;   // the one-workgroup form for lists of 65 536 .. 131 071 points (round 5): per-workgroup run scratch, list of refused clouds
   DevBuf vb2[6];  // second scratch set of the pair form: staging, run sums, counts/flags/offsets, offsets
   DevBuf pp[5];   // per-point passes: pre-integration samples, staged points, dq, dp, flag
@@ -406,28 +401,23 @@ msfl_status build_index_pair(msfl_handle* h, const float4* pts_c, int n_c, const
   return MSFL_OK;
 }
 
-// the two fallback lists of the whole-batch fit kernel (msfl_kernels.cuh: fit_fallback_kernel), n_surf + 1 ints each, zeroed when (re)allocated
-msfl_status ensure_fit_fallback(msfl_handle* h, int n_surf) {
-  const size_t words = (size_t)std::max(n_surf, 0) + 1;
-  if (h->fit_fallback_words >= words) return MSFL_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));            // a launch in flight may still read the old lists
-  HIPCHK(h, h->fit_fallback.reserve(2 * words * sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->fit_fallback.p, 0, 2 * words * sizeof(int), h->stream));
-  h->fit_fallback_words = words; h->fit_fallback_parity = 0;
-  return MSFL_OK;
+// A 5-NN launch: batch, poses and status, then the eight map arguments (descriptor, sorted points and cell table of the corner
+// map, the same of the surf map, the two position tables) and the acceptance gate that every form takes, then the form's own.
+template <class Kernel, class... Tail>
+void launch_knn5(msfl_handle* h, Kernel kernel, dim3 grid, dim3 block, const BatchView& bv, const double* d_poses, const int* d_status,
+                 Tail... tail) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, h->stream, bv, d_poses, d_status,
+                     (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
+                     (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
+                     (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(), h->prm.map_knn_max_sq_dist, tail...);
 }
 
 // one data-association pass = kNN kernel + fit kernel
 // (records [rec_begin, rec_end) of the batch; rec_end < 0: all of them)
-// seed: `nn` still holds this batch's neighbours from the previous outer iteration (same records, same map index): the 5-NN search
-// starts from the bound they give (knn5_seed_bound; exact, MSFL_KNN_SEED=0 switches it off for A/B)
 void s_launch_assoc(msfl_handle* h, const BatchView& bv_all, const double* d_poses, const int* d_status, bool deskew,
                     const DeskewView& dv, int n_rec, double* full = nullptr, int rec_begin = 0, int rec_end = -1, bool second_pass = false) {
-  // the whole-batch kernels number `nn` by feature slot, the per-record ones by record (msfl_kernels.cuh: feature_slot); a seeded second pass
-  // reads the first pass's lists, so it is only seeded when both passes use the same numbering (a host-buffer batch's first pass runs chunk by chunk)
-  const bool whole_batch = !deskew && !bv_all.dyn && rec_end < 0 && (rec_end >= 0 ? rec_end - rec_begin : n_rec) >= 65536 && !full && h->timing != 3;
-  const bool seed = second_pass && h->knn_seed && h->nn_by_feature == whole_batch;
-  h->nn_by_feature = whole_batch;
+  // the whole-batch kernels number `nn` by feature slot, the per-record ones by record (msfl_kernels.cuh: feature_slot)
+  const bool whole_batch = !deskew && !bv_all.dyn && rec_end < 0 && n_rec >= 65536 && !full && h->timing != 3;
   hipStream_t st = h->stream;
   int* nn = h->nn.as<int>();
   BatchView bv = bv_all;
@@ -435,66 +425,24 @@ void s_launch_assoc(msfl_handle* h, const BatchView& bv_all, const double* d_pos
   if (n_rec <= 0) return;
   const dim3 grid(div_up(n_rec, kAssocBlock)), block(kAssocBlock);
   {
-    ScopedTimer timer(h, second_pass ? T_ASSOC_SEEDED : T_ASSOC);      // second-pass launches are timed (and counted) on their own, seeded or not
+    ScopedTimer timer(h, second_pass ? T_ASSOC_SEEDED : T_ASSOC);      // second-pass launches are timed (and counted) on their own
     if (h->timing == 3) {
       unsigned long long* cnt = h->knn_count.as<unsigned long long>();
-      if (deskew)
-        hipLaunchKernelGGL((knn5_scan2map_kernel<true, true>), grid, block, 0, st, bv, d_poses, d_status,
-                           (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                           (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                           (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(),
-                           h->prm.map_knn_max_sq_dist, dv, nn, cnt);
-      else if (seed)
-        hipLaunchKernelGGL((knn5_scan2map_kernel<false, true, true>), grid, block, 0, st, bv, d_poses, d_status,
-                           (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                           (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                           (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(),
-                           h->prm.map_knn_max_sq_dist, dv, nn, cnt + 1);
-      else
-        hipLaunchKernelGGL((knn5_scan2map_kernel<false, true>), grid, block, 0, st, bv, d_poses, d_status,
-                           (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                           (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                           (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(),
-                           h->prm.map_knn_max_sq_dist, dv, nn, cnt + (second_pass ? 1 : 0));
+      if (deskew) launch_knn5(h, knn5_scan2map_kernel<true, true>, grid, block, bv, d_poses, d_status, dv, nn, cnt, nullptr, nullptr);
+      else launch_knn5(h, knn5_scan2map_kernel<false, true>, grid, block, bv, d_poses, d_status, dv, nn, cnt + (second_pass ? 1 : 0), nullptr, nullptr);
     } else if (whole_batch) {       // a whole large batch: one body per feature kind (-2 %)
       const int n_s = bv.n_surf_total, n_c = n_rec - n_s;
       const int edge_blocks = div_up(n_c, kAssocBlock), plane_blocks = div_up(n_s, kAssocBlock);
-      if (seed)
-        hipLaunchKernelGGL(knn5_scan2map_split_kernel<true>, dim3(edge_blocks + plane_blocks), block, 0, st, bv, d_poses, d_status,
-                           (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                           (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                           (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(), h->prm.map_knn_max_sq_dist, nn, edge_blocks);
-      else
-        hipLaunchKernelGGL(knn5_scan2map_split_kernel<false>, dim3(edge_blocks + plane_blocks), block, 0, st, bv, d_poses, d_status,
-                           (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                           (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                           (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(), h->prm.map_knn_max_sq_dist, nn, edge_blocks);
+      launch_knn5(h, knn5_scan2map_split_kernel, dim3(edge_blocks + plane_blocks), block, bv, d_poses, d_status, nn, edge_blocks);
     } else if (!deskew && (h->knn_form == 2 || (h->knn_form == 0 && (n_rec <= kKnnRowsMaxRecords ||
                                                                        // the SLAM step launches over the list CAPACITIES (device-side counts): a 64-beam scan's ~11-17 k
                                                                        // queries sit in a ~150 k-slot launch whose surplus workgroups leave at once
                                                                        (bv.dyn && n_rec <= 8 * kKnnRowsMaxRecords)))))
-      hipLaunchKernelGGL(knn5_scan2map_rows_kernel, dim3(div_up(n_rec, kKnnRowsBlock / kKnnRowLanes)), dim3(kKnnRowsBlock), 0, st, bv, d_poses, d_status,
-                         (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                         (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                         (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(), h->prm.map_knn_max_sq_dist, nn);
+      launch_knn5(h, knn5_scan2map_rows_kernel, dim3(div_up(n_rec, kKnnRowsBlock / kKnnRowLanes)), dim3(kKnnRowsBlock), bv, d_poses, d_status, nn);
     else if (deskew)
-      hipLaunchKernelGGL(knn5_scan2map_kernel<true>, grid, block, 0, st, bv, d_poses, d_status,
-                         (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                         (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                         (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(),
-                         h->prm.map_knn_max_sq_dist, dv, nn);
-    else if (seed)
-      hipLaunchKernelGGL((knn5_scan2map_kernel<false, false, true>), grid, block, 0, st, bv, d_poses, d_status,
-                         (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                         (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                         (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(),
-                         h->prm.map_knn_max_sq_dist, dv, nn);
+      launch_knn5(h, knn5_scan2map_kernel<true>, grid, block, bv, d_poses, d_status, dv, nn, nullptr, nullptr, nullptr);
     else
-      hipLaunchKernelGGL(knn5_scan2map_kernel<false>, grid, block, 0, st, bv, d_poses, d_status,
-                         (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                         (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                         (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(),
-                         h->prm.map_knn_max_sq_dist, dv, nn);
+      launch_knn5(h, knn5_scan2map_kernel<false>, grid, block, bv, d_poses, d_status, dv, nn, nullptr, nullptr, nullptr);
   }
   {
     ScopedTimer timer(h, T_FIT);
@@ -507,19 +455,9 @@ void s_launch_assoc(msfl_handle* h, const BatchView& bv_all, const double* d_pos
         // a whole large batch: corner and surf features through their own specialisations of the fit (msfl_kernels.cuh)
         const int n_c = n_rec - bv.n_surf_total, n_s = bv.n_surf_total;
         const int edge_blocks = div_up(n_c, kAssocBlock), plane_blocks = div_up(n_s, kAssocBlock);
-        // fallback lists (count + record numbers) of the deferred pivoted-QR fits: two, used alternately, each re-armed by the OTHER launch's
-        // fallback kernel (zeroed at allocation)
-        // (sized by ensure_fit_fallback in the callers, which can report an allocation failure)
-        int* fb = h->fit_fallback.as<int>() + (size_t)h->fit_fallback_parity * h->fit_fallback_words;
-        int* fb_next = h->fit_fallback.as<int>() + (size_t)(1 - h->fit_fallback_parity) * h->fit_fallback_words; (void)fb_next;
-        h->fit_fallback_parity ^= 1;
         hipLaunchKernelGGL(fit_scan2map_split_kernel, dim3(edge_blocks + plane_blocks), block, 0, st, bv, h->map_c.sorted.as<float4>(),
                            h->map_s.sorted.as<float4>(), (const int*)nn, h->prm.line_eigen_ratio, h->prm.plane_tolerance, dv,
-                           h->records.as<double>(), full, edge_blocks, fb);
-#if MSFL_FIT_DEFER
-        hipLaunchKernelGGL(fit_fallback_kernel, dim3(64), dim3(64), 0, st, bv, h->map_s.sorted.as<float4>(), (const int*)nn, h->prm.plane_tolerance,
-                           h->records.as<double>(), full, (const int*)fb, fb_next);
-#endif
+                           h->records.as<double>(), full, edge_blocks);
       } else
       hipLaunchKernelGGL(fit_scan2map_kernel<false>, grid, block, 0, st, bv, h->map_c.sorted.as<float4>(),
                          h->map_s.sorted.as<float4>(), (const int*)nn, h->prm.line_eigen_ratio, h->prm.plane_tolerance, dv,
@@ -562,7 +500,6 @@ msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner,
     dv.pprime = h->pprime.as<double>();
   }
   const SolverParams sp = solver_params(h->prm, 0);
-  { const msfl_status fs = ensure_fit_fallback(h, bv.n_surf_total); if (fs) return fs; }
   for (int it = 0; it < h->prm.outer_iterations; it++) {
     if (it == 0 && (n_chunks > 1 || enqueue_chunk)) {
       for (int c = 0; c < n_chunks; c++) {
@@ -668,7 +605,6 @@ msfl_status msfl_create(const msfl_params* params, int device, msfl_handle** out
   if (const char* e = std::getenv("MSFL_H2D_SUB_CHUNKS")) { const int c = std::atoi(e); if (c >= 1) h->h2d_sub_chunks = c; }
   if (const char* e = std::getenv("MSFL_ODOM_BRUTE")) h->odom_force_brute = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_INDEX_SINGLE")) h->index_single = std::atoi(e) != 0;
-  if (const char* e = std::getenv("MSFL_KNN_SEED")) h->knn_seed = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_KNN_FORM")) h->knn_form = !std::strcmp(e, "lane") ? 1 : !std::strcmp(e, "rows") ? 2 : 0;
   if (const char* e = std::getenv("MSFL_ODOM_WAVE_MAX_TARGETS")) h->odom_wave_max_targets = std::atoll(e);
   if (const char* e = std::getenv("MSFL_VOXEL_GLOBAL")) h->voxel_force_global = std::atoi(e) != 0;
@@ -715,7 +651,7 @@ void msfl_destroy(msfl_handle* h) {
   for (auto& b : h->pr) b.release();
   for (auto& b : h->vb) b.release();
   for (auto& b : h->vb2) b.release();
-  h->vox_big_scratch.release(); h->vox_big_list.release(); h->fit_fallback.release();
+  h->vox_big_scratch.release(); h->vox_big_list.release();
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
 }
@@ -760,7 +696,7 @@ msfl_status msfl_set_timing(msfl_handle* h, int enabled) {
   msfl_status s = enter(h); if (s) return s;
   h->timing = enabled < 0 ? 0 : (enabled > 3 ? 1 : enabled);
   if (h->timing == 3 && !h->knn_count.p) {
-    HIPCHK(h, h->knn_count.reserve(2 * sizeof(unsigned long long)));     // [first-pass launches, seeded launches]
+    HIPCHK(h, h->knn_count.reserve(2 * sizeof(unsigned long long)));     // [first-pass launches, second-pass launches]
     HIPCHK(h, hipMemsetAsync(h->knn_count.p, 0, 2 * sizeof(unsigned long long), h->stream));
   }
   return MSFL_OK;
@@ -1012,7 +948,6 @@ msfl_status msfl_associate_scan2map(msfl_handle* h, const msfl_point* corner, in
   s = stage_single(h, corner, n_corner, surf, n_surf, pose, bv); if (s) return s;
   DeskewView dv{};
   HIPCHK(h, h->pprime.reserve((size_t)n * 6 * sizeof(double)));   // {C,N} staging for the host-format output
-  s = ensure_fit_fallback(h, bv.n_surf_total); if (s) return s;
   s_launch_assoc(h, bv, h->poses.as<double>(), h->status.as<int>(), false, dv, n, h->pprime.as<double>());
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(records_out, h->pprime.p, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -157,11 +157,8 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
     if (n_rec > 0) {
       {
         ScopedTimer timer(h, it > 0 ? T_ASSOC_SEEDED : T_ASSOC);
-        hipLaunchKernelGGL((knn5_scan2map_kernel<false, false, false, true>), grid, block, 0, st, bv, (const double*)d_poses, (const int*)d_status,
-                           (const GridDesc*)h->map_c.gdesc.as<GridDesc>(), h->map_c.sorted.as<float4>(), h->map_c.cell_start.as<int>(),
-                           (const GridDesc*)h->map_s.gdesc.as<GridDesc>(), h->map_s.sorted.as<float4>(), h->map_s.cell_start.as<int>(),
-                           (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(), h->prm.map_knn_max_sq_dist, dv, h->nn.as<int>(),
-                           (unsigned long long*)nullptr, (const int*)h->pr[PR_BASE_C].as<int>(), (const int*)h->pr[PR_BASE_S].as<int>());
+        launch_knn5(h, knn5_scan2map_kernel<false, false, true>, grid, block, bv, d_poses, d_status, dv, h->nn.as<int>(),
+                    nullptr, h->pr[PR_BASE_C].as<int>(), h->pr[PR_BASE_S].as<int>());
       }
       {
         ScopedTimer timer(h, T_FIT);       // nn holds positions in the concatenated sorted maps: the fit gathers as ever

@@ -299,11 +299,7 @@ __device__ __forceinline__ void top5_init(Top5& t, float bound) {
   t.k0 = t.k1 = t.k2 = t.k3 = t.k4 = ((unsigned long long)__float_as_uint(bound) << 32) | 0xffffffffull;
 }
 __device__ __forceinline__ float top5_d4(const Top5& t) { return __uint_as_float((unsigned int)(t.k4 >> 32)); }  // the gate while < 5 found
-__device__ __forceinline__ float top_d4(const Top5& t) { return top5_d4(t); }
 
-#ifndef MSFL_TOP5_SELECT
-#define MSFL_TOP5_SELECT 0          /* 1: the compare / select insertion network of rounds 1-3 (A/B) */
-#endif
 // The inline assembly below (v_min_f64 / v_max_f64 / v_med3_u32 by their gfx950 mnemonics) is written for the one target this library
 // has: a device pass for anything else stops here with a message instead of an assembler error deep in a template.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -326,14 +322,6 @@ __device__ __forceinline__ void top5_insert(Top5& t, float d, int idx) {
   if (__float_as_uint(d) > (unsigned int)(t.k4 >> 32)) return;
   const unsigned long long x = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned int)idx;
   if (!(x < t.k4)) return;
-#if MSFL_TOP5_SELECT
-  const bool c3 = x < t.k3, c2 = x < t.k2, c1 = x < t.k1, c0 = x < t.k0;
-  t.k4 = c3 ? t.k3 : x;
-  t.k3 = c3 ? (c2 ? t.k2 : x) : t.k3;
-  t.k2 = c2 ? (c1 ? t.k1 : x) : t.k2;
-  t.k1 = c1 ? (c0 ? t.k0 : x) : t.k1;
-  t.k0 = c0 ? x : t.k0;
-#else
   // Sorted insertion as a min / max chain on the keys READ AS DOUBLES.  A key's high word is the bit pattern of a non-negative f32
   // (< 2^31), so as an f64 it is a non-negative finite number or denormal (exponent field = the top 11 bits of the f32 pattern:
   // <= 0x7fc even for an f32 NaN), and for non-negative doubles the IEEE order IS the unsigned order of the bit patterns; f64
@@ -345,7 +333,6 @@ __device__ __forceinline__ void top5_insert(Top5& t, float d, int idx) {
   const unsigned long long c2 = u64_max_f(t.k2, c1); t.k2 = u64_min_f(t.k2, c1);
   const unsigned long long c3 = u64_max_f(t.k3, c2); t.k3 = u64_min_f(t.k3, c2);
   t.k4 = c3;                    // = min(k4, c3): x < k4 (the guard above) and k3 <= k4, so the largest of {k0..k3, x} is below k4
-#endif
 }
 
 // Round 4, the walk's own top list: SIX 32-bit keys (distance bits & ~7) | slot, sorted, and the candidates' positions in the
@@ -362,9 +349,6 @@ __device__ __forceinline__ void top5_insert(Top5& t, float d, int idx) {
 // is searched again with the exact 64-bit keys (Top5): two distances within 2^-21 relative of each other, ~1e-6 of the queries
 // on a scanned surface, every query on an exact lattice.  The 6th key's stored position may be stale (a candidate that tied
 // with it overwrote the slot without entering); the 6th is never output and can only leave the list.
-#ifndef MSFL_KNN_KEY32
-#define MSFL_KNN_KEY32 1            /* 0: the 64-bit (distance, index) keys of rounds 1-4a in every kernel (A/B) */
-#endif
 constexpr unsigned int kTopSentinel = 0xffffff00u;      // sentinels 0xffffff00 + 9 i: six different t, slots 0..5, above every f32 distance pattern
 // k = med3(below, k, x) IN PLACE (below <= k): the sorted list's element after x has been inserted somewhere
 __device__ __forceinline__ void u32_med3_into(unsigned int& k, unsigned int below, unsigned int x) {
@@ -373,7 +357,7 @@ __device__ __forceinline__ void u32_med3_into(unsigned int& k, unsigned int belo
 struct Top6K {
   unsigned int k0, k1, k2, k3, k4, k5;
   unsigned int bound;               // min(k4 | 7, gate bits): the pre-filter, a conservative 5th distance for the row / cell bounds
-  unsigned int gate;                // acceptance gate bits (or the seeded initial bound)
+  unsigned int gate;                // acceptance gate bits
   int* col;                         // this lane's column of the slot table: col[slot * kTopSlotStride]
 };
 constexpr int kTopSlots = 6;
@@ -390,9 +374,6 @@ __device__ __forceinline__ bool top_settled(const Top6K& t, float accept_gate) {
 __device__ __forceinline__ bool top_found(const Top6K& t) { return t.k4 < kTopSentinel; }     // five real candidates within the gate
 template <int STRIDE>
 __device__ __forceinline__ int top_pos(const Top6K& t, unsigned int k) { return (int)((unsigned int)t.col[(k & 7u) * STRIDE] >> 4); }   // stored: byte offset
-
-template <int STRIDE>
-__device__ __forceinline__ void top_insert(Top5& t, float d, int idx, int) { top5_insert(t, d, idx); }
 
 // flann::L2_Simple<float>: ((dx*dx) + dy*dy) + dz*dz, every operation rounded to f32
 __device__ __forceinline__ float l2_simple(float4 a, float3 q) {
@@ -425,13 +406,10 @@ __device__ __forceinline__ float axis_gap(float u, int c) {
   return fmaxf(g - 1e-3f, 0.0f);
 }
 
-// max_sq_dist here is the INITIAL bound of the search: the acceptance gate, or (second outer iteration) something tighter
-// that five real map points are known to meet (knn5_seed_bound).
-// TOP: Top5 (exact 64-bit keys) or Top6K (32-bit keys + slot table with lane stride STRIDE ints, exact unless !top_settled); the caller
-// initialises it with the search's initial bound.
-template <class TOP, int STRIDE = 64>
+// The exact walk on 64-bit keys (Top5, initialised by the caller with the acceptance gate): the search again of a query that the
+// truncated-key walk below (knn5_grid_k32) leaves ambiguous.
 __device__ __forceinline__ void knn5_grid(const GridDesc& g, const float4* __restrict__ sorted,
-                                          const int* __restrict__ cell_start, float3 q, TOP& t,
+                                          const int* __restrict__ cell_start, float3 q, Top5& t,
                                           int& n_cand) {      // n_cand: candidates evaluated (dead code unless the caller reads it)
   const float ux = (q.x - g.ox) * g.inv_cell_x, uy = (q.y - g.oy) * g.inv_cell, uz = (q.z - g.oz) * g.inv_cell;
   const int cx = grid_coord(q.x, g.ox, g.inv_cell_x, g.dx);
@@ -471,17 +449,16 @@ __device__ __forceinline__ void knn5_grid(const GridDesc& g, const float4* __res
     n_cand += e - s;
     const float4* p = sorted + s;
     const float4* const pe = sorted + e;
-    int pos = s;                            // position in the sorted map (Top6K's payload; dead code for Top5)
-    for (; p + 1 < pe; p += 2, pos += 2) {  // two loads in flight, one address register
+    for (; p + 1 < pe; p += 2) {            // two loads in flight, one address register
       float4 m0 = p[0], m1 = p[1];
       // keep the index word in the 16-byte load: left alone, the compiler splits it off into a second,
       // dependent load inside the (latency-critical) insertion path
       asm volatile("" : "+v"(m0.w));
-      top_insert<STRIDE>(t, l2_simple_pk(m0, qxy, q.z), __float_as_int(m0.w), pos);
+      top5_insert(t, l2_simple_pk(m0, qxy, q.z), __float_as_int(m0.w));
       asm volatile("" : "+v"(m1.w));
-      top_insert<STRIDE>(t, l2_simple_pk(m1, qxy, q.z), __float_as_int(m1.w), pos + 1);
+      top5_insert(t, l2_simple_pk(m1, qxy, q.z), __float_as_int(m1.w));
     }
-    if (p < pe) { float4 m = p[0]; asm volatile("" : "+v"(m.w)); top_insert<STRIDE>(t, l2_simple_pk(m, qxy, q.z), __float_as_int(m.w), pos); }
+    if (p < pe) { float4 m = p[0]; asm volatile("" : "+v"(m.w)); top5_insert(t, l2_simple_pk(m, qxy, q.z), __float_as_int(m.w)); }
   };
 #pragma unroll
   for (int r = 0; r < 9; r++) {
@@ -502,7 +479,7 @@ __device__ __forceinline__ void knn5_grid(const GridDesc& g, const float4* __res
     if (y < 0 || y >= g.dy || z < 0 || z >= g.dz) continue;
     const float row2 = (gy * gy + gz * gz) * cell2;
     const int row = (z * g.dy + y) * g.dx;
-    const float d4 = top_d4(t);
+    const float d4 = top5_d4(t);
     if (row2 > d4) continue;                  // d4 is the acceptance gate until five neighbours are known
     // trim the x range: drop end cells whose lower bound exceeds the 5th-best distance
     // a cell is dropped when its lower bound exceeds d4; the bounds shrink towards the query, so count the
@@ -623,27 +600,6 @@ __device__ __forceinline__ void knn5_grid_k32(const GridDesc& g, const float4* _
   visit(v_fy && v_fz, base0 - off_y - off_z, q_fy + q_fz);
 }
 
-// Second outer iteration (mapping_scan_matcher.cc:75: the association loop runs kOptimalNum = 2 times on the same clouds): the five
-// neighbours the first pass found for this feature (positions in the sorted map, still in `nn`) are five DISTINCT real map
-// points, so the largest of their f32 distances to the re-transformed query is an upper bound of the new 5th-nearest
-// distance.  Starting the top-5 from (min(gate, that distance), 0xffffffff) sentinels trims rows and x-cells from the first
-// row on and the result is still the exact top-5 by (distance, index): a candidate AT the bound compares below the sentinel's
-// index word, and at least five real candidates are within the bound.  A feature the first pass rejected keeps the gate.
-__device__ __forceinline__ float knn5_seed_bound(const float4* __restrict__ sorted, const int* __restrict__ prev, float3 q, float gate) {
-  const int p0 = prev[0];
-  if (p0 < 0) return gate;
-  const int p1 = prev[1], p2 = prev[2], p3 = prev[3], p4 = prev[4];
-  const float4 m0 = sorted[p0], m1 = sorted[p1], m2 = sorted[p2], m3 = sorted[p3], m4 = sorted[p4];
-  const msfl_f2 qxy = {q.x, q.y};
-  float m = l2_simple_pk(m0, qxy, q.z);
-  float d;
-  d = l2_simple_pk(m1, qxy, q.z); m = d > m ? d : m;
-  d = l2_simple_pk(m2, qxy, q.z); m = d > m ? d : m;
-  d = l2_simple_pk(m3, qxy, q.z); m = d > m ? d : m;
-  d = l2_simple_pk(m4, qxy, q.z); m = d > m ? d : m;
-  return m < gate ? m : gate;         // a NaN distance (non-finite query) leaves the gate in place
-}
-
 struct FitOut { d3 C, N; bool ok; };
 
 // mapping_scan_matcher.cc:130-151
@@ -673,14 +629,7 @@ __device__ __forceinline__ FitOut edge_fit(const float4 (&nb)[5], double ratio) 
 }
 
 // mapping_scan_matcher.cc:199-222
-#ifndef MSFL_PLANE_ADJ
-#define MSFL_PLANE_ADJ 1            /* 0: the unpivoted-QR fast path of round 3 instead of the centred adjugate form (A/B) */
-#endif
-// DEFER (round 5, the whole-batch fit kernel): an ill-conditioned neighbourhood does not run the pivoted QR here but is reported through
-// `deferred` and fitted by fit_fallback_kernel; with the fallback out of this binary the hot path needs fewer registers (more
-// wavefronts per SIMD).  The result is the same function of the five points either way.
-template <bool DEFER = false>
-__device__ __forceinline__ FitOut plane_fit(const float4 (&nb)[5], double tol, bool* deferred = nullptr) {
+__device__ __forceinline__ FitOut plane_fit(const float4 (&nb)[5], double tol) {
   FitOut o; o.ok = false; o.C = mk3(0, 0, 0); o.N = mk3(0, 0, 0);
   d3 c = mk3(0, 0, 0);
 #pragma unroll
@@ -688,23 +637,13 @@ __device__ __forceinline__ FitOut plane_fit(const float4 (&nb)[5], double tol, b
   c = mk3(c.x / 5.0, c.y / 5.0, c.z / 5.0);
   bool well = false;
   d3 x = mk3(0, 0, 0);
-#if MSFL_PLANE_ADJ
   if (!MSFL_IEEE_DIV) {                            // direction of the least-squares solution only: all the fit uses
     double q[5][3];                                // centred points (not kept across the fallback: the distance test re-forms them)
 #pragma unroll
     for (int j = 0; j < 5; j++) { q[j][0] = (double)nb[j].x - c.x; q[j][1] = (double)nb[j].y - c.y; q[j][2] = (double)nb[j].z - c.z; }
     x = plane_normal_centred(q, c, well);
   }
-#else
-  {
-    double A[5][3], b[5];
-#pragma unroll
-    for (int j = 0; j < 5; j++) { A[j][0] = (double)nb[j].x; A[j][1] = (double)nb[j].y; A[j][2] = (double)nb[j].z; b[j] = -1.0; }
-    if (!MSFL_IEEE_DIV) x = lstsq5x3_fast(A, b, well);             // overwrites A, b
-  }
-#endif
-  if (DEFER && !well) { *deferred = true; return o; }
-  if (!DEFER && !well) {                           // ill-conditioned or rank-deficient: the reference's pivoted QR decides
+  if (!well) {                           // ill-conditioned or rank-deficient: the reference's pivoted QR decides
     double A[5][3], b[5];
 #pragma unroll
     for (int j = 0; j < 5; j++) { A[j][0] = (double)nb[j].x; A[j][1] = (double)nb[j].y; A[j][2] = (double)nb[j].z; b[j] = -1.0; }
@@ -792,7 +731,7 @@ struct DeskewView {
 #endif
 constexpr int kAssocBlock = MSFL_ASSOC_BLOCK;      // threads per workgroup of the 5-NN and fit kernels
 // PAIRS: scan b is registered against ITS OWN map (msfl_pairs.cuh): descriptor gcp[b] / gsp[b], cell table slice at cbase_*[b]
-template <bool DESKEW, bool COUNT = false, bool SEED = false, bool PAIRS = false>
+template <bool DESKEW, bool COUNT = false, bool PAIRS = false>
 __global__ void __launch_bounds__(kAssocBlock)
 knn5_scan2map_kernel(BatchView bv, const double* __restrict__ poses, const int* __restrict__ status,
                      const GridDesc* __restrict__ gcp, const float4* __restrict__ map_c, const int* __restrict__ cs_c,
@@ -835,27 +774,19 @@ knn5_scan2map_kernel(BatchView bv, const double* __restrict__ poses, const int* 
   }
   Top5 t;
   int n_cand = 0;
-  const float bound = SEED ? knn5_seed_bound(is_edge ? map_c : map_s, out, q, max_sq_dist) : max_sq_dist;
-#if MSFL_KNN_KEY32
   // the walk on truncated 32-bit keys first (Top6K); a lane it leaves ambiguous is searched again with the exact keys below
   __shared__ int s_slot[kTopSlots * kAssocBlock];
   Top6K tk;
-  top_init(tk, bound, s_slot + threadIdx.x);
+  top_init(tk, max_sq_dist, s_slot + threadIdx.x);
   if (is_edge) { const GridDesc gc = gcp[PAIRS ? b : 0]; knn5_grid_k32<kAssocBlock>(gc, map_c, cs_c, q, tk, n_cand, PAIRS ? cbase_c[b] : 0); }
   else { const GridDesc gs = gsp[PAIRS ? b : 0]; knn5_grid_k32<kAssocBlock>(gs, map_s, cs_s, q, tk, n_cand, PAIRS ? cbase_s[b] : 0); }
   const bool settled = top_settled(tk, max_sq_dist);
   if (!settled) {
     int n_again = 0;                   // the candidate counter reports the first walk
-    top5_init(t, bound);
+    top5_init(t, max_sq_dist);
     if (is_edge) { const GridDesc gc = gcp[PAIRS ? b : 0]; knn5_grid(gc, map_c, cs_c + (PAIRS ? cbase_c[b] : 0), q, t, n_again); }
     else { const GridDesc gs = gsp[PAIRS ? b : 0]; knn5_grid(gs, map_s, cs_s + (PAIRS ? cbase_s[b] : 0), q, t, n_again); }
   }
-#else
-  const bool settled = false;
-  top5_init(t, bound);
-  if (is_edge) { const GridDesc gc = gcp[PAIRS ? b : 0]; knn5_grid(gc, map_c, cs_c + (PAIRS ? cbase_c[b] : 0), q, t, n_cand); }
-  else { const GridDesc gs = gsp[PAIRS ? b : 0]; knn5_grid(gs, map_s, cs_s + (PAIRS ? cbase_s[b] : 0), q, t, n_cand); }
-#endif
   if (COUNT) {                                                  // one atomic per wavefront: sum over the lanes still here
     const unsigned long long act = __ballot(1);
     unsigned long long m = act;
@@ -863,7 +794,6 @@ knn5_scan2map_kernel(BatchView bv, const double* __restrict__ poses, const int* 
     while (m) { const int l = __ffsll((long long)m) - 1; tot += __shfl(n_cand, l); m &= m - 1; }
     if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) atomicAdd(n_candidates, (unsigned long long)tot);
   }
-#if MSFL_KNN_KEY32
   if (settled) {
     if (top_found(tk)) {                                                              // :128 / :198: the 5th is below the gate
       out[0] = top_pos<kAssocBlock>(tk, tk.k0); out[1] = top_pos<kAssocBlock>(tk, tk.k1); out[2] = top_pos<kAssocBlock>(tk, tk.k2);
@@ -873,7 +803,6 @@ knn5_scan2map_kernel(BatchView bv, const double* __restrict__ poses, const int* 
     }
     return;
   }
-#endif
   if ((unsigned int)t.k4 != 0xffffffffu && (double)top5_d4(t) < (double)max_sq_dist) {      // :128 / :198
     // original map index -> position in the sorted map array (the fit kernel then gathers directly);
     // done here because this kernel runs at 8 waves/SIMD and hides the extra dependent load
@@ -893,7 +822,7 @@ __device__ __forceinline__ V uniform_load(const V* p) {
 
 // K4a for a whole large batch of the plain branch: blocks [0, edge_blocks) serve the corner features (corner map index), the rest
 // the surf features, so that a wavefront never holds both kinds and each body knows its map at compile time.
-template <bool EDGE, bool SEED>
+template <bool EDGE>
 __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double* __restrict__ poses, const int* __restrict__ status,
                                               const GridDesc* __restrict__ gp, const float4* __restrict__ map, const int* __restrict__ cs,
                                               const int* __restrict__ po, float max_sq_dist, int* __restrict__ nn, int block, int* s_slot) {
@@ -925,10 +854,8 @@ __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double*
   const float3 q = transform_point_f32(T, f.x, f.y, f.z);                          // :123 / :193
   int n_cand = 0;
   const GridDesc gd = *gp;
-  const float bound = SEED ? knn5_seed_bound(map, out, q, max_sq_dist) : max_sq_dist;
-#if MSFL_KNN_KEY32
   Top6K tk;
-  top_init(tk, bound, s_slot + threadIdx.x);
+  top_init(tk, max_sq_dist, s_slot + threadIdx.x);
   knn5_grid_k32<kAssocBlock>(gd, map, cs, q, tk, n_cand);
   if (top_settled(tk, max_sq_dist)) {
     if (top_found(tk)) {                                                              // :128 / :198: the 5th is below the gate (t differs from the gate's)
@@ -940,9 +867,8 @@ __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double*
     return;
   }
   // ambiguous under the truncated keys: the exact (distance, index) search
-#endif
   Top5 t;
-  top5_init(t, bound);
+  top5_init(t, max_sq_dist);
   knn5_grid(gd, map, cs, q, t, n_cand);
   if ((unsigned int)t.k4 != 0xffffffffu && (double)top5_d4(t) < (double)max_sq_dist) {      // :128 / :198
     out[0] = po[(unsigned int)t.k0]; out[1] = po[(unsigned int)t.k1]; out[2] = po[(unsigned int)t.k2];
@@ -951,15 +877,14 @@ __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double*
     out[0] = -1; out[1] = -1; out[2] = -1; out[3] = -1; out[4] = -1;
   }
 }
-template <bool SEED>
 __global__ void __launch_bounds__(kAssocBlock)
 knn5_scan2map_split_kernel(BatchView bv, const double* __restrict__ poses, const int* __restrict__ status,
                            const GridDesc* __restrict__ gcp, const float4* __restrict__ map_c, const int* __restrict__ cs_c,
                            const GridDesc* __restrict__ gsp, const float4* __restrict__ map_s, const int* __restrict__ cs_s,
                            const int* __restrict__ pos_c, const int* __restrict__ pos_s, float max_sq_dist, int* __restrict__ nn, int edge_blocks) {
-  __shared__ int s_slot[MSFL_KNN_KEY32 ? kTopSlots * kAssocBlock : 1];        // Top6K's slot table: 6 positions per lane
-  if ((int)blockIdx.x < edge_blocks) knn5_one_kind<true, SEED>(bv, poses, status, gcp, map_c, cs_c, pos_c, max_sq_dist, nn, (int)blockIdx.x, s_slot);
-  else knn5_one_kind<false, SEED>(bv, poses, status, gsp, map_s, cs_s, pos_s, max_sq_dist, nn, (int)blockIdx.x - edge_blocks, s_slot);
+  __shared__ int s_slot[kTopSlots * kAssocBlock];        // Top6K's slot table: 6 positions per lane
+  if ((int)blockIdx.x < edge_blocks) knn5_one_kind<true>(bv, poses, status, gcp, map_c, cs_c, pos_c, max_sq_dist, nn, (int)blockIdx.x, s_slot);
+  else knn5_one_kind<false>(bv, poses, status, gsp, map_s, cs_s, pos_s, max_sq_dist, nn, (int)blockIdx.x - edge_blocks, s_slot);
 }
 
 // K4a, latency form: the same exact 5-NN for a launch too small to fill the machine (one scan per call: ~5 000 queries are
@@ -1063,10 +988,10 @@ knn5_scan2map_rows_kernel(BatchView bv, const double* __restrict__ poses, const 
 #endif
 // KIND 0: every record of [rec_begin, n_records) (one thread each, edges and planes as they come); KIND 1 / 2: the launch covers
 // the batch's corner / surf features only (thread = feature index in its cloud), so that the compiler sees one of the two fits.
-template <bool DESKEW, int KIND, bool DEFER = false>
+template <bool DESKEW, int KIND>
 __device__ __forceinline__ void fit_one(const BatchView& bv, const float4* __restrict__ map_c, const float4* __restrict__ map_s,
                                         const int* __restrict__ nn, double line_ratio, double plane_tol, const DeskewView& dv,
-                                        double* __restrict__ rec, double* __restrict__ full, int block, int* __restrict__ fallback = nullptr) {
+                                        double* __restrict__ rec, double* __restrict__ full, int block) {
   int g = 0, b = 0, local = 0, nc = 0, fi = 0;
   size_t slot;
   if (KIND == 0) {
@@ -1093,12 +1018,7 @@ __device__ __forceinline__ void fit_one(const BatchView& bv, const float4* __res
   const bool have = p0 >= 0;                                  // no match: the other four slots were never written
   const float4 nb[5] = {mp[have ? p0 : 0], mp[have ? p1 : 0], mp[have ? p2 : 0], mp[have ? p3 : 0], mp[have ? p4 : 0]};
   if (p0 >= 0) {
-    bool deferred = false;
-    fo = is_edge ? edge_fit(nb, line_ratio) : plane_fit<DEFER>(nb, plane_tol, &deferred);
-    if (DEFER && deferred) {                                    // fallback[0]: count, then the surf features' indices; the record written
-      const int at = atomicAdd(fallback, 1);                    // below (rejected) is overwritten by fit_fallback_kernel
-      fallback[1 + at] = fi;
-    }
+    fo = is_edge ? edge_fit(nb, line_ratio) : plane_fit(nb, plane_tol);
     if (DESKEW && fo.ok) {
       // C' = C - (Vi dt - G dt^2/2): the velocity block is constant (mapping_scan_matcher.cc:94)
       static_assert(!DESKEW || KIND == 0, "the de-skew branch runs the per-record kernel");
@@ -1135,38 +1055,15 @@ fit_scan2map_kernel(BatchView bv, const float4* __restrict__ map_c, const float4
 // through its own specialisation of the body, at four wavefronts per SIMD (the plane fit alone needs 131 registers, the
 // mixed body 135: three wavefronts).  The edge blocks come first so that their longer per-record chain (the Jacobi
 // eigen-solver) runs under the plane blocks instead of forming the launch's tail.
-#ifndef MSFL_FIT_DEFER
-#define MSFL_FIT_DEFER 0            /* 1: the pivoted-QR fallback of the whole-batch fit kernel deferred to fit_fallback_kernel (round 5: the hot kernel
-                                       drops to 92 VGPRs / 5 waves per SIMD and 0.098 ms, but the extra launch costs what it saves: 0.1063 vs 0.1045 ms
-                                       per pass for both; docs/rejected_experiments.md).  `make defer` builds it; the test of the path runs on either. */
-#endif
 #ifndef MSFL_FIT_SPLIT_WAVES
-#define MSFL_FIT_SPLIT_WAVES (MSFL_FIT_DEFER ? 5 : 4)
+#define MSFL_FIT_SPLIT_WAVES 4
 #endif
 __global__ void __launch_bounds__(kAssocBlock, MSFL_FIT_SPLIT_WAVES)
 fit_scan2map_split_kernel(BatchView bv, const float4* __restrict__ map_c, const float4* __restrict__ map_s,
                           const int* __restrict__ nn, double line_ratio, double plane_tol, DeskewView dv,
-                          double* __restrict__ rec, double* __restrict__ full, int edge_blocks, int* __restrict__ fallback) {
+                          double* __restrict__ rec, double* __restrict__ full, int edge_blocks) {
   if ((int)blockIdx.x < edge_blocks) fit_one<false, 1>(bv, map_c, map_s, nn, line_ratio, plane_tol, dv, rec, full, (int)blockIdx.x);
-  else fit_one<false, 2, MSFL_FIT_DEFER != 0>(bv, map_c, map_s, nn, line_ratio, plane_tol, dv, rec, full, (int)blockIdx.x - edge_blocks, fallback);
-}
-// The planes whose neighbourhood failed the guards of plane_normal_centred (rank-deficient or ill-conditioned: a handful per million on
-// scanned surfaces): the reference's pivoted QR (plane_fit's non-deferred body), one thread each over a fixed small grid, the count
-// read on the device.  Re-arms the OTHER counter of the ping-pong pair for the next launch (this one is still being read).
-__global__ void __launch_bounds__(64)
-fit_fallback_kernel(BatchView bv, const float4* __restrict__ map_s, const int* __restrict__ nn, double plane_tol,
-                    double* __restrict__ rec, double* __restrict__ full, const int* __restrict__ fallback, int* __restrict__ next_counter) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *next_counter = 0;
-  const int n = fallback[0];
-  (void)full;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
-    const int fi = fallback[1 + e];                              // a surf feature's index in its cloud array
-    const int* in = nn + 5 * feature_slot(bv, false, fi);
-    const float4 nb[5] = {map_s[in[0]], map_s[in[1]], map_s[in[2]], map_s[in[3]], map_s[in[4]]};
-    const FitOut fo = plane_fit<false>(nb, plane_tol);
-    double* out = rec + plane_rec_off(bv, fi);
-    out[0] = fo.N.x; out[1] = fo.N.y; out[2] = fo.N.z; out[3] = dot(fo.N, fo.C);
-  }
+  else fit_one<false, 2>(bv, map_c, map_s, nn, line_ratio, plane_tol, dv, rec, full, (int)blockIdx.x - edge_blocks);
 }
 
 // {C, N} x n_records (host/debug format) -> compact internal records
@@ -1254,16 +1151,9 @@ constexpr int kLmBlock = MSFL_LM_BLOCK;                        // threads per sc
 #define MSFL_ODOM_LM_BLOCK 128
 #endif
 constexpr int kOdomLmBlock = MSFL_ODOM_LM_BLOCK;               // scan-to-scan: ~500 records per pair
-#ifndef MSFL_LM_EDGE_CACHE
-#define MSFL_LM_EDGE_CACHE 0
-#endif
-// Optional LDS cache for the edge records (build switch, default off): the edge loop has only 2-3
-// iterations per lane and takes 26 % of the evaluation time for 11 % of the records, but caching them
-// (at the planes' expense) measured 0.336 / 0.338 ms vs 0.331 ms without.
 // cache sizes per workgroup size: 76 KB x 2 workgroups per CU (256 threads), 36.6 KB x 4 (128: the small
 // scan-to-scan problems, measured 0.365 ms per call vs 0.448 with 256 threads and 0.382 with 64), 17 KB x 8 (64:
 // one wavefront per problem, no cross-wave barrier)
-constexpr int lm_edge_cache(int block) { return block == 256 ? MSFL_LM_EDGE_CACHE : 0; }      // 60 B each
 // 512 threads: the one-solve-per-call SLAM step, where the machine is empty and a solve is as long as its chain of passes
 // (3 072 planes x 44 B = 132 KB, one workgroup per CU)
 // trips of the streamed plane loop whose loads are requested together (see evaluate_pass): 512 threads have <= 10 trips in all
@@ -1278,16 +1168,14 @@ constexpr int lm_plane_cache(int block) {
 #ifdef MSFL_LM_PLANE_CACHE
   return block == 256 ? MSFL_LM_PLANE_CACHE : block == 128 ? 832 : block == 512 ? 3072 : 384;
 #else
-  return block == 256 ? ((1728 - (lm_edge_cache(256) * 60 + 43) / 44) & ~63) : block == 128 ? 832 : block == 512 ? 3072 : 384;
+  return block == 256 ? 1728 : block == 128 ? 832 : block == 512 ? 3072 : 384;
 #endif
 }
 template <int BLOCK>
 struct PlaneCache {
-  static constexpr int kPlanes = lm_plane_cache(BLOCK), kEdges = lm_edge_cache(BLOCK);
+  static constexpr int kPlanes = lm_plane_cache(BLOCK);
   double nx[kPlanes], ny[kPlanes], nz[kPlanes], d0[kPlanes];
   float px[kPlanes], py[kPlanes], pz[kPlanes];
-  double ecx[kEdges + 1], ecy[kEdges + 1], ecz[kEdges + 1], enx[kEdges + 1], eny[kEdges + 1], enz[kEdges + 1];
-  float epx[kEdges + 1], epy[kEdges + 1], epz[kEdges + 1];
 };
 
 // Accepted edge correspondences of a solve, in index order.  Only ~40 % of the corner features pass the line test,
@@ -1392,7 +1280,7 @@ __device__ __forceinline__ void evaluate_pass(const pose7& T, double huber,
         plane_row(mk3(pc.nx[i], pc.ny[i], pc.nz[i]), pc.d0[i], mk3((double)pc.px[i], (double)pc.py[i], (double)pc.pz[i]));
     }
   };
-  if (pprime == nullptr && PlaneCache<BLOCK>::kEdges == 0) {
+  if (pprime == nullptr) {
     // Round 6 (profiles/r06_lm_ablation.md: the edge rows were two to four DEPENDENT memory round trips per pass, 3.4 us of a 28 us pass and
     // 8 us of the first one): the loads of up to kEdgeGroup trips are requested together (clamped index, no branch around them), and in the
     // later passes the LDS-resident plane rows -- which wait for nothing -- are accumulated while those loads are in flight.  The rows of a
@@ -1424,31 +1312,16 @@ __device__ __forceinline__ void evaluate_pass(const pose7& T, double huber,
         edge_row(ei[u], mk3(e6[u][0], e6[u][1], e6[u][2]), mk3(e6[u][3], e6[u][4], e6[u][5]), mk3((double)ef[u].x, (double)ef[u].y, (double)ef[u].z));
       }
     }
-  } else {
+  } else {                                          // de-skew: the points are the records' f64 p' (no plane cache)
     for (int k = threadIdx.x; k < n_walk; k += BLOCK) {
       const bool listed = !FILL && k < n_listed;
       const int i = FILL ? k : (listed ? (int)el.idx[k] : kEdgeListMax + (k - n_listed));
-      d3 C, N, p;
-      if (!FILL && pprime == nullptr && i < PlaneCache<BLOCK>::kEdges) {
-        C = mk3(pc.ecx[i], pc.ecy[i], pc.ecz[i]); N = mk3(pc.enx[i], pc.eny[i], pc.enz[i]);
-        p = mk3((double)pc.epx[i], (double)pc.epy[i], (double)pc.epz[i]);
-      } else {
-        const double* r6 = rec + 6 * (size_t)i;
-        C = mk3(r6[0], r6[1], r6[2]);
-        N = mk3(r6[3], r6[4], r6[5]);
-        if (pprime) p = mk3(pprime[3 * (size_t)i], pprime[3 * (size_t)i + 1], pprime[3 * (size_t)i + 2]);
-        else {
-          const float4 f = corner[i];                              // curr_point: untransformed (:146)
-          p = mk3((double)f.x, (double)f.y, (double)f.z);
-          if (FILL && i < PlaneCache<BLOCK>::kEdges) {
-            pc.ecx[i] = C.x; pc.ecy[i] = C.y; pc.ecz[i] = C.z; pc.enx[i] = N.x; pc.eny[i] = N.y; pc.enz[i] = N.z;
-            pc.epx[i] = f.x; pc.epy[i] = f.y; pc.epz[i] = f.z;
-          }
-        }
-      }
+      const double* r6 = rec + 6 * (size_t)i;
+      const d3 C = mk3(r6[0], r6[1], r6[2]);
+      const d3 N = mk3(r6[3], r6[4], r6[5]);
+      const d3 p = mk3(pprime[3 * (size_t)i], pprime[3 * (size_t)i + 1], pprime[3 * (size_t)i + 2]);
       edge_row(i, C, N, p);
     }
-    cached_planes();
   }
   LM_T(t_edges_done);
   // (b) the streamed rest (everything in the FILL pass): ~1 GB per launch with all 1 024 solves resident (PMC r02).  A thread's

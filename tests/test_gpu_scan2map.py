@@ -391,7 +391,7 @@ def test_candidate_counter_mode_counts_and_keeps_results(gpu):
     assert np.array_equal(p0, p1) and np.array_equal(s0, s1)
     n_query = 2 * (len(inp["corner"]) + len(inp["surf"]))                # two outer iterations
     assert t.launches_assoc == 2
-    n_cand = t.knn_candidates + t.knn_candidates_seeded               # first pass (from the gate) + second pass (seeded bound)
+    n_cand = t.knn_candidates + t.knn_candidates_seeded               # first pass + second pass
     assert 5 * n_query * 0.5 < n_cand < 2000 * n_query                # at least ~5 per accepted query, far below the map size
     assert 0 < t.knn_candidates_seeded                                # the second pass is counted on its own
     assert t.launches_assoc_seeded == 1 and 0 < t.ms_assoc_seeded < t.ms_assoc
@@ -504,24 +504,22 @@ def test_truncated_key_walk_is_exact_on_ties_and_at_the_gate(oracle, monkeypatch
             h.close()
 
 
-@pytest.mark.parametrize("form", ["lane", "split"])
-def test_seeded_second_pass_finds_the_same_neighbours(oracle, monkeypatch, form):
-    """The second outer iteration's 5-NN search starts from the bound the first iteration's five neighbours give
-    (knn5_seed_bound) instead of the acceptance gate.  It must remain the EXACT top-5 by (distance, index): against a handle
-    with MSFL_KNN_SEED=0 the poses, statuses, accepted counts, iteration counts and costs are equal bit for bit -- on
-    thinned maps with holes and guesses up to a metre off (neighbour sets that change between the passes, features accepted
-    in one pass only), on the lattice map (ties at the bound, duplicates), and through both one-lane-per-query kernels
-    (`lane`: the mixed kernel of small batches; `split`: the per-kind kernel of batches of >= 65 536 features)."""
+def test_5nn_forms_agree_through_both_outer_iterations(oracle, monkeypatch):
+    """Both outer iterations of a match must find the same neighbours through every form of the 5-NN search: the per-kind kernel
+    of batches of >= 65 536 features (`split`), the mixed one-lane-per-query kernel (`lane`) and the row-parallel form (`rows`).
+    Poses, statuses, accepted counts, iteration counts and costs are equal bit for bit -- on thinned maps with holes and guesses
+    up to 0.6 m off (neighbour sets that change between the passes, features accepted in one pass only; the batch against single
+    calls through `lane` and `rows`), and on the lattice map (ties at the gate, duplicates; `lane` against `rows`)."""
     from msf_loam_amd import capi
-    monkeypatch.setenv("MSFL_KNN_FORM", "lane")
-    monkeypatch.setenv("MSFL_KNN_SEED", "0")
-    h0 = capi.Handle(0)
-    monkeypatch.setenv("MSFL_KNN_SEED", "1")
-    h1 = capi.Handle(0)
+    hs = {}
+    for form in ("lane", "rows"):
+        monkeypatch.setenv("MSFL_KNN_FORM", form)
+        hs[form] = capi.Handle(0)
+    monkeypatch.delenv("MSFL_KNN_FORM")
     try:
         _, mc, ms = common.small_world()
         n_seeds = max(int(os.environ.get("MSFL_FUZZ_SEEDS", "6")), 6)
-        reps = 16 if form == "split" else 1          # 16 x ~5 000 features per job: beyond the split kernel's 65 536-feature threshold
+        reps = 16                                      # 16 x ~5 000 features per job: beyond the split kernel's 65 536-feature threshold
         for seed in range(n_seeds):
             rng = np.random.default_rng(9100 + seed)
             keep_c = rng.uniform(size=len(mc)) < rng.uniform(0.3, 1.0)
@@ -538,46 +536,39 @@ def test_seeded_second_pass_finds_the_same_neighbours(oracle, monkeypatch, form)
                     g[3:] = synth.quat_mul(g[3:], np.r_[0.5 * rng.normal(0, rng.choice([0.005, 0.03]), 3), 1.0]); g[3:] /= np.linalg.norm(g[3:])
                     cs.append(corner); ss.append(surf); co.append(co[-1] + len(corner)); so.append(so[-1] + len(surf)); gs.append(g)
             args = (np.concatenate(cs), np.array(co, np.int32), np.concatenate(ss), np.array(so, np.int32))
-            if form == "split":
-                assert co[-1] + so[-1] >= 65536
-            out = []
-            for h in (h0, h1):
+            assert co[-1] + so[-1] >= 65536
+            for h in hs.values():
                 h.set_map(mc2, ms2)
-                out.append(h.match_scan2map_batch(*args, np.array(gs), want_info=True))
-            (p0, s0, i0), (p1, s1, i1) = out
-            assert np.array_equal(p0, p1) and np.array_equal(s0, s1)
-            for a, b in zip(i0, i1):
-                assert list(a.n_edge) == list(b.n_edge) and list(a.n_plane) == list(b.n_plane) and list(a.lm_iterations) == list(b.lm_iterations)
-                assert list(a.final_cost) == list(b.final_cost)
-            if seed == 0:                              # the second pass really runs seeded, on fewer candidates
-                h1.set_timing(3); h1.get_timing(reset=True)
-                h1.match_scan2map_batch(*args, np.array(gs))
-                t = h1.get_timing(reset=True); h1.set_timing(0)
-                assert 0 < t.knn_candidates_seeded < 0.95 * t.knn_candidates
-        if form == "lane":
-            # lattice map: exactly equal f32 distances at the bound, duplicated points; two different small motions between the passes
-            g_ = np.arange(-6, 7, dtype=np.float32) * 0.5
-            X, Y = np.meshgrid(g_, g_, indexing="ij")
-            plane = np.stack([X.ravel(), Y.ravel(), np.full(X.size, -1.5, np.float32)], 1)
-            wall = np.stack([np.full(X.size, 3.5, np.float32), X.ravel(), Y.ravel() + 1.5], 1)
-            lat = np.concatenate([plane, wall, plane[::7]])
-            lat = np.concatenate([lat, np.zeros((len(lat), 1), np.float32)], 1).astype(np.float32)
-            line = np.stack([np.zeros(60, np.float32), np.zeros(60, np.float32), np.arange(60, dtype=np.float32) * 0.125], 1)
-            pole = np.concatenate([line, line[::5]]); pole = np.concatenate([pole, np.zeros((len(pole), 1), np.float32)], 1).astype(np.float32)
-            rng = np.random.default_rng(4)
-            q = np.concatenate([plane[rng.integers(0, len(plane), 300)] + rng.choice([0.0, 0.25, 0.125], (300, 3)).astype(np.float32),
-                                wall[rng.integers(0, len(wall), 300)] + rng.choice([0.0, 0.25, -0.125], (300, 3)).astype(np.float32)])
-            surf = np.concatenate([q, np.zeros((len(q), 1), np.float32)], 1).astype(np.float32)
-            corner = np.concatenate([line[::3] + np.float32(0.05), np.zeros((20, 1), np.float32)], 1).astype(np.float32)
-            for pose in (np.array([0, 0, 0, 0, 0, 0, 1.0]), np.array([0.125, -0.25, 0.0, 0, 0, 0, 1.0]), np.array([0.01, 0.02, -0.03, 0, 0, 0.002, 1.0])):
-                res = []
-                for h in (h0, h1):
-                    h.set_map(pole, lat)
-                    res.append(h.match_scan2map(corner, surf, pose / np.r_[1, 1, 1, [np.linalg.norm(pose[3:])] * 4]))
-                assert res[0][0] == res[1][0] and np.array_equal(res[0][1], res[1][1])
-                assert list(res[0][2].n_plane) == list(res[1][2].n_plane) and list(res[0][2].final_cost) == list(res[1][2].final_cost)
+            pb, sb, ib = hs["lane"].match_scan2map_batch(*args, np.array(gs), want_info=True)     # the whole batch: split kernel
+            for j in range(len(gs)):
+                for form, h in hs.items():
+                    s1, p1, i1 = h.match_scan2map(cs[j], ss[j], gs[j])
+                    assert sb[j] == s1 and np.array_equal(pb[j], p1), (seed, form, j)
+                    assert list(ib[j].n_edge) == list(i1.n_edge) and list(ib[j].n_plane) == list(i1.n_plane), (seed, form, j)
+                    assert list(ib[j].lm_iterations) == list(i1.lm_iterations) and list(ib[j].final_cost) == list(i1.final_cost), (seed, form, j)
+        # lattice map: exactly equal f32 distances at the gate, duplicated points; two different small motions between the passes
+        g_ = np.arange(-6, 7, dtype=np.float32) * 0.5
+        X, Y = np.meshgrid(g_, g_, indexing="ij")
+        plane = np.stack([X.ravel(), Y.ravel(), np.full(X.size, -1.5, np.float32)], 1)
+        wall = np.stack([np.full(X.size, 3.5, np.float32), X.ravel(), Y.ravel() + 1.5], 1)
+        lat = np.concatenate([plane, wall, plane[::7]])
+        lat = np.concatenate([lat, np.zeros((len(lat), 1), np.float32)], 1).astype(np.float32)
+        line = np.stack([np.zeros(60, np.float32), np.zeros(60, np.float32), np.arange(60, dtype=np.float32) * 0.125], 1)
+        pole = np.concatenate([line, line[::5]]); pole = np.concatenate([pole, np.zeros((len(pole), 1), np.float32)], 1).astype(np.float32)
+        rng = np.random.default_rng(4)
+        q = np.concatenate([plane[rng.integers(0, len(plane), 300)] + rng.choice([0.0, 0.25, 0.125], (300, 3)).astype(np.float32),
+                            wall[rng.integers(0, len(wall), 300)] + rng.choice([0.0, 0.25, -0.125], (300, 3)).astype(np.float32)])
+        surf = np.concatenate([q, np.zeros((len(q), 1), np.float32)], 1).astype(np.float32)
+        corner = np.concatenate([line[::3] + np.float32(0.05), np.zeros((20, 1), np.float32)], 1).astype(np.float32)
+        for h in hs.values():
+            h.set_map(pole, lat)
+        for pose in (np.array([0, 0, 0, 0, 0, 0, 1.0]), np.array([0.125, -0.25, 0.0, 0, 0, 0, 1.0]), np.array([0.01, 0.02, -0.03, 0, 0, 0.002, 1.0])):
+            res = [h.match_scan2map(corner, surf, pose / np.r_[1, 1, 1, [np.linalg.norm(pose[3:])] * 4]) for h in (hs["lane"], hs["rows"])]
+            assert res[0][0] == res[1][0] and np.array_equal(res[0][1], res[1][1])
+            assert list(res[0][2].n_plane) == list(res[1][2].n_plane) and list(res[0][2].final_cost) == list(res[1][2].final_cost)
     finally:
-        h0.close(); h1.close()
+        for h in hs.values():
+            h.close()
 
 
 @pytest.mark.parametrize("kind", ["outdoor", "corridor"])
@@ -645,11 +636,11 @@ def test_other_worlds_follow_the_oracle(gpu, oracle, kind):
         h.close()
 
 
-def test_deferred_pivoted_qr_planes_equal_the_inline_fallback(gpu, oracle):
-    """Round 5: the whole-batch fit kernel (batches of >= 65 536 features) no longer carries the pivoted-QR fallback of the plane fit; a
-    neighbourhood that fails the guards of the adjugate form (planes through the origin: A n = -1 has no solution; collinear
-    neighbours; a plane seen from 1 km away) goes to a list and is fitted by fit_fallback_kernel.  120 copies of a job that is FULL of
-    such neighbourhoods, against the single-call path (which keeps the fallback inline) bit for bit, and the oracle's accept sets."""
+def test_ill_conditioned_planes_batch_equals_single_calls(gpu, oracle):
+    """A neighbourhood that fails the guards of the plane fit's adjugate form (planes through the origin: A n = -1 has no solution;
+    collinear neighbours; a plane seen from 1 km away) is fitted by the reference's pivoted QR.  120 copies of a job that is FULL of
+    such neighbourhoods through the whole-batch fit kernel (batches of >= 65 536 features), against the single-call path bit for
+    bit, three times over, and the oracle's accept sets."""
     rng = np.random.default_rng(61)
     g_ = np.arange(-6, 7, dtype=np.float32) * 0.5
     X, Y = np.meshgrid(g_, g_, indexing="ij")
@@ -682,7 +673,7 @@ def test_deferred_pivoted_qr_planes_equal_the_inline_fallback(gpu, oracle):
     guesses = np.array([poses[i % 3] for i in range(B)])
     co = np.arange(B + 1, dtype=np.int32) * len(corner); so = np.arange(B + 1, dtype=np.int32) * len(surf)
     assert co[-1] + so[-1] >= 65536
-    for rep in range(3):                             # the two fallback lists alternate: three batches use both and re-arm both
+    for rep in range(3):
         pb, sb, ib = gpu.match_scan2map_batch(np.tile(corner, (B, 1)), co, np.tile(surf, (B, 1)), so, guesses, want_info=True)
         for i in range(3):
             s1, p1, i1 = gpu.match_scan2map(corner, surf, poses[i])
