@@ -210,10 +210,13 @@ def world_drive(world, kind, n):
     return np.array(poses)
 
 
-def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=False, maps_out=None, quirks=False, imu=None, clouds_out=None):
+def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=False, maps_out=None, quirks=False, imu=None, clouds_out=None,
+             uncertainty=None, unc_out=None):
     """The same loop through the device-resident SLAM step (msfl_slam_add_scan): raw scan in, pose out, one
     synchronisation per scan (pipelined=False) or none until the record is fetched one scan later (pipelined=True: the
     odometry chain of scan k + 1 runs under the mapping chain of scan k, like the reference's two threads).
+    uncertainty: a min_eigenvalue turns msfl_slam_set_uncertainty on; unc_out (a list) then receives per scan the (odometry, mapping)
+    records of msfl_slam_get_uncertainty.
     Returns (poses, records, wall-clock ms per scan over the scans after the second)."""
     from msf_loam_amd import capi
     n = len(poses_true)
@@ -225,6 +228,9 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
         cap, rings = 200000, 128
     slam = capi.Slam(device, max_scan_points=cap, max_rings=rings, pose_odom2map=poses_true[0],
                      reference_quirks=1 if quirks else 0, keep_clouds=1 if clouds_out is not None else 0)
+    if uncertainty is not None:
+        slam.set_uncertainty(True, uncertainty)
+    want_unc = uncertainty is not None and unc_out is not None
     recs = [None] * n
     t_start = None
     for k in range(n):
@@ -235,10 +241,14 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
             slam.add_scan(*scans[k], wait=False, imu=im)
             if k >= 1:
                 recs[k - 1] = slam.result(k - 1)
+                if want_unc:
+                    unc_out.append(slam.get_uncertainty(k - 1))
                 if clouds_out is not None:
                     clouds_out.append(slam.clouds(k - 1))
         else:
             recs[k] = slam.add_scan(*scans[k], imu=im)
+            if want_unc:
+                unc_out.append(slam.get_uncertainty(k))
             if clouds_out is not None:
                 clouds_out.append(slam.clouds(k))
         if verbose and k % 50 == 0 and recs[max(k - 1, 0)] is not None:
@@ -246,6 +256,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
             print(k, list(r.grid_corner)[:3], list(r.grid_surf)[:3], r.status_mapping, file=sys.stderr)
     if pipelined:
         recs[n - 1] = slam.result(n - 1)
+        if want_unc:
+            unc_out.append(slam.get_uncertainty(n - 1))
         if clouds_out is not None:
             clouds_out.append(slam.clouds(n - 1))
     wall = time.perf_counter() - t_start if t_start is not None else 0.0
@@ -274,6 +286,9 @@ def main():
                     help="room: the SURVEY 8d world and its loop; outdoor / corridor: msf_loam_amd/worlds.py with a drive down the street / the axis (round 5)")
     ap.add_argument("--beams", type=int, choices=[16, 64], default=16, help="64: the KITTI-scale sensor of BASELINE configs[3] (64 x 1 900, -24.8 .. +2 degrees)")
     ap.add_argument("--keep-clouds", action="store_true", help="msfl_slam_config.keep_clouds = 1 and fetch every scan's clouds (what PublishScan would publish)")
+    ap.add_argument("--uncertainty", type=float, nargs="?", const=150.0, default=None, metavar="MIN_EIGENVALUE",
+                    help="msfl_slam_set_uncertainty: print per scan the smallest eigenvalue of the mapping solve's information matrix, n_degenerate "
+                         "at this threshold (default 150) and the weakest direction [dt(3), dtheta(3)]")
     args = ap.parse_args()
     if args.world == "room":
         world = synth.World(ground_half=45.0)
@@ -291,8 +306,16 @@ def main():
     scans = [synth.make_scan(world, truth[k], synth.SEED + 5000 + k, **kw) for k in range(args.scans)]
     import gc
     gc.collect(); gc.disable()
+    unc = []
     est, recs, ms = run_slam(world, truth, pipelined=args.mode == "slam-pipelined", scans=scans, quirks=args.reference_quirks,
-                             imu=synthetic_imu(truth) if args.imu else None, clouds_out=[] if args.keep_clouds else None)
+                             imu=synthetic_imu(truth) if args.imu else None, clouds_out=[] if args.keep_clouds else None,
+                             uncertainty=args.uncertainty, unc_out=unc)
+    for k, u in enumerate(unc):
+        m = u[1]
+        if m["valid"]:
+            print("scan %4d  lambda_min %10.2f  n_degenerate %d  weakest %s" % (k, m["eigenvalues"][0], m["n_degenerate"], np.array2string(m["eigenvectors"][0], precision=3, suppress_small=True)), file=sys.stderr)
+        else:
+            print("scan %4d  no mapping solve" % k, file=sys.stderr)
     last = recs[-1]
     if args.dump_poses:
         np.save(args.dump_poses, est)

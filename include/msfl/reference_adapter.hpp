@@ -25,6 +25,8 @@
 //   msfl::adapter::MatchScan2Scan(h, scan_last, scan_curr, pose_estimate_curr2last)    odometry_scan_matcher.cc:43-285
 //   msfl::adapter::MatchScan2Map(h, cloud_map, scan_curr, is_initialized, preintegration, gravity_vector,
 //                                pose_estimate_map_scan2world, velocity)               mapping_scan_matcher.cc:61-278 (after :28-59)
+// and, for the covariance block of the odometry message (common/rigid_transform.h ToROS leaves it zero):
+//   msfl::adapter::SetUncertaintySink(h, &record, min_eigenvalue)  once;  msfl::adapter::CovarianceInParentFrame(pose, record, scale, out36)
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -260,6 +262,34 @@ inline void UndistortCloud(msfl_handle* h, const IntegrationT& preintegration, C
   const PreintegrationView pv(preintegration);
   Check(msfl_undistort_cloud(h, &pv.pre, pts.data(), static_cast<int>(pts.size()), MSFL_MEM_HOST), h, "msfl_undistort_cloud");
   for (std::size_t i = 0; i < pts.size(); ++i) { auto& p = (*cloud)[i]; p.x = pts[i].x; p.y = pts[i].y; p.z = pts[i].z; }
+}
+
+// ---- uncertainty of the last registration (msfl_match_uncertainty).  `record` must outlive the handle's matcher calls (one
+// registration per call on this side of the boundary, so a sink of one record); nullptr turns the output off again.
+inline void SetUncertaintySink(msfl_handle* h, msfl_match_uncertainty* record, double min_eigenvalue = 0.0) {
+  Check(msfl_set_uncertainty(h, record, record ? 1 : 0, MSFL_MEM_HOST, min_eigenvalue), h, "msfl_set_uncertainty");
+}
+
+// out (row-major 6 x 6) = scale * A * unc.covariance * A^T with A = diag(I, R(pose)): the tangent space of the solve rotates about
+// the BODY axes (q = q * dq), geometry_msgs::PoseWithCovariance wants rotations about the fixed parent axes, in the same
+// [x y z, rot x y z] order.  `scale`: unc.sigma2, or the variance of the caller's own sensor model (the covariance is for
+// unit-variance residuals).  This is the array to copy into PoseWithCovariance::covariance.
+template <class RigidT>
+inline void CovarianceInParentFrame(const RigidT& pose, const msfl_match_uncertainty& unc, double scale, double out[36]) {
+  double v[7];
+  RigidToArray(pose, v);
+  const double x = v[3], y = v[4], z = v[5], w = v[6];
+  const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)},
+                          {2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)},
+                          {2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)}};
+  const double* S = unc.covariance;
+  double M[6][6];                                                        // A * S: the rotation rows turned
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j)
+      M[i][j] = i < 3 ? S[6 * i + j] : R[i - 3][0] * S[18 + j] + R[i - 3][1] * S[24 + j] + R[i - 3][2] * S[30 + j];
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j)
+      out[6 * i + j] = scale * (j < 3 ? M[i][j] : M[i][3] * R[j - 3][0] + M[i][4] * R[j - 3][1] + M[i][5] * R[j - 3][2]);
 }
 
 }  // namespace adapter

@@ -150,11 +150,20 @@ class ScanMatcher {
   ScanMatcher& operator=(const ScanMatcher&) = delete;
   msfl_handle* handle() const { return h_; }
   const msfl_match_info& last_info() const { return info_; }
+  // Opt-in: every later Match* call also delivers the information matrix / covariance of its last solve (msfl_match_uncertainty);
+  // eigen-directions below min_eigenvalue count as degenerate.  Poses are bit-identical with and without it.
+  void EnableUncertainty(double min_eigenvalue = 0.0) { adapter::SetUncertaintySink(h_, &unc_, min_eigenvalue); }
+  void DisableUncertainty() { adapter::SetUncertaintySink(h_, nullptr); unc_ = msfl_match_uncertainty{}; }
+  // The last Match* call's record (valid = 0, all zero: the output is off, or no solve ran in that call).
+  const msfl_match_uncertainty& last_uncertainty() const { return unc_; }
 
  protected:
   msfl_handle* h_ = nullptr;
   msfl_match_info info_{};
+  msfl_match_uncertainty unc_{};
 };
+
+using adapter::CovarianceInParentFrame;   // (pose, last_uncertainty(), scale, double out[36]) -> PoseWithCovariance::covariance
 
 class OdometryScanMatcher : public ScanMatcher {
  public:
@@ -164,6 +173,7 @@ class OdometryScanMatcher : public ScanMatcher {
   virtual bool MatchScan2Scan(const TimestampedPointCloud<PointTypeOriginal>& scan_last,
                               const TimestampedPointCloud<PointTypeOriginal>& scan_curr,
                               Rigid3d* pose_estimate_curr2last) {
+    unc_ = msfl_match_uncertainty{};
     return adapter::MatchScan2Scan(h_, scan_last, scan_curr, pose_estimate_curr2last, &info_);
   }
 };
@@ -190,6 +200,7 @@ class MappingScanMatcher : public ScanMatcher {
                      const TimestampedPointCloud<PointType>& scan_curr,
                      const bool is_initialized, const DeskewInputs* deskew,
                      Rigid3d* pose_estimate_map_scan2world, Vector3d* velocity) {
+    unc_ = msfl_match_uncertainty{};
     const std::vector<msfl_point> mc = detail::Pack(*cloud_map.cloud_corner_less_sharp);
     const std::vector<msfl_point> ms = detail::Pack(*cloud_map.cloud_surf_less_flat);
     detail::Check(msfl_set_map(h_, mc.data(), static_cast<int>(mc.size()), ms.data(), static_cast<int>(ms.size()), MSFL_MEM_HOST),
@@ -243,6 +254,7 @@ class MappingScanMatcher : public ScanMatcher {
                              "branch from the IMU-only solve of prev_state (mapping_scan_matcher.cc:28-59), not from the incoming pose");
     if (!pose_estimate_map_scan2world || !velocity) throw std::invalid_argument("MatchScan2Map: null pose / velocity");
     imu_presolve_(prev_state, pose_estimate_map_scan2world, velocity);  // .cc:58-59
+    unc_ = msfl_match_uncertainty{};
     return adapter::MatchScan2Map(h_, cloud_map, scan_curr, true, preintegration, gravity_vector, pose_estimate_map_scan2world, velocity, &info_);
   }
 
@@ -356,6 +368,15 @@ class LaserSlam {
     return Unpack(rec_);
   }
   const msfl_slam_result& last_record() const { return rec_; }
+  // msfl_slam_set_uncertainty / msfl_slam_get_uncertainty: the records of MatchScan2Scan and MatchScan2Map of one of the last four scans
+  void EnableUncertainty(double min_eigenvalue = 0.0) {
+    const msfl_status st = msfl_slam_set_uncertainty(s_, 1, min_eigenvalue);
+    if (st != MSFL_OK) throw std::runtime_error(std::string("msfl_slam_set_uncertainty: ") + msfl_status_string(st) + " " + msfl_slam_last_error(s_));
+  }
+  void Uncertainty(int scan_index, msfl_match_uncertainty* odometry, msfl_match_uncertainty* mapping) {
+    const msfl_status st = msfl_slam_get_uncertainty(s_, scan_index, odometry, mapping);
+    if (st != MSFL_OK) throw std::runtime_error(std::string("msfl_slam_get_uncertainty: ") + msfl_status_string(st) + " " + msfl_slam_last_error(s_));
+  }
 
   // What the reference publishes per scan (PublishScan, laser_mapping.cc:418-440) and accumulates for its PLY dump (:214-217), for one of the
   // last two scans fed (keep_clouds): the scan as a TimestampedPointCloud whose five clouds are the de-skewed ones, and cloud_full_res in the map frame.

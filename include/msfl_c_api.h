@@ -115,6 +115,26 @@ typedef struct msfl_match_info {
   double final_cost[2];      /* cost at the returned pose */
 } msfl_match_info;
 
+/* Per-registration uncertainty of the returned pose (opt-in: msfl_set_uncertainty / msfl_slam_set_uncertainty).  The reference
+   has nothing here: its odometry messages are geometry_msgs::PoseWithCovariance whose 36 covariance doubles stay zero.
+   `covariance` is for UNIT-VARIANCE residuals, which is what ceres::Covariance returns: scale it by `sigma2` (the a-posteriori
+   variance factor of this solve) or by the variance of your own sensor model before using it as a pose covariance.  Both
+   matrices are in the solver's tangent space; the rotation block is BODY-frame (see `information`), so a consumer that wants
+   fixed parent axes (ROS) rotates it first: msfl::CovarianceInParentFrame in include/msfl/scan_matcher.hpp. */
+typedef struct msfl_match_uncertainty {
+  double information[36];   /* row-major H = J^T J of the LAST solve's problem at the RETURNED pose, robustified as Ceres
+                               evaluates it (rows scaled by sqrt(rho'), i.e. what ceres::Covariance would see); tangent order
+                               [dt(3), dtheta(3)] of PoseLocalParameterization: t += dt (parent frame), q = q * dq(dtheta) (body frame) */
+  double eigenvalues[6];    /* ascending */
+  double eigenvectors[36];  /* row k = unit eigenvector of eigenvalues[k]; sign: its largest-magnitude component (lowest index on ties) is positive */
+  double covariance[36];    /* sum over kept k of v_k v_k^T / lambda_k: inverse of H, pseudo-inverse when directions are dropped */
+  double sigma2;            /* a-posteriori variance factor 2 * final_cost / (n_residuals - 6); 0 when n_residuals <= 6 */
+  int n_residuals;          /* 3 * edges + planes of that solve */
+  int n_degenerate;         /* eigenvalues below max(min_eigenvalue, 1e-14 * lambda_max): dropped from `covariance` */
+  int valid;                /* 0: no solve ran for this registration (status != 0, empty problem, too few correspondences): record all zero */
+  int reserved_;
+} msfl_match_uncertainty;
+
 /* Accumulated GPU time per kernel class, measured with HIP events on the handle's stream
    (enabled by msfl_set_timing).  Used by bench.py for the live roofline figure. */
 typedef struct msfl_timing {
@@ -163,6 +183,18 @@ const char* msfl_last_error(const msfl_handle* h);
    "distance evaluations per second" figure only). */
 msfl_status msfl_set_timing(msfl_handle* h, int enabled);
 msfl_status msfl_get_timing(msfl_handle* h, msfl_timing* out, int reset);
+
+/* Uncertainty output, off by default.  out == NULL turns it off.  Otherwise EVERY later matcher call on this handle
+   (msfl_match_scan2map, _batch, both deskew forms, msfl_match_pairs_batch, msfl_solve_records, msfl_match_scan2scan, _batch)
+   writes one record per registration into out[0 .. n), in the call's order; a call with more registrations than `capacity`
+   returns MSFL_CAPACITY before it stages or launches anything (poses untouched).  A registration whose per-scan status is not 0, or
+   whose last solve had nothing to solve, gets an all-zero record (valid = 0); a call that itself fails writes nothing.
+     mem == MSFL_MEM_DEVICE : `out` is a device pointer, the write is asynchronous on the handle's stream, nothing is synchronised;
+     mem == MSFL_MEM_HOST   : the records are copied like `info` (the call synchronises).
+   min_eigenvalue (>= 0): eigen-directions of the information matrix below it are counted in n_degenerate and left out of
+   `covariance`.  Poses, statuses and `info` of every call are bit-identical with the feature on and off: one more kernel runs
+   after the last solve and reads what the solve left behind. */
+msfl_status msfl_set_uncertainty(msfl_handle* h, msfl_match_uncertainty* out, int capacity, msfl_mem mem, double min_eigenvalue);
 
 /* ------------------------------------------------------------------------------------------ */
 /* stage C — scan-to-local-map registration                                                   */
@@ -620,6 +652,15 @@ msfl_status msfl_slam_add_scan_imu(msfl_slam* s, const msfl_point* pts, const ui
 
 /* Wait for the scan with the given index (one of the last four fed) and deliver its record. */
 msfl_status msfl_slam_get_result(msfl_slam* s, int scan_index, msfl_slam_result* result);
+
+/* Uncertainty of the two registrations of every scan fed from now on (enabled != 0), see msfl_match_uncertainty; min_eigenvalue as
+   in msfl_set_uncertainty.  Results (msfl_slam_result) are bit-identical with the feature on and off. */
+msfl_status msfl_slam_set_uncertainty(msfl_slam* s, int enabled, double min_eigenvalue);
+/* The records of scan `scan_index` (one of the last four fed, like msfl_slam_get_result; waits for it): MatchScan2Scan's and
+   MatchScan2Map's.  Either pointer may be NULL.  odometry->valid == 0 for scan 0 and where MatchScan2Scan returned false;
+   mapping->valid == 0 when the gate (min_map_corner / min_map_surf) kept the match from running.  MSFL_BAD_ARG for a scan that
+   was fed while the feature was off. */
+msfl_status msfl_slam_get_uncertainty(msfl_slam* s, int scan_index, msfl_match_uncertainty* odometry, msfl_match_uncertainty* mapping);
 
 /* msfl_slam_config.keep_clouds: the clouds of scan `scan_index` (it must be one of the last TWO fed: the buffers belong to a set that
    the scan after next reuses).  Waits for that scan's chain.

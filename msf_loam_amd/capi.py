@@ -28,6 +28,7 @@ EXPORTED = [
     "msfl_grid_create", "msfl_grid_destroy", "msfl_grid_insert_scan", "msfl_grid_get_surrounded", "msfl_grid_size", "msfl_grid_dump",
     "msfl_slam_default_config", "msfl_slam_create", "msfl_slam_destroy", "msfl_slam_add_scan", "msfl_slam_add_scan_imu", "msfl_slam_get_result", "msfl_slam_grids",
     "msfl_slam_last_error", "msfl_slam_get_clouds",
+    "msfl_set_uncertainty", "msfl_slam_set_uncertainty", "msfl_slam_get_uncertainty",
 ]
 
 
@@ -59,6 +60,20 @@ class MatchInfo(C.Structure):
     _fields_ = [("status", C.c_int), ("n_edge", C.c_int * 2), ("n_plane", C.c_int * 2),
                 ("lm_iterations", C.c_int * 2), ("lm_successful", C.c_int * 2),
                 ("initial_cost", C.c_double * 2), ("final_cost", C.c_double * 2)]
+
+
+class MatchUncertainty(C.Structure):
+    """msfl_match_uncertainty: information matrix of the last solve at the returned pose, its eigen-decomposition and covariance."""
+    _fields_ = [("information", C.c_double * 36), ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36),
+                ("covariance", C.c_double * 36), ("sigma2", C.c_double), ("n_residuals", C.c_int), ("n_degenerate", C.c_int),
+                ("valid", C.c_int), ("reserved_", C.c_int)]
+
+
+# the same record as a numpy structured dtype (Handle.uncertainty, Slam.get_uncertainty)
+UNCERTAINTY_DTYPE = np.dtype([("information", np.float64, (6, 6)), ("eigenvalues", np.float64, (6,)), ("eigenvectors", np.float64, (6, 6)),
+                              ("covariance", np.float64, (6, 6)), ("sigma2", np.float64), ("n_residuals", np.int32),
+                              ("n_degenerate", np.int32), ("valid", np.int32), ("reserved_", np.int32)])
+assert UNCERTAINTY_DTYPE.itemsize == C.sizeof(MatchUncertainty)
 
 
 class Timing(C.Structure):
@@ -228,6 +243,33 @@ class Handle:
         t = Timing()
         self._check(self.lib.msfl_get_timing(self.h, C.byref(t), C.c_int(int(reset))), "msfl_get_timing")
         return t
+
+    # ---- uncertainty output (msfl_set_uncertainty) ----
+    def set_uncertainty(self, n, min_eigenvalue=0.0):
+        """Every later matcher call writes one msfl_match_uncertainty per registration into a host buffer of `n` records
+        owned by this object (read it with uncertainty()).  n = 0 / None turns the feature off."""
+        if not n:
+            self._check(self.lib.msfl_set_uncertainty(self.h, None, C.c_int(0), C.c_int(MEM_HOST), C.c_double(0.0)), "msfl_set_uncertainty")
+            self._unc = None
+            return
+        buf = np.zeros(int(n), UNCERTAINTY_DTYPE)
+        self._check(self.lib.msfl_set_uncertainty(self.h, _vp(buf), C.c_int(int(n)), C.c_int(MEM_HOST), C.c_double(float(min_eigenvalue))),
+                    "msfl_set_uncertainty")
+        self._unc = buf
+
+    def uncertainty(self, n=None):
+        """The first `n` records (default: all) the last matcher call wrote, as a copy of the numpy structured array."""
+        buf = getattr(self, "_unc", None)
+        if buf is None:
+            raise RuntimeError("uncertainty output is off: call set_uncertainty(n) first")
+        return buf[:len(buf) if n is None else int(n)].copy()
+
+    def set_uncertainty_device(self, ptr, capacity, min_eigenvalue=0.0):
+        """Device-pointer variant for the *_device calls: `ptr` (torch tensor / raw pointer / None = off) holds `capacity` records of
+        UNCERTAINTY_DTYPE.itemsize bytes; written asynchronously on the handle's stream."""
+        self._unc = None
+        self._check(self.lib.msfl_set_uncertainty(self.h, _vp(ptr), C.c_int(int(capacity) if ptr is not None else 0), C.c_int(MEM_DEVICE),
+                                                  C.c_double(float(min_eigenvalue))), "msfl_set_uncertainty(device)")
 
     # ---- stage C ----
     def set_map(self, corner, surf, n_corner=None, n_surf=None, mem=MEM_HOST):
@@ -655,6 +697,19 @@ class Slam:
         if st != OK:
             raise MsflError(st, "msfl_slam_get_result", self._err())
         return r
+
+    def set_uncertainty(self, enabled=True, min_eigenvalue=0.0):
+        st = self.lib.msfl_slam_set_uncertainty(self.s, C.c_int(1 if enabled else 0), C.c_double(float(min_eigenvalue)))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_set_uncertainty", self._err())
+
+    def get_uncertainty(self, scan_index):
+        """(odometry, mapping) records of one of the last four scans fed: a numpy structured array of two UNCERTAINTY_DTYPE records."""
+        out = np.zeros(2, UNCERTAINTY_DTYPE)
+        st = self.lib.msfl_slam_get_uncertainty(self.s, C.c_int(int(scan_index)), C.c_void_p(out[0:1].ctypes.data), C.c_void_p(out[1:2].ctypes.data))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_get_uncertainty", self._err())
+        return out
 
     def clouds(self, scan_index):
         """keep_clouds=1: the scan's data products as host arrays (msfl_slam_get_clouds, MSFL_MEM_HOST): dict with full_scan (n,4),

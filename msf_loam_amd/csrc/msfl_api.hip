@@ -29,6 +29,7 @@
 #include "msfl_odom.cuh"
 #include "msfl_grid.cuh"
 #include "msfl_deskew.cuh"
+#include "msfl_uncertainty.cuh"
 
 using namespace msfl;
 
@@ -164,6 +165,13 @@ struct msfl_handle_s {
   DevBuf pp[5];   // per-point passes: pre-integration samples, staged points, dq, dp, flag
   DevBuf pr[5];   // batched (map, scan) pairs: map offsets and cell-table bases per cloud kind, preset status
 
+  // msfl_set_uncertainty: where every matcher call writes one msfl_match_uncertainty per registration (null: feature off)
+  msfl_match_uncertainty* unc_out = nullptr;
+  int unc_capacity = 0;
+  msfl_mem unc_mem = MSFL_MEM_HOST;
+  double unc_min_eigenvalue = 0.0;
+  DevBuf unc_dev;                         // device staging of a host sink
+
   PinRing pin;
   PinBuf readback;
   hipStream_t copy_stream = nullptr;      // host-buffer batches: H2D of chunk k+1 under the compute of chunk k
@@ -252,6 +260,32 @@ SolverParams solver_params(const msfl_params& p, int min_corr) {
 }
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
+
+// ---- msfl_set_uncertainty plumbing shared by every matcher entry point ----
+static_assert(sizeof(UncRecord) == sizeof(msfl_match_uncertainty), "uncertainty record layout");
+// First thing a matcher call does, before it stages or launches anything: refuse a call with more registrations than the sink holds.
+msfl_status unc_check(msfl_handle* h, int n, const char* who) {
+  if (h->unc_out && n > h->unc_capacity)
+    return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_uncertainty sink holds " +
+                                      std::to_string(h->unc_capacity));
+  return MSFL_OK;
+}
+// Where the kernel writes the n records of this call (null: feature off).
+msfl_status unc_target(msfl_handle* h, int n, UncRecord** d_unc) {
+  *d_unc = nullptr;
+  if (!h->unc_out) return MSFL_OK;
+  if (h->unc_mem == MSFL_MEM_DEVICE) { *d_unc = reinterpret_cast<UncRecord*>(h->unc_out); return MSFL_OK; }
+  HIPCHK(h, h->unc_dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(UncRecord)));
+  *d_unc = h->unc_dev.as<UncRecord>();
+  return MSFL_OK;
+}
+// A host sink is copied like `info`; the caller synchronises afterwards (unc_host(h) tells it to).
+inline bool unc_host(const msfl_handle* h) { return h->unc_out && h->unc_mem == MSFL_MEM_HOST; }
+msfl_status unc_deliver(msfl_handle* h, int n, const UncRecord* d_unc) {
+  if (unc_host(h) && d_unc && n > 0)
+    HIPCHK(h, hipMemcpyAsync(h->unc_out, d_unc, (size_t)n * sizeof(UncRecord), hipMemcpyDeviceToHost, h->stream));
+  return MSFL_OK;
+}
 
 __global__ void __launch_bounds__(256) zero_ints_kernel(int* __restrict__ p, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -472,7 +506,8 @@ void s_launch_assoc(msfl_handle* h, const BatchView& bv_all, const double* d_pos
 msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner, const int* h_corner_off,
                                   const float4* d_surf, const int* h_surf_off, double* d_poses, int* d_status,
                                   DevMatchInfo* d_info, const DeskewView* deskew, int n_chunks = 1, const int* chunk_b = nullptr,
-                                  hipEvent_t* chunk_ev = nullptr, const std::function<hipError_t(int)>* enqueue_chunk = nullptr) {
+                                  hipEvent_t* chunk_ev = nullptr, const std::function<hipError_t(int)>* enqueue_chunk = nullptr,
+                                  UncRecord* d_unc = nullptr) {
   hipStream_t st = h->stream;
   // offsets -> device: [corner_off (B+1) | surf_off (B+1) | rec_off (B+1)]
   std::vector<int> offs(3 * (size_t)(B + 1));
@@ -519,6 +554,8 @@ msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner,
                          (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp);
     }
   }
+  launch_uncertainty<kLmBlock>(st, B, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr, h->records.as<double>(), d_poses, d_status,
+                               d_info, h->prm.outer_iterations - 1, sp, h->unc_min_eigenvalue, d_unc);
   HIPCHK(h, hipGetLastError());
   return MSFL_OK;
 }
@@ -642,7 +679,7 @@ void msfl_destroy(msfl_handle* h) {
   DevBuf* bufs[] = {&h->map_c.sorted, &h->map_c.cell_start, &h->map_s.sorted, &h->map_s.cell_start, &h->map_c.pos_of, &h->map_s.pos_of,
                     &h->map_c.gdesc, &h->map_s.gdesc, &h->map_c.bbox, &h->map_s.bbox, &h->in_corner,
                     &h->in_surf, &h->in_off, &h->poses, &h->status, &h->info, &h->records, &h->pprime, &h->nn,
-                    &h->idx_cell_of, &h->idx_count, &h->idx_scanned, &h->idx_bbox, &h->idx_cub, &h->idx_stage, &h->knn_count};
+                    &h->idx_cell_of, &h->idx_count, &h->idx_scanned, &h->idx_bbox, &h->idx_cub, &h->idx_stage, &h->knn_count, &h->unc_dev};
   for (auto* b : bufs) b->release();
   for (auto& b : h->dk) b.release();
   for (auto& b : h->ex) b.release();
@@ -673,6 +710,17 @@ msfl_status msfl_reset_stream(msfl_handle* h) {
 msfl_status msfl_synchronize(msfl_handle* h) {
   msfl_status s = enter(h); if (s) return s;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MSFL_OK;
+}
+
+msfl_status msfl_set_uncertainty(msfl_handle* h, msfl_match_uncertainty* out, int capacity, msfl_mem mem, double min_eigenvalue) {
+  msfl_status s = enter(h); if (s) return s;
+  if (out && (capacity < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE) || !(min_eigenvalue >= 0.0)))
+    return fail(h, MSFL_BAD_ARG, "msfl_set_uncertainty: capacity < 1, unknown memory kind or a negative / NaN min_eigenvalue");
+  h->unc_out = out;
+  h->unc_capacity = out ? capacity : 0;
+  h->unc_mem = mem;
+  h->unc_min_eigenvalue = out ? min_eigenvalue : 0.0;
   return MSFL_OK;
 }
 
@@ -763,7 +811,8 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
   if (B < 0 || (B > 0 && (!corner_off || !surf_off || !poses_io)))
     return fail(h, MSFL_BAD_ARG, "msfl_match_scan2map_batch: null argument");
   if (B == 0) return MSFL_OK;
-  msfl_status s = check_map(h); if (s) return s;
+  msfl_status s = unc_check(h, B, "msfl_match_scan2map"); if (s) return s;
+  s = check_map(h); if (s) return s;
   hipStream_t st = h->stream;
   const int c0 = corner_off[0], s0 = surf_off[0];
   const int ncp = corner_off[B] - c0, nsp = surf_off[B] - s0;
@@ -799,7 +848,9 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
   // patterns into it from the second replay on -- ROCm 7.2, tests/test_gpu_scan2map.py::test_the_batch_step_replays_from_a_captured_graph)
   hipLaunchKernelGGL(zero_ints_kernel, dim3(div_up(B, 256)), dim3(256), 0, st, d_status, B);
   DevMatchInfo* d_info = nullptr;
-  if (info) {
+  UncRecord* d_unc = nullptr;
+  s = unc_target(h, B, &d_unc); if (s) return s;
+  if (info || d_unc) {                    // the uncertainty record takes sigma2 from the solve's own final cost
     static_assert(sizeof(DevMatchInfo) == sizeof(msfl_match_info), "info layout");
     HIPCHK(h, h->info.reserve((size_t)B * sizeof(DevMatchInfo)));
     HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)B * sizeof(DevMatchInfo), st));
@@ -827,7 +878,7 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
     dvp = &dv;
   }
   if (n_chunks == 1) {
-    s = match_scan2map_device(h, B, d_corner, co.data(), d_surf, so.data(), d_poses, d_status, d_info, dvp);
+    s = match_scan2map_device(h, B, d_corner, co.data(), d_surf, so.data(), d_poses, d_status, d_info, dvp, 1, nullptr, nullptr, nullptr, d_unc);
     if (s) return s;
   } else {
     if (!h->copy_stream) {
@@ -857,7 +908,7 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
         return e;
       };
       s = match_scan2map_device(h, Bp, d_corner, co.data() + pb0, d_surf, so.data() + pb0, d_poses + 7 * (size_t)pb0, d_status + pb0,
-                                d_info ? d_info + pb0 : nullptr, nullptr, ns_p, sub_b, h->copy_ev, &enqueue_chunk);
+                                d_info ? d_info + pb0 : nullptr, nullptr, ns_p, sub_b, h->copy_ev, &enqueue_chunk, d_unc ? d_unc + pb0 : nullptr);
       if (s) return s;
     }
   }
@@ -866,7 +917,8 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
     if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
   }
   if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, (size_t)B * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
-  if (mem == MSFL_MEM_HOST || info) HIPCHK(h, hipStreamSynchronize(st));
+  s = unc_deliver(h, B, d_unc); if (s) return s;
+  if (mem == MSFL_MEM_HOST || info || unc_host(h)) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 
@@ -961,8 +1013,11 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
   if (n_corner < 0 || n_surf < 0 || !pose_io || (n_corner + n_surf > 0 && !records) || (n_corner && !corner) || (n_surf && !surf))
     return fail(h, MSFL_BAD_ARG, "msfl_solve_records: bad argument");
   const int n = n_corner + n_surf;
+  s = unc_check(h, 1, "msfl_solve_records"); if (s) return s;
   BatchView bv;
   s = stage_single(h, corner, n_corner, surf, n_surf, pose_io, bv); if (s) return s;
+  UncRecord* d_unc = nullptr;
+  s = unc_target(h, 1, &d_unc); if (s) return s;
   if (n) {
     HIPCHK(h, h->pprime.reserve((size_t)n * 6 * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(h->pprime.p, records, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -970,20 +1025,23 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
                        h->records.as<double>());
   }
   DevMatchInfo* d_info = nullptr;
-  if (info) {
+  if (info || d_unc) {
     HIPCHK(h, h->info.reserve(sizeof(DevMatchInfo)));
     HIPCHK(h, hipMemsetAsync(h->info.p, 0, sizeof(DevMatchInfo), h->stream));
     d_info = h->info.as<DevMatchInfo>();
   }
+  const SolverParams sp = solver_params(h->prm, 0);
   {
     ScopedTimer timer(h, T_SOLVE);
     hipLaunchKernelGGL(lm_solve_kernel<kLmBlock>, dim3(1), dim3(kLmBlock), 0, h->stream, bv, (const double*)nullptr,
-                       (const double*)h->records.as<double>(), h->poses.as<double>(), h->status.as<int>(), d_info, 0,
-                       solver_params(h->prm, 0));
+                       (const double*)h->records.as<double>(), h->poses.as<double>(), h->status.as<int>(), d_info, 0, sp);
   }
+  launch_uncertainty<kLmBlock>(h->stream, 1, bv, nullptr, h->records.as<double>(), h->poses.as<double>(), h->status.as<int>(), d_info, 0, sp,
+                               h->unc_min_eigenvalue, d_unc);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(pose_io, h->poses.p, 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, sizeof(DevMatchInfo), hipMemcpyDeviceToHost, h->stream));
+  s = unc_deliver(h, 1, d_unc); if (s) return s;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return MSFL_OK;
 }

@@ -84,6 +84,7 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
   if (P == 0) return MSFL_OK;
   // the segmented index build launches 2-D over (chunk, pair): HIP caps gridDim.y at 65 535 (ADVICE r04) — say so up front, before any staging
   if (P > 65535) return fail(h, MSFL_CAPACITY, "msfl_match_pairs_batch: at most 65535 pairs per call (got " + std::to_string(P) + "); split the batch");
+  s = unc_check(h, P, "msfl_match_pairs_batch"); if (s) return s;
   for (int p = 0; p < P; p++)
     if (map_corner_off[p + 1] < map_corner_off[p] || map_surf_off[p + 1] < map_surf_off[p] || corner_off[p + 1] < corner_off[p] || surf_off[p + 1] < surf_off[p])
       return fail(h, MSFL_BAD_ARG, "msfl_match_pairs_batch: offset arrays must be non-decreasing");
@@ -133,7 +134,9 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
   if (mem != MSFL_MEM_DEVICE || !status) { HIPCHK(h, h->status.reserve((size_t)P * sizeof(int))); d_status = h->status.as<int>(); }
   HIPCHK(h, h->pin.upload(d_status, st0.data(), (size_t)P * sizeof(int), st));
   DevMatchInfo* d_info = nullptr;
-  if (info) {
+  UncRecord* d_unc = nullptr;
+  s = unc_target(h, P, &d_unc); if (s) return s;
+  if (info || d_unc) {
     HIPCHK(h, h->info.reserve((size_t)P * sizeof(DevMatchInfo)));
     HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)P * sizeof(DevMatchInfo), st));
     d_info = h->info.as<DevMatchInfo>();
@@ -170,13 +173,16 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
     hipLaunchKernelGGL(lm_solve_kernel<kLmBlock>, dim3(P), dim3(kLmBlock), 0, st, bv, (const double*)nullptr, (const double*)h->records.as<double>(),
                        d_poses, d_status, d_info, it, sp);
   }
+  launch_uncertainty<kLmBlock>(st, P, bv, nullptr, h->records.as<double>(), d_poses, d_status, d_info, h->prm.outer_iterations - 1, sp,
+                               h->unc_min_eigenvalue, d_unc);
   HIPCHK(h, hipGetLastError());
   if (mem == MSFL_MEM_HOST) {
     HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)P * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, st));
   }
   if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, (size_t)P * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
-  if (mem == MSFL_MEM_HOST || info) HIPCHK(h, hipStreamSynchronize(st));
+  s = unc_deliver(h, P, d_unc); if (s) return s;
+  if (mem == MSFL_MEM_HOST || info || unc_host(h)) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 

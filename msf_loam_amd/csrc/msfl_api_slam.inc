@@ -35,7 +35,7 @@ struct SlamScanBuf {                    // everything derived from ONE scan that
 };
 
 constexpr int kSlamSlots = 4;
-struct SlamJob { int k, n, imu_mode; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
+struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
 constexpr int kSlamProfileSkip = 20;                    // MSFL_SLAM_HOST_PROFILE leaves the first scans (allocations) out
 #ifndef MSFL_SLAM_ODOM_LANES
 #define MSFL_SLAM_ODOM_LANES 64
@@ -72,6 +72,12 @@ struct msfl_slam_s {
   DevBuf map_c, map_s;                  // surrounded map clouds
   DevBuf rec[kSlamSlots];               // device result records
   PinBuf rec_host;                      // kSlamSlots records
+  // msfl_slam_set_uncertainty: two msfl_match_uncertainty per slot {odometry, mapping}; they travel with the slot's result copy
+  bool unc_on = false;
+  double unc_min_eigenvalue = 0.0;
+  DevBuf unc[kSlamSlots];
+  PinBuf unc_host;                      // kSlamSlots x 2 records
+  bool unc_held[kSlamSlots] = {};       // the scan in this slot was fed with the feature on
   hipEvent_t ev_done[kSlamSlots] = {};
   long long seq_c[kSlamSlots] = {}, seq_s[kSlamSlots] = {};   // map-store insert sequence numbers of the scan in each slot
   bool applied[kSlamSlots] = {};        // the slot's grid reports have been folded into the stores' host-side bounds
@@ -146,7 +152,8 @@ __global__ void slam_result_kernel(msfl_slam_result* __restrict__ r, int scan_in
 
 // MatchScan2Scan on device-resident clouds whose sizes live on the device: the column-grid path of scan2scan_batch_impl for
 // one pair, launches sized by the per-scan caps.  d_off = [ls | lf | sharp | flat | rec] offset pairs.
-msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamScanBuf& cur, const SlamCaps& caps, double* d_pose, DevMatchInfo* d_info) {
+msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamScanBuf& cur, const SlamCaps& caps, double* d_pose, DevMatchInfo* d_info,
+                          UncRecord* d_unc = nullptr, double unc_min_eig = 0.0) {
   hipStream_t st = h->stream;
   const int B = 1;
   const int* d_off = cur.odo_off.as<int>();
@@ -214,6 +221,8 @@ msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamSca
                          (const double*)h->records.as<double>(), d_pose, d_status, d_info, it, sp);
     }
   }
+  launch_uncertainty<kSlamOdomLmBlock>(st, B, bv, nullptr, h->records.as<double>(), d_pose, d_status, d_info, h->prm.outer_iterations - 1, sp,
+                                       unc_min_eig, d_unc);
   HIPCHK(h, hipGetLastError());
   return MSFL_OK;
 }
@@ -221,7 +230,8 @@ msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamSca
 // MatchScan2Map against the index in h->map_c / map_s, scan clouds and their (device-side) sizes given by in_off.
 // deskew != nullptr: the is_initialized branch (Deskew factors; dq / dp / V / G all device-side, pprime provided here).
 msfl_status scan2map_dyn(msfl_handle* h, const float4* d_corner, const float4* d_surf, const int* d_in_off, int cap_corner, int cap_surf,
-                         double* d_pose, int* d_status, DevMatchInfo* d_info, const DeskewView* deskew = nullptr) {
+                         double* d_pose, int* d_status, DevMatchInfo* d_info, const DeskewView* deskew = nullptr,
+                         UncRecord* d_unc = nullptr, double unc_min_eig = 0.0) {
   hipStream_t st = h->stream;
   const int n_rec_cap = cap_corner + cap_surf;
   HIPCHK(h, h->records.reserve(((size_t)4 * cap_surf + (size_t)6 * cap_corner + 8) * sizeof(double)));
@@ -246,6 +256,8 @@ msfl_status scan2map_dyn(msfl_handle* h, const float4* d_corner, const float4* d
     hipLaunchKernelGGL(lm_solve_kernel<kSlamLmBlock>, dim3(1), dim3(kSlamLmBlock), 0, st, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr,
                        (const double*)h->records.as<double>(), d_pose, d_status, d_info, it, sp);
   }
+  launch_uncertainty<kSlamLmBlock>(st, 1, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr, h->records.as<double>(), d_pose, d_status,
+                                   d_info, h->prm.outer_iterations - 1, sp, unc_min_eig, d_unc);
   HIPCHK(h, hipGetLastError());
   return MSFL_OK;
 }
@@ -360,6 +372,8 @@ void msfl_slam_destroy(msfl_slam* s) {
   for (DevBuf* d : {&s->chain, &s->vox_scratch, &s->vox_big, &s->meta, &s->map_c, &s->map_s}) d->release();
   for (auto& d : s->rec) d.release();
   s->rec_host.release();
+  for (auto& b : s->unc) b.release();
+  s->unc_host.release();
   for (auto e : s->ev_done) if (e) (void)hipEventDestroy(e);
   if (s->gc) msfl_grid_destroy(s->gc);
   if (s->gs) msfl_grid_destroy(s->gs);
@@ -458,6 +472,34 @@ msfl_status msfl_slam_get_result(msfl_slam* s, int scan_index, msfl_slam_result*
   SHIP(s, hipEventSynchronize(s->ev_done[slot]));
   { std::lock_guard<std::mutex> gl(s->mu_grid); slam_harvest(s, false); }
   *result = s->rec_host.as<msfl_slam_result>()[slot];
+  return MSFL_OK;
+}
+
+msfl_status msfl_slam_set_uncertainty(msfl_slam* s, int enabled, double min_eigenvalue) {
+  if (!s) return MSFL_BAD_ARG;
+  if (enabled && !(min_eigenvalue >= 0.0)) return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_uncertainty: negative or NaN min_eigenvalue");
+  SHIP(s, hipSetDevice(s->ho->device));
+  if (enabled && !s->unc_host.p) {
+    for (auto& b : s->unc) SHIP(s, b.reserve(2 * sizeof(UncRecord)));
+    SHIP(s, s->unc_host.reserve(kSlamSlots * 2 * sizeof(UncRecord)));
+  }
+  s->unc_on = enabled != 0;             // read once per msfl_slam_add_scan: scans already fed keep what they were fed with
+  s->unc_min_eigenvalue = enabled ? min_eigenvalue : 0.0;
+  return MSFL_OK;
+}
+
+msfl_status msfl_slam_get_uncertainty(msfl_slam* s, int scan_index, msfl_match_uncertainty* odometry, msfl_match_uncertainty* mapping) {
+  if (!s) return MSFL_BAD_ARG;
+  if (scan_index < 0 || scan_index >= s->n_scans || scan_index < s->n_scans - kSlamSlots)
+    return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_uncertainty: that scan's record is no longer (or not yet) held");
+  const int slot = scan_index % kSlamSlots;
+  if (!s->unc_held[slot]) return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_uncertainty: that scan was fed with msfl_slam_set_uncertainty off");
+  SHIP(s, hipSetDevice(s->ho->device));
+  { const msfl_status ws = slam_wait_mapped(s, scan_index); if (ws) return ws; }
+  SHIP(s, hipEventSynchronize(s->ev_done[slot]));
+  const msfl_match_uncertainty* u = s->unc_host.as<msfl_match_uncertainty>() + 2 * slot;
+  if (odometry) *odometry = u[0];
+  if (mapping) *mapping = u[1];
   return MSFL_OK;
 }
 
@@ -576,6 +618,7 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   };
   slam_harvest(s, false);
   msfl_slam_result* rec = s->rec[slot].as<msfl_slam_result>();
+  UncRecord* unc_map = jb.unc ? s->unc[slot].as<UncRecord>() + 1 : nullptr;
   const SlamImuDev* d_imu = cur.imu.as<SlamImuDev>();
   const int cap_ls = std::min(n, s->caps.less_sharp), cap_lf = std::min(n, s->caps.less_flat);
   double* chain = s->chain.as<double>();
@@ -628,10 +671,10 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
     dv.corner_dq = dq_c; dv.corner_dp = dp_c; dv.surf_dq = dq_s; dv.surf_dp = dp_s;
     dv.V = d_imu->velocity; dv.G_dev = d_imu->gravity;
     SCHK(s, hm, scan2map_dyn(hm, cur.vox_c.as<float4>(), cur.vox_s.as<float4>(), meta + META_OFF, cap_ls, n, pose_map,
-                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), &dv));
+                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), &dv, unc_map, jb.unc_min_eig));
   } else {
     SCHK(s, hm, scan2map_dyn(hm, cur.vox_c.as<float4>(), cur.vox_s.as<float4>(), meta + META_OFF, cap_ls, n, pose_map,
-                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping)));
+                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), nullptr, unc_map, jb.unc_min_eig));
   }
   hipLaunchKernelGGL(slam_map_pose_kernel, dim3(1), dim3(1), 0, sm, odom2map, (const double*)poses_k, pose_map, 1);          // TransformUpdate
   if (imu_mode == 2)    // DoUndistort (laser_mapping.cc:197-211) on the clouds InsertScan2Map is about to insert
@@ -658,6 +701,8 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
                      (const int*)cur.odo_status.as<int>());
   SHIP(s, hipGetLastError());
   SHIP(s, hipMemcpyAsync(s->rec_host.as<msfl_slam_result>() + slot, rec, sizeof(msfl_slam_result), hipMemcpyDeviceToHost, sm));
+  if (jb.unc)
+    SHIP(s, hipMemcpyAsync(s->unc_host.as<UncRecord>() + 2 * slot, s->unc[slot].p, 2 * sizeof(UncRecord), hipMemcpyDeviceToHost, sm));
   SHIP(s, hipEventRecord(s->ev_done[slot], sm));
   seg("record");
   s->applied[slot] = false;
@@ -705,6 +750,10 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   msfl_slam_result* rec = s->rec[slot].as<msfl_slam_result>();
   s->enqueueing = true;                 // from here on a failure leaves work of this scan on the streams: the pipeline is poisoned
   SHIP(s, hipMemsetAsync(rec, 0, sizeof(msfl_slam_result), so));
+  const bool unc = s->unc_on;
+  const double unc_min_eig = s->unc_min_eigenvalue;
+  s->unc_held[slot] = unc;
+  if (unc) SHIP(s, hipMemsetAsync(s->unc[slot].p, 0, 2 * sizeof(UncRecord), so));      // scan 0 has no odometry match, a closed gate no mapping match
   if (imu_mode != 0 || cur.imu_mode != 0) {
     // SlamImuDev header + [sum_dt n | delta_q 4n | delta_p 3n] in one copy (pinned ring slot: the caller's arrays are free on return)
     const size_t np = pre ? (size_t)pre->n : 0, head = offsetof(SlamImuDev, data) / sizeof(double);
@@ -777,7 +826,8 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   double* chain = s->chain.as<double>();
   double* poses_k = cur.poses.as<double>();
   if (k > 0) {                                                   // laser_odometry.cc:72-75: the first scan only initialises
-    SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, reinterpret_cast<DevMatchInfo*>(&rec->odometry)));
+    SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, reinterpret_cast<DevMatchInfo*>(&rec->odometry),
+                              unc ? s->unc[slot].as<UncRecord>() : nullptr, unc_min_eig));
   }
   hipLaunchKernelGGL(slam_odom_pose_kernel, dim3(1), dim3(1), 0, so, (const double*)chain, chain + 7, poses_k, poses_k + 14,
                      (const int*)cur.cnt.as<int>(), k == 0 ? 1 : 0);
@@ -790,7 +840,7 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
     s->host_wait_s += std::chrono::duration<double>(t_free - t_call).count();
     s->host_enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_free).count();
   }
-  const SlamJob job{k, n, imu_mode};
+  const SlamJob job{k, n, imu_mode, unc, unc_min_eig};
   if (s->threaded) {
     std::unique_lock<std::mutex> lk(s->mu);
     s->cv_done.wait(lk, [&] { return !s->has_job; });            // the mapping thread is at most one scan behind

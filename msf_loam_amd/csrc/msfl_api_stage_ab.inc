@@ -203,6 +203,7 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
                                  int* status, msfl_match_info* info, msfl_mem mem) {
   if (B < 0 || (B > 0 && (!c0 || !c1 || !c2 || !c3 || !poses_io))) return fail(h, MSFL_BAD_ARG, "msfl_match_scan2scan_batch: null argument");
   if (B == 0) return MSFL_OK;
+  { const msfl_status us = unc_check(h, B, "msfl_match_scan2scan"); if (us) return us; }
   const msfl_ring_cloud_batch* cl[4] = {c0, c1, c2, c3};
   hipStream_t st = h->stream;
   for (int k = 0; k < 4; k++) {
@@ -249,7 +250,9 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
   else { HIPCHK(h, h->od[OD_STATUS].reserve((size_t)B * sizeof(int))); d_status = h->od[OD_STATUS].as<int>(); }
   HIPCHK(h, hipMemsetAsync(d_status, 0, (size_t)B * sizeof(int), st));
   DevMatchInfo* d_info = nullptr;
-  if (info) {
+  UncRecord* d_unc = nullptr;
+  { const msfl_status us = unc_target(h, B, &d_unc); if (us) return us; }
+  if (info || d_unc) {
     HIPCHK(h, h->info.reserve((size_t)B * sizeof(DevMatchInfo)));
     HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)B * sizeof(DevMatchInfo), st));
     d_info = h->info.as<DevMatchInfo>();
@@ -337,13 +340,16 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
                          (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp);
     }
   }
+  launch_uncertainty<kOdomLmBlock>(st, B, bv, nullptr, h->records.as<double>(), d_poses, d_status, d_info, h->prm.outer_iterations - 1, sp,
+                                   h->unc_min_eigenvalue, d_unc);
   HIPCHK(h, hipGetLastError());
   if (mem == MSFL_MEM_HOST) {
     HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
   }
   if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, (size_t)B * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
-  if (mem == MSFL_MEM_HOST || info) HIPCHK(h, hipStreamSynchronize(st));
+  { const msfl_status us = unc_deliver(h, B, d_unc); if (us) return us; }
+  if (mem == MSFL_MEM_HOST || info || unc_host(h)) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 
