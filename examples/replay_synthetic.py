@@ -211,12 +211,13 @@ def world_drive(world, kind, n):
 
 
 def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=False, maps_out=None, quirks=False, imu=None, clouds_out=None,
-             uncertainty=None, unc_out=None):
+             uncertainty=None, unc_out=None, priors=None):
     """The same loop through the device-resident SLAM step (msfl_slam_add_scan): raw scan in, pose out, one
     synchronisation per scan (pipelined=False) or none until the record is fetched one scan later (pipelined=True: the
     odometry chain of scan k + 1 runs under the mapping chain of scan k, like the reference's two threads).
     uncertainty: a min_eigenvalue turns msfl_slam_set_uncertainty on; unc_out (a list) then receives per scan the (odometry, mapping)
     records of msfl_slam_get_uncertainty.
+    priors: per scan None or an (odometry, mapping) pair for msfl_slam_set_next_prior, each None or (pose7, sqrt_information 6 x 6).
     Returns (poses, records, wall-clock ms per scan over the scans after the second)."""
     from msf_loam_amd import capi
     n = len(poses_true)
@@ -237,6 +238,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
         if k == 2:
             t_start = time.perf_counter()
         im = imu[k] if imu is not None else None
+        if priors is not None and priors[k] is not None:
+            slam.set_next_prior(odometry=priors[k][0], mapping=priors[k][1])
         if pipelined:
             slam.add_scan(*scans[k], wait=False, imu=im)
             if k >= 1:

@@ -27,7 +27,10 @@
 //                                pose_estimate_map_scan2world, velocity)               mapping_scan_matcher.cc:61-278 (after :28-59)
 // and, for the covariance block of the odometry message (common/rigid_transform.h ToROS leaves it zero):
 //   msfl::adapter::SetUncertaintySink(h, &record, min_eigenvalue)  once;  msfl::adapter::CovarianceInParentFrame(pose, record, scale, out36)
+// and, where the reference's IMUFactor on the scan-to-map problem is commented out (mapping_scan_matcher.cc:84-94):
+//   msfl::adapter::SetPosePrior(h, &prior_record, predicted_pose, sqrt_information)  before MatchScan2Map;  ClearPosePrior(h) after
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -268,6 +271,58 @@ inline void UndistortCloud(msfl_handle* h, const IntegrationT& preintegration, C
 // registration per call on this side of the boundary, so a sink of one record); nullptr turns the output off again.
 inline void SetUncertaintySink(msfl_handle* h, msfl_match_uncertainty* record, double min_eigenvalue = 0.0) {
   Check(msfl_set_uncertainty(h, record, record ? 1 : 0, MSFL_MEM_HOST, min_eigenvalue), h, "msfl_set_uncertainty");
+}
+
+// ---- Gaussian prior on the pose of the handle's NEXT registrations (msfl_pose_prior; docs/kernels/prior.md): what the reference's
+// commented-out IMUFactor on the scan-to-map problem (mapping_scan_matcher.cc:84-94) was for.  `record` must outlive the handle's
+// matcher calls (the library keeps the pointer; one registration per call on this side, so one record); nullptr turns it off.
+// sqrt_information: row-major 6 x 6 L with information = L^T L, in the tangent order [dt, dtheta] of msfl_match_uncertainty; a
+// matrix type with operator()(i, j) (Eigen::Matrix<double, 6, 6>) or a flat row-major operator[](6 * i + j).
+template <class M, class = void>
+struct Mat6 {
+  static double Get(const M& m, int i, int j) { return static_cast<double>(m[static_cast<std::size_t>(6 * i + j)]); }
+};
+template <class M>
+struct Mat6<M, typename voider<decltype(std::declval<const M&>()(0, 0))>::type> {
+  static double Get(const M& m, int i, int j) { return static_cast<double>(m(i, j)); }
+};
+template <class RigidT, class M>
+inline void SetPosePrior(msfl_handle* h, msfl_pose_prior* record, const RigidT& mean, const M& sqrt_information) {
+  RigidToArray(mean, record->pose);
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j) record->sqrt_information[6 * i + j] = Mat6<M>::Get(sqrt_information, i, j);
+  Check(msfl_set_pose_prior(h, record, 1, MSFL_MEM_HOST), h, "msfl_set_pose_prior");
+}
+inline void ClearPosePrior(msfl_handle* h) { Check(msfl_set_pose_prior(h, nullptr, 0, MSFL_MEM_HOST), h, "msfl_set_pose_prior"); }
+
+// covariance (row-major 6 x 6, symmetric positive definite, tangent order [dt, dtheta]) -> L with L^T L = covariance^-1: the
+// inverse of the lower Cholesky factor C of the covariance (covariance = C C^T, so its inverse is C^-T C^-1).  Host side, a few
+// hundred flops.  Returns false (out untouched) when the matrix is not positive definite.
+inline bool SqrtInformationFromCovariance(const double covariance[36], double out[36]) {
+  double C[6][6] = {};
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double s = covariance[6 * i + j];
+      for (int k = 0; k < j; ++k) s -= C[i][k] * C[j][k];
+      if (i == j) {
+        if (!(s > 0.0)) return false;
+        C[i][i] = std::sqrt(s);
+      } else {
+        C[i][j] = s / C[j][j];
+      }
+    }
+  double L[6][6] = {};                                                   // L = C^-1, lower triangular, column by column
+  for (int j = 0; j < 6; ++j) {
+    L[j][j] = 1.0 / C[j][j];
+    for (int i = j + 1; i < 6; ++i) {
+      double s = 0.0;
+      for (int k = j; k < i; ++k) s -= C[i][k] * L[k][j];
+      L[i][j] = s / C[i][i];
+    }
+  }
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j) out[6 * i + j] = L[i][j];
+  return true;
 }
 
 // out (row-major 6 x 6) = scale * A * unc.covariance * A^T with A = diag(I, R(pose)): the tangent space of the solve rotates about

@@ -45,6 +45,7 @@ struct PointCloud {
 };
 
 using Vector3d = std::array<double, 3>;
+using Matrix6d = std::array<double, 36>;                               // row-major 6 x 6 (Eigen::Matrix<double, 6, 6> on the reference's side)
 
 // rigid_transform.h:36-128.  rotation stored [x y z w] like Eigen::Quaterniond::coeffs().
 class Rigid3d {
@@ -156,12 +157,27 @@ class ScanMatcher {
   void DisableUncertainty() { adapter::SetUncertaintySink(h_, nullptr); unc_ = msfl_match_uncertainty{}; }
   // The last Match* call's record (valid = 0, all zero: the output is off, or no solve ran in that call).
   const msfl_match_uncertainty& last_uncertainty() const { return unc_; }
+  // Opt-in: a Gaussian prior on the pose joins every solve of the later Match* calls until ClearPosePrior (msfl_pose_prior:
+  // residual L [t - t0 ; 2 vec(conj(q0) q)], no loss function; tangent order [dt, dtheta] like last_uncertainty().information).
+  // For MatchScan2Map the pose is the world pose (an IMU-predicted pose, a GPS fix), for MatchScan2Scan the relative one.
+  void SetPosePrior(const Rigid3d& mean, const Matrix6d& sqrt_information) { adapter::SetPosePrior(h_, &prior_, mean, sqrt_information); }
+  void ClearPosePrior() { adapter::ClearPosePrior(h_); }
 
  protected:
   msfl_handle* h_ = nullptr;
   msfl_match_info info_{};
   msfl_match_uncertainty unc_{};
+  msfl_pose_prior prior_{};
 };
+
+// L with L^T L = covariance^-1 for SetPosePrior (6 x 6 Cholesky of the inverse, host side); throws when `covariance` is not
+// positive definite.
+inline Matrix6d SqrtInformationFromCovariance(const Matrix6d& covariance) {
+  Matrix6d out{};
+  if (!adapter::SqrtInformationFromCovariance(covariance.data(), out.data()))
+    throw std::invalid_argument("SqrtInformationFromCovariance: the covariance is not positive definite");
+  return out;
+}
 
 using adapter::CovarianceInParentFrame;   // (pose, last_uncertainty(), scale, double out[36]) -> PoseWithCovariance::covariance
 

@@ -135,6 +135,20 @@ typedef struct msfl_match_uncertainty {
   int reserved_;
 } msfl_match_uncertainty;
 
+/* Optional Gaussian prior on the pose of one registration (opt-in: msfl_set_pose_prior / msfl_slam_set_next_prior): one more
+   6-row residual block of the solved problem, WITHOUT a loss function (docs/kernels/prior.md).  For the pose x = (t, q):
+     qe = conj(q0) * q, negated when qe.w < 0;   e = [t - t0 ; 2 * qe.xyz];   r = L e;   cost 1/2 |r|^2
+   and, in the tangent space of PoseLocalParameterization, J = L * blockdiag(I3, qe.w * I3 + skew(qe.xyz)).  The tangent order
+   [dt(3), dtheta(3)] and the body-frame rotation block are those of msfl_match_uncertainty.information: a Cholesky factor
+   (upper triangular R with R^T R = information, or any L with L^T L = the wanted information, any rank) of a previous
+   `information` or of an inverse covariance goes in unchanged.  The prior is not a correspondence: the min_correspondences gate
+   and the "no correspondence at all: pose untouched" rule do not see it.  A record whose 36 sqrt_information entries are all
+   zero is skipped: that registration is bit-identical to one without a prior. */
+typedef struct msfl_pose_prior {
+  double pose[7];              /* prior mean (t0, q0): x y z, then the UNIT quaternion x y z w */
+  double sqrt_information[36]; /* row-major 6 x 6 L; information = L^T L */
+} msfl_pose_prior;
+
 /* Accumulated GPU time per kernel class, measured with HIP events on the handle's stream
    (enabled by msfl_set_timing).  Used by bench.py for the live roofline figure. */
 typedef struct msfl_timing {
@@ -195,6 +209,19 @@ msfl_status msfl_get_timing(msfl_handle* h, msfl_timing* out, int reset);
    `covariance`.  Poses, statuses and `info` of every call are bit-identical with the feature on and off: one more kernel runs
    after the last solve and reads what the solve left behind. */
 msfl_status msfl_set_uncertainty(msfl_handle* h, msfl_match_uncertainty* out, int capacity, msfl_mem mem, double min_eigenvalue);
+
+/* Pose priors, off by default.  priors == NULL turns them off.  Otherwise priors[b] is part of the problem of registration b in
+   EVERY solve (both outer iterations) of every later matcher call on this handle (the calls msfl_set_uncertainty lists); a call
+   with more registrations than `count` returns MSFL_CAPACITY before it stages or launches anything (poses untouched).  The
+   pointer is kept, not the records: they are read at each call.
+     mem == MSFL_MEM_DEVICE : `priors` is a device pointer, read on the handle's stream at each call, nothing is synchronised;
+                              a record with a non-finite entry gives that registration the status MSFL_BAD_ARG (pose untouched).
+     mem == MSFL_MEM_HOST   : the records are copied at each call like the other host inputs; a non-finite entry makes the call
+                              return MSFL_BAD_ARG (msfl_last_error names the entry) before anything is staged.
+   initial_cost / final_cost of `info` include the prior's cost; n_edge / n_plane do not change.  With msfl_set_uncertainty on,
+   `information` is the posterior one (lidar J^T J + the prior's, at the returned pose) and n_residuals counts the six prior rows.
+   With the feature off, or for an all-zero record, every output is bit-identical to what it was without this call. */
+msfl_status msfl_set_pose_prior(msfl_handle* h, const msfl_pose_prior* priors, int count, msfl_mem mem);
 
 /* ------------------------------------------------------------------------------------------ */
 /* stage C — scan-to-local-map registration                                                   */
@@ -661,6 +688,13 @@ msfl_status msfl_slam_set_uncertainty(msfl_slam* s, int enabled, double min_eige
    mapping->valid == 0 when the gate (min_map_corner / min_map_surf) kept the match from running.  MSFL_BAD_ARG for a scan that
    was fed while the feature was off. */
 msfl_status msfl_slam_get_uncertainty(msfl_slam* s, int scan_index, msfl_match_uncertainty* odometry, msfl_match_uncertainty* mapping);
+
+/* Pose priors for the NEXT msfl_slam_add_scan[_imu] only (host pointers, copied here; either may be NULL = none):
+     odometry : on that scan's MatchScan2Scan, whose unknown is the RELATIVE pose pose_curr2last;
+     mapping  : on its scan-to-map solve, whose unknown is the WORLD pose pose_map (a GPS fix, an IMU-predicted pose).
+   The records travel with the scan that consumes them, so feeding further scans while that one is still queued is safe.
+   MSFL_BAD_ARG for a non-finite entry (nothing is changed then). */
+msfl_status msfl_slam_set_next_prior(msfl_slam* s, const msfl_pose_prior* odometry, const msfl_pose_prior* mapping);
 
 /* msfl_slam_config.keep_clouds: the clouds of scan `scan_index` (it must be one of the last TWO fed: the buffers belong to a set that
    the scan after next reuses).  Waits for that scan's chain.

@@ -29,6 +29,7 @@ EXPORTED = [
     "msfl_slam_default_config", "msfl_slam_create", "msfl_slam_destroy", "msfl_slam_add_scan", "msfl_slam_add_scan_imu", "msfl_slam_get_result", "msfl_slam_grids",
     "msfl_slam_last_error", "msfl_slam_get_clouds",
     "msfl_set_uncertainty", "msfl_slam_set_uncertainty", "msfl_slam_get_uncertainty",
+    "msfl_set_pose_prior", "msfl_slam_set_next_prior",
 ]
 
 
@@ -74,6 +75,25 @@ UNCERTAINTY_DTYPE = np.dtype([("information", np.float64, (6, 6)), ("eigenvalues
                               ("covariance", np.float64, (6, 6)), ("sigma2", np.float64), ("n_residuals", np.int32),
                               ("n_degenerate", np.int32), ("valid", np.int32), ("reserved_", np.int32)])
 assert UNCERTAINTY_DTYPE.itemsize == C.sizeof(MatchUncertainty)
+
+
+class PosePrior(C.Structure):
+    """msfl_pose_prior: prior mean (t0, q0 xyzw) and the row-major 6 x 6 square-root information L (information = L^T L)."""
+    _fields_ = [("pose", C.c_double * 7), ("sqrt_information", C.c_double * 36)]
+
+
+# the same record as a numpy structured dtype (Handle.set_pose_prior, Slam.set_next_prior)
+POSE_PRIOR_DTYPE = np.dtype([("pose", np.float64, (7,)), ("sqrt_information", np.float64, (6, 6))])
+assert POSE_PRIOR_DTYPE.itemsize == C.sizeof(PosePrior)
+
+
+def pose_priors(poses, sqrt_info):
+    """(B, 7) prior means and (B, 6, 6) square-root information matrices -> B records of POSE_PRIOR_DTYPE."""
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 7)
+    rec = np.zeros(len(poses), POSE_PRIOR_DTYPE)
+    rec["pose"] = poses
+    rec["sqrt_information"] = np.asarray(sqrt_info, dtype=np.float64).reshape(len(poses), 6, 6)
+    return rec
 
 
 class Timing(C.Structure):
@@ -270,6 +290,24 @@ class Handle:
         self._unc = None
         self._check(self.lib.msfl_set_uncertainty(self.h, _vp(ptr), C.c_int(int(capacity) if ptr is not None else 0), C.c_int(MEM_DEVICE),
                                                   C.c_double(float(min_eigenvalue))), "msfl_set_uncertainty(device)")
+
+    # ---- pose priors (msfl_set_pose_prior) ----
+    def set_pose_prior(self, poses, sqrt_info):
+        """priors[b] = (poses[b], sqrt_info[b]) joins the problem of registration b of every later matcher call.  The records
+        live in a host buffer owned by this object (the library reads it at each call)."""
+        rec = pose_priors(poses, sqrt_info)
+        self._check(self.lib.msfl_set_pose_prior(self.h, _vp(rec), C.c_int(len(rec)), C.c_int(MEM_HOST)), "msfl_set_pose_prior")
+        self._prior = rec
+
+    def set_pose_prior_device(self, ptr, count):
+        """Device-pointer variant: `ptr` (torch tensor / raw pointer) holds `count` records of POSE_PRIOR_DTYPE.itemsize bytes, read on
+        the handle's stream at each matcher call."""
+        self._check(self.lib.msfl_set_pose_prior(self.h, _vp(ptr), C.c_int(int(count)), C.c_int(MEM_DEVICE)), "msfl_set_pose_prior(device)")
+        self._prior = ptr
+
+    def clear_pose_prior(self):
+        self._check(self.lib.msfl_set_pose_prior(self.h, None, C.c_int(0), C.c_int(MEM_HOST)), "msfl_set_pose_prior")
+        self._prior = None
 
     # ---- stage C ----
     def set_map(self, corner, surf, n_corner=None, n_surf=None, mem=MEM_HOST):
@@ -702,6 +740,14 @@ class Slam:
         st = self.lib.msfl_slam_set_uncertainty(self.s, C.c_int(1 if enabled else 0), C.c_double(float(min_eigenvalue)))
         if st != OK:
             raise MsflError(st, "msfl_slam_set_uncertainty", self._err())
+
+    def set_next_prior(self, odometry=None, mapping=None):
+        """Pose priors for the NEXT add_scan only: each a (pose7, sqrt_information 6 x 6) pair or None.  `odometry` joins that scan's
+        scan-to-scan solve (relative pose), `mapping` its scan-to-map solve (world pose)."""
+        rec = [None if p is None else pose_priors(p[0], [p[1]]) for p in (odometry, mapping)]
+        st = self.lib.msfl_slam_set_next_prior(self.s, _vp(rec[0]), _vp(rec[1]))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_set_next_prior", self._err())
 
     def get_uncertainty(self, scan_index):
         """(odometry, mapping) records of one of the last four scans fed: a numpy structured array of two UNCERTAINTY_DTYPE records."""

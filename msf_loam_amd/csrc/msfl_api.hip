@@ -171,6 +171,11 @@ struct msfl_handle_s {
   msfl_mem unc_mem = MSFL_MEM_HOST;
   double unc_min_eigenvalue = 0.0;
   DevBuf unc_dev;                         // device staging of a host sink
+  // msfl_set_pose_prior: priors[b] joins the problem of registration b of every matcher call (null: feature off)
+  const msfl_pose_prior* prior_in = nullptr;
+  int prior_count = 0;
+  msfl_mem prior_mem = MSFL_MEM_HOST;
+  DevBuf prior_dev;                       // device staging of host records
 
   PinRing pin;
   PinBuf readback;
@@ -279,6 +284,37 @@ msfl_status unc_target(msfl_handle* h, int n, UncRecord** d_unc) {
   *d_unc = h->unc_dev.as<UncRecord>();
   return MSFL_OK;
 }
+// ---- msfl_set_pose_prior plumbing shared by every matcher entry point ----
+static_assert(sizeof(PosePrior) == sizeof(msfl_pose_prior), "pose prior record layout");
+// With unc_check, before anything is staged or launched: refuse a call with more registrations than there are records, and host
+// records with a non-finite entry (device records are checked by the solve kernel: per-scan status MSFL_BAD_ARG).
+msfl_status prior_check(msfl_handle* h, int n, const char* who) {
+  if (!h->prior_in) return MSFL_OK;
+  if (n > h->prior_count)
+    return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, msfl_set_pose_prior gave " +
+                                      std::to_string(h->prior_count) + " records");
+  if (h->prior_mem == MSFL_MEM_HOST) {
+    for (int b = 0; b < n; b++) {
+      const double* w = reinterpret_cast<const double*>(h->prior_in + b);
+      for (int k = 0; k < kPriorWords; k++)
+        if (!std::isfinite(w[k]))
+          return fail(h, MSFL_BAD_ARG, std::string(who) + ": the pose prior of registration " + std::to_string(b) + " has a non-finite entry (" +
+                                           (k < 7 ? "pose[" + std::to_string(k) : "sqrt_information[" + std::to_string(k - 7)) + "])");
+    }
+  }
+  return MSFL_OK;
+}
+// The records of this call on the device (null: feature off): the caller's device pointer, or a copy of its host records on stream st.
+msfl_status prior_target(msfl_handle* h, int n, hipStream_t st, const PosePrior** d_prior) {
+  *d_prior = nullptr;
+  if (!h->prior_in || n <= 0) return MSFL_OK;
+  if (h->prior_mem == MSFL_MEM_DEVICE) { *d_prior = reinterpret_cast<const PosePrior*>(h->prior_in); return MSFL_OK; }
+  HIPCHK(h, h->prior_dev.reserve((size_t)n * sizeof(PosePrior)));
+  HIPCHK(h, h->pin.upload(h->prior_dev.p, h->prior_in, (size_t)n * sizeof(PosePrior), st));
+  *d_prior = h->prior_dev.as<PosePrior>();
+  return MSFL_OK;
+}
+
 // A host sink is copied like `info`; the caller synchronises afterwards (unc_host(h) tells it to).
 inline bool unc_host(const msfl_handle* h) { return h->unc_out && h->unc_mem == MSFL_MEM_HOST; }
 msfl_status unc_deliver(msfl_handle* h, int n, const UncRecord* d_unc) {
@@ -507,7 +543,7 @@ msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner,
                                   const float4* d_surf, const int* h_surf_off, double* d_poses, int* d_status,
                                   DevMatchInfo* d_info, const DeskewView* deskew, int n_chunks = 1, const int* chunk_b = nullptr,
                                   hipEvent_t* chunk_ev = nullptr, const std::function<hipError_t(int)>* enqueue_chunk = nullptr,
-                                  UncRecord* d_unc = nullptr) {
+                                  UncRecord* d_unc = nullptr, const PosePrior* d_prior = nullptr) {
   hipStream_t st = h->stream;
   // offsets -> device: [corner_off (B+1) | surf_off (B+1) | rec_off (B+1)]
   std::vector<int> offs(3 * (size_t)(B + 1));
@@ -549,13 +585,12 @@ msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner,
     }
     {
       ScopedTimer timer(h, T_SOLVE);
-      hipLaunchKernelGGL(lm_solve_kernel<kLmBlock>, dim3(B), dim3(kLmBlock), 0, st, bv,
-                         deskew ? (const double*)dv.pprime : (const double*)nullptr,
-                         (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp);
+      launch_lm_solve<kLmBlock>(st, B, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr,
+                                (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp, d_prior);
     }
   }
   launch_uncertainty<kLmBlock>(st, B, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr, h->records.as<double>(), d_poses, d_status,
-                               d_info, h->prm.outer_iterations - 1, sp, h->unc_min_eigenvalue, d_unc);
+                               d_info, h->prm.outer_iterations - 1, sp, h->unc_min_eigenvalue, d_unc, d_prior);
   HIPCHK(h, hipGetLastError());
   return MSFL_OK;
 }
@@ -679,7 +714,7 @@ void msfl_destroy(msfl_handle* h) {
   DevBuf* bufs[] = {&h->map_c.sorted, &h->map_c.cell_start, &h->map_s.sorted, &h->map_s.cell_start, &h->map_c.pos_of, &h->map_s.pos_of,
                     &h->map_c.gdesc, &h->map_s.gdesc, &h->map_c.bbox, &h->map_s.bbox, &h->in_corner,
                     &h->in_surf, &h->in_off, &h->poses, &h->status, &h->info, &h->records, &h->pprime, &h->nn,
-                    &h->idx_cell_of, &h->idx_count, &h->idx_scanned, &h->idx_bbox, &h->idx_cub, &h->idx_stage, &h->knn_count, &h->unc_dev};
+                    &h->idx_cell_of, &h->idx_count, &h->idx_scanned, &h->idx_bbox, &h->idx_cub, &h->idx_stage, &h->knn_count, &h->unc_dev, &h->prior_dev};
   for (auto* b : bufs) b->release();
   for (auto& b : h->dk) b.release();
   for (auto& b : h->ex) b.release();
@@ -721,6 +756,16 @@ msfl_status msfl_set_uncertainty(msfl_handle* h, msfl_match_uncertainty* out, in
   h->unc_capacity = out ? capacity : 0;
   h->unc_mem = mem;
   h->unc_min_eigenvalue = out ? min_eigenvalue : 0.0;
+  return MSFL_OK;
+}
+
+msfl_status msfl_set_pose_prior(msfl_handle* h, const msfl_pose_prior* priors, int count, msfl_mem mem) {
+  msfl_status s = enter(h); if (s) return s;
+  if (priors && (count < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE)))
+    return fail(h, MSFL_BAD_ARG, "msfl_set_pose_prior: count < 1 or unknown memory kind");
+  h->prior_in = priors;
+  h->prior_count = priors ? count : 0;
+  h->prior_mem = mem;
   return MSFL_OK;
 }
 
@@ -812,6 +857,7 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
     return fail(h, MSFL_BAD_ARG, "msfl_match_scan2map_batch: null argument");
   if (B == 0) return MSFL_OK;
   msfl_status s = unc_check(h, B, "msfl_match_scan2map"); if (s) return s;
+  s = prior_check(h, B, "msfl_match_scan2map"); if (s) return s;
   s = check_map(h); if (s) return s;
   hipStream_t st = h->stream;
   const int c0 = corner_off[0], s0 = surf_off[0];
@@ -850,6 +896,8 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
   DevMatchInfo* d_info = nullptr;
   UncRecord* d_unc = nullptr;
   s = unc_target(h, B, &d_unc); if (s) return s;
+  const PosePrior* d_prior = nullptr;
+  s = prior_target(h, B, st, &d_prior); if (s) return s;
   if (info || d_unc) {                    // the uncertainty record takes sigma2 from the solve's own final cost
     static_assert(sizeof(DevMatchInfo) == sizeof(msfl_match_info), "info layout");
     HIPCHK(h, h->info.reserve((size_t)B * sizeof(DevMatchInfo)));
@@ -878,7 +926,7 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
     dvp = &dv;
   }
   if (n_chunks == 1) {
-    s = match_scan2map_device(h, B, d_corner, co.data(), d_surf, so.data(), d_poses, d_status, d_info, dvp, 1, nullptr, nullptr, nullptr, d_unc);
+    s = match_scan2map_device(h, B, d_corner, co.data(), d_surf, so.data(), d_poses, d_status, d_info, dvp, 1, nullptr, nullptr, nullptr, d_unc, d_prior);
     if (s) return s;
   } else {
     if (!h->copy_stream) {
@@ -908,7 +956,8 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
         return e;
       };
       s = match_scan2map_device(h, Bp, d_corner, co.data() + pb0, d_surf, so.data() + pb0, d_poses + 7 * (size_t)pb0, d_status + pb0,
-                                d_info ? d_info + pb0 : nullptr, nullptr, ns_p, sub_b, h->copy_ev, &enqueue_chunk, d_unc ? d_unc + pb0 : nullptr);
+                                d_info ? d_info + pb0 : nullptr, nullptr, ns_p, sub_b, h->copy_ev, &enqueue_chunk, d_unc ? d_unc + pb0 : nullptr,
+                                d_prior ? d_prior + pb0 : nullptr);
       if (s) return s;
     }
   }
@@ -1014,10 +1063,13 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
     return fail(h, MSFL_BAD_ARG, "msfl_solve_records: bad argument");
   const int n = n_corner + n_surf;
   s = unc_check(h, 1, "msfl_solve_records"); if (s) return s;
+  s = prior_check(h, 1, "msfl_solve_records"); if (s) return s;
   BatchView bv;
   s = stage_single(h, corner, n_corner, surf, n_surf, pose_io, bv); if (s) return s;
   UncRecord* d_unc = nullptr;
   s = unc_target(h, 1, &d_unc); if (s) return s;
+  const PosePrior* d_prior = nullptr;
+  s = prior_target(h, 1, h->stream, &d_prior); if (s) return s;
   if (n) {
     HIPCHK(h, h->pprime.reserve((size_t)n * 6 * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(h->pprime.p, records, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1033,11 +1085,11 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
   const SolverParams sp = solver_params(h->prm, 0);
   {
     ScopedTimer timer(h, T_SOLVE);
-    hipLaunchKernelGGL(lm_solve_kernel<kLmBlock>, dim3(1), dim3(kLmBlock), 0, h->stream, bv, (const double*)nullptr,
-                       (const double*)h->records.as<double>(), h->poses.as<double>(), h->status.as<int>(), d_info, 0, sp);
+    launch_lm_solve<kLmBlock>(h->stream, 1, bv, (const double*)nullptr, (const double*)h->records.as<double>(), h->poses.as<double>(),
+                              h->status.as<int>(), d_info, 0, sp, d_prior);
   }
   launch_uncertainty<kLmBlock>(h->stream, 1, bv, nullptr, h->records.as<double>(), h->poses.as<double>(), h->status.as<int>(), d_info, 0, sp,
-                               h->unc_min_eigenvalue, d_unc);
+                               h->unc_min_eigenvalue, d_unc, d_prior);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(pose_io, h->poses.p, 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, sizeof(DevMatchInfo), hipMemcpyDeviceToHost, h->stream));

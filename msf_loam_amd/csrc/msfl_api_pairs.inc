@@ -85,6 +85,7 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
   // the segmented index build launches 2-D over (chunk, pair): HIP caps gridDim.y at 65 535 (ADVICE r04) — say so up front, before any staging
   if (P > 65535) return fail(h, MSFL_CAPACITY, "msfl_match_pairs_batch: at most 65535 pairs per call (got " + std::to_string(P) + "); split the batch");
   s = unc_check(h, P, "msfl_match_pairs_batch"); if (s) return s;
+  s = prior_check(h, P, "msfl_match_pairs_batch"); if (s) return s;
   for (int p = 0; p < P; p++)
     if (map_corner_off[p + 1] < map_corner_off[p] || map_surf_off[p + 1] < map_surf_off[p] || corner_off[p + 1] < corner_off[p] || surf_off[p + 1] < surf_off[p])
       return fail(h, MSFL_BAD_ARG, "msfl_match_pairs_batch: offset arrays must be non-decreasing");
@@ -136,6 +137,8 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
   DevMatchInfo* d_info = nullptr;
   UncRecord* d_unc = nullptr;
   s = unc_target(h, P, &d_unc); if (s) return s;
+  const PosePrior* d_prior = nullptr;
+  s = prior_target(h, P, st, &d_prior); if (s) return s;
   if (info || d_unc) {
     HIPCHK(h, h->info.reserve((size_t)P * sizeof(DevMatchInfo)));
     HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)P * sizeof(DevMatchInfo), st));
@@ -170,11 +173,10 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
       }
     }
     ScopedTimer timer(h, T_SOLVE);
-    hipLaunchKernelGGL(lm_solve_kernel<kLmBlock>, dim3(P), dim3(kLmBlock), 0, st, bv, (const double*)nullptr, (const double*)h->records.as<double>(),
-                       d_poses, d_status, d_info, it, sp);
+    launch_lm_solve<kLmBlock>(st, P, bv, (const double*)nullptr, (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp, d_prior);
   }
   launch_uncertainty<kLmBlock>(st, P, bv, nullptr, h->records.as<double>(), d_poses, d_status, d_info, h->prm.outer_iterations - 1, sp,
-                               h->unc_min_eigenvalue, d_unc);
+                               h->unc_min_eigenvalue, d_unc, d_prior);
   HIPCHK(h, hipGetLastError());
   if (mem == MSFL_MEM_HOST) {
     HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)P * 7 * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -35,7 +35,7 @@ struct SlamScanBuf {                    // everything derived from ONE scan that
 };
 
 constexpr int kSlamSlots = 4;
-struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
+struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; bool prior_map; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
 constexpr int kSlamProfileSkip = 20;                    // MSFL_SLAM_HOST_PROFILE leaves the first scans (allocations) out
 #ifndef MSFL_SLAM_ODOM_LANES
 #define MSFL_SLAM_ODOM_LANES 64
@@ -78,6 +78,12 @@ struct msfl_slam_s {
   DevBuf unc[kSlamSlots];
   PinBuf unc_host;                      // kSlamSlots x 2 records
   bool unc_held[kSlamSlots] = {};       // the scan in this slot was fed with the feature on
+  // msfl_slam_set_next_prior: {odometry, mapping} records for the NEXT scan only.  They are copied to the slot of the scan that
+  // consumes them (on its odometry stream, ahead of ev_odo), so a later msfl_slam_add_scan cannot overwrite what a queued
+  // mapping chain has not read yet: a slot is reused only after its scan's record is out.
+  msfl_pose_prior next_prior[2] = {};
+  bool next_prior_set[2] = {};
+  DevBuf prior[kSlamSlots];
   hipEvent_t ev_done[kSlamSlots] = {};
   long long seq_c[kSlamSlots] = {}, seq_s[kSlamSlots] = {};   // map-store insert sequence numbers of the scan in each slot
   bool applied[kSlamSlots] = {};        // the slot's grid reports have been folded into the stores' host-side bounds
@@ -153,7 +159,7 @@ __global__ void slam_result_kernel(msfl_slam_result* __restrict__ r, int scan_in
 // MatchScan2Scan on device-resident clouds whose sizes live on the device: the column-grid path of scan2scan_batch_impl for
 // one pair, launches sized by the per-scan caps.  d_off = [ls | lf | sharp | flat | rec] offset pairs.
 msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamScanBuf& cur, const SlamCaps& caps, double* d_pose, DevMatchInfo* d_info,
-                          UncRecord* d_unc = nullptr, double unc_min_eig = 0.0) {
+                          UncRecord* d_unc = nullptr, double unc_min_eig = 0.0, const PosePrior* d_prior = nullptr) {
   hipStream_t st = h->stream;
   const int B = 1;
   const int* d_off = cur.odo_off.as<int>();
@@ -217,12 +223,12 @@ msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamSca
     {
       ScopedTimer timer(h, T_SOLVE);
       // one solve on an empty machine: the wide workgroup of the mapping solve (~570 records: one per thread and pass)
-      hipLaunchKernelGGL(lm_solve_kernel<kSlamOdomLmBlock>, dim3(B), dim3(kSlamOdomLmBlock), 0, st, bv, (const double*)nullptr,
-                         (const double*)h->records.as<double>(), d_pose, d_status, d_info, it, sp);
+      launch_lm_solve<kSlamOdomLmBlock>(st, B, bv, (const double*)nullptr, (const double*)h->records.as<double>(), d_pose, d_status, d_info, it, sp,
+                                        d_prior);
     }
   }
   launch_uncertainty<kSlamOdomLmBlock>(st, B, bv, nullptr, h->records.as<double>(), d_pose, d_status, d_info, h->prm.outer_iterations - 1, sp,
-                                       unc_min_eig, d_unc);
+                                       unc_min_eig, d_unc, d_prior);
   HIPCHK(h, hipGetLastError());
   return MSFL_OK;
 }
@@ -231,7 +237,7 @@ msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamSca
 // deskew != nullptr: the is_initialized branch (Deskew factors; dq / dp / V / G all device-side, pprime provided here).
 msfl_status scan2map_dyn(msfl_handle* h, const float4* d_corner, const float4* d_surf, const int* d_in_off, int cap_corner, int cap_surf,
                          double* d_pose, int* d_status, DevMatchInfo* d_info, const DeskewView* deskew = nullptr,
-                         UncRecord* d_unc = nullptr, double unc_min_eig = 0.0) {
+                         UncRecord* d_unc = nullptr, double unc_min_eig = 0.0, const PosePrior* d_prior = nullptr) {
   hipStream_t st = h->stream;
   const int n_rec_cap = cap_corner + cap_surf;
   HIPCHK(h, h->records.reserve(((size_t)4 * cap_surf + (size_t)6 * cap_corner + 8) * sizeof(double)));
@@ -253,11 +259,11 @@ msfl_status scan2map_dyn(msfl_handle* h, const float4* d_corner, const float4* d
     ScopedTimer timer(h, T_SOLVE);
     // one solve on an empty machine: 512 threads share its ~4 600 records (the batch kernel's 128 threads per solve are sized
     // for 1 024 concurrent solves); the per-thread summation order differs from the batch kernel's, the result by rounding
-    hipLaunchKernelGGL(lm_solve_kernel<kSlamLmBlock>, dim3(1), dim3(kSlamLmBlock), 0, st, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr,
-                       (const double*)h->records.as<double>(), d_pose, d_status, d_info, it, sp);
+    launch_lm_solve<kSlamLmBlock>(st, 1, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr, (const double*)h->records.as<double>(),
+                                  d_pose, d_status, d_info, it, sp, d_prior);
   }
   launch_uncertainty<kSlamLmBlock>(st, 1, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr, h->records.as<double>(), d_pose, d_status,
-                                   d_info, h->prm.outer_iterations - 1, sp, unc_min_eig, d_unc);
+                                   d_info, h->prm.outer_iterations - 1, sp, unc_min_eig, d_unc, d_prior);
   HIPCHK(h, hipGetLastError());
   return MSFL_OK;
 }
@@ -373,6 +379,7 @@ void msfl_slam_destroy(msfl_slam* s) {
   for (auto& d : s->rec) d.release();
   s->rec_host.release();
   for (auto& b : s->unc) b.release();
+  for (auto& b : s->prior) b.release();
   s->unc_host.release();
   for (auto e : s->ev_done) if (e) (void)hipEventDestroy(e);
   if (s->gc) msfl_grid_destroy(s->gc);
@@ -485,6 +492,26 @@ msfl_status msfl_slam_set_uncertainty(msfl_slam* s, int enabled, double min_eige
   }
   s->unc_on = enabled != 0;             // read once per msfl_slam_add_scan: scans already fed keep what they were fed with
   s->unc_min_eigenvalue = enabled ? min_eigenvalue : 0.0;
+  return MSFL_OK;
+}
+
+msfl_status msfl_slam_set_next_prior(msfl_slam* s, const msfl_pose_prior* odometry, const msfl_pose_prior* mapping) {
+  if (!s) return MSFL_BAD_ARG;
+  const msfl_pose_prior* in[2] = {odometry, mapping};
+  for (int a = 0; a < 2; a++) {
+    if (!in[a]) continue;
+    const double* w = reinterpret_cast<const double*>(in[a]);
+    for (int k = 0; k < kPriorWords; k++)
+      if (!std::isfinite(w[k]))
+        return sfail(s, MSFL_BAD_ARG, std::string("msfl_slam_set_next_prior: the ") + (a ? "mapping" : "odometry") + " prior has a non-finite entry");
+  }
+  SHIP(s, hipSetDevice(s->ho->device));
+  if ((odometry || mapping) && !s->prior[0].p)
+    for (auto& b : s->prior) SHIP(s, b.reserve(2 * sizeof(PosePrior)));
+  for (int a = 0; a < 2; a++) {
+    s->next_prior_set[a] = in[a] != nullptr;
+    if (in[a]) s->next_prior[a] = *in[a];
+  }
   return MSFL_OK;
 }
 
@@ -619,6 +646,7 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   slam_harvest(s, false);
   msfl_slam_result* rec = s->rec[slot].as<msfl_slam_result>();
   UncRecord* unc_map = jb.unc ? s->unc[slot].as<UncRecord>() + 1 : nullptr;
+  const PosePrior* prior_map = jb.prior_map ? s->prior[slot].as<PosePrior>() + 1 : nullptr;   // uploaded ahead of cur.ev_odo
   const SlamImuDev* d_imu = cur.imu.as<SlamImuDev>();
   const int cap_ls = std::min(n, s->caps.less_sharp), cap_lf = std::min(n, s->caps.less_flat);
   double* chain = s->chain.as<double>();
@@ -671,10 +699,10 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
     dv.corner_dq = dq_c; dv.corner_dp = dp_c; dv.surf_dq = dq_s; dv.surf_dp = dp_s;
     dv.V = d_imu->velocity; dv.G_dev = d_imu->gravity;
     SCHK(s, hm, scan2map_dyn(hm, cur.vox_c.as<float4>(), cur.vox_s.as<float4>(), meta + META_OFF, cap_ls, n, pose_map,
-                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), &dv, unc_map, jb.unc_min_eig));
+                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), &dv, unc_map, jb.unc_min_eig, prior_map));
   } else {
     SCHK(s, hm, scan2map_dyn(hm, cur.vox_c.as<float4>(), cur.vox_s.as<float4>(), meta + META_OFF, cap_ls, n, pose_map,
-                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), nullptr, unc_map, jb.unc_min_eig));
+                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), nullptr, unc_map, jb.unc_min_eig, prior_map));
   }
   hipLaunchKernelGGL(slam_map_pose_kernel, dim3(1), dim3(1), 0, sm, odom2map, (const double*)poses_k, pose_map, 1);          // TransformUpdate
   if (imu_mode == 2)    // DoUndistort (laser_mapping.cc:197-211) on the clouds InsertScan2Map is about to insert
@@ -754,6 +782,10 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   const double unc_min_eig = s->unc_min_eigenvalue;
   s->unc_held[slot] = unc;
   if (unc) SHIP(s, hipMemsetAsync(s->unc[slot].p, 0, 2 * sizeof(UncRecord), so));      // scan 0 has no odometry match, a closed gate no mapping match
+  // msfl_slam_set_next_prior: consumed by this scan, whatever becomes of it
+  const bool prior_odo = s->next_prior_set[0], prior_map = s->next_prior_set[1];
+  s->next_prior_set[0] = s->next_prior_set[1] = false;
+  if (prior_odo || prior_map) SHIP(s, ho->pin.upload(s->prior[slot].p, s->next_prior, 2 * sizeof(PosePrior), so));
   if (imu_mode != 0 || cur.imu_mode != 0) {
     // SlamImuDev header + [sum_dt n | delta_q 4n | delta_p 3n] in one copy (pinned ring slot: the caller's arrays are free on return)
     const size_t np = pre ? (size_t)pre->n : 0, head = offsetof(SlamImuDev, data) / sizeof(double);
@@ -827,7 +859,7 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   double* poses_k = cur.poses.as<double>();
   if (k > 0) {                                                   // laser_odometry.cc:72-75: the first scan only initialises
     SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, reinterpret_cast<DevMatchInfo*>(&rec->odometry),
-                              unc ? s->unc[slot].as<UncRecord>() : nullptr, unc_min_eig));
+                              unc ? s->unc[slot].as<UncRecord>() : nullptr, unc_min_eig, prior_odo ? s->prior[slot].as<PosePrior>() : nullptr));
   }
   hipLaunchKernelGGL(slam_odom_pose_kernel, dim3(1), dim3(1), 0, so, (const double*)chain, chain + 7, poses_k, poses_k + 14,
                      (const int*)cur.cnt.as<int>(), k == 0 ? 1 : 0);
@@ -840,7 +872,7 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
     s->host_wait_s += std::chrono::duration<double>(t_free - t_call).count();
     s->host_enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_free).count();
   }
-  const SlamJob job{k, n, imu_mode, unc, unc_min_eig};
+  const SlamJob job{k, n, imu_mode, unc, unc_min_eig, prior_map};
   if (s->threaded) {
     std::unique_lock<std::mutex> lk(s->mu);
     s->cv_done.wait(lk, [&] { return !s->has_job; });            // the mapping thread is at most one scan behind

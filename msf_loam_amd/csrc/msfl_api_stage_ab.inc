@@ -204,6 +204,7 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
   if (B < 0 || (B > 0 && (!c0 || !c1 || !c2 || !c3 || !poses_io))) return fail(h, MSFL_BAD_ARG, "msfl_match_scan2scan_batch: null argument");
   if (B == 0) return MSFL_OK;
   { const msfl_status us = unc_check(h, B, "msfl_match_scan2scan"); if (us) return us; }
+  { const msfl_status us = prior_check(h, B, "msfl_match_scan2scan"); if (us) return us; }
   const msfl_ring_cloud_batch* cl[4] = {c0, c1, c2, c3};
   hipStream_t st = h->stream;
   for (int k = 0; k < 4; k++) {
@@ -252,6 +253,8 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
   DevMatchInfo* d_info = nullptr;
   UncRecord* d_unc = nullptr;
   { const msfl_status us = unc_target(h, B, &d_unc); if (us) return us; }
+  const PosePrior* d_prior = nullptr;
+  { const msfl_status us = prior_target(h, B, st, &d_prior); if (us) return us; }
   if (info || d_unc) {
     HIPCHK(h, h->info.reserve((size_t)B * sizeof(DevMatchInfo)));
     HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)B * sizeof(DevMatchInfo), st));
@@ -336,12 +339,12 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
     }
     {
       ScopedTimer timer(h, T_SOLVE);
-      hipLaunchKernelGGL(lm_solve_kernel<kOdomLmBlock>, dim3(B), dim3(kOdomLmBlock), 0, st, bv, (const double*)nullptr,
-                         (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp);
+      launch_lm_solve<kOdomLmBlock>(st, B, bv, (const double*)nullptr, (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp,
+                                    d_prior);
     }
   }
   launch_uncertainty<kOdomLmBlock>(st, B, bv, nullptr, h->records.as<double>(), d_poses, d_status, d_info, h->prm.outer_iterations - 1, sp,
-                                   h->unc_min_eigenvalue, d_unc);
+                                   h->unc_min_eigenvalue, d_unc, d_prior);
   HIPCHK(h, hipGetLastError());
   if (mem == MSFL_MEM_HOST) {
     HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -1661,6 +1661,76 @@ __device__ __noinline__ int tr_decide(TrState& tr, const double* red, const Solv
 }
 
 
+// ---- optional Gaussian pose prior (msfl_set_pose_prior; docs/kernels/prior.md) ---------------------------------
+// One more residual block of the solved problem, WITHOUT a loss function: r = L e, e = [t - t0 ; 2 vec(conj(q0) q)]
+// (the quaternion taken with w >= 0), J = L blockdiag(I, w I + skew(v)) in the tangent of PoseLocalParameterization.
+struct PosePrior { double pose[7]; double sqrt_information[36]; };   // mirrors msfl_pose_prior
+// Code that only runs with a prior is tagged with a section name of its own.  The device link still produces one .text, but the
+// tag changes where the functions are emitted: prior_accumulate then lands behind lm_solve_kernel<128> instead of between
+// tr_decide and it, so the feature-off batch solve keeps its distance to tr_propose / tr_decide (checked with nm on the code
+// object of both commits).  MEASURED (docs/kernels/prior.md): with the sibling kernel emitted in front of lm_solve_kernel<128>,
+// the instruction-identical feature-off solve ran 1.2 % slower, from its place in the code object alone.
+#define MSFL_PRIOR_TEXT __attribute__((section(".text.msfl_prior")))
+constexpr int kPriorWords = (int)(sizeof(PosePrior) / sizeof(double));
+static_assert(kPriorWords == 43, "msfl_pose_prior layout");
+
+// Adds the prior's {cost, g[6], H[21]} at pose x to the packed sums in `red`.  Lane 0 only, serial (a few hundred
+// flops), called AFTER the block reduction of the lidar rows: the summation order is (lidar sum) + (prior sum), the
+// prior sum row by row, whatever the block width.  Shared by lm_solve_kernel's prior form and uncertainty_kernel's.
+__device__ __noinline__ MSFL_PRIOR_TEXT void prior_accumulate(const pose7 x, const PosePrior* prior, double* red) {
+  const double* p0 = prior->pose;
+  const double* L = prior->sqrt_information;
+  quat qc; qc.x = -p0[3]; qc.y = -p0[4]; qc.z = -p0[5]; qc.w = p0[6];
+  quat qe = quat_mul(qc, x.q);
+  if (qe.w < 0.0) { qe.x = -qe.x; qe.y = -qe.y; qe.z = -qe.z; qe.w = -qe.w; }
+  const double e[6] = {x.t.x - p0[0], x.t.y - p0[1], x.t.z - p0[2], 2.0 * qe.x, 2.0 * qe.y, 2.0 * qe.z};
+  // rotation block of d e / d delta at delta = 0: w I + skew(v)
+  const double M[3][3] = {{qe.w, -qe.z, qe.y}, {qe.z, qe.w, -qe.x}, {-qe.y, qe.x, qe.w}};
+  double s[kAcc];
+#pragma unroll
+  for (int k = 0; k < kAcc; k++) s[k] = 0.0;
+  for (int i = 0; i < 6; i++) {
+    double l[6], j[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) l[k] = L[6 * i + k];
+    double r = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) r += l[k] * e[k];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      j[c] = l[c];
+      j[3 + c] = l[3] * M[0][c] + l[4] * M[1][c] + l[5] * M[2][c];
+    }
+    s[0] += r * r;
+#pragma unroll
+    for (int k = 0; k < 6; k++) s[1 + k] += j[k] * r;
+    int n = 7;
+#pragma unroll
+    for (int p = 0; p < 6; p++)
+#pragma unroll
+      for (int q = p; q < 6; q++) s[n++] += j[p] * j[q];
+  }
+  red[0] += 0.5 * s[0];
+#pragma unroll
+  for (int k = 1; k < kAcc; k++) red[k] += s[k];
+}
+
+// Registration b's prior record -> LDS (43 lanes, plain loads).  Every thread of the workgroup calls this.
+// bad: some entry is not finite; use: some sqrt_information entry is non-zero (an all-zero record is SKIPPED, not added).
+template <int BLOCK>
+__device__ __forceinline__ void prior_stage(const PosePrior* __restrict__ src, PosePrior& dst, int& bad, int& use) {
+  static_assert(BLOCK >= 64, "43 lanes stage the record");
+  int my_bad = 0, my_use = 0;
+  if (threadIdx.x < kPriorWords) {
+    const double v = reinterpret_cast<const double*>(src)[threadIdx.x];
+    reinterpret_cast<double*>(&dst)[threadIdx.x] = v;
+    my_bad = !isfinite(v);
+    my_use = threadIdx.x >= 7 && v != 0.0;
+  }
+  bad = __syncthreads_or(my_bad);
+  use = __syncthreads_or(my_use);
+}
+
 // One workgroup per scan, persistent over all trust-region iterations of one ceres::Solve.
 // Lane 0 runs the (serial, tiny) trust-region logic between evaluation passes; every pass
 // evaluates cost AND the normal equations at the candidate, so an accepted step needs no second
@@ -1673,122 +1743,30 @@ __global__ void __launch_bounds__(BLOCK, MSFL_LM_WAVES)
 lm_solve_kernel(BatchView bv, const double* __restrict__ pprime_all, const double* __restrict__ rec_all,
                 double* __restrict__ poses, int* __restrict__ status, DevMatchInfo* __restrict__ info,
                 int outer_it, SolverParams prm) {
-  __shared__ LmShared<BLOCK> sh;
-  __shared__ PlaneCache<BLOCK> s_cache;
-  __shared__ EdgeList s_edges;
-  const int b = blockIdx.x;
-  if (status[b] != 0) return;
-  if (threadIdx.x < kEdgeListMax / 32) s_edges.mask[threadIdx.x] = 0;
-  __syncthreads();
-  const int nc = bv.corner_off[b + 1] - bv.corner_off[b];
-  const int ns = bv.surf_off[b + 1] - bv.surf_off[b];
-  const float4* corner = bv.corner + bv.corner_off[b];
-  const float4* surf = bv.surf + bv.surf_off[b];
-  const size_t r0 = (size_t)bv.rec_off[b];
-  const double* rec = rec_all + edge_rec_off(bv, bv.corner_off[b]);
-  const double* recp = rec_all + plane_rec_off(bv, bv.surf_off[b]);
-  const double* pprime = pprime_all ? pprime_all + 3 * r0 : nullptr;
-  double* pose_g = poses + 7 * (size_t)b;
-  TrState& tr = sh.tr;
-  LM_T(t_begin);
-  {
-    double acc[kAcc];
-    int ne, np;
-    const pose7 T = load_pose(pose_g);
-    LM_T(t0);
-    evaluate_pass<BLOCK, true>(T, prm.huber, corner, nc, surf, ns, pprime, rec, recp, s_cache, s_edges, acc, ne, np);
-    LM_T(t1);
-    block_reduce<BLOCK>(sh, acc, ne, np);
-    LM_T(t2);
-    LM_ADD(0, t1 - t0); LM_ADD(1, t2 - t1); LM_ADD(4, 1);
-  }
-  LM_T(t_s0);
-  // mask -> index list (32 lanes of wavefront 0, one mask word each; ascending index order, so the list and with it the
-  // summation order of the later passes is a function of the records alone)
-  if (threadIdx.x < kEdgeListMax / 32) {
-    unsigned m = s_edges.mask[threadIdx.x];
-    const int c = __popc(m);
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) { const int v = __shfl_up(incl, o); if ((int)threadIdx.x >= o) incl += v; }
-    int at = incl - c;
-    while (m) { const int bit = __ffs((int)m) - 1; s_edges.idx[at++] = (unsigned short)(32 * threadIdx.x + bit); m &= m - 1; }
-    if (threadIdx.x == kEdgeListMax / 32 - 1) s_edges.n = incl;
-  }
-  if (threadIdx.x == 0) {
-    const int n_edge = sh.cnt[0], n_plane = sh.cnt[1];
-    int go = 1;
-    if (info) { info[b].n_edge[outer_it] = n_edge; info[b].n_plane[outer_it] = n_plane; }
-    tr.cost = 0.0; tr.iteration = 0; tr.successful = 0;
-    if (n_edge + n_plane < prm.min_correspondences) {
-      status[b] = 1;                       // MSFL_TOO_FEW_CORRESPONDENCES (odometry_scan_matcher.cc:262-267)
-      if (info) info[b].status = 1;
-      go = 0;
-    } else if (n_edge + n_plane == 0) {
-      go = 0;                              // Ceres: empty problem, parameters untouched
-    } else {
-#pragma unroll
-      for (int k = 0; k < kAcc; k++) tr.sys[k] = sh.red[k];
-#pragma unroll
-      for (int i = 0; i < 7; i++) tr.x[i] = pose_g[i];
-      tr.cost = sh.red[0];
-      if (info) info[b].initial_cost[outer_it] = tr.cost;
-      // jacobi_scaling from iteration 0: 1 / (1 + sqrt(diag(J^T J)))
-      const int dg[6] = {7, 13, 18, 22, 25, 27};   // packed positions of H[i][i]
-#pragma unroll
-      for (int i = 0; i < 6; i++) tr.scale[i] = 1.0 / (1.0 + sqrt(sh.red[dg[i]]));
-      const pose7 x = load_pose(tr.x);
-      tr.gmax = gradient_max_norm_for_test(x, tr.sys + 1, prm.gtol);
-      tr.x_norm = pose_norm(x);
-      tr.radius = prm.radius0; tr.decrease_factor = 2.0; tr.model_cost_change = 0.0;
-      tr.invalid = 0; tr.reuse_diagonal = 0; tr.step_ok = 1;
-      go = tr_propose(tr, prm);
-    }
-    sh.go = go;
-  }
-  __syncthreads();
-  LM_T(t_s1);
-  LM_ADD(2, t_s1 - t_s0);
-  bool solved = (sh.cnt[0] + sh.cnt[1] >= prm.min_correspondences) && (sh.cnt[0] + sh.cnt[1] > 0);
-  while (sh.go) {
-    double acc[kAcc];
-    int ne, np;
-    const pose7 T = load_pose(tr.cand);   // lane 0 overwrites go / cand only after the reduction's barrier, which every
-                                           // thread reaches after this read: no barrier of its own needed
-    LM_T(t0);
-    evaluate_pass<BLOCK, false>(T, prm.huber, corner, nc, surf, ns, pprime, rec, recp, s_cache, s_edges, acc, ne, np);
-    LM_T(t1);
-    block_reduce<BLOCK>(sh, acc, ne, np);
-    LM_T(t2);
-#ifdef MSFL_LM_PROFILE
-    if (threadIdx.x == 0) {
-      const unsigned long long c0 = wall_clock64();
-      const int cont = tr_decide(tr, sh.red, prm);
-      const unsigned long long c1 = wall_clock64();
-      sh.go = cont ? tr_propose(tr, prm) : 0;
-      const unsigned long long c2 = wall_clock64();
-      atomicAdd(&g_lm_prof[6], c1 - c0); atomicAdd(&g_lm_prof[7], c2 - c1);
-    }
-#else
-    if (threadIdx.x == 0) sh.go = tr_decide(tr, sh.red, prm) ? tr_propose(tr, prm) : 0;
-#endif
-    __syncthreads();
-    LM_T(t3);
-    LM_ADD(0, t1 - t0); LM_ADD(1, t2 - t1); LM_ADD(2, t3 - t2); LM_ADD(4, 1);
-  }
-  LM_T(t_end);
-  LM_ADD(3, t_end - t_begin); LM_ADD(5, 1);
-  if (threadIdx.x == 0) {
-    if (solved) {
-#pragma unroll
-      for (int i = 0; i < 7; i++) pose_g[i] = tr.x[i];
-    }
-    if (info) {
-      info[b].lm_iterations[outer_it] = tr.iteration;
-      info[b].lm_successful[outer_it] = tr.successful;
-      info[b].final_cost[outer_it] = tr.cost;
-    }
-  }
+#define MSFL_LM_PRIOR 0
+#include "msfl_lm_solve_body.inc"
+#undef MSFL_LM_PRIOR
+}
+
+// The sibling with the pose prior: prior_all[b] is one more residual block of registration b's problem.
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK, MSFL_LM_WAVES) MSFL_PRIOR_TEXT
+lm_solve_prior_kernel(BatchView bv, const double* __restrict__ pprime_all, const double* __restrict__ rec_all,
+                      double* __restrict__ poses, int* __restrict__ status, DevMatchInfo* __restrict__ info,
+                      int outer_it, SolverParams prm, const PosePrior* __restrict__ prior_all) {
+#define MSFL_LM_PRIOR 1
+#include "msfl_lm_solve_body.inc"
+#undef MSFL_LM_PRIOR
+}
+
+// The one launch helper of all six solve sites: `prior` null = feature off, the kernel that was always launched.
+template <int BLOCK>
+inline void launch_lm_solve(hipStream_t st, int n_scans, const BatchView& bv, const double* pprime, const double* records, double* poses,
+                            int* status, DevMatchInfo* info, int outer_it, const SolverParams& sp, const PosePrior* prior) {
+  if (!prior)
+    hipLaunchKernelGGL(lm_solve_kernel<BLOCK>, dim3(n_scans), dim3(BLOCK), 0, st, bv, pprime, records, poses, status, info, outer_it, sp);
+  else
+    hipLaunchKernelGGL(lm_solve_prior_kernel<BLOCK>, dim3(n_scans), dim3(BLOCK), 0, st, bv, pprime, records, poses, status, info, outer_it, sp, prior);
 }
 
 }  // namespace msfl
