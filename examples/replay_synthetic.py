@@ -110,8 +110,13 @@ def synthetic_imu(poses_true, switch_at=50, seed=synth.SEED + 900, samples=45):
     return out
 
 
-def run(backend, world, poses_true, verbose=False, maps_out=None, scans=None, quirks=False, imu=None, clouds_out=None):
-    """quirks: FilterLessFlatLessCornerFeature as the reference executes it (laser_mapping.cc:340-364: the surf cloud cut to its first
+def run(backend, world, poses_true, verbose=False, maps_out=None, scans=None, quirks=False, imu=None, clouds_out=None, new_grids=None,
+        map_window=None, window_out=None):
+    """new_grids: a factory of the two map stores (corner, surf) to use instead of backend.new_grids().
+    map_window: (half_cells, every_n_scans) -> both stores are cropped (their crop(center, half_cells)) around the translation of
+    pose_map after the inserts of every every_n_scans-th scan, like msfl_slam_set_map_window; window_out (a list) then receives per
+    scan the (corner, surf) crop infos or None.
+    quirks: FilterLessFlatLessCornerFeature as the reference executes it (laser_mapping.cc:340-364: the surf cloud cut to its first
     n_less_sharp points).  imu: per-scan dicts (synthetic_imu) -> UndistortScan before the match while not initialised
     (:170-176), the is_initialized matcher branch + DoUndistort before the insert afterwards (:197-211); needs a backend with
     undistort / deskew / scan2map_deskew (the oracle backend of the tests)."""
@@ -123,7 +128,7 @@ def run(backend, world, poses_true, verbose=False, maps_out=None, scans=None, qu
     odo2first = np.array([0, 0, 0, 0, 0, 0, 1.0])        # pose_scan2world_ (odometry frame = first scan)
     curr2last = np.array([0, 0, 0, 0, 0, 0, 1.0])
     odom2map = poses_true[0].copy()                       # anchor the map frame at the true first pose
-    grid_c, grid_s = backend.new_grids()                  # hybrid_grid_map_corner_ / hybrid_grid_map_surf_
+    grid_c, grid_s = new_grids() if new_grids is not None else backend.new_grids()   # hybrid_grid_map_corner_ / hybrid_grid_map_surf_
     last = None
     est, t_stage = [], dict(extract=0.0, odometry=0.0, voxel=0.0, surround=0.0, mapping=0.0, insert=0.0)
     for k in range(n):
@@ -174,6 +179,12 @@ def run(backend, world, poses_true, verbose=False, maps_out=None, scans=None, qu
                                    flat=f["flat"], less_flat=f["less_flat"]))
         grid_c.insert_scan(transform_(pose_map, ls))                          # InsertScan2Map, laser_mapping.cc:330-338
         grid_s.insert_scan(transform_(pose_map, lf))
+        if map_window is not None:                                            # the windowed local map: forget what lies outside
+            infos = None
+            if (k + 1) % map_window[1] == 0:
+                infos = (grid_c.crop(pose_map[:3], map_window[0]), grid_s.crop(pose_map[:3], map_window[0]))
+            if window_out is not None:
+                window_out.append(infos)
         t5 = time.perf_counter()
         last = f
         est.append(pose_map)
@@ -211,13 +222,15 @@ def world_drive(world, kind, n):
 
 
 def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=False, maps_out=None, quirks=False, imu=None, clouds_out=None,
-             uncertainty=None, unc_out=None, priors=None):
+             uncertainty=None, unc_out=None, priors=None, map_window=None, window_out=None, slam_hook=None):
     """The same loop through the device-resident SLAM step (msfl_slam_add_scan): raw scan in, pose out, one
     synchronisation per scan (pipelined=False) or none until the record is fetched one scan later (pipelined=True: the
     odometry chain of scan k + 1 runs under the mapping chain of scan k, like the reference's two threads).
     uncertainty: a min_eigenvalue turns msfl_slam_set_uncertainty on; unc_out (a list) then receives per scan the (odometry, mapping)
     records of msfl_slam_get_uncertainty.
     priors: per scan None or an (odometry, mapping) pair for msfl_slam_set_next_prior, each None or (pose7, sqrt_information 6 x 6).
+    map_window: (half_cells, every_n_scans) for msfl_slam_set_map_window; window_out (a list) then receives per scan the (corner, surf)
+    records of msfl_slam_get_map_window.  slam_hook(slam, k): called before scan k is fed.
     Returns (poses, records, wall-clock ms per scan over the scans after the second)."""
     from msf_loam_amd import capi
     n = len(poses_true)
@@ -232,12 +245,17 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     if uncertainty is not None:
         slam.set_uncertainty(True, uncertainty)
     want_unc = uncertainty is not None and unc_out is not None
+    if map_window is not None:
+        slam.set_map_window(map_window[0], map_window[1])
+    want_win = window_out is not None
     recs = [None] * n
     t_start = None
     for k in range(n):
         if k == 2:
             t_start = time.perf_counter()
         im = imu[k] if imu is not None else None
+        if slam_hook is not None:
+            slam_hook(slam, k)
         if priors is not None and priors[k] is not None:
             slam.set_next_prior(odometry=priors[k][0], mapping=priors[k][1])
         if pipelined:
@@ -246,12 +264,16 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
                 recs[k - 1] = slam.result(k - 1)
                 if want_unc:
                     unc_out.append(slam.get_uncertainty(k - 1))
+                if want_win:
+                    window_out.append(slam.get_map_window(k - 1))
                 if clouds_out is not None:
                     clouds_out.append(slam.clouds(k - 1))
         else:
             recs[k] = slam.add_scan(*scans[k], imu=im)
             if want_unc:
                 unc_out.append(slam.get_uncertainty(k))
+            if want_win:
+                window_out.append(slam.get_map_window(k))
             if clouds_out is not None:
                 clouds_out.append(slam.clouds(k))
         if verbose and k % 50 == 0 and recs[max(k - 1, 0)] is not None:
@@ -261,6 +283,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
         recs[n - 1] = slam.result(n - 1)
         if want_unc:
             unc_out.append(slam.get_uncertainty(n - 1))
+        if want_win:
+            window_out.append(slam.get_map_window(n - 1))
         if clouds_out is not None:
             clouds_out.append(slam.clouds(n - 1))
     wall = time.perf_counter() - t_start if t_start is not None else 0.0
@@ -292,7 +316,16 @@ def main():
     ap.add_argument("--uncertainty", type=float, nargs="?", const=150.0, default=None, metavar="MIN_EIGENVALUE",
                     help="msfl_slam_set_uncertainty: print per scan the smallest eigenvalue of the mapping solve's information matrix, n_degenerate "
                          "at this threshold (default 150) and the weakest direction [dt(3), dtheta(3)]")
+    ap.add_argument("--map-window", default=None, metavar="HX,HY,HZ[,N]",
+                    help="msfl_slam_set_map_window: crop both map stores to +-HX,HY,HZ cells around the pose after every N-th scan (default 1); "
+                         "23,23,23 is the smallest window that takes nothing from the registration of the scan at its centre")
     args = ap.parse_args()
+    map_window = None
+    if args.map_window:
+        w = [int(v) for v in args.map_window.split(",")]
+        if len(w) not in (3, 4):
+            ap.error("--map-window takes HX,HY,HZ[,N]")
+        map_window = (tuple(w[:3]), w[3] if len(w) == 4 else 1)
     if args.world == "room":
         world = synth.World(ground_half=45.0)
         truth = trajectory(args.scans)
@@ -312,7 +345,7 @@ def main():
     unc = []
     est, recs, ms = run_slam(world, truth, pipelined=args.mode == "slam-pipelined", scans=scans, quirks=args.reference_quirks,
                              imu=synthetic_imu(truth) if args.imu else None, clouds_out=[] if args.keep_clouds else None,
-                             uncertainty=args.uncertainty, unc_out=unc)
+                             uncertainty=args.uncertainty, unc_out=unc, map_window=map_window)
     for k, u in enumerate(unc):
         m = u[1]
         if m["valid"]:
@@ -323,6 +356,7 @@ def main():
     if args.dump_poses:
         np.save(args.dump_poses, est)
     print(json.dumps({"mode": args.mode, "world": args.world, "beams": args.beams, "keep_clouds": bool(args.keep_clouds), "scans": args.scans, "reference_quirks": bool(args.reference_quirks), "imu": bool(args.imu),
+                      "map_window": args.map_window,
                       "ate_rmse_m": ate(est, truth),
                       "final_error_m_rad": synth.pose_error(est[-1], truth[-1]), "ms_per_scan_end_to_end": ms,
                       "scans_per_s": 1e3 / ms if ms else None,

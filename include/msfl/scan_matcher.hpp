@@ -326,6 +326,22 @@ class HybridGrid {
     adapter::InsertScan(h_, g_, *scan);
   }
 
+  // Not in the reference (its HybridGrid never removes a cell): forget every cell further than half_cells cells from the cell of
+  // `center` (msfl_grid_crop).  evicted != nullptr receives the removed points, cells ascending, as msfl_grid_dump would have
+  // delivered them.
+  msfl_grid_crop_info Crop(const std::array<double, 3>& center, const std::array<int, 3>& half_cells, std::vector<msfl_point>* evicted = nullptr) {
+    msfl_grid_crop_info info{};
+    int n_points = 0;
+    if (evicted) {
+      detail::Check(msfl_grid_size(g_, &n_points, nullptr), h_, "msfl_grid_size");
+      evicted->resize(static_cast<std::size_t>(n_points));
+    }
+    detail::Check(msfl_grid_crop(g_, center.data(), half_cells.data(), evicted ? evicted->data() : nullptr, n_points, MSFL_MEM_HOST, &info), h_,
+                  "msfl_grid_crop");
+    if (evicted) evicted->resize(static_cast<std::size_t>(info.n_points_evicted));
+    return info;
+  }
+
  private:
   msfl_handle* h_ = nullptr;
   msfl_grid* g_ = nullptr;
@@ -388,6 +404,18 @@ class LaserSlam {
   void EnableUncertainty(double min_eigenvalue = 0.0) {
     const msfl_status st = msfl_slam_set_uncertainty(s_, 1, min_eigenvalue);
     if (st != MSFL_OK) throw std::runtime_error(std::string("msfl_slam_set_uncertainty: ") + msfl_status_string(st) + " " + msfl_slam_last_error(s_));
+  }
+  // msfl_slam_set_map_window: after the inserts of every every_n_scans-th scan both map stores forget what lies further than half_cells
+  // cells from the pose (23 cells of 3 m change no pose while the sensor's range stays inside them); ClearMapWindow turns it off again.  MapWindow: what the crops of one of
+  // the last four scans did (all zero where none ran).
+  void SetMapWindow(const std::array<int, 3>& half_cells, int every_n_scans = 1) {
+    const msfl_status st = msfl_slam_set_map_window(s_, half_cells.data(), every_n_scans);
+    if (st != MSFL_OK) throw std::runtime_error(std::string("msfl_slam_set_map_window: ") + msfl_status_string(st) + " " + msfl_slam_last_error(s_));
+  }
+  void ClearMapWindow() { (void)msfl_slam_set_map_window(s_, nullptr, 0); }
+  void MapWindow(int scan_index, msfl_grid_crop_info* corner, msfl_grid_crop_info* surf) {
+    const msfl_status st = msfl_slam_get_map_window(s_, scan_index, corner, surf);
+    if (st != MSFL_OK) throw std::runtime_error(std::string("msfl_slam_get_map_window: ") + msfl_status_string(st) + " " + msfl_slam_last_error(s_));
   }
   void Uncertainty(int scan_index, msfl_match_uncertainty* odometry, msfl_match_uncertainty* mapping) {
     const msfl_status st = msfl_slam_get_uncertainty(s_, scan_index, odometry, mapping);

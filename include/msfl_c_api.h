@@ -551,6 +551,42 @@ msfl_status msfl_grid_size(msfl_grid* g, int* n_points, int* n_cells);
 /* all points, cells ascending (the reference dumps the map to PLY on shutdown, laser_mapping.cc:95-113) */
 msfl_status msfl_grid_dump(msfl_grid* g, msfl_point* out, int capacity, int* n_out, msfl_mem mem);
 
+/* {ix, iy, iz, count} of every cell into the host array `cells` (capacity x 4 ints), in the order of msfl_grid_dump: the dump's
+   points [sum of the counts before, + count) belong to that cell.  A dump alone cannot be split back into cells (a centroid may
+   round across the boundary of the cell that owns it); with this list a saved map can be read again cell by cell.  *n_out receives
+   the number of cells; MSFL_CAPACITY if it exceeds `capacity` (the first `capacity` cells are still written). */
+msfl_status msfl_grid_dump_cells(msfl_grid* g, int* cells, int capacity, int* n_out);
+
+/* {n_points, n_cells, pool_top, pool_capacity_points, cell_capacity, device_bytes}: live sizes, the first free slot of the point
+   pool, the capacities of the pool and of the cell table, and the device memory the store holds.  Synchronises like msfl_grid_size. */
+msfl_status msfl_grid_stats(msfl_grid* g, long long out[6]);
+
+/* Windowed local map.  HybridGrid never removes a cell, so a store that is only inserted into grows with the distance driven.
+   msfl_grid_crop forgets every cell outside a window of cells: with c = lround(f32(center) / resolution) per axis (the cell
+   InsertScan files a point at `center` under), cell (ix, iy, iz) is kept iff |ix - cx| <= half_cells[0] && |iy - cy| <=
+   half_cells[1] && |iz - cz| <= half_cells[2].  Kept cells are untouched (points, order, what the surround query delivers); the
+   room of the others is reclaimed by the store's next compaction.  GetSurroundedCloud reads nothing beyond 60 m + 1 m of the
+   sensor (hybrid_grid.cc:474-485), so a window of 23 cells of 3 m around the sensor takes nothing from the registration of a scan
+   taken there.  What it does take away are returns from beyond the window, which the unbounded map would have kept until the
+   sensor came within 60 m of them: with a sensor whose range stays inside the window nothing changes at all.
+     evicted == NULL : the evicted points are dropped.
+     otherwise       : `evicted` (`capacity` points; host or device memory as `mem` says) receives them, cells ascending and in
+                       stored order inside a cell: the order msfl_grid_dump would have delivered them in.  If they are more than
+                       `capacity` the crop is refused as a whole: the map is unchanged, info->applied = 0, the counts in `info`
+                       say how much room is needed, MSFL_CAPACITY is returned.
+   Evicted points that are inserted again with msfl_grid_insert_scan pass through the voxel filter again (they are centroids
+   already): there is no way to load a tile back unfiltered.
+   MSFL_BAD_ARG: a negative half_cells entry, a centre that is not finite (in f32), info == NULL. */
+typedef struct msfl_grid_crop_info {
+  int n_cells_evicted, n_points_evicted;   /* what this crop removed (full counts, also when it was refused) */
+  int n_cells, n_points;                   /* live sizes after the crop */
+  int center_cell[3];                      /* (ix, iy, iz) the window was centred on */
+  int applied;                             /* 1, or 0 when the crop was refused: map unchanged */
+} msfl_grid_crop_info;
+
+msfl_status msfl_grid_crop(msfl_grid* g, const double center[3], const int half_cells[3],
+                           msfl_point* evicted, int capacity, msfl_mem mem, msfl_grid_crop_info* info);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* The per-scan SLAM step, device-resident (BASELINE configs[2]: sequential odometry + mapping).*/
@@ -616,7 +652,8 @@ typedef struct msfl_slam_result {
   int n_full, n_sharp, n_less_sharp, n_flat, n_less_flat;   /* extraction counts */
   int n_corner_ds, n_surf_ds;           /* after the 0.2 / 0.4 m voxel filters (:264-270) */
   int n_map_corner, n_map_surf;         /* GetSurroundedCloud sizes (:273-278) */
-  int grid_corner[8], grid_surf[8];     /* map store after the inserts: {points, cells, pool_top, dropped, overflow, cells touched, ...} */
+  int grid_corner[8], grid_surf[8];     /* map store after the inserts: {points, cells, pool_top, dropped, overflow, cells touched, ...};
+                                           on a scan that msfl_slam_set_map_window cropped, [0..2] are the sizes AFTER the crop */
   int status_imu;             /* 0, or MSFL_BAD_ARG: a less-sharp / less-flat point's relative time lies outside the scan's
                                  pre-integration span (GetDeltaQP CHECK-aborts there, scan_undistortion.cc:26-30; CHECK_GE(time, 0) :12):
                                  the scan is then neither matched nor inserted (status_mapping = MSFL_BAD_ARG as well) */
@@ -695,6 +732,19 @@ msfl_status msfl_slam_get_uncertainty(msfl_slam* s, int scan_index, msfl_match_u
    The records travel with the scan that consumes them, so feeding further scans while that one is still queued is safe.
    MSFL_BAD_ARG for a non-finite entry (nothing is changed then). */
 msfl_status msfl_slam_set_next_prior(msfl_slam* s, const msfl_pose_prior* odometry, const msfl_pose_prior* mapping);
+
+/* Windowed local map (see msfl_grid_crop): from the next scan fed on, after the two InsertScan calls of every scan with
+   (scan_index + 1) % every_n_scans == 0 both stores are cropped to +-half_cells cells around the translation of that scan's
+   pose_map, on the device and without a synchronisation.  half_cells == NULL turns the window off (the default; every_n_scans is
+   then ignored).  The evicted points are dropped: a caller who wants the global map keeps msfl_slam_config.keep_clouds and
+   accumulates full_map, the map-frame full cloud per scan, which is what the reference accumulates for its PLY dump
+   (laser_mapping.cc:214-217).  On a cropped scan grid_corner[0..2] / grid_surf[0..2] of the record are the sizes after the crop.
+   With a window of at least 23 cells of 3 m per axis and a sensor range inside it, poses and records are bit-identical to a run
+   without the window (see msfl_grid_crop for longer ranges).  MSFL_BAD_ARG: a negative entry, every_n_scans < 1. */
+msfl_status msfl_slam_set_map_window(msfl_slam* s, const int half_cells[3], int every_n_scans);
+/* What the crops of scan `scan_index` (one of the last four fed; waits for it) did to the corner / surf store.  Either pointer may
+   be NULL.  All-zero records for a scan on which no crop ran. */
+msfl_status msfl_slam_get_map_window(msfl_slam* s, int scan_index, msfl_grid_crop_info* corner, msfl_grid_crop_info* surf);
 
 /* msfl_slam_config.keep_clouds: the clouds of scan `scan_index` (it must be one of the last TWO fed: the buffers belong to a set that
    the scan after next reuses).  Waits for that scan's chain.

@@ -26,6 +26,7 @@ EXPORTED = [
     "msfl_transform_cloud",
     "msfl_delta_qp", "msfl_deskew_cloud", "msfl_undistort_cloud",
     "msfl_grid_create", "msfl_grid_destroy", "msfl_grid_insert_scan", "msfl_grid_get_surrounded", "msfl_grid_size", "msfl_grid_dump",
+    "msfl_grid_crop", "msfl_grid_dump_cells", "msfl_grid_stats", "msfl_slam_set_map_window", "msfl_slam_get_map_window",
     "msfl_slam_default_config", "msfl_slam_create", "msfl_slam_destroy", "msfl_slam_add_scan", "msfl_slam_add_scan_imu", "msfl_slam_get_result", "msfl_slam_grids",
     "msfl_slam_last_error", "msfl_slam_get_clouds",
     "msfl_set_uncertainty", "msfl_slam_set_uncertainty", "msfl_slam_get_uncertainty",
@@ -138,6 +139,19 @@ class FeaturesBatch(C.Structure):
                 ("flat_idx", C.c_void_p), ("less_flat_idx", C.c_void_p),
                 ("n_full", C.c_void_p), ("n_sharp", C.c_void_p), ("n_less_sharp", C.c_void_p),
                 ("n_flat", C.c_void_p), ("n_less_flat", C.c_void_p)]
+
+
+class GridCropInfo(C.Structure):
+    """msfl_grid_crop_info; `status` (a Python attribute) is the msfl_status of the call that filled it."""
+    _fields_ = [("n_cells_evicted", C.c_int), ("n_points_evicted", C.c_int), ("n_cells", C.c_int), ("n_points", C.c_int),
+                ("center_cell", C.c_int * 3), ("applied", C.c_int)]
+    status = OK
+
+    def as_tuple(self):
+        return (self.n_cells_evicted, self.n_points_evicted, self.n_cells, self.n_points, tuple(self.center_cell), self.applied)
+
+
+GRID_STATS = ("n_points", "n_cells", "pool_top", "pool_capacity_points", "cell_capacity", "device_bytes")
 
 
 class SlamConfig(C.Structure):
@@ -633,6 +647,46 @@ class Grid:
         self.handle._check(self.lib.msfl_grid_dump(self.g, _vp(out), C.c_int(cap), C.byref(n_out), C.c_int(MEM_HOST)), "msfl_grid_dump")
         return out[:n_out.value].copy()
 
+    def dump_cells(self):
+        """(n_cells, 4) int32 {ix, iy, iz, count}, in the order of dump()."""
+        cap = max(self.size()[1], 1)
+        out = np.zeros((cap, 4), np.int32)
+        n_out = C.c_int(0)
+        self.handle._check(self.lib.msfl_grid_dump_cells(self.g, _vp(out), C.c_int(cap), C.byref(n_out)), "msfl_grid_dump_cells")
+        return out[:n_out.value].copy()
+
+    def stats(self):
+        """dict of msfl_grid_stats: n_points, n_cells, pool_top, pool_capacity_points, cell_capacity, device_bytes."""
+        out = (C.c_longlong * 6)()
+        self.handle._check(self.lib.msfl_grid_stats(self.g, out), "msfl_grid_stats")
+        return dict(zip(GRID_STATS, (int(v) for v in out)))
+
+    def crop(self, center, half_cells, keep_evicted=False, capacity=None, allow=()):
+        """Forget every cell outside +-half_cells cells around the cell of `center` (msfl_grid_crop).  Returns the GridCropInfo, or
+        (info, evicted (m, 4) array) with keep_evicted; capacity: room for the evicted points (default: every live point).  A crop
+        refused for want of room raises unless CAPACITY is in `allow` (then info.applied == 0 and the array is empty)."""
+        center = (C.c_double * 3)(*[float(v) for v in center])
+        half = (C.c_int * 3)(*[int(v) for v in half_cells])
+        info = GridCropInfo()
+        ev, cap = None, 0
+        if keep_evicted:
+            cap = self.size()[0] if capacity is None else int(capacity)
+            ev = np.zeros((max(cap, 1), 4), np.float32)
+        info.status = self.handle._check(self.lib.msfl_grid_crop(self.g, center, half, _vp(ev), C.c_int(cap), C.c_int(MEM_HOST), C.byref(info)),
+                                         "msfl_grid_crop", allow)
+        if not keep_evicted:
+            return info
+        return info, ev[:info.n_points_evicted if info.applied else 0].copy()
+
+    def crop_device(self, center, half_cells, evicted_ptr, capacity, allow=()):
+        """msfl_grid_crop with a device buffer for the evicted points; returns the GridCropInfo."""
+        center = (C.c_double * 3)(*[float(v) for v in center])
+        half = (C.c_int * 3)(*[int(v) for v in half_cells])
+        info = GridCropInfo()
+        info.status = self.handle._check(self.lib.msfl_grid_crop(self.g, center, half, _vp(evicted_ptr), C.c_int(int(capacity)), C.c_int(MEM_DEVICE),
+                                                                 C.byref(info)), "msfl_grid_crop(device)", allow)
+        return info
+
 
 class _BorrowedGrid(Grid):
     """A map store owned by a Slam pipeline (never destroyed from here)."""
@@ -756,6 +810,22 @@ class Slam:
         if st != OK:
             raise MsflError(st, "msfl_slam_get_uncertainty", self._err())
         return out
+
+    def set_map_window(self, half_cells, every_n_scans=1):
+        """Crop both map stores to +-half_cells cells around pose_map after the inserts of every every_n_scans-th scan fed from
+        now on (msfl_slam_set_map_window); half_cells=None turns the window off."""
+        half = None if half_cells is None else (C.c_int * 3)(*[int(v) for v in half_cells])
+        st = self.lib.msfl_slam_set_map_window(self.s, half, C.c_int(int(every_n_scans)))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_set_map_window", self._err())
+
+    def get_map_window(self, scan_index):
+        """(corner, surf) GridCropInfo of one of the last four scans fed; all zero where no crop ran."""
+        a, b = GridCropInfo(), GridCropInfo()
+        st = self.lib.msfl_slam_get_map_window(self.s, C.c_int(int(scan_index)), C.byref(a), C.byref(b))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_get_map_window", self._err())
+        return a, b
 
     def clouds(self, scan_index):
         """keep_clouds=1: the scan's data products as host arrays (msfl_slam_get_clouds, MSFL_MEM_HOST): dict with full_scan (n,4),

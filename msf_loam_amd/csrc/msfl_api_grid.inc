@@ -15,7 +15,8 @@ struct msfl_grid_s {
   DevBuf keys, keys_s, vals, vals_s, head, tpos, xf, xs, t_key, t_ns, t_old, t_woff, t_rank, t_cnt;
   // surround / dump scratch
   DevBuf cnt, off, stage, pose, report_dev;
-  PinBuf report;                                  // int[8] read-back: {points, cells, pool_top, bad, overflow, touched, work, surround_total}
+  DevBuf crop;                                    // crop scratch: keep flag and rank per cell (cnt / off hold the evicted counts and offsets)
+  PinBuf report;                                  // int[8] read-back: {points, cells, pool_top, bad, overflow, touched, work, surround_total}, then the int[8] crop info
   // What the host knows: exact sizes as of the newest insert whose report it has seen, plus the inserts enqueued since
   // (sequence number, point capacity).  Every launch bound and capacity decision derives from these upper bounds, so
   // inserts and queries can be enqueued without waiting for the ones before them.
@@ -53,9 +54,9 @@ msfl_status grid_init_state(msfl_grid* g) {
   GridState init{};
   init.epoch = 1;
   HIPCHK(h, h->pin.upload(g->state.p, &init, sizeof(init), h->stream));
-  HIPCHK(h, g->report_dev.reserve(8 * sizeof(int)));
-  HIPCHK(h, g->report.reserve(8 * sizeof(int)));
-  std::memset(g->report.p, 0, 8 * sizeof(int));
+  HIPCHK(h, g->report_dev.reserve(16 * sizeof(int)));
+  HIPCHK(h, g->report.reserve(16 * sizeof(int)));
+  std::memset(g->report.p, 0, 16 * sizeof(int));
   return MSFL_OK;
 }
 
@@ -230,6 +231,54 @@ msfl_status grid_read_report(msfl_grid* g) {
   return grid_apply_report(g, g->report.as<int>(), g->last_seq);
 }
 
+// Stream-ordered crop to the window of +-half cells around the cell of the device-resident `d_center` (3 doubles).  d_evicted:
+// device buffer of `capacity` points for the evicted points, or null (dropped).  info_dst: device int[8] (msfl_grid_crop_info).
+// report_dst as in grid_insert_enqueue; with sizes_only only its first three words are rewritten (the SLAM step's record keeps
+// what the insert before the crop published in the others).  Takes a sequence number like an insert of zero points: the bounds
+// come down when the report is applied.
+msfl_status grid_crop_enqueue(msfl_grid* g, const double* d_center, const int half[3], float4* d_evicted, int capacity, int* info_dst,
+                              int* report_dst = nullptr, bool sizes_only = false) {
+  msfl_handle* h = g->h;
+  hipStream_t st = h->stream;
+  GridState* gs = g->state.as<GridState>();
+  const int bound = (int)std::min<long long>(g->ub_cells, g->cell_cap);
+  const GridWindow w{half[0], half[1], half[2]};
+  int *keep = nullptr, *rank = nullptr, *ecnt = nullptr, *eoff = nullptr;
+  if (bound > 0) {
+    const int cur = g->cur_tab, nxt = 1 - cur;
+    HIPCHK(h, g->crop.reserve(2 * (size_t)bound * sizeof(int)));
+    HIPCHK(h, g->cnt.reserve((size_t)bound * sizeof(int)));
+    HIPCHK(h, g->off.reserve((size_t)bound * sizeof(int)));
+    keep = g->crop.as<int>(); rank = keep + bound; ecnt = g->cnt.as<int>(); eoff = g->off.as<int>();
+    const unsigned long long* keys = g->ckey[cur].as<unsigned long long>();
+    const int* ccnt = g->ccnt[cur].as<int>();
+    if (bound <= kGridOneBlockMax) {
+      hipLaunchKernelGGL(grid_crop_scan_kernel, dim3(1), dim3(1024), 0, st, keys, ccnt, bound, d_center, g->d.resolution, w, keep, rank, ecnt, eoff,
+                         (const GridState*)gs);
+    } else {
+      hipLaunchKernelGGL(grid_crop_flag_kernel, dim3(div_up(bound, 256)), dim3(256), 0, st, keys, ccnt, bound, d_center, g->d.resolution, w, keep, ecnt,
+                         (const GridState*)gs);
+      size_t tb = 0;
+      HIPCHK(h, rocprim::exclusive_scan(nullptr, tb, keep, rank, 0, (size_t)bound, rocprim::plus<int>(), st));
+      HIPCHK(h, h->idx_cub.reserve(tb));
+      HIPCHK(h, rocprim::exclusive_scan(h->idx_cub.p, tb, keep, rank, 0, (size_t)bound, rocprim::plus<int>(), st));
+      HIPCHK(h, rocprim::exclusive_scan(h->idx_cub.p, tb, ecnt, eoff, 0, (size_t)bound, rocprim::plus<int>(), st));
+    }
+    hipLaunchKernelGGL(grid_crop_commit_kernel, dim3(std::min(bound, 4096)), dim3(256), 0, st, keys, (const int*)g->cstart[cur].as<int>(), ccnt,
+                       (const int*)g->cstamp[cur].as<int>(), g->ckey[nxt].as<unsigned long long>(), g->cstart[nxt].as<int>(), g->ccnt[nxt].as<int>(),
+                       g->cstamp[nxt].as<int>(), (const float4*)g->pool[g->cur_pool].as<float4>(), (const int*)keep, (const int*)rank, (const int*)ecnt,
+                       (const int*)eoff, bound, d_evicted, capacity, (const GridState*)gs);
+    g->cur_tab = nxt;
+  }
+  hipLaunchKernelGGL(grid_crop_finish_kernel, dim3(1), dim3(1), 0, st, gs, (const int*)keep, (const int*)rank, (const int*)ecnt, (const int*)eoff, bound, d_center,
+                     g->d.resolution, d_evicted ? 1 : 0, capacity, info_dst, report_dst ? report_dst : g->report_dev.as<int>(), sizes_only ? 1 : 0);
+  HIPCHK(h, hipGetLastError());
+  if (!report_dst) { HIPCHK(h, hipMemcpyAsync(g->report.p, g->report_dev.p, 16 * sizeof(int), hipMemcpyDeviceToHost, st)); g->pending = true; }
+  g->last_seq = g->next_seq++;
+  g->inflight.emplace_back(g->last_seq, 0);
+  return MSFL_OK;
+}
+
 // Stream-ordered GetSurroundedCloud.  scan = d_scan[idx ? idx[k] : k], k < min(n_cap, *n_dev); pose on the device.
 // The cloud goes to d_out (capacity points), its size to *d_n_out (device, optional) and to GridState::surround_total.
 msfl_status grid_surround_enqueue(msfl_grid* g, const float4* d_scan, const int* d_idx, int n_cap, const int* n_dev, const double* d_pose,
@@ -292,7 +341,7 @@ void msfl_grid_destroy(msfl_grid* g) {
   (void)hipStreamSynchronize(g->h->stream);
   DevBuf* bufs[] = {&g->state, &g->pool[0], &g->pool[1], &g->ckey[0], &g->ckey[1], &g->cstart[0], &g->cstart[1], &g->ccnt[0], &g->ccnt[1],
                     &g->cstamp[0], &g->cstamp[1], &g->keys, &g->keys_s, &g->vals, &g->vals_s, &g->head, &g->tpos, &g->xf, &g->xs, &g->t_key, &g->t_ns,
-                    &g->t_old, &g->t_woff, &g->t_rank, &g->t_cnt, &g->cnt, &g->off, &g->stage, &g->pose, &g->report_dev};
+                    &g->t_old, &g->t_woff, &g->t_rank, &g->t_cnt, &g->cnt, &g->off, &g->stage, &g->pose, &g->report_dev, &g->crop};
   for (auto* b : bufs) b->release();
   g->report.release();
   delete g;
@@ -387,6 +436,78 @@ msfl_status msfl_grid_dump(msfl_grid* g, msfl_point* out, int capacity, int* n_o
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   return g->n_points > capacity ? MSFL_CAPACITY : MSFL_OK;
+}
+
+// Forget every cell outside the window of +-half_cells cells around the cell of `center` (msfl_c_api.h).
+msfl_status msfl_grid_crop(msfl_grid* g, const double center[3], const int half_cells[3], msfl_point* evicted, int capacity, msfl_mem mem,
+                           msfl_grid_crop_info* info) {
+  if (!g) return MSFL_BAD_ARG;
+  msfl_handle* h = g->h;
+  msfl_status s = enter(h); if (s) return s;
+  if (!info || !center || !half_cells || half_cells[0] < 0 || half_cells[1] < 0 || half_cells[2] < 0 || !std::isfinite(center[0]) ||
+      !std::isfinite(center[1]) || !std::isfinite(center[2]) || !std::isfinite((float)center[0]) || !std::isfinite((float)center[1]) ||
+      !std::isfinite((float)center[2]) || (evicted && capacity < 0))
+    return fail(h, MSFL_BAD_ARG, "msfl_grid_crop: bad argument");
+  hipStream_t st = h->stream;
+  if (g->pending) { HIPCHK(h, hipStreamSynchronize(st)); (void)grid_read_report(g); }
+  HIPCHK(h, g->pose.reserve(8 * sizeof(double)));
+  HIPCHK(h, h->pin.upload(g->pose.p, center, 3 * sizeof(double), st));
+  float4* d_ev = reinterpret_cast<float4*>(evicted);
+  const int stage_cap = (int)std::min<long long>(capacity, g->ub_points);   // no more than the live points can be evicted
+  if (evicted && mem == MSFL_MEM_HOST) { HIPCHK(h, g->stage.reserve((size_t)std::max(stage_cap, 1) * sizeof(float4))); d_ev = g->stage.as<float4>(); }
+  int* d_info = g->report_dev.as<int>() + 8;
+  s = grid_crop_enqueue(g, g->pose.as<double>(), half_cells, d_ev, capacity, d_info); if (s) return s;
+  HIPCHK(h, hipStreamSynchronize(st));
+  s = grid_read_report(g); if (s) return s;
+  static_assert(sizeof(msfl_grid_crop_info) == CROP_WORDS * sizeof(int), "msfl_grid_crop_info is the device record");
+  std::memcpy(info, g->report.as<int>() + 8, sizeof(*info));
+  if (!info->applied) return fail(h, MSFL_CAPACITY, "msfl_grid_crop: more evicted points than `capacity`; map unchanged");
+  if (evicted && mem == MSFL_MEM_HOST && info->n_points_evicted > 0) {
+    HIPCHK(h, hipMemcpyAsync(evicted, d_ev, (size_t)info->n_points_evicted * sizeof(float4), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+  }
+  return MSFL_OK;
+}
+
+// {ix, iy, iz, count} of every cell, in the order of msfl_grid_dump
+msfl_status msfl_grid_dump_cells(msfl_grid* g, int* cells, int capacity, int* n_out) {
+  if (!g) return MSFL_BAD_ARG;
+  msfl_handle* h = g->h;
+  msfl_status s = enter(h); if (s) return s;
+  if (!n_out || capacity < 0 || (capacity > 0 && !cells)) return fail(h, MSFL_BAD_ARG, "msfl_grid_dump_cells: bad argument");
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (g->pending) (void)grid_read_report(g);
+  *n_out = g->n_cells;
+  const int m = std::min(g->n_cells, capacity);
+  if (m > 0) {
+    std::vector<unsigned long long> keys((size_t)m);
+    std::vector<int> cnt((size_t)m);
+    HIPCHK(h, hipMemcpy(keys.data(), g->ckey[g->cur_tab].p, (size_t)m * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(cnt.data(), g->ccnt[g->cur_tab].p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+    const int lim = 1 << (kGridCellBits - 1), mask = (1 << kGridCellBits) - 1;
+    for (int c = 0; c < m; c++) {
+      cells[4 * c] = (int)(keys[c] & mask) - lim; cells[4 * c + 1] = (int)((keys[c] >> kGridCellBits) & mask) - lim;
+      cells[4 * c + 2] = (int)(keys[c] >> (2 * kGridCellBits)) - lim; cells[4 * c + 3] = cnt[c];
+    }
+  }
+  return g->n_cells > capacity ? MSFL_CAPACITY : MSFL_OK;
+}
+
+// {n_points, n_cells, pool_top, pool_capacity_points, cell_capacity, device_bytes}
+msfl_status msfl_grid_stats(msfl_grid* g, long long out[6]) {
+  if (!g || !out) return MSFL_BAD_ARG;
+  if (g->pending) {
+    msfl_status s = enter(g->h); if (s) return s;
+    HIPCHK(g->h, hipStreamSynchronize(g->h->stream));
+    (void)grid_read_report(g);
+  }
+  const DevBuf* bufs[] = {&g->state, &g->pool[0], &g->pool[1], &g->ckey[0], &g->ckey[1], &g->cstart[0], &g->cstart[1], &g->ccnt[0], &g->ccnt[1],
+                          &g->cstamp[0], &g->cstamp[1], &g->keys, &g->keys_s, &g->vals, &g->vals_s, &g->head, &g->tpos, &g->xf, &g->xs, &g->t_key, &g->t_ns,
+                          &g->t_old, &g->t_woff, &g->t_rank, &g->t_cnt, &g->cnt, &g->off, &g->stage, &g->pose, &g->report_dev, &g->crop};
+  long long bytes = 0;
+  for (auto* b : bufs) bytes += (long long)b->cap;
+  out[0] = g->n_points; out[1] = g->n_cells; out[2] = g->pool_top; out[3] = (long long)pool_capacity(g); out[4] = g->cell_cap; out[5] = bytes;
+  return MSFL_OK;
 }
 
 }  // extern "C"

@@ -35,7 +35,7 @@ struct SlamScanBuf {                    // everything derived from ONE scan that
 };
 
 constexpr int kSlamSlots = 4;
-struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; bool prior_map; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
+struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; bool prior_map; bool crop; int half[3]; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
 constexpr int kSlamProfileSkip = 20;                    // MSFL_SLAM_HOST_PROFILE leaves the first scans (allocations) out
 #ifndef MSFL_SLAM_ODOM_LANES
 #define MSFL_SLAM_ODOM_LANES 64
@@ -84,6 +84,13 @@ struct msfl_slam_s {
   msfl_pose_prior next_prior[2] = {};
   bool next_prior_set[2] = {};
   DevBuf prior[kSlamSlots];
+  // msfl_slam_set_map_window: both stores are cropped to +-win_half cells around pose_map after the inserts of every win_every-th scan.
+  // Two msfl_grid_crop_info {corner, surf} per slot; they travel with the slot's result copy.
+  bool win_on = false;
+  int win_half[3] = {}, win_every = 1;
+  DevBuf win[kSlamSlots];
+  PinBuf win_host;                      // kSlamSlots x 2 records
+  bool win_held[kSlamSlots] = {};       // a crop ran on the scan in this slot
   hipEvent_t ev_done[kSlamSlots] = {};
   long long seq_c[kSlamSlots] = {}, seq_s[kSlamSlots] = {};   // map-store insert sequence numbers of the scan in each slot
   bool applied[kSlamSlots] = {};        // the slot's grid reports have been folded into the stores' host-side bounds
@@ -380,6 +387,8 @@ void msfl_slam_destroy(msfl_slam* s) {
   s->rec_host.release();
   for (auto& b : s->unc) b.release();
   for (auto& b : s->prior) b.release();
+  for (auto& b : s->win) b.release();
+  s->win_host.release();
   s->unc_host.release();
   for (auto e : s->ev_done) if (e) (void)hipEventDestroy(e);
   if (s->gc) msfl_grid_destroy(s->gc);
@@ -512,6 +521,39 @@ msfl_status msfl_slam_set_next_prior(msfl_slam* s, const msfl_pose_prior* odomet
     s->next_prior_set[a] = in[a] != nullptr;
     if (in[a]) s->next_prior[a] = *in[a];
   }
+  return MSFL_OK;
+}
+
+msfl_status msfl_slam_set_map_window(msfl_slam* s, const int half_cells[3], int every_n_scans) {
+  if (!s) return MSFL_BAD_ARG;
+  if (!half_cells) { s->win_on = false; return MSFL_OK; }          // read once per msfl_slam_add_scan, like msfl_slam_set_uncertainty
+  if (half_cells[0] < 0 || half_cells[1] < 0 || half_cells[2] < 0 || every_n_scans < 1)
+    return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_map_window: negative half_cells or every_n_scans < 1");
+  SHIP(s, hipSetDevice(s->ho->device));
+  if (!s->win_host.p) {
+    for (auto& b : s->win) SHIP(s, b.reserve(2 * CROP_WORDS * sizeof(int)));
+    SHIP(s, s->win_host.reserve(kSlamSlots * 2 * CROP_WORDS * sizeof(int)));
+  }
+  for (int a = 0; a < 3; a++) s->win_half[a] = half_cells[a];
+  s->win_every = every_n_scans;
+  s->win_on = true;
+  return MSFL_OK;
+}
+
+msfl_status msfl_slam_get_map_window(msfl_slam* s, int scan_index, msfl_grid_crop_info* corner, msfl_grid_crop_info* surf) {
+  if (!s) return MSFL_BAD_ARG;
+  if (scan_index < 0 || scan_index >= s->n_scans || scan_index < s->n_scans - kSlamSlots)
+    return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_map_window: that scan's record is no longer (or not yet) held");
+  const int slot = scan_index % kSlamSlots;
+  if (corner) std::memset(corner, 0, sizeof(*corner));
+  if (surf) std::memset(surf, 0, sizeof(*surf));
+  if (!s->win_held[slot]) return MSFL_OK;                           // no crop ran on that scan
+  SHIP(s, hipSetDevice(s->ho->device));
+  { const msfl_status ws = slam_wait_mapped(s, scan_index); if (ws) return ws; }
+  SHIP(s, hipEventSynchronize(s->ev_done[slot]));
+  const msfl_grid_crop_info* w = s->win_host.as<msfl_grid_crop_info>() + 2 * slot;
+  if (corner) *corner = w[0];
+  if (surf) *surf = w[1];
   return MSFL_OK;
 }
 
@@ -718,9 +760,12 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   const long long seq_c0 = s->gc->last_seq, seq_s0 = s->gs->last_seq;
   SHIP(s, hipStreamWaitEvent(sc, cur.ev_match, 0));
   SCHK(s, hc, grid_insert_enqueue(s->gc, cur.map_ls.as<float4>(), cap_ls, cnt + SC_USE_LS, pose_map, rec->grid_corner));
+  int* win = jb.crop ? s->win[slot].as<int>() : nullptr;          // msfl_slam_set_map_window: each store forgets what lies outside the window
+  if (jb.crop) SCHK(s, hc, grid_crop_enqueue(s->gc, pose_map, jb.half, nullptr, 0, win, rec->grid_corner, true));
   SHIP(s, hipEventRecord(cur.ev_cdone, sc));
   seg("corner insert");
   SCHK(s, hm, grid_insert_enqueue(s->gs, cur.map_lf.as<float4>(), cap_lf, cnt + SC_USE_LF, pose_map, rec->grid_surf));
+  if (jb.crop) SCHK(s, hm, grid_crop_enqueue(s->gs, pose_map, jb.half, nullptr, 0, win + CROP_WORDS, rec->grid_surf, true));
   SHIP(s, hipStreamWaitEvent(sm, cur.ev_cdone, 0));
   seg("surf insert");
   s->seq_c[slot] = s->gc->last_seq != seq_c0 ? s->gc->last_seq : 0;
@@ -731,6 +776,8 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   SHIP(s, hipMemcpyAsync(s->rec_host.as<msfl_slam_result>() + slot, rec, sizeof(msfl_slam_result), hipMemcpyDeviceToHost, sm));
   if (jb.unc)
     SHIP(s, hipMemcpyAsync(s->unc_host.as<UncRecord>() + 2 * slot, s->unc[slot].p, 2 * sizeof(UncRecord), hipMemcpyDeviceToHost, sm));
+  if (jb.crop)
+    SHIP(s, hipMemcpyAsync(s->win_host.as<int>() + 2 * CROP_WORDS * slot, s->win[slot].p, 2 * CROP_WORDS * sizeof(int), hipMemcpyDeviceToHost, sm));
   SHIP(s, hipEventRecord(s->ev_done[slot], sm));
   seg("record");
   s->applied[slot] = false;
@@ -872,7 +919,9 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
     s->host_wait_s += std::chrono::duration<double>(t_free - t_call).count();
     s->host_enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_free).count();
   }
-  const SlamJob job{k, n, imu_mode, unc, unc_min_eig, prior_map};
+  const bool crop = s->win_on && (k + 1) % s->win_every == 0;
+  s->win_held[slot] = crop;
+  const SlamJob job{k, n, imu_mode, unc, unc_min_eig, prior_map, crop, {s->win_half[0], s->win_half[1], s->win_half[2]}};
   if (s->threaded) {
     std::unique_lock<std::mutex> lk(s->mu);
     s->cv_done.wait(lk, [&] { return !s->has_job; });            // the mapping thread is at most one scan behind

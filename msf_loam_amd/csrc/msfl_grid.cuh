@@ -732,4 +732,122 @@ grid_emit_kernel(const float4* __restrict__ pool, const int* __restrict__ cell_s
   if (blockIdx.x == 0 && threadIdx.x == 0) st->epoch += 1;         // nothing in this kernel reads it: the next query stamps with a fresh value
 }
 
+// ---- Crop: forget every cell outside a window of cells (the reference's HybridGrid never removes a cell) -----------------------
+// A cell (ix, iy, iz) is kept iff |ix - cx| <= hx && |iy - cy| <= hy && |iz - cz| <= hz, c = grid_cell_index((float)center, resolution).
+// The kept entries move, in order, to the other table buffer; the evicted slabs become pool garbage (reclaimed by the next
+// compaction) after an optional copy to `evicted`, cells ascending, stored order inside a cell: what a dump would have delivered.
+// `center` is read from device memory (3 doubles: the translation of a device-resident pose).  A crop that would deliver more
+// than `capacity` points, or whose centre is not finite, is refused as a whole: the table is carried over unchanged.
+struct GridWindow { int hx, hy, hz; };
+
+// what one crop did, as the host sees it (msfl_grid_crop_info, 8 ints)
+enum { CROP_CELLS_EVICTED = 0, CROP_POINTS_EVICTED, CROP_CELLS, CROP_POINTS, CROP_CX, CROP_CY, CROP_CZ, CROP_APPLIED, CROP_WORDS };
+
+__device__ __forceinline__ bool grid_crop_center(const double* __restrict__ center, float resolution, int& cx, int& cy, int& cz) {
+  const float x = (float)center[0], y = (float)center[1], z = (float)center[2];
+  const bool ok = isfinite(x) && isfinite(y) && isfinite(z);      // the host API refuses such a centre; a device-resident pose is checked here
+  cx = ok ? grid_cell_index(x, resolution) : 0; cy = ok ? grid_cell_index(y, resolution) : 0; cz = ok ? grid_cell_index(z, resolution) : 0;
+  return ok;
+}
+__device__ __forceinline__ bool grid_crop_keeps(unsigned long long key, int cx, int cy, int cz, GridWindow w) {
+  int ix, iy, iz;
+  grid_cell_of_key(key, ix, iy, iz);
+  const long long dx = (long long)ix - cx, dy = (long long)iy - cy, dz = (long long)iz - cz;      // a far-away centre is any int
+  return (dx < 0 ? -dx : dx) <= w.hx && (dy < 0 ? -dy : dy) <= w.hy && (dz < 0 ? -dz : dz) <= w.hz;
+}
+
+// per cell: keep flag and evicted point count (both 0 beyond the live cells, so the device-wide scans need no tail pass)
+__global__ void __launch_bounds__(256)
+grid_crop_flag_kernel(const unsigned long long* __restrict__ keys, const int* __restrict__ cell_cnt, int bound, const double* __restrict__ center,
+                      float resolution, GridWindow w, int* __restrict__ keep, int* __restrict__ ecnt, const GridState* __restrict__ st) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= bound) return;
+  int cx, cy, cz;
+  const bool ok = grid_crop_center(center, resolution, cx, cy, cz);
+  int k = 0, e = 0;
+  if (c < st->n_cells) { k = (!ok || grid_crop_keeps(keys[c], cx, cy, cz, w)) ? 1 : 0; e = k ? 0 : cell_cnt[c]; }
+  keep[c] = k; ecnt[c] = e;
+}
+
+// the same + the two exclusive scans (rank among the kept cells, offset among the evicted points) in one workgroup
+__global__ void __launch_bounds__(1024)
+grid_crop_scan_kernel(const unsigned long long* __restrict__ keys, const int* __restrict__ cell_cnt, int bound, const double* __restrict__ center,
+                      float resolution, GridWindow w, int* __restrict__ keep, int* __restrict__ rank, int* __restrict__ ecnt, int* __restrict__ eoff,
+                      const GridState* __restrict__ st) {
+  __shared__ int s_wave[16];
+  bound = min(bound, st->n_cells);                       // grid_crop_commit_kernel reads none of the arrays beyond the live cells
+  int cx, cy, cz;
+  const bool ok = grid_crop_center(center, resolution, cx, cy, cz);
+  int carry_k = 0, carry_e = 0;
+  for (int base = 0; base < bound; base += 4 * 1024) {
+    const int c0 = base + 4 * (int)threadIdx.x;
+    int k[4], e[4], tk = 0, te = 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int c = c0 + u;
+      k[u] = 0; e[u] = 0;
+      if (c < bound) { k[u] = (!ok || grid_crop_keeps(keys[c], cx, cy, cz, w)) ? 1 : 0; e[u] = k[u] ? 0 : cell_cnt[c]; }
+      tk += k[u]; te += e[u];
+    }
+    int total_k, total_e;
+    int run_k = carry_k + block_incl_scan_1024(tk, s_wave, total_k) - tk;
+    int run_e = carry_e + block_incl_scan_1024(te, s_wave, total_e) - te;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int c = c0 + u;
+      if (c < bound) { keep[c] = k[u]; rank[c] = run_k; ecnt[c] = e[u]; eoff[c] = run_e; }
+      run_k += k[u]; run_e += e[u];
+    }
+    carry_k += total_k; carry_e += total_e;
+  }
+}
+
+// kept entries to the other table buffer at their rank, evicted slabs to `evicted` at their offsets (workgroup-stride, like
+// grid_emit_kernel).  Refused (more than `capacity` points to deliver): every entry is carried over where it is.
+__global__ void __launch_bounds__(256)
+grid_crop_commit_kernel(const unsigned long long* __restrict__ keys_in, const int* __restrict__ start_in, const int* __restrict__ cnt_in,
+                        const int* __restrict__ stamp_in, unsigned long long* __restrict__ keys_out, int* __restrict__ start_out,
+                        int* __restrict__ cnt_out, int* __restrict__ stamp_out, const float4* __restrict__ pool, const int* __restrict__ keep,
+                        const int* __restrict__ rank, const int* __restrict__ ecnt, const int* __restrict__ eoff, int bound,
+                        float4* __restrict__ evicted, int capacity, const GridState* __restrict__ st) {
+  const int nc = min(st->n_cells, bound);
+  if (nc == 0) return;
+  const bool refused = evicted != nullptr && eoff[nc - 1] + ecnt[nc - 1] > capacity;
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += gridDim.x * blockDim.x) {      // the table: one thread per cell
+    if (!keep[c] && !refused) continue;
+    const int o = refused ? c : rank[c];
+    keys_out[o] = keys_in[c]; start_out[o] = start_in[c]; cnt_out[o] = cnt_in[c]; stamp_out[o] = stamp_in[c];
+  }
+  if (!evicted || refused) return;
+  for (int c = blockIdx.x; c < nc; c += gridDim.x) {                                               // the slabs: one workgroup per cell
+    const int m = ecnt[c];
+    if (m == 0) continue;
+    const int s = start_in[c], o = eoff[c];
+    for (int i = threadIdx.x; i < m; i += blockDim.x) if (o + i < capacity) evicted[o + i] = pool[s + i];
+  }
+}
+
+// one thread: fold the crop into the state, write the info record and the report (sizes_only: report[3..7] keep what the
+// insert before this crop published, the SLAM step's record).  bound == 0: the table is empty, nothing ran before this.
+__global__ void grid_crop_finish_kernel(GridState* __restrict__ st, const int* __restrict__ keep, const int* __restrict__ rank, const int* __restrict__ ecnt,
+                                        const int* __restrict__ eoff, int bound, const double* __restrict__ center, float resolution,
+                                        int has_evicted, int capacity, int* __restrict__ info, int* __restrict__ report, int sizes_only) {
+  const int nc = min(st->n_cells, bound);
+  int cx, cy, cz;
+  const bool ok = grid_crop_center(center, resolution, cx, cy, cz);
+  const int n_keep = nc > 0 ? rank[nc - 1] + keep[nc - 1] : 0, n_ev_pts = nc > 0 ? eoff[nc - 1] + ecnt[nc - 1] : 0;
+  const int applied = (ok && !(has_evicted && n_ev_pts > capacity)) ? 1 : 0;
+  const int n_ev_cells = nc - n_keep;
+  if (applied) { st->n_cells -= n_ev_cells; st->n_points -= n_ev_pts; }
+  if (info) {
+    info[CROP_CELLS_EVICTED] = n_ev_cells; info[CROP_POINTS_EVICTED] = n_ev_pts; info[CROP_CELLS] = st->n_cells; info[CROP_POINTS] = st->n_points;
+    info[CROP_CX] = cx; info[CROP_CY] = cy; info[CROP_CZ] = cz; info[CROP_APPLIED] = applied;
+  }
+  if (report) {
+    report[0] = st->n_points; report[1] = st->n_cells; report[2] = st->pool_top;
+    if (!sizes_only) { report[3] = 0; report[4] = 0; report[5] = 0; report[6] = 0; report[7] = st->surround_total; }
+  }
+  st->bad = 0; st->overflow = 0; st->n_touched = 0; st->n_new_cells = 0; st->work = 0; st->delta_points = 0; st->n_big = 0;
+}
+
 }  // namespace msfl

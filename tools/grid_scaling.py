@@ -5,6 +5,11 @@ Each inserted "scan" is 6 000 points on a patch of ground and walls that moves 2
 less-flat list lands in ~150 cells of 3 m); the map therefore grows by a few thousand voxels per scan.  Prints one JSON
 line per checkpoint: map points / cells, ms per insert and ms per surround query (wall clock around the C call, host
 buffers, so the figures include the PCIe copy of the scan and, for the query, of the result).
+
+--window HX,HY,HZ: the windowed-map leg instead.  A translating stream of 16-beam-sized scans (the same scan_at clouds) is
+inserted twice, into a store that is cropped to the window after every insert (msfl_grid_crop around the scan's centre) and into
+one that is not; prints msfl_grid_stats of both at the start and at the end, and per checkpoint the median ms per insert of both
+and per crop.
 """
 import argparse, gc, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,12 +29,42 @@ def scan_at(rng, k, n):
     return p, c
 
 
+def window_leg(a):
+    half = [int(v) for v in a.window.split(",")]
+    assert len(half) == 3, "--window takes HX,HY,HZ"
+    h = capi.Handle()
+    stores = {"windowed": capi.Grid(h, 3.0, 0.2), "free": capi.Grid(h, 3.0, 0.2)}
+    rngs = {k: np.random.default_rng(7) for k in stores}
+    gc.collect(); gc.disable()
+    t = {"windowed": [], "free": [], "crop": []}
+    for k in range(a.scans):
+        for name, g in stores.items():
+            p, c = scan_at(rngs[name], k, a.points)
+            t0 = time.perf_counter(); g.insert_scan(p); t1 = time.perf_counter()
+            t[name].append(t1 - t0)
+            if name == "windowed":
+                info = g.crop(c, half)
+                t["crop"].append(time.perf_counter() - t1)
+        if k == 0:
+            print(json.dumps({"scans": 1, "stats": {name: g.stats() for name, g in stores.items()}}), flush=True)
+        if (k + 1) % a.every == 0:
+            print(json.dumps({"scans": k + 1, "window_cells": info.n_cells, "evicted_cells_last_crop": info.n_cells_evicted,
+                              **{name + "_ms": round(1e3 * float(np.median(v[-a.every:])), 4) for name, v in t.items()}}), flush=True)
+    print(json.dumps({"scans": a.scans, "stats": {name: g.stats() for name, g in stores.items()}}), flush=True)
+    for g in stores.values():
+        g.close()
+    h.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scans", type=int, default=1200)
     ap.add_argument("--points", type=int, default=6000)
     ap.add_argument("--every", type=int, default=100)
+    ap.add_argument("--window", default=None, metavar="HX,HY,HZ", help="the windowed-map leg: insert with and without a crop to this window after every insert")
     a = ap.parse_args()
+    if a.window:
+        return window_leg(a)
     rng = np.random.default_rng(7)
     h = capi.Handle()
     g = capi.Grid(h, 3.0, 0.2)
