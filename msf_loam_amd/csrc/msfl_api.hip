@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <utility>
 #include <chrono>
 #include <string>
 #include <vector>
@@ -35,9 +36,16 @@ using namespace msfl;
 
 namespace {
 
+// The three buffer kinds own what they hold: destroying a handle, a map store or a SLAM session frees every one of their members
+// (the owner makes its device current first).
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }   // grow_keep
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     size_t want = std::max(bytes, cap + cap / 2);          // geometric growth: a buffer that grows a little per call
@@ -59,6 +67,10 @@ struct PinRing {
   static constexpr int kSlots = 8;
   PinSlot slot[kSlots];
   int next = 0;
+  PinRing() = default;
+  PinRing(const PinRing&) = delete;
+  PinRing& operator=(const PinRing&) = delete;
+  ~PinRing() { release(); }
   hipError_t upload(void* dst, const void* src, size_t bytes, hipStream_t st) {
     PinSlot& s = slot[next];
     next = (next + 1) % kSlots;
@@ -93,6 +105,10 @@ struct PinRing {
 // memory goes through the runtime's staging path, which stalls for tens of milliseconds once in a while.
 struct PinBuf {
   void* p = nullptr; size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     const size_t want = (std::max<size_t>(std::max(bytes, cap + cap / 2), 4096) + 4095) & ~size_t(4095);
@@ -266,29 +282,27 @@ SolverParams solver_params(const msfl_params& p, int min_corr) {
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
-// ---- msfl_set_uncertainty plumbing shared by every matcher entry point ----
+// ---- What a registration call carries besides its clouds: the info record, the msfl_set_uncertainty sink and the msfl_set_pose_prior
+// records, all on the device.  Every solve site runs reg_check -> reg_open -> solve_outer -> reg_close (the SLAM step fills its
+// RegSinks from the scan's slot instead of reg_open / reg_close).
 static_assert(sizeof(UncRecord) == sizeof(msfl_match_uncertainty), "uncertainty record layout");
-// First thing a matcher call does, before it stages or launches anything: refuse a call with more registrations than the sink holds.
-msfl_status unc_check(msfl_handle* h, int n, const char* who) {
+static_assert(sizeof(PosePrior) == sizeof(msfl_pose_prior), "pose prior record layout");
+static_assert(sizeof(DevMatchInfo) == sizeof(msfl_match_info), "info layout");
+struct RegSinks {
+  DevMatchInfo* info = nullptr;      // never null when `unc` is not: the uncertainty record takes sigma2 from the solve's own final cost
+  UncRecord* unc = nullptr;          // null: feature off
+  const PosePrior* prior = nullptr;  // null: feature off
+  double unc_min_eig = 0.0;
+  RegSinks at(int b) const { return {info ? info + b : nullptr, unc ? unc + b : nullptr, prior ? prior + b : nullptr, unc_min_eig}; }   // a part of a batch
+};
+
+// First thing a matcher call does, before it stages or launches anything: refuse a call with more registrations than the sink holds or
+// than there are prior records, and host prior records with a non-finite entry (device records are checked by the solve kernel:
+// per-scan status MSFL_BAD_ARG).
+msfl_status reg_check(msfl_handle* h, int n, const char* who) {
   if (h->unc_out && n > h->unc_capacity)
     return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_uncertainty sink holds " +
                                       std::to_string(h->unc_capacity));
-  return MSFL_OK;
-}
-// Where the kernel writes the n records of this call (null: feature off).
-msfl_status unc_target(msfl_handle* h, int n, UncRecord** d_unc) {
-  *d_unc = nullptr;
-  if (!h->unc_out) return MSFL_OK;
-  if (h->unc_mem == MSFL_MEM_DEVICE) { *d_unc = reinterpret_cast<UncRecord*>(h->unc_out); return MSFL_OK; }
-  HIPCHK(h, h->unc_dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(UncRecord)));
-  *d_unc = h->unc_dev.as<UncRecord>();
-  return MSFL_OK;
-}
-// ---- msfl_set_pose_prior plumbing shared by every matcher entry point ----
-static_assert(sizeof(PosePrior) == sizeof(msfl_pose_prior), "pose prior record layout");
-// With unc_check, before anything is staged or launched: refuse a call with more registrations than there are records, and host
-// records with a non-finite entry (device records are checked by the solve kernel: per-scan status MSFL_BAD_ARG).
-msfl_status prior_check(msfl_handle* h, int n, const char* who) {
   if (!h->prior_in) return MSFL_OK;
   if (n > h->prior_count)
     return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, msfl_set_pose_prior gave " +
@@ -304,23 +318,90 @@ msfl_status prior_check(msfl_handle* h, int n, const char* who) {
   }
   return MSFL_OK;
 }
-// The records of this call on the device (null: feature off): the caller's device pointer, or a copy of its host records on stream st.
-msfl_status prior_target(msfl_handle* h, int n, hipStream_t st, const PosePrior** d_prior) {
-  *d_prior = nullptr;
-  if (!h->prior_in || n <= 0) return MSFL_OK;
-  if (h->prior_mem == MSFL_MEM_DEVICE) { *d_prior = reinterpret_cast<const PosePrior*>(h->prior_in); return MSFL_OK; }
-  HIPCHK(h, h->prior_dev.reserve((size_t)n * sizeof(PosePrior)));
-  HIPCHK(h, h->pin.upload(h->prior_dev.p, h->prior_in, (size_t)n * sizeof(PosePrior), st));
-  *d_prior = h->prior_dev.as<PosePrior>();
+
+inline bool unc_host(const msfl_handle* h) { return h->unc_out && h->unc_mem == MSFL_MEM_HOST; }
+
+// Where the kernels of this call of n registrations find their sinks: the caller's device pointers, or device staging of its host ones
+// (the prior records are copied on stream st, ahead of the clearing of the info records).  want_info: the caller asked for the info records.
+msfl_status reg_open(msfl_handle* h, int n, hipStream_t st, bool want_info, RegSinks* k) {
+  *k = RegSinks{};
+  k->unc_min_eig = h->unc_min_eigenvalue;
+  if (h->unc_out && h->unc_mem == MSFL_MEM_DEVICE) k->unc = reinterpret_cast<UncRecord*>(h->unc_out);
+  else if (h->unc_out) {
+    HIPCHK(h, h->unc_dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(UncRecord)));
+    k->unc = h->unc_dev.as<UncRecord>();
+  }
+  if (h->prior_in && n > 0 && h->prior_mem == MSFL_MEM_DEVICE) k->prior = reinterpret_cast<const PosePrior*>(h->prior_in);
+  else if (h->prior_in && n > 0) {
+    HIPCHK(h, h->prior_dev.reserve((size_t)n * sizeof(PosePrior)));
+    HIPCHK(h, h->pin.upload(h->prior_dev.p, h->prior_in, (size_t)n * sizeof(PosePrior), st));
+    k->prior = h->prior_dev.as<PosePrior>();
+  }
+  if (want_info || k->unc) {
+    HIPCHK(h, h->info.reserve((size_t)n * sizeof(DevMatchInfo)));
+    HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)n * sizeof(DevMatchInfo), st));
+    k->info = h->info.as<DevMatchInfo>();
+  }
   return MSFL_OK;
 }
 
-// A host sink is copied like `info`; the caller synchronises afterwards (unc_host(h) tells it to).
-inline bool unc_host(const msfl_handle* h) { return h->unc_out && h->unc_mem == MSFL_MEM_HOST; }
-msfl_status unc_deliver(msfl_handle* h, int n, const UncRecord* d_unc) {
-  if (unc_host(h) && d_unc && n > 0)
-    HIPCHK(h, hipMemcpyAsync(h->unc_out, d_unc, (size_t)n * sizeof(UncRecord), hipMemcpyDeviceToHost, h->stream));
+// What goes back to the caller: poses and status of a host-memory call, the info records, a host uncertainty sink; then the stream is
+// waited for if anything went to host memory.
+msfl_status reg_close(msfl_handle* h, int n, msfl_mem mem, double* poses_io, const double* d_poses, int* status, const int* d_status,
+                      msfl_match_info* info, const RegSinks& k) {
+  hipStream_t st = h->stream;
+  if (mem == MSFL_MEM_HOST) {
+    HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+  }
+  if (info) HIPCHK(h, hipMemcpyAsync(info, k.info, (size_t)n * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
+  if (unc_host(h) && k.unc && n > 0) HIPCHK(h, hipMemcpyAsync(h->unc_out, k.unc, (size_t)n * sizeof(UncRecord), hipMemcpyDeviceToHost, st));
+  if (mem == MSFL_MEM_HOST || info || unc_host(h)) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
+}
+
+// The outer loop of every registration: per outer iteration the site's own association launches (`assoc(it)`, which may fail), then the
+// LM solve of all n problems; after the last one the uncertainty records, if asked for.  BLOCK: the site's solve workgroup.
+template <int BLOCK, class Assoc>
+msfl_status solve_outer(msfl_handle* h, int n, const BatchView& bv, const double* pprime, double* d_poses, int* d_status, const RegSinks& k,
+                        const SolverParams& sp, int n_outer, Assoc&& assoc) {
+  hipStream_t st = h->stream;
+  const double* records = h->records.as<double>();
+  for (int it = 0; it < n_outer; it++) {
+    { const msfl_status as = assoc(it); if (as) return as; }
+    ScopedTimer timer(h, T_SOLVE);
+    launch_lm_solve<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, it, sp, k.prior);
+  }
+  launch_uncertainty<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, n_outer - 1, sp, k.unc_min_eig, k.unc, k.prior);
+  HIPCHK(h, hipGetLastError());
+  return MSFL_OK;
+}
+
+// [corner_off | surf_off | rec_off] (n + 1 ints each) of a batch of n scans from its host offsets, into h->in_off; *n_rec: its records.
+msfl_status upload_batch_offsets(msfl_handle* h, int n, const int* corner_off, const int* surf_off, int* n_rec) {
+  std::vector<int> offs(3 * (size_t)(n + 1));
+  for (int b = 0; b <= n; b++) {
+    offs[b] = corner_off[b];
+    offs[(n + 1) + b] = surf_off[b];
+    offs[2 * (n + 1) + b] = corner_off[b] - corner_off[0] + surf_off[b] - surf_off[0];
+    if (b > 0 && (corner_off[b] < corner_off[b - 1] || surf_off[b] < surf_off[b - 1]))
+      return fail(h, MSFL_BAD_ARG, "offset arrays must be non-decreasing");
+  }
+  *n_rec = offs[2 * (n + 1) + n];
+  return upload_in_off(h, offs.data(), offs.size(), h->stream);
+}
+
+// The view over a device offset table whose rows corner_off, surf_off and rec_off lie `stride` ints apart.  dyn = 1: the SLAM step's
+// device-written table (BatchView::dyn: n_records and n_surf_total are then capacities, c0 = s0 = 0).
+BatchView batch_view(const float4* d_corner, const float4* d_surf, const int* d_table, int stride, int n_scans, int n_records, int c0, int s0,
+                     int n_surf_total, int dyn = 0) {
+  BatchView bv;
+  bv.corner = d_corner; bv.corner_off = d_table;
+  bv.surf = d_surf; bv.surf_off = d_table + stride;
+  bv.rec_off = d_table + 2 * stride;
+  bv.n_scans = n_scans; bv.n_records = n_records;
+  bv.c0 = c0; bv.s0 = s0; bv.n_surf_total = n_surf_total; bv.dyn = dyn;
+  return bv;
 }
 
 __global__ void __launch_bounds__(256) zero_ints_kernel(int* __restrict__ p, int n) {
@@ -539,60 +620,36 @@ void s_launch_assoc(msfl_handle* h, const BatchView& bv_all, const double* d_pos
 // `n_chunks` > 1: the features of scans [chunk_b[c], chunk_b[c + 1]) are valid on the device once `chunk_ev[c]` has
 // fired (host-buffer batches: they arrive over PCIe on another stream).  The first association pass then runs chunk by
 // chunk behind the copies; everything after it sees the whole batch.
-msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner, const int* h_corner_off,
-                                  const float4* d_surf, const int* h_surf_off, double* d_poses, int* d_status,
-                                  DevMatchInfo* d_info, const DeskewView* deskew, int n_chunks = 1, const int* chunk_b = nullptr,
-                                  hipEvent_t* chunk_ev = nullptr, const std::function<hipError_t(int)>* enqueue_chunk = nullptr,
-                                  UncRecord* d_unc = nullptr, const PosePrior* d_prior = nullptr) {
-  hipStream_t st = h->stream;
-  // offsets -> device: [corner_off (B+1) | surf_off (B+1) | rec_off (B+1)]
-  std::vector<int> offs(3 * (size_t)(B + 1));
-  for (int b = 0; b <= B; b++) {
-    offs[b] = h_corner_off[b];
-    offs[(B + 1) + b] = h_surf_off[b];
-    offs[2 * (B + 1) + b] = h_corner_off[b] - h_corner_off[0] + h_surf_off[b] - h_surf_off[0];
-    if (b > 0 && (h_corner_off[b] < h_corner_off[b - 1] || h_surf_off[b] < h_surf_off[b - 1]))
-      return fail(h, MSFL_BAD_ARG, "offset arrays must be non-decreasing");
-  }
-  const int n_rec = offs[2 * (B + 1) + B];
-  { const msfl_status us = upload_in_off(h, offs.data(), offs.size(), st); if (us) return us; }
+msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner, const int* h_corner_off, const float4* d_surf,
+                                  const int* h_surf_off, double* d_poses, int* d_status, const RegSinks& sinks, const DeskewView* deskew,
+                                  int n_chunks = 1, const int* chunk_b = nullptr, hipEvent_t* chunk_ev = nullptr,
+                                  const std::function<hipError_t(int)>* enqueue_chunk = nullptr) {
+  int n_rec = 0;
+  { const msfl_status us = upload_batch_offsets(h, B, h_corner_off, h_surf_off, &n_rec); if (us) return us; }
   HIPCHK(h, h->records.reserve(std::max<size_t>(1, (size_t)n_rec) * 6 * sizeof(double)));
   HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)n_rec) * 5 * sizeof(int)));
-  BatchView bv;
-  bv.corner = d_corner; bv.corner_off = h->in_off.as<int>();
-  bv.surf = d_surf; bv.surf_off = h->in_off.as<int>() + (B + 1);
-  bv.rec_off = h->in_off.as<int>() + 2 * (B + 1);
-  bv.n_scans = B; bv.n_records = n_rec;
-  bv.c0 = h_corner_off[0]; bv.s0 = h_surf_off[0]; bv.n_surf_total = h_surf_off[B] - h_surf_off[0];
+  const BatchView bv = batch_view(d_corner, d_surf, h->in_off.as<int>(), B + 1, B, n_rec, h_corner_off[0], h_surf_off[0], h_surf_off[B] - h_surf_off[0]);
   DeskewView dv{};
   if (deskew) {
     dv = *deskew;
     HIPCHK(h, h->pprime.reserve(std::max<size_t>(1, (size_t)n_rec) * 3 * sizeof(double)));
     dv.pprime = h->pprime.as<double>();
   }
-  const SolverParams sp = solver_params(h->prm, 0);
-  for (int it = 0; it < h->prm.outer_iterations; it++) {
+  const auto rec_at = [&](int b) { return h_corner_off[b] - h_corner_off[0] + h_surf_off[b] - h_surf_off[0]; };   // rec_off[b]
+  return solve_outer<kLmBlock>(h, B, bv, dv.pprime, d_poses, d_status, sinks, solver_params(h->prm, 0), h->prm.outer_iterations, [&](int it) -> msfl_status {
     if (it == 0 && (n_chunks > 1 || enqueue_chunk)) {
       for (int c = 0; c < n_chunks; c++) {
         // the copy of chunk c is ENQUEUED here, right before the kernels that wait for it: a copy from pageable memory
         // holds the calling thread until it is staged, and the kernels of chunk c - 1 must be in the queue by then
         if (enqueue_chunk) HIPCHK(h, (*enqueue_chunk)(c));
-        HIPCHK(h, hipStreamWaitEvent(st, chunk_ev[c], 0));
-        s_launch_assoc(h, bv, d_poses, d_status, deskew != nullptr, dv, n_rec, nullptr, offs[2 * (B + 1) + chunk_b[c]], offs[2 * (B + 1) + chunk_b[c + 1]]);
+        HIPCHK(h, hipStreamWaitEvent(h->stream, chunk_ev[c], 0));
+        s_launch_assoc(h, bv, d_poses, d_status, deskew != nullptr, dv, n_rec, nullptr, rec_at(chunk_b[c]), rec_at(chunk_b[c + 1]));
       }
     } else if (n_rec > 0) {
       s_launch_assoc(h, bv, d_poses, d_status, deskew != nullptr, dv, n_rec, nullptr, 0, -1, it > 0);
     }
-    {
-      ScopedTimer timer(h, T_SOLVE);
-      launch_lm_solve<kLmBlock>(st, B, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr,
-                                (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp, d_prior);
-    }
-  }
-  launch_uncertainty<kLmBlock>(st, B, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr, h->records.as<double>(), d_poses, d_status,
-                               d_info, h->prm.outer_iterations - 1, sp, h->unc_min_eigenvalue, d_unc, d_prior);
-  HIPCHK(h, hipGetLastError());
-  return MSFL_OK;
+    return MSFL_OK;
+  });
 }
 
 msfl_status check_map(msfl_handle* h) {
@@ -703,29 +760,14 @@ void msfl_destroy(msfl_handle* h) {
   (void)hipStreamSynchronize(h->stream);
   collect_timing(h);
   for (auto e : h->free_events) (void)hipEventDestroy(e);
-  h->pin.release();
-  h->readback.release();
   if (h->copy_stream) { (void)hipStreamDestroy(h->copy_stream); for (auto e : h->copy_ev) if (e) (void)hipEventDestroy(e); }
   for (MapIndex* mi : {&h->map_c, &h->map_s}) {
     if (mi->want_pending) (void)hipEventSynchronize(mi->want_ev);
     if (mi->want_ev) (void)hipEventDestroy(mi->want_ev);
     if (mi->want_host) (void)hipHostFree(mi->want_host);
   }
-  DevBuf* bufs[] = {&h->map_c.sorted, &h->map_c.cell_start, &h->map_s.sorted, &h->map_s.cell_start, &h->map_c.pos_of, &h->map_s.pos_of,
-                    &h->map_c.gdesc, &h->map_s.gdesc, &h->map_c.bbox, &h->map_s.bbox, &h->in_corner,
-                    &h->in_surf, &h->in_off, &h->poses, &h->status, &h->info, &h->records, &h->pprime, &h->nn,
-                    &h->idx_cell_of, &h->idx_count, &h->idx_scanned, &h->idx_bbox, &h->idx_cub, &h->idx_stage, &h->knn_count, &h->unc_dev, &h->prior_dev};
-  for (auto* b : bufs) b->release();
-  for (auto& b : h->dk) b.release();
-  for (auto& b : h->ex) b.release();
-  for (auto& b : h->od) b.release();
-  for (auto& b : h->pp) b.release();
-  for (auto& b : h->pr) b.release();
-  for (auto& b : h->vb) b.release();
-  for (auto& b : h->vb2) b.release();
-  h->vox_big_scratch.release(); h->vox_big_list.release();
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-  delete h;
+  delete h;                               // every DevBuf / PinBuf member and the pinned ring free themselves
 }
 
 msfl_status msfl_set_stream(msfl_handle* h, void* hip_stream) {
@@ -856,8 +898,7 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
   if (B < 0 || (B > 0 && (!corner_off || !surf_off || !poses_io)))
     return fail(h, MSFL_BAD_ARG, "msfl_match_scan2map_batch: null argument");
   if (B == 0) return MSFL_OK;
-  msfl_status s = unc_check(h, B, "msfl_match_scan2map"); if (s) return s;
-  s = prior_check(h, B, "msfl_match_scan2map"); if (s) return s;
+  msfl_status s = reg_check(h, B, "msfl_match_scan2map"); if (s) return s;
   s = check_map(h); if (s) return s;
   hipStream_t st = h->stream;
   const int c0 = corner_off[0], s0 = surf_off[0];
@@ -893,17 +934,8 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
   // (a kernel, not hipMemsetAsync: replayed from a captured HIP graph the memset node of a 24-byte status array wrote host-pointer
   // patterns into it from the second replay on -- ROCm 7.2, tests/test_gpu_scan2map.py::test_the_batch_step_replays_from_a_captured_graph)
   hipLaunchKernelGGL(zero_ints_kernel, dim3(div_up(B, 256)), dim3(256), 0, st, d_status, B);
-  DevMatchInfo* d_info = nullptr;
-  UncRecord* d_unc = nullptr;
-  s = unc_target(h, B, &d_unc); if (s) return s;
-  const PosePrior* d_prior = nullptr;
-  s = prior_target(h, B, st, &d_prior); if (s) return s;
-  if (info || d_unc) {                    // the uncertainty record takes sigma2 from the solve's own final cost
-    static_assert(sizeof(DevMatchInfo) == sizeof(msfl_match_info), "info layout");
-    HIPCHK(h, h->info.reserve((size_t)B * sizeof(DevMatchInfo)));
-    HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)B * sizeof(DevMatchInfo), st));
-    d_info = h->info.as<DevMatchInfo>();
-  }
+  RegSinks sinks;
+  s = reg_open(h, B, st, info != nullptr, &sinks); if (s) return s;
   DeskewView dv{}; const DeskewView* dvp = nullptr;
   if (deskew) {
     // the four per-feature arrays are indexed like the feature arrays (corner_off / surf_off), velocity per scan
@@ -926,7 +958,7 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
     dvp = &dv;
   }
   if (n_chunks == 1) {
-    s = match_scan2map_device(h, B, d_corner, co.data(), d_surf, so.data(), d_poses, d_status, d_info, dvp, 1, nullptr, nullptr, nullptr, d_unc, d_prior);
+    s = match_scan2map_device(h, B, d_corner, co.data(), d_surf, so.data(), d_poses, d_status, sinks, dvp);
     if (s) return s;
   } else {
     if (!h->copy_stream) {
@@ -956,19 +988,11 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
         return e;
       };
       s = match_scan2map_device(h, Bp, d_corner, co.data() + pb0, d_surf, so.data() + pb0, d_poses + 7 * (size_t)pb0, d_status + pb0,
-                                d_info ? d_info + pb0 : nullptr, nullptr, ns_p, sub_b, h->copy_ev, &enqueue_chunk, d_unc ? d_unc + pb0 : nullptr,
-                                d_prior ? d_prior + pb0 : nullptr);
+                                sinks.at(pb0), nullptr, ns_p, sub_b, h->copy_ev, &enqueue_chunk);
       if (s) return s;
     }
   }
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-  }
-  if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, (size_t)B * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
-  s = unc_deliver(h, B, d_unc); if (s) return s;
-  if (mem == MSFL_MEM_HOST || info || unc_host(h)) HIPCHK(h, hipStreamSynchronize(st));
-  return MSFL_OK;
+  return reg_close(h, B, mem, poses_io, d_poses, status, d_status, info, sinks);
 }
 
 msfl_status msfl_match_scan2map_batch(msfl_handle* h, int n_scans, const msfl_point* corner, const int* corner_off,
@@ -1027,13 +1051,10 @@ static msfl_status stage_single(msfl_handle* h, const msfl_point* corner, int n_
   if (n_surf) HIPCHK(h, hipMemcpyAsync(h->in_surf.p, surf, (size_t)n_surf * sizeof(float4), hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemcpyAsync(h->poses.p, pose, 7 * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(h, hipMemsetAsync(h->status.p, 0, sizeof(int), st));
-  const int offs[6] = {0, n_corner, 0, n_surf, 0, n_corner + n_surf};
-  { const msfl_status us = upload_in_off(h, offs, 6, st); if (us) return us; }
-  bv.corner = h->in_corner.as<float4>(); bv.corner_off = h->in_off.as<int>();
-  bv.surf = h->in_surf.as<float4>(); bv.surf_off = h->in_off.as<int>() + 2;
-  bv.rec_off = h->in_off.as<int>() + 4;
-  bv.n_scans = 1; bv.n_records = n_corner + n_surf;
-  bv.c0 = 0; bv.s0 = 0; bv.n_surf_total = n_surf;
+  const int co[2] = {0, n_corner}, so[2] = {0, n_surf};
+  int n_rec = 0;
+  { const msfl_status us = upload_batch_offsets(h, 1, co, so, &n_rec); if (us) return us; }
+  bv = batch_view(h->in_corner.as<float4>(), h->in_surf.as<float4>(), h->in_off.as<int>(), 2, 1, n_rec, 0, 0, n_surf);
   return MSFL_OK;
 }
 
@@ -1062,40 +1083,21 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
   if (n_corner < 0 || n_surf < 0 || !pose_io || (n_corner + n_surf > 0 && !records) || (n_corner && !corner) || (n_surf && !surf))
     return fail(h, MSFL_BAD_ARG, "msfl_solve_records: bad argument");
   const int n = n_corner + n_surf;
-  s = unc_check(h, 1, "msfl_solve_records"); if (s) return s;
-  s = prior_check(h, 1, "msfl_solve_records"); if (s) return s;
+  s = reg_check(h, 1, "msfl_solve_records"); if (s) return s;
   BatchView bv;
   s = stage_single(h, corner, n_corner, surf, n_surf, pose_io, bv); if (s) return s;
-  UncRecord* d_unc = nullptr;
-  s = unc_target(h, 1, &d_unc); if (s) return s;
-  const PosePrior* d_prior = nullptr;
-  s = prior_target(h, 1, h->stream, &d_prior); if (s) return s;
+  RegSinks sinks;
+  s = reg_open(h, 1, h->stream, info != nullptr, &sinks); if (s) return s;
   if (n) {
     HIPCHK(h, h->pprime.reserve((size_t)n * 6 * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(h->pprime.p, records, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(pack_records_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, bv, (const double*)h->pprime.as<double>(),
                        h->records.as<double>());
   }
-  DevMatchInfo* d_info = nullptr;
-  if (info || d_unc) {
-    HIPCHK(h, h->info.reserve(sizeof(DevMatchInfo)));
-    HIPCHK(h, hipMemsetAsync(h->info.p, 0, sizeof(DevMatchInfo), h->stream));
-    d_info = h->info.as<DevMatchInfo>();
-  }
-  const SolverParams sp = solver_params(h->prm, 0);
-  {
-    ScopedTimer timer(h, T_SOLVE);
-    launch_lm_solve<kLmBlock>(h->stream, 1, bv, (const double*)nullptr, (const double*)h->records.as<double>(), h->poses.as<double>(),
-                              h->status.as<int>(), d_info, 0, sp, d_prior);
-  }
-  launch_uncertainty<kLmBlock>(h->stream, 1, bv, nullptr, h->records.as<double>(), h->poses.as<double>(), h->status.as<int>(), d_info, 0, sp,
-                               h->unc_min_eigenvalue, d_unc, d_prior);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(pose_io, h->poses.p, 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, sizeof(DevMatchInfo), hipMemcpyDeviceToHost, h->stream));
-  s = unc_deliver(h, 1, d_unc); if (s) return s;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return MSFL_OK;
+  s = solve_outer<kLmBlock>(h, 1, bv, nullptr, h->poses.as<double>(), h->status.as<int>(), sinks, solver_params(h->prm, 0), 1,
+                            [](int) { return MSFL_OK; });                              // the records are given: nothing to associate
+  if (s) return s;
+  return reg_close(h, 1, MSFL_MEM_HOST, pose_io, h->poses.as<double>(), nullptr, nullptr, info, sinks);   // (host memory: always waited for)
 }
 
 }  // extern "C"

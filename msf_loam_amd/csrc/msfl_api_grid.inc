@@ -43,8 +43,7 @@ msfl_status grow_keep(msfl_handle* h, DevBuf& b, size_t bytes, size_t keep) {
   HIPCHK(h, nb.reserve(std::max(bytes, b.cap + b.cap / 2)));
   if (b.p && keep) HIPCHK(h, hipMemcpyAsync(nb.p, b.p, std::min(keep, b.cap), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  b.release();
-  b = nb;
+  b = std::move(nb);
   return MSFL_OK;
 }
 
@@ -339,11 +338,6 @@ void msfl_grid_destroy(msfl_grid* g) {
   if (!g) return;
   (void)hipSetDevice(g->h->device);
   (void)hipStreamSynchronize(g->h->stream);
-  DevBuf* bufs[] = {&g->state, &g->pool[0], &g->pool[1], &g->ckey[0], &g->ckey[1], &g->cstart[0], &g->cstart[1], &g->ccnt[0], &g->ccnt[1],
-                    &g->cstamp[0], &g->cstamp[1], &g->keys, &g->keys_s, &g->vals, &g->vals_s, &g->head, &g->tpos, &g->xf, &g->xs, &g->t_key, &g->t_ns,
-                    &g->t_old, &g->t_woff, &g->t_rank, &g->t_cnt, &g->cnt, &g->off, &g->stage, &g->pose, &g->report_dev, &g->crop};
-  for (auto* b : bufs) b->release();
-  g->report.release();
   delete g;
 }
 

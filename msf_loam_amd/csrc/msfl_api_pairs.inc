@@ -84,8 +84,7 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
   if (P == 0) return MSFL_OK;
   // the segmented index build launches 2-D over (chunk, pair): HIP caps gridDim.y at 65 535 (ADVICE r04) — say so up front, before any staging
   if (P > 65535) return fail(h, MSFL_CAPACITY, "msfl_match_pairs_batch: at most 65535 pairs per call (got " + std::to_string(P) + "); split the batch");
-  s = unc_check(h, P, "msfl_match_pairs_batch"); if (s) return s;
-  s = prior_check(h, P, "msfl_match_pairs_batch"); if (s) return s;
+  s = reg_check(h, P, "msfl_match_pairs_batch"); if (s) return s;
   for (int p = 0; p < P; p++)
     if (map_corner_off[p + 1] < map_corner_off[p] || map_surf_off[p + 1] < map_surf_off[p] || corner_off[p + 1] < corner_off[p] || surf_off[p + 1] < surf_off[p])
       return fail(h, MSFL_BAD_ARG, "msfl_match_pairs_batch: offset arrays must be non-decreasing");
@@ -134,58 +133,29 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
   int* d_status = status;
   if (mem != MSFL_MEM_DEVICE || !status) { HIPCHK(h, h->status.reserve((size_t)P * sizeof(int))); d_status = h->status.as<int>(); }
   HIPCHK(h, h->pin.upload(d_status, st0.data(), (size_t)P * sizeof(int), st));
-  DevMatchInfo* d_info = nullptr;
-  UncRecord* d_unc = nullptr;
-  s = unc_target(h, P, &d_unc); if (s) return s;
-  const PosePrior* d_prior = nullptr;
-  s = prior_target(h, P, st, &d_prior); if (s) return s;
-  if (info || d_unc) {
-    HIPCHK(h, h->info.reserve((size_t)P * sizeof(DevMatchInfo)));
-    HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)P * sizeof(DevMatchInfo), st));
-    d_info = h->info.as<DevMatchInfo>();
-  }
-  // offsets -> device: [corner_off | surf_off | rec_off], as match_scan2map_device
-  std::vector<int> offs(3 * (size_t)(P + 1));
-  for (int p = 0; p <= P; p++) { offs[p] = co[p]; offs[(P + 1) + p] = so[p]; offs[2 * (P + 1) + p] = co[p] - co[0] + so[p] - so[0]; }
-  const int n_rec = offs[2 * (P + 1) + P];
-  { const msfl_status us = upload_in_off(h, offs.data(), offs.size(), st); if (us) return us; }
+  RegSinks sinks;
+  s = reg_open(h, P, st, info != nullptr, &sinks); if (s) return s;
+  int n_rec = 0;
+  s = upload_batch_offsets(h, P, co.data(), so.data(), &n_rec); if (s) return s;
   HIPCHK(h, h->records.reserve(std::max<size_t>(1, (size_t)n_rec) * 6 * sizeof(double)));
   HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)n_rec) * 5 * sizeof(int)));
-  BatchView bv;
-  bv.corner = d_corner; bv.corner_off = h->in_off.as<int>();
-  bv.surf = d_surf; bv.surf_off = h->in_off.as<int>() + (P + 1);
-  bv.rec_off = h->in_off.as<int>() + 2 * (P + 1);
-  bv.n_scans = P; bv.n_records = n_rec; bv.c0 = co[0]; bv.s0 = so[0]; bv.n_surf_total = so[P] - so[0];
+  const BatchView bv = batch_view(d_corner, d_surf, h->in_off.as<int>(), P + 1, P, n_rec, co[0], so[0], so[P] - so[0]);
   DeskewView dv{};
-  const SolverParams sp = solver_params(h->prm, 0);
   const dim3 grid(std::max(1, div_up(n_rec, kAssocBlock))), block(kAssocBlock);
-  for (int it = 0; it < h->prm.outer_iterations; it++) {
-    if (n_rec > 0) {
-      {
-        ScopedTimer timer(h, it > 0 ? T_ASSOC_SEEDED : T_ASSOC);
-        launch_knn5(h, knn5_scan2map_kernel<false, false, true>, grid, block, bv, d_poses, d_status, dv, h->nn.as<int>(),
-                    nullptr, h->pr[PR_BASE_C].as<int>(), h->pr[PR_BASE_S].as<int>());
-      }
-      {
-        ScopedTimer timer(h, T_FIT);       // nn holds positions in the concatenated sorted maps: the fit gathers as ever
-        hipLaunchKernelGGL(fit_scan2map_kernel<false>, grid, block, 0, st, bv, h->map_c.sorted.as<float4>(), h->map_s.sorted.as<float4>(),
-                           (const int*)h->nn.as<int>(), h->prm.line_eigen_ratio, h->prm.plane_tolerance, dv, h->records.as<double>(), (double*)nullptr);
-      }
+  s = solve_outer<kLmBlock>(h, P, bv, nullptr, d_poses, d_status, sinks, solver_params(h->prm, 0), h->prm.outer_iterations, [&](int it) {
+    if (n_rec <= 0) return MSFL_OK;
+    {
+      ScopedTimer timer(h, it > 0 ? T_ASSOC_SEEDED : T_ASSOC);
+      launch_knn5(h, knn5_scan2map_kernel<false, false, true>, grid, block, bv, d_poses, d_status, dv, h->nn.as<int>(),
+                  nullptr, h->pr[PR_BASE_C].as<int>(), h->pr[PR_BASE_S].as<int>());
     }
-    ScopedTimer timer(h, T_SOLVE);
-    launch_lm_solve<kLmBlock>(st, P, bv, (const double*)nullptr, (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp, d_prior);
-  }
-  launch_uncertainty<kLmBlock>(st, P, bv, nullptr, h->records.as<double>(), d_poses, d_status, d_info, h->prm.outer_iterations - 1, sp,
-                               h->unc_min_eigenvalue, d_unc, d_prior);
-  HIPCHK(h, hipGetLastError());
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)P * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)P * sizeof(int), hipMemcpyDeviceToHost, st));
-  }
-  if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, (size_t)P * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
-  s = unc_deliver(h, P, d_unc); if (s) return s;
-  if (mem == MSFL_MEM_HOST || info || unc_host(h)) HIPCHK(h, hipStreamSynchronize(st));
-  return MSFL_OK;
+    ScopedTimer timer(h, T_FIT);       // nn holds positions in the concatenated sorted maps: the fit gathers as ever
+    hipLaunchKernelGGL(fit_scan2map_kernel<false>, grid, block, 0, st, bv, h->map_c.sorted.as<float4>(), h->map_s.sorted.as<float4>(),
+                       (const int*)h->nn.as<int>(), h->prm.line_eigen_ratio, h->prm.plane_tolerance, dv, h->records.as<double>(), (double*)nullptr);
+    return MSFL_OK;
+  });
+  if (s) return s;
+  return reg_close(h, P, mem, poses_io, d_poses, status, d_status, info, sinks);
 }
 
 }  // extern "C"

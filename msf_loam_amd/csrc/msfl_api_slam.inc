@@ -142,6 +142,21 @@ msfl_status sfail(msfl_slam* s, msfl_status st, const std::string& msg) {
   do { hipError_t e__ = (expr); if (e__ != hipSuccess) return sfail(s, MSFL_HIP_ERROR, std::string(#expr) + ": " + hipGetErrorString(e__)); } while (0)
 #define SCHK(s, h, expr) do { msfl_status st__ = (expr); if (st__) return sfail(s, st__, (h)->last_error); } while (0)
 
+// The getters' preamble.  slam_slot_of: the slot that holds the record of scan `scan_index`, or the error of `who` when the record is
+// no longer (or not yet) held.  slam_slot_ready: wait until that record, and what travels with it, is on the host.
+msfl_status slam_slot_of(msfl_slam* s, int scan_index, const char* who, int* slot) {
+  if (scan_index < 0 || scan_index >= s->n_scans || scan_index < s->n_scans - kSlamSlots)
+    return sfail(s, MSFL_BAD_ARG, std::string(who) + ": that scan's record is no longer (or not yet) held");
+  *slot = scan_index % kSlamSlots;
+  return MSFL_OK;
+}
+msfl_status slam_slot_ready(msfl_slam* s, int scan_index) {
+  SHIP(s, hipSetDevice(s->ho->device));
+  { const msfl_status ws = slam_wait_mapped(s, scan_index); if (ws) return ws; }
+  SHIP(s, hipEventSynchronize(s->ev_done[scan_index % kSlamSlots]));
+  return MSFL_OK;
+}
+
 __global__ void slam_result_kernel(msfl_slam_result* __restrict__ r, int scan_index, int* __restrict__ cnt, const double* __restrict__ poses_k,
                                    const double* __restrict__ odom2map, const int* __restrict__ meta, const int* __restrict__ vmeta,
                                    const int* __restrict__ odo_status) {
@@ -165,19 +180,14 @@ __global__ void slam_result_kernel(msfl_slam_result* __restrict__ r, int scan_in
 
 // MatchScan2Scan on device-resident clouds whose sizes live on the device: the column-grid path of scan2scan_batch_impl for
 // one pair, launches sized by the per-scan caps.  d_off = [ls | lf | sharp | flat | rec] offset pairs.
-msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamScanBuf& cur, const SlamCaps& caps, double* d_pose, DevMatchInfo* d_info,
-                          UncRecord* d_unc = nullptr, double unc_min_eig = 0.0, const PosePrior* d_prior = nullptr) {
+msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamScanBuf& cur, const SlamCaps& caps, double* d_pose, const RegSinks& sinks) {
   hipStream_t st = h->stream;
   const int B = 1;
   const int* d_off = cur.odo_off.as<int>();
   int* d_status = cur.odo_status.as<int>();
   const int n_rec_cap = caps.sharp + caps.flat;
   HIPCHK(h, h->records.reserve(((size_t)4 * caps.flat + (size_t)6 * caps.sharp + 8) * sizeof(double)));
-  BatchView bv;
-  bv.corner = cur.sharp.as<float4>(); bv.corner_off = d_off + 4;
-  bv.surf = cur.flat.as<float4>();    bv.surf_off = d_off + 6;
-  bv.rec_off = d_off + 8;
-  bv.n_scans = B; bv.n_records = n_rec_cap; bv.c0 = 0; bv.s0 = 0; bv.n_surf_total = caps.flat; bv.dyn = 1;
+  const BatchView bv = batch_view(cur.sharp.as<float4>(), cur.flat.as<float4>(), d_off + 4, 2, B, n_rec_cap, 0, 0, caps.flat, 1);
   OdomView ov;
   ov.last_ls = last.ls.as<float4>(); ov.last_ls_ring = last.ls_ring.as<uint16_t>(); ov.last_ls_off = d_off;
   ov.last_lf = last.lf.as<float4>(); ov.last_lf_ring = last.lf_ring.as<uint16_t>(); ov.last_lf_off = d_off + 2;
@@ -215,64 +225,41 @@ msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamSca
     msfl_status bs = launch_odom_bin(h, st, job_lf, job_ls, 2 * B, B, std::min<long long>(caps.less_flat, last.n));
     if (bs != MSFL_OK) return bs;
   }
-  for (int it = 0; it < h->prm.outer_iterations; it++) {
-    {
-      ScopedTimer timer(h, T_ODOM);
-      // pairs the column grid cannot take (mode != 0) and, without the grid, everything
-      hipLaunchKernelGGL(assoc_scan2scan_kernel, dim3(div_up(n_rec_cap, 256), B), dim3(256), 0, st, bv, ov, (const double*)d_pose,
-                         (const int*)d_status, h->records.as<double>(), oix.mode, oie.mode);
-      if (use_grid) {
-        const int plane_blocks = div_up(B, 8) * 8 * oix.tiles, edge_blocks = div_up(B, 8) * 8 * oie.tiles;
-        hipLaunchKernelGGL((assoc_scan2scan_grid_kernel<kSlamOdomLanes>), dim3(plane_blocks + edge_blocks), dim3(kOdomBlock), 0, st, bv, ov, oix, oie,
-                           plane_blocks, (const double*)d_pose, (const int*)d_status, h->records.as<double>());
-      }
+  // one solve on an empty machine: the wide workgroup of the mapping solve (~570 records: one per thread and pass)
+  return solve_outer<kSlamOdomLmBlock>(h, B, bv, nullptr, d_pose, d_status, sinks, sp, h->prm.outer_iterations, [&](int) {
+    ScopedTimer timer(h, T_ODOM);
+    // pairs the column grid cannot take (mode != 0) and, without the grid, everything
+    hipLaunchKernelGGL(assoc_scan2scan_kernel, dim3(div_up(n_rec_cap, 256), B), dim3(256), 0, st, bv, ov, (const double*)d_pose,
+                       (const int*)d_status, h->records.as<double>(), oix.mode, oie.mode);
+    if (use_grid) {
+      const int plane_blocks = div_up(B, 8) * 8 * oix.tiles, edge_blocks = div_up(B, 8) * 8 * oie.tiles;
+      hipLaunchKernelGGL((assoc_scan2scan_grid_kernel<kSlamOdomLanes>), dim3(plane_blocks + edge_blocks), dim3(kOdomBlock), 0, st, bv, ov, oix, oie,
+                         plane_blocks, (const double*)d_pose, (const int*)d_status, h->records.as<double>());
     }
-    {
-      ScopedTimer timer(h, T_SOLVE);
-      // one solve on an empty machine: the wide workgroup of the mapping solve (~570 records: one per thread and pass)
-      launch_lm_solve<kSlamOdomLmBlock>(st, B, bv, (const double*)nullptr, (const double*)h->records.as<double>(), d_pose, d_status, d_info, it, sp,
-                                        d_prior);
-    }
-  }
-  launch_uncertainty<kSlamOdomLmBlock>(st, B, bv, nullptr, h->records.as<double>(), d_pose, d_status, d_info, h->prm.outer_iterations - 1, sp,
-                                       unc_min_eig, d_unc, d_prior);
-  HIPCHK(h, hipGetLastError());
-  return MSFL_OK;
+    return MSFL_OK;
+  });
 }
 
 // MatchScan2Map against the index in h->map_c / map_s, scan clouds and their (device-side) sizes given by in_off.
 // deskew != nullptr: the is_initialized branch (Deskew factors; dq / dp / V / G all device-side, pprime provided here).
 msfl_status scan2map_dyn(msfl_handle* h, const float4* d_corner, const float4* d_surf, const int* d_in_off, int cap_corner, int cap_surf,
-                         double* d_pose, int* d_status, DevMatchInfo* d_info, const DeskewView* deskew = nullptr,
-                         UncRecord* d_unc = nullptr, double unc_min_eig = 0.0, const PosePrior* d_prior = nullptr) {
-  hipStream_t st = h->stream;
+                         double* d_pose, int* d_status, const RegSinks& sinks, const DeskewView* deskew = nullptr) {
   const int n_rec_cap = cap_corner + cap_surf;
   HIPCHK(h, h->records.reserve(((size_t)4 * cap_surf + (size_t)6 * cap_corner + 8) * sizeof(double)));
   HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)n_rec_cap) * 5 * sizeof(int)));
-  BatchView bv;
-  bv.corner = d_corner; bv.corner_off = d_in_off;
-  bv.surf = d_surf;     bv.surf_off = d_in_off + 2;
-  bv.rec_off = d_in_off + 4;
-  bv.n_scans = 1; bv.n_records = n_rec_cap; bv.c0 = 0; bv.s0 = 0; bv.n_surf_total = cap_surf; bv.dyn = 1;
+  const BatchView bv = batch_view(d_corner, d_surf, d_in_off, 2, 1, n_rec_cap, 0, 0, cap_surf, 1);
   DeskewView dv{};
   if (deskew) {
     dv = *deskew;
     HIPCHK(h, h->pprime.reserve(std::max<size_t>(1, (size_t)n_rec_cap) * 3 * sizeof(double)));
     dv.pprime = h->pprime.as<double>();
   }
-  const SolverParams sp = solver_params(h->prm, 0);
-  for (int it = 0; it < h->prm.outer_iterations; it++) {
+  // one solve on an empty machine: 512 threads share its ~4 600 records (the batch kernel's 128 threads per solve are sized
+  // for 1 024 concurrent solves); the per-thread summation order differs from the batch kernel's, the result by rounding
+  return solve_outer<kSlamLmBlock>(h, 1, bv, dv.pprime, d_pose, d_status, sinks, solver_params(h->prm, 0), h->prm.outer_iterations, [&](int) {
     s_launch_assoc(h, bv, d_pose, d_status, deskew != nullptr, dv, n_rec_cap);
-    ScopedTimer timer(h, T_SOLVE);
-    // one solve on an empty machine: 512 threads share its ~4 600 records (the batch kernel's 128 threads per solve are sized
-    // for 1 024 concurrent solves); the per-thread summation order differs from the batch kernel's, the result by rounding
-    launch_lm_solve<kSlamLmBlock>(st, 1, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr, (const double*)h->records.as<double>(),
-                                  d_pose, d_status, d_info, it, sp, d_prior);
-  }
-  launch_uncertainty<kSlamLmBlock>(st, 1, bv, deskew ? (const double*)dv.pprime : (const double*)nullptr, h->records.as<double>(), d_pose, d_status,
-                                   d_info, h->prm.outer_iterations - 1, sp, unc_min_eig, d_unc, d_prior);
-  HIPCHK(h, hipGetLastError());
-  return MSFL_OK;
+    return MSFL_OK;
+  });
 }
 
 // one list through the one-workgroup voxel filter: the 256-thread form, escalating on the device to the 1024-thread one
@@ -375,21 +362,8 @@ void msfl_slam_destroy(msfl_slam* s) {
   if (s->hm) (void)hipStreamSynchronize(s->hm->stream);
   if (s->hc) (void)hipStreamSynchronize(s->hc->stream);
   if (s->hv) (void)hipStreamSynchronize(s->hv->stream);
-  for (auto& b : s->sb) {
-    for (DevBuf* d : {&b.in_pts, &b.in_ring, &b.full, &b.fring, &b.curv, &b.label, &b.idx, &b.cnt, &b.ex_off, &b.sharp, &b.ls, &b.ls_ring, &b.flat,
-                      &b.lf, &b.lf_ring, &b.odo_off, &b.odo_status, &b.poses, &b.vox_c, &b.vox_s, &b.vsum_c, &b.vsum_s, &b.vmeta, &b.map_ls, &b.map_lf,
-                      &b.imu, &b.dqp, &b.full_scan, &b.full_map}) d->release();
-    b.upload.release();
+  for (auto& b : s->sb)
     for (hipEvent_t e : {b.ev_odo, b.ev_pose, b.ev_cready, b.ev_match, b.ev_cdone, b.ev_feat, b.ev_vox}) if (e) (void)hipEventDestroy(e);
-  }
-  for (DevBuf* d : {&s->chain, &s->vox_scratch, &s->vox_big, &s->meta, &s->map_c, &s->map_s}) d->release();
-  for (auto& d : s->rec) d.release();
-  s->rec_host.release();
-  for (auto& b : s->unc) b.release();
-  for (auto& b : s->prior) b.release();
-  for (auto& b : s->win) b.release();
-  s->win_host.release();
-  s->unc_host.release();
   for (auto e : s->ev_done) if (e) (void)hipEventDestroy(e);
   if (s->gc) msfl_grid_destroy(s->gc);
   if (s->gs) msfl_grid_destroy(s->gs);
@@ -480,12 +454,9 @@ msfl_status msfl_slam_create(const msfl_params* params, const msfl_slam_config* 
 
 msfl_status msfl_slam_get_result(msfl_slam* s, int scan_index, msfl_slam_result* result) {
   if (!s || !result) return MSFL_BAD_ARG;
-  if (scan_index < 0 || scan_index >= s->n_scans || scan_index < s->n_scans - kSlamSlots)
-    return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_result: that scan's record is no longer (or not yet) held");
-  SHIP(s, hipSetDevice(s->ho->device));
-  const int slot = scan_index % kSlamSlots;
-  { const msfl_status ws = slam_wait_mapped(s, scan_index); if (ws) return ws; }
-  SHIP(s, hipEventSynchronize(s->ev_done[slot]));
+  int slot;
+  { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_result", &slot); if (rs) return rs; }
+  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
   { std::lock_guard<std::mutex> gl(s->mu_grid); slam_harvest(s, false); }
   *result = s->rec_host.as<msfl_slam_result>()[slot];
   return MSFL_OK;
@@ -542,15 +513,12 @@ msfl_status msfl_slam_set_map_window(msfl_slam* s, const int half_cells[3], int 
 
 msfl_status msfl_slam_get_map_window(msfl_slam* s, int scan_index, msfl_grid_crop_info* corner, msfl_grid_crop_info* surf) {
   if (!s) return MSFL_BAD_ARG;
-  if (scan_index < 0 || scan_index >= s->n_scans || scan_index < s->n_scans - kSlamSlots)
-    return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_map_window: that scan's record is no longer (or not yet) held");
-  const int slot = scan_index % kSlamSlots;
+  int slot;
+  { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_map_window", &slot); if (rs) return rs; }
   if (corner) std::memset(corner, 0, sizeof(*corner));
   if (surf) std::memset(surf, 0, sizeof(*surf));
   if (!s->win_held[slot]) return MSFL_OK;                           // no crop ran on that scan
-  SHIP(s, hipSetDevice(s->ho->device));
-  { const msfl_status ws = slam_wait_mapped(s, scan_index); if (ws) return ws; }
-  SHIP(s, hipEventSynchronize(s->ev_done[slot]));
+  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
   const msfl_grid_crop_info* w = s->win_host.as<msfl_grid_crop_info>() + 2 * slot;
   if (corner) *corner = w[0];
   if (surf) *surf = w[1];
@@ -559,13 +527,10 @@ msfl_status msfl_slam_get_map_window(msfl_slam* s, int scan_index, msfl_grid_cro
 
 msfl_status msfl_slam_get_uncertainty(msfl_slam* s, int scan_index, msfl_match_uncertainty* odometry, msfl_match_uncertainty* mapping) {
   if (!s) return MSFL_BAD_ARG;
-  if (scan_index < 0 || scan_index >= s->n_scans || scan_index < s->n_scans - kSlamSlots)
-    return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_uncertainty: that scan's record is no longer (or not yet) held");
-  const int slot = scan_index % kSlamSlots;
+  int slot;
+  { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_uncertainty", &slot); if (rs) return rs; }
   if (!s->unc_held[slot]) return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_uncertainty: that scan was fed with msfl_slam_set_uncertainty off");
-  SHIP(s, hipSetDevice(s->ho->device));
-  { const msfl_status ws = slam_wait_mapped(s, scan_index); if (ws) return ws; }
-  SHIP(s, hipEventSynchronize(s->ev_done[slot]));
+  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
   const msfl_match_uncertainty* u = s->unc_host.as<msfl_match_uncertainty>() + 2 * slot;
   if (odometry) *odometry = u[0];
   if (mapping) *mapping = u[1];
@@ -577,10 +542,8 @@ msfl_status msfl_slam_get_clouds(msfl_slam* s, int scan_index, msfl_slam_clouds*
   if (!s->cfg.keep_clouds) return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_clouds: the pipeline was created without msfl_slam_config.keep_clouds");
   if (scan_index < 0 || scan_index >= s->n_scans || scan_index < s->n_scans - 2)
     return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_clouds: the clouds of a scan are held until the scan after next is fed");
-  SHIP(s, hipSetDevice(s->ho->device));
-  const int slot = scan_index % kSlamSlots;
-  { const msfl_status ws = slam_wait_mapped(s, scan_index); if (ws) return ws; }
-  SHIP(s, hipEventSynchronize(s->ev_done[slot]));
+  const int slot = scan_index % kSlamSlots;                         // (its own window: the clouds live in the two buffer sets)
+  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
   const SlamScanBuf& b = s->sb[scan_index & 1];
   const msfl_slam_result& r = s->rec_host.as<msfl_slam_result>()[slot];
   const bool ok = r.status_extract == MSFL_OK;
@@ -687,8 +650,9 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   };
   slam_harvest(s, false);
   msfl_slam_result* rec = s->rec[slot].as<msfl_slam_result>();
-  UncRecord* unc_map = jb.unc ? s->unc[slot].as<UncRecord>() + 1 : nullptr;
-  const PosePrior* prior_map = jb.prior_map ? s->prior[slot].as<PosePrior>() + 1 : nullptr;   // uploaded ahead of cur.ev_odo
+  // the slot's second records are the mapping match's (the prior was uploaded ahead of cur.ev_odo)
+  const RegSinks map_sinks{reinterpret_cast<DevMatchInfo*>(&rec->mapping), jb.unc ? s->unc[slot].as<UncRecord>() + 1 : nullptr,
+                           jb.prior_map ? s->prior[slot].as<PosePrior>() + 1 : nullptr, jb.unc_min_eig};
   const SlamImuDev* d_imu = cur.imu.as<SlamImuDev>();
   const int cap_ls = std::min(n, s->caps.less_sharp), cap_lf = std::min(n, s->caps.less_flat);
   double* chain = s->chain.as<double>();
@@ -740,11 +704,9 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
     DeskewView dv{};
     dv.corner_dq = dq_c; dv.corner_dp = dp_c; dv.surf_dq = dq_s; dv.surf_dp = dp_s;
     dv.V = d_imu->velocity; dv.G_dev = d_imu->gravity;
-    SCHK(s, hm, scan2map_dyn(hm, cur.vox_c.as<float4>(), cur.vox_s.as<float4>(), meta + META_OFF, cap_ls, n, pose_map,
-                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), &dv, unc_map, jb.unc_min_eig, prior_map));
+    SCHK(s, hm, scan2map_dyn(hm, cur.vox_c.as<float4>(), cur.vox_s.as<float4>(), meta + META_OFF, cap_ls, n, pose_map, meta + META_STATUS, map_sinks, &dv));
   } else {
-    SCHK(s, hm, scan2map_dyn(hm, cur.vox_c.as<float4>(), cur.vox_s.as<float4>(), meta + META_OFF, cap_ls, n, pose_map,
-                             meta + META_STATUS, reinterpret_cast<DevMatchInfo*>(&rec->mapping), nullptr, unc_map, jb.unc_min_eig, prior_map));
+    SCHK(s, hm, scan2map_dyn(hm, cur.vox_c.as<float4>(), cur.vox_s.as<float4>(), meta + META_OFF, cap_ls, n, pose_map, meta + META_STATUS, map_sinks));
   }
   hipLaunchKernelGGL(slam_map_pose_kernel, dim3(1), dim3(1), 0, sm, odom2map, (const double*)poses_k, pose_map, 1);          // TransformUpdate
   if (imu_mode == 2)    // DoUndistort (laser_mapping.cc:197-211) on the clouds InsertScan2Map is about to insert
@@ -905,8 +867,9 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   double* chain = s->chain.as<double>();
   double* poses_k = cur.poses.as<double>();
   if (k > 0) {                                                   // laser_odometry.cc:72-75: the first scan only initialises
-    SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, reinterpret_cast<DevMatchInfo*>(&rec->odometry),
-                              unc ? s->unc[slot].as<UncRecord>() : nullptr, unc_min_eig, prior_odo ? s->prior[slot].as<PosePrior>() : nullptr));
+    const RegSinks odo_sinks{reinterpret_cast<DevMatchInfo*>(&rec->odometry), unc ? s->unc[slot].as<UncRecord>() : nullptr,
+                             prior_odo ? s->prior[slot].as<PosePrior>() : nullptr, unc_min_eig};
+    SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, odo_sinks));
   }
   hipLaunchKernelGGL(slam_odom_pose_kernel, dim3(1), dim3(1), 0, so, (const double*)chain, chain + 7, poses_k, poses_k + 14,
                      (const int*)cur.cnt.as<int>(), k == 0 ? 1 : 0);

@@ -203,8 +203,7 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
                                  int* status, msfl_match_info* info, msfl_mem mem) {
   if (B < 0 || (B > 0 && (!c0 || !c1 || !c2 || !c3 || !poses_io))) return fail(h, MSFL_BAD_ARG, "msfl_match_scan2scan_batch: null argument");
   if (B == 0) return MSFL_OK;
-  { const msfl_status us = unc_check(h, B, "msfl_match_scan2scan"); if (us) return us; }
-  { const msfl_status us = prior_check(h, B, "msfl_match_scan2scan"); if (us) return us; }
+  { const msfl_status us = reg_check(h, B, "msfl_match_scan2scan"); if (us) return us; }
   const msfl_ring_cloud_batch* cl[4] = {c0, c1, c2, c3};
   hipStream_t st = h->stream;
   for (int k = 0; k < 4; k++) {
@@ -250,23 +249,12 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
   if (mem == MSFL_MEM_DEVICE && status) d_status = status;
   else { HIPCHK(h, h->od[OD_STATUS].reserve((size_t)B * sizeof(int))); d_status = h->od[OD_STATUS].as<int>(); }
   HIPCHK(h, hipMemsetAsync(d_status, 0, (size_t)B * sizeof(int), st));
-  DevMatchInfo* d_info = nullptr;
-  UncRecord* d_unc = nullptr;
-  { const msfl_status us = unc_target(h, B, &d_unc); if (us) return us; }
-  const PosePrior* d_prior = nullptr;
-  { const msfl_status us = prior_target(h, B, st, &d_prior); if (us) return us; }
-  if (info || d_unc) {
-    HIPCHK(h, h->info.reserve((size_t)B * sizeof(DevMatchInfo)));
-    HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)B * sizeof(DevMatchInfo), st));
-    d_info = h->info.as<DevMatchInfo>();
-  }
+  RegSinks sinks;
+  { const msfl_status us = reg_open(h, B, st, info != nullptr, &sinks); if (us) return us; }
   HIPCHK(h, h->records.reserve(std::max<size_t>(1, (size_t)n_rec) * 6 * sizeof(double)));
-  BatchView bv;
-  bv.corner = d_pts[2]; bv.corner_off = d_off + 2 * (B + 1);
-  bv.surf = d_pts[3];   bv.surf_off = d_off + 3 * (B + 1);
-  bv.rec_off = d_off + 4 * (B + 1);
-  bv.n_scans = B; bv.n_records = n_rec;
-  bv.c0 = offs[2 * (B + 1)]; bv.s0 = offs[3 * (B + 1)]; bv.n_surf_total = offs[3 * (B + 1) + B] - offs[3 * (B + 1)];
+  // the current scan's sharp / flat lists are the problem's corner / surf clouds: rows 2, 3 and 4 of the table
+  const BatchView bv = batch_view(d_pts[2], d_pts[3], d_off + 2 * (B + 1), B + 1, B, n_rec, offs[2 * (B + 1)], offs[3 * (B + 1)],
+                                  offs[3 * (B + 1) + B] - offs[3 * (B + 1)]);
   OdomView ov;
   ov.last_ls = d_pts[0]; ov.last_ls_ring = d_ring[0]; ov.last_ls_off = d_off;
   ov.last_lf = d_pts[1]; ov.last_lf_ring = d_ring[1]; ov.last_lf_off = d_off + (B + 1);
@@ -321,39 +309,25 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
     msfl_status bs = launch_odom_bin(h, st, job_lf, job_ls, use_grid_e ? 2 * B : B, B, longest);     // both families in one launch
     if (bs != MSFL_OK) return bs;
   }
-  for (int it = 0; it < h->prm.outer_iterations; it++) {
-    if (max_q > 0) {
-      ScopedTimer timer(h, T_ODOM);
-      if (latency_path) {
-        hipLaunchKernelGGL(assoc_scan2scan_wave_kernel, dim3(div_up(max_q, 4), B), dim3(256), 0, st, bv, ov,
-                           (const double*)d_poses, (const int*)d_status, h->records.as<double>());
-      } else {
-        hipLaunchKernelGGL(assoc_scan2scan_kernel, dim3(div_up(max_q, 256), B), dim3(256), 0, st, bv, ov,
-                           (const double*)d_poses, (const int*)d_status, h->records.as<double>(), oix.mode, oie.mode);
-        if (use_grid) {
-          const int plane_blocks = div_up(B, 8) * 8 * oix.tiles, edge_blocks = use_grid_e ? div_up(B, 8) * 8 * oie.tiles : 0;
-          hipLaunchKernelGGL((assoc_scan2scan_grid_kernel<kOdomLanes>), dim3(plane_blocks + edge_blocks), dim3(kOdomBlock), 0, st, bv, ov, oix, oie,
-                             plane_blocks, (const double*)d_poses, (const int*)d_status, h->records.as<double>());
-        }
+  const msfl_status ss = solve_outer<kOdomLmBlock>(h, B, bv, nullptr, d_poses, d_status, sinks, sp, h->prm.outer_iterations, [&](int) {
+    if (max_q <= 0) return MSFL_OK;
+    ScopedTimer timer(h, T_ODOM);
+    if (latency_path) {
+      hipLaunchKernelGGL(assoc_scan2scan_wave_kernel, dim3(div_up(max_q, 4), B), dim3(256), 0, st, bv, ov,
+                         (const double*)d_poses, (const int*)d_status, h->records.as<double>());
+    } else {
+      hipLaunchKernelGGL(assoc_scan2scan_kernel, dim3(div_up(max_q, 256), B), dim3(256), 0, st, bv, ov,
+                         (const double*)d_poses, (const int*)d_status, h->records.as<double>(), oix.mode, oie.mode);
+      if (use_grid) {
+        const int plane_blocks = div_up(B, 8) * 8 * oix.tiles, edge_blocks = use_grid_e ? div_up(B, 8) * 8 * oie.tiles : 0;
+        hipLaunchKernelGGL((assoc_scan2scan_grid_kernel<kOdomLanes>), dim3(plane_blocks + edge_blocks), dim3(kOdomBlock), 0, st, bv, ov, oix, oie,
+                           plane_blocks, (const double*)d_poses, (const int*)d_status, h->records.as<double>());
       }
     }
-    {
-      ScopedTimer timer(h, T_SOLVE);
-      launch_lm_solve<kOdomLmBlock>(st, B, bv, (const double*)nullptr, (const double*)h->records.as<double>(), d_poses, d_status, d_info, it, sp,
-                                    d_prior);
-    }
-  }
-  launch_uncertainty<kOdomLmBlock>(st, B, bv, nullptr, h->records.as<double>(), d_poses, d_status, d_info, h->prm.outer_iterations - 1, sp,
-                                   h->unc_min_eigenvalue, d_unc, d_prior);
-  HIPCHK(h, hipGetLastError());
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)B * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-  }
-  if (info) HIPCHK(h, hipMemcpyAsync(info, d_info, (size_t)B * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
-  { const msfl_status us = unc_deliver(h, B, d_unc); if (us) return us; }
-  if (mem == MSFL_MEM_HOST || info || unc_host(h)) HIPCHK(h, hipStreamSynchronize(st));
-  return MSFL_OK;
+    return MSFL_OK;
+  });
+  if (ss) return ss;
+  return reg_close(h, B, mem, poses_io, d_poses, status, d_status, info, sinks);
 }
 
 }  // namespace

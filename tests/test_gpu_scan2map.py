@@ -399,6 +399,57 @@ def test_candidate_counter_mode_counts_and_keeps_results(gpu):
     assert t0.knn_candidates == 0 and t0.knn_candidates_seeded == 0      # reset
 
 
+def _launch_counts(h):
+    t = h.get_timing(reset=True)
+    return {name[len("launches_"):]: getattr(t, name) for name, _ in t._fields_ if name.startswith("launches_") and getattr(t, name)}
+
+
+def test_timer_classes_of_every_registration_entry_point(oracle):
+    """msfl_set_timing(h, 1) with default parameters (two outer iterations): the launches every timer class counts for one call of
+    each registration entry point.  bench.py divides ms_* by launches_*, so a timer that moves to another launch, or a launch that
+    joins a class (the uncertainty kernel belongs to none), changes what is reported without changing a result."""
+    import bench
+    from msf_loam_amd import capi
+    from tests import test_gpu_pairs, test_gpu_scan2scan
+    h = capi.Handle(0)
+    h.set_timing(1)
+    # scan-to-map batch: a first and a seeded second association pass (the seeded one counts in both classes), a fit and a solve per
+    # outer iteration; the index build belongs to msfl_set_map
+    inp = bench.build_inputs(8, 20000, 0)
+    h.set_map(inp["map_corner"], inp["map_surf"])
+    assert _launch_counts(h) == {"index": 1}
+    args = (inp["corner"], inp["corner_off"], inp["surf"], inp["surf_off"])
+    scan2map = {"assoc": 2, "assoc_seeded": 1, "fit": 2, "solve": 2}
+    poses, status, _ = h.match_scan2map_batch(*args, inp["guesses"].copy())
+    assert _launch_counts(h) == scan2map
+    h.set_uncertainty(8)                                           # the uncertainty launch adds to no class
+    poses_u, status_u, _ = h.match_scan2map_batch(*args, inp["guesses"].copy())
+    assert _launch_counts(h) == scan2map
+    assert np.array_equal(poses, poses_u) and np.array_equal(status, status_u) and not status.any()
+    assert np.all(h.uncertainty()["n_residuals"] > 0)
+    h.set_uncertainty(0)
+    # msfl_solve_records: one solve, nothing else
+    _, mc, ms = common.small_world()
+    pts, ring, truth, guess = common.scans(1)[0]
+    _, corner, surf = common.features_from_oracle(oracle, pts, ring)
+    rec, _ = _oracle_records(oracle, mc, ms, corner, surf, guess)
+    h.solve_records(corner, surf, rec, guess)
+    assert _launch_counts(h) == {"solve": 1}
+    # scan-to-scan batch, 3 pairs: the column-grid index build of the previous scans (these less-flat clouds are beyond the
+    # one-wavefront-per-query form), then one association span and one solve per outer iteration; no map classes
+    pairs = [test_gpu_scan2scan._clouds(*test_gpu_scan2scan._pair(oracle, i)) for i in range(3)]
+    _, status, _ = h.match_scan2scan_batch(test_gpu_scan2scan._batch_sets(pairs), np.tile([0, 0, 0, 0, 0, 0, 1.0], (3, 1)))
+    assert not status.any()
+    assert _launch_counts(h) == {"odom": 3, "solve": 2}
+    # pairs batch, 2 pairs: as scan-to-map, plus one index build per cloud kind
+    mcs, mss, cs, ss, guesses, _ = test_gpu_pairs._pairs(oracle, 2, np.random.default_rng(11))
+    (mc, mco), (ms, mso), (c, co), (s, so) = (test_gpu_pairs._cat(x) for x in (mcs, mss, cs, ss))
+    _, status, _ = h.match_pairs_batch(mc, mco, ms, mso, c, co, s, so, guesses)
+    assert not status.any()
+    assert _launch_counts(h) == dict(scan2map, index=2)
+    h.close()
+
+
 def test_both_forms_of_the_5nn_search_agree_bit_for_bit(oracle, monkeypatch):
     """Launches of up to 32 768 queries take the row-parallel latency form of the 5-NN kernel (sixteen lanes per query, one
     lane per (y, z) row, five-round merge), larger ones the one-lane-per-query form.  An exact top-5 over (distance,
