@@ -151,6 +151,7 @@ struct msfl_handle_s {
   int grid_cap_cells = 64 * 1024 * 1024;  // hard limit of the dense cell table (MSFL_GRID_CAP_CELLS)
   int h2d_chunk_scans = 512;              // MSFL_H2D_CHUNK_SCANS: scans per PCIe chunk of a host-buffer batch (>= 2 chunks to pipeline)
   int h2d_sub_chunks = 2;                 // MSFL_H2D_SUB_CHUNKS: pieces a chunk arrives in (its first association pass follows them)
+  int solve_records_block = 0;            // MSFL_SOLVE_RECORDS_BLOCK: kSlamLmBlock = msfl_solve_records runs the SLAM step's solve kernels; anything else: kLmBlock
   // set by msfl_voxel_downsample_batch when it refuses a cloud for a non-finite point: the cloud's number (-1: none) and where its
   // points are on the device (the staged copy of a host batch, or the caller's device array).  msfl_voxel_downsample reads these,
   // not the error text, to run PCL's drop-the-non-finite-points path.
@@ -732,6 +733,7 @@ msfl_status msfl_create(const msfl_params* params, int device, msfl_handle** out
   if (const char* e = std::getenv("MSFL_GRID_CAP_CELLS")) { const int c = std::atoi(e); if (c >= 8 && c <= (1 << 28)) h->grid_cap_cells = c; }
   if (const char* e = std::getenv("MSFL_H2D_CHUNK_SCANS")) { const int c = std::atoi(e); if (c >= 1) h->h2d_chunk_scans = c; }
   if (const char* e = std::getenv("MSFL_H2D_SUB_CHUNKS")) { const int c = std::atoi(e); if (c >= 1) h->h2d_sub_chunks = c; }
+  if (const char* e = std::getenv("MSFL_SOLVE_RECORDS_BLOCK")) h->solve_records_block = std::atoi(e);
   if (const char* e = std::getenv("MSFL_ODOM_BRUTE")) h->odom_force_brute = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_INDEX_SINGLE")) h->index_single = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_KNN_FORM")) h->knn_form = !std::strcmp(e, "lane") ? 1 : !std::strcmp(e, "rows") ? 2 : 0;
@@ -1077,6 +1079,16 @@ msfl_status msfl_associate_scan2map(msfl_handle* h, const msfl_point* corner, in
   return MSFL_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// One solve of the records already in h->records, in the workgroup MSFL_SOLVE_RECORDS_BLOCK chose.  Defined at the end of this file:
+// kSlamLmBlock and the SLAM step's <kSlamLmBlock> instantiations, which this only reuses, come with msfl_api_slam.inc.
+msfl_status solve_given_records(msfl_handle* h, const BatchView& bv, const RegSinks& sinks);
+}  // namespace
+
+extern "C" {
+
 msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_corner, const msfl_point* surf, int n_surf,
                                const double* records, double pose_io[7], msfl_match_info* info) {
   msfl_status s = enter(h); if (s) return s;
@@ -1094,8 +1106,7 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
     hipLaunchKernelGGL(pack_records_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, bv, (const double*)h->pprime.as<double>(),
                        h->records.as<double>());
   }
-  s = solve_outer<kLmBlock>(h, 1, bv, nullptr, h->poses.as<double>(), h->status.as<int>(), sinks, solver_params(h->prm, 0), 1,
-                            [](int) { return MSFL_OK; });                              // the records are given: nothing to associate
+  s = solve_given_records(h, bv, sinks);
   if (s) return s;
   return reg_close(h, 1, MSFL_MEM_HOST, pose_io, h->poses.as<double>(), nullptr, nullptr, info, sinks);   // (host memory: always waited for)
 }
@@ -1107,3 +1118,15 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
 #include "msfl_api_deskew.inc"
 #include "msfl_api_slam.inc"
 #include "msfl_api_pairs.inc"
+
+namespace {
+
+msfl_status solve_given_records(msfl_handle* h, const BatchView& bv, const RegSinks& sinks) {
+  const auto no_assoc = [](int) { return MSFL_OK; };        // the records are given: nothing to associate
+  const SolverParams sp = solver_params(h->prm, 0);
+  if (h->solve_records_block == kSlamLmBlock)                // (any other value, kLmBlock included: the default workgroup)
+    return solve_outer<kSlamLmBlock>(h, 1, bv, nullptr, h->poses.as<double>(), h->status.as<int>(), sinks, sp, 1, no_assoc);
+  return solve_outer<kLmBlock>(h, 1, bv, nullptr, h->poses.as<double>(), h->status.as<int>(), sinks, sp, 1, no_assoc);
+}
+
+}  // namespace

@@ -143,26 +143,36 @@ def test_batch_equals_single_and_is_deterministic(gpu, oracle):
         assert np.array_equal(p, poses1[b]), "batch result must equal the single-scan call bit for bit"
 
 
+PARTED_SPLITS = ((8, 1), (8, 3), (20, 2), (13, 8))          # (MSFL_H2D_CHUNK_SCANS, MSFL_H2D_SUB_CHUNKS)
+
+
+def _ragged_batch40(oracle):
+    """40 ragged scans (six room scans repeated, every fifth one cut down, scan 17 without features): per-scan feature lists,
+    guesses and true poses."""
+    sc = common.scans(6)
+    feats = [common.features_from_oracle(oracle, p, r)[1:] for p, r, _, _ in sc]
+    corners, surfs, guesses, truths = [], [], [], []
+    for i in range(40):
+        c, sf = feats[i % 6]
+        if i == 17: c, sf = c[:0], sf[:0]                    # nothing to match
+        if i % 5 == 3: c, sf = c[: len(c) // 2], sf[: len(sf) // 3]
+        corners.append(c); surfs.append(sf); guesses.append(sc[i % 6][3]); truths.append(sc[i % 6][2])
+    return corners, surfs, guesses, truths
+
+
 def test_host_batches_arrive_in_parts_and_pieces(gpu, oracle, monkeypatch):
     """A host-buffer batch crosses PCIe in parts (each registered completely while the next one is copied) that arrive in
     pieces (a part's first association pass follows them): whatever the split, every scan's result equals the unsplit
     host call bit for bit, also with ragged scans and a scan without features."""
     from msf_loam_amd import capi
     _, mc, ms = common.small_world()
-    sc = common.scans(6)
-    feats = [common.features_from_oracle(oracle, p, r)[1:] for p, r, _, _ in sc]
-    corners, surfs, guesses = [], [], []
-    for i in range(40):
-        c, sf = feats[i % 6]
-        if i == 17: c, sf = c[:0], sf[:0]                    # nothing to match
-        if i % 5 == 3: c, sf = c[: len(c) // 2], sf[: len(sf) // 3]
-        corners.append(c); surfs.append(sf); guesses.append(sc[i % 6][3])
+    corners, surfs, guesses, _ = _ragged_batch40(oracle)
     co = np.cumsum([0] + [len(c) for c in corners]).astype(np.int32)
     so = np.cumsum([0] + [len(x) for x in surfs]).astype(np.int32)
     C, S = np.concatenate(corners), np.concatenate(surfs)
     gpu.set_map(mc, ms)
     want, want_st, _ = gpu.match_scan2map_batch(C, co, S, so, guesses)          # 40 scans: below the default part size, one copy
-    for part, pieces in ((8, 1), (8, 3), (20, 2), (13, 8)):
+    for part, pieces in PARTED_SPLITS:
         monkeypatch.setenv("MSFL_H2D_CHUNK_SCANS", str(part))
         monkeypatch.setenv("MSFL_H2D_SUB_CHUNKS", str(pieces))
         h = capi.Handle(0)
@@ -173,6 +183,76 @@ def test_host_batches_arrive_in_parts_and_pieces(gpu, oracle, monkeypatch):
             h.close()
         assert np.array_equal(got_st, want_st) and np.array_equal(got, want), (part, pieces)
     assert np.all(want_st == 0) and np.array_equal(want[17], np.asarray(guesses[17], np.float64))    # an empty problem leaves its pose alone
+
+
+def _info_fields(info):
+    """Every field of a MatchInfo (or of each record of an array of them) as plain tuples."""
+    one = lambda r: tuple(tuple(v) if hasattr(v, "__len__") else v for v in (getattr(r, f) for f, _ in type(r)._fields_))
+    return [one(r) for r in info] if hasattr(info, "__len__") else one(info)
+
+
+def test_parted_host_batches_carry_their_sinks(gpu, oracle, monkeypatch):
+    """The same splits with the info records, a host uncertainty sink and 40 distinct host priors on at once: a part starting at
+    scan pb0 must read prior pb0 + b and write info / uncertainty record pb0 + b (RegSinks::at).  Every split equals the unsplit
+    call bit for bit, and the unsplit call's scan b equals a single msfl_match_scan2map call made with prior b alone, which ties
+    each result to ITS record; once more with the priors and the sink behind device pointers."""
+    import torch
+    from msf_loam_amd import capi
+    from tests.test_gpu_pose_prior import MIN_EIG, _real_priors
+    _, mc, ms = common.small_world()
+    corners, surfs, guesses, truths = _ragged_batch40(oracle)
+    B = len(corners)
+    co = np.cumsum([0] + [len(c) for c in corners]).astype(np.int32)
+    so = np.cumsum([0] + [len(x) for x in surfs]).astype(np.int32)
+    C, S = np.concatenate(corners), np.concatenate(surfs)
+    means, Ls = _real_priors(truths)
+    means[17] = 0.0; Ls[17] = 0.0                            # the scan without features: an all-zero record
+    assert len({m.tobytes() for m in means}) == B            # distinct: a record read from the wrong slot changes the result
+
+    def run(device_sinks=False):
+        h = capi.Handle(0)
+        try:
+            h.set_map(mc, ms)
+            if device_sinks:
+                dev = torch.device("cuda", 0)
+                d_prior = torch.from_numpy(np.frombuffer(capi.pose_priors(means, Ls).tobytes(), np.uint8).copy()).to(dev)
+                d_unc = torch.full((B * capi.UNCERTAINTY_DTYPE.itemsize,), 0x5A, dtype=torch.uint8, device=dev)
+                torch.cuda.synchronize()
+                h.set_pose_prior_device(d_prior, B)
+                h.set_uncertainty_device(d_unc, B, MIN_EIG)
+            else:
+                h.set_pose_prior(means, Ls)
+                h.set_uncertainty(B, MIN_EIG)
+            poses, st, info = h.match_scan2map_batch(C, co, S, so, guesses, want_info=True)
+            h.synchronize()
+            unc = np.frombuffer(d_unc.cpu().numpy().tobytes(), capi.UNCERTAINTY_DTYPE) if device_sinks else h.uncertainty(B)
+            return poses, st, _info_fields(info), unc.tobytes()
+        finally:
+            h.close()
+
+    want = run()                                             # 40 scans: below the default part size, one copy
+    assert np.all(want[1] == 0) and np.array_equal(want[0][17], np.asarray(guesses[17], np.float64))
+    size = capi.UNCERTAINTY_DTYPE.itemsize
+    assert want[3][17 * size:18 * size] == bytes(size) and sum(want[3][b * size:(b + 1) * size] != bytes(size) for b in range(B)) == B - 1
+    # scan b of the batch is the single call with prior b
+    h1 = capi.Handle(0)
+    h1.set_map(mc, ms)
+    h1.set_uncertainty(1, MIN_EIG)
+    for b in range(B):
+        h1.set_pose_prior([means[b]], [Ls[b]])
+        s1, pose1, info1 = h1.match_scan2map(corners[b], surfs[b], guesses[b])
+        assert s1 == want[1][b] and np.array_equal(pose1, want[0][b]) and _info_fields(info1) == want[2][b], b
+        assert h1.uncertainty(1).tobytes() == want[3][b * size:(b + 1) * size], b
+    h1.close()
+    for part, pieces in PARTED_SPLITS:
+        monkeypatch.setenv("MSFL_H2D_CHUNK_SCANS", str(part))
+        monkeypatch.setenv("MSFL_H2D_SUB_CHUNKS", str(pieces))
+        for device_sinks in ((False, True) if (part, pieces) == (8, 3) else (False,)):
+            got = run(device_sinks)
+            assert np.array_equal(got[1], want[1]) and np.array_equal(got[0], want[0]), (part, pieces, device_sinks)
+            for b in range(B):
+                assert got[2][b] == want[2][b], (part, pieces, device_sinks, b)
+                assert got[3][b * size:(b + 1) * size] == want[3][b * size:(b + 1) * size], (part, pieces, device_sinks, b)
 
 
 def test_edge_cases(gpu, oracle):
