@@ -222,7 +222,7 @@ def world_drive(world, kind, n):
 
 
 def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=False, maps_out=None, quirks=False, imu=None, clouds_out=None,
-             uncertainty=None, unc_out=None, priors=None, map_window=None, window_out=None, slam_hook=None):
+             uncertainty=None, unc_out=None, priors=None, map_window=None, window_out=None, slam_hook=None, load_map=None, save_map=None):
     """The same loop through the device-resident SLAM step (msfl_slam_add_scan): raw scan in, pose out, one
     synchronisation per scan (pipelined=False) or none until the record is fetched one scan later (pipelined=True: the
     odometry chain of scan k + 1 runs under the mapping chain of scan k, like the reference's two threads).
@@ -231,6 +231,9 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     priors: per scan None or an (odometry, mapping) pair for msfl_slam_set_next_prior, each None or (pose7, sqrt_information 6 x 6).
     map_window: (half_cells, every_n_scans) for msfl_slam_set_map_window; window_out (a list) then receives per scan the (corner, surf)
     records of msfl_slam_get_map_window.  slam_hook(slam, k): called before scan k is fed.
+    load_map: PREFIX -> PREFIX.corner.npz / PREFIX.surf.npz (msf_loam_amd/mapio.py) are loaded into the session's two stores before the
+    first scan (msfl_grid_load_cells: the stores hold the saved cells bit for bit, and scan 0 is registered against them); poses_true[0]
+    is then the pose of the first scan in the saved map's frame.  save_map: PREFIX -> the two stores are written there after the run.
     Returns (poses, records, wall-clock ms per scan over the scans after the second)."""
     from msf_loam_amd import capi
     n = len(poses_true)
@@ -248,6 +251,10 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     if map_window is not None:
         slam.set_map_window(map_window[0], map_window[1])
     want_win = window_out is not None
+    if load_map is not None:
+        from msf_loam_amd import mapio
+        for grid, side in zip(slam.grids(), ("corner", "surf")):
+            mapio.load_grid("%s.%s.npz" % (load_map, side), grid)
     recs = [None] * n
     t_start = None
     for k in range(n):
@@ -292,6 +299,10 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     if maps_out is not None:
         gc_, gs_ = slam.grids()
         maps_out["corner"], maps_out["surf"] = gc_.dump(), gs_.dump()
+    if save_map is not None:
+        from msf_loam_amd import mapio
+        for grid, side in zip(slam.grids(), ("corner", "surf")):
+            mapio.save_grid("%s.%s.npz" % (save_map, side), grid)
     slam.close()
     return est, recs, 1e3 * wall / max(n - 2, 1)
 
@@ -319,7 +330,14 @@ def main():
     ap.add_argument("--map-window", default=None, metavar="HX,HY,HZ[,N]",
                     help="msfl_slam_set_map_window: crop both map stores to +-HX,HY,HZ cells around the pose after every N-th scan (default 1); "
                          "23,23,23 is the smallest window that takes nothing from the registration of the scan at its centre")
+    ap.add_argument("--save-map", default=None, metavar="PREFIX",
+                    help="after the run write the two map stores to PREFIX.corner.npz / PREFIX.surf.npz (msfl_grid_dump_cells + msfl_grid_dump)")
+    ap.add_argument("--load-map", default=None, metavar="PREFIX",
+                    help="before the first scan load PREFIX.corner.npz / PREFIX.surf.npz into the session's stores (msfl_grid_load_cells): "
+                         "localise in a saved map; the first true pose anchors the session in the saved map's frame")
     args = ap.parse_args()
+    if args.mode == "staged" and (args.save_map or args.load_map):
+        ap.error("--save-map / --load-map need the slam modes")
     map_window = None
     if args.map_window:
         w = [int(v) for v in args.map_window.split(",")]
@@ -345,7 +363,7 @@ def main():
     unc = []
     est, recs, ms = run_slam(world, truth, pipelined=args.mode == "slam-pipelined", scans=scans, quirks=args.reference_quirks,
                              imu=synthetic_imu(truth) if args.imu else None, clouds_out=[] if args.keep_clouds else None,
-                             uncertainty=args.uncertainty, unc_out=unc, map_window=map_window)
+                             uncertainty=args.uncertainty, unc_out=unc, map_window=map_window, load_map=args.load_map, save_map=args.save_map)
     for k, u in enumerate(unc):
         m = u[1]
         if m["valid"]:
@@ -356,7 +374,7 @@ def main():
     if args.dump_poses:
         np.save(args.dump_poses, est)
     print(json.dumps({"mode": args.mode, "world": args.world, "beams": args.beams, "keep_clouds": bool(args.keep_clouds), "scans": args.scans, "reference_quirks": bool(args.reference_quirks), "imu": bool(args.imu),
-                      "map_window": args.map_window,
+                      "map_window": args.map_window, "load_map": args.load_map, "save_map": args.save_map,
                       "ate_rmse_m": ate(est, truth),
                       "final_error_m_rad": synth.pose_error(est[-1], truth[-1]), "ms_per_scan_end_to_end": ms,
                       "scans_per_s": 1e3 / ms if ms else None,

@@ -342,6 +342,35 @@ class HybridGrid {
     return info;
   }
 
+  // Crop that also says WHICH cells went (msfl_grid_crop_tiles): `cells` receives {ix, iy, iz, count} of every evicted cell (4 ints
+  // each) in the order of `evicted`.  The pair goes unchanged into LoadCells.
+  msfl_grid_crop_info CropTiles(const std::array<double, 3>& center, const std::array<int, 3>& half_cells, std::vector<msfl_point>* evicted,
+                                std::vector<int>* cells) {
+    msfl_grid_crop_info info{};
+    int n_points = 0, n_cells = 0;
+    detail::Check(msfl_grid_size(g_, &n_points, &n_cells), h_, "msfl_grid_size");
+    evicted->resize(static_cast<std::size_t>(n_points) + 1);
+    cells->resize(4 * static_cast<std::size_t>(n_cells) + 4);
+    detail::Check(msfl_grid_crop_tiles(g_, center.data(), half_cells.data(), evicted->data(), n_points, cells->data(), n_cells, MSFL_MEM_HOST, &info),
+                  h_, "msfl_grid_crop_tiles");
+    evicted->resize(static_cast<std::size_t>(info.n_points_evicted));
+    cells->resize(4 * static_cast<std::size_t>(info.n_cells_evicted));
+    return info;
+  }
+
+  // Dumped or evicted cells back, verbatim (msfl_grid_load_cells): `cells` holds {ix, iy, iz, count} per cell, keys ascending, `pts`
+  // their points back to back -- what CropTiles, or msfl_grid_dump_cells + msfl_grid_dump, delivered.  No voxel filter runs and a
+  // point's cell is not re-derived from its coordinates.  A listed cell that is live already refuses the load as a whole (throws;
+  // conflict != nullptr has received one 0/1 flag per listed cell by then).
+  msfl_grid_load_info LoadCells(const std::vector<int>& cells, const std::vector<msfl_point>& pts, std::vector<int>* conflict = nullptr) {
+    msfl_grid_load_info info{};
+    const int n_cells = static_cast<int>(cells.size() / 4);
+    if (conflict) conflict->assign(static_cast<std::size_t>(n_cells), 0);
+    detail::Check(msfl_grid_load_cells(g_, cells.data(), n_cells, pts.data(), static_cast<int>(pts.size()), MSFL_MEM_HOST,
+                                       conflict && n_cells > 0 ? conflict->data() : nullptr, &info), h_, "msfl_grid_load_cells");
+    return info;
+  }
+
  private:
   msfl_handle* h_ = nullptr;
   msfl_grid* g_ = nullptr;

@@ -575,7 +575,7 @@ msfl_status msfl_grid_stats(msfl_grid* g, long long out[6]);
                        `capacity` the crop is refused as a whole: the map is unchanged, info->applied = 0, the counts in `info`
                        say how much room is needed, MSFL_CAPACITY is returned.
    Evicted points that are inserted again with msfl_grid_insert_scan pass through the voxel filter again (they are centroids
-   already): there is no way to load a tile back unfiltered.
+   already) and are filed by their own coordinates; msfl_grid_crop_tiles + msfl_grid_load_cells below bring a tile back as it was.
    MSFL_BAD_ARG: a negative half_cells entry, a centre that is not finite (in f32), info == NULL. */
 typedef struct msfl_grid_crop_info {
   int n_cells_evicted, n_points_evicted;   /* what this crop removed (full counts, also when it was refused) */
@@ -586,6 +586,43 @@ typedef struct msfl_grid_crop_info {
 
 msfl_status msfl_grid_crop(msfl_grid* g, const double center[3], const int half_cells[3],
                            msfl_point* evicted, int capacity, msfl_mem mem, msfl_grid_crop_info* info);
+
+/* msfl_grid_crop with `evicted` required, which also says WHICH cells went: `evicted_cells` (host, cell_capacity x 4 ints) receives
+   {ix, iy, iz, count} of the evicted cells in the order of `evicted` (cells ascending).  The pair goes unchanged into
+   msfl_grid_load_cells.  More evicted cells than `cell_capacity` refuses the crop as a whole exactly as too many points does
+   (map unchanged, info->applied = 0, the counts in `info` say how much room is needed, MSFL_CAPACITY).
+   MSFL_BAD_ARG: as msfl_grid_crop; evicted == NULL, evicted_cells == NULL, a negative capacity. */
+msfl_status msfl_grid_crop_tiles(msfl_grid* g, const double center[3], const int half_cells[3], msfl_point* evicted, int capacity,
+                                 int* evicted_cells, int cell_capacity, msfl_mem mem, msfl_grid_crop_info* info);
+
+/* Load dumped or evicted cells back, bit for bit.
+     cells : host array of n_cells x 4 ints {ix, iy, iz, count}: what msfl_grid_dump_cells / msfl_grid_crop_tiles write.
+     pts   : n_points points (host or device memory as `mem` says), the cells' points back to back in list order and, inside a cell,
+             in stored order: what msfl_grid_dump and the `evicted` buffer of a crop deliver.
+     conflict : optional, host, n_cells ints: 1 where the listed cell is live in the store already, else 0.
+   Every listed cell becomes a live cell whose slab is the given points in the given order, untouched: no voxel filter, and the
+   cell is NOT re-derived from the coordinates.  The points are trusted to belong to their cell; a dump cannot be checked by
+   coordinates, because a stored centroid may round across the boundary of the cell or voxel that owns it.  The new cells' surround
+   stamp is 0.  Live cells are untouched: points, order, stamps and what the surround query delivers.  A loaded cell is
+   indistinguishable from one that never left, for the surround query and for every later insert that touches it.
+   Refused before anything is staged, MSFL_BAD_ARG (msfl_last_error names the rule): info == NULL; cells or pts NULL where needed; a
+   negative size; a count <= 0; an index outside [-8192, 8191]; keys not strictly ascending in (iz, iy, ix); counts that do not sum
+   to n_points.  n_cells == 0 is a no-op that fills `info` with applied = 1.
+   Refused on the device, as a whole (the map is unchanged bit for bit, info->applied = 0, the counts in `info` are filled):
+     a listed cell that is live already : MSFL_BAD_ARG; n_conflicts and conflict[] say which.  Load the others with this call and
+                                          merge those with msfl_grid_insert_scan, the only way to merge into a live cell.
+     a point that is not finite         : MSFL_CAPACITY, the status msfl_grid_insert_scan gives for it. */
+typedef struct msfl_grid_load_info {
+  int n_cells_loaded, n_points_loaded;   /* what this call added; 0, 0 when it was refused */
+  int n_cells, n_points;                 /* live sizes after the call */
+  int n_conflicts;                       /* cells of the list that are live in the store already */
+  int n_bad_points;                      /* points the insert's key kernel would drop a scan for (not finite) */
+  int applied;                           /* 1, or 0: refused as a whole, map unchanged */
+  int reserved_;
+} msfl_grid_load_info;
+
+msfl_status msfl_grid_load_cells(msfl_grid* g, const int* cells, int n_cells, const msfl_point* pts, int n_points, msfl_mem mem,
+                                 int* conflict, msfl_grid_load_info* info);
 
 
 /* ------------------------------------------------------------------------------------------ */

@@ -5,6 +5,7 @@ if the shared library is missing or a call fails, it raises.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -26,7 +27,7 @@ EXPORTED = [
     "msfl_transform_cloud",
     "msfl_delta_qp", "msfl_deskew_cloud", "msfl_undistort_cloud",
     "msfl_grid_create", "msfl_grid_destroy", "msfl_grid_insert_scan", "msfl_grid_get_surrounded", "msfl_grid_size", "msfl_grid_dump",
-    "msfl_grid_crop", "msfl_grid_dump_cells", "msfl_grid_stats", "msfl_slam_set_map_window", "msfl_slam_get_map_window",
+    "msfl_grid_crop", "msfl_grid_crop_tiles", "msfl_grid_load_cells", "msfl_grid_dump_cells", "msfl_grid_stats", "msfl_slam_set_map_window", "msfl_slam_get_map_window",
     "msfl_slam_default_config", "msfl_slam_create", "msfl_slam_destroy", "msfl_slam_add_scan", "msfl_slam_add_scan_imu", "msfl_slam_get_result", "msfl_slam_grids",
     "msfl_slam_last_error", "msfl_slam_get_clouds",
     "msfl_set_uncertainty", "msfl_slam_set_uncertainty", "msfl_slam_get_uncertainty",
@@ -151,6 +152,16 @@ class GridCropInfo(C.Structure):
         return (self.n_cells_evicted, self.n_points_evicted, self.n_cells, self.n_points, tuple(self.center_cell), self.applied)
 
 
+class GridLoadInfo(C.Structure):
+    """msfl_grid_load_info; `status` (a Python attribute) is the msfl_status of the call that filled it."""
+    _fields_ = [("n_cells_loaded", C.c_int), ("n_points_loaded", C.c_int), ("n_cells", C.c_int), ("n_points", C.c_int),
+                ("n_conflicts", C.c_int), ("n_bad_points", C.c_int), ("applied", C.c_int), ("reserved_", C.c_int)]
+    status = OK
+
+    def as_tuple(self):
+        return (self.n_cells_loaded, self.n_points_loaded, self.n_cells, self.n_points, self.n_conflicts, self.n_bad_points, self.applied)
+
+
 GRID_STATS = ("n_points", "n_cells", "pool_top", "pool_capacity_points", "cell_capacity", "device_bytes")
 
 
@@ -246,6 +257,8 @@ class Handle:
 
     def close(self):
         if self.h:
+            for g in list(getattr(self, "_grids", ())):           # a grid must be destroyed before its handle (msfl_c_api.h)
+                g.close()
             self.lib.msfl_destroy(self.h)
             self.h = C.c_void_p()
 
@@ -598,8 +611,12 @@ class Grid:
     def __init__(self, handle, resolution=3.0, leaf=0.2):
         self.handle = handle
         self.lib = handle.lib
+        self.resolution, self.leaf = float(resolution), float(leaf)          # what the store was created with (mapio.save_grid)
         self.g = C.c_void_p()
         handle._check(self.lib.msfl_grid_create(handle.h, C.c_float(resolution), C.c_float(leaf), C.byref(self.g)), "msfl_grid_create")
+        if not hasattr(handle, "_grids"):
+            handle._grids = weakref.WeakSet()
+        handle._grids.add(self)                                     # Handle.close() closes the grids that are still open first
 
     def close(self):
         if self.g:
@@ -687,12 +704,48 @@ class Grid:
                                                                  C.byref(info)), "msfl_grid_crop(device)", allow)
         return info
 
+    def crop_tiles(self, center, half_cells, capacity=None, cell_capacity=None, allow=()):
+        """msfl_grid_crop_tiles: (GridCropInfo, evicted cells (m, 4) int32 {ix, iy, iz, count}, evicted points), the pair load_cells
+        takes.  capacity / cell_capacity: room for the points / cells (default: every live one).  A refused crop raises unless
+        CAPACITY is in `allow` (then info.applied == 0 and both arrays are empty)."""
+        center = (C.c_double * 3)(*[float(v) for v in center])
+        half = (C.c_int * 3)(*[int(v) for v in half_cells])
+        info = GridCropInfo()
+        n_pts, n_cells = self.size()
+        cap = n_pts if capacity is None else int(capacity)
+        ccap = n_cells if cell_capacity is None else int(cell_capacity)
+        ev, cells = np.zeros((max(cap, 1), 4), np.float32), np.zeros((max(ccap, 1), 4), np.int32)
+        info.status = self.handle._check(self.lib.msfl_grid_crop_tiles(self.g, center, half, _vp(ev), C.c_int(cap), _vp(cells), C.c_int(ccap),
+                                                                       C.c_int(MEM_HOST), C.byref(info)), "msfl_grid_crop_tiles", allow)
+        ok = info.applied and info.status == OK
+        return info, cells[:info.n_cells_evicted if ok else 0].copy(), ev[:info.n_points_evicted if ok else 0].copy()
+
+    def _load(self, cells, pts_ptr, n_points, mem, allow, want_conflicts, what):
+        cells = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 4))
+        info = GridLoadInfo()
+        conflict = np.zeros(max(len(cells), 1), np.int32) if want_conflicts else None
+        info.status = self.handle._check(self.lib.msfl_grid_load_cells(self.g, _vp(cells), C.c_int(len(cells)), pts_ptr, C.c_int(int(n_points)),
+                                                                       C.c_int(mem), _vp(conflict), C.byref(info)), what, allow)
+        return (info, conflict[:len(cells)]) if want_conflicts else info
+
+    def load_cells(self, cells, pts, allow=(), want_conflicts=False):
+        """msfl_grid_load_cells: `cells` (m, 4) {ix, iy, iz, count} and their points (n, 4), as dump_cells() / dump() or crop_tiles()
+        deliver them, become live cells verbatim.  Returns the GridLoadInfo, or (info, per-cell 0/1 "already live" flags) with
+        want_conflicts.  A refused load raises unless its status (BAD_ARG / CAPACITY) is in `allow`."""
+        pts = _pts(pts)
+        return self._load(cells, _vp(pts), len(pts), MEM_HOST, allow, want_conflicts, "msfl_grid_load_cells")
+
+    def load_cells_device(self, cells, pts_ptr, n_points, allow=(), want_conflicts=False):
+        """msfl_grid_load_cells with the points in device memory (`cells` stays a host array)."""
+        return self._load(cells, _vp(pts_ptr), n_points, MEM_DEVICE, allow, want_conflicts, "msfl_grid_load_cells(device)")
+
 
 class _BorrowedGrid(Grid):
     """A map store owned by a Slam pipeline (never destroyed from here)."""
 
-    def __init__(self, lib, g, err):
+    def __init__(self, lib, g, err, resolution=None, leaf=None):
         self.lib, self.g, self._err = lib, g, err
+        self.resolution, self.leaf = resolution, leaf
         self.handle = self
 
     def _check(self, status, what, allow=()):
@@ -720,6 +773,7 @@ class Slam:
                 c.pose_odom2map[k] = float(pose_odom2map[k])
         for k, v in cfg.items():
             setattr(c, k, v)
+        self._grid_shape = (float(c.map_resolution), float(c.leaf_corner), float(c.leaf_surf))
         self.s = C.c_void_p()
         st = self.lib.msfl_slam_create(C.byref(params) if params is not None else None, C.byref(c), C.c_int(device), C.byref(self.s))
         if st != OK:
@@ -848,4 +902,5 @@ class Slam:
         st = self.lib.msfl_slam_grids(self.s, C.byref(a), C.byref(b))
         if st != OK:
             raise MsflError(st, "msfl_slam_grids", self._err())
-        return _BorrowedGrid(self.lib, a, self._err), _BorrowedGrid(self.lib, b, self._err)
+        res, leaf_c, leaf_s = self._grid_shape
+        return _BorrowedGrid(self.lib, a, self._err, res, leaf_c), _BorrowedGrid(self.lib, b, self._err, res, leaf_s)

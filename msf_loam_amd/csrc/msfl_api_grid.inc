@@ -16,6 +16,8 @@ struct msfl_grid_s {
   // surround / dump scratch
   DevBuf cnt, off, stage, pose, report_dev;
   DevBuf crop;                                    // crop scratch: keep flag and rank per cell (cnt / off hold the evicted counts and offsets)
+  DevBuf crop_cells;                              // msfl_grid_crop_tiles: {ix, iy, iz, count} of the evicted cells
+  DevBuf load;                                    // load scratch: the staged cell list, then key, position, conflict flag, count and slab offset per listed cell
   PinBuf report;                                  // int[8] read-back: {points, cells, pool_top, bad, overflow, touched, work, surround_total}, then the int[8] crop info
   // What the host knows: exact sizes as of the newest insert whose report it has seen, plus the inserts enqueued since
   // (sequence number, point capacity).  Every launch bound and capacity decision derives from these upper bounds, so
@@ -82,11 +84,11 @@ msfl_status grid_pack(msfl_grid* g, float4* out, long long capacity, bool into_p
   return MSFL_OK;
 }
 
-// Capacity planning before an insert of up to n_cap points, from host-known upper bounds only (never a device round trip):
-// the cell tables take every new point as a new cell, the pool takes every live point as touched and every cell as large.
-msfl_status grid_reserve_for_insert(msfl_grid* g, int n_cap) {
+// Capacity planning from host-known upper bounds only (never a device round trip): room for `add_cells` more table entries and
+// `add_pool` more pool slots above the bounds; the pool is compacted into the other buffer (grown if need be) when they do not fit.
+msfl_status grid_reserve(msfl_grid* g, long long add_cells, long long add_pool) {
   msfl_handle* h = g->h;
-  const long long need_cells = g->ub_cells + n_cap;
+  const long long need_cells = g->ub_cells + add_cells;
   if (need_cells > g->cell_cap) {
     const long long want = std::max<long long>(std::max<long long>(need_cells + need_cells / 2, kGridMinCells), 2LL * g->cell_cap);
     if (want > (1LL << 30)) return fail(h, MSFL_CAPACITY, "msfl_grid: cell table beyond 2^30 entries");
@@ -99,7 +101,7 @@ msfl_status grid_reserve_for_insert(msfl_grid* g, int n_cap) {
     }
     g->cell_cap = (int)want;
   }
-  const long long work = grid_work_bound(g->ub_points, n_cap);
+  const long long work = add_pool;
   if (g->ub_top + work > (long long)pool_capacity(g)) {
     // compact into the other buffer (grown if the live points plus one worst-case insert would not leave it half empty)
     const long long want = std::max<long long>(std::max<long long>(2 * (g->ub_points + work), g->min_pool), (long long)pool_capacity(g));
@@ -118,6 +120,10 @@ msfl_status grid_reserve_for_insert(msfl_grid* g, int n_cap) {
   }
   return MSFL_OK;
 }
+
+// before an insert of up to n_cap points: the cell tables take every new point as a new cell, the pool takes every live point as
+// touched and every cell as large
+msfl_status grid_reserve_for_insert(msfl_grid* g, int n_cap) { return grid_reserve(g, n_cap, grid_work_bound(g->ub_points, n_cap)); }
 
 // Stream-ordered InsertScan: `d_pts` (device, up to n_cap points, the first *n_dev of them valid when n_dev != null) ->
 // optional rigid transform by the device pose `d_pose` -> merged into the touched cells.  No host synchronisation; the
@@ -231,12 +237,13 @@ msfl_status grid_read_report(msfl_grid* g) {
 }
 
 // Stream-ordered crop to the window of +-half cells around the cell of the device-resident `d_center` (3 doubles).  d_evicted:
-// device buffer of `capacity` points for the evicted points, or null (dropped).  info_dst: device int[8] (msfl_grid_crop_info).
+// device buffer of `capacity` points for the evicted points, or null (dropped).  d_ev_cells: device buffer for {ix, iy, iz, count} of
+// the evicted cells (min(cell_capacity, live cells) x 4 ints), or null.  info_dst: device int[8] (msfl_grid_crop_info).
 // report_dst as in grid_insert_enqueue; with sizes_only only its first three words are rewritten (the SLAM step's record keeps
 // what the insert before the crop published in the others).  Takes a sequence number like an insert of zero points: the bounds
 // come down when the report is applied.
 msfl_status grid_crop_enqueue(msfl_grid* g, const double* d_center, const int half[3], float4* d_evicted, int capacity, int* info_dst,
-                              int* report_dst = nullptr, bool sizes_only = false) {
+                              int* report_dst = nullptr, bool sizes_only = false, int* d_ev_cells = nullptr, int cell_capacity = 0) {
   msfl_handle* h = g->h;
   hipStream_t st = h->stream;
   GridState* gs = g->state.as<GridState>();
@@ -266,13 +273,58 @@ msfl_status grid_crop_enqueue(msfl_grid* g, const double* d_center, const int ha
     hipLaunchKernelGGL(grid_crop_commit_kernel, dim3(std::min(bound, 4096)), dim3(256), 0, st, keys, (const int*)g->cstart[cur].as<int>(), ccnt,
                        (const int*)g->cstamp[cur].as<int>(), g->ckey[nxt].as<unsigned long long>(), g->cstart[nxt].as<int>(), g->ccnt[nxt].as<int>(),
                        g->cstamp[nxt].as<int>(), (const float4*)g->pool[g->cur_pool].as<float4>(), (const int*)keep, (const int*)rank, (const int*)ecnt,
-                       (const int*)eoff, bound, d_evicted, capacity, (const GridState*)gs);
+                       (const int*)eoff, bound, d_evicted, capacity, d_ev_cells, cell_capacity, (const GridState*)gs);
     g->cur_tab = nxt;
   }
   hipLaunchKernelGGL(grid_crop_finish_kernel, dim3(1), dim3(1), 0, st, gs, (const int*)keep, (const int*)rank, (const int*)ecnt, (const int*)eoff, bound, d_center,
-                     g->d.resolution, d_evicted ? 1 : 0, capacity, info_dst, report_dst ? report_dst : g->report_dev.as<int>(), sizes_only ? 1 : 0);
+                     g->d.resolution, d_evicted ? 1 : 0, capacity, d_ev_cells ? 1 : 0, cell_capacity, info_dst,
+                     report_dst ? report_dst : g->report_dev.as<int>(), sizes_only ? 1 : 0);
   HIPCHK(h, hipGetLastError());
   if (!report_dst) { HIPCHK(h, hipMemcpyAsync(g->report.p, g->report_dev.p, 16 * sizeof(int), hipMemcpyDeviceToHost, st)); g->pending = true; }
+  g->last_seq = g->next_seq++;
+  g->inflight.emplace_back(g->last_seq, 0);
+  return MSFL_OK;
+}
+
+// Stream-ordered load of `n_cells` listed cells with `n_points` points (both exact: the host validated the list).  d_cells: the
+// staged list at the head of g->load; d_pts: the points on the device.  info_dst: device int[8] (msfl_grid_load_info).  Takes a
+// sequence number like an insert; the bounds rise by the exact sizes and come down again with the report when the load was refused.
+msfl_status grid_load_enqueue(msfl_grid* g, const int* d_cells, int n_cells, const float4* d_pts, int n_points, int* info_dst, int* report_dst = nullptr) {
+  msfl_handle* h = g->h;
+  hipStream_t st = h->stream;
+  msfl_status s = grid_reserve(g, n_cells, n_points); if (s) return s;
+  GridState* gs = g->state.as<GridState>();
+  const int cur = g->cur_tab, nxt = 1 - cur;
+  const size_t n = (size_t)n_cells;
+  // scratch behind the staged list (16 bytes per cell): key (8), position, conflict flag, count, offset (4 each)
+  unsigned long long* lkey = reinterpret_cast<unsigned long long*>(g->load.as<char>() + 16 * n);
+  int* lpos = reinterpret_cast<int*>(lkey + n);
+  int *lconf = lpos + n, *lcnt = lconf + n, *loff = lcnt + n;
+  const unsigned long long* keys = g->ckey[cur].as<unsigned long long>();
+  const int pool_cap = (int)std::min<size_t>(pool_capacity(g), INT32_MAX);
+  if (n_cells <= kGridOneBlockMax) {
+    hipLaunchKernelGGL(grid_load_plan_kernel, dim3(1), dim3(1024), 0, st, d_cells, n_cells, keys, lkey, lpos, lconf, loff, gs);
+  } else {
+    hipLaunchKernelGGL(grid_load_flag_kernel, dim3(div_up(n_cells, 256)), dim3(256), 0, st, d_cells, n_cells, keys, lkey, lpos, lconf, lcnt, gs);
+    size_t tb = 0;
+    HIPCHK(h, rocprim::exclusive_scan(nullptr, tb, lcnt, loff, 0, n, rocprim::plus<int>(), st));
+    HIPCHK(h, h->idx_cub.reserve(tb));
+    HIPCHK(h, rocprim::exclusive_scan(h->idx_cub.p, tb, lcnt, loff, 0, n, rocprim::plus<int>(), st));
+  }
+  hipLaunchKernelGGL(grid_load_copy_kernel, dim3(div_up(n_points, 256)), dim3(256), 0, st, d_pts, n_points, g->pool[g->cur_pool].as<float4>(), pool_cap, gs);
+  const int bound = (int)std::min<long long>(g->ub_cells + n_cells, g->cell_cap);
+  hipLaunchKernelGGL(grid_load_commit_kernel, dim3(div_up(bound, 256)), dim3(256), 0, st, keys, (const int*)g->cstart[cur].as<int>(),
+                     (const int*)g->ccnt[cur].as<int>(), (const int*)g->cstamp[cur].as<int>(), g->ckey[nxt].as<unsigned long long>(),
+                     g->cstart[nxt].as<int>(), g->ccnt[nxt].as<int>(), g->cstamp[nxt].as<int>(), d_cells, (const unsigned long long*)lkey,
+                     (const int*)lpos, (const int*)loff, n_cells, n_points, bound, pool_cap, g->cell_cap, (const GridState*)gs);
+  hipLaunchKernelGGL(grid_load_finish_kernel, dim3(1), dim3(1), 0, st, gs, n_cells, n_points, pool_cap, g->cell_cap, info_dst,
+                     report_dst ? report_dst : g->report_dev.as<int>());
+  HIPCHK(h, hipGetLastError());
+  if (!report_dst) { HIPCHK(h, hipMemcpyAsync(g->report.p, g->report_dev.p, 16 * sizeof(int), hipMemcpyDeviceToHost, st)); g->pending = true; }
+  g->cur_tab = nxt;
+  g->ub_top += n_points;
+  g->ub_points += n_points;
+  g->ub_cells += n_cells;
   g->last_seq = g->next_seq++;
   g->inflight.emplace_back(g->last_seq, 0);
   return MSFL_OK;
@@ -433,15 +485,15 @@ msfl_status msfl_grid_dump(msfl_grid* g, msfl_point* out, int capacity, int* n_o
 }
 
 // Forget every cell outside the window of +-half_cells cells around the cell of `center` (msfl_c_api.h).
-msfl_status msfl_grid_crop(msfl_grid* g, const double center[3], const int half_cells[3], msfl_point* evicted, int capacity, msfl_mem mem,
-                           msfl_grid_crop_info* info) {
+static msfl_status grid_crop_sync(msfl_grid* g, const double center[3], const int half_cells[3], msfl_point* evicted, int capacity, int* evicted_cells,
+                                  int cell_capacity, bool tiles, msfl_mem mem, msfl_grid_crop_info* info) {
   if (!g) return MSFL_BAD_ARG;
   msfl_handle* h = g->h;
   msfl_status s = enter(h); if (s) return s;
   if (!info || !center || !half_cells || half_cells[0] < 0 || half_cells[1] < 0 || half_cells[2] < 0 || !std::isfinite(center[0]) ||
       !std::isfinite(center[1]) || !std::isfinite(center[2]) || !std::isfinite((float)center[0]) || !std::isfinite((float)center[1]) ||
-      !std::isfinite((float)center[2]) || (evicted && capacity < 0))
-    return fail(h, MSFL_BAD_ARG, "msfl_grid_crop: bad argument");
+      !std::isfinite((float)center[2]) || (evicted && capacity < 0) || (tiles && (!evicted || !evicted_cells || cell_capacity < 0)))
+    return fail(h, MSFL_BAD_ARG, tiles ? "msfl_grid_crop_tiles: bad argument" : "msfl_grid_crop: bad argument");
   hipStream_t st = h->stream;
   if (g->pending) { HIPCHK(h, hipStreamSynchronize(st)); (void)grid_read_report(g); }
   HIPCHK(h, g->pose.reserve(8 * sizeof(double)));
@@ -450,17 +502,96 @@ msfl_status msfl_grid_crop(msfl_grid* g, const double center[3], const int half_
   const int stage_cap = (int)std::min<long long>(capacity, g->ub_points);   // no more than the live points can be evicted
   if (evicted && mem == MSFL_MEM_HOST) { HIPCHK(h, g->stage.reserve((size_t)std::max(stage_cap, 1) * sizeof(float4))); d_ev = g->stage.as<float4>(); }
   int* d_info = g->report_dev.as<int>() + 8;
-  s = grid_crop_enqueue(g, g->pose.as<double>(), half_cells, d_ev, capacity, d_info); if (s) return s;
+  int* d_cells = nullptr;
+  if (tiles) {                                                               // no more than the live cells can be evicted
+    HIPCHK(h, g->crop_cells.reserve((size_t)std::max<long long>(std::min<long long>(cell_capacity, g->ub_cells), 1) * 4 * sizeof(int)));
+    d_cells = g->crop_cells.as<int>();
+  }
+  s = grid_crop_enqueue(g, g->pose.as<double>(), half_cells, d_ev, capacity, d_info, nullptr, false, d_cells, cell_capacity); if (s) return s;
   HIPCHK(h, hipStreamSynchronize(st));
   s = grid_read_report(g); if (s) return s;
   static_assert(sizeof(msfl_grid_crop_info) == CROP_WORDS * sizeof(int), "msfl_grid_crop_info is the device record");
   std::memcpy(info, g->report.as<int>() + 8, sizeof(*info));
-  if (!info->applied) return fail(h, MSFL_CAPACITY, "msfl_grid_crop: more evicted points than `capacity`; map unchanged");
+  if (!info->applied)
+    return fail(h, MSFL_CAPACITY, tiles ? "msfl_grid_crop_tiles: more evicted points than `capacity` or more evicted cells than `cell_capacity`; map unchanged"
+                                        : "msfl_grid_crop: more evicted points than `capacity`; map unchanged");
+  bool copying = false;
+  if (tiles && info->n_cells_evicted > 0) {
+    HIPCHK(h, hipMemcpyAsync(evicted_cells, d_cells, (size_t)info->n_cells_evicted * 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+    copying = true;
+  }
   if (evicted && mem == MSFL_MEM_HOST && info->n_points_evicted > 0) {
     HIPCHK(h, hipMemcpyAsync(evicted, d_ev, (size_t)info->n_points_evicted * sizeof(float4), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
+    copying = true;
   }
+  if (copying) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
+}
+
+msfl_status msfl_grid_crop(msfl_grid* g, const double center[3], const int half_cells[3], msfl_point* evicted, int capacity, msfl_mem mem,
+                           msfl_grid_crop_info* info) {
+  return grid_crop_sync(g, center, half_cells, evicted, capacity, nullptr, 0, false, mem, info);
+}
+
+// msfl_grid_crop that also delivers {ix, iy, iz, count} of the evicted cells, in the order of `evicted` (msfl_c_api.h)
+msfl_status msfl_grid_crop_tiles(msfl_grid* g, const double center[3], const int half_cells[3], msfl_point* evicted, int capacity,
+                                 int* evicted_cells, int cell_capacity, msfl_mem mem, msfl_grid_crop_info* info) {
+  return grid_crop_sync(g, center, half_cells, evicted, capacity, evicted_cells, cell_capacity, true, mem, info);
+}
+
+// Dumped or evicted cells back into the store, verbatim (msfl_c_api.h)
+msfl_status msfl_grid_load_cells(msfl_grid* g, const int* cells, int n_cells, const msfl_point* pts, int n_points, msfl_mem mem, int* conflict,
+                                 msfl_grid_load_info* info) {
+  if (!g) return MSFL_BAD_ARG;
+  msfl_handle* h = g->h;
+  msfl_status s = enter(h); if (s) return s;
+  if (!info || n_cells < 0 || n_points < 0 || (n_cells > 0 && !cells) || (n_points > 0 && !pts))
+    return fail(h, MSFL_BAD_ARG, "msfl_grid_load_cells: bad argument");
+  const int lim = 1 << (kGridCellBits - 1);
+  long long sum = 0;
+  unsigned long long prev = 0;
+  for (int j = 0; j < n_cells; j++) {
+    const int* c = cells + 4 * (size_t)j;
+    if (c[3] <= 0) return fail(h, MSFL_BAD_ARG, "msfl_grid_load_cells: a listed cell with a count <= 0");
+    if (c[0] < -lim || c[0] >= lim || c[1] < -lim || c[1] >= lim || c[2] < -lim || c[2] >= lim)
+      return fail(h, MSFL_BAD_ARG, "msfl_grid_load_cells: a cell index outside [-8192, 8191]");
+    const unsigned long long key = ((unsigned long long)(c[2] + lim) << (2 * kGridCellBits)) | ((unsigned long long)(c[1] + lim) << kGridCellBits) |
+                                   (unsigned long long)(c[0] + lim);
+    if (j > 0 && key <= prev) return fail(h, MSFL_BAD_ARG, "msfl_grid_load_cells: cells not strictly ascending in (iz, iy, ix)");
+    prev = key;
+    sum += c[3];
+  }
+  if (sum != n_points) return fail(h, MSFL_BAD_ARG, "msfl_grid_load_cells: the counts do not sum to n_points");
+  hipStream_t st = h->stream;
+  if (g->pending) { HIPCHK(h, hipStreamSynchronize(st)); (void)grid_read_report(g); }
+  static_assert(sizeof(msfl_grid_load_info) == LOAD_WORDS * sizeof(int), "msfl_grid_load_info is the device record");
+  if (n_cells == 0) {
+    std::memset(info, 0, sizeof(*info));
+    info->n_cells = g->n_cells; info->n_points = g->n_points; info->applied = 1;
+    return MSFL_OK;
+  }
+  const size_t n = (size_t)n_cells;
+  HIPCHK(h, g->load.reserve(n * (16 + 8 + 4 * 4)));
+  HIPCHK(h, hipMemcpyAsync(g->load.p, cells, n * 16, hipMemcpyHostToDevice, st));
+  const float4* d_pts = reinterpret_cast<const float4*>(pts);
+  if (mem == MSFL_MEM_HOST) {
+    HIPCHK(h, g->stage.reserve((size_t)n_points * sizeof(float4)));
+    HIPCHK(h, hipMemcpyAsync(g->stage.p, pts, (size_t)n_points * sizeof(float4), hipMemcpyHostToDevice, st));
+    d_pts = g->stage.as<float4>();
+  }
+  int* d_info = g->report_dev.as<int>() + 8;
+  s = grid_load_enqueue(g, g->load.as<int>(), n_cells, d_pts, n_points, d_info); if (s) return s;
+  HIPCHK(h, hipStreamSynchronize(st));
+  s = grid_read_report(g); if (s) return s;
+  std::memcpy(info, g->report.as<int>() + 8, sizeof(*info));
+  if (conflict) {
+    const int* lconf = reinterpret_cast<const int*>(g->load.as<char>() + 16 * n + 8 * n) + n;
+    HIPCHK(h, hipMemcpy(conflict, lconf, n * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  if (info->applied) return MSFL_OK;
+  if (info->n_conflicts > 0) return fail(h, MSFL_BAD_ARG, "msfl_grid_load_cells: a listed cell is live in the store already; map unchanged");
+  if (info->n_bad_points > 0) return fail(h, MSFL_CAPACITY, "msfl_grid_load_cells: a point is not finite; map unchanged");
+  return fail(h, MSFL_CAPACITY, "msfl_grid_load_cells: internal capacity exceeded; map unchanged");
 }
 
 // {ix, iy, iz, count} of every cell, in the order of msfl_grid_dump
@@ -497,7 +628,7 @@ msfl_status msfl_grid_stats(msfl_grid* g, long long out[6]) {
   }
   const DevBuf* bufs[] = {&g->state, &g->pool[0], &g->pool[1], &g->ckey[0], &g->ckey[1], &g->cstart[0], &g->cstart[1], &g->ccnt[0], &g->ccnt[1],
                           &g->cstamp[0], &g->cstamp[1], &g->keys, &g->keys_s, &g->vals, &g->vals_s, &g->head, &g->tpos, &g->xf, &g->xs, &g->t_key, &g->t_ns,
-                          &g->t_old, &g->t_woff, &g->t_rank, &g->t_cnt, &g->cnt, &g->off, &g->stage, &g->pose, &g->report_dev, &g->crop};
+                          &g->t_old, &g->t_woff, &g->t_rank, &g->t_cnt, &g->cnt, &g->off, &g->stage, &g->pose, &g->report_dev, &g->crop, &g->crop_cells, &g->load};
   long long bytes = 0;
   for (auto* b : bufs) bytes += (long long)b->cap;
   out[0] = g->n_points; out[1] = g->n_cells; out[2] = g->pool_top; out[3] = (long long)pool_capacity(g); out[4] = g->cell_cap; out[5] = bytes;

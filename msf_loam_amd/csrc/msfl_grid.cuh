@@ -55,6 +55,7 @@ struct GridState {
   int delta_points;       // sum over touched cells of (points after - points before)
   int n_big;              // touched cells the small rebuild kernel left to the large one
   int surround_total;     // points delivered by the last surround query
+  int n_conflicts;        // a load in flight: listed cells that are live already (zeroed again by grid_load_finish_kernel)
 };
 
 // HybridGridBase::GetCellIndex (:422-426): lround(double(p / resolution)), division in f32
@@ -803,17 +804,25 @@ grid_crop_scan_kernel(const unsigned long long* __restrict__ keys, const int* __
 }
 
 // kept entries to the other table buffer at their rank, evicted slabs to `evicted` at their offsets (workgroup-stride, like
-// grid_emit_kernel).  Refused (more than `capacity` points to deliver): every entry is carried over where it is.
+// grid_emit_kernel).  Refused (more than `capacity` points to deliver, or more than `cell_capacity` cell records): every entry is
+// carried over where it is.  ev_cells != null receives {ix, iy, iz, count} of evicted cell c at index c - rank[c], the order of `evicted`.
 __global__ void __launch_bounds__(256)
 grid_crop_commit_kernel(const unsigned long long* __restrict__ keys_in, const int* __restrict__ start_in, const int* __restrict__ cnt_in,
                         const int* __restrict__ stamp_in, unsigned long long* __restrict__ keys_out, int* __restrict__ start_out,
                         int* __restrict__ cnt_out, int* __restrict__ stamp_out, const float4* __restrict__ pool, const int* __restrict__ keep,
                         const int* __restrict__ rank, const int* __restrict__ ecnt, const int* __restrict__ eoff, int bound,
-                        float4* __restrict__ evicted, int capacity, const GridState* __restrict__ st) {
+                        float4* __restrict__ evicted, int capacity, int* __restrict__ ev_cells, int cell_capacity,
+                        const GridState* __restrict__ st) {
   const int nc = min(st->n_cells, bound);
   if (nc == 0) return;
-  const bool refused = evicted != nullptr && eoff[nc - 1] + ecnt[nc - 1] > capacity;
+  const bool refused = (evicted != nullptr && eoff[nc - 1] + ecnt[nc - 1] > capacity) ||
+                       (ev_cells != nullptr && nc - (rank[nc - 1] + keep[nc - 1]) > cell_capacity);
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < nc; c += gridDim.x * blockDim.x) {      // the table: one thread per cell
+    if (!keep[c] && !refused && ev_cells) {
+      int ix, iy, iz;
+      grid_cell_of_key(keys_in[c], ix, iy, iz);
+      reinterpret_cast<int4*>(ev_cells)[c - rank[c]] = make_int4(ix, iy, iz, cnt_in[c]);
+    }
     if (!keep[c] && !refused) continue;
     const int o = refused ? c : rank[c];
     keys_out[o] = keys_in[c]; start_out[o] = start_in[c]; cnt_out[o] = cnt_in[c]; stamp_out[o] = stamp_in[c];
@@ -831,13 +840,14 @@ grid_crop_commit_kernel(const unsigned long long* __restrict__ keys_in, const in
 // insert before this crop published, the SLAM step's record).  bound == 0: the table is empty, nothing ran before this.
 __global__ void grid_crop_finish_kernel(GridState* __restrict__ st, const int* __restrict__ keep, const int* __restrict__ rank, const int* __restrict__ ecnt,
                                         const int* __restrict__ eoff, int bound, const double* __restrict__ center, float resolution,
-                                        int has_evicted, int capacity, int* __restrict__ info, int* __restrict__ report, int sizes_only) {
+                                        int has_evicted, int capacity, int has_ev_cells, int cell_capacity, int* __restrict__ info,
+                                        int* __restrict__ report, int sizes_only) {
   const int nc = min(st->n_cells, bound);
   int cx, cy, cz;
   const bool ok = grid_crop_center(center, resolution, cx, cy, cz);
   const int n_keep = nc > 0 ? rank[nc - 1] + keep[nc - 1] : 0, n_ev_pts = nc > 0 ? eoff[nc - 1] + ecnt[nc - 1] : 0;
-  const int applied = (ok && !(has_evicted && n_ev_pts > capacity)) ? 1 : 0;
   const int n_ev_cells = nc - n_keep;
+  const int applied = (ok && !(has_evicted && n_ev_pts > capacity) && !(has_ev_cells && n_ev_cells > cell_capacity)) ? 1 : 0;
   if (applied) { st->n_cells -= n_ev_cells; st->n_points -= n_ev_pts; }
   if (info) {
     info[CROP_CELLS_EVICTED] = n_ev_cells; info[CROP_POINTS_EVICTED] = n_ev_pts; info[CROP_CELLS] = st->n_cells; info[CROP_POINTS] = st->n_points;
@@ -848,6 +858,120 @@ __global__ void grid_crop_finish_kernel(GridState* __restrict__ st, const int* _
     if (!sizes_only) { report[3] = 0; report[4] = 0; report[5] = 0; report[6] = 0; report[7] = st->surround_total; }
   }
   st->bad = 0; st->overflow = 0; st->n_touched = 0; st->n_new_cells = 0; st->work = 0; st->delta_points = 0; st->n_big = 0;
+}
+
+// ---- Load: cells that were dumped or evicted come back verbatim ----------------------------------------------------------------
+// The caller lists cells {ix, iy, iz, count}, keys strictly ascending (the host checked that, the index range and the counts), and
+// their points back to back in list order, stored order inside a cell: what a dump or the `evicted` buffer of a crop delivers.
+// Every listed cell becomes a live cell whose slab is those points, untouched (no filter, the cell is not re-derived from the
+// coordinates: a centroid may round across the boundary of the cell that owns it), stamp 0.  The new slabs lie back to back at the
+// pool top in list order, so the points move by one flat copy.  Live cells keep their start, count and stamp and only move up in
+// the table.  A listed cell that is live already, a point that is not finite (the insert's key kernel drops a scan for one), or
+// too little room refuses the load as a whole: the table is carried over unchanged and nothing in the state moves; what the copy
+// wrote lies beyond the pool top, where nothing reads.
+enum { LOAD_CELLS_LOADED = 0, LOAD_POINTS_LOADED, LOAD_CELLS, LOAD_POINTS, LOAD_CONFLICTS, LOAD_BAD_POINTS, LOAD_APPLIED, LOAD_RESERVED, LOAD_WORDS };
+
+// the decision every kernel after the plan and the copy takes alike (the counters are complete by then)
+__device__ __forceinline__ bool grid_load_refused(const GridState* __restrict__ st, int n_list, int n_pts, int pool_cap, int cell_cap) {
+  return st->n_conflicts != 0 || st->bad != 0 || (long long)st->pool_top + n_pts > (long long)pool_cap || (long long)st->n_cells + n_list > (long long)cell_cap;
+}
+
+// one listed cell: key, insert position in the live table, conflict flag
+__device__ __forceinline__ int grid_load_place(const int* __restrict__ cells, int j, const unsigned long long* __restrict__ keys, int nc,
+                                               unsigned long long* __restrict__ lkey, int* __restrict__ lpos, int* __restrict__ lconf) {
+  const int4 c = reinterpret_cast<const int4*>(cells)[j];
+  const unsigned long long key = grid_cell_key(c.x, c.y, c.z);
+  const int p = grid_lower_bound(keys, nc, key);
+  const int conflict = (p < nc && keys[p] == key) ? 1 : 0;
+  lkey[j] = key; lpos[j] = p; lconf[j] = conflict;
+  return conflict;
+}
+
+// plan, device-wide form: place every listed cell and lay its count out for the scan of the slab offsets
+__global__ void __launch_bounds__(256)
+grid_load_flag_kernel(const int* __restrict__ cells, int n_list, const unsigned long long* __restrict__ keys, unsigned long long* __restrict__ lkey,
+                      int* __restrict__ lpos, int* __restrict__ lconf, int* __restrict__ lcnt, GridState* __restrict__ st) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_list) return;
+  if (grid_load_place(cells, j, keys, st->n_cells, lkey, lpos, lconf)) atomicAdd(&st->n_conflicts, 1);
+  lcnt[j] = cells[4 * j + 3];
+}
+
+// plan, one workgroup: the same + the exclusive scan of the counts (the shape of grid_crop_scan_kernel)
+__global__ void __launch_bounds__(1024)
+grid_load_plan_kernel(const int* __restrict__ cells, int n_list, const unsigned long long* __restrict__ keys, unsigned long long* __restrict__ lkey,
+                      int* __restrict__ lpos, int* __restrict__ lconf, int* __restrict__ loff, GridState* __restrict__ st) {
+  __shared__ int s_wave[16];
+  const int nc = st->n_cells;
+  int carry = 0, conflicts = 0;
+  for (int base = 0; base < n_list; base += 4 * 1024) {
+    const int j0 = base + 4 * (int)threadIdx.x;
+    int m[4], t = 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int j = j0 + u;
+      m[u] = 0;
+      if (j < n_list) { m[u] = cells[4 * j + 3]; conflicts += grid_load_place(cells, j, keys, nc, lkey, lpos, lconf); }
+      t += m[u];
+    }
+    int total;
+    int run = carry + block_incl_scan_1024(t, s_wave, total) - t;
+#pragma unroll
+    for (int u = 0; u < 4; u++) { const int j = j0 + u; if (j < n_list) loff[j] = run; run += m[u]; }
+    carry += total;
+  }
+  if (conflicts) atomicAdd(&st->n_conflicts, conflicts);
+}
+
+// the points: pool[pool_top + i] = pts[i], one point per lane; a point that is not finite is counted on the way
+__global__ void __launch_bounds__(256)
+grid_load_copy_kernel(const float4* __restrict__ pts, int n_pts, float4* __restrict__ pool, int pool_cap, GridState* __restrict__ st) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pts) return;
+  const int top = st->pool_top;
+  if ((long long)top + n_pts > (long long)pool_cap) return;           // refused for want of room (the host sizes the pool so that this cannot happen)
+  const float4 p = pts[i];
+  pool[top + i] = p;
+  if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) atomicAdd(&st->bad, 1);
+}
+
+// the merged table into the other buffer: live entry i moves up by the listed keys below it, listed cell j goes to lpos[j] + j
+__global__ void __launch_bounds__(256)
+grid_load_commit_kernel(const unsigned long long* __restrict__ keys_in, const int* __restrict__ start_in, const int* __restrict__ cnt_in,
+                        const int* __restrict__ stamp_in, unsigned long long* __restrict__ keys_out, int* __restrict__ start_out,
+                        int* __restrict__ cnt_out, int* __restrict__ stamp_out, const int* __restrict__ cells, const unsigned long long* __restrict__ lkey,
+                        const int* __restrict__ lpos, const int* __restrict__ loff, int n_list, int n_pts, int bound, int pool_cap, int cell_cap,
+                        const GridState* __restrict__ st) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= bound) return;
+  const int nc = st->n_cells;
+  const bool refused = grid_load_refused(st, n_list, n_pts, pool_cap, cell_cap);
+  if (i < nc) {
+    const unsigned long long k = keys_in[i];
+    const int o = refused ? i : i + grid_lower_bound(lkey, n_list, k);
+    keys_out[o] = k; start_out[o] = start_in[i]; cnt_out[o] = cnt_in[i]; stamp_out[o] = stamp_in[i];
+  } else if (i - nc < n_list && !refused) {
+    const int j = i - nc, o = lpos[j] + j;
+    keys_out[o] = lkey[j]; start_out[o] = st->pool_top + loff[j]; cnt_out[o] = cells[4 * j + 3]; stamp_out[o] = 0;
+  }
+}
+
+// one thread: fold the load into the state, write the info record (msfl_grid_load_info, 8 ints) and the report
+__global__ void grid_load_finish_kernel(GridState* __restrict__ st, int n_list, int n_pts, int pool_cap, int cell_cap, int* __restrict__ info,
+                                        int* __restrict__ report) {
+  const bool refused = grid_load_refused(st, n_list, n_pts, pool_cap, cell_cap);
+  const int conflicts = st->n_conflicts, bad = st->bad;
+  if (!refused) { st->n_cells += n_list; st->n_points += n_pts; st->pool_top += n_pts; }
+  if (info) {
+    info[LOAD_CELLS_LOADED] = refused ? 0 : n_list; info[LOAD_POINTS_LOADED] = refused ? 0 : n_pts; info[LOAD_CELLS] = st->n_cells;
+    info[LOAD_POINTS] = st->n_points; info[LOAD_CONFLICTS] = conflicts; info[LOAD_BAD_POINTS] = bad; info[LOAD_APPLIED] = refused ? 0 : 1;
+    info[LOAD_RESERVED] = 0;
+  }
+  if (report) {
+    report[0] = st->n_points; report[1] = st->n_cells; report[2] = st->pool_top;
+    report[3] = 0; report[4] = 0; report[5] = 0; report[6] = 0; report[7] = st->surround_total;
+  }
+  st->bad = 0; st->overflow = 0; st->n_touched = 0; st->n_new_cells = 0; st->work = 0; st->delta_points = 0; st->n_big = 0; st->n_conflicts = 0;
 }
 
 }  // namespace msfl
