@@ -222,13 +222,16 @@ def world_drive(world, kind, n):
 
 
 def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=False, maps_out=None, quirks=False, imu=None, clouds_out=None,
-             uncertainty=None, unc_out=None, priors=None, map_window=None, window_out=None, slam_hook=None, load_map=None, save_map=None):
+             uncertainty=None, unc_out=None, priors=None, map_window=None, window_out=None, slam_hook=None, load_map=None, save_map=None,
+             degeneracy=None, degen_out=None):
     """The same loop through the device-resident SLAM step (msfl_slam_add_scan): raw scan in, pose out, one
     synchronisation per scan (pipelined=False) or none until the record is fetched one scan later (pipelined=True: the
     odometry chain of scan k + 1 runs under the mapping chain of scan k, like the reference's two threads).
     uncertainty: a min_eigenvalue turns msfl_slam_set_uncertainty on; unc_out (a list) then receives per scan the (odometry, mapping)
     records of msfl_slam_get_uncertainty.
     priors: per scan None or an (odometry, mapping) pair for msfl_slam_set_next_prior, each None or (pose7, sqrt_information 6 x 6).
+    degeneracy: (min_eig_odometry, min_eig_mapping), either None = that matcher off, turns msfl_slam_set_degeneracy on; degen_out (a list)
+    then receives per scan the (odometry, mapping) records of msfl_slam_get_degeneracy.
     map_window: (half_cells, every_n_scans) for msfl_slam_set_map_window; window_out (a list) then receives per scan the (corner, surf)
     records of msfl_slam_get_map_window.  slam_hook(slam, k): called before scan k is fed.
     load_map: PREFIX -> PREFIX.corner.npz / PREFIX.surf.npz (msf_loam_amd/mapio.py) are loaded into the session's two stores before the
@@ -248,6 +251,9 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     if uncertainty is not None:
         slam.set_uncertainty(True, uncertainty)
     want_unc = uncertainty is not None and unc_out is not None
+    if degeneracy is not None:
+        slam.set_degeneracy(odometry=degeneracy[0], mapping=degeneracy[1])
+    want_degen = degeneracy is not None and degen_out is not None
     if map_window is not None:
         slam.set_map_window(map_window[0], map_window[1])
     want_win = window_out is not None
@@ -271,6 +277,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
                 recs[k - 1] = slam.result(k - 1)
                 if want_unc:
                     unc_out.append(slam.get_uncertainty(k - 1))
+                if want_degen:
+                    degen_out.append(slam.get_degeneracy(k - 1))
                 if want_win:
                     window_out.append(slam.get_map_window(k - 1))
                 if clouds_out is not None:
@@ -279,6 +287,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
             recs[k] = slam.add_scan(*scans[k], imu=im)
             if want_unc:
                 unc_out.append(slam.get_uncertainty(k))
+            if want_degen:
+                degen_out.append(slam.get_degeneracy(k))
             if want_win:
                 window_out.append(slam.get_map_window(k))
             if clouds_out is not None:
@@ -290,6 +300,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
         recs[n - 1] = slam.result(n - 1)
         if want_unc:
             unc_out.append(slam.get_uncertainty(n - 1))
+        if want_degen:
+            degen_out.append(slam.get_degeneracy(n - 1))
         if want_win:
             window_out.append(slam.get_map_window(n - 1))
         if clouds_out is not None:
@@ -327,6 +339,9 @@ def main():
     ap.add_argument("--uncertainty", type=float, nargs="?", const=150.0, default=None, metavar="MIN_EIGENVALUE",
                     help="msfl_slam_set_uncertainty: print per scan the smallest eigenvalue of the mapping solve's information matrix, n_degenerate "
                          "at this threshold (default 150) and the weakest direction [dt(3), dtheta(3)]")
+    ap.add_argument("--degeneracy", default=None, metavar="MIN_EIG_ODOM,MIN_EIG_MAP",
+                    help="msfl_slam_set_degeneracy: both matchers hold the eigen-directions of their entry matrix below the given threshold at the "
+                         "guess (solution remapping); prints per scan n_held of the two outer iterations of both matchers")
     ap.add_argument("--map-window", default=None, metavar="HX,HY,HZ[,N]",
                     help="msfl_slam_set_map_window: crop both map stores to +-HX,HY,HZ cells around the pose after every N-th scan (default 1); "
                          "23,23,23 is the smallest window that takes nothing from the registration of the scan at its centre")
@@ -344,6 +359,12 @@ def main():
         if len(w) not in (3, 4):
             ap.error("--map-window takes HX,HY,HZ[,N]")
         map_window = (tuple(w[:3]), w[3] if len(w) == 4 else 1)
+    degeneracy = None
+    if args.degeneracy:
+        d = [float(v) for v in args.degeneracy.split(",")]
+        if len(d) != 2:
+            ap.error("--degeneracy takes MIN_EIG_ODOM,MIN_EIG_MAP")
+        degeneracy = tuple(d)
     if args.world == "room":
         world = synth.World(ground_half=45.0)
         truth = trajectory(args.scans)
@@ -360,10 +381,14 @@ def main():
     scans = [synth.make_scan(world, truth[k], synth.SEED + 5000 + k, **kw) for k in range(args.scans)]
     import gc
     gc.collect(); gc.disable()
-    unc = []
+    unc, degen = [], []
     est, recs, ms = run_slam(world, truth, pipelined=args.mode == "slam-pipelined", scans=scans, quirks=args.reference_quirks,
                              imu=synthetic_imu(truth) if args.imu else None, clouds_out=[] if args.keep_clouds else None,
-                             uncertainty=args.uncertainty, unc_out=unc, map_window=map_window, load_map=args.load_map, save_map=args.save_map)
+                             uncertainty=args.uncertainty, unc_out=unc, map_window=map_window, load_map=args.load_map, save_map=args.save_map,
+                             degeneracy=degeneracy, degen_out=degen)
+    for k, (o, m) in enumerate(degen):
+        print("scan %4d  n_held odometry %s mapping %s  lambda_min of the mapping solves %s" %
+              (k, list(o["n_held"]), list(m["n_held"]), np.array2string(m["eigenvalues"][:, 0], precision=2)), file=sys.stderr)
     for k, u in enumerate(unc):
         m = u[1]
         if m["valid"]:
@@ -374,7 +399,7 @@ def main():
     if args.dump_poses:
         np.save(args.dump_poses, est)
     print(json.dumps({"mode": args.mode, "world": args.world, "beams": args.beams, "keep_clouds": bool(args.keep_clouds), "scans": args.scans, "reference_quirks": bool(args.reference_quirks), "imu": bool(args.imu),
-                      "map_window": args.map_window, "load_map": args.load_map, "save_map": args.save_map,
+                      "map_window": args.map_window, "degeneracy": args.degeneracy, "load_map": args.load_map, "save_map": args.save_map,
                       "ate_rmse_m": ate(est, truth),
                       "final_error_m_rad": synth.pose_error(est[-1], truth[-1]), "ms_per_scan_end_to_end": ms,
                       "scans_per_s": 1e3 / ms if ms else None,

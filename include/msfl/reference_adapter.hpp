@@ -29,6 +29,8 @@
 //   msfl::adapter::SetUncertaintySink(h, &record, min_eigenvalue)  once;  msfl::adapter::CovarianceInParentFrame(pose, record, scale, out36)
 // and, where the reference's IMUFactor on the scan-to-map problem is commented out (mapping_scan_matcher.cc:84-94):
 //   msfl::adapter::SetPosePrior(h, &prior_record, predicted_pose, sqrt_information)  before MatchScan2Map;  ClearPosePrior(h) after
+// and, for the degenerate geometry the reference steps through ("lidar trajectory will drift in illed situation", :84):
+//   msfl::adapter::SetDegeneracy(h, &degeneracy_record, min_eigenvalue)  once;  ClearDegeneracy(h) to switch it off
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -294,6 +296,13 @@ inline void SetPosePrior(msfl_handle* h, msfl_pose_prior* record, const RigidT& 
   Check(msfl_set_pose_prior(h, record, 1, MSFL_MEM_HOST), h, "msfl_set_pose_prior");
 }
 inline void ClearPosePrior(msfl_handle* h) { Check(msfl_set_pose_prior(h, nullptr, 0, MSFL_MEM_HOST), h, "msfl_set_pose_prior"); }
+
+// ---- degeneracy-aware solve (msfl_set_degeneracy): eigen-directions of a solve's entry matrix below min_eigenvalue stay at the guess.
+// `record` (may be null) receives the last call's msfl_degeneracy_record and must outlive the handle's matcher calls.
+inline void SetDegeneracy(msfl_handle* h, msfl_degeneracy_record* record, double min_eigenvalue) {
+  Check(msfl_set_degeneracy(h, 1, min_eigenvalue, record, record ? 1 : 0, MSFL_MEM_HOST), h, "msfl_set_degeneracy");
+}
+inline void ClearDegeneracy(msfl_handle* h) { Check(msfl_set_degeneracy(h, 0, 0.0, nullptr, 0, MSFL_MEM_HOST), h, "msfl_set_degeneracy"); }
 
 // covariance (row-major 6 x 6, symmetric positive definite, tangent order [dt, dtheta]) -> L with L^T L = covariance^-1: the
 // inverse of the lower Cholesky factor C of the covariance (covariance = C C^T, so its inverse is C^-T C^-1).  Host side, a few

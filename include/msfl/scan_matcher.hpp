@@ -162,12 +162,19 @@ class ScanMatcher {
   // For MatchScan2Map the pose is the world pose (an IMU-predicted pose, a GPS fix), for MatchScan2Scan the relative one.
   void SetPosePrior(const Rigid3d& mean, const Matrix6d& sqrt_information) { adapter::SetPosePrior(h_, &prior_, mean, sqrt_information); }
   void ClearPosePrior() { adapter::ClearPosePrior(h_); }
+  // Opt-in: degeneracy-aware solve (msfl_set_degeneracy; solution remapping after Zhang & Singh).  Every solve of the later Match*
+  // calls decomposes its entry matrix and leaves the eigen-directions below min_eigenvalue at the guess; last_degeneracy() is the
+  // last call's record.  A registration with nothing held is bit-identical to one without the feature.
+  void SetDegeneracy(double min_eigenvalue) { adapter::SetDegeneracy(h_, &degen_, min_eigenvalue); }
+  void ClearDegeneracy() { adapter::ClearDegeneracy(h_); degen_ = msfl_degeneracy_record{}; }
+  const msfl_degeneracy_record& last_degeneracy() const { return degen_; }
 
  protected:
   msfl_handle* h_ = nullptr;
   msfl_match_info info_{};
   msfl_match_uncertainty unc_{};
   msfl_pose_prior prior_{};
+  msfl_degeneracy_record degen_{};
 };
 
 // L with L^T L = covariance^-1 for SetPosePrior (6 x 6 Cholesky of the inverse, host side); throws when `covariance` is not

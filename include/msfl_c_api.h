@@ -149,6 +149,17 @@ typedef struct msfl_pose_prior {
   double sqrt_information[36]; /* row-major 6 x 6 L; information = L^T L */
 } msfl_pose_prior;
 
+/* Per-solve record of the degeneracy-aware solve (opt-in: msfl_set_degeneracy / msfl_slam_set_degeneracy;
+   docs/kernels/degeneracy.md).  Index = outer iteration, as in msfl_match_info: every solve of a registration decomposes the
+   matrix H0 it enters with ({lidar rows, robustified} + the pose prior's block, if one is set) and holds the eigen-directions
+   below the threshold at the guess. */
+typedef struct msfl_degeneracy_record {
+  double eigenvalues[2][6];    /* of H0 at that solve's entry pose, ascending */
+  double eigenvectors[2][36];  /* row k = eigenvector k, tangent order [dt, dtheta], sign as in msfl_match_uncertainty */
+  int n_held[2];               /* eigenvalues below max(min_eigenvalue, 1e-14 * lambda_max): the solve did not move along them */
+  int valid[2];                /* 0: no solve ran, the slice is all zero */
+} msfl_degeneracy_record;
+
 /* Accumulated GPU time per kernel class, measured with HIP events on the handle's stream
    (enabled by msfl_set_timing).  Used by bench.py for the live roofline figure. */
 typedef struct msfl_timing {
@@ -222,6 +233,18 @@ msfl_status msfl_set_uncertainty(msfl_handle* h, msfl_match_uncertainty* out, in
    `information` is the posterior one (lidar J^T J + the prior's, at the returned pose) and n_residuals counts the six prior rows.
    With the feature off, or for an all-zero record, every output is bit-identical to what it was without this call. */
 msfl_status msfl_set_pose_prior(msfl_handle* h, const msfl_pose_prior* priors, int count, msfl_mem mem);
+
+/* Degeneracy-aware solve (solution remapping after Zhang & Singh), off by default; enabled == 0 turns it off.  Otherwise every
+   solve of every later matcher call on this handle (the calls msfl_set_uncertainty lists; each outer iteration is one solve)
+   decomposes its entry matrix H0 and updates the pose only along the eigen-directions with
+   lambda_k >= max(min_eigenvalue, 1e-14 * lambda_max); the others stay at the guess.  A solve with nothing held is bit-identical
+   to the feature-off solve; with all six held the pose passes through (lm_iterations = lm_successful = 0, final_cost =
+   initial_cost, status 0).  A pose prior (msfl_set_pose_prior) is part of H0, so it can make a direction observable.
+   `out` may be NULL (the remapping still runs); otherwise one record per registration goes to out[0 .. n) with the memory kinds,
+   the MSFL_CAPACITY rule and "a failing call writes nothing" of msfl_set_uncertainty.  MSFL_BAD_ARG for a negative or
+   non-finite min_eigenvalue.  The uncertainty output keeps its meaning: the full information at the returned pose. */
+msfl_status msfl_set_degeneracy(msfl_handle* h, int enabled, double min_eigenvalue, msfl_degeneracy_record* out, int capacity,
+                                msfl_mem mem);
 
 /* ------------------------------------------------------------------------------------------ */
 /* stage C — scan-to-local-map registration                                                   */
@@ -762,6 +785,16 @@ msfl_status msfl_slam_set_uncertainty(msfl_slam* s, int enabled, double min_eige
    mapping->valid == 0 when the gate (min_map_corner / min_map_surf) kept the match from running.  MSFL_BAD_ARG for a scan that
    was fed while the feature was off. */
 msfl_status msfl_slam_get_uncertainty(msfl_slam* s, int scan_index, msfl_match_uncertainty* odometry, msfl_match_uncertainty* mapping);
+
+/* Degeneracy-aware solve (msfl_set_degeneracy) of the two registrations of every scan fed from now on: `odometry` switches
+   MatchScan2Scan's solves, `mapping` MatchScan2Map's, each with a threshold of its own (their information matrices live on
+   different scales).  With both 0 the feature is off.  MSFL_BAD_ARG for a negative or non-finite threshold of a matcher that is
+   switched on.  Where nothing is held the results (msfl_slam_result) are bit-identical to a run without the feature. */
+msfl_status msfl_slam_set_degeneracy(msfl_slam* s, int odometry, int mapping, double min_eig_odometry, double min_eig_mapping);
+/* The records of scan `scan_index`, under the rules of msfl_slam_get_uncertainty (one of the last four fed; waits for it; either
+   pointer may be NULL; MSFL_BAD_ARG for a scan that was fed while both switches were off).  A matcher that was off, or did not
+   run, leaves its record all zero. */
+msfl_status msfl_slam_get_degeneracy(msfl_slam* s, int scan_index, msfl_degeneracy_record* odometry, msfl_degeneracy_record* mapping);
 
 /* Pose priors for the NEXT msfl_slam_add_scan[_imu] only (host pointers, copied here; either may be NULL = none):
      odometry : on that scan's MatchScan2Scan, whose unknown is the RELATIVE pose pose_curr2last;

@@ -32,6 +32,7 @@ EXPORTED = [
     "msfl_slam_last_error", "msfl_slam_get_clouds",
     "msfl_set_uncertainty", "msfl_slam_set_uncertainty", "msfl_slam_get_uncertainty",
     "msfl_set_pose_prior", "msfl_slam_set_next_prior",
+    "msfl_set_degeneracy", "msfl_slam_set_degeneracy", "msfl_slam_get_degeneracy",
 ]
 
 
@@ -87,6 +88,17 @@ class PosePrior(C.Structure):
 # the same record as a numpy structured dtype (Handle.set_pose_prior, Slam.set_next_prior)
 POSE_PRIOR_DTYPE = np.dtype([("pose", np.float64, (7,)), ("sqrt_information", np.float64, (6, 6))])
 assert POSE_PRIOR_DTYPE.itemsize == C.sizeof(PosePrior)
+
+
+class DegeneracyRecord(C.Structure):
+    """msfl_degeneracy_record: per outer iteration the eigen-decomposition of the solve's entry matrix and the number of held directions."""
+    _fields_ = [("eigenvalues", (C.c_double * 6) * 2), ("eigenvectors", (C.c_double * 36) * 2), ("n_held", C.c_int * 2), ("valid", C.c_int * 2)]
+
+
+# the same record as a numpy structured dtype (Handle.degeneracy, Slam.get_degeneracy)
+DEGENERACY_DTYPE = np.dtype([("eigenvalues", np.float64, (2, 6)), ("eigenvectors", np.float64, (2, 6, 6)), ("n_held", np.int32, (2,)),
+                             ("valid", np.int32, (2,))])
+assert DEGENERACY_DTYPE.itemsize == C.sizeof(DegeneracyRecord) == 688
 
 
 def pose_priors(poses, sqrt_info):
@@ -317,6 +329,33 @@ class Handle:
         self._unc = None
         self._check(self.lib.msfl_set_uncertainty(self.h, _vp(ptr), C.c_int(int(capacity) if ptr is not None else 0), C.c_int(MEM_DEVICE),
                                                   C.c_double(float(min_eigenvalue))), "msfl_set_uncertainty(device)")
+
+    # ---- degeneracy-aware solve (msfl_set_degeneracy) ----
+    def set_degeneracy(self, min_eigenvalue, n=0):
+        """Every later solve holds the eigen-directions of its entry matrix below `min_eigenvalue` at the guess.  n > 0: one
+        msfl_degeneracy_record per registration goes to a host buffer of `n` records owned by this object (read it with degeneracy())."""
+        buf = np.zeros(int(n), DEGENERACY_DTYPE) if n else None
+        self._check(self.lib.msfl_set_degeneracy(self.h, C.c_int(1), C.c_double(float(min_eigenvalue)), _vp(buf), C.c_int(int(n) if n else 0),
+                                                 C.c_int(MEM_HOST)), "msfl_set_degeneracy")
+        self._degen = buf
+
+    def set_degeneracy_device(self, min_eigenvalue, ptr, capacity):
+        """Device-pointer sink: `ptr` (torch tensor / raw pointer) holds `capacity` records of DEGENERACY_DTYPE.itemsize bytes, written
+        asynchronously on the handle's stream."""
+        self._check(self.lib.msfl_set_degeneracy(self.h, C.c_int(1), C.c_double(float(min_eigenvalue)), _vp(ptr), C.c_int(int(capacity)),
+                                                 C.c_int(MEM_DEVICE)), "msfl_set_degeneracy(device)")
+        self._degen = None
+
+    def clear_degeneracy(self):
+        self._check(self.lib.msfl_set_degeneracy(self.h, C.c_int(0), C.c_double(0.0), None, C.c_int(0), C.c_int(MEM_HOST)), "msfl_set_degeneracy")
+        self._degen = None
+
+    def degeneracy(self, n=None):
+        """The first `n` records (default: all) the last matcher call wrote, as a copy of the numpy structured array."""
+        buf = getattr(self, "_degen", None)
+        if buf is None:
+            raise RuntimeError("no degeneracy record sink: call set_degeneracy(min_eigenvalue, n) first")
+        return buf[:len(buf) if n is None else int(n)].copy()
 
     # ---- pose priors (msfl_set_pose_prior) ----
     def set_pose_prior(self, poses, sqrt_info):
@@ -848,6 +887,23 @@ class Slam:
         st = self.lib.msfl_slam_set_uncertainty(self.s, C.c_int(1 if enabled else 0), C.c_double(float(min_eigenvalue)))
         if st != OK:
             raise MsflError(st, "msfl_slam_set_uncertainty", self._err())
+
+    def set_degeneracy(self, odometry=None, mapping=None):
+        """Degeneracy-aware solve of every scan fed from now on: `odometry` / `mapping` is the eigenvalue threshold of that matcher,
+        None leaves it off."""
+        st = self.lib.msfl_slam_set_degeneracy(self.s, C.c_int(odometry is not None), C.c_int(mapping is not None),
+                                               C.c_double(0.0 if odometry is None else float(odometry)),
+                                               C.c_double(0.0 if mapping is None else float(mapping)))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_set_degeneracy", self._err())
+
+    def get_degeneracy(self, scan_index):
+        """(odometry, mapping) records of DEGENERACY_DTYPE of one of the last four scans fed (waits for it)."""
+        out = np.zeros(2, DEGENERACY_DTYPE)
+        st = self.lib.msfl_slam_get_degeneracy(self.s, C.c_int(int(scan_index)), C.c_void_p(out[0:1].ctypes.data), C.c_void_p(out[1:2].ctypes.data))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_get_degeneracy", self._err())
+        return out[0], out[1]
 
     def set_next_prior(self, odometry=None, mapping=None):
         """Pose priors for the NEXT add_scan only: each a (pose7, sqrt_information 6 x 6) pair or None.  `odometry` joins that scan's

@@ -31,6 +31,7 @@
 #include "msfl_grid.cuh"
 #include "msfl_deskew.cuh"
 #include "msfl_uncertainty.cuh"
+#include "msfl_degeneracy.cuh"
 
 using namespace msfl;
 
@@ -193,6 +194,13 @@ struct msfl_handle_s {
   int prior_count = 0;
   msfl_mem prior_mem = MSFL_MEM_HOST;
   DevBuf prior_dev;                       // device staging of host records
+  // msfl_set_degeneracy: every solve holds the eigen-directions of its entry matrix below the threshold (0: feature off)
+  int degen_on = 0;
+  double degen_min_eigenvalue = 0.0;
+  msfl_degeneracy_record* degen_out = nullptr;   // optional sink, one record per registration
+  int degen_capacity = 0;
+  msfl_mem degen_mem = MSFL_MEM_HOST;
+  DevBuf degen_dev;                       // device staging of a host sink
 
   PinRing pin;
   PinBuf readback;
@@ -289,12 +297,19 @@ inline int div_up(int a, int b) { return (a + b - 1) / b; }
 static_assert(sizeof(UncRecord) == sizeof(msfl_match_uncertainty), "uncertainty record layout");
 static_assert(sizeof(PosePrior) == sizeof(msfl_pose_prior), "pose prior record layout");
 static_assert(sizeof(DevMatchInfo) == sizeof(msfl_match_info), "info layout");
+static_assert(sizeof(DegenRecord) == sizeof(msfl_degeneracy_record), "degeneracy record layout");
 struct RegSinks {
   DevMatchInfo* info = nullptr;      // never null when `unc` is not: the uncertainty record takes sigma2 from the solve's own final cost
   UncRecord* unc = nullptr;          // null: feature off
   const PosePrior* prior = nullptr;  // null: feature off
   double unc_min_eig = 0.0;
-  RegSinks at(int b) const { return {info ? info + b : nullptr, unc ? unc + b : nullptr, prior ? prior + b : nullptr, unc_min_eig}; }   // a part of a batch
+  int degen_on = 0;                  // msfl_set_degeneracy: 0 = feature off
+  double degen_min_eig = 0.0;
+  DegenRecord* degen = nullptr;      // optional record sink of the feature (zeroed before the first solve)
+  RegSinks at(int b) const {         // a part of a batch
+    return {info ? info + b : nullptr, unc ? unc + b : nullptr, prior ? prior + b : nullptr, unc_min_eig, degen_on, degen_min_eig,
+            degen ? degen + b : nullptr};
+  }
 };
 
 // First thing a matcher call does, before it stages or launches anything: refuse a call with more registrations than the sink holds or
@@ -304,6 +319,9 @@ msfl_status reg_check(msfl_handle* h, int n, const char* who) {
   if (h->unc_out && n > h->unc_capacity)
     return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_uncertainty sink holds " +
                                       std::to_string(h->unc_capacity));
+  if (h->degen_on && h->degen_out && n > h->degen_capacity)
+    return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_degeneracy sink holds " +
+                                      std::to_string(h->degen_capacity));
   if (!h->prior_in) return MSFL_OK;
   if (n > h->prior_count)
     return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, msfl_set_pose_prior gave " +
@@ -321,6 +339,7 @@ msfl_status reg_check(msfl_handle* h, int n, const char* who) {
 }
 
 inline bool unc_host(const msfl_handle* h) { return h->unc_out && h->unc_mem == MSFL_MEM_HOST; }
+inline bool degen_host(const msfl_handle* h) { return h->degen_on && h->degen_out && h->degen_mem == MSFL_MEM_HOST; }
 
 // Where the kernels of this call of n registrations find their sinks: the caller's device pointers, or device staging of its host ones
 // (the prior records are copied on stream st, ahead of the clearing of the info records).  want_info: the caller asked for the info records.
@@ -337,6 +356,17 @@ msfl_status reg_open(msfl_handle* h, int n, hipStream_t st, bool want_info, RegS
     HIPCHK(h, h->prior_dev.reserve((size_t)n * sizeof(PosePrior)));
     HIPCHK(h, h->pin.upload(h->prior_dev.p, h->prior_in, (size_t)n * sizeof(PosePrior), st));
     k->prior = h->prior_dev.as<PosePrior>();
+  }
+  if (h->degen_on) {
+    k->degen_on = 1;
+    k->degen_min_eig = h->degen_min_eigenvalue;
+    if (h->degen_out && h->degen_mem == MSFL_MEM_DEVICE) k->degen = reinterpret_cast<DegenRecord*>(h->degen_out);
+    else if (h->degen_out) {
+      HIPCHK(h, h->degen_dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(DegenRecord)));
+      k->degen = h->degen_dev.as<DegenRecord>();
+    }
+    // the solve kernel writes a slice only where it solves: every other slice stays all zero (valid = 0)
+    if (k->degen && n > 0) HIPCHK(h, hipMemsetAsync(k->degen, 0, (size_t)n * sizeof(DegenRecord), st));
   }
   if (want_info || k->unc) {
     HIPCHK(h, h->info.reserve((size_t)n * sizeof(DevMatchInfo)));
@@ -357,7 +387,9 @@ msfl_status reg_close(msfl_handle* h, int n, msfl_mem mem, double* poses_io, con
   }
   if (info) HIPCHK(h, hipMemcpyAsync(info, k.info, (size_t)n * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
   if (unc_host(h) && k.unc && n > 0) HIPCHK(h, hipMemcpyAsync(h->unc_out, k.unc, (size_t)n * sizeof(UncRecord), hipMemcpyDeviceToHost, st));
-  if (mem == MSFL_MEM_HOST || info || unc_host(h)) HIPCHK(h, hipStreamSynchronize(st));
+  if (degen_host(h) && k.degen && n > 0)
+    HIPCHK(h, hipMemcpyAsync(h->degen_out, k.degen, (size_t)n * sizeof(DegenRecord), hipMemcpyDeviceToHost, st));
+  if (mem == MSFL_MEM_HOST || info || unc_host(h) || degen_host(h)) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 
@@ -371,7 +403,7 @@ msfl_status solve_outer(msfl_handle* h, int n, const BatchView& bv, const double
   for (int it = 0; it < n_outer; it++) {
     { const msfl_status as = assoc(it); if (as) return as; }
     ScopedTimer timer(h, T_SOLVE);
-    launch_lm_solve<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, it, sp, k.prior);
+    launch_lm_solve<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, it, sp, k.prior, k.degen_on, k.degen_min_eig, k.degen);
   }
   launch_uncertainty<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, n_outer - 1, sp, k.unc_min_eig, k.unc, k.prior);
   HIPCHK(h, hipGetLastError());
@@ -800,6 +832,20 @@ msfl_status msfl_set_uncertainty(msfl_handle* h, msfl_match_uncertainty* out, in
   h->unc_capacity = out ? capacity : 0;
   h->unc_mem = mem;
   h->unc_min_eigenvalue = out ? min_eigenvalue : 0.0;
+  return MSFL_OK;
+}
+
+msfl_status msfl_set_degeneracy(msfl_handle* h, int enabled, double min_eigenvalue, msfl_degeneracy_record* out, int capacity, msfl_mem mem) {
+  msfl_status s = enter(h); if (s) return s;
+  if (enabled && (!(min_eigenvalue >= 0.0) || !std::isfinite(min_eigenvalue)))
+    return fail(h, MSFL_BAD_ARG, "msfl_set_degeneracy: min_eigenvalue negative or not finite");
+  if (enabled && out && (capacity < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE)))
+    return fail(h, MSFL_BAD_ARG, "msfl_set_degeneracy: capacity < 1 or unknown memory kind");
+  h->degen_on = enabled != 0;
+  h->degen_min_eigenvalue = enabled ? min_eigenvalue : 0.0;
+  h->degen_out = enabled ? out : nullptr;
+  h->degen_capacity = enabled && out ? capacity : 0;
+  h->degen_mem = mem;
   return MSFL_OK;
 }
 

@@ -35,7 +35,7 @@ struct SlamScanBuf {                    // everything derived from ONE scan that
 };
 
 constexpr int kSlamSlots = 4;
-struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; bool prior_map; bool crop; int half[3]; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
+struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; bool prior_map; bool crop; int half[3]; bool degen, degen_map; double degen_map_min_eig; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
 constexpr int kSlamProfileSkip = 20;                    // MSFL_SLAM_HOST_PROFILE leaves the first scans (allocations) out
 #ifndef MSFL_SLAM_ODOM_LANES
 #define MSFL_SLAM_ODOM_LANES 64
@@ -78,6 +78,13 @@ struct msfl_slam_s {
   DevBuf unc[kSlamSlots];
   PinBuf unc_host;                      // kSlamSlots x 2 records
   bool unc_held[kSlamSlots] = {};       // the scan in this slot was fed with the feature on
+  // msfl_slam_set_degeneracy: the two matchers' switches and thresholds; two msfl_degeneracy_record per slot {odometry, mapping},
+  // which travel with the slot's result copy like the uncertainty records
+  bool degen_on[2] = {};
+  double degen_min_eigenvalue[2] = {};
+  DevBuf degen[kSlamSlots];
+  PinBuf degen_host;                    // kSlamSlots x 2 records
+  bool degen_held[kSlamSlots] = {};     // the scan in this slot was fed with the feature on (either matcher)
   // msfl_slam_set_next_prior: {odometry, mapping} records for the NEXT scan only.  They are copied to the slot of the scan that
   // consumes them (on its odometry stream, ahead of ev_odo), so a later msfl_slam_add_scan cannot overwrite what a queued
   // mapping chain has not read yet: a slot is reused only after its scan's record is out.
@@ -475,6 +482,34 @@ msfl_status msfl_slam_set_uncertainty(msfl_slam* s, int enabled, double min_eige
   return MSFL_OK;
 }
 
+msfl_status msfl_slam_set_degeneracy(msfl_slam* s, int odometry, int mapping, double min_eig_odometry, double min_eig_mapping) {
+  if (!s) return MSFL_BAD_ARG;
+  if ((odometry && !(min_eig_odometry >= 0.0 && std::isfinite(min_eig_odometry))) || (mapping && !(min_eig_mapping >= 0.0 && std::isfinite(min_eig_mapping))))
+    return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_degeneracy: a threshold is negative or not finite");
+  SHIP(s, hipSetDevice(s->ho->device));
+  if ((odometry || mapping) && !s->degen_host.p) {
+    for (auto& b : s->degen) SHIP(s, b.reserve(2 * sizeof(DegenRecord)));
+    SHIP(s, s->degen_host.reserve(kSlamSlots * 2 * sizeof(DegenRecord)));
+  }
+  s->degen_on[0] = odometry != 0;       // read once per msfl_slam_add_scan, like msfl_slam_set_uncertainty
+  s->degen_on[1] = mapping != 0;
+  s->degen_min_eigenvalue[0] = odometry ? min_eig_odometry : 0.0;
+  s->degen_min_eigenvalue[1] = mapping ? min_eig_mapping : 0.0;
+  return MSFL_OK;
+}
+
+msfl_status msfl_slam_get_degeneracy(msfl_slam* s, int scan_index, msfl_degeneracy_record* odometry, msfl_degeneracy_record* mapping) {
+  if (!s) return MSFL_BAD_ARG;
+  int slot;
+  { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_degeneracy", &slot); if (rs) return rs; }
+  if (!s->degen_held[slot]) return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_degeneracy: that scan was fed with msfl_slam_set_degeneracy off");
+  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
+  const msfl_degeneracy_record* d = s->degen_host.as<msfl_degeneracy_record>() + 2 * slot;
+  if (odometry) *odometry = d[0];
+  if (mapping) *mapping = d[1];
+  return MSFL_OK;
+}
+
 msfl_status msfl_slam_set_next_prior(msfl_slam* s, const msfl_pose_prior* odometry, const msfl_pose_prior* mapping) {
   if (!s) return MSFL_BAD_ARG;
   const msfl_pose_prior* in[2] = {odometry, mapping};
@@ -652,7 +687,8 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   msfl_slam_result* rec = s->rec[slot].as<msfl_slam_result>();
   // the slot's second records are the mapping match's (the prior was uploaded ahead of cur.ev_odo)
   const RegSinks map_sinks{reinterpret_cast<DevMatchInfo*>(&rec->mapping), jb.unc ? s->unc[slot].as<UncRecord>() + 1 : nullptr,
-                           jb.prior_map ? s->prior[slot].as<PosePrior>() + 1 : nullptr, jb.unc_min_eig};
+                           jb.prior_map ? s->prior[slot].as<PosePrior>() + 1 : nullptr, jb.unc_min_eig,
+                           jb.degen_map ? 1 : 0, jb.degen_map_min_eig, jb.degen_map ? s->degen[slot].as<DegenRecord>() + 1 : nullptr};
   const SlamImuDev* d_imu = cur.imu.as<SlamImuDev>();
   const int cap_ls = std::min(n, s->caps.less_sharp), cap_lf = std::min(n, s->caps.less_flat);
   double* chain = s->chain.as<double>();
@@ -738,6 +774,8 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   SHIP(s, hipMemcpyAsync(s->rec_host.as<msfl_slam_result>() + slot, rec, sizeof(msfl_slam_result), hipMemcpyDeviceToHost, sm));
   if (jb.unc)
     SHIP(s, hipMemcpyAsync(s->unc_host.as<UncRecord>() + 2 * slot, s->unc[slot].p, 2 * sizeof(UncRecord), hipMemcpyDeviceToHost, sm));
+  if (jb.degen)
+    SHIP(s, hipMemcpyAsync(s->degen_host.as<DegenRecord>() + 2 * slot, s->degen[slot].p, 2 * sizeof(DegenRecord), hipMemcpyDeviceToHost, sm));
   if (jb.crop)
     SHIP(s, hipMemcpyAsync(s->win_host.as<int>() + 2 * CROP_WORDS * slot, s->win[slot].p, 2 * CROP_WORDS * sizeof(int), hipMemcpyDeviceToHost, sm));
   SHIP(s, hipEventRecord(s->ev_done[slot], sm));
@@ -791,6 +829,10 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   const double unc_min_eig = s->unc_min_eigenvalue;
   s->unc_held[slot] = unc;
   if (unc) SHIP(s, hipMemsetAsync(s->unc[slot].p, 0, 2 * sizeof(UncRecord), so));      // scan 0 has no odometry match, a closed gate no mapping match
+  const bool degen_odo = s->degen_on[0], degen_map = s->degen_on[1];
+  const double degen_odo_min_eig = s->degen_min_eigenvalue[0], degen_map_min_eig = s->degen_min_eigenvalue[1];
+  s->degen_held[slot] = degen_odo || degen_map;
+  if (degen_odo || degen_map) SHIP(s, hipMemsetAsync(s->degen[slot].p, 0, 2 * sizeof(DegenRecord), so));   // a slice stays zero where no solve runs
   // msfl_slam_set_next_prior: consumed by this scan, whatever becomes of it
   const bool prior_odo = s->next_prior_set[0], prior_map = s->next_prior_set[1];
   s->next_prior_set[0] = s->next_prior_set[1] = false;
@@ -868,7 +910,8 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   double* poses_k = cur.poses.as<double>();
   if (k > 0) {                                                   // laser_odometry.cc:72-75: the first scan only initialises
     const RegSinks odo_sinks{reinterpret_cast<DevMatchInfo*>(&rec->odometry), unc ? s->unc[slot].as<UncRecord>() : nullptr,
-                             prior_odo ? s->prior[slot].as<PosePrior>() : nullptr, unc_min_eig};
+                             prior_odo ? s->prior[slot].as<PosePrior>() : nullptr, unc_min_eig,
+                             degen_odo ? 1 : 0, degen_odo_min_eig, degen_odo ? s->degen[slot].as<DegenRecord>() : nullptr};
     SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, odo_sinks));
   }
   hipLaunchKernelGGL(slam_odom_pose_kernel, dim3(1), dim3(1), 0, so, (const double*)chain, chain + 7, poses_k, poses_k + 14,
@@ -884,7 +927,7 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   }
   const bool crop = s->win_on && (k + 1) % s->win_every == 0;
   s->win_held[slot] = crop;
-  const SlamJob job{k, n, imu_mode, unc, unc_min_eig, prior_map, crop, {s->win_half[0], s->win_half[1], s->win_half[2]}};
+  const SlamJob job{k, n, imu_mode, unc, unc_min_eig, prior_map, crop, {s->win_half[0], s->win_half[1], s->win_half[2]}, degen_odo || degen_map, degen_map, degen_map_min_eig};
   if (s->threaded) {
     std::unique_lock<std::mutex> lk(s->mu);
     s->cv_done.wait(lk, [&] { return !s->has_job; });            // the mapping thread is at most one scan behind

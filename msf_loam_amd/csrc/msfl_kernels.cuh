@@ -1525,108 +1525,9 @@ __device__ __forceinline__ void unpack_system(const double* sys, double (&H)[6][
 // dozen global round trips per call on a single lane (found with clock reads inside the function: the six clamps of the
 // LM diagonal alone took 7 us).
 __device__ __noinline__ int tr_propose(TrState& tr, const SolverParams prm) {
-  for (;;) {
-    if (tr.iteration >= prm.max_iterations) return 0;
-    if (tr.step_ok && tr.gmax <= prm.gtol) return 0;
-    if (tr.radius < prm.radius_min) return 0;
-    tr.iteration++;
-    // A = S H S (+ LM damping); its Cholesky factor goes to L, A itself stays readable for the model cost change.
-    double A[6][6], gs[6], y[6], lm2[6];
-    {
-      int n = 7;
-#pragma unroll
-      for (int p = 0; p < 6; p++)
-#pragma unroll
-        for (int q = p; q < 6; q++) { const double v = tr.sys[n++] * tr.scale[p] * tr.scale[q]; A[p][q] = v; A[q][p] = v; }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) gs[i] = tr.sys[1 + i] * tr.scale[i];
-    if (!tr.reuse_diagonal) {
-#pragma unroll
-      for (int i = 0; i < 6; i++) tr.diagonal[i] = fmin(fmax(A[i][i], prm.min_diag), prm.max_diag);
-    }
-    double hs_diag[6];                     // undamped diagonal of S H S, for the model cost change below
-    // Ceres' LM strategy appends sqrt(diagonal / radius) as extra Jacobian rows, i.e. adds diagonal / radius to the
-    // normal equations: formed directly here (one division for all six), equal up to the rounding of sqrt(.)^2
-    const double inv_radius = 1.0 / tr.radius;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-      lm2[i] = tr.diagonal[i] * inv_radius;
-      hs_diag[i] = A[i][i];
-      A[i][i] += lm2[i];
-    }
-    // factorise, solve, then step^T Hs step from the very values A was formed from (off-diagonal entries of A and the
-    // diagonal saved before damping): no second pass over the packed system in LDS.  The factor is kept as
-    // L[i][j] (i > j) and the RECIPROCALS of its diagonal: one reciprocal square root per column instead of a
-    // square root and 2 x (5 - j) + 2 divisions (this serial, single-lane chain is latency bound: ~200 clocks each)
-    double L[6][6], dinv[6];
-    bool ok = true;
-#pragma unroll
-    for (int jc = 0; jc < 6; jc++) {
-      double s = A[jc][jc];
-#pragma unroll
-      for (int k = 0; k < jc; k++) s = __builtin_fma(-L[jc][k], L[jc][k], s);
-      if (!(s > 0.0)) ok = false;
-      dinv[jc] = fast_rsqrt(s);
-#pragma unroll
-      for (int i = jc + 1; i < 6; i++) {
-        double v = A[i][jc];
-#pragma unroll
-        for (int k = 0; k < jc; k++) v = __builtin_fma(-L[i][k], L[jc][k], v);
-        L[i][jc] = v * dinv[jc];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-      double s = gs[i];
-#pragma unroll
-      for (int k = 0; k < i; k++) s = __builtin_fma(-L[i][k], y[k], s);
-      y[i] = s * dinv[i];
-    }
-    double step[6];
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-      double s = y[i];
-#pragma unroll
-      for (int k = i + 1; k < 6; k++) s = __builtin_fma(-L[k][i], step[k], s);
-      step[i] = s * dinv[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) { if (!isfinite(step[i])) ok = false; step[i] = -step[i]; }
-    tr.reuse_diagonal = 1;
-    double mcc = 0.0;
-    if (ok) {
-      double gts = 0.0, shs = 0.0;
-#pragma unroll
-      for (int i = 0; i < 6; i++) {
-        gts += gs[i] * step[i];
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-          // Hs[i][j]: the value A was formed from (A itself off the diagonal, the saved entry on it)
-          shs += step[i] * (i == j ? hs_diag[i] : A[i][j]) * step[j];
-        }
-      }
-      mcc = -gts - 0.5 * shs;
-    }
-    tr.model_cost_change = mcc;
-    if (!ok || !(mcc > 0.0)) {          // HandleInvalidStep
-      if (++tr.invalid >= prm.max_invalid) return 0;
-      tr.radius *= 0.5;
-      tr.step_ok = 0;
-      continue;
-    }
-    tr.invalid = 0;
-    const pose7 x = load_pose(tr.x);
-    const pose7 cand = pose_plus(x, mk3(step[0] * tr.scale[0], step[1] * tr.scale[1], step[2] * tr.scale[2]),
-                                 mk3(step[3] * tr.scale[3], step[4] * tr.scale[4], step[5] * tr.scale[5]));
-    store_pose(tr.cand, cand);
-    double sn = 0.0;
-#pragma unroll
-    for (int i = 0; i < 7; i++) { const double d = tr.x[i] - tr.cand[i]; sn += d * d; }
-    sn = sqrt(sn);
-    if (sn <= prm.ptol * (tr.x_norm + prm.ptol)) return 0;   // ParameterToleranceReached
-    return 1;
-  }
+#define MSFL_TR_DEGEN 0
+#include "msfl_tr_propose_body.inc"
+#undef MSFL_TR_DEGEN
 }
 
 // FunctionToleranceReached / IsStepSuccessful / HandleSuccessfulStep / HandleUnsuccessfulStep,
@@ -1744,7 +1645,9 @@ lm_solve_kernel(BatchView bv, const double* __restrict__ pprime_all, const doubl
                 double* __restrict__ poses, int* __restrict__ status, DevMatchInfo* __restrict__ info,
                 int outer_it, SolverParams prm) {
 #define MSFL_LM_PRIOR 0
+#define MSFL_LM_DEGEN 0
 #include "msfl_lm_solve_body.inc"
+#undef MSFL_LM_DEGEN
 #undef MSFL_LM_PRIOR
 }
 
@@ -1755,18 +1658,34 @@ lm_solve_prior_kernel(BatchView bv, const double* __restrict__ pprime_all, const
                       double* __restrict__ poses, int* __restrict__ status, DevMatchInfo* __restrict__ info,
                       int outer_it, SolverParams prm, const PosePrior* __restrict__ prior_all) {
 #define MSFL_LM_PRIOR 1
+#define MSFL_LM_DEGEN 0
 #include "msfl_lm_solve_body.inc"
+#undef MSFL_LM_DEGEN
 #undef MSFL_LM_PRIOR
 }
 
-// The one launch helper of all six solve sites: `prior` null = feature off, the kernel that was always launched.
+// The sibling with solution remapping (msfl_set_degeneracy), defined in msfl_degeneracy.cuh: it needs the Jacobi routine of
+// msfl_uncertainty.cuh.  `prior_all` may be null there.
+struct DegenRecord;
+template <int BLOCK>
+__global__ void lm_solve_degen_kernel(BatchView bv, const double* __restrict__ pprime_all, const double* __restrict__ rec_all,
+                                      double* __restrict__ poses, int* __restrict__ status, DevMatchInfo* __restrict__ info,
+                                      int outer_it, SolverParams prm, const PosePrior* __restrict__ prior_all, double degen_min_eig,
+                                      DegenRecord* __restrict__ degen_out);
+
+// The one launch helper of all six solve sites: `prior` null and `degen_on` 0 = both features off, the kernel that was always
+// launched.  With degen_on the remapping sibling runs (with or without a prior); `degen_out` may be null.
 template <int BLOCK>
 inline void launch_lm_solve(hipStream_t st, int n_scans, const BatchView& bv, const double* pprime, const double* records, double* poses,
-                            int* status, DevMatchInfo* info, int outer_it, const SolverParams& sp, const PosePrior* prior) {
-  if (!prior)
+                            int* status, DevMatchInfo* info, int outer_it, const SolverParams& sp, const PosePrior* prior,
+                            int degen_on = 0, double degen_min_eig = 0.0, DegenRecord* degen_out = nullptr) {
+  if (!degen_on && !prior)          // the plain kernel is named first: the kernels are emitted in this order (docs/kernels/prior.md)
     hipLaunchKernelGGL(lm_solve_kernel<BLOCK>, dim3(n_scans), dim3(BLOCK), 0, st, bv, pprime, records, poses, status, info, outer_it, sp);
-  else
+  else if (!degen_on)
     hipLaunchKernelGGL(lm_solve_prior_kernel<BLOCK>, dim3(n_scans), dim3(BLOCK), 0, st, bv, pprime, records, poses, status, info, outer_it, sp, prior);
+  else
+    hipLaunchKernelGGL(lm_solve_degen_kernel<BLOCK>, dim3(n_scans), dim3(BLOCK), 0, st, bv, pprime, records, poses, status, info, outer_it, sp,
+                       prior, degen_min_eig, degen_out);
 }
 
 }  // namespace msfl

@@ -1,12 +1,18 @@
-// Body of lm_solve_kernel (MSFL_LM_PRIOR 0) and lm_solve_prior_kernel (MSFL_LM_PRIOR 1), included once in each (msfl_kernels.cuh).
+// Body of lm_solve_kernel (MSFL_LM_PRIOR 0), lm_solve_prior_kernel (MSFL_LM_PRIOR 1), both in msfl_kernels.cuh, and
+// lm_solve_degen_kernel (MSFL_LM_DEGEN 1, msfl_degeneracy.cuh), included once in each.
 // A textual include, not a shared device function: the feature-off kernel is then token for token the kernel it was before the
 // pose prior existed, so its code object cannot move (docs/kernels/prior.md).  In scope: BLOCK, bv, pprime_all, rec_all, poses,
-// status, info, outer_it, prm and, with MSFL_LM_PRIOR, prior_all.
+// status, info, outer_it, prm and, with MSFL_LM_PRIOR, prior_all.  With MSFL_LM_DEGEN: prior_all (may be null: the prior lines sit
+// behind a run-time check, there is no sibling for "prior + degeneracy"), degen_min_eig and degen_out (may be null).
   __shared__ LmShared<BLOCK> sh;
   __shared__ PlaneCache<BLOCK> s_cache;
   __shared__ EdgeList s_edges;
 #if MSFL_LM_PRIOR
   __shared__ PosePrior s_prior;
+#endif
+#if MSFL_LM_DEGEN
+  __shared__ PosePrior s_prior;
+  __shared__ DegenState s_degen;
 #endif
   const int b = blockIdx.x;
   if (status[b] != 0) return;
@@ -17,6 +23,17 @@
     int bad;
     prior_stage<BLOCK>(prior_all + b, s_prior, bad, use_prior);
     if (bad) {                                 // uniform: a non-finite prior is refused, the pose passes through
+      if (threadIdx.x == 0) { status[b] = 3; if (info) info[b].status = 3; }   // MSFL_BAD_ARG
+      return;
+    }
+  }
+#endif
+#if MSFL_LM_DEGEN
+  int use_prior = 0;
+  if (prior_all) {                             // uniform (a kernel argument)
+    int bad;
+    prior_stage<BLOCK>(prior_all + b, s_prior, bad, use_prior);
+    if (bad) {
       if (threadIdx.x == 0) { status[b] = 3; if (info) info[b].status = 3; }   // MSFL_BAD_ARG
       return;
     }
@@ -73,6 +90,13 @@
 #if MSFL_LM_PRIOR
       if (use_prior) prior_accumulate(load_pose(pose_g), &s_prior, sh.red);
 #endif
+#if MSFL_LM_DEGEN
+      if (use_prior) prior_accumulate(load_pose(pose_g), &s_prior, sh.red);
+      // H0 of this solve: lidar rows + prior block.  Decomposed once; V_k is fixed for the solve, as the Jacobi scaling is.
+      const int n_held = degen_decompose(sh.red, degen_min_eig, s_degen);
+      if (degen_out) degen_write_record(s_degen, degen_out + b, outer_it);
+      if (n_held > 0 && n_held < 6) degen_rotate(s_degen, sh.red);
+#endif
 #pragma unroll
       for (int k = 0; k < kAcc; k++) tr.sys[k] = sh.red[k];
 #pragma unroll
@@ -84,11 +108,21 @@
 #pragma unroll
       for (int i = 0; i < 6; i++) tr.scale[i] = 1.0 / (1.0 + sqrt(sh.red[dg[i]]));
       const pose7 x = load_pose(tr.x);
+#if MSFL_LM_DEGEN
+      tr.gmax = n_held > 0 && n_held < 6 ? degen_gradient_max_norm(s_degen, tr.x, tr.sys + 1, prm.gtol)
+                                         : gradient_max_norm_for_test(x, tr.sys + 1, prm.gtol);
+#else
       tr.gmax = gradient_max_norm_for_test(x, tr.sys + 1, prm.gtol);
+#endif
       tr.x_norm = pose_norm(x);
       tr.radius = prm.radius0; tr.decrease_factor = 2.0; tr.model_cost_change = 0.0;
       tr.invalid = 0; tr.reuse_diagonal = 0; tr.step_ok = 1;
+#if MSFL_LM_DEGEN
+      if (n_held == 6) go = 0;             // nothing observable: no step, the pose passes through, counts stay 0
+      else go = n_held > 0 ? tr_propose_degen(tr, prm, s_degen) : tr_propose(tr, prm);
+#else
       go = tr_propose(tr, prm);
+#endif
     }
     sh.go = go;
   }
@@ -109,7 +143,21 @@
 #if MSFL_LM_PRIOR
     if (use_prior && threadIdx.x == 0) prior_accumulate(load_pose(tr.cand), &s_prior, sh.red);
 #endif
-#ifdef MSFL_LM_PROFILE
+#if MSFL_LM_DEGEN
+    if (threadIdx.x == 0) {
+      if (use_prior) prior_accumulate(load_pose(tr.cand), &s_prior, sh.red);
+      if (s_degen.n_held > 0) {              // 0 < n_held < 6 here: the all-held solve never enters the loop
+        degen_rotate(s_degen, sh.red);
+        const int accepted = tr.successful;
+        int cont = tr_decide(tr, sh.red, prm);
+        // tr_decide took the gradient max norm of an accepted step in the pose tangent; the reduced problem's replaces it
+        if (cont && tr.successful != accepted) tr.gmax = degen_gradient_max_norm(s_degen, tr.x, tr.sys + 1, prm.gtol);
+        sh.go = cont ? tr_propose_degen(tr, prm, s_degen) : 0;
+      } else {
+        sh.go = tr_decide(tr, sh.red, prm) ? tr_propose(tr, prm) : 0;
+      }
+    }
+#elif defined(MSFL_LM_PROFILE)
     if (threadIdx.x == 0) {
       const unsigned long long c0 = wall_clock64();
       const int cont = tr_decide(tr, sh.red, prm);
