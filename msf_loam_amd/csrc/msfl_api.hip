@@ -445,7 +445,8 @@ __global__ void __launch_bounds__(256) zero_ints_kernel(int* __restrict__ p, int
 // Build the exact-kNN grid over `pts` (device pointer, n points).  Fully asynchronous: the grid
 // descriptor is computed and kept on the device; the dense cell table has a fixed capacity
 // (default 4 M cells, MSFL_GRID_CAP_CELLS) and the device grows the cell edge if the map's bounding
-// box would need more (larger cells stay exact).
+// box would need more, or more than kGridMaxDim cells along one axis (larger cells stay exact: tested
+// to 12 km extents, docs/kernels/scan2map.md "Index geometry").
 msfl_status build_index(msfl_handle* h, const float4* pts, int n, MapIndex& mi, const int* n_dev = nullptr) {
   ScopedTimer timer(h, T_INDEX);
   // the 5-NN walk addresses candidates by 32-bit byte offsets into the sorted copy (knn5_grid_k32)

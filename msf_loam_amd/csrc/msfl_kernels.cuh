@@ -117,9 +117,24 @@ __device__ __forceinline__ void grid_desc_squares(GridDesc& g) {
   const float cell = 1.0f / g.inv_cell, cellx = 1.0f / g.inv_cell_x;
   g.cell2 = cell * cell; g.cellx2 = cellx * cellx;
 }
+// Most cells along one axis (x: sub-cells).  The walk's two margins are ABSOLUTE, in cells: the cell edge exceeds the radius by
+// 0.1 % (two points inside the gate are at most 0.999001 cells apart, so the reach of one cell, kGridXSub sub-cells, has 9.99e-4
+// cells to spare) and axis_gap shrinks every lower bound by 1e-3 cell.  The rounding error of u = fl(fl(v - o) * inv) is
+// RELATIVE: fl(v - o) is off by at most half an ulp, <= 2^-24 |v - o|, which the product scales to <= 2^-24 |u| cells, and the
+// product's own rounding adds <= 2^-24 |u|.  The difference of two computed coordinates near |u| (a query and a map point; a
+// lower bound measures the query against an integer that the point's computed coordinate does not pass) is therefore within
+// 4 * 2^-24 |u| = 2^-22 |u| cells of the true one.  A query that matters lies within one cell of the box, so |u| <= dim + 1, and
+//   2^-22 * (4096 + 1) = 9.768e-4 < 9.99e-4 < 1e-3
+// (the error reaches 1e-3 at |u| = 4194).  The f32 rounding of inv itself is a common scale factor (6e-8 of a difference of at
+// most kGridXSub cells) and the bounds' own arithmetic is relative 2^-23 or so of bounds below 2 cells: both far inside the
+// 2.2e-5 cells left.  Beyond the limit the skipped-row and trimmed-cell tests DO lose true neighbours (tests/test_knn_grid_model.py
+// finds them from |u| ~ 12 000 in y and ~ 18 000 in x), so such a box gets larger cells, like one that exceeds the table.
+constexpr int kGridMaxDim = 4096;
+
 // bbox -> grid descriptor, entirely on the device so that msfl_set_map needs no host round trip.
-// Cell edge = 1.001 * acceptance radius, grown by 26 % steps until the dense table fits `cap_cells`
-// (larger cells stay exact).  An empty cloud yields n_cells = 1, n_pts = 0.
+// Cell edge = 1.001 * acceptance radius, grown by 26 % steps until the dense table fits `cap_cells` and no axis has more than
+// kGridMaxDim cells (larger cells stay exact: tested to 12 km extents, docs/kernels/scan2map.md "Index geometry").  A box
+// within both limits at the base edge keeps the descriptor it always had.  An empty cloud yields n_cells = 1, n_pts = 0.
 __device__ __forceinline__ GridDesc grid_desc_from_bbox(const int* __restrict__ bbox, double radius, int cap_cells) {
   GridDesc g;
   const int b0 = bbox[0];
@@ -144,7 +159,7 @@ __device__ __forceinline__ GridDesc grid_desc_from_bbox(const int* __restrict__ 
       total *= dims[a];
     }
     if (first) { g.want_cells = total < 2.0e9 ? (int)total : 2000000000; first = false; }
-    if (total <= (double)cap_cells) break;
+    if (total <= (double)cap_cells && max(dims[0], max(dims[1], dims[2])) <= kGridMaxDim) break;
     cell *= 1.26;
   }
   g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
