@@ -31,6 +31,8 @@
 //   msfl::adapter::SetPosePrior(h, &prior_record, predicted_pose, sqrt_information)  before MatchScan2Map;  ClearPosePrior(h) after
 // and, for the degenerate geometry the reference steps through ("lidar trajectory will drift in illed situation", :84):
 //   msfl::adapter::SetDegeneracy(h, &degeneracy_record, min_eigenvalue)  once;  ClearDegeneracy(h) to switch it off
+// and, for a health figure of a registration or the verification of a candidate pose against the map of the last MatchScan2Map:
+//   msfl::adapter::ScorePoses(h, scan_curr, poses, max_dist) -> std::vector<PoseScore> (Fitness(n_features), Rmse())
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -223,6 +225,35 @@ inline bool MatchScan2Map(msfl_handle* h, const StampedT& cloud_map, const Stamp
   Check(st, h, "msfl_match_scan2map");
   *pose_estimate_map_scan2world = RigidFromArray<RigidT>(v);               // :271 / :268 (velocity unchanged: its block is constant, :94)
   return true;
+}
+
+// ---- fitness of a scan at candidate poses against the map the handle holds (msfl_score_poses; not in the reference, whose only
+// health figures are the solver's own).  Call it after MatchScan2Map (the map of that call is still resident) with the returned
+// pose to grade the registration, or with a candidate pose (a loop closure, a GPS fix) before accepting it.  Only
+// cloud_corner_less_sharp and cloud_surf_less_flat of `scan` are read; `poses` is any container of rigids (size(), operator[]).
+struct PoseScore : msfl_pose_score {
+  // inlier fraction over n_features = corner + surf features of the scan
+  double Fitness(std::size_t n_features) const {
+    return n_features ? (static_cast<double>(inliers[0]) + static_cast<double>(inliers[1])) / static_cast<double>(n_features) : 0.0;
+  }
+  // root mean squared inlier distance in metres (NaN without inliers)
+  double Rmse() const {
+    const double n = static_cast<double>(inliers[0]) + static_cast<double>(inliers[1]);
+    const double sum = (static_cast<double>(sum_sq_q32[0]) + static_cast<double>(sum_sq_q32[1])) / 4294967296.0;
+    return n > 0 ? std::sqrt(sum / n) : std::nan("");
+  }
+};
+template <class StampedT, class RigidVecT>
+inline std::vector<PoseScore> ScorePoses(msfl_handle* h, const StampedT& scan, const RigidVecT& poses, double max_dist) {
+  const std::vector<msfl_point> c = Pack(*scan.cloud_corner_less_sharp);
+  const std::vector<msfl_point> s = Pack(*scan.cloud_surf_less_flat);
+  std::vector<double> v(7 * poses.size());
+  for (std::size_t i = 0; i < poses.size(); ++i) RigidToArray(poses[i], v.data() + 7 * i);
+  std::vector<PoseScore> out(poses.size());
+  static_assert(sizeof(PoseScore) == sizeof(msfl_pose_score), "PoseScore adds no member");
+  Check(msfl_score_poses(h, c.data(), static_cast<int>(c.size()), s.data(), static_cast<int>(s.size()), v.data(), static_cast<int>(poses.size()),
+                         max_dist, out.data(), nullptr, nullptr, MSFL_MEM_HOST), h, "msfl_score_poses");
+  return out;
 }
 
 // ---- HybridGrid::GetSurroundedCloud / InsertScan (hybrid_grid.cc:462-534; callers laser_mapping.cc:273-278,330-338) on a

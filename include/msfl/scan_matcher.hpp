@@ -186,6 +186,7 @@ inline Matrix6d SqrtInformationFromCovariance(const Matrix6d& covariance) {
   return out;
 }
 
+using adapter::PoseScore;                 // msfl_pose_score + Fitness(n_features), Rmse()
 using adapter::CovarianceInParentFrame;   // (pose, last_uncertainty(), scale, double out[36]) -> PoseWithCovariance::covariance
 
 class OdometryScanMatcher : public ScanMatcher {
@@ -279,6 +280,14 @@ class MappingScanMatcher : public ScanMatcher {
     imu_presolve_(prev_state, pose_estimate_map_scan2world, velocity);  // .cc:58-59
     unc_ = msfl_match_uncertainty{};
     return adapter::MatchScan2Map(h_, cloud_map, scan_curr, true, preintegration, gravity_vector, pose_estimate_map_scan2world, velocity, &info_);
+  }
+
+  // Not in the reference: how well `scan` fits the map of the last MatchScan2Map at each of `poses` (msfl_score_poses): per pose the
+  // features with a map point of their kind within max_dist (<= 1 m with the default parameters) and the sum of their squared
+  // distances.  Independent of the solver and comparable between poses: grade the returned pose, or verify a candidate before use.
+  template <class StampedT, class RigidVecT>
+  std::vector<PoseScore> ScorePoses(const StampedT& scan, const RigidVecT& poses, double max_dist) {
+    return adapter::ScorePoses(h_, scan, poses, max_dist);
   }
 
  private:

@@ -308,6 +308,53 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
                                    const msfl_point* surf, const int* surf_off,
                                    double* poses_io, int* status, msfl_match_info* info, msfl_mem mem);
 
+/* Fitness of a scan at given poses against the resident map, independent of any solve (the role of PCL's
+   getFitnessScore): for every pose and every feature, the nearest map point OF THE FEATURE'S KIND (corner features
+   query the corner map, surf features the surf map) within max_dist of the transformed feature, exactly: f32 transform
+   and f32 squared distance as in the matcher, ties resolved to the lowest original map index.  A feature is an inlier
+   when that squared distance d2 satisfies d2 <= (float)(max_dist * max_dist).  Sums are kept in fixed point, so a record
+   is bit-reproducible whatever the call's shape: use it to grade a registration, to verify a candidate pose (a loop
+   closure, a GPS fix, a result of msfl_match_pairs_batch) or to rank many hypotheses for one scan. */
+typedef struct msfl_pose_score {
+  int inliers[2];                     /* corner, surf features with a map point of their kind within max_dist */
+  unsigned long long sum_sq_q32[2];   /* sum over those of rint(d2 * 2^32): squared metres in units of 2^-32 */
+  int status;                         /* 0, or MSFL_BAD_ARG for a pose with a non-finite entry (record otherwise zero) */
+  int reserved_;
+} msfl_pose_score;
+
+/* Scores one scan at n_poses poses (msfl_score_poses) or scan b of n_scans at the poses [pose_off[b], pose_off[b+1])
+   (msfl_score_poses_batch; scores[i] belongs to poses[7*i .. 7*i+6]).
+     corner/surf (+ offsets) : the scan's feature clouds as in msfl_match_scan2map(_batch), scan frame.
+     poses                   : 7 doubles each (t, q xyzw), scan -> map.
+     d2_out, nn_out          : optional (NULL: not wanted), n_poses x (n_corner + n_surf) values, row h = pose h, corner
+                               features first: the squared distance and the ORIGINAL index (position in the cloud given to
+                               msfl_set_map) of the nearest map point; +inf and -1 when none lies within max_dist, or when
+                               the feature or its transformed point is not finite.
+   Rules:
+     - MSFL_NO_MAP without a resident single map, which includes the state after msfl_match_pairs_batch.
+     - MSFL_BAD_ARG unless 0 < max_dist, max_dist^2 <= params.map_knn_max_sq_dist (the index is only exact up to the radius
+       it was built for) and max_dist^2 <= 64 (the sum of any scan of fewer than 2^24 features then stays below 2^63); a NaN
+       max_dist is MSFL_BAD_ARG.  A scan of 2^24 features or more is MSFL_CAPACITY.
+     - Offset arrays are HOST arrays (n_scans + 1 prefix offsets each), like in every batch call.
+     - With MSFL_MEM_DEVICE the clouds, poses, scores and d2_out / nn_out are device pointers and the call is asynchronous
+       on the handle's stream, ordered after a preceding asynchronous msfl_set_map.
+     - A map side without points gives zero inliers of that kind, not an error (no MSFL_MAP_TOO_SMALL here).
+     - A pose with a non-finite entry gets status MSFL_BAD_ARG and an otherwise zero record (its d2_out / nn_out rows are
+       +inf / -1); the call still returns MSFL_OK and the other poses are unaffected.
+     - Any number of poses: more than fit one launch are served by several.
+     - The call uses scratch of its own and never touches poses, records, neighbour lists or the index: a matcher call
+       after it is bit-identical to one without it. */
+msfl_status msfl_score_poses(msfl_handle* h,
+                             const msfl_point* corner, int n_corner,
+                             const msfl_point* surf, int n_surf,
+                             const double* poses, int n_poses, double max_dist,
+                             msfl_pose_score* scores, float* d2_out, int* nn_out, msfl_mem mem);
+msfl_status msfl_score_poses_batch(msfl_handle* h, int n_scans,
+                                   const msfl_point* corner, const int* corner_off,
+                                   const msfl_point* surf, const int* surf_off,
+                                   const double* poses, const int* pose_off,
+                                   double max_dist, msfl_pose_score* scores, msfl_mem mem);
+
 /* Kernel-level entry points (the two halves of one outer iteration), exposed so that parity tests
    can pin the data association and the solver separately:
      msfl_associate_scan2map : mapping_scan_matcher.cc:109-246 at a fixed pose.  records_out gets

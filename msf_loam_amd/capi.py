@@ -33,6 +33,7 @@ EXPORTED = [
     "msfl_set_uncertainty", "msfl_slam_set_uncertainty", "msfl_slam_get_uncertainty",
     "msfl_set_pose_prior", "msfl_slam_set_next_prior",
     "msfl_set_degeneracy", "msfl_slam_set_degeneracy", "msfl_slam_get_degeneracy",
+    "msfl_score_poses", "msfl_score_poses_batch",
 ]
 
 
@@ -99,6 +100,35 @@ class DegeneracyRecord(C.Structure):
 DEGENERACY_DTYPE = np.dtype([("eigenvalues", np.float64, (2, 6)), ("eigenvectors", np.float64, (2, 6, 6)), ("n_held", np.int32, (2,)),
                              ("valid", np.int32, (2,))])
 assert DEGENERACY_DTYPE.itemsize == C.sizeof(DegeneracyRecord) == 688
+
+
+class PoseScore(C.Structure):
+    """msfl_pose_score: per feature kind (corner, surf) the inliers of one pose and the fixed-point sum of their squared distances."""
+    _fields_ = [("inliers", C.c_int * 2), ("sum_sq_q32", C.c_ulonglong * 2), ("status", C.c_int), ("reserved_", C.c_int)]
+
+
+# the same record as a numpy structured dtype (Handle.score_poses, Handle.score_poses_batch)
+POSE_SCORE_DTYPE = np.dtype([("inliers", np.int32, (2,)), ("sum_sq_q32", np.uint64, (2,)), ("status", np.int32), ("reserved_", np.int32)])
+assert POSE_SCORE_DTYPE.itemsize == C.sizeof(PoseScore) == 32
+
+
+def fitness(scores, n_corner, n_surf):
+    """Inlier fraction of each record: (corner + surf inliers) / (n_corner + n_surf); n_corner / n_surf may be per-record arrays.
+    A scan without features has fitness 0."""
+    n = np.asarray(n_corner, np.float64) + np.asarray(n_surf, np.float64)
+    inl = scores["inliers"].sum(-1).astype(np.float64)
+    return np.divide(inl, n, out=np.zeros(np.broadcast(inl, n).shape), where=n > 0)
+
+
+def rmse(scores):
+    """Root mean squared inlier distance of each record in metres: sqrt(sum_sq_q32 / 2^32 / inliers); NaN without inliers."""
+    inl = scores["inliers"].sum(-1).astype(np.float64)
+    tot = scores["sum_sq_q32"].astype(np.float64).sum(-1) / 4294967296.0     # (each sum is below 2^63; the float64 rounding is 2^-53 relative)
+    return np.sqrt(np.divide(tot, inl, out=np.full(np.shape(inl), np.nan), where=inl > 0))
+
+
+def _on_device(x):
+    return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
 
 
 def pose_priors(poses, sqrt_info):
@@ -602,6 +632,86 @@ class Handle:
         self._check(self.lib.msfl_match_pairs_batch(self.h, C.c_int(P), _vp(d_map_corner), _vp(offs[0]), _vp(d_map_surf), _vp(offs[1]), _vp(d_corner),
                                                     _vp(offs[2]), _vp(d_surf), _vp(offs[3]), _vp(d_poses), _vp(d_status), None, C.c_int(MEM_DEVICE)),
                     "msfl_match_pairs_batch(device)")
+
+    # ---- pose scoring (msfl_score_poses) ----
+    def score_poses_device(self, corner, n_corner, surf, n_surf, poses, n_poses, max_dist, scores, d2_out=None, nn_out=None):
+        """Device-pointer form (torch tensors / raw pointers), asynchronous on the handle's stream: `scores` holds n_poses records of
+        POSE_SCORE_DTYPE.itemsize bytes, d2_out / nn_out (optional) n_poses x (n_corner + n_surf) float32 / int32."""
+        self._check(self.lib.msfl_score_poses(self.h, _vp(corner), C.c_int(int(n_corner)), _vp(surf), C.c_int(int(n_surf)), _vp(poses),
+                                              C.c_int(int(n_poses)), C.c_double(float(max_dist)), _vp(scores), _vp(d2_out), _vp(nn_out),
+                                              C.c_int(MEM_DEVICE)), "msfl_score_poses(device)")
+
+    def score_poses_batch_device(self, n_scans, corner, corner_off, surf, surf_off, poses, pose_off, max_dist, scores):
+        """Device-pointer batch form, asynchronous; the three offset arrays are host arrays."""
+        offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off, pose_off)]
+        self._check(self.lib.msfl_score_poses_batch(self.h, C.c_int(int(n_scans)), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses),
+                                                    _vp(offs[2]), C.c_double(float(max_dist)), _vp(scores), C.c_int(MEM_DEVICE)),
+                    "msfl_score_poses_batch(device)")
+
+    def _device_scores(self, like, n):
+        import torch
+        return torch.empty(max(int(n), 1) * POSE_SCORE_DTYPE.itemsize, dtype=torch.uint8, device=like.device)
+
+    @staticmethod
+    def _device_inputs(corner, surf, poses):
+        import torch
+        if not (_on_device(corner) and _on_device(surf) and _on_device(poses)):
+            raise TypeError("score_poses: clouds and poses must all be device tensors, or none of them")
+        if corner.dtype != torch.float32 or surf.dtype != torch.float32 or poses.dtype != torch.float64:
+            raise TypeError("score_poses: device clouds are float32, device poses float64")
+        return corner.contiguous(), surf.contiguous(), poses.contiguous()
+
+    @staticmethod
+    def _scores_to_host(buf, n):
+        return buf.cpu().numpy().view(POSE_SCORE_DTYPE)[:int(n)].copy()
+
+    def score_poses(self, corner, surf, poses, max_dist, want_nn=False):
+        """Fitness of one scan at each of `poses` (P, 7) against the resident map: P records of POSE_SCORE_DTYPE (see fitness() and
+        rmse()).  want_nn: also (d2, nn), each (P, n_corner + n_surf), corner features first: squared distance and original map index
+        of every feature's nearest map point of its kind (+inf / -1 without one within max_dist).  numpy arrays go through host
+        memory; torch device tensors (float32 (n, 4) clouds, float64 poses) through the device form on the handle's stream."""
+        if _on_device(corner) or _on_device(surf) or _on_device(poses):
+            import torch
+            corner, surf, poses = self._device_inputs(corner, surf, poses)
+            nc, ns, P = corner.numel() // 4, surf.numel() // 4, poses.numel() // 7
+            buf = self._device_scores(poses, P)
+            d2 = torch.empty((P, nc + ns), dtype=torch.float32, device=poses.device) if want_nn else None
+            nn = torch.empty((P, nc + ns), dtype=torch.int32, device=poses.device) if want_nn else None
+            self.score_poses_device(corner, nc, surf, ns, poses, P, max_dist, buf, d2, nn)
+            self.synchronize()
+            rec = self._scores_to_host(buf, P)
+            return (rec, d2.cpu().numpy(), nn.cpu().numpy()) if want_nn else rec
+        corner, surf = _pts(corner), _pts(surf)
+        poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
+        P, F = len(poses), len(corner) + len(surf)
+        rec = np.zeros(P, POSE_SCORE_DTYPE)
+        d2 = np.zeros((P, F), np.float32) if want_nn else None
+        nn = np.zeros((P, F), np.int32) if want_nn else None
+        self._check(self.lib.msfl_score_poses(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)), _vp(poses), C.c_int(P),
+                                              C.c_double(float(max_dist)), _vp(rec), _vp(d2), _vp(nn), C.c_int(MEM_HOST)), "msfl_score_poses")
+        return (rec, d2, nn) if want_nn else rec
+
+    def score_poses_batch(self, corner, corner_off, surf, surf_off, poses, pose_off, max_dist):
+        """Scan b (features [corner_off[b], corner_off[b+1]) / surf likewise) at the poses [pose_off[b], pose_off[b+1]): one record of
+        POSE_SCORE_DTYPE per pose.  Offsets are host arrays; clouds and poses numpy arrays or, all three, torch device tensors."""
+        offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off, pose_off)]
+        B = len(offs[0]) - 1
+        if _on_device(corner) or _on_device(surf) or _on_device(poses):
+            corner, surf, poses = self._device_inputs(corner, surf, poses)
+            P = poses.numel() // 7
+            buf = self._device_scores(poses, P)
+            self.score_poses_batch_device(B, corner, offs[0], surf, offs[1], poses, offs[2], max_dist, buf)
+            self.synchronize()
+            rec = np.zeros(P, POSE_SCORE_DTYPE)                     # poses outside [pose_off[0], pose_off[B]) keep zero records
+            p0, p1 = (int(offs[2][0]), int(offs[2][-1])) if B > 0 else (0, 0)
+            rec[p0:p1] = self._scores_to_host(buf, P)[p0:p1]
+            return rec
+        corner, surf = _pts(corner), _pts(surf)
+        poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
+        rec = np.zeros(len(poses), POSE_SCORE_DTYPE)
+        self._check(self.lib.msfl_score_poses_batch(self.h, C.c_int(B), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]),
+                                                    C.c_double(float(max_dist)), _vp(rec), C.c_int(MEM_HOST)), "msfl_score_poses_batch")
+        return rec
 
     def transform_cloud(self, pts, pose7):
         """TransformPointCloud (laser_mapping.cc:24-31)."""

@@ -182,6 +182,7 @@ struct msfl_handle_s {
   DevBuf vb2[6];  // second scratch set of the pair form: staging, run sums, counts/flags/offsets, offsets
   DevBuf pp[5];   // per-point passes: pre-integration samples, staged points, dq, dp, flag
   DevBuf pr[5];   // batched (map, scan) pairs: map offsets and cell-table bases per cloud kind, preset status
+  DevBuf sc[8];   // msfl_score_poses*: staged clouds and poses, offset table, records, per-feature outputs, scan of each hypothesis (no other call touches them)
 
   // msfl_set_uncertainty: where every matcher call writes one msfl_match_uncertainty per registration (null: feature off)
   msfl_match_uncertainty* unc_out = nullptr;
@@ -1165,6 +1166,7 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
 #include "msfl_api_deskew.inc"
 #include "msfl_api_slam.inc"
 #include "msfl_api_pairs.inc"
+#include "msfl_api_score.inc"
 
 namespace {
 
