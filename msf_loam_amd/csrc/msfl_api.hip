@@ -124,10 +124,10 @@ struct PinBuf {
 
 struct MapIndex {
   DevBuf gdesc;        // GridDesc, computed on the device (no host round trip in msfl_set_map)
-  DevBuf bbox;         // 6 ordered ints, armed once and re-armed by grid_scatter_kernel (grid_setup_kernel for an empty cloud)
+  DevBuf bbox;         // 6 ordered ints, armed once and re-armed by every build's last launch (grid_build_done)
   int cap_cells = 0;   // capacity of cell_start / count (cells)
-  // feedback for the table span of the next build (asynchronous read-back, never waited for)
-  int* want_host = nullptr; hipEvent_t want_ev = nullptr; bool want_pending = false; int span = 0;
+  PinBuf want;         // one int the build's last launch writes: the table size the bounding box wanted, feedback for the span of the
+  int span = 0;        // NEXT build's table (read whenever the next build starts, never waited for)
   DevBuf sorted;      // float4[n]
   DevBuf pos_of;      // int[n]: original index -> position in `sorted`
   DevBuf cell_start;  // int[n_cells + 1]
@@ -443,53 +443,50 @@ __global__ void __launch_bounds__(256) zero_ints_kernel(int* __restrict__ p, int
   if (i < n) p[i] = 0;
 }
 
-// Build the exact-kNN grid over `pts` (device pointer, n points).  Fully asynchronous: the grid
-// descriptor is computed and kept on the device; the dense cell table has a fixed capacity
-// (default 4 M cells, MSFL_GRID_CAP_CELLS) and the device grows the cell edge if the map's bounding
-// box would need more, or more than kGridMaxDim cells along one axis (larger cells stay exact: tested
-// to 12 km extents, docs/kernels/scan2map.md "Index geometry").
-msfl_status build_index(msfl_handle* h, const float4* pts, int n, MapIndex& mi, const int* n_dev = nullptr) {
-  ScopedTimer timer(h, T_INDEX);
+// What every index build does on the host before its launches: the size check, the span of the dense cell table, the buffers
+// that belong to the map, the bbox armed.  The span is what the previous build of this map said it needs (+25 %), else 1 M
+// cells (MSFL_GRID_CAP_CELLS bounds it).  The device grows the cell edge when the bounding box needs more than the span, or
+// more than kGridMaxDim cells along one axis (larger cells stay exact, just more candidates per cell: tested to 12 km extents,
+// docs/kernels/scan2map.md "Index geometry"), and reports the wanted size for the next build.
+msfl_status index_prepare(msfl_handle* h, MapIndex& mi, int n) {
   // the 5-NN walk addresses candidates by 32-bit byte offsets into the sorted copy (knn5_grid_k32)
   if (n >= (1 << 28)) return fail(h, MSFL_BAD_ARG, "map cloud of 2^28 points or more (the index addresses 16-byte points by 32-bit byte offsets)");
   mi.n_input = n;
-  hipStream_t st = h->stream;
-  // span of the dense cell table: what the previous build of this map said it needs (+25 %), else 1 M
-  // cells.  The device grows the cell edge when the bounding box needs more than `cap` (still exact,
-  // just more candidates per cell), and reports the wanted size for the next build.
-  if (!mi.want_host) {
-    HIPCHK(h, hipHostMalloc((void**)&mi.want_host, sizeof(int), hipHostMallocDefault));
-    HIPCHK(h, hipEventCreateWithFlags(&mi.want_ev, hipEventDisableTiming));
-    *mi.want_host = 0;
-  }
-  if (mi.want_pending && hipEventQuery(mi.want_ev) == hipSuccess) {
-    mi.want_pending = false;
-    const long long w = (long long)(*mi.want_host) + (*mi.want_host) / 4 + 1024;
-    mi.span = (int)std::min<long long>(std::max<long long>(w, 65536), h->grid_cap_cells);
-  }
+  if (!mi.want.p) { HIPCHK(h, mi.want.reserve(sizeof(int))); *mi.want.as<int>() = 0; }
+  const int seen = *(volatile int*)mi.want.as<int>();
+  if (seen > 0) mi.span = (int)std::min<long long>(std::max<long long>((long long)seen + seen / 4 + 1024, 65536), h->grid_cap_cells);
   if (mi.span <= 0) mi.span = std::min(1 << 20, h->grid_cap_cells);
-  const int cap = mi.span;
+  mi.cap_cells = mi.span;
   HIPCHK(h, mi.gdesc.reserve(sizeof(GridDesc)));
+  HIPCHK(h, mi.cell_start.reserve(((size_t)mi.span + 1) * sizeof(int)));
+  HIPCHK(h, mi.sorted.reserve(std::max<size_t>(1, (size_t)n) * sizeof(float4)));
+  HIPCHK(h, mi.pos_of.reserve(std::max<size_t>(1, (size_t)n) * sizeof(int)));
+  if (!mi.bbox.p) {                       // armed once; every build re-arms it after the last read
+    HIPCHK(h, mi.bbox.reserve(6 * sizeof(int)));
+    const int init[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
+    HIPCHK(h, h->pin.upload(mi.bbox.p, init, sizeof(init), h->stream));
+  }
+  return MSFL_OK;
+}
+
+// Build the exact-kNN grid over `pts` (device pointer, n points; n_dev: the SLAM step's device-side count, n is then its bound).
+// Fully asynchronous: the grid descriptor is computed and kept on the device.
+msfl_status build_index(msfl_handle* h, const float4* pts, int n, MapIndex& mi, const int* n_dev = nullptr) {
+  ScopedTimer timer(h, T_INDEX);
+  msfl_status ps = index_prepare(h, mi, n); if (ps) return ps;
+  hipStream_t st = h->stream;
+  const int cap = mi.span;
   HIPCHK(h, h->idx_cell_of.reserve(std::max<size_t>(1, (size_t)n) * sizeof(int)));
   const void* count_before = h->idx_count.p;
   HIPCHK(h, h->idx_count.reserve(((size_t)cap + 1) * sizeof(int)));
   if (h->idx_count.p != count_before) h->idx_count_zero = 0;
-  HIPCHK(h, mi.cell_start.reserve(((size_t)cap + 1) * sizeof(int)));
-  HIPCHK(h, mi.sorted.reserve(std::max<size_t>(1, (size_t)n) * sizeof(float4)));
-  HIPCHK(h, mi.pos_of.reserve(std::max<size_t>(1, (size_t)n) * sizeof(int)));
-  mi.cap_cells = cap;
-  if (!mi.bbox.p) {                       // armed once; the build re-arms it after the last read
-    HIPCHK(h, mi.bbox.reserve(6 * sizeof(int)));
-    const int init[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
-    HIPCHK(h, h->pin.upload(mi.bbox.p, init, sizeof(init), st));
-  }
   if (n > 0) {
     const int blocks = std::min(div_up(n, 1024), 256);   // 6 atomics per workgroup, all on one line: four points per lane and pass
     hipLaunchKernelGGL(grid_bbox_kernel, dim3(blocks), dim3(256), 0, st, pts, n, mi.bbox.as<int>(), n_dev);
   }
   const double radius = std::sqrt((double)h->prm.map_knn_max_sq_dist);
   if (n == 0)
-    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(1), 0, st, mi.bbox.as<int>(), radius, cap, mi.gdesc.as<GridDesc>());
+    hipLaunchKernelGGL(grid_setup_kernel, dim3(1), dim3(1), 0, st, mi.bbox.as<int>(), radius, cap, mi.gdesc.as<GridDesc>(), mi.want.as<int>());
   // the table is cleared / scanned over the cells actually used last time (+ margin) when known,
   // else over the full capacity; the device never indexes beyond n_cells <= cap.
   const size_t span = (size_t)cap + 1;
@@ -508,25 +505,16 @@ msfl_status build_index(msfl_handle* h, const float4* pts, int n, MapIndex& mi, 
   if (n > 0)
     hipLaunchKernelGGL(grid_scatter_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, pts, n, h->idx_cell_of.as<int>(),
                        mi.cell_start.as<int>(), h->idx_count.as<int>(), mi.sorted.as<float4>(), mi.pos_of.as<int>(),
-                       mi.gdesc.as<GridDesc>(), mi.bbox.as<int>(), n_dev);
+                       mi.gdesc.as<GridDesc>(), mi.bbox.as<int>(), mi.want.as<int>(), n_dev);
   HIPCHK(h, hipGetLastError());
   h->idx_count_zero = std::max(zeroed, span);
-  if (!mi.want_pending) {
-    HIPCHK(h, hipMemcpyAsync(mi.want_host, &mi.gdesc.as<GridDesc>()->want_cells, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipEventRecord(mi.want_ev, st));
-    mi.want_pending = true;
-  }
   return MSFL_OK;
 }
 
-// Both maps of msfl_set_map through one chain of five launches (msfl_kernels.cuh: GridPairJob).  Same results as two build_index calls;
+// Both maps of msfl_set_map through one chain of five launches (msfl_knn_index.cuh: GridPairJob).  Same results as two build_index calls;
 // used when both clouds are non-empty and their sizes are host-side numbers (the per-scan SLAM step builds its maps on streams of their own).
-// The wanted table size comes back through a pinned host word the scatter launch writes (no copy, no event): it is a hint for the NEXT
-// build's table span, so whichever value the host happens to see -- the previous build's or this one's -- is fine.
 msfl_status build_index_pair(msfl_handle* h, const float4* pts_c, int n_c, const float4* pts_s, int n_s) {
   ScopedTimer timer(h, T_INDEX);
-  if ((long long)n_c >= (1 << 28) || (long long)n_s >= (1 << 28))
-    return fail(h, MSFL_BAD_ARG, "map cloud of 2^28 points or more (the index addresses 16-byte points by 32-bit byte offsets)");
   hipStream_t st = h->stream;
   MapIndex* mi[2] = {&h->map_c, &h->map_s};
   const float4* pts[2] = {pts_c, pts_s};
@@ -534,32 +522,10 @@ msfl_status build_index_pair(msfl_handle* h, const float4* pts_c, int n_c, const
   GridPairJob j;
   for (int m = 0; m < 2; m++) {
     MapIndex& x = *mi[m];
-    x.n_input = n[m];
-    if (!x.want_host) {
-      HIPCHK(h, hipHostMalloc((void**)&x.want_host, sizeof(int), hipHostMallocDefault));
-      HIPCHK(h, hipEventCreateWithFlags(&x.want_ev, hipEventDisableTiming));
-      *x.want_host = 0;
-    }
-    if (x.want_pending) { HIPCHK(h, hipEventSynchronize(x.want_ev)); x.want_pending = false; }   // a read-back copy of an earlier single build
-    const int seen = *(volatile int*)x.want_host;
-    if (seen > 0) {
-      const long long w = (long long)seen + seen / 4 + 1024;
-      x.span = (int)std::min<long long>(std::max<long long>(w, 65536), h->grid_cap_cells);
-    }
-    if (x.span <= 0) x.span = std::min(1 << 20, h->grid_cap_cells);
-    x.cap_cells = x.span;
-    HIPCHK(h, x.gdesc.reserve(sizeof(GridDesc)));
-    HIPCHK(h, x.cell_start.reserve(((size_t)x.span + 1) * sizeof(int)));
-    HIPCHK(h, x.sorted.reserve((size_t)n[m] * sizeof(float4)));
-    HIPCHK(h, x.pos_of.reserve((size_t)n[m] * sizeof(int)));
-    if (!x.bbox.p) {                       // armed once; every build re-arms it after the last read
-      HIPCHK(h, x.bbox.reserve(6 * sizeof(int)));
-      const int init[6] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN, INT32_MIN};
-      HIPCHK(h, h->pin.upload(x.bbox.p, init, sizeof(init), st));
-    }
+    msfl_status ps = index_prepare(h, x, n[m]); if (ps) return ps;
     j.pts[m] = pts[m]; j.n[m] = n[m]; j.bbox[m] = x.bbox.as<int>(); j.gdesc[m] = x.gdesc.as<GridDesc>(); j.cap[m] = x.span;
     j.cell_start[m] = x.cell_start.as<int>(); j.sorted[m] = x.sorted.as<float4>(); j.pos_of[m] = x.pos_of.as<int>();
-    j.want_host[m] = x.want_host;
+    j.want_host[m] = x.want.as<int>();
   }
   const size_t span = (size_t)j.cap[0] + 1 + (size_t)j.cap[1] + 1;
   HIPCHK(h, h->idx_cell_of.reserve(((size_t)n_c + (size_t)n_s) * sizeof(int)));
@@ -797,11 +763,6 @@ void msfl_destroy(msfl_handle* h) {
   collect_timing(h);
   for (auto e : h->free_events) (void)hipEventDestroy(e);
   if (h->copy_stream) { (void)hipStreamDestroy(h->copy_stream); for (auto e : h->copy_ev) if (e) (void)hipEventDestroy(e); }
-  for (MapIndex* mi : {&h->map_c, &h->map_s}) {
-    if (mi->want_pending) (void)hipEventSynchronize(mi->want_ev);
-    if (mi->want_ev) (void)hipEventDestroy(mi->want_ev);
-    if (mi->want_host) (void)hipHostFree(mi->want_host);
-  }
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;                               // every DevBuf / PinBuf member and the pinned ring free themselves
 }

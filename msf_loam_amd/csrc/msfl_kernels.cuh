@@ -1,7 +1,7 @@
 // msfl_kernels.cuh — HIP kernels of the scan-to-map registration path (gfx950 / CDNA4).
 //
-//   K3  map grid index      replaces pcl::KdTreeFLANN::setInputCloud   mapping_scan_matcher.cc:66-73
-//   K4  assoc_scan2map      replaces the two association loops         mapping_scan_matcher.cc:109-246
+//   K3  map grid index      replaces pcl::KdTreeFLANN::setInputCloud   mapping_scan_matcher.cc:66-73   (msfl_knn_index.cuh)
+//   K4 assoc_scan2map      replaces the two association loops         mapping_scan_matcher.cc:109-246
 //   K5+K6 lm_solve          replaces ceres::Solve (LM, Huber)          mapping_scan_matcher.cc:250-272
 //
 // Data layout in HBM:
@@ -17,603 +17,13 @@
 #include <stdint.h>
 
 #include "msfl_math.cuh"
+#include "msfl_knn_index.cuh"
 
 namespace msfl {
 
 // ---------------------------------------------------------------------------------------------
-// K3: uniform-grid index.  Cell edge >= 1.001 * sqrt(max_sq_dist) so the 27-cell neighbourhood
-// of a query contains every map point whose f32 distance can pass the reference's
-// `pointSearchSqDis[4] < 1.0` gate: exact-kNN-equivalent on every ACCEPTED query.
+// K4: association = transform + exact 5-NN (the walks of msfl_knn_index.cuh) + line / plane fit -> {C, N} record
 // ---------------------------------------------------------------------------------------------
-#ifndef MSFL_GRID_XSUB
-#define MSFL_GRID_XSUB 3
-#endif
-constexpr int kGridXSub = MSFL_GRID_XSUB;
-
-struct GridDesc {
-  float ox, oy, oz;   // origin = bbox min
-  float inv_cell;     // 1 / cell edge in y and z
-  float inv_cell_x;   // cells are kGridXSub times finer along x (the fastest index): a (y,z) row of 2*kGridXSub+1 cells
-                      // is still ONE contiguous range, but its ends can be trimmed in finer steps
-  int dx, dy, dz;
-  int n_pts;          // finite points indexed
-  int n_cells;
-  int reach;          // cells scanned on each side of the query cell (1)
-  int want_cells;     // cells the bbox needs at the base cell edge (saturated); host feedback for the next build
-  float cell2, cellx2;  // (1 / inv_cell)^2 and (1 / inv_cell_x)^2 in f32: every query needs them, computed once per build
-};
-
-// order-preserving float <-> int encoding for atomicMin/Max
-__device__ __forceinline__ int float_to_ordered(float f) {
-  const int i = __float_as_int(f);
-  return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__host__ __device__ __forceinline__ float ordered_to_float(int i) {
-  const int j = i >= 0 ? i : i ^ 0x7fffffff;
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __int_as_float(j);
-#else
-  float f; __builtin_memcpy(&f, &j, 4); return f;
-#endif
-}
-
-// bbox[0..2] = min (ordered ints), bbox[3..5] = max; pre-initialised to INT_MAX / INT_MIN
-// n_dev (optional): the number of valid points lives on the device (a surrounded cloud that never visits the host);
-// `n` is then the launch's upper bound
-__device__ __forceinline__ void grid_bbox_body(const float4* __restrict__ pts, int n, int* __restrict__ bbox, int block, int n_blocks) {
-  __shared__ float s_mn[4][3], s_mx[4][3];
-  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  auto take = [&](float4 p) {
-    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-      mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-      mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-    }
-  };
-  const int stride = n_blocks * blockDim.x;
-  int i = block * blockDim.x + threadIdx.x;
-  for (; i + 3 * stride < n; i += 4 * stride) {       // four independent loads in flight per lane
-    const float4 p0 = pts[i], p1 = pts[i + stride], p2 = pts[i + 2 * stride], p3 = pts[i + 3 * stride];
-    take(p0); take(p1); take(p2); take(p3);
-  }
-  for (; i < n; i += stride) take(pts[i]);
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_xor(mn[a], o));
-      mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o));
-    }
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) { s_mn[wave][a] = mn[a]; s_mx[wave][a] = mx[a]; }
-  }
-  __syncthreads();
-  // six lanes, one atomic each per workgroup (they all land on one cache line: keep them few)
-  if (threadIdx.x < 3) {
-    const int a = threadIdx.x;
-    const float v = fminf(fminf(s_mn[0][a], s_mn[1][a]), fminf(s_mn[2][a], s_mn[3][a]));
-    if (v != INFINITY) atomicMin(&bbox[a], float_to_ordered(v));
-  } else if (threadIdx.x < 6) {
-    const int a = threadIdx.x - 3;
-    const float v = fmaxf(fmaxf(s_mx[0][a], s_mx[1][a]), fmaxf(s_mx[2][a], s_mx[3][a]));
-    if (v != -INFINITY) atomicMax(&bbox[3 + a], float_to_ordered(v));
-  }
-}
-__global__ void __launch_bounds__(256) grid_bbox_kernel(const float4* __restrict__ pts, int n, int* __restrict__ bbox, const int* __restrict__ n_dev = nullptr) {
-  if (n_dev) n = min(n, max(*n_dev, 0));
-  grid_bbox_body(pts, n, bbox, (int)blockIdx.x, (int)gridDim.x);
-}
-
-__device__ __forceinline__ int grid_coord(float v, float o, float inv, int dim) {
-  // clamp in float first: far-away queries must not overflow the int conversion
-  float u = floorf((v - o) * inv);
-  u = fminf(fmaxf(u, -2.0f), (float)dim + 1.0f);
-  return (int)u;
-}
-
-__device__ __forceinline__ void grid_desc_squares(GridDesc& g) {
-  const float cell = 1.0f / g.inv_cell, cellx = 1.0f / g.inv_cell_x;
-  g.cell2 = cell * cell; g.cellx2 = cellx * cellx;
-}
-// Most cells along one axis (x: sub-cells).  The walk's two margins are ABSOLUTE, in cells: the cell edge exceeds the radius by
-// 0.1 % (two points inside the gate are at most 0.999001 cells apart, so the reach of one cell, kGridXSub sub-cells, has 9.99e-4
-// cells to spare) and axis_gap shrinks every lower bound by 1e-3 cell.  The rounding error of u = fl(fl(v - o) * inv) is
-// RELATIVE: fl(v - o) is off by at most half an ulp, <= 2^-24 |v - o|, which the product scales to <= 2^-24 |u| cells, and the
-// product's own rounding adds <= 2^-24 |u|.  The difference of two computed coordinates near |u| (a query and a map point; a
-// lower bound measures the query against an integer that the point's computed coordinate does not pass) is therefore within
-// 4 * 2^-24 |u| = 2^-22 |u| cells of the true one.  A query that matters lies within one cell of the box, so |u| <= dim + 1, and
-//   2^-22 * (4096 + 1) = 9.768e-4 < 9.99e-4 < 1e-3
-// (the error reaches 1e-3 at |u| = 4194).  The f32 rounding of inv itself is a common scale factor (6e-8 of a difference of at
-// most kGridXSub cells) and the bounds' own arithmetic is relative 2^-23 or so of bounds below 2 cells: both far inside the
-// 2.2e-5 cells left.  Beyond the limit the skipped-row and trimmed-cell tests DO lose true neighbours (tests/test_knn_grid_model.py
-// finds them from |u| ~ 12 000 in y and ~ 18 000 in x), so such a box gets larger cells, like one that exceeds the table.
-constexpr int kGridMaxDim = 4096;
-
-// bbox -> grid descriptor, entirely on the device so that msfl_set_map needs no host round trip.
-// Cell edge = 1.001 * acceptance radius, grown by 26 % steps until the dense table fits `cap_cells` and no axis has more than
-// kGridMaxDim cells (larger cells stay exact: tested to 12 km extents, docs/kernels/scan2map.md "Index geometry").  A box
-// within both limits at the base edge keeps the descriptor it always had.  An empty cloud yields n_cells = 1, n_pts = 0.
-__device__ __forceinline__ GridDesc grid_desc_from_bbox(const int* __restrict__ bbox, double radius, int cap_cells) {
-  GridDesc g;
-  const int b0 = bbox[0];
-  g.n_pts = 0; g.reach = 1;
-  if (b0 == 0x7fffffff) {            // no finite point
-    g.ox = g.oy = g.oz = 0.f; g.inv_cell = 1.f; g.inv_cell_x = (float)kGridXSub; g.dx = g.dy = g.dz = 1; g.n_cells = 1; g.want_cells = 1;
-    grid_desc_squares(g);
-    return g;
-  }
-  float mn[3], mx[3];
-  for (int a = 0; a < 3; a++) { mn[a] = ordered_to_float(bbox[a]); mx[a] = ordered_to_float(bbox[3 + a]); }
-  double cell = 1.001 * radius;
-  int dims[3];
-  bool first = true;
-  g.want_cells = 1;
-  for (;;) {
-    double total = 1.0;
-    for (int a = 0; a < 3; a++) {
-      const double edge = a == 0 ? cell / kGridXSub : cell;
-      dims[a] = (int)floor(((double)mx[a] - (double)mn[a]) / edge) + 2;   // +1 spare cell: f32 rounding of (v-o)*inv
-      if (dims[a] < 2) dims[a] = 2;
-      total *= dims[a];
-    }
-    if (first) { g.want_cells = total < 2.0e9 ? (int)total : 2000000000; first = false; }
-    if (total <= (double)cap_cells && max(dims[0], max(dims[1], dims[2])) <= kGridMaxDim) break;
-    cell *= 1.26;
-  }
-  g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
-  g.inv_cell = (float)(1.0 / cell);
-  g.inv_cell_x = (float)((double)kGridXSub / cell);
-  g.dx = dims[0]; g.dy = dims[1]; g.dz = dims[2];
-  g.n_cells = g.dx * g.dy * g.dz;
-  grid_desc_squares(g);
-  return g;
-}
-
-__device__ __forceinline__ void grid_bbox_rearm(int* __restrict__ bbox) {
-  for (int a = 0; a < 3; a++) { bbox[a] = 0x7fffffff; bbox[3 + a] = (int)0x80000000; }
-}
-
-// Only launched for an EMPTY cloud (nothing else runs then); a non-empty build derives the descriptor
-// inside grid_count_kernel and re-arms the bbox in grid_scatter_kernel.
-__global__ void grid_setup_kernel(int* __restrict__ bbox, double radius, int cap_cells, GridDesc* __restrict__ out) {
-  *out = grid_desc_from_bbox(bbox, radius, cap_cells);
-  grid_bbox_rearm(bbox);
-}
-
-// Every workgroup derives the (identical) descriptor from the finished bbox itself: one launch less
-// per build than a separate one-thread setup kernel; workgroup 0 publishes it.
-__device__ __forceinline__ void grid_count_body(const float4* __restrict__ pts, int n, const int* __restrict__ bbox,
-                                                double radius, int cap_cells, GridDesc* __restrict__ gout,
-                                                int* __restrict__ cell_of, int* __restrict__ count, int block) {
-  __shared__ GridDesc s_g;
-  if (threadIdx.x == 0) {
-    s_g = grid_desc_from_bbox(bbox, radius, cap_cells);
-    if (block == 0) *gout = s_g;
-  }
-  __syncthreads();
-  const int i = block * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const GridDesc g = s_g;
-  const float4 p = pts[i];
-  int c = -1;
-  if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
-    int cx = grid_coord(p.x, g.ox, g.inv_cell_x, g.dx); cx = min(max(cx, 0), g.dx - 1);
-    int cy = grid_coord(p.y, g.oy, g.inv_cell, g.dy); cy = min(max(cy, 0), g.dy - 1);
-    int cz = grid_coord(p.z, g.oz, g.inv_cell, g.dz); cz = min(max(cz, 0), g.dz - 1);
-    c = (cz * g.dy + cy) * g.dx + cx;
-    atomicAdd(&count[c], 1);
-  }
-  cell_of[i] = c;
-}
-__global__ void __launch_bounds__(256) grid_count_kernel(const float4* __restrict__ pts, int n, const int* __restrict__ bbox,
-                                                          double radius, int cap_cells, GridDesc* __restrict__ gout,
-                                                          int* __restrict__ cell_of, int* __restrict__ count, const int* __restrict__ n_dev = nullptr) {
-  if (n_dev) n = min(n, max(*n_dev, 0));
-  grid_count_body(pts, n, bbox, radius, cap_cells, gout, cell_of, count, (int)blockIdx.x);
-}
-
-// cursor[] holds the per-cell counts on entry and is consumed — it is all zeros again afterwards, so
-// the next build needs no memset; the order inside a cell is arbitrary, which is harmless because
-// the kNN selection uses the total order (d2, original index).
-__global__ void __launch_bounds__(256) grid_scatter_kernel(const float4* __restrict__ pts, int n,
-                                                            const int* __restrict__ cell_of,
-                                                            const int* __restrict__ cell_start, int* __restrict__ cursor,
-                                                            float4* __restrict__ sorted, int* __restrict__ pos_of,
-                                                            GridDesc* __restrict__ g, int* __restrict__ bbox, const int* __restrict__ n_dev = nullptr) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n_dev) n = min(n, max(*n_dev, 0));
-  if (i == 0) { g->n_pts = cell_start[g->n_cells]; grid_bbox_rearm(bbox); }     // number of indexed (finite) points; bbox ready for the next build
-  if (i >= n) return;
-  const int c = cell_of[i];
-  if (c < 0) { pos_of[i] = -1; return; }
-  const int k = atomicSub(&cursor[c], 1) - 1;
-  float4 p = pts[i];
-  p.w = __int_as_float(i);
-  sorted[cell_start[c] + k] = p;
-  pos_of[i] = cell_start[c] + k;      // original index -> position (the fit kernel fetches by index)
-}
-
-// ---- both maps of msfl_set_map through ONE chain of launches (round 6) -------------------------------------------------------
-// The corner map (a few thousand points) and the surf map used to be indexed one after the other: ten launches and two 4-byte
-// read-back copies in front of every batch, ~45 us of mostly launch-to-launch latency.  Here every launch serves both clouds
-// (blocks [0, blocks0) the first, the rest the second), the two count tables sit back to back and are prefix-summed by ONE
-// rocPRIM scan, and the scatter launch also writes each map's own cell table from the combined sums (the second map's minus the
-// first map's total) and the grids' wanted size straight into pinned host memory.  Same descriptors, same tables, same sorted
-// copies up to the (arbitrary, never observable) order inside a cell as two single builds.
-struct GridPairJob {
-  const float4* pts[2]; int n[2];
-  int* bbox[2]; GridDesc* gdesc[2]; int cap[2];
-  int* cell_of;              // [n[0] | n[1]]
-  int* count;                // [cap[0] + 1 | cap[1] + 1], zero on entry, zero again on exit
-  int* scanned;              // exclusive prefix sums of `count` over both tables (the scatter launch reads them)
-  int* cell_start[2]; float4* sorted[2]; int* pos_of[2];
-  int* want_host[2];         // pinned host words: cells the bounding box needs at the base cell edge (feedback for the next build)
-  int blocks0;               // workgroups of the per-point launches that serve map 0
-  int bbox_blocks0;          // the same for the bounding-box launch
-  double radius;
-};
-__global__ void __launch_bounds__(256) grid_bbox_pair_kernel(GridPairJob j) {
-  const int m = (int)blockIdx.x < j.bbox_blocks0 ? 0 : 1;
-  const int block = m ? (int)blockIdx.x - j.bbox_blocks0 : (int)blockIdx.x;
-  grid_bbox_body(j.pts[m], j.n[m], j.bbox[m], block, m ? (int)gridDim.x - j.bbox_blocks0 : j.bbox_blocks0);
-}
-__global__ void __launch_bounds__(256) grid_count_pair_kernel(GridPairJob j) {
-  const int m = (int)blockIdx.x < j.blocks0 ? 0 : 1;
-  const int block = m ? (int)blockIdx.x - j.blocks0 : (int)blockIdx.x;
-  grid_count_body(j.pts[m], j.n[m], j.bbox[m], j.radius, j.cap[m], j.gdesc[m], j.cell_of + (m ? j.n[0] : 0), j.count + (m ? j.cap[0] + 1 : 0), block);
-}
-__global__ void __launch_bounds__(256) grid_scatter_pair_kernel(GridPairJob j) {
-  const int t0 = j.cap[0] + 1, t_all = t0 + j.cap[1] + 1;
-  const int base1 = j.scanned[t0];                         // = the first map's indexed points (its table's last entries count nothing)
-  // (a) each map's own cell table, by every thread of the launch in turn
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < t_all; t += gridDim.x * blockDim.x) {
-    if (t < t0) j.cell_start[0][t] = j.scanned[t];
-    else j.cell_start[1][t - t0] = j.scanned[t] - base1;
-  }
-  // (b) the points
-  const int m = (int)blockIdx.x < j.blocks0 ? 0 : 1;
-  const int block = m ? (int)blockIdx.x - j.blocks0 : (int)blockIdx.x;
-  const int i = block * blockDim.x + threadIdx.x;
-  const int* scanned = j.scanned + (m ? t0 : 0);
-  const int sub = m ? base1 : 0;
-  if (i == 0) {
-    GridDesc* g = j.gdesc[m];
-    g->n_pts = scanned[g->n_cells] - sub;
-    *j.want_host[m] = g->want_cells;
-    grid_bbox_rearm(j.bbox[m]);
-  }
-  if (i >= j.n[m]) return;
-  const int c = (j.cell_of + (m ? j.n[0] : 0))[i];
-  if (c < 0) { j.pos_of[m][i] = -1; return; }
-  const int k = atomicSub(&(j.count + (m ? t0 : 0))[c], 1) - 1;
-  float4 p = j.pts[m][i];
-  p.w = __int_as_float(i);
-  const int at = scanned[c] - sub + k;
-  j.sorted[m][at] = p;
-  j.pos_of[m][i] = at;
-}
-
-// ---------------------------------------------------------------------------------------------
-// K4: association = transform + exact 5-NN + line / plane fit -> {C, N} record
-// ---------------------------------------------------------------------------------------------
-
-// Running 5 best as packed 64-bit keys (f32 distance bits << 32 | original map index): distances
-// are >= 0 so the bit pattern is monotone, and one unsigned compare realises the total order
-// (distance, index).  Branch-free sorted insertion: 5 compares + 10 selects on register pairs.
-struct Top5 {
-  unsigned long long k0, k1, k2, k3, k4;
-};
-
-// Every slot starts at (bound, 0xffffffff): a result is only ACCEPTED when its 5th distance is below the
-// reference's gate (< 1.0, mapping_scan_matcher.cc:128,198), so candidates at or beyond the gate can be
-// dropped at the pre-filter and rows / end cells farther than it pruned from the first row on.  A query
-// with fewer than five neighbours inside the gate keeps the sentinel in k4 and is rejected.
-__device__ __forceinline__ void top5_init(Top5& t, float bound) {
-  t.k0 = t.k1 = t.k2 = t.k3 = t.k4 = ((unsigned long long)__float_as_uint(bound) << 32) | 0xffffffffull;
-}
-__device__ __forceinline__ float top5_d4(const Top5& t) { return __uint_as_float((unsigned int)(t.k4 >> 32)); }  // the gate while < 5 found
-
-// The inline assembly below (v_min_f64 / v_max_f64 / v_med3_u32 by their gfx950 mnemonics) is written for the one target this library
-// has: a device pass for anything else stops here with a message instead of an assembler error deep in a template.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "libmsfl_hip is written for gfx950 (MI355X) only: build with --offload-arch=gfx950"
-#endif
-// unsigned 64-bit min / max of two keys whose high words are < 2^31, on the f64 min / max unit (see top5_insert)
-__device__ __forceinline__ unsigned long long u64_min_f(unsigned long long a, unsigned long long b) {
-  double r;
-  asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(__longlong_as_double((long long)a)), "v"(__longlong_as_double((long long)b)));
-  return (unsigned long long)__double_as_longlong(r);
-}
-__device__ __forceinline__ unsigned long long u64_max_f(unsigned long long a, unsigned long long b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(__longlong_as_double((long long)a)), "v"(__longlong_as_double((long long)b)));
-  return (unsigned long long)__double_as_longlong(r);
-}
-__device__ __forceinline__ void top5_insert(Top5& t, float d, int idx) {
-  // cheap pre-filter on the distance word alone (a full-rate 32-bit compare; the bit pattern of a
-  // non-negative float is monotone), then the exact 64-bit (distance, index) order
-  if (__float_as_uint(d) > (unsigned int)(t.k4 >> 32)) return;
-  const unsigned long long x = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned int)idx;
-  if (!(x < t.k4)) return;
-  // Sorted insertion as a min / max chain on the keys READ AS DOUBLES.  A key's high word is the bit pattern of a non-negative f32
-  // (< 2^31), so as an f64 it is a non-negative finite number or denormal (exponent field = the top 11 bits of the f32 pattern:
-  // <= 0x7fc even for an f32 NaN), and for non-negative doubles the IEEE order IS the unsigned order of the bit patterns; f64
-  // denormals are preserved (the default f64 mode), min / max select one operand bit for bit.  8 instructions instead of
-  // 5 x v_cmp_lt_u64 + 16 x v_cndmask_b32 (all of the 4-clock class): the insertion pass runs for the whole wavefront whenever one
-  // lane inserts and was ~30 % of the kernel.
-  const unsigned long long c0 = u64_max_f(t.k0, x); t.k0 = u64_min_f(t.k0, x);
-  const unsigned long long c1 = u64_max_f(t.k1, c0); t.k1 = u64_min_f(t.k1, c0);
-  const unsigned long long c2 = u64_max_f(t.k2, c1); t.k2 = u64_min_f(t.k2, c1);
-  const unsigned long long c3 = u64_max_f(t.k3, c2); t.k3 = u64_min_f(t.k3, c2);
-  t.k4 = c3;                    // = min(k4, c3): x < k4 (the guard above) and k3 <= k4, so the largest of {k0..k3, x} is below k4
-}
-
-// Round 4, the walk's own top list: SIX 32-bit keys (distance bits & ~7) | slot, sorted, and the candidates' positions in the
-// sorted map kept per (slot, lane) in LDS.  A candidate that passes the pre-filter takes the slot of the key it can only evict
-// (the 6th), stores its position there and goes through 1 x v_min_u32 + 5 x v_med3_u32 — ~45 clocks per insertion pass of the
-// wavefront instead of ~78 for the 64-bit min / max chain above (the pass runs for all 64 lanes whenever one lane inserts:
-// ~47 passes per wavefront).  The keys order candidates by their distance truncated to 29 bits (t = bits >> 3); the result is
-// the exact top-5 by (distance, index) whenever the six final keys have six different t:
-//  * a candidate dropped at the pre-filter had t > t(5th at that time) >= t(final 5th);
-//  * every other candidate was offered to the list, which keeps the six smallest keys offered, so a candidate outside the final
-//    top-5 with t == t(final 5th) implies t(final 6th) == t(final 5th);
-//  * with different t the truncated order IS the order of the exact distances, and the index word is never consulted.
-// A lane whose final keys show an equal-t neighbour pair (or whose 5th shares its t with the acceptance gate) is AMBIGUOUS and
-// is searched again with the exact 64-bit keys (Top5): two distances within 2^-21 relative of each other, ~1e-6 of the queries
-// on a scanned surface, every query on an exact lattice.  The 6th key's stored position may be stale (a candidate that tied
-// with it overwrote the slot without entering); the 6th is never output and can only leave the list.
-constexpr unsigned int kTopSentinel = 0xffffff00u;      // sentinels 0xffffff00 + 9 i: six different t, slots 0..5, above every f32 distance pattern
-// k = med3(below, k, x) IN PLACE (below <= k): the sorted list's element after x has been inserted somewhere
-__device__ __forceinline__ void u32_med3_into(unsigned int& k, unsigned int below, unsigned int x) {
-  asm("v_med3_u32 %0, %1, %0, %2" : "+v"(k) : "v"(below), "v"(x));
-}
-struct Top6K {
-  unsigned int k0, k1, k2, k3, k4, k5;
-  unsigned int bound;               // min(k4 | 7, gate bits): the pre-filter, a conservative 5th distance for the row / cell bounds
-  unsigned int gate;                // acceptance gate bits
-  int* col;                         // this lane's column of the slot table: col[slot * kTopSlotStride]
-};
-constexpr int kTopSlots = 6;
-__device__ __forceinline__ void top_init(Top6K& t, float bound, int* col) {
-  t.k0 = kTopSentinel; t.k1 = kTopSentinel + 9; t.k2 = kTopSentinel + 18; t.k3 = kTopSentinel + 27; t.k4 = kTopSentinel + 36; t.k5 = kTopSentinel + 45;
-  t.gate = __float_as_uint(bound); t.bound = t.gate; t.col = col;
-}
-__device__ __forceinline__ float top_d4(const Top6K& t) { return __uint_as_float(t.bound); }
-// true: the five nearest and their order are decided by the truncated keys (see above); false: search again with Top5
-__device__ __forceinline__ bool top_settled(const Top6K& t, float accept_gate) {
-  const unsigned int amb = min(min(min(t.k0 ^ t.k1, t.k1 ^ t.k2), min(t.k2 ^ t.k3, t.k3 ^ t.k4)), min(t.k4 ^ t.k5, t.k4 ^ __float_as_uint(accept_gate)));
-  return amb >= 8u;
-}
-__device__ __forceinline__ bool top_found(const Top6K& t) { return t.k4 < kTopSentinel; }     // five real candidates within the gate
-template <int STRIDE>
-__device__ __forceinline__ int top_pos(const Top6K& t, unsigned int k) { return (int)((unsigned int)t.col[(k & 7u) * STRIDE] >> 4); }   // stored: byte offset
-
-// flann::L2_Simple<float>: ((dx*dx) + dy*dy) + dz*dz, every operation rounded to f32
-__device__ __forceinline__ float l2_simple(float4 a, float3 q) {
-  const float dx = a.x - q.x, dy = a.y - q.y, dz = a.z - q.z;
-  float r = dx * dx;
-  r = r + dy * dy;
-  r = r + dz * dz;
-  return r;
-}
-// the same arithmetic with x and y in one packed-f32 lane pair (v_pk_add_f32 / v_pk_mul_f32: two
-// IEEE operations per instruction, individually rounded, so the result is bit-identical)
-typedef float msfl_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float l2_simple_pk(float4 a, msfl_f2 qxy, float qz) {
-  const msfl_f2 axy = {a.x, a.y};
-  const msfl_f2 dxy = axy - qxy;
-  const msfl_f2 sxy = dxy * dxy;
-  const float dz = a.z - qz;
-  float r = sxy.x + sxy.y;
-  r = r + dz * dz;
-  return r;
-}
-
-// Exact 5-NN over the 27-cell neighbourhood.  Rows (y,z) are visited centre-first and a row / an
-// end cell of a row is skipped when a LOWER BOUND of its distance to the query already exceeds the
-// current 5th-best distance, so the result is identical to scanning all 27 cells.  The bound is
-// shrunk by 1e-3 cell to stay conservative under the f32 rounding of cell coordinates.
-__device__ __forceinline__ float axis_gap(float u, int c) {
-  // distance (in cell units) from coordinate u to the interval [c, c+1], minus slack, floored at 0
-  const float g = fmaxf((float)c - u, u - (float)(c + 1));
-  return fmaxf(g - 1e-3f, 0.0f);
-}
-
-// The exact walk on 64-bit keys (Top5, initialised by the caller with the acceptance gate): the search again of a query that the
-// truncated-key walk below (knn5_grid_k32) leaves ambiguous.
-__device__ __forceinline__ void knn5_grid(const GridDesc& g, const float4* __restrict__ sorted,
-                                          const int* __restrict__ cell_start, float3 q, Top5& t,
-                                          int& n_cand) {      // n_cand: candidates evaluated (dead code unless the caller reads it)
-  const float ux = (q.x - g.ox) * g.inv_cell_x, uy = (q.y - g.oy) * g.inv_cell, uz = (q.z - g.oz) * g.inv_cell;
-  const int cx = grid_coord(q.x, g.ox, g.inv_cell_x, g.dx);
-  const int cy = grid_coord(q.y, g.oy, g.inv_cell, g.dy);
-  const int cz = grid_coord(q.z, g.oz, g.inv_cell, g.dz);
-  const int xs = max(cx - kGridXSub, 0), xe = min(cx + kGridXSub, g.dx - 1);
-  if (xs > xe) return;
-  const float cell2 = g.cell2;
-  // per-axis lower bounds for the three y and three z cell offsets, computed once
-  const float gy0 = axis_gap(uy, cy - 1), gy1 = axis_gap(uy, cy), gy2 = axis_gap(uy, cy + 1);
-  const float gz0 = axis_gap(uz, cz - 1), gz1 = axis_gap(uz, cz), gz2 = axis_gap(uz, cz + 1);
-  const float cellx2 = g.cellx2;
-  // squared lower bounds of the kGridXSub cells left of / right of the query cell, outermost first: they
-  // are the same for all nine rows, so the per-row trimming is two adds and two compares per side
-  float gxa[kGridXSub], gxb[kGridXSub];
-#pragma unroll
-  for (int k = 0; k < kGridXSub; k++) {
-    const float ga = axis_gap(ux, xs + k), gb = axis_gap(ux, xe - k);
-    gxa[k] = ga * ga * cellx2; gxb[k] = gb * gb * cellx2;
-  }
-  const msfl_f2 qxy = {q.x, q.y};
-  // Visit order of the 9 (dy, dz) rows, PER QUERY: centre, then the two side rows on the query's near sides (smaller
-  // gap first), the two far side rows, the near-near diagonal, the two mixed diagonals, the far-far diagonal.  Any
-  // order is exact (a row is only skipped on a lower bound); this one makes the 64 queries of a wavefront need the
-  // same loop POSITIONS: with a fixed (-y, +y, -z, +z) order each position ran for the ~19 lanes whose near side it
-  // happened to be and cost the longest of their ranges, now the first two positions carry nearly all of that work
-  // and the later ones are skipped by the whole wavefront; the 5th-best distance also tightens sooner.
-  const bool y_lo = gy0 <= gy2, z_lo = gz0 <= gz2;                 // near side: the smaller gap
-  const int sy = y_lo ? -1 : 1, sz = z_lo ? -1 : 1;
-  const float g_ny = y_lo ? gy0 : gy2, g_fy = y_lo ? gy2 : gy0;
-  const float g_nz = z_lo ? gz0 : gz2, g_fz = z_lo ? gz2 : gz0;
-  const bool ny_first = g_ny <= g_nz, fy_first = g_fy <= g_fz;
-  const bool e_first = g_ny * g_ny + g_fz * g_fz <= g_fy * g_fy + g_nz * g_nz;   // (near y, far z) before (far y, near z)
-  // candidates of the cells [a, b] of a row: x-adjacent cells are contiguous in the sorted array
-  auto scan = [&](int row, int a, int b) __attribute__((always_inline)) {
-    const int s = cell_start[row + a], e = cell_start[row + b + 1];
-    n_cand += e - s;
-    const float4* p = sorted + s;
-    const float4* const pe = sorted + e;
-    for (; p + 1 < pe; p += 2) {            // two loads in flight, one address register
-      float4 m0 = p[0], m1 = p[1];
-      // keep the index word in the 16-byte load: left alone, the compiler splits it off into a second,
-      // dependent load inside the (latency-critical) insertion path
-      asm volatile("" : "+v"(m0.w));
-      top5_insert(t, l2_simple_pk(m0, qxy, q.z), __float_as_int(m0.w));
-      asm volatile("" : "+v"(m1.w));
-      top5_insert(t, l2_simple_pk(m1, qxy, q.z), __float_as_int(m1.w));
-    }
-    if (p < pe) { float4 m = p[0]; asm volatile("" : "+v"(m.w)); top5_insert(t, l2_simple_pk(m, qxy, q.z), __float_as_int(m.w)); }
-  };
-#pragma unroll
-  for (int r = 0; r < 9; r++) {
-    int dy, dz; float gy, gz;
-    if (r == 0) { dy = 0; dz = 0; gy = gy1; gz = gz1; }
-    else if (r == 1 || r == 2) {                                    // near side rows
-      const bool yrow = (r == 1) == ny_first;
-      dy = yrow ? sy : 0; dz = yrow ? 0 : sz; gy = yrow ? g_ny : gy1; gz = yrow ? gz1 : g_nz;
-    } else if (r == 3 || r == 4) {                                  // far side rows
-      const bool yrow = (r == 3) == fy_first;
-      dy = yrow ? -sy : 0; dz = yrow ? 0 : -sz; gy = yrow ? g_fy : gy1; gz = yrow ? gz1 : g_fz;
-    } else if (r == 5) { dy = sy; dz = sz; gy = g_ny; gz = g_nz; }
-    else if (r == 6 || r == 7) {                                    // mixed diagonals
-      const bool e = (r == 6) == e_first;                           // e: (near y, far z)
-      dy = e ? sy : -sy; dz = e ? -sz : sz; gy = e ? g_ny : g_fy; gz = e ? g_fz : g_nz;
-    } else { dy = -sy; dz = -sz; gy = g_fy; gz = g_fz; }
-    const int y = cy + dy, z = cz + dz;
-    if (y < 0 || y >= g.dy || z < 0 || z >= g.dz) continue;
-    const float row2 = (gy * gy + gz * gz) * cell2;
-    const int row = (z * g.dy + y) * g.dx;
-    const float d4 = top5_d4(t);
-    if (row2 > d4) continue;                  // d4 is the acceptance gate until five neighbours are known
-    // trim the x range: drop end cells whose lower bound exceeds the 5th-best distance
-    // a cell is dropped when its lower bound exceeds d4; the bounds shrink towards the query, so count the
-    // leading run of dropped cells on each side
-    int a = xs, b = xe;
-    bool da = true, db = true;
-#pragma unroll
-    for (int k = 0; k < kGridXSub; k++) {
-      da = da && (row2 + gxa[k] > d4); a += da ? 1 : 0;
-      db = db && (row2 + gxb[k] > d4); b -= db ? 1 : 0;
-    }
-    if (a > b) continue;                      // only near the grid border: every remaining cell is out of reach
-    scan(row, a, b);
-  }
-}
-
-// The same walk for Top6K, written for the instruction count (the kernel is VALU-issue bound: every wave instruction of a
-// visited row is paid 64 lanes wide).  Differences to knn5_grid, none of which changes the result:
-//  * candidates are addressed by 32-bit BYTE offsets from the (scalar) map base (saddr loads, 32-bit loop control; a map is
-//    < 2^28 points: msfl_set_map refuses more) and the slot table stores the byte offset (position = offset >> 4 at the end);
-//  * a row's end cells are trimmed by COUNTING the cells whose bound exceeds (5th distance - row bound): the per-side bounds
-//    are made monotone at set-up (a cell at or beyond the query's own cell gets 0), so the count is the leading run;
-//  * row validity (y, z inside the grid) and the row bases come from six set-up compares / two offsets instead of four
-//    compares and two 32-bit multiplies per row.
-template <int STRIDE>
-__device__ __forceinline__ void top_insert_off(Top6K& t, float d, unsigned int off) {
-  const unsigned int db = __float_as_uint(d);
-  if (db > t.bound) return;
-  const unsigned int slot = t.k5 & 7u;
-  const unsigned int x = (db & ~7u) | slot;
-  t.col[slot * STRIDE] = (int)off;
-  u32_med3_into(t.k5, t.k4, x); u32_med3_into(t.k4, t.k3, x); u32_med3_into(t.k3, t.k2, x);
-  u32_med3_into(t.k2, t.k1, x); u32_med3_into(t.k1, t.k0, x);
-  t.k0 = min(t.k0, x);
-  t.bound = min(t.k4 | 7u, t.gate);
-}
-template <int STRIDE>
-__device__ __forceinline__ void knn5_grid_k32(const GridDesc& g, const float4* __restrict__ sorted,
-                                              const int* __restrict__ cell_start, float3 q, Top6K& t, int& n_cand,
-                                              int cell_base = 0) {        // cell_base: this map's slice of a shared cell table (pairs)
-  const float ux = (q.x - g.ox) * g.inv_cell_x, uy = (q.y - g.oy) * g.inv_cell, uz = (q.z - g.oz) * g.inv_cell;
-  const int cx = grid_coord(q.x, g.ox, g.inv_cell_x, g.dx);
-  const int cy = grid_coord(q.y, g.oy, g.inv_cell, g.dy);
-  const int cz = grid_coord(q.z, g.oz, g.inv_cell, g.dz);
-  const int xs = max(cx - kGridXSub, 0), xe = min(cx + kGridXSub, g.dx - 1);
-  if (xs > xe) return;
-  const float cell2 = g.cell2, cellx2 = g.cellx2;
-  const float gy0 = axis_gap(uy, cy - 1), gy1 = axis_gap(uy, cy), gy2 = axis_gap(uy, cy + 1);
-  const float gz0 = axis_gap(uz, cz - 1), gz1 = axis_gap(uz, cz), gz2 = axis_gap(uz, cz + 1);
-  float gxa[kGridXSub], gxb[kGridXSub];       // outermost first, non-increasing
-#pragma unroll
-  for (int k = 0; k < kGridXSub; k++) {
-    const float ga = axis_gap(ux, xs + k), gb = axis_gap(ux, xe - k);
-    gxa[k] = xs + k < cx ? ga * ga * cellx2 : 0.0f;
-    gxb[k] = xe - k > cx ? gb * gb * cellx2 : 0.0f;
-  }
-  const msfl_f2 qxy = {q.x, q.y};
-  const bool y_lo = gy0 <= gy2, z_lo = gz0 <= gz2;                 // near side: the smaller gap
-  const float g_ny = y_lo ? gy0 : gy2, g_fy = y_lo ? gy2 : gy0;
-  const float g_nz = z_lo ? gz0 : gz2, g_fz = z_lo ? gz2 : gz0;
-  const float q_ny = g_ny * g_ny, q_fy = g_fy * g_fy, q_nz = g_nz * g_nz, q_fz = g_fz * g_fz, q_y1 = gy1 * gy1, q_z1 = gz1 * gz1;
-  const bool ny_first = g_ny <= g_nz, fy_first = g_fy <= g_fz;
-  const bool e_first = q_ny + q_fz <= q_fy + q_nz;                 // (near y, far z) before (far y, near z)
-  // validity of the three y and three z cell coordinates, near / centre / far
-  const int sy = y_lo ? -1 : 1, sz = z_lo ? -1 : 1;
-  const bool v_y1 = (unsigned int)cy < (unsigned int)g.dy, v_ny = (unsigned int)(cy + sy) < (unsigned int)g.dy, v_fy = (unsigned int)(cy - sy) < (unsigned int)g.dy;
-  const bool v_z1 = (unsigned int)cz < (unsigned int)g.dz, v_nz = (unsigned int)(cz + sz) < (unsigned int)g.dz, v_fz = (unsigned int)(cz - sz) < (unsigned int)g.dz;
-  const int base0 = (cz * g.dy + cy) * g.dx + cell_base;           // only used where the row is valid
-  const int off_y = y_lo ? -g.dx : g.dx;                           // near-side steps
-  const int zstep = g.dy * g.dx;
-  const int off_z = z_lo ? -zstep : zstep;
-  const char* const mapb = (const char*)sorted;
-  auto visit = [&](bool valid, int row, float rowq) __attribute__((always_inline)) {
-    const float row2 = rowq * cell2;
-    const float d4 = top_d4(t);
-    if (!valid || row2 > d4) return;           // d4: the acceptance gate until five neighbours are known, then >= the 5th distance
-    const float room = d4 - row2;
-    int a = xs, b = xe;
-#pragma unroll
-    for (int k = 0; k < kGridXSub; k++) { a += gxa[k] > room ? 1 : 0; b -= gxb[k] > room ? 1 : 0; }
-    if (a > b) return;
-    const unsigned int s = (unsigned int)cell_start[(unsigned int)(row + a)], e = (unsigned int)cell_start[(unsigned int)(row + b + 1)];
-    if (s == e) return;
-    n_cand += (int)(e - s);
-    unsigned int off = s << 4;
-    const unsigned int end = e << 4, last = end - 16u;      // last: offset of the range's last point (>= off)
-    for (; off < last; off += 32u) {           // two loads in flight
-      float4 m0 = *(const float4*)(mapb + off), m1 = *(const float4*)(mapb + off + 16u);
-      asm volatile("" : "+v"(m0.w));           // keep the 16-byte loads (12-byte loads: slower in rounds 1-2, no change in round 4b)
-      top_insert_off<STRIDE>(t, l2_simple_pk(m0, qxy, q.z), off);
-      asm volatile("" : "+v"(m1.w));
-      top_insert_off<STRIDE>(t, l2_simple_pk(m1, qxy, q.z), off + 16u);
-    }
-    if (off < end) { float4 m = *(const float4*)(mapb + off); asm volatile("" : "+v"(m.w)); top_insert_off<STRIDE>(t, l2_simple_pk(m, qxy, q.z), off); }
-  };
-  // the same per-query row order as knn5_grid: centre, near sides (smaller gap first), far sides, near-near, mixed diagonals, far-far
-  visit(v_y1 && v_z1, base0, q_y1 + q_z1);
-  {
-    const bool va = v_ny && v_z1, vb = v_y1 && v_nz;               // A: near-y side row, B: near-z side row
-    const float ra = q_ny + q_z1, rb = q_y1 + q_nz;
-    visit(ny_first ? va : vb, base0 + (ny_first ? off_y : off_z), ny_first ? ra : rb);
-    visit(ny_first ? vb : va, base0 + (ny_first ? off_z : off_y), ny_first ? rb : ra);
-  }
-  {
-    const bool va = v_fy && v_z1, vb = v_y1 && v_fz;
-    const float ra = q_fy + q_z1, rb = q_y1 + q_fz;
-    visit(fy_first ? va : vb, base0 - (fy_first ? off_y : off_z), fy_first ? ra : rb);
-    visit(fy_first ? vb : va, base0 - (fy_first ? off_z : off_y), fy_first ? rb : ra);
-  }
-  visit(v_ny && v_nz, base0 + off_y + off_z, q_ny + q_nz);
-  {
-    const bool va = v_ny && v_fz, vb = v_fy && v_nz;               // A: (near y, far z)
-    const float ra = q_ny + q_fz, rb = q_fy + q_nz;
-    const int oa = off_y - off_z, ob = off_z - off_y;
-    visit(e_first ? va : vb, base0 + (e_first ? oa : ob), e_first ? ra : rb);
-    visit(e_first ? vb : va, base0 + (e_first ? ob : oa), e_first ? rb : ra);
-  }
-  visit(v_fy && v_fz, base0 - off_y - off_z, q_fy + q_fz);
-}
 
 struct FitOut { d3 C, N; bool ok; };
 
@@ -939,24 +349,21 @@ knn5_scan2map_rows_kernel(BatchView bv, const double* __restrict__ poses, const 
   Top5 t;
   top5_init(t, max_sq_dist);
   const unsigned long long sentinel = t.k0;
-  const float ux = (q.x - gd.ox) * gd.inv_cell_x, uy = (q.y - gd.oy) * gd.inv_cell, uz = (q.z - gd.oz) * gd.inv_cell;
-  const int cx = grid_coord(q.x, gd.ox, gd.inv_cell_x, gd.dx);
-  const int cy = grid_coord(q.y, gd.oy, gd.inv_cell, gd.dy);
-  const int cz = grid_coord(q.z, gd.oz, gd.inv_cell, gd.dz);
-  const int xs = max(cx - kGridXSub, 0), xe = min(cx + kGridXSub, gd.dx - 1);
-  const int y = cy + (sl % 3) - 1, z = cz + (sl / 3) - 1;
-  if (sl < 9 && xs <= xe && y >= 0 && y < gd.dy && z >= 0 && z < gd.dz) {
-    const float gy = axis_gap(uy, y), gz = axis_gap(uz, z);
+  const GridQuery w = grid_query(gd, q);
+  const int y = w.cy + (sl % 3) - 1, z = w.cz + (sl / 3) - 1;
+  if (sl < 9 && w.xs <= w.xe && y >= 0 && y < gd.dy && z >= 0 && z < gd.dz) {
+    const float gy = axis_gap(w.uy, y), gz = axis_gap(w.uz, z);
     const float row2 = (gy * gy + gz * gz) * gd.cell2;
     if (!(row2 > max_sq_dist)) {
       // end cells whose lower bound is beyond the gate hold no acceptable candidate
-      int a = xs, e_cell = xe;
+      float gxa[kGridXSub], gxb[kGridXSub];
+      grid_x_bounds(gd, w, gxa, gxb);
+      int a = w.xs, e_cell = w.xe;
       bool da = true, db = true;
 #pragma unroll
       for (int k = 0; k < kGridXSub; k++) {
-        const float ga = axis_gap(ux, xs + k), gb = axis_gap(ux, xe - k);
-        da = da && (row2 + ga * ga * gd.cellx2 > max_sq_dist); a += da ? 1 : 0;
-        db = db && (row2 + gb * gb * gd.cellx2 > max_sq_dist); e_cell -= db ? 1 : 0;
+        da = da && (row2 + gxa[k] > max_sq_dist); a += da ? 1 : 0;
+        db = db && (row2 + gxb[k] > max_sq_dist); e_cell -= db ? 1 : 0;
       }
       if (a <= e_cell) {
         const int row = (z * gd.dy + y) * gd.dx;

@@ -5,8 +5,8 @@
 //   score_poses_kernel   one lane per (hypothesis, feature): transform, nearest map point of the feature's kind within the
 //                        threshold, then an integer reduction into the hypothesis' record
 //
-// The walk has the geometry of knn5_grid (msfl_kernels.cuh): the same descriptor, grid_coord, axis_gap with its 1e-3 slack,
-// nine (y, z) rows centre-first in the per-query near-side order, x ends trimmed on the per-side lower bounds.  Its state is
+// The walk is grid_walk_exact (msfl_knn_index.cuh), the one knn5_grid takes: nine (y, z) rows centre-first in the per-query
+// near-side order, x ends trimmed on the per-side lower bounds.  Its state is
 // ONE key (f32 distance bits, original index), initialised to (threshold, no index), and a row or end cell is skipped when
 // its lower bound exceeds the key's distance.  A lower bound never exceeds the f32 distance of a point in the cell (that is
 // what the slack is for), so a skipped cell holds no point at or below the current best: the result equals a brute-force
@@ -73,64 +73,14 @@ constexpr unsigned int kScoreNoIndex = 0xffffffffu;   // above every original in
 // Exact nearest neighbour of q within the distance of `best` on entry; best keeps (distance, original index) of the winner.
 __device__ __forceinline__ void nn1_grid(const GridDesc& g, const float4* __restrict__ sorted, const int* __restrict__ cell_start,
                                          float3 q, unsigned long long& best) {
-  const float ux = (q.x - g.ox) * g.inv_cell_x, uy = (q.y - g.oy) * g.inv_cell, uz = (q.z - g.oz) * g.inv_cell;
-  const int cx = grid_coord(q.x, g.ox, g.inv_cell_x, g.dx);
-  const int cy = grid_coord(q.y, g.oy, g.inv_cell, g.dy);
-  const int cz = grid_coord(q.z, g.oz, g.inv_cell, g.dz);
-  const int xs = max(cx - kGridXSub, 0), xe = min(cx + kGridXSub, g.dx - 1);
-  if (xs > xe) return;
-  const float cell2 = g.cell2, cellx2 = g.cellx2;
-  const float gy0 = axis_gap(uy, cy - 1), gy1 = axis_gap(uy, cy), gy2 = axis_gap(uy, cy + 1);
-  const float gz0 = axis_gap(uz, cz - 1), gz1 = axis_gap(uz, cz), gz2 = axis_gap(uz, cz + 1);
-  float gxa[kGridXSub], gxb[kGridXSub];     // squared lower bounds of the end cells, outermost first (the same for all nine rows)
-#pragma unroll
-  for (int k = 0; k < kGridXSub; k++) {
-    const float ga = axis_gap(ux, xs + k), gb = axis_gap(ux, xe - k);
-    gxa[k] = ga * ga * cellx2; gxb[k] = gb * gb * cellx2;
-  }
-  // row order of knn5_grid: centre, near side rows (smaller gap first), far side rows, near-near, mixed diagonals, far-far
-  const bool y_lo = gy0 <= gy2, z_lo = gz0 <= gz2;
-  const int sy = y_lo ? -1 : 1, sz = z_lo ? -1 : 1;
-  const float g_ny = y_lo ? gy0 : gy2, g_fy = y_lo ? gy2 : gy0;
-  const float g_nz = z_lo ? gz0 : gz2, g_fz = z_lo ? gz2 : gz0;
-  const bool ny_first = g_ny <= g_nz, fy_first = g_fy <= g_fz;
-  const bool e_first = g_ny * g_ny + g_fz * g_fz <= g_fy * g_fy + g_nz * g_nz;
-#pragma unroll
-  for (int r = 0; r < 9; r++) {
-    int dy, dz; float gy, gz;
-    if (r == 0) { dy = 0; dz = 0; gy = gy1; gz = gz1; }
-    else if (r == 1 || r == 2) {
-      const bool yrow = (r == 1) == ny_first;
-      dy = yrow ? sy : 0; dz = yrow ? 0 : sz; gy = yrow ? g_ny : gy1; gz = yrow ? gz1 : g_nz;
-    } else if (r == 3 || r == 4) {
-      const bool yrow = (r == 3) == fy_first;
-      dy = yrow ? -sy : 0; dz = yrow ? 0 : -sz; gy = yrow ? g_fy : gy1; gz = yrow ? gz1 : g_fz;
-    } else if (r == 5) { dy = sy; dz = sz; gy = g_ny; gz = g_nz; }
-    else if (r == 6 || r == 7) {
-      const bool e = (r == 6) == e_first;
-      dy = e ? sy : -sy; dz = e ? -sz : sz; gy = e ? g_ny : g_fy; gz = e ? g_fz : g_nz;
-    } else { dy = -sy; dz = -sz; gy = g_fy; gz = g_fz; }
-    const int y = cy + dy, z = cz + dz;
-    if (y < 0 || y >= g.dy || z < 0 || z >= g.dz) continue;
-    const float row2 = (gy * gy + gz * gz) * cell2;
-    const float d_best = __uint_as_float((unsigned int)(best >> 32));
-    if (row2 > d_best) continue;
-    int a = xs, b = xe;
-    bool da = true, db = true;
-#pragma unroll
-    for (int k = 0; k < kGridXSub; k++) {     // the leading run of end cells out of reach, per side
-      da = da && (row2 + gxa[k] > d_best); a += da ? 1 : 0;
-      db = db && (row2 + gxb[k] > d_best); b -= db ? 1 : 0;
-    }
-    if (a > b) continue;
-    const int row = (z * g.dy + y) * g.dx;
-    const int s = cell_start[row + a], e = cell_start[row + b + 1];     // x-adjacent cells are contiguous in the sorted array
+  grid_walk_exact(g, cell_start, q, [&]() __attribute__((always_inline)) { return __uint_as_float((unsigned int)(best >> 32)); },
+                  [&](int s, int e) __attribute__((always_inline)) {
     for (int i = s; i < e; i++) {
       const float4 m = sorted[i];
       const unsigned long long k = score_key(l2_simple(m, q), __float_as_uint(m.w));
       best = k < best ? k : best;
     }
-  }
+  });
 }
 
 // grid: x = workgroups of one hypothesis (its scan's corner features first, then its surf features; a workgroup holds one

@@ -15,7 +15,8 @@ An exact top five by (distance, index) does not depend on the cell size, the wal
   pairs           msfl_match_pairs_batch on (generic, rod_x_2.7km) against single calls
   table life      the sequence knn_grid_cases.TABLE_LIFE of msfl_set_map calls on ONE handle (spans grow and shrink, the pair
                   and single build paths alternate, a one-point map in between): after every call the records equal those of a
-                  fresh handle given only that map; with the default cap and with MSFL_GRID_CAP_CELLS=65536
+                  fresh handle given only that map; with the default cap and with MSFL_GRID_CAP_CELLS=65536, and each of the
+                  two again with MSFL_INDEX_SINGLE=1 on the long-lived handle
   non-finite      the generic map with NaN / Inf points interleaved gives the oracle's records on the map without them
 
 A map of fewer than five points is refused (MSFL_MAP_TOO_SMALL) by every handle alike; the build has run by then.
@@ -269,10 +270,13 @@ def test_pairs_batch_equals_single_calls_on_a_rod(gpu):
         h.close()
 
 
-@pytest.mark.parametrize("cap", [None, 65536], ids=["default", "cap65536"])
-def test_table_life_across_builds_of_one_handle(cap):
+@pytest.mark.parametrize("cap,single", [(None, False), (65536, False), (None, True), (65536, True)],
+                         ids=["default", "cap65536", "default-single", "cap65536-single"])
+def test_table_life_across_builds_of_one_handle(cap, single):
     """Spans grow (rod_y_12km wants 384 k cells at the base edge) and shrink back, the pair and the single build paths alternate,
-    and a one-point map is built in between: the shared count table must come back all zero from every build."""
+    and a one-point map is built in between: the shared count table must come back all zero from every build.  single: the
+    long-lived handle builds every map with MSFL_INDEX_SINGLE=1, so the single build's report of the wanted table size is what
+    sets every later span."""
     def records(h, c):
         return [_associate(h, c, pose) for pose in c.poses]
 
@@ -286,13 +290,14 @@ def test_table_life_across_builds_of_one_handle(cap):
         finally:
             h.close()
     assert fresh["corner_1pt"][0] == TOO_SMALL and fresh["empty_corner"][0] == TOO_SMALL and not isinstance(fresh["generic"][0], str)
-    h = _handle(cap)
+    h = _handle(cap, single=single)
     try:
         for step, name in enumerate(gc.TABLE_LIFE):
             c = gc.case(name)
             h.set_map(c.mc, c.ms)
             for k, (a, b) in enumerate(zip(records(h, c), fresh[name])):
-                _assert_same(a, b, "cap %s, step %d (%s), pose %d: the long-lived handle against a fresh one" % (cap or "default", step, name, k))
+                _assert_same(a, b, "cap %s%s, step %d (%s), pose %d: the long-lived handle against a fresh one"
+                             % (cap or "default", ", single builds" if single else "", step, name, k))
     finally:
         h.close()
 

@@ -1,4 +1,4 @@
-"""CPU model of the 5-NN walk's truncated-key top list (msf_loam_amd/csrc/msfl_kernels.cuh: Top6K, top_insert_off, top_settled).
+"""CPU model of the 5-NN walk's truncated-key top list (msf_loam_amd/csrc/msfl_knn_index.cuh: Top6K, top_insert_off, top_settled).
 
 The HIP kernels keep six sorted 32-bit keys (f32 distance bits & ~7) | slot, store each kept candidate's position in a slot
 table and search a query again with exact 64-bit (distance, index) keys when `top_settled` is false.  This test restates
