@@ -223,7 +223,7 @@ def world_drive(world, kind, n):
 
 def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=False, maps_out=None, quirks=False, imu=None, clouds_out=None,
              uncertainty=None, unc_out=None, priors=None, map_window=None, window_out=None, slam_hook=None, load_map=None, save_map=None,
-             degeneracy=None, degen_out=None):
+             degeneracy=None, degen_out=None, reject=None, reject_out=None):
     """The same loop through the device-resident SLAM step (msfl_slam_add_scan): raw scan in, pose out, one
     synchronisation per scan (pipelined=False) or none until the record is fetched one scan later (pipelined=True: the
     odometry chain of scan k + 1 runs under the mapping chain of scan k, like the reference's two threads).
@@ -232,6 +232,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     priors: per scan None or an (odometry, mapping) pair for msfl_slam_set_next_prior, each None or (pose7, sqrt_information 6 x 6).
     degeneracy: (min_eig_odometry, min_eig_mapping), either None = that matcher off, turns msfl_slam_set_degeneracy on; degen_out (a list)
     then receives per scan the (odometry, mapping) records of msfl_slam_get_degeneracy.
+    reject: (odometry, mapping), each None = that matcher off or a capi.OutlierRejection, turns msfl_slam_set_outlier_rejection on; reject_out
+    (a list) then receives per scan the (odometry, mapping) records of msfl_slam_get_rejection.
     map_window: (half_cells, every_n_scans) for msfl_slam_set_map_window; window_out (a list) then receives per scan the (corner, surf)
     records of msfl_slam_get_map_window.  slam_hook(slam, k): called before scan k is fed.
     load_map: PREFIX -> PREFIX.corner.npz / PREFIX.surf.npz (msf_loam_amd/mapio.py) are loaded into the session's two stores before the
@@ -254,6 +256,9 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     if degeneracy is not None:
         slam.set_degeneracy(odometry=degeneracy[0], mapping=degeneracy[1])
     want_degen = degeneracy is not None and degen_out is not None
+    if reject is not None:
+        slam.set_outlier_rejection(odometry=reject[0], mapping=reject[1])
+    want_reject = reject is not None and reject_out is not None
     if map_window is not None:
         slam.set_map_window(map_window[0], map_window[1])
     want_win = window_out is not None
@@ -279,6 +284,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
                     unc_out.append(slam.get_uncertainty(k - 1))
                 if want_degen:
                     degen_out.append(slam.get_degeneracy(k - 1))
+                if want_reject:
+                    reject_out.append(slam.get_rejection(k - 1))
                 if want_win:
                     window_out.append(slam.get_map_window(k - 1))
                 if clouds_out is not None:
@@ -289,6 +296,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
                 unc_out.append(slam.get_uncertainty(k))
             if want_degen:
                 degen_out.append(slam.get_degeneracy(k))
+            if want_reject:
+                reject_out.append(slam.get_rejection(k))
             if want_win:
                 window_out.append(slam.get_map_window(k))
             if clouds_out is not None:
@@ -302,6 +311,8 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
             unc_out.append(slam.get_uncertainty(n - 1))
         if want_degen:
             degen_out.append(slam.get_degeneracy(n - 1))
+        if want_reject:
+            reject_out.append(slam.get_rejection(n - 1))
         if want_win:
             window_out.append(slam.get_map_window(n - 1))
         if clouds_out is not None:
@@ -342,6 +353,9 @@ def main():
     ap.add_argument("--degeneracy", default=None, metavar="MIN_EIG_ODOM,MIN_EIG_MAP",
                     help="msfl_slam_set_degeneracy: both matchers hold the eigen-directions of their entry matrix below the given threshold at the "
                          "guess (solution remapping); prints per scan n_held of the two outer iterations of both matchers")
+    ap.add_argument("--reject", default=None, metavar="threshold:T | fraction:F",
+                    help="msfl_slam_set_outlier_rejection on both matchers, in front of the last outer iteration's solve: threshold:0.2 rejects "
+                         "correspondences whose residual norm exceeds 0.2, fraction:0.15 the 15 %% largest of every scan; prints per scan what went")
     ap.add_argument("--map-window", default=None, metavar="HX,HY,HZ[,N]",
                     help="msfl_slam_set_map_window: crop both map stores to +-HX,HY,HZ cells around the pose after every N-th scan (default 1); "
                          "23,23,23 is the smallest window that takes nothing from the registration of the scan at its centre")
@@ -365,6 +379,14 @@ def main():
         if len(d) != 2:
             ap.error("--degeneracy takes MIN_EIG_ODOM,MIN_EIG_MAP")
         degeneracy = tuple(d)
+    reject = None
+    if args.reject:
+        from msf_loam_amd import capi
+        kind, _, value = args.reject.partition(":")
+        if kind not in ("threshold", "fraction") or not value:
+            ap.error("--reject takes threshold:T or fraction:F")
+        cfg = capi.outlier_rejection(**{kind: float(value)})
+        reject = (cfg, cfg)
     if args.world == "room":
         world = synth.World(ground_half=45.0)
         truth = trajectory(args.scans)
@@ -381,11 +403,15 @@ def main():
     scans = [synth.make_scan(world, truth[k], synth.SEED + 5000 + k, **kw) for k in range(args.scans)]
     import gc
     gc.collect(); gc.disable()
-    unc, degen = [], []
+    unc, degen, rejected = [], [], []
     est, recs, ms = run_slam(world, truth, pipelined=args.mode == "slam-pipelined", scans=scans, quirks=args.reference_quirks,
                              imu=synthetic_imu(truth) if args.imu else None, clouds_out=[] if args.keep_clouds else None,
                              uncertainty=args.uncertainty, unc_out=unc, map_window=map_window, load_map=args.load_map, save_map=args.save_map,
-                             degeneracy=degeneracy, degen_out=degen)
+                             degeneracy=degeneracy, degen_out=degen, reject=reject, reject_out=rejected)
+    for k, (o, m) in enumerate(rejected):
+        print("scan %4d  rejected edges / planes of the last solve: odometry %d of %d / %d of %d  mapping %d of %d / %d of %d" %
+              (k, o["n_edge_rejected"][1], o["n_edge_in"][1], o["n_plane_rejected"][1], o["n_plane_in"][1],
+               m["n_edge_rejected"][1], m["n_edge_in"][1], m["n_plane_rejected"][1], m["n_plane_in"][1]), file=sys.stderr)
     for k, (o, m) in enumerate(degen):
         print("scan %4d  n_held odometry %s mapping %s  lambda_min of the mapping solves %s" %
               (k, list(o["n_held"]), list(m["n_held"]), np.array2string(m["eigenvalues"][:, 0], precision=2)), file=sys.stderr)
@@ -399,7 +425,7 @@ def main():
     if args.dump_poses:
         np.save(args.dump_poses, est)
     print(json.dumps({"mode": args.mode, "world": args.world, "beams": args.beams, "keep_clouds": bool(args.keep_clouds), "scans": args.scans, "reference_quirks": bool(args.reference_quirks), "imu": bool(args.imu),
-                      "map_window": args.map_window, "degeneracy": args.degeneracy, "load_map": args.load_map, "save_map": args.save_map,
+                      "map_window": args.map_window, "degeneracy": args.degeneracy, "reject": args.reject, "load_map": args.load_map, "save_map": args.save_map,
                       "ate_rmse_m": ate(est, truth),
                       "final_error_m_rad": synth.pose_error(est[-1], truth[-1]), "ms_per_scan_end_to_end": ms,
                       "scans_per_s": 1e3 / ms if ms else None,

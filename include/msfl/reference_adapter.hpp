@@ -31,6 +31,8 @@
 //   msfl::adapter::SetPosePrior(h, &prior_record, predicted_pose, sqrt_information)  before MatchScan2Map;  ClearPosePrior(h) after
 // and, for the degenerate geometry the reference steps through ("lidar trajectory will drift in illed situation", :84):
 //   msfl::adapter::SetDegeneracy(h, &degeneracy_record, min_eigenvalue)  once;  ClearDegeneracy(h) to switch it off
+// and, against correspondences that are simply wrong (moved objects; the reference's commented-out RefineByRejectOutliersWithThreshold):
+//   msfl::adapter::SetOutlierRejection(h, &rejection_record, MSFL_REJECT_THRESHOLD, 0.2)  once;  ClearOutlierRejection(h) to switch it off
 // and, for a health figure of a registration or the verification of a candidate pose against the map of the last MatchScan2Map:
 //   msfl::adapter::ScorePoses(h, scan_curr, poses, max_dist) -> std::vector<PoseScore> (Fitness(n_features), Rmse())
 #pragma once
@@ -334,6 +336,21 @@ inline void SetDegeneracy(msfl_handle* h, msfl_degeneracy_record* record, double
   Check(msfl_set_degeneracy(h, 1, min_eigenvalue, record, record ? 1 : 0, MSFL_MEM_HOST), h, "msfl_set_degeneracy");
 }
 inline void ClearDegeneracy(msfl_handle* h) { Check(msfl_set_degeneracy(h, 0, 0.0, nullptr, 0, MSFL_MEM_HOST), h, "msfl_set_degeneracy"); }
+
+// ---- outlier rejection in front of the solve (msfl_set_outlier_rejection).  mode MSFL_REJECT_THRESHOLD: `value` is the residual norm
+// above which a correspondence goes (the reference's constant: 0.2); MSFL_REJECT_FRACTION: the fraction of a scan's correspondences
+// that goes.  `record` (may be null) receives the last call's msfl_rejection_record and must outlive the handle's matcher calls.
+inline void SetOutlierRejection(msfl_handle* h, msfl_rejection_record* record, int mode, double value, int which = MSFL_REJECT_LAST_OUTER) {
+  msfl_outlier_rejection cfg{};
+  cfg.mode = mode;
+  cfg.threshold = mode == MSFL_REJECT_THRESHOLD ? value : 0.0;
+  cfg.fraction = mode == MSFL_REJECT_FRACTION ? value : 0.0;
+  cfg.which = which;
+  Check(msfl_set_outlier_rejection(h, &cfg, record, record ? 1 : 0, MSFL_MEM_HOST), h, "msfl_set_outlier_rejection");
+}
+inline void ClearOutlierRejection(msfl_handle* h) {
+  Check(msfl_set_outlier_rejection(h, nullptr, nullptr, 0, MSFL_MEM_HOST), h, "msfl_set_outlier_rejection");
+}
 
 // covariance (row-major 6 x 6, symmetric positive definite, tangent order [dt, dtheta]) -> L with L^T L = covariance^-1: the
 // inverse of the lower Cholesky factor C of the covariance (covariance = C C^T, so its inverse is C^-T C^-1).  Host side, a few

@@ -168,6 +168,12 @@ class ScanMatcher {
   void SetDegeneracy(double min_eigenvalue) { adapter::SetDegeneracy(h_, &degen_, min_eigenvalue); }
   void ClearDegeneracy() { adapter::ClearDegeneracy(h_); degen_ = msfl_degeneracy_record{}; }
   const msfl_degeneracy_record& last_degeneracy() const { return degen_; }
+  // Opt-in: outlier rejection in front of the solve (msfl_set_outlier_rejection).  mode MSFL_REJECT_THRESHOLD: correspondences whose
+  // loss-free residual norm exceeds `value` go (the reference's commented-out call uses 0.2); MSFL_REJECT_FRACTION: the `value`
+  // largest share of every scan's.  last_rejection() is the last call's record.
+  void SetOutlierRejection(int mode, double value, int which = MSFL_REJECT_LAST_OUTER) { adapter::SetOutlierRejection(h_, &reject_, mode, value, which); }
+  void ClearOutlierRejection() { adapter::ClearOutlierRejection(h_); reject_ = msfl_rejection_record{}; }
+  const msfl_rejection_record& last_rejection() const { return reject_; }
 
  protected:
   msfl_handle* h_ = nullptr;
@@ -175,6 +181,7 @@ class ScanMatcher {
   msfl_match_uncertainty unc_{};
   msfl_pose_prior prior_{};
   msfl_degeneracy_record degen_{};
+  msfl_rejection_record reject_{};
 };
 
 // L with L^T L = covariance^-1 for SetPosePrior (6 x 6 Cholesky of the inverse, host side); throws when `covariance` is not

@@ -160,6 +160,25 @@ typedef struct msfl_degeneracy_record {
   int valid[2];                /* 0: no solve ran, the slice is all zero */
 } msfl_degeneracy_record;
 
+/* Outlier rejection in front of the solve (opt-in: msfl_set_outlier_rejection / msfl_slam_set_outlier_rejection;
+   docs/kernels/rejection.md).  The reference's hooks are RefineByRejectOutliersWithThreshold / ...WithFrac (scan_matcher.cc:13-76). */
+enum { MSFL_REJECT_OFF = 0, MSFL_REJECT_THRESHOLD = 1, MSFL_REJECT_FRACTION = 2 };   /* msfl_outlier_rejection.mode */
+enum { MSFL_REJECT_LAST_OUTER = 0, MSFL_REJECT_EVERY_OUTER = 1 };                    /* msfl_outlier_rejection.which */
+typedef struct msfl_outlier_rejection {
+  int mode;          /* MSFL_REJECT_OFF / _THRESHOLD / _FRACTION */
+  double threshold;  /* THRESHOLD: a correspondence goes unless its loss-free residual norm is <= threshold (reference: 0.2) */
+  double fraction;   /* FRACTION: the ceil(n * fraction) correspondences of a scan with the largest residual norm go; in [0, 1] */
+  int which;         /* MSFL_REJECT_LAST_OUTER (the reference's choice): before the last outer iteration's solve only; _EVERY_OUTER */
+} msfl_outlier_rejection;
+/* Per-solve record of the rejection; index = outer iteration, as in msfl_match_info.  56 bytes. */
+typedef struct msfl_rejection_record {
+  int n_edge_in[2], n_plane_in[2];              /* correspondences entering the solve, before rejection */
+  int n_edge_rejected[2], n_plane_rejected[2];  /* of them rejected */
+  double cut_sq[2];  /* squared residual norm at the cut: threshold^2 (THRESHOLD), the smallest rejected one (FRACTION; NaN if that
+                        one is not finite); 0 when nothing was rejected */
+  int valid[2];      /* 0: rejection did not run in front of that solve, the slice is all zero */
+} msfl_rejection_record;
+
 /* Accumulated GPU time per kernel class, measured with HIP events on the handle's stream
    (enabled by msfl_set_timing).  Used by bench.py for the live roofline figure. */
 typedef struct msfl_timing {
@@ -245,6 +264,24 @@ msfl_status msfl_set_pose_prior(msfl_handle* h, const msfl_pose_prior* priors, i
    non-finite min_eigenvalue.  The uncertainty output keeps its meaning: the full information at the returned pose. */
 msfl_status msfl_set_degeneracy(msfl_handle* h, int enabled, double min_eigenvalue, msfl_degeneracy_record* out, int capacity,
                                 msfl_mem mem);
+
+/* Outlier rejection, off by default; cfg == NULL or cfg->mode == MSFL_REJECT_OFF turns it off.  Otherwise, in every later matcher
+   call on this handle (the calls msfl_set_uncertainty lists), the selected solves (cfg->which; msfl_solve_records has one solve,
+   which both values select) are preceded by a pass over the scan's correspondences at the solve's entry pose, all on the device:
+     s = |N x (R p + t - C)|^2 for an edge, (N.(R p + t) - N.C)^2 for a plane, in f64 and without the loss;
+     THRESHOLD : a correspondence is rejected iff !(s <= threshold^2), so one with a non-finite s goes;
+     FRACTION  : with n the scan's correspondences of both kinds, the k = ceil(n * fraction) of them with the largest s go (the
+                 product in double: n = 100, fraction = 0.07 rejects 8).  Equal s: the higher index goes first, corner features
+                 numbered before surf features; a non-finite s ranks above every finite one.
+   A rejected correspondence is from there on one that association refused: n_edge / n_plane of msfl_match_info count the
+   survivors, odom_min_correspondences and the empty-problem rule apply to the survivors, and the uncertainty record is the
+   information of the survivors.  A scan whose status is not 0 is skipped.
+   `out` may be NULL (rejection still runs); otherwise one record per registration goes to out[0 .. n) with the memory kinds,
+   the MSFL_CAPACITY rule and "a failing call writes nothing" of msfl_set_uncertainty.  MSFL_BAD_ARG for an unknown mode or
+   `which`, a negative or non-finite threshold, or a fraction outside [0, 1].  With the feature off nothing is launched, staged
+   or allocated and every output is bit-identical to what it was without this call. */
+msfl_status msfl_set_outlier_rejection(msfl_handle* h, const msfl_outlier_rejection* cfg, msfl_rejection_record* out, int capacity,
+                                       msfl_mem mem);
 
 /* ------------------------------------------------------------------------------------------ */
 /* stage C — scan-to-local-map registration                                                   */
@@ -842,6 +879,15 @@ msfl_status msfl_slam_set_degeneracy(msfl_slam* s, int odometry, int mapping, do
    pointer may be NULL; MSFL_BAD_ARG for a scan that was fed while both switches were off).  A matcher that was off, or did not
    run, leaves its record all zero. */
 msfl_status msfl_slam_get_degeneracy(msfl_slam* s, int scan_index, msfl_degeneracy_record* odometry, msfl_degeneracy_record* mapping);
+
+/* Outlier rejection (msfl_set_outlier_rejection) of the two registrations of every scan fed from now on: `odometry` configures
+   MatchScan2Scan's solves, `mapping` MatchScan2Map's; NULL (or mode MSFL_REJECT_OFF) leaves that matcher without it.  The
+   reference tests odom_min_correspondences before its (commented-out) rejection call; here the survivors decide.
+   MSFL_BAD_ARG under the rules of msfl_set_outlier_rejection. */
+msfl_status msfl_slam_set_outlier_rejection(msfl_slam* s, const msfl_outlier_rejection* odometry, const msfl_outlier_rejection* mapping);
+/* The records of scan `scan_index`, under the rules of msfl_slam_get_degeneracy (MSFL_BAD_ARG for a scan that was fed while both
+   matchers had the feature off).  A matcher that was off, or did not run, leaves its record all zero. */
+msfl_status msfl_slam_get_rejection(msfl_slam* s, int scan_index, msfl_rejection_record* odometry, msfl_rejection_record* mapping);
 
 /* Pose priors for the NEXT msfl_slam_add_scan[_imu] only (host pointers, copied here; either may be NULL = none):
      odometry : on that scan's MatchScan2Scan, whose unknown is the RELATIVE pose pose_curr2last;

@@ -33,6 +33,7 @@ EXPORTED = [
     "msfl_set_uncertainty", "msfl_slam_set_uncertainty", "msfl_slam_get_uncertainty",
     "msfl_set_pose_prior", "msfl_slam_set_next_prior",
     "msfl_set_degeneracy", "msfl_slam_set_degeneracy", "msfl_slam_get_degeneracy",
+    "msfl_set_outlier_rejection", "msfl_slam_set_outlier_rejection", "msfl_slam_get_rejection",
     "msfl_score_poses", "msfl_score_poses_batch",
 ]
 
@@ -100,6 +101,36 @@ class DegeneracyRecord(C.Structure):
 DEGENERACY_DTYPE = np.dtype([("eigenvalues", np.float64, (2, 6)), ("eigenvectors", np.float64, (2, 6, 6)), ("n_held", np.int32, (2,)),
                              ("valid", np.int32, (2,))])
 assert DEGENERACY_DTYPE.itemsize == C.sizeof(DegeneracyRecord) == 688
+
+
+REJECT_OFF, REJECT_THRESHOLD, REJECT_FRACTION = 0, 1, 2          # msfl_outlier_rejection.mode
+REJECT_LAST_OUTER, REJECT_EVERY_OUTER = 0, 1                      # msfl_outlier_rejection.which
+
+
+class OutlierRejection(C.Structure):
+    """msfl_outlier_rejection: mode, threshold (THRESHOLD), fraction (FRACTION) and the solves it runs in front of."""
+    _fields_ = [("mode", C.c_int), ("threshold", C.c_double), ("fraction", C.c_double), ("which", C.c_int)]
+
+
+class RejectionRecord(C.Structure):
+    """msfl_rejection_record: per outer iteration the correspondences entering the solve, those rejected and the cut."""
+    _fields_ = [("n_edge_in", C.c_int * 2), ("n_plane_in", C.c_int * 2), ("n_edge_rejected", C.c_int * 2), ("n_plane_rejected", C.c_int * 2),
+                ("cut_sq", C.c_double * 2), ("valid", C.c_int * 2)]
+
+
+# the same record as a numpy structured dtype (Handle.rejection, Slam.get_rejection)
+REJECTION_DTYPE = np.dtype([("n_edge_in", np.int32, (2,)), ("n_plane_in", np.int32, (2,)), ("n_edge_rejected", np.int32, (2,)),
+                            ("n_plane_rejected", np.int32, (2,)), ("cut_sq", np.float64, (2,)), ("valid", np.int32, (2,))])
+assert REJECTION_DTYPE.itemsize == C.sizeof(RejectionRecord) == 56
+
+
+def outlier_rejection(threshold=None, fraction=None, which=REJECT_LAST_OUTER):
+    """The msfl_outlier_rejection of exactly one of `threshold` (metres) and `fraction` (of a scan's correspondences)."""
+    if (threshold is None) == (fraction is None):
+        raise ValueError("give exactly one of threshold and fraction")
+    if threshold is not None:
+        return OutlierRejection(REJECT_THRESHOLD, float(threshold), 0.0, int(which))
+    return OutlierRejection(REJECT_FRACTION, 0.0, float(fraction), int(which))
 
 
 class PoseScore(C.Structure):
@@ -379,6 +410,36 @@ class Handle:
     def clear_degeneracy(self):
         self._check(self.lib.msfl_set_degeneracy(self.h, C.c_int(0), C.c_double(0.0), None, C.c_int(0), C.c_int(MEM_HOST)), "msfl_set_degeneracy")
         self._degen = None
+
+    # ---- outlier rejection in front of the solve (msfl_set_outlier_rejection) ----
+    def set_outlier_rejection(self, threshold=None, fraction=None, which=REJECT_LAST_OUTER, n=0):
+        """Every later matcher call rejects correspondences in front of the selected solves: those whose loss-free residual norm exceeds
+        `threshold`, or the ceil(n * fraction) largest of each scan.  n > 0: one msfl_rejection_record per registration goes to a host
+        buffer of `n` records owned by this object (read it with rejection())."""
+        cfg = outlier_rejection(threshold, fraction, which)
+        buf = np.zeros(int(n), REJECTION_DTYPE) if n else None
+        self._check(self.lib.msfl_set_outlier_rejection(self.h, C.byref(cfg), _vp(buf), C.c_int(int(n) if n else 0), C.c_int(MEM_HOST)),
+                    "msfl_set_outlier_rejection")
+        self._reject = buf
+
+    def set_outlier_rejection_device(self, ptr, capacity, threshold=None, fraction=None, which=REJECT_LAST_OUTER):
+        """Device-pointer sink: `ptr` (torch tensor / raw pointer) holds `capacity` records of REJECTION_DTYPE.itemsize bytes, written
+        asynchronously on the handle's stream."""
+        cfg = outlier_rejection(threshold, fraction, which)
+        self._check(self.lib.msfl_set_outlier_rejection(self.h, C.byref(cfg), _vp(ptr), C.c_int(int(capacity)), C.c_int(MEM_DEVICE)),
+                    "msfl_set_outlier_rejection(device)")
+        self._reject = None
+
+    def clear_outlier_rejection(self):
+        self._check(self.lib.msfl_set_outlier_rejection(self.h, None, None, C.c_int(0), C.c_int(MEM_HOST)), "msfl_set_outlier_rejection")
+        self._reject = None
+
+    def rejection(self, n=None):
+        """The first `n` records (default: all) the last matcher call wrote, as a copy of the numpy structured array."""
+        buf = getattr(self, "_reject", None)
+        if buf is None:
+            raise RuntimeError("no rejection record sink: call set_outlier_rejection(..., n=n) first")
+        return buf[:len(buf) if n is None else int(n)].copy()
 
     def degeneracy(self, n=None):
         """The first `n` records (default: all) the last matcher call wrote, as a copy of the numpy structured array."""
@@ -1006,6 +1067,22 @@ class Slam:
                                                C.c_double(0.0 if mapping is None else float(mapping)))
         if st != OK:
             raise MsflError(st, "msfl_slam_set_degeneracy", self._err())
+
+    def set_outlier_rejection(self, odometry=None, mapping=None):
+        """Outlier rejection of every scan fed from now on: `odometry` / `mapping` is that matcher's OutlierRejection
+        (capi.outlier_rejection(...)), None leaves it off."""
+        st = self.lib.msfl_slam_set_outlier_rejection(self.s, None if odometry is None else C.byref(odometry),
+                                                      None if mapping is None else C.byref(mapping))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_set_outlier_rejection", self._err())
+
+    def get_rejection(self, scan_index):
+        """(odometry, mapping) records of REJECTION_DTYPE of one of the last four scans fed (waits for it)."""
+        out = np.zeros(2, REJECTION_DTYPE)
+        st = self.lib.msfl_slam_get_rejection(self.s, C.c_int(int(scan_index)), C.c_void_p(out[0:1].ctypes.data), C.c_void_p(out[1:2].ctypes.data))
+        if st != OK:
+            raise MsflError(st, "msfl_slam_get_rejection", self._err())
+        return out[0], out[1]
 
     def get_degeneracy(self, scan_index):
         """(odometry, mapping) records of DEGENERACY_DTYPE of one of the last four scans fed (waits for it)."""

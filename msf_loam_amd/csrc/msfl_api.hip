@@ -32,6 +32,7 @@
 #include "msfl_deskew.cuh"
 #include "msfl_uncertainty.cuh"
 #include "msfl_degeneracy.cuh"
+#include "msfl_reject.cuh"
 
 using namespace msfl;
 
@@ -202,6 +203,15 @@ struct msfl_handle_s {
   int degen_capacity = 0;
   msfl_mem degen_mem = MSFL_MEM_HOST;
   DevBuf degen_dev;                       // device staging of a host sink
+  // msfl_set_outlier_rejection: records are rejected between association and solve (mode MSFL_REJECT_OFF: feature off)
+  int rej_mode = MSFL_REJECT_OFF;
+  double rej_thr2 = 0.0, rej_fraction = 0.0;     // threshold squared; fraction
+  int rej_which = MSFL_REJECT_LAST_OUTER;
+  msfl_rejection_record* rej_out = nullptr;      // optional sink, one record per registration
+  int rej_capacity = 0;
+  msfl_mem rej_mem = MSFL_MEM_HOST;
+  DevBuf rej_dev;                         // device staging of a host sink
+  DevBuf rej_keys;                        // fraction mode: one u64 per record of the call
 
   PinRing pin;
   PinBuf readback;
@@ -299,6 +309,7 @@ static_assert(sizeof(UncRecord) == sizeof(msfl_match_uncertainty), "uncertainty 
 static_assert(sizeof(PosePrior) == sizeof(msfl_pose_prior), "pose prior record layout");
 static_assert(sizeof(DevMatchInfo) == sizeof(msfl_match_info), "info layout");
 static_assert(sizeof(DegenRecord) == sizeof(msfl_degeneracy_record), "degeneracy record layout");
+static_assert(sizeof(RejectRecord) == sizeof(msfl_rejection_record) && sizeof(RejectRecord) == 56, "rejection record layout");
 struct RegSinks {
   DevMatchInfo* info = nullptr;      // never null when `unc` is not: the uncertainty record takes sigma2 from the solve's own final cost
   UncRecord* unc = nullptr;          // null: feature off
@@ -307,9 +318,13 @@ struct RegSinks {
   int degen_on = 0;                  // msfl_set_degeneracy: 0 = feature off
   double degen_min_eig = 0.0;
   DegenRecord* degen = nullptr;      // optional record sink of the feature (zeroed before the first solve)
+  int rej_mode = MSFL_REJECT_OFF;    // msfl_set_outlier_rejection: MSFL_REJECT_OFF = feature off
+  double rej_thr2 = 0.0, rej_fraction = 0.0;
+  int rej_which = MSFL_REJECT_LAST_OUTER;
+  RejectRecord* rej = nullptr;       // optional record sink of the feature (zeroed before the first solve)
   RegSinks at(int b) const {         // a part of a batch
     return {info ? info + b : nullptr, unc ? unc + b : nullptr, prior ? prior + b : nullptr, unc_min_eig, degen_on, degen_min_eig,
-            degen ? degen + b : nullptr};
+            degen ? degen + b : nullptr, rej_mode, rej_thr2, rej_fraction, rej_which, rej ? rej + b : nullptr};
   }
 };
 
@@ -323,6 +338,9 @@ msfl_status reg_check(msfl_handle* h, int n, const char* who) {
   if (h->degen_on && h->degen_out && n > h->degen_capacity)
     return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_degeneracy sink holds " +
                                       std::to_string(h->degen_capacity));
+  if (h->rej_mode != MSFL_REJECT_OFF && h->rej_out && n > h->rej_capacity)
+    return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_outlier_rejection sink holds " +
+                                      std::to_string(h->rej_capacity));
   if (!h->prior_in) return MSFL_OK;
   if (n > h->prior_count)
     return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, msfl_set_pose_prior gave " +
@@ -341,6 +359,7 @@ msfl_status reg_check(msfl_handle* h, int n, const char* who) {
 
 inline bool unc_host(const msfl_handle* h) { return h->unc_out && h->unc_mem == MSFL_MEM_HOST; }
 inline bool degen_host(const msfl_handle* h) { return h->degen_on && h->degen_out && h->degen_mem == MSFL_MEM_HOST; }
+inline bool rej_host(const msfl_handle* h) { return h->rej_mode != MSFL_REJECT_OFF && h->rej_out && h->rej_mem == MSFL_MEM_HOST; }
 
 // Where the kernels of this call of n registrations find their sinks: the caller's device pointers, or device staging of its host ones
 // (the prior records are copied on stream st, ahead of the clearing of the info records).  want_info: the caller asked for the info records.
@@ -369,6 +388,16 @@ msfl_status reg_open(msfl_handle* h, int n, hipStream_t st, bool want_info, RegS
     // the solve kernel writes a slice only where it solves: every other slice stays all zero (valid = 0)
     if (k->degen && n > 0) HIPCHK(h, hipMemsetAsync(k->degen, 0, (size_t)n * sizeof(DegenRecord), st));
   }
+  if (h->rej_mode != MSFL_REJECT_OFF) {
+    k->rej_mode = h->rej_mode; k->rej_thr2 = h->rej_thr2; k->rej_fraction = h->rej_fraction; k->rej_which = h->rej_which;
+    if (h->rej_out && h->rej_mem == MSFL_MEM_DEVICE) k->rej = reinterpret_cast<RejectRecord*>(h->rej_out);
+    else if (h->rej_out) {
+      HIPCHK(h, h->rej_dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(RejectRecord)));
+      k->rej = h->rej_dev.as<RejectRecord>();
+    }
+    // the kernels write a slice only where a solve follows: every other slice stays all zero (valid = 0)
+    if (k->rej && n > 0) HIPCHK(h, hipMemsetAsync(k->rej, 0, (size_t)n * sizeof(RejectRecord), st));
+  }
   if (want_info || k->unc) {
     HIPCHK(h, h->info.reserve((size_t)n * sizeof(DevMatchInfo)));
     HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)n * sizeof(DevMatchInfo), st));
@@ -390,19 +419,27 @@ msfl_status reg_close(msfl_handle* h, int n, msfl_mem mem, double* poses_io, con
   if (unc_host(h) && k.unc && n > 0) HIPCHK(h, hipMemcpyAsync(h->unc_out, k.unc, (size_t)n * sizeof(UncRecord), hipMemcpyDeviceToHost, st));
   if (degen_host(h) && k.degen && n > 0)
     HIPCHK(h, hipMemcpyAsync(h->degen_out, k.degen, (size_t)n * sizeof(DegenRecord), hipMemcpyDeviceToHost, st));
-  if (mem == MSFL_MEM_HOST || info || unc_host(h) || degen_host(h)) HIPCHK(h, hipStreamSynchronize(st));
+  if (rej_host(h) && k.rej && n > 0)
+    HIPCHK(h, hipMemcpyAsync(h->rej_out, k.rej, (size_t)n * sizeof(RejectRecord), hipMemcpyDeviceToHost, st));
+  if (mem == MSFL_MEM_HOST || info || unc_host(h) || degen_host(h) || rej_host(h)) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 
 // The outer loop of every registration: per outer iteration the site's own association launches (`assoc(it)`, which may fail), then the
 // LM solve of all n problems; after the last one the uncertainty records, if asked for.  BLOCK: the site's solve workgroup.
+// With msfl_set_outlier_rejection the selected solves are preceded by the rejection launch over the records association just wrote
+// (msfl_reject.cuh); longest: records of the call's longest scan, for that launch's grid (< 0: bv.n_records, a bound).
 template <int BLOCK, class Assoc>
 msfl_status solve_outer(msfl_handle* h, int n, const BatchView& bv, const double* pprime, double* d_poses, int* d_status, const RegSinks& k,
-                        const SolverParams& sp, int n_outer, Assoc&& assoc) {
+                        const SolverParams& sp, int n_outer, Assoc&& assoc, int longest = -1) {
   hipStream_t st = h->stream;
   const double* records = h->records.as<double>();
+  if (k.rej_mode == MSFL_REJECT_FRACTION) HIPCHK(h, h->rej_keys.reserve(std::max<size_t>(1, (size_t)bv.n_records) * sizeof(unsigned long long)));
   for (int it = 0; it < n_outer; it++) {
     { const msfl_status as = assoc(it); if (as) return as; }
+    if (k.rej_mode != MSFL_REJECT_OFF && (k.rej_which == MSFL_REJECT_EVERY_OUTER || it == n_outer - 1))
+      launch_reject(st, k.rej_mode, n, longest < 0 ? bv.n_records : longest, bv, pprime, h->records.as<double>(), d_poses, d_status, k.rej, it,
+                    k.rej_thr2, k.rej_fraction, h->rej_keys.as<unsigned long long>());
     ScopedTimer timer(h, T_SOLVE);
     launch_lm_solve<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, it, sp, k.prior, k.degen_on, k.degen_min_eig, k.degen);
   }
@@ -637,6 +674,8 @@ msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner,
     dv.pprime = h->pprime.as<double>();
   }
   const auto rec_at = [&](int b) { return h_corner_off[b] - h_corner_off[0] + h_surf_off[b] - h_surf_off[0]; };   // rec_off[b]
+  int longest = 0;
+  for (int b = 0; b < B; b++) longest = std::max(longest, rec_at(b + 1) - rec_at(b));
   return solve_outer<kLmBlock>(h, B, bv, dv.pprime, d_poses, d_status, sinks, solver_params(h->prm, 0), h->prm.outer_iterations, [&](int it) -> msfl_status {
     if (it == 0 && (n_chunks > 1 || enqueue_chunk)) {
       for (int c = 0; c < n_chunks; c++) {
@@ -650,7 +689,7 @@ msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner,
       s_launch_assoc(h, bv, d_poses, d_status, deskew != nullptr, dv, n_rec, nullptr, 0, -1, it > 0);
     }
     return MSFL_OK;
-  });
+  }, longest);
 }
 
 msfl_status check_map(msfl_handle* h) {
@@ -809,6 +848,31 @@ msfl_status msfl_set_degeneracy(msfl_handle* h, int enabled, double min_eigenval
   h->degen_out = enabled ? out : nullptr;
   h->degen_capacity = enabled && out ? capacity : 0;
   h->degen_mem = mem;
+  return MSFL_OK;
+}
+
+msfl_status msfl_set_outlier_rejection(msfl_handle* h, const msfl_outlier_rejection* cfg, msfl_rejection_record* out, int capacity, msfl_mem mem) {
+  msfl_status s = enter(h); if (s) return s;
+  const bool on = cfg && cfg->mode != MSFL_REJECT_OFF;
+  if (on) {
+    if (cfg->mode != MSFL_REJECT_THRESHOLD && cfg->mode != MSFL_REJECT_FRACTION)
+      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: unknown mode");
+    if (cfg->which != MSFL_REJECT_LAST_OUTER && cfg->which != MSFL_REJECT_EVERY_OUTER)
+      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: `which` is neither MSFL_REJECT_LAST_OUTER nor MSFL_REJECT_EVERY_OUTER");
+    if (cfg->mode == MSFL_REJECT_THRESHOLD && (!(cfg->threshold >= 0.0) || !std::isfinite(cfg->threshold)))
+      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: threshold negative or not finite");
+    if (cfg->mode == MSFL_REJECT_FRACTION && !(cfg->fraction >= 0.0 && cfg->fraction <= 1.0))
+      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: fraction outside [0, 1]");
+    if (out && (capacity < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE)))
+      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: capacity < 1 or unknown memory kind");
+  }
+  h->rej_mode = on ? cfg->mode : MSFL_REJECT_OFF;
+  h->rej_thr2 = on && cfg->mode == MSFL_REJECT_THRESHOLD ? cfg->threshold * cfg->threshold : 0.0;
+  h->rej_fraction = on && cfg->mode == MSFL_REJECT_FRACTION ? cfg->fraction : 0.0;
+  h->rej_which = on ? cfg->which : MSFL_REJECT_LAST_OUTER;
+  h->rej_out = on ? out : nullptr;
+  h->rej_capacity = on && out ? capacity : 0;
+  h->rej_mem = mem;
   return MSFL_OK;
 }
 

@@ -142,6 +142,8 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
   const BatchView bv = batch_view(d_corner, d_surf, h->in_off.as<int>(), P + 1, P, n_rec, co[0], so[0], so[P] - so[0]);
   DeskewView dv{};
   const dim3 grid(std::max(1, div_up(n_rec, kAssocBlock))), block(kAssocBlock);
+  int longest = 0;
+  for (int p = 0; p < P; p++) longest = std::max(longest, (co[p + 1] - co[p]) + (so[p + 1] - so[p]));
   s = solve_outer<kLmBlock>(h, P, bv, nullptr, d_poses, d_status, sinks, solver_params(h->prm, 0), h->prm.outer_iterations, [&](int it) {
     if (n_rec <= 0) return MSFL_OK;
     {
@@ -153,7 +155,7 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
     hipLaunchKernelGGL(fit_scan2map_kernel<false>, grid, block, 0, st, bv, h->map_c.sorted.as<float4>(), h->map_s.sorted.as<float4>(),
                        (const int*)h->nn.as<int>(), h->prm.line_eigen_ratio, h->prm.plane_tolerance, dv, h->records.as<double>(), (double*)nullptr);
     return MSFL_OK;
-  });
+  }, longest);
   if (s) return s;
   return reg_close(h, P, mem, poses_io, d_poses, status, d_status, info, sinks);
 }

@@ -35,7 +35,7 @@ struct SlamScanBuf {                    // everything derived from ONE scan that
 };
 
 constexpr int kSlamSlots = 4;
-struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; bool prior_map; bool crop; int half[3]; bool degen, degen_map; double degen_map_min_eig; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
+struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; bool prior_map; bool crop; int half[3]; bool degen, degen_map; double degen_map_min_eig; bool rej; msfl_outlier_rejection rej_map; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
 constexpr int kSlamProfileSkip = 20;                    // MSFL_SLAM_HOST_PROFILE leaves the first scans (allocations) out
 #ifndef MSFL_SLAM_ODOM_LANES
 #define MSFL_SLAM_ODOM_LANES 64
@@ -85,6 +85,12 @@ struct msfl_slam_s {
   DevBuf degen[kSlamSlots];
   PinBuf degen_host;                    // kSlamSlots x 2 records
   bool degen_held[kSlamSlots] = {};     // the scan in this slot was fed with the feature on (either matcher)
+  // msfl_slam_set_outlier_rejection: the two matchers' configurations {odometry, mapping} (mode MSFL_REJECT_OFF: off); two
+  // msfl_rejection_record per slot, which travel with the slot's result copy like the degeneracy records
+  msfl_outlier_rejection rej_cfg[2] = {};
+  DevBuf rej[kSlamSlots];
+  PinBuf rej_host;                      // kSlamSlots x 2 records
+  bool rej_held[kSlamSlots] = {};       // the scan in this slot was fed with the feature on (either matcher)
   // msfl_slam_set_next_prior: {odometry, mapping} records for the NEXT scan only.  They are copied to the slot of the scan that
   // consumes them (on its odometry stream, ahead of ev_odo), so a later msfl_slam_add_scan cannot overwrite what a queued
   // mapping chain has not read yet: a slot is reused only after its scan's record is out.
@@ -510,6 +516,43 @@ msfl_status msfl_slam_get_degeneracy(msfl_slam* s, int scan_index, msfl_degenera
   return MSFL_OK;
 }
 
+msfl_status msfl_slam_set_outlier_rejection(msfl_slam* s, const msfl_outlier_rejection* odometry, const msfl_outlier_rejection* mapping) {
+  if (!s) return MSFL_BAD_ARG;
+  const msfl_outlier_rejection* in[2] = {odometry, mapping};
+  msfl_outlier_rejection cfg[2] = {};
+  for (int a = 0; a < 2; a++) {
+    if (!in[a] || in[a]->mode == MSFL_REJECT_OFF) continue;
+    const msfl_outlier_rejection& c = *in[a];
+    if ((c.mode != MSFL_REJECT_THRESHOLD && c.mode != MSFL_REJECT_FRACTION) || (c.which != MSFL_REJECT_LAST_OUTER && c.which != MSFL_REJECT_EVERY_OUTER))
+      return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_outlier_rejection: unknown mode or `which`");
+    if (c.mode == MSFL_REJECT_THRESHOLD && !(c.threshold >= 0.0 && std::isfinite(c.threshold)))
+      return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_outlier_rejection: a threshold is negative or not finite");
+    if (c.mode == MSFL_REJECT_FRACTION && !(c.fraction >= 0.0 && c.fraction <= 1.0))
+      return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_outlier_rejection: a fraction is outside [0, 1]");
+    cfg[a] = c;
+  }
+  SHIP(s, hipSetDevice(s->ho->device));
+  if ((cfg[0].mode || cfg[1].mode) && !s->rej_host.p) {
+    for (auto& b : s->rej) SHIP(s, b.reserve(2 * sizeof(RejectRecord)));
+    SHIP(s, s->rej_host.reserve(kSlamSlots * 2 * sizeof(RejectRecord)));
+  }
+  s->rej_cfg[0] = cfg[0];               // read once per msfl_slam_add_scan, like msfl_slam_set_degeneracy
+  s->rej_cfg[1] = cfg[1];
+  return MSFL_OK;
+}
+
+msfl_status msfl_slam_get_rejection(msfl_slam* s, int scan_index, msfl_rejection_record* odometry, msfl_rejection_record* mapping) {
+  if (!s) return MSFL_BAD_ARG;
+  int slot;
+  { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_rejection", &slot); if (rs) return rs; }
+  if (!s->rej_held[slot]) return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_rejection: that scan was fed with msfl_slam_set_outlier_rejection off");
+  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
+  const msfl_rejection_record* d = s->rej_host.as<msfl_rejection_record>() + 2 * slot;
+  if (odometry) *odometry = d[0];
+  if (mapping) *mapping = d[1];
+  return MSFL_OK;
+}
+
 msfl_status msfl_slam_set_next_prior(msfl_slam* s, const msfl_pose_prior* odometry, const msfl_pose_prior* mapping) {
   if (!s) return MSFL_BAD_ARG;
   const msfl_pose_prior* in[2] = {odometry, mapping};
@@ -688,7 +731,9 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   // the slot's second records are the mapping match's (the prior was uploaded ahead of cur.ev_odo)
   const RegSinks map_sinks{reinterpret_cast<DevMatchInfo*>(&rec->mapping), jb.unc ? s->unc[slot].as<UncRecord>() + 1 : nullptr,
                            jb.prior_map ? s->prior[slot].as<PosePrior>() + 1 : nullptr, jb.unc_min_eig,
-                           jb.degen_map ? 1 : 0, jb.degen_map_min_eig, jb.degen_map ? s->degen[slot].as<DegenRecord>() + 1 : nullptr};
+                           jb.degen_map ? 1 : 0, jb.degen_map_min_eig, jb.degen_map ? s->degen[slot].as<DegenRecord>() + 1 : nullptr,
+                           jb.rej_map.mode, jb.rej_map.threshold * jb.rej_map.threshold, jb.rej_map.fraction, jb.rej_map.which,
+                           jb.rej_map.mode ? s->rej[slot].as<RejectRecord>() + 1 : nullptr};
   const SlamImuDev* d_imu = cur.imu.as<SlamImuDev>();
   const int cap_ls = std::min(n, s->caps.less_sharp), cap_lf = std::min(n, s->caps.less_flat);
   double* chain = s->chain.as<double>();
@@ -776,6 +821,8 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
     SHIP(s, hipMemcpyAsync(s->unc_host.as<UncRecord>() + 2 * slot, s->unc[slot].p, 2 * sizeof(UncRecord), hipMemcpyDeviceToHost, sm));
   if (jb.degen)
     SHIP(s, hipMemcpyAsync(s->degen_host.as<DegenRecord>() + 2 * slot, s->degen[slot].p, 2 * sizeof(DegenRecord), hipMemcpyDeviceToHost, sm));
+  if (jb.rej)
+    SHIP(s, hipMemcpyAsync(s->rej_host.as<RejectRecord>() + 2 * slot, s->rej[slot].p, 2 * sizeof(RejectRecord), hipMemcpyDeviceToHost, sm));
   if (jb.crop)
     SHIP(s, hipMemcpyAsync(s->win_host.as<int>() + 2 * CROP_WORDS * slot, s->win[slot].p, 2 * CROP_WORDS * sizeof(int), hipMemcpyDeviceToHost, sm));
   SHIP(s, hipEventRecord(s->ev_done[slot], sm));
@@ -833,6 +880,10 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   const double degen_odo_min_eig = s->degen_min_eigenvalue[0], degen_map_min_eig = s->degen_min_eigenvalue[1];
   s->degen_held[slot] = degen_odo || degen_map;
   if (degen_odo || degen_map) SHIP(s, hipMemsetAsync(s->degen[slot].p, 0, 2 * sizeof(DegenRecord), so));   // a slice stays zero where no solve runs
+  const msfl_outlier_rejection rej_odo = s->rej_cfg[0], rej_map = s->rej_cfg[1];
+  const bool rej_any = rej_odo.mode != MSFL_REJECT_OFF || rej_map.mode != MSFL_REJECT_OFF;
+  s->rej_held[slot] = rej_any;
+  if (rej_any) SHIP(s, hipMemsetAsync(s->rej[slot].p, 0, 2 * sizeof(RejectRecord), so));   // a slice stays zero where no solve runs
   // msfl_slam_set_next_prior: consumed by this scan, whatever becomes of it
   const bool prior_odo = s->next_prior_set[0], prior_map = s->next_prior_set[1];
   s->next_prior_set[0] = s->next_prior_set[1] = false;
@@ -911,7 +962,9 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   if (k > 0) {                                                   // laser_odometry.cc:72-75: the first scan only initialises
     const RegSinks odo_sinks{reinterpret_cast<DevMatchInfo*>(&rec->odometry), unc ? s->unc[slot].as<UncRecord>() : nullptr,
                              prior_odo ? s->prior[slot].as<PosePrior>() : nullptr, unc_min_eig,
-                             degen_odo ? 1 : 0, degen_odo_min_eig, degen_odo ? s->degen[slot].as<DegenRecord>() : nullptr};
+                             degen_odo ? 1 : 0, degen_odo_min_eig, degen_odo ? s->degen[slot].as<DegenRecord>() : nullptr,
+                             rej_odo.mode, rej_odo.threshold * rej_odo.threshold, rej_odo.fraction, rej_odo.which,
+                             rej_odo.mode ? s->rej[slot].as<RejectRecord>() : nullptr};
     SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, odo_sinks));
   }
   hipLaunchKernelGGL(slam_odom_pose_kernel, dim3(1), dim3(1), 0, so, (const double*)chain, chain + 7, poses_k, poses_k + 14,
@@ -927,7 +980,7 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   }
   const bool crop = s->win_on && (k + 1) % s->win_every == 0;
   s->win_held[slot] = crop;
-  const SlamJob job{k, n, imu_mode, unc, unc_min_eig, prior_map, crop, {s->win_half[0], s->win_half[1], s->win_half[2]}, degen_odo || degen_map, degen_map, degen_map_min_eig};
+  const SlamJob job{k, n, imu_mode, unc, unc_min_eig, prior_map, crop, {s->win_half[0], s->win_half[1], s->win_half[2]}, degen_odo || degen_map, degen_map, degen_map_min_eig, rej_any, rej_map};
   if (s->threaded) {
     std::unique_lock<std::mutex> lk(s->mu);
     s->cv_done.wait(lk, [&] { return !s->has_job; });            // the mapping thread is at most one scan behind

@@ -325,7 +325,7 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
       }
     }
     return MSFL_OK;
-  });
+  }, max_q);
   if (ss) return ss;
   return reg_close(h, B, mem, poses_io, d_poses, status, d_status, info, sinks);
 }
