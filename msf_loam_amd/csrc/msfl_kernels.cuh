@@ -951,36 +951,42 @@ __device__ __noinline__ int tr_propose(TrState& tr, const SolverParams prm) {
 #include "msfl_tr_propose_body.inc"
 #undef MSFL_TR_DEGEN
 }
+// The same text once more, inlined into the one kernel whose launch is a third of the batch step: lm_solve_kernel<128> (see
+// lm_tr_propose below).  The call form stays for every other solve kernel.
+__device__ __forceinline__ int tr_propose_inline(TrState& tr, const SolverParams prm) {
+#define MSFL_TR_DEGEN 0
+#include "msfl_tr_propose_body.inc"
+#undef MSFL_TR_DEGEN
+}
 
 // FunctionToleranceReached / IsStepSuccessful / HandleSuccessfulStep / HandleUnsuccessfulStep,
 // lane 0 only; `red` = {cost, g, H} evaluated at tr.cand.  Returns 1 to continue.
 __device__ __noinline__ int tr_decide(TrState& tr, const double* red, const SolverParams prm) {
-  const double cand_cost = red[0];
-  const double cost_change = tr.cost - cand_cost;
-  if (fabs(cost_change) <= prm.ftol * tr.cost) return 0;
-  const double rel = cost_change / tr.model_cost_change;
-  if (rel > prm.min_relative_decrease) {
-#pragma unroll
-    for (int i = 0; i < 7; i++) tr.x[i] = tr.cand[i];
-#pragma unroll
-    for (int k = 0; k < kAcc; k++) tr.sys[k] = red[k];
-    const pose7 x = load_pose(tr.x);
-    tr.x_norm = pose_norm(x);
-    tr.cost = cand_cost;
-    tr.gmax = gradient_max_norm_for_test(x, tr.sys + 1, prm.gtol);
-    const double t = 2.0 * rel - 1.0;
-    tr.radius = fmin(tr.radius / fmax(1.0 / 3.0, 1.0 - t * t * t), prm.radius_max);
-    tr.decrease_factor = 2.0;
-    tr.reuse_diagonal = 0;
-    tr.step_ok = 1;
-    tr.successful++;
-  } else {
-    tr.radius = tr.radius / tr.decrease_factor;
-    tr.decrease_factor *= 2.0;
-    tr.reuse_diagonal = 1;
-    tr.step_ok = 0;
-  }
-  return 1;
+#include "msfl_tr_decide_body.inc"
+}
+__device__ __forceinline__ int tr_decide_inline(TrState& tr, const double* red, const SolverParams prm) {
+#include "msfl_tr_decide_body.inc"
+}
+
+// MEASURED (profiles/r07_lm_pipeline.md): as calls, the two functions cost lm_solve_kernel<128> 7 % of its launch.  A call makes the
+// compiler wait for every outstanding load in front of it, saves and restores the caller's registers through scratch (376 B per
+// lane, all of the kernel's private segment) and keeps whatever is live across it in the callee-saved half of the register file.
+// Inlined, the kernel has no private segment at all, 255 VGPRs, no spill: 0.1862 -> 0.1725 ms per launch on the bench batch, the
+// results bit for bit the same (tests/test_gpu_lm_pipeline.py).  -DMSFL_LM_TR_INLINE=0 builds the calls everywhere, as before.
+// Only the plain 128-thread kernel takes the inlined form: it is the one that was measured.  The prior and degeneracy siblings and the
+// 512-thread SLAM solve keep the calls (INL = false is the text they always had).
+#ifndef MSFL_LM_TR_INLINE
+#define MSFL_LM_TR_INLINE 1
+#endif
+template <bool INL>
+__device__ __forceinline__ int lm_tr_propose(TrState& tr, const SolverParams prm) {
+  if constexpr (INL) return tr_propose_inline(tr, prm);
+  else return tr_propose(tr, prm);
+}
+template <bool INL>
+__device__ __forceinline__ int lm_tr_decide(TrState& tr, const double* red, const SolverParams prm) {
+  if constexpr (INL) return tr_decide_inline(tr, red, prm);
+  else return tr_decide(tr, red, prm);
 }
 
 

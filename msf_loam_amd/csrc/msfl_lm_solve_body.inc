@@ -50,6 +50,8 @@
   const double* pprime = pprime_all ? pprime_all + 3 * r0 : nullptr;
   double* pose_g = poses + 7 * (size_t)b;
   TrState& tr = sh.tr;
+  // trust-region functions inlined (msfl_kernels.cuh, lm_tr_propose): the plain 128-thread kernel only
+  [[maybe_unused]] constexpr bool kTrInline = MSFL_LM_TR_INLINE && !MSFL_LM_PRIOR && !MSFL_LM_DEGEN && BLOCK < 512;
   LM_T(t_begin);
   {
     double acc[kAcc];
@@ -121,7 +123,7 @@
       if (n_held == 6) go = 0;             // nothing observable: no step, the pose passes through, counts stay 0
       else go = n_held > 0 ? tr_propose_degen(tr, prm, s_degen) : tr_propose(tr, prm);
 #else
-      go = tr_propose(tr, prm);
+      go = lm_tr_propose<kTrInline>(tr, prm);
 #endif
     }
     sh.go = go;
@@ -167,7 +169,7 @@
       atomicAdd(&g_lm_prof[6], c1 - c0); atomicAdd(&g_lm_prof[7], c2 - c1);
     }
 #else
-    if (threadIdx.x == 0) sh.go = tr_decide(tr, sh.red, prm) ? tr_propose(tr, prm) : 0;
+    if (threadIdx.x == 0) sh.go = lm_tr_decide<kTrInline>(tr, sh.red, prm) ? lm_tr_propose<kTrInline>(tr, prm) : 0;
 #endif
     __syncthreads();
     LM_T(t3);
