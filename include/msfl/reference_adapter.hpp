@@ -35,6 +35,8 @@
 //   msfl::adapter::SetOutlierRejection(h, &rejection_record, MSFL_REJECT_THRESHOLD, 0.2)  once;  ClearOutlierRejection(h) to switch it off
 // and, for a health figure of a registration or the verification of a candidate pose against the map of the last MatchScan2Map:
 //   msfl::adapter::ScorePoses(h, scan_curr, poses, max_dist) -> std::vector<PoseScore> (Fitness(n_features), Rmse())
+// and, where the reference's src/slam/loop_closure is an empty class: which earlier scan looks like this one, and at which yaw
+//   msfl::PlaceDatabase places;  places.Add(cloud) per scan;  places.Query(cloud, max_index, n_prefilter, k) -> std::vector<PlaceMatch> (Yaw())
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -405,4 +407,70 @@ inline void CovarianceInParentFrame(const RigidT& pose, const msfl_match_uncerta
 }
 
 }  // namespace adapter
+
+// ---- place recognition (msfl_places_*): a database of polar scan descriptors on the device, independent of every matcher handle.
+struct PlaceMatch : msfl_place_match {
+  bool Valid() const { return index >= 0; }
+  // the yaw between the two visits that `shift` stands for, radians in (-pi, pi]
+  double Yaw(int n_sector) const {
+    const double two_pi = 6.283185307179586476925286766559;
+    const double a = two_pi * static_cast<double>(((shift % n_sector) + n_sector) % n_sector) / static_cast<double>(n_sector);
+    return a > 0.5 * two_pi ? a - two_pi : a;
+  }
+};
+
+class PlaceDatabase {
+ public:
+  explicit PlaceDatabase(int device = 0, const msfl_place_config* config = nullptr) {
+    if (config) cfg_ = *config; else msfl_places_default_config(&cfg_);
+    Check(msfl_places_create(&cfg_, device, &p_), "msfl_places_create");
+  }
+  ~PlaceDatabase() { msfl_places_destroy(p_); }
+  PlaceDatabase(const PlaceDatabase&) = delete;
+  PlaceDatabase& operator=(const PlaceDatabase&) = delete;
+
+  const msfl_place_config& config() const { return cfg_; }
+  int size() const { return msfl_places_size(p_); }
+  msfl_places* get() const { return p_; }
+
+  // describes the cloud (any point type with x, y, z, intensity) and appends it; returns its index
+  template <class CloudT>
+  int Add(const CloudT& cloud) {
+    const std::vector<msfl_point> pts = adapter::Pack(cloud);
+    const int off[2] = {0, static_cast<int>(pts.size())};
+    int first = -1;
+    Check(msfl_places_add(p_, pts.data(), off, 1, MSFL_MEM_HOST, &first), "msfl_places_add");
+    return first;
+  }
+
+  // the k best entries below max_index (negative: every entry) for the cloud, ordered by (distance, index); n_prefilter as in the C ABI
+  template <class CloudT>
+  std::vector<PlaceMatch> Query(const CloudT& cloud, int max_index = -1, int n_prefilter = 0, int k = 1) {
+    const std::vector<msfl_point> pts = adapter::Pack(cloud);
+    const int off[2] = {0, static_cast<int>(pts.size())};
+    std::vector<PlaceMatch> out(static_cast<std::size_t>(k > 0 ? k : 0));
+    static_assert(sizeof(PlaceMatch) == sizeof(msfl_place_match), "PlaceMatch adds no member");
+    Check(msfl_places_query(p_, pts.data(), off, 1, max_index >= 0 ? &max_index : nullptr, n_prefilter, k, out.data(), MSFL_MEM_HOST),
+          "msfl_places_query");
+    return out;
+  }
+
+  // as Query, for an entry that is stored already (entry i against max_index = i - 50: the loop-closure search)
+  std::vector<PlaceMatch> QueryEntry(int entry, int max_index = -1, int n_prefilter = 0, int k = 1) {
+    std::vector<PlaceMatch> out(static_cast<std::size_t>(k > 0 ? k : 0));
+    Check(msfl_places_query_entries(p_, &entry, 1, max_index >= 0 ? &max_index : nullptr, n_prefilter, k, out.data(), MSFL_MEM_HOST),
+          "msfl_places_query_entries");
+    return out;
+  }
+
+  double Yaw(const msfl_place_match& m) const { return static_cast<const PlaceMatch&>(m).Yaw(cfg_.n_sector); }
+
+ private:
+  void Check(msfl_status s, const char* what) const {
+    if (s != MSFL_OK) throw std::runtime_error(std::string(what) + ": " + msfl_status_string(s) + " " + (p_ ? msfl_places_last_error(p_) : ""));
+  }
+  msfl_place_config cfg_{};
+  msfl_places* p_ = nullptr;
+};
+
 }  // namespace msfl

@@ -325,6 +325,9 @@ class ScanRegistration {
   Rigid3d lidar2imu_;
 };
 
+// msfl::PlaceDatabase / msfl::PlaceMatch (place recognition, where the reference's src/slam/loop_closure is an empty class) come with
+// reference_adapter.hpp: Add(cloud), Query(cloud, max_index, n_prefilter, k), Yaw(match).
+
 // HybridGrid (src/slam/map/hybrid_grid.h:27-39): the local map store, resident on the device.
 // The reference passes the pcl::VoxelGrid filter to InsertScan; here its leaf is fixed at
 // construction (laser_mapping.cc:60-68 uses one leaf per map for the whole run).

@@ -929,6 +929,69 @@ msfl_status msfl_slam_get_clouds(msfl_slam* s, int scan_index, msfl_slam_clouds*
 msfl_status msfl_slam_grids(msfl_slam* s, msfl_grid** corner, msfl_grid** surf);
 const char* msfl_slam_last_error(const msfl_slam* s);
 
+/* ------------------------------------------------------------------------------------------------------------------
+   Place recognition: a device-resident database of polar scan descriptors (after Scan Context, Kim & Kim 2018) that
+   answers "which earlier scan looks like this one, and at which yaw".  docs/kernels/place.md holds the full definition;
+   in short, all f32 against tables the host builds once in double and rounds to f32
+   (e2[k] = (k max_range / n_ring)^2, lo2 = min_range^2, bc/bs[k] = cos/sin(2 pi k / n_sector)):
+     - a point with a non-finite coordinate is skipped; r2 = x*x + y*y; skipped unless lo2 <= r2 < e2[n_ring];
+     - ring = #{k in [1, n_ring) : r2 >= e2[k]};  the point is mirrored through the origin into the upper half plane
+       (y > 0, or y == 0 and x > 0) and sector = (mirrored ? n_sector/2 : 0) + #{k in [1, n_sector/2) : bc[k] y' - bs[k] x' >= 0};
+     - v = z + (float)height_offset, skipped unless v > 0;  D[ring][sector] = max(D[ring][sector], v), starting from 0.
+   Per entry: ring_key[r] = number of sectors with D[r][s] > 0; column norms in f64.
+   Distance of query q to entry c at shift s (column j of q against column (j + s) mod n_sector of c): the mean over the
+   columns j with both norms > 0 of 1 - dot_j / (|q_j| |c_j+s|), in f64 with ascending summation; +inf without such a
+   column.  A result carries the minimum over s and the lowest s that attains it: the yaw between the two visits in steps
+   of 2 pi / n_sector.  Every sum has one stated order: results do not depend on batch shape or launch shape.
+   The object owns a stream and its memory and is independent of msfl_handle and msfl_slam. */
+typedef struct msfl_place_config {
+  int n_ring;            /* 1 .. 32   (default 20) */
+  int n_sector;          /* 2 .. 120, even (default 60) */
+  double min_range;      /* 0 <= min_range < max_range (defaults 0.3, 80.0), metres in the scan's xy plane */
+  double max_range;
+  double height_offset;  /* added to z, so that heights are positive: roughly the sensor's height above ground (default 2.0) */
+  int capacity;          /* entries the database can hold, fixed at creation (default 16384) */
+} msfl_place_config;
+
+typedef struct msfl_place_match {
+  int index;             /* entry, -1 in an unused slot */
+  int shift;             /* columns; see above */
+  int ring_key_d2;       /* squared distance of the two ring keys */
+  int n_columns;         /* columns that entered the mean at `shift` */
+  double distance;       /* +inf in an unused slot and for a descriptor without a common column */
+} msfl_place_match;
+
+typedef struct msfl_places_s msfl_places;
+/* MSFL_BAD_ARG for a config outside the limits above, a non-finite value or capacity < 1.  NULL config = defaults. */
+void        msfl_places_default_config(msfl_place_config* c);
+msfl_status msfl_places_create(const msfl_place_config* c, int device, msfl_places** out);
+void        msfl_places_destroy(msfl_places* p);
+msfl_status msfl_places_set_stream(msfl_places* p, void* hip_stream);   /* as msfl_set_stream */
+msfl_status msfl_places_synchronize(msfl_places* p);
+int         msfl_places_size(const msfl_places* p);                     /* entries added so far (host count) */
+const char* msfl_places_last_error(const msfl_places* p);
+/* Rules for the calls below:
+     - MSFL_CAPACITY when an add would exceed `capacity`: nothing is added, not even part of the batch.
+     - MSFL_BAD_ARG: k < 1 or k > 64, n_prefilter < 0, decreasing offsets, an entry index that is no entry, a max_index
+       outside [0, size], descriptors with a value that is negative or not finite (host memory: checked before staging; device
+       memory: checked on the device, which waits for the stream; the whole add is refused).
+     - A scan with no binnable point is a valid all-zero entry; its distance to anything is +inf.
+     - Offsets, entry lists and max_index are HOST arrays.  With MSFL_MEM_DEVICE clouds, descriptors and results are device
+       pointers (16-byte aligned points) and the call is asynchronous on the object's stream: a query after an add sees the
+       new entries.  msfl_slam_get_clouds(..., MSFL_MEM_DEVICE).full_scan can be handed over as it is.
+     - Candidates of query i are the entries below max_index[i] (NULL: every entry present when the call is enqueued).
+       n_prefilter == 0 compares all of them; n_prefilter > 0 only the n_prefilter with the smallest ring_key_d2, ties to the
+       lowest index.  Results: k records per query ordered by (distance, index), unused slots {-1, 0, 0, 0, +inf}. */
+/* describe n_scans scans (concatenated points + n_scans+1 HOST prefix offsets) and append them; *first_index = index of the first */
+msfl_status msfl_places_add(msfl_places* p, const msfl_point* pts, const int* off, int n_scans, msfl_mem mem, int* first_index);
+/* append n ready descriptors (n x n_ring x n_sector f32, row-major [ring][sector]) - what msfl_places_get delivered; keys and norms are recomputed */
+msfl_status msfl_places_add_descriptors(msfl_places* p, const float* desc, int n, msfl_mem mem, int* first_index);
+msfl_status msfl_places_get(msfl_places* p, int first, int n, float* desc_out, int* ring_key_out /* n x n_ring, may be NULL */, msfl_mem mem);
+msfl_status msfl_places_query(msfl_places* p, const msfl_point* pts, const int* off, int n_queries, const int* max_index,
+                              int n_prefilter, int k, msfl_place_match* out /* n_queries x k */, msfl_mem mem);
+msfl_status msfl_places_query_entries(msfl_places* p, const int* entries /* HOST */, int n_queries, const int* max_index,
+                                      int n_prefilter, int k, msfl_place_match* out, msfl_mem mem);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

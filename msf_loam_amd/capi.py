@@ -35,6 +35,9 @@ EXPORTED = [
     "msfl_set_degeneracy", "msfl_slam_set_degeneracy", "msfl_slam_get_degeneracy",
     "msfl_set_outlier_rejection", "msfl_slam_set_outlier_rejection", "msfl_slam_get_rejection",
     "msfl_score_poses", "msfl_score_poses_batch",
+    "msfl_places_default_config", "msfl_places_create", "msfl_places_destroy", "msfl_places_set_stream", "msfl_places_synchronize",
+    "msfl_places_size", "msfl_places_last_error", "msfl_places_add", "msfl_places_add_descriptors", "msfl_places_get",
+    "msfl_places_query", "msfl_places_query_entries",
 ]
 
 
@@ -156,6 +159,29 @@ def rmse(scores):
     inl = scores["inliers"].sum(-1).astype(np.float64)
     tot = scores["sum_sq_q32"].astype(np.float64).sum(-1) / 4294967296.0     # (each sum is below 2^63; the float64 rounding is 2^-53 relative)
     return np.sqrt(np.divide(tot, inl, out=np.full(np.shape(inl), np.nan), where=inl > 0))
+
+
+class PlaceConfig(C.Structure):
+    """msfl_place_config: polar bins, range gate, height offset and the fixed capacity of the database."""
+    _fields_ = [("n_ring", C.c_int), ("n_sector", C.c_int), ("min_range", C.c_double), ("max_range", C.c_double),
+                ("height_offset", C.c_double), ("capacity", C.c_int)]
+
+
+class PlaceMatch(C.Structure):
+    """msfl_place_match: one candidate of a query, its column shift and its rotation-invariant distance."""
+    _fields_ = [("index", C.c_int), ("shift", C.c_int), ("ring_key_d2", C.c_int), ("n_columns", C.c_int), ("distance", C.c_double)]
+
+
+# the same record as a numpy structured dtype (Places.query, Places.query_entries)
+PLACE_MATCH_DTYPE = np.dtype([("index", np.int32), ("shift", np.int32), ("ring_key_d2", np.int32), ("n_columns", np.int32),
+                              ("distance", np.float64)])
+assert PLACE_MATCH_DTYPE.itemsize == C.sizeof(PlaceMatch) == 24
+
+
+def place_yaw(shift, n_sector):
+    """Yaw in radians, in (-pi, pi], that a column shift stands for (steps of 2 pi / n_sector); arrays welcome."""
+    a = 2.0 * np.pi * (np.asarray(shift) % int(n_sector)) / int(n_sector)
+    return np.where(a > np.pi, a - 2.0 * np.pi, a)[()]
 
 
 def _on_device(x):
@@ -1147,3 +1173,157 @@ class Slam:
             raise MsflError(st, "msfl_slam_grids", self._err())
         res, leaf_c, leaf_s = self._grid_shape
         return _BorrowedGrid(self.lib, a, self._err, res, leaf_c), _BorrowedGrid(self.lib, b, self._err, res, leaf_s)
+
+
+class Places:
+    """Owns one msfl_places: a device-resident database of polar scan descriptors (msfl_places_*), independent of any Handle.
+    Keyword arguments are the fields of msfl_place_config (n_ring, n_sector, min_range, max_range, height_offset, capacity)."""
+
+    def __init__(self, device=0, **cfg):
+        self.lib = load()
+        self.lib.msfl_places_last_error.restype = C.c_char_p
+        self.lib.msfl_places_last_error.argtypes = [C.c_void_p]
+        self.lib.msfl_places_size.argtypes = [C.c_void_p]
+        self.config = PlaceConfig()
+        self.lib.msfl_places_default_config(C.byref(self.config))
+        for k, v in cfg.items():
+            if k not in dict(PlaceConfig._fields_):
+                raise TypeError("unknown msfl_place_config field %r" % (k,))
+            setattr(self.config, k, v)
+        self.p = C.c_void_p()
+        s = self.lib.msfl_places_create(C.byref(self.config), C.c_int(device), C.byref(self.p))
+        if s != OK:
+            raise MsflError(s, "msfl_places_create", "(a config outside its limits, or no GPU: there is no CPU fallback)")
+
+    n_ring = property(lambda self: self.config.n_ring)
+    n_sector = property(lambda self: self.config.n_sector)
+
+    def close(self):
+        if self.p:
+            self.lib.msfl_places_destroy(self.p)
+            self.p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, s, what, allow=()):
+        if s != OK and s not in allow:
+            raise MsflError(s, what, (self.lib.msfl_places_last_error(self.p) or b"").decode())
+        return s
+
+    def set_stream(self, stream_ptr):
+        self._check(self.lib.msfl_places_set_stream(self.p, C.c_void_p(stream_ptr)), "msfl_places_set_stream")
+
+    def synchronize(self):
+        self._check(self.lib.msfl_places_synchronize(self.p), "msfl_places_synchronize")
+
+    def size(self):
+        return int(self.lib.msfl_places_size(self.p))
+
+    def __len__(self):
+        return self.size()
+
+    @staticmethod
+    def _scans(scans, off):
+        """one (n, 4) cloud, a list of clouds, or concatenated points + offsets -> (points, int32 offsets)"""
+        if off is None:
+            if isinstance(scans, np.ndarray) and scans.ndim == 2:
+                scans = [scans]
+            scans = [_pts(a) for a in scans]
+            off = np.zeros(len(scans) + 1, np.int32)
+            if scans:
+                off[1:] = np.cumsum([len(a) for a in scans])
+            pts = np.concatenate(scans) if scans else np.zeros((0, 4), np.float32)
+            return np.ascontiguousarray(pts, np.float32), off
+        return _pts(scans), np.ascontiguousarray(off, np.int32)
+
+    def add(self, scans, off=None, allow=()):
+        """Describes and appends scans: one (n, 4) cloud, a list of clouds, or concatenated points with prefix offsets.  Returns the
+        index of the first new entry (or the refusing status when it is in `allow`)."""
+        pts, off = self._scans(scans, off)
+        first = C.c_int(-1)
+        s = self._check(self.lib.msfl_places_add(self.p, _vp(pts), _vp(off), C.c_int(len(off) - 1), C.c_int(MEM_HOST), C.byref(first)),
+                        "msfl_places_add", allow)
+        return first.value if s == OK else s
+
+    def add_device(self, pts, off, allow=()):
+        """Device-pointer form (torch tensor / raw pointer of 16-byte points), asynchronous on the object's stream; `off` is a host array."""
+        off = np.ascontiguousarray(off, np.int32)
+        first = C.c_int(-1)
+        s = self._check(self.lib.msfl_places_add(self.p, _vp(pts), _vp(off), C.c_int(len(off) - 1), C.c_int(MEM_DEVICE), C.byref(first)),
+                        "msfl_places_add(device)", allow)
+        return first.value if s == OK else s
+
+    def _desc(self, desc):
+        d = np.ascontiguousarray(np.asarray(desc, np.float32).reshape(-1, self.n_ring, self.n_sector))
+        return d
+
+    def add_descriptors(self, desc, allow=()):
+        """Appends ready descriptors (n, n_ring, n_sector) float32 - what get() delivered; keys and norms are recomputed."""
+        d = self._desc(desc)
+        first = C.c_int(-1)
+        s = self._check(self.lib.msfl_places_add_descriptors(self.p, _vp(d), C.c_int(len(d)), C.c_int(MEM_HOST), C.byref(first)),
+                        "msfl_places_add_descriptors", allow)
+        return first.value if s == OK else s
+
+    def add_descriptors_device(self, desc, n, allow=()):
+        first = C.c_int(-1)
+        s = self._check(self.lib.msfl_places_add_descriptors(self.p, _vp(desc), C.c_int(int(n)), C.c_int(MEM_DEVICE), C.byref(first)),
+                        "msfl_places_add_descriptors(device)", allow)
+        return first.value if s == OK else s
+
+    def get(self, first=0, n=None, want_ring_key=False):
+        """Descriptors [first, first + n) as (n, n_ring, n_sector) float32; with want_ring_key also the (n, n_ring) int32 ring keys."""
+        n = self.size() - first if n is None else int(n)
+        d = np.zeros((max(n, 0), self.n_ring, self.n_sector), np.float32)
+        rk = np.zeros((max(n, 0), self.n_ring), np.int32) if want_ring_key else None
+        self._check(self.lib.msfl_places_get(self.p, C.c_int(int(first)), C.c_int(n), _vp(d), _vp(rk), C.c_int(MEM_HOST)), "msfl_places_get")
+        return (d, rk) if want_ring_key else d
+
+    def get_device(self, first, n, desc_out, ring_key_out=None):
+        self._check(self.lib.msfl_places_get(self.p, C.c_int(int(first)), C.c_int(int(n)), _vp(desc_out), _vp(ring_key_out), C.c_int(MEM_DEVICE)),
+                    "msfl_places_get(device)")
+
+    @staticmethod
+    def _max_index(max_index, n):
+        if max_index is None:
+            return None
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(max_index, np.int32), (n,)))
+        return m
+
+    def query(self, scans, off=None, max_index=None, n_prefilter=0, k=1, allow=()):
+        """The k best entries for each scan: (Q, k) records of PLACE_MATCH_DTYPE ordered by (distance, index).  max_index: None (every
+        entry), one int or one per query: only entries below it are candidates."""
+        pts, off = self._scans(scans, off)
+        Q = len(off) - 1
+        out = np.zeros((max(Q, 0), max(int(k), 0)), PLACE_MATCH_DTYPE)
+        mi = self._max_index(max_index, Q)
+        s = self._check(self.lib.msfl_places_query(self.p, _vp(pts), _vp(off), C.c_int(Q), _vp(mi), C.c_int(int(n_prefilter)), C.c_int(int(k)),
+                                                   _vp(out), C.c_int(MEM_HOST)), "msfl_places_query", allow)
+        return out if s == OK else s
+
+    def query_device(self, pts, off, out, max_index=None, n_prefilter=0, k=1, allow=()):
+        """Device-pointer form, asynchronous: `out` holds Q x k records of 24 bytes on the device; off / max_index are host arrays."""
+        off = np.ascontiguousarray(off, np.int32)
+        mi = self._max_index(max_index, len(off) - 1)
+        return self._check(self.lib.msfl_places_query(self.p, _vp(pts), _vp(off), C.c_int(len(off) - 1), _vp(mi), C.c_int(int(n_prefilter)),
+                                                      C.c_int(int(k)), _vp(out), C.c_int(MEM_DEVICE)), "msfl_places_query(device)", allow)
+
+    def query_entries(self, entries, max_index=None, n_prefilter=0, k=1, allow=()):
+        """As query(), for entries that are stored already (e.g. entry i against max_index = i - 50: the loop-closure search)."""
+        e = np.ascontiguousarray(np.atleast_1d(np.asarray(entries, np.int32)))
+        out = np.zeros((len(e), max(int(k), 0)), PLACE_MATCH_DTYPE)
+        mi = self._max_index(max_index, len(e))
+        s = self._check(self.lib.msfl_places_query_entries(self.p, _vp(e), C.c_int(len(e)), _vp(mi), C.c_int(int(n_prefilter)), C.c_int(int(k)),
+                                                           _vp(out), C.c_int(MEM_HOST)), "msfl_places_query_entries", allow)
+        return out if s == OK else s
+
+    def query_entries_device(self, entries, out, max_index=None, n_prefilter=0, k=1, allow=()):
+        e = np.ascontiguousarray(np.atleast_1d(np.asarray(entries, np.int32)))
+        mi = self._max_index(max_index, len(e))
+        return self._check(self.lib.msfl_places_query_entries(self.p, _vp(e), C.c_int(len(e)), _vp(mi), C.c_int(int(n_prefilter)),
+                                                              C.c_int(int(k)), _vp(out), C.c_int(MEM_DEVICE)),
+                           "msfl_places_query_entries(device)", allow)

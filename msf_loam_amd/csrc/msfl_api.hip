@@ -1192,6 +1192,7 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
 #include "msfl_api_slam.inc"
 #include "msfl_api_pairs.inc"
 #include "msfl_api_score.inc"
+#include "msfl_api_place.inc"
 
 namespace {
 

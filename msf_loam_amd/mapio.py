@@ -85,3 +85,54 @@ def load_grid(path, grid):
     if np.float32(grid.leaf) != np.float32(l):
         raise MapFileError("the file's leaf is %g, the store's %g" % (l, grid.leaf))
     return grid.load_cells(cells, points)
+
+
+# ---- place database (capi.Places) ----
+
+PLACES_FORMAT = 1
+PLACE_CONFIG_FIELDS = ("n_ring", "n_sector", "min_range", "max_range", "height_offset", "capacity")
+
+
+def save_places(path, places):
+    """The config and every descriptor of a capi.Places as one .npz.  Returns the number of entries."""
+    desc = places.get(0, places.size())
+    cfg = {k: getattr(places.config, k) for k in PLACE_CONFIG_FIELDS}
+    with open(path, "wb") as f:
+        np.savez(f, places_format=np.int32(PLACES_FORMAT), descriptors=desc,
+                 **{k: (np.int32(v) if isinstance(v, int) else np.float64(v)) for k, v in cfg.items()})
+    return len(desc)
+
+
+def read_places(path):
+    """-> (config dict, descriptors (n, n_ring, n_sector) float32), checked by the rules msfl_places_add_descriptors applies."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in ("places_format", "descriptors") + PLACE_CONFIG_FIELDS if k not in z.files]
+        if missing:
+            raise MapFileError("not a place file: no %s" % ", ".join(missing))
+        if int(z["places_format"]) != PLACES_FORMAT:
+            raise MapFileError("place file format %d, this reader knows %d" % (int(z["places_format"]), PLACES_FORMAT))
+        cfg = {k: (int(z[k]) if k in ("n_ring", "n_sector", "capacity") else float(z[k])) for k in PLACE_CONFIG_FIELDS}
+        desc = z["descriptors"]
+    if desc.dtype != np.float32 or desc.ndim != 3 or desc.shape[1:] != (cfg["n_ring"], cfg["n_sector"]):
+        raise MapFileError("descriptors: an (n, %d, %d) float32 array is needed, got %s %s" % (cfg["n_ring"], cfg["n_sector"], desc.dtype, desc.shape))
+    if not (np.isfinite(desc).all() and (desc >= 0).all()):
+        raise MapFileError("a descriptor value is negative or not finite")
+    return cfg, np.ascontiguousarray(desc)
+
+
+def load_places(path, places=None, device=0, capacity=None):
+    """A place file into a capi.Places through msfl_places_add_descriptors.  places=None creates one with the file's config
+    (`capacity` overrides the file's); an existing one must have the file's bins, range gate and height offset.  Returns it."""
+    from . import capi
+    cfg, desc = read_places(path)
+    if places is None:
+        if capacity is not None:
+            cfg["capacity"] = int(capacity)
+        places = capi.Places(device, **cfg)
+    else:
+        for k in PLACE_CONFIG_FIELDS[:-1]:
+            if getattr(places.config, k) != cfg[k]:
+                raise MapFileError("the file's %s is %r, the database's %r" % (k, cfg[k], getattr(places.config, k)))
+    if len(desc):
+        places.add_descriptors(desc)
+    return places
