@@ -462,6 +462,10 @@ msfl_status upload_batch_offsets(msfl_handle* h, int n, const int* corner_off, c
   return upload_in_off(h, offs.data(), offs.size(), h->stream);
 }
 
+// Bytes of the record buffer of a batch of n_rec records, n_surf of them planes (msfl_record_tiles.h: the plane tiles, padded to whole
+// tiles, then the edge records).
+size_t record_bytes(size_t n_rec, size_t n_surf) { return rec_reserve_doubles(n_rec, n_surf) * sizeof(double); }
+
 // The view over a device offset table whose rows corner_off, surf_off and rec_off lie `stride` ints apart.  dyn = 1: the SLAM step's
 // device-written table (BatchView::dyn: n_records and n_surf_total are then capacities, c0 = s0 = 0).
 BatchView batch_view(const float4* d_corner, const float4* d_surf, const int* d_table, int stride, int n_scans, int n_records, int c0, int s0,
@@ -601,12 +605,17 @@ void launch_knn5(msfl_handle* h, Kernel kernel, dim3 grid, dim3 block, const Bat
                      (const int*)h->map_c.pos_of.as<int>(), (const int*)h->map_s.pos_of.as<int>(), h->prm.map_knn_max_sq_dist, tail...);
 }
 
+// Does an association pass over ALL n_rec records of this batch take the whole-batch kernels?  They number `nn` by corner feature and
+// keep a surf feature's list in its record tile; the per-record kernels number `nn` by record (msfl_kernels.cuh: corner_slot, plane_nn_store).
+bool assoc_whole_batch(const msfl_handle* h, const BatchView& bv, bool deskew, int n_rec, const double* full) {
+  return !deskew && !bv.dyn && n_rec >= 65536 && !full && h->timing != 3;
+}
+
 // one data-association pass = kNN kernel + fit kernel
 // (records [rec_begin, rec_end) of the batch; rec_end < 0: all of them)
 void s_launch_assoc(msfl_handle* h, const BatchView& bv_all, const double* d_poses, const int* d_status, bool deskew,
                     const DeskewView& dv, int n_rec, double* full = nullptr, int rec_begin = 0, int rec_end = -1, bool second_pass = false) {
-  // the whole-batch kernels number `nn` by feature slot, the per-record ones by record (msfl_kernels.cuh: feature_slot)
-  const bool whole_batch = !deskew && !bv_all.dyn && rec_end < 0 && n_rec >= 65536 && !full && h->timing != 3;
+  const bool whole_batch = rec_end < 0 && assoc_whole_batch(h, bv_all, deskew, n_rec, full);
   hipStream_t st = h->stream;
   int* nn = h->nn.as<int>();
   BatchView bv = bv_all;
@@ -622,7 +631,7 @@ void s_launch_assoc(msfl_handle* h, const BatchView& bv_all, const double* d_pos
     } else if (whole_batch) {       // a whole large batch: one body per feature kind (-2 %)
       const int n_s = bv.n_surf_total, n_c = n_rec - n_s;
       const int edge_blocks = div_up(n_c, kAssocBlock), plane_blocks = div_up(n_s, kAssocBlock);
-      launch_knn5(h, knn5_scan2map_split_kernel, dim3(edge_blocks + plane_blocks), block, bv, d_poses, d_status, nn, edge_blocks);
+      launch_knn5(h, knn5_scan2map_split_kernel, dim3(edge_blocks + plane_blocks), block, bv, d_poses, d_status, nn, h->records.as<double>(), edge_blocks);
     } else if (!deskew && (h->knn_form == 2 || (h->knn_form == 0 && (n_rec <= kKnnRowsMaxRecords ||
                                                                        // the SLAM step launches over the list CAPACITIES (device-side counts): a 64-beam scan's ~11-17 k
                                                                        // queries sit in a ~150 k-slot launch whose surplus workgroups leave at once
@@ -664,9 +673,11 @@ msfl_status match_scan2map_device(msfl_handle* h, int B, const float4* d_corner,
                                   const std::function<hipError_t(int)>* enqueue_chunk = nullptr) {
   int n_rec = 0;
   { const msfl_status us = upload_batch_offsets(h, B, h_corner_off, h_surf_off, &n_rec); if (us) return us; }
-  HIPCHK(h, h->records.reserve(std::max<size_t>(1, (size_t)n_rec) * 6 * sizeof(double)));
-  HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)n_rec) * 5 * sizeof(int)));
+  HIPCHK(h, h->records.reserve(record_bytes((size_t)n_rec, (size_t)(h_surf_off[B] - h_surf_off[0]))));
   const BatchView bv = batch_view(d_corner, d_surf, h->in_off.as<int>(), B + 1, B, n_rec, h_corner_off[0], h_surf_off[0], h_surf_off[B] - h_surf_off[0]);
+  // every pass through the whole-batch kernels: `nn` holds the corner features' lists only (the surf lists live in the record tiles)
+  const bool nn_corner_only = n_chunks == 1 && !enqueue_chunk && assoc_whole_batch(h, bv, deskew != nullptr, n_rec, nullptr);
+  HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)(nn_corner_only ? n_rec - bv.n_surf_total : n_rec)) * 5 * sizeof(int)));
   DeskewView dv{};
   if (deskew) {
     dv = *deskew;
@@ -1120,7 +1131,7 @@ static msfl_status stage_single(msfl_handle* h, const msfl_point* corner, int n_
   HIPCHK(h, h->poses.reserve(7 * sizeof(double)));
   HIPCHK(h, h->status.reserve(sizeof(int)));
 
-  HIPCHK(h, h->records.reserve(std::max<size_t>(1, (size_t)(n_corner + n_surf)) * 6 * sizeof(double)));
+  HIPCHK(h, h->records.reserve(record_bytes((size_t)n_corner + (size_t)n_surf, (size_t)n_surf)));
   HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)(n_corner + n_surf)) * 5 * sizeof(int)));
   if (n_corner) HIPCHK(h, hipMemcpyAsync(h->in_corner.p, corner, (size_t)n_corner * sizeof(float4), hipMemcpyHostToDevice, st));
   if (n_surf) HIPCHK(h, hipMemcpyAsync(h->in_surf.p, surf, (size_t)n_surf * sizeof(float4), hipMemcpyHostToDevice, st));

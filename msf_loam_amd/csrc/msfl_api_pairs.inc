@@ -137,7 +137,7 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
   s = reg_open(h, P, st, info != nullptr, &sinks); if (s) return s;
   int n_rec = 0;
   s = upload_batch_offsets(h, P, co.data(), so.data(), &n_rec); if (s) return s;
-  HIPCHK(h, h->records.reserve(std::max<size_t>(1, (size_t)n_rec) * 6 * sizeof(double)));
+  HIPCHK(h, h->records.reserve(record_bytes((size_t)n_rec, (size_t)(so[P] - so[0]))));
   HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)n_rec) * 5 * sizeof(int)));
   const BatchView bv = batch_view(d_corner, d_surf, h->in_off.as<int>(), P + 1, P, n_rec, co[0], so[0], so[P] - so[0]);
   DeskewView dv{};

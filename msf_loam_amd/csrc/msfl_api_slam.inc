@@ -199,7 +199,7 @@ msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamSca
   const int* d_off = cur.odo_off.as<int>();
   int* d_status = cur.odo_status.as<int>();
   const int n_rec_cap = caps.sharp + caps.flat;
-  HIPCHK(h, h->records.reserve(((size_t)4 * caps.flat + (size_t)6 * caps.sharp + 8) * sizeof(double)));
+  HIPCHK(h, h->records.reserve((rec_buffer_doubles((size_t)caps.sharp, (size_t)caps.flat) + 8) * sizeof(double)));
   const BatchView bv = batch_view(cur.sharp.as<float4>(), cur.flat.as<float4>(), d_off + 4, 2, B, n_rec_cap, 0, 0, caps.flat, 1);
   OdomView ov;
   ov.last_ls = last.ls.as<float4>(); ov.last_ls_ring = last.ls_ring.as<uint16_t>(); ov.last_ls_off = d_off;
@@ -258,7 +258,7 @@ msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamSca
 msfl_status scan2map_dyn(msfl_handle* h, const float4* d_corner, const float4* d_surf, const int* d_in_off, int cap_corner, int cap_surf,
                          double* d_pose, int* d_status, const RegSinks& sinks, const DeskewView* deskew = nullptr) {
   const int n_rec_cap = cap_corner + cap_surf;
-  HIPCHK(h, h->records.reserve(((size_t)4 * cap_surf + (size_t)6 * cap_corner + 8) * sizeof(double)));
+  HIPCHK(h, h->records.reserve((rec_buffer_doubles((size_t)cap_corner, (size_t)cap_surf) + 8) * sizeof(double)));
   HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)n_rec_cap) * 5 * sizeof(int)));
   const BatchView bv = batch_view(d_corner, d_surf, d_in_off, 2, 1, n_rec_cap, 0, 0, cap_surf, 1);
   DeskewView dv{};

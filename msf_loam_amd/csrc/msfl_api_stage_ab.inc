@@ -251,7 +251,7 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
   HIPCHK(h, hipMemsetAsync(d_status, 0, (size_t)B * sizeof(int), st));
   RegSinks sinks;
   { const msfl_status us = reg_open(h, B, st, info != nullptr, &sinks); if (us) return us; }
-  HIPCHK(h, h->records.reserve(std::max<size_t>(1, (size_t)n_rec) * 6 * sizeof(double)));
+  HIPCHK(h, h->records.reserve(record_bytes((size_t)n_rec, (size_t)(offs[3 * (B + 1) + B] - offs[3 * (B + 1)]))));
   // the current scan's sharp / flat lists are the problem's corner / surf clouds: rows 2, 3 and 4 of the table
   const BatchView bv = batch_view(d_pts[2], d_pts[3], d_off + 2 * (B + 1), B + 1, B, n_rec, offs[2 * (B + 1)], offs[3 * (B + 1)],
                                   offs[3 * (B + 1) + B] - offs[3 * (B + 1)]);

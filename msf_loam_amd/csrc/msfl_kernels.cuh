@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "msfl_math.cuh"
+#include "msfl_record_tiles.h"
 #include "msfl_knn_index.cuh"
 
 namespace msfl {
@@ -121,21 +122,41 @@ __device__ __forceinline__ int find_scan(const int* __restrict__ rec_off, int n_
   return lo;
 }
 
-// Neighbour lists of the WHOLE-BATCH kernels (knn5_scan2map_split_kernel -> fit_scan2map_split_kernel; round 6): a feature's five neighbours
-// sit at slot (f - c0) for corner feature f and (all corner features) + (f - s0) for surf feature f -- a function of the feature's index in
-// its cloud array alone, like the record offsets below.  The per-record kernels number `nn` by record (scan by scan, corners then
-// surfs), which costs a wavefront the scan search and the offset loads before its first useful load; the fit kernel is a short
-// latency chain at four wavefronts per SIMD and that prologue was a tenth of it.  Producer and consumer of a batch always use the same numbering.
-__device__ __forceinline__ size_t feature_slot(const BatchView& bv, bool edge, int f) {
-  return edge ? (size_t)(f - bv.c0) : (size_t)(bv.n_records - bv.n_surf_total) + (size_t)(f - bv.s0);
-}
+// Neighbour lists of the WHOLE-BATCH kernels (knn5_scan2map_split_kernel -> fit_scan2map_split_kernel; round 6): the five neighbours of
+// corner feature f sit at slot (f - c0) of `nn`, those of surf feature f in the record tile that its plane record will occupy
+// (plane_nn_store / plane_nn_load below) -- functions of the feature's index in its cloud array alone, like the record offsets.  The
+// per-record kernels number `nn` by record (scan by scan, corners then surfs), which costs a wavefront the scan search and the offset
+// loads before its first useful load; the fit kernel is a short latency chain at four wavefronts per SIMD and that prologue was a
+// tenth of it.  Producer and consumer of a batch always use the same numbering.
+__device__ __forceinline__ size_t corner_slot(const BatchView& bv, int f) { return (size_t)(f - bv.c0); }
 
-// Record buffer: the PLANE records of the whole batch first (4 doubles each, so every record is one aligned 32-byte
-// line), then the edge records (6 doubles each); both are indexed by the feature's index in its cloud, so a record can be
-// written from any processing order.  Offsets in doubles:
-__device__ __forceinline__ size_t plane_rec_off(const BatchView& bv, int fi_surf) { return 4 * (size_t)(fi_surf - bv.s0); }
+// Record buffer (msfl_record_tiles.h): the PLANE records of the whole batch first, in lane-transposed tiles of 64 rows, then the edge
+// records (6 doubles each); both are indexed by the feature's index in its cloud, so a record can be written from any processing
+// order.  A plane row is only ever reached through plane_slot + plane_rec_load / plane_rec_store:
+__device__ __forceinline__ size_t plane_slot(const BatchView& bv, int fi_surf) { return (size_t)(fi_surf - bv.s0); }
 __device__ __forceinline__ size_t edge_rec_off(const BatchView& bv, int fi_corner) {
-  return 4 * (size_t)bv.n_surf_total + 6 * (size_t)(fi_corner - bv.c0);
+  return rec_edge((size_t)bv.n_surf_total, (size_t)(fi_corner - bv.c0));
+}
+// row {N.x, N.y, N.z, N.C} of plane slot g; rec: start of the record buffer
+__device__ __forceinline__ void plane_rec_load(const double* rec, size_t g, double (&r)[4]) {
+  const double2 a = *(const double2*)(rec + rec_tile_xy(g)), b = *(const double2*)(rec + rec_tile_zc(g));
+  r[0] = a.x; r[1] = a.y; r[2] = b.x; r[3] = b.y;
+}
+__device__ __forceinline__ void plane_rec_store(double* rec, size_t g, double nx, double ny, double nz, double d0) {
+  *(double2*)(rec + rec_tile_xy(g)) = make_double2(nx, ny);
+  *(double2*)(rec + rec_tile_zc(g)) = make_double2(nz, d0);
+}
+// The whole-batch 5-NN list of plane slot g, kept in the tile between the 5-NN launch and the fit launch that turns the tile into
+// records: {p0..p3} of the 64 lanes are the tile's first 1 024 bytes, p4 of the 64 lanes the next 256 -- whole lines either way.
+__device__ __forceinline__ void plane_nn_store(double* rec, size_t g, int p0, int p1, int p2, int p3, int p4) {
+  char* t = (char*)rec;
+  *(int4*)(t + rec_tile_nn4(g)) = make_int4(p0, p1, p2, p3);
+  *(int*)(t + rec_tile_nn1(g)) = p4;
+}
+__device__ __forceinline__ void plane_nn_load(const double* rec, size_t g, int (&p)[5]) {
+  const char* t = (const char*)rec;
+  const int4 a = *(const int4*)(t + rec_tile_nn4(g));
+  p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w; p[4] = *(const int*)(t + rec_tile_nn1(g));
 }
 
 struct DeskewView {
@@ -250,7 +271,7 @@ __device__ __forceinline__ V uniform_load(const V* p) {
 template <bool EDGE>
 __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double* __restrict__ poses, const int* __restrict__ status,
                                               const GridDesc* __restrict__ gp, const float4* __restrict__ map, const int* __restrict__ cs,
-                                              const int* __restrict__ po, float max_sq_dist, int* __restrict__ nn, int block, int* s_slot) {
+                                              const int* __restrict__ po, float max_sq_dist, int* __restrict__ nn, double* __restrict__ rec, int block, int* s_slot) {
   const int* off = EDGE ? bv.corner_off : bv.surf_off;
   const int f_i = off[0] + block * (int)blockDim.x + (int)threadIdx.x;
   if (f_i >= off[bv.n_scans]) return;
@@ -273,8 +294,13 @@ __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double*
     st = status[b];
     T = load_pose(poses + 7 * b);
   }
-  int* out = nn + 5 * feature_slot(bv, EDGE, f_i);
-  if (st != 0) { out[0] = -1; out[1] = -1; out[2] = -1; out[3] = -1; out[4] = -1; return; }
+  // nearest first; all five are always written: the fit kernel loads them unconditionally.  A corner feature's list goes to its slot of
+  // `nn`, a surf feature's into the record tile its plane record will occupy (msfl_record_tiles.h)
+  auto put = [&](int p0, int p1, int p2, int p3, int p4) __attribute__((always_inline)) {
+    if (EDGE) { int* out = nn + 5 * corner_slot(bv, f_i); out[0] = p0; out[1] = p1; out[2] = p2; out[3] = p3; out[4] = p4; }
+    else plane_nn_store(rec, plane_slot(bv, f_i), p0, p1, p2, p3, p4);
+  };
+  if (st != 0) { put(-1, -1, -1, -1, -1); return; }
   const float4 f = EDGE ? bv.corner[f_i] : bv.surf[f_i];
   const float3 q = transform_point_f32(T, f.x, f.y, f.z);                          // :123 / :193
   int n_cand = 0;
@@ -284,10 +310,10 @@ __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double*
   knn5_grid_k32<kAssocBlock>(gd, map, cs, q, tk, n_cand);
   if (top_settled(tk, max_sq_dist)) {
     if (top_found(tk)) {                                                              // :128 / :198: the 5th is below the gate (t differs from the gate's)
-      out[0] = top_pos<kAssocBlock>(tk, tk.k0); out[1] = top_pos<kAssocBlock>(tk, tk.k1); out[2] = top_pos<kAssocBlock>(tk, tk.k2);
-      out[3] = top_pos<kAssocBlock>(tk, tk.k3); out[4] = top_pos<kAssocBlock>(tk, tk.k4);   // nearest first, positions in the sorted map
+      put(top_pos<kAssocBlock>(tk, tk.k0), top_pos<kAssocBlock>(tk, tk.k1), top_pos<kAssocBlock>(tk, tk.k2),
+          top_pos<kAssocBlock>(tk, tk.k3), top_pos<kAssocBlock>(tk, tk.k4));   // positions in the sorted map
     } else {
-      out[0] = -1; out[1] = -1; out[2] = -1; out[3] = -1; out[4] = -1;
+      put(-1, -1, -1, -1, -1);
     }
     return;
   }
@@ -296,20 +322,20 @@ __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double*
   top5_init(t, max_sq_dist);
   knn5_grid(gd, map, cs, q, t, n_cand);
   if ((unsigned int)t.k4 != 0xffffffffu && (double)top5_d4(t) < (double)max_sq_dist) {      // :128 / :198
-    out[0] = po[(unsigned int)t.k0]; out[1] = po[(unsigned int)t.k1]; out[2] = po[(unsigned int)t.k2];
-    out[3] = po[(unsigned int)t.k3]; out[4] = po[(unsigned int)t.k4];       // nearest first
+    put(po[(unsigned int)t.k0], po[(unsigned int)t.k1], po[(unsigned int)t.k2], po[(unsigned int)t.k3], po[(unsigned int)t.k4]);
   } else {
-    out[0] = -1; out[1] = -1; out[2] = -1; out[3] = -1; out[4] = -1;
+    put(-1, -1, -1, -1, -1);
   }
 }
 __global__ void __launch_bounds__(kAssocBlock)
 knn5_scan2map_split_kernel(BatchView bv, const double* __restrict__ poses, const int* __restrict__ status,
                            const GridDesc* __restrict__ gcp, const float4* __restrict__ map_c, const int* __restrict__ cs_c,
                            const GridDesc* __restrict__ gsp, const float4* __restrict__ map_s, const int* __restrict__ cs_s,
-                           const int* __restrict__ pos_c, const int* __restrict__ pos_s, float max_sq_dist, int* __restrict__ nn, int edge_blocks) {
+                           const int* __restrict__ pos_c, const int* __restrict__ pos_s, float max_sq_dist, int* __restrict__ nn,
+                           double* __restrict__ rec, int edge_blocks) {
   __shared__ int s_slot[kTopSlots * kAssocBlock];        // Top6K's slot table: 6 positions per lane
-  if ((int)blockIdx.x < edge_blocks) knn5_one_kind<true>(bv, poses, status, gcp, map_c, cs_c, pos_c, max_sq_dist, nn, (int)blockIdx.x, s_slot);
-  else knn5_one_kind<false>(bv, poses, status, gsp, map_s, cs_s, pos_s, max_sq_dist, nn, (int)blockIdx.x - edge_blocks, s_slot);
+  if ((int)blockIdx.x < edge_blocks) knn5_one_kind<true>(bv, poses, status, gcp, map_c, cs_c, pos_c, max_sq_dist, nn, rec, (int)blockIdx.x, s_slot);
+  else knn5_one_kind<false>(bv, poses, status, gsp, map_s, cs_s, pos_s, max_sq_dist, nn, rec, (int)blockIdx.x - edge_blocks, s_slot);
 }
 
 // K4a, latency form: the same exact 5-NN for a launch too small to fill the machine (one scan per call: ~5 000 queries are
@@ -410,12 +436,17 @@ knn5_scan2map_rows_kernel(BatchView bv, const double* __restrict__ poses, const 
 #endif
 // KIND 0: every record of [rec_begin, n_records) (one thread each, edges and planes as they come); KIND 1 / 2: the launch covers
 // the batch's corner / surf features only (thread = feature index in its cloud), so that the compiler sees one of the two fits.
+// The whole-batch plane form (KIND 2) reads its neighbour lists from `rec` itself: one wavefront owns one tile (thread = plane slot, 64
+// consecutive slots per wavefront), loads the tile's lists and overwrites the tile with the records.  A lane's {N.z, N.C} covers the
+// bytes of other lanes' p4, so `rec` is not __restrict__ and the loads are pinned ahead of everything that follows; they sit in
+// uniform control flow, so all 64 lists have been requested by one instruction each before any lane can store.
 template <bool DESKEW, int KIND>
 __device__ __forceinline__ void fit_one(const BatchView& bv, const float4* __restrict__ map_c, const float4* __restrict__ map_s,
-                                        const int* __restrict__ nn, double line_ratio, double plane_tol, const DeskewView& dv,
-                                        double* __restrict__ rec, double* __restrict__ full, int block) {
+                                        const int* nn, double line_ratio, double plane_tol, const DeskewView& dv,
+                                        double* rec, double* __restrict__ full, int block) {
+  static_assert(kAssocBlock % kRecTileRows == 0, "a wavefront of the whole-batch fit owns one record tile");
   int g = 0, b = 0, local = 0, nc = 0, fi = 0;
-  size_t slot;
+  size_t slot = 0;
   if (KIND == 0) {
     g = bv.rec_begin + block * blockDim.x + threadIdx.x;
     if (g >= batch_records(bv)) return;
@@ -424,18 +455,20 @@ __device__ __forceinline__ void fit_one(const BatchView& bv, const float4* __res
     nc = bv.corner_off[b + 1] - bv.corner_off[b];
     slot = (size_t)g;
   } else {
-    // whole-batch form: neighbour slot and record offset are functions of the feature's index alone (feature_slot): no scan search,
-    // the wavefront's first load is its neighbour list
+    // whole-batch form: neighbour slot and record offset are functions of the feature's index alone (corner_slot, plane_slot): no scan
+    // search, the wavefront's first load is its neighbour list
     fi = (KIND == 1 ? bv.c0 : bv.s0) + block * blockDim.x + threadIdx.x;
     if (fi >= (KIND == 1 ? bv.c0 + (bv.n_records - bv.n_surf_total) : bv.s0 + bv.n_surf_total)) return;
-    slot = feature_slot(bv, KIND == 1, fi);
+    if (KIND == 1) slot = corner_slot(bv, fi);
   }
-  const int* in = nn + 5 * slot;
   const bool is_edge = KIND == 0 ? local < nc : KIND == 1;
   FitOut fo; fo.ok = false; fo.C = mk3(0, 0, 0); fo.N = mk3(0, 0, 0);
   // all five indices at once and the five neighbours unconditionally (index 0 stands in when there is no match): behind the
   // `p0 >= 0` test the loads came as three dependent round trips (first index, the other four, the points)
-  const int p0 = in[0], p1 = in[1], p2 = in[2], p3 = in[3], p4 = in[4];
+  int pl[5];
+  if (KIND == 2) { plane_nn_load(rec, plane_slot(bv, fi), pl); asm volatile("" ::: "memory"); }
+  else { const int* in = nn + 5 * slot; pl[0] = in[0]; pl[1] = in[1]; pl[2] = in[2]; pl[3] = in[3]; pl[4] = in[4]; }
+  const int p0 = pl[0], p1 = pl[1], p2 = pl[2], p3 = pl[3], p4 = pl[4];
   const float4* mp = is_edge ? map_c : map_s;
   const bool have = p0 >= 0;                                  // no match: the other four slots were never written
   const float4 nb[5] = {mp[have ? p0 : 0], mp[have ? p1 : 0], mp[have ? p2 : 0], mp[have ? p3 : 0], mp[have ? p4 : 0]};
@@ -457,8 +490,7 @@ __device__ __forceinline__ void fit_one(const BatchView& bv, const float4* __res
     out[0] = fo.C.x; out[1] = fo.C.y; out[2] = fo.C.z;
     out[3] = fo.N.x; out[4] = fo.N.y; out[5] = fo.N.z;
   } else {
-    double* out = rec + plane_rec_off(bv, KIND == 0 ? bv.surf_off[b] + (local - nc) : fi);
-    out[0] = fo.N.x; out[1] = fo.N.y; out[2] = fo.N.z; out[3] = dot(fo.N, fo.C);
+    plane_rec_store(rec, plane_slot(bv, KIND == 0 ? bv.surf_off[b] + (local - nc) : fi), fo.N.x, fo.N.y, fo.N.z, dot(fo.N, fo.C));
   }
   if (KIND == 0 && full) {                                      // (the whole-batch form is not launched with a `full` output)
     double* o = full + 6 * (size_t)g;
@@ -482,8 +514,8 @@ fit_scan2map_kernel(BatchView bv, const float4* __restrict__ map_c, const float4
 #endif
 __global__ void __launch_bounds__(kAssocBlock, MSFL_FIT_SPLIT_WAVES)
 fit_scan2map_split_kernel(BatchView bv, const float4* __restrict__ map_c, const float4* __restrict__ map_s,
-                          const int* __restrict__ nn, double line_ratio, double plane_tol, DeskewView dv,
-                          double* __restrict__ rec, double* __restrict__ full, int edge_blocks) {
+                          const int* nn, double line_ratio, double plane_tol, DeskewView dv,
+                          double* rec, double* __restrict__ full, int edge_blocks) {      // (rec: see fit_one)
   if ((int)blockIdx.x < edge_blocks) fit_one<false, 1>(bv, map_c, map_s, nn, line_ratio, plane_tol, dv, rec, full, (int)blockIdx.x);
   else fit_one<false, 2>(bv, map_c, map_s, nn, line_ratio, plane_tol, dv, rec, full, (int)blockIdx.x - edge_blocks);
 }
@@ -501,8 +533,7 @@ __global__ void __launch_bounds__(256) pack_records_kernel(BatchView bv, const d
 #pragma unroll
     for (int k = 0; k < 6; k++) out[k] = in[k];
   } else {
-    double* out = rec + plane_rec_off(bv, bv.surf_off[b] + (local - nc));
-    out[0] = in[3]; out[1] = in[4]; out[2] = in[5]; out[3] = in[3] * in[0] + in[4] * in[1] + in[5] * in[2];
+    plane_rec_store(rec, plane_slot(bv, bv.surf_off[b] + (local - nc)), in[3], in[4], in[5], in[3] * in[0] + in[4] * in[1] + in[5] * in[2]);
   }
 }
 
@@ -633,7 +664,8 @@ __device__ __forceinline__ void evaluate_pass(const pose7& T, double huber,
                                               const float4* __restrict__ surf, int ns,
                                               const double* __restrict__ pprime,   // may be null
                                               const double* __restrict__ rec,      // this scan's edge records
-                                              const double* __restrict__ recp,     // this scan's plane records
+                                              const double* __restrict__ recp,     // the record buffer (plane tiles first) ...
+                                              size_t g0,                           // ... and this scan's first plane slot in it
                                               PlaneCache<BLOCK>& pc, EdgeList& el,
                                               double (&acc)[kAcc], int& n_edge, int& n_plane) {
 #pragma unroll
@@ -761,8 +793,7 @@ __device__ __forceinline__ void evaluate_pass(const pose7& T, double huber,
 #pragma unroll
       for (int u = 0; u < kGroup; u++) {
         const int iu = min(i + u * BLOCK, ns - 1);
-        const double* r4 = recp + 4 * (size_t)iu;
-        gn[u][0] = r4[0]; gn[u][1] = r4[1]; gn[u][2] = r4[2]; gn[u][3] = r4[3];
+        plane_rec_load(recp, g0 + (size_t)iu, gn[u]);
         gf[u] = surf[iu];
       }
 #pragma unroll
@@ -778,7 +809,8 @@ __device__ __forceinline__ void evaluate_pass(const pose7& T, double huber,
     }
   }
   for (; i < ns; i += BLOCK) {
-    const double* r4 = recp + 4 * (size_t)i;
+    double r4[4];
+    plane_rec_load(recp, g0 + (size_t)i, r4);
     const d3 N = mk3(r4[0], r4[1], r4[2]); const double d0 = r4[3];
     d3 p;
     if (pprime) { const size_t q = (size_t)(nc + i); p = mk3(pprime[3 * q], pprime[3 * q + 1], pprime[3 * q + 2]); }

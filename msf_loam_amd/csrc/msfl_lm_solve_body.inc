@@ -46,7 +46,8 @@
   const float4* surf = bv.surf + bv.surf_off[b];
   const size_t r0 = (size_t)bv.rec_off[b];
   const double* rec = rec_all + edge_rec_off(bv, bv.corner_off[b]);
-  const double* recp = rec_all + plane_rec_off(bv, bv.surf_off[b]);
+  const double* recp = rec_all;
+  const size_t g0 = plane_slot(bv, bv.surf_off[b]);
   const double* pprime = pprime_all ? pprime_all + 3 * r0 : nullptr;
   double* pose_g = poses + 7 * (size_t)b;
   TrState& tr = sh.tr;
@@ -58,7 +59,7 @@
     int ne, np;
     const pose7 T = load_pose(pose_g);
     LM_T(t0);
-    evaluate_pass<BLOCK, true>(T, prm.huber, corner, nc, surf, ns, pprime, rec, recp, s_cache, s_edges, acc, ne, np);
+    evaluate_pass<BLOCK, true>(T, prm.huber, corner, nc, surf, ns, pprime, rec, recp, g0, s_cache, s_edges, acc, ne, np);
     LM_T(t1);
     block_reduce<BLOCK>(sh, acc, ne, np);
     LM_T(t2);
@@ -138,7 +139,7 @@
     const pose7 T = load_pose(tr.cand);   // lane 0 overwrites go / cand only after the reduction's barrier, which every
                                            // thread reaches after this read: no barrier of its own needed
     LM_T(t0);
-    evaluate_pass<BLOCK, false>(T, prm.huber, corner, nc, surf, ns, pprime, rec, recp, s_cache, s_edges, acc, ne, np);
+    evaluate_pass<BLOCK, false>(T, prm.huber, corner, nc, surf, ns, pprime, rec, recp, g0, s_cache, s_edges, acc, ne, np);
     LM_T(t1);
     block_reduce<BLOCK>(sh, acc, ne, np);
     LM_T(t2);

@@ -63,10 +63,12 @@ assoc_scan2scan_kernel(BatchView bv, OdomView ov, const double* __restrict__ pos
   const int qi = q0 + threadIdx.x;
   const bool has_q = qi < nq;
   // compact records: sharp (edge) features 6 doubles {C,N}, flat (plane) features 4 doubles {N, N.C}
-  double* out = rec + (qi < n_sharp ? edge_rec_off(bv, bv.corner_off[b] + qi) : plane_rec_off(bv, bv.surf_off[b] + (qi - n_sharp)));
+  // element k of this query's record: an edge record is 6 consecutive doubles, a plane row sits in its tile (msfl_record_tiles.h)
+  const size_t out0 = qi < n_sharp ? edge_rec_off(bv, bv.corner_off[b] + qi) : plane_slot(bv, bv.surf_off[b] + (qi - n_sharp));
+  auto out = [&](int k) -> double& { return rec[qi < n_sharp ? out0 + k : rec_tile_elem(out0, k)]; };
   const int out_len = qi < n_sharp ? 6 : 4;
   if (status[b] != 0) {
-    if (has_q) for (int k = 0; k < out_len; k++) out[k] = 0.0;
+    if (has_q) for (int k = 0; k < out_len; k++) out(k) = 0.0;
     return;
   }
   // plane_mode[b] == 0: the column-grid kernel below owns this pair's plane queries
@@ -187,10 +189,10 @@ assoc_scan2scan_kernel(BatchView bv, OdomView ov, const double* __restrict__ pos
           C = odom_centroid3(A, Bp, Cp);
         }
       }
-      if (edge_pass) { out[0] = C.x; out[1] = C.y; out[2] = C.z; out[3] = N.x; out[4] = N.y; out[5] = N.z; }
-      else { out[0] = N.x; out[1] = N.y; out[2] = N.z; out[3] = dot(N, C); }
+      if (edge_pass) { out(0) = C.x; out(1) = C.y; out(2) = C.z; out(3) = N.x; out(4) = N.y; out(5) = N.z; }
+      else { plane_rec_store(rec, out0, N.x, N.y, N.z, dot(N, C)); }
     } else if (mine) {
-      for (int k = 0; k < out_len; k++) out[k] = 0.0;
+      for (int k = 0; k < out_len; k++) out(k) = 0.0;
     }
   }
 }
@@ -232,7 +234,8 @@ assoc_scan2scan_wave_kernel(BatchView bv, OdomView ov, const double* __restrict_
   const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (qi >= n_sharp + n_flat) return;
   const bool edge = qi < n_sharp;
-  double* out = rec + (edge ? edge_rec_off(bv, bv.corner_off[b] + qi) : plane_rec_off(bv, bv.surf_off[b] + (qi - n_sharp)));
+  const size_t out0 = edge ? edge_rec_off(bv, bv.corner_off[b] + qi) : plane_slot(bv, bv.surf_off[b] + (qi - n_sharp));
+  auto out = [&](int k) -> double& { return rec[edge ? out0 + k : rec_tile_elem(out0, k)]; };
   const int out_len = edge ? 6 : 4;
   const float4* tp = edge ? ov.last_ls + ov.last_ls_off[b] : ov.last_lf + ov.last_lf_off[b];
   const uint16_t* tr = edge ? ov.last_ls_ring + ov.last_ls_off[b] : ov.last_lf_ring + ov.last_lf_off[b];
@@ -254,7 +257,7 @@ assoc_scan2scan_wave_kernel(BatchView bv, OdomView ov, const double* __restrict_
     closest = best.j;
   }
   if (!ok) {
-    if (lane < out_len) out[lane] = 0.0;
+    if (lane < out_len) out(lane) = 0.0;
     return;
   }
   const int id = tr[closest];
@@ -300,7 +303,7 @@ assoc_scan2scan_wave_kernel(BatchView bv, OdomView ov, const double* __restrict_
       const d3 A = mk3((double)a.x, (double)a.y, (double)a.z), Bp = mk3((double)c.x, (double)c.y, (double)c.z);
       N = odom_unit(A - Bp); C = A;
     }
-    out[0] = C.x; out[1] = C.y; out[2] = C.z; out[3] = N.x; out[4] = N.y; out[5] = N.z;
+    out(0) = C.x; out(1) = C.y; out(2) = C.z; out(3) = N.x; out(4) = N.y; out(5) = N.z;
   } else {
     if (min2 >= 0 && min3 >= 0) {
       const float4 a = tp[closest], c = tp[min2], e = tp[min3];
@@ -309,7 +312,7 @@ assoc_scan2scan_wave_kernel(BatchView bv, OdomView ov, const double* __restrict_
       N = odom_unit(cross(A - Bp, A - Cp));
       C = odom_centroid3(A, Bp, Cp);
     }
-    out[0] = N.x; out[1] = N.y; out[2] = N.z; out[3] = dot(N, C);
+    plane_rec_store(rec, out0, N.x, N.y, N.z, dot(N, C));
   }
 }
 
@@ -767,7 +770,8 @@ __device__ __forceinline__ void odom_grid_query(const BatchView& bv, const OdomV
   const int qf = tile * (kOdomBlock / L) + threadIdx.x / L;
   if (qf >= (EDGE ? n_sharp : n_flat)) return;
   constexpr int kOut = EDGE ? 6 : 4;
-  double* out = rec + (EDGE ? edge_rec_off(bv, bv.corner_off[b] + qf) : plane_rec_off(bv, bv.surf_off[b] + qf));
+  const size_t out0 = EDGE ? edge_rec_off(bv, bv.corner_off[b] + qf) : plane_slot(bv, bv.surf_off[b] + qf);
+  auto out = [&](int k) -> double& { return rec[EDGE ? out0 + k : rec_tile_elem(out0, k)]; };
   const int* t_off = EDGE ? ov.last_ls_off : ov.last_lf_off;
   const int s0 = t_off[b], s1 = t_off[b + 1];
   const float4* tp = (EDGE ? ov.last_ls : ov.last_lf) + s0;
@@ -779,7 +783,7 @@ __device__ __forceinline__ void odom_grid_query(const BatchView& bv, const OdomV
     q = transform_point_f32(load_pose(poses + 7 * b), f.x, f.y, f.z);
     ok = fabsf(q.x) < (float)(kOdomRange + 7) && fabsf(q.y) < (float)(kOdomRange + 7);   // also rejects NaN
   }
-  if (!ok) { if (sl < kOut) out[sl] = 0.0; return; }
+  if (!ok) { if (sl < kOut) out(sl) = 0.0; return; }
   const float fx = floorf(q.x), fy = floorf(q.y);
   const OdomPairDesc pd = ix.desc[b];
   const int cx = (int)fx - pd.ox, cy = (int)fy - pd.oy;           // may lie outside [0, W) x [0, H): the walk clips
@@ -805,7 +809,7 @@ __device__ __forceinline__ void odom_grid_query(const BatchView& bv, const OdomV
     kbest = group_min_key<L>(kbest);
     if (__uint_as_float((unsigned)(kbest >> 32)) < odom_gap_sq(q, fx, fy, r)) break;
   }
-  if (!(__uint_as_float((unsigned)(kbest >> 32)) < thr)) { if (sl < kOut) out[sl] = 0.0; return; }    // :87 / :173 (NaN / none: not <)
+  if (!(__uint_as_float((unsigned)(kbest >> 32)) < thr)) { if (sl < kOut) out(sl) = 0.0; return; }    // :87 / :173 (NaN / none: not <)
   const int closest = (int)((unsigned)kbest & 0xffffffu), id = (int)((unsigned)kbest >> 24 & 0xffu);
   // ---- ring-window minima (:183-232).  The reference sweeps forward from `closest` (rings up to id + nearby_scan), then
   //      backward (down to id - nearby_scan), with running minima that start at the gate and are replaced on strict '<':
@@ -867,7 +871,7 @@ __device__ __forceinline__ void odom_grid_query(const BatchView& bv, const OdomV
       N = odom_unit(A - Bp);
       C = A;
     }
-    out[0] = C.x; out[1] = C.y; out[2] = C.z; out[3] = N.x; out[4] = N.y; out[5] = N.z;
+    out(0) = C.x; out(1) = C.y; out(2) = C.z; out(3) = N.x; out(4) = N.y; out(5) = N.z;
     return;
   }
   if (min2 >= 0 && min3 >= 0) {                                  // :234-256, lidar_factor.h:70-78
@@ -877,7 +881,7 @@ __device__ __forceinline__ void odom_grid_query(const BatchView& bv, const OdomV
     N = odom_unit(cross(A - Bp, A - Cp));
     C = odom_centroid3(A, Bp, Cp);
   }
-  out[0] = N.x; out[1] = N.y; out[2] = N.z; out[3] = dot(N, C);
+  plane_rec_store(rec, out0, N.x, N.y, N.z, dot(N, C));
 }
 
 // One launch for both query kinds: blocks [0, plane_blocks) serve the flat queries, the rest the sharp ones.  The edge

@@ -33,7 +33,7 @@ struct RejectScan {
   int nc, ns;                 // corner / surf features
   const float4* corner; const float4* surf;
   double* rec;                // its edge records {C, N}
-  double* recp;               // its plane records {N, d0}
+  double* recp; size_t g0;    // the record buffer and the scan's first plane slot in it: plane records {N, d0} (plane_rec_load)
   const double* pprime;       // de-skew: its f64 points p' (corner features first), else null
 };
 
@@ -44,7 +44,7 @@ __device__ __forceinline__ RejectScan reject_scan(const BatchView& bv, const dou
   s.corner = bv.corner + bv.corner_off[b];
   s.surf = bv.surf + bv.surf_off[b];
   s.rec = rec_all + edge_rec_off(bv, bv.corner_off[b]);
-  s.recp = rec_all + plane_rec_off(bv, bv.surf_off[b]);
+  s.recp = rec_all; s.g0 = plane_slot(bv, bv.surf_off[b]);
   s.pprime = pprime_all ? pprime_all + 3 * (size_t)bv.rec_off[b] : nullptr;
   return s;
 }
@@ -68,7 +68,8 @@ __device__ __forceinline__ bool reject_residual(const RejectScan& sc, const mat3
     const d3 r = cross(N, d);
     s = __builtin_fma(r.x, r.x, __builtin_fma(r.y, r.y, r.z * r.z));
   } else {
-    const double* r4 = sc.recp + 4 * (size_t)k;
+    double r4[4];
+    plane_rec_load(sc.recp, sc.g0 + (size_t)k, r4);
     const d3 N = mk3(r4[0], r4[1], r4[2]);
     if (N.x == 0.0 && N.y == 0.0 && N.z == 0.0) return false;
     const double r = __builtin_fma(N.x, q.x, __builtin_fma(N.y, q.y, N.z * q.z)) - r4[3];
@@ -80,7 +81,7 @@ __device__ __forceinline__ bool reject_residual(const RejectScan& sc, const mat3
 // A rejected record becomes a refused correspondence: N = 0 (and d0 = 0 for a plane).  Plain vector stores.
 __device__ __forceinline__ void reject_zero(const RejectScan& sc, int i) {
   if (i < sc.nc) { double* r6 = sc.rec + 6 * (size_t)i; r6[3] = 0.0; r6[4] = 0.0; r6[5] = 0.0; }
-  else { double* r4 = sc.recp + 4 * (size_t)(i - sc.nc); r4[0] = 0.0; r4[1] = 0.0; r4[2] = 0.0; r4[3] = 0.0; }
+  else plane_rec_store(sc.recp, sc.g0 + (size_t)(i - sc.nc), 0.0, 0.0, 0.0, 0.0);
 }
 
 // grid: x = chunks of kRejectBlock records over the call's longest scan, y = scan row0 + blockIdx.y.  `out` (may be null) was zeroed

@@ -28,12 +28,13 @@
     const float4* corner = bv.corner + bv.corner_off[b];
     const float4* surf = bv.surf + bv.surf_off[b];
     const double* rec = rec_all + edge_rec_off(bv, bv.corner_off[b]);
-    const double* recp = rec_all + plane_rec_off(bv, bv.surf_off[b]);
+    const double* recp = rec_all;
+    const size_t g0 = plane_slot(bv, bv.surf_off[b]);
     const double* pprime = pprime_all ? pprime_all + 3 * (size_t)bv.rec_off[b] : nullptr;
     double acc[kAcc];
     int ne, np;
     const pose7 T = load_pose(poses + 7 * (size_t)b);
-    evaluate_pass<BLOCK, true>(T, huber, corner, nc, surf, ns, pprime, rec, recp, s_cache, s_edges, acc, ne, np);
+    evaluate_pass<BLOCK, true>(T, huber, corner, nc, surf, ns, pprime, rec, recp, g0, s_cache, s_edges, acc, ne, np);
     block_reduce<BLOCK>(sh, acc, ne, np);
 #if MSFL_UNC_PRIOR
     if (use_prior && threadIdx.x == 0) prior_accumulate(T, &s_prior, sh.red);
