@@ -139,6 +139,30 @@ enum TimerClass { T_ASSOC = 0, T_SOLVE, T_INDEX, T_EXTRACT, T_ODOM, T_FIT, T_ASS
 
 struct TimedSpan { hipEvent_t a, b; int cls; };
 
+// ---- What a registration call carries besides its clouds.  RegOptions: the value knobs of the optional features (the handle keeps one,
+// the SLAM session one per matcher).  RecordSink: where the handle's caller wants one record per registration (or, for the prior, gives
+// one).  RegSinks, below the handle: the options plus the device pointers one call's kernels use.  A new optional feature adds one member
+// to RegOptions, one RecordSink to the handle and one SlotRecords to the SLAM session (msfl_api_slam.inc).
+struct RejectOptions {               // msfl_set_outlier_rejection, normalised (reject_options): the inactive mode's parameter is zero
+  int mode = MSFL_REJECT_OFF;        // MSFL_REJECT_OFF = feature off
+  double thr2 = 0.0, fraction = 0.0; // threshold squared; fraction
+  int which = MSFL_REJECT_LAST_OUTER;
+};
+struct RegOptions {
+  double unc_min_eig = 0.0;
+  int degen_on = 0;                  // msfl_set_degeneracy: 0 = feature off
+  double degen_min_eig = 0.0;
+  RejectOptions rej;
+};
+struct RecordSink {
+  void* out = nullptr;               // the caller's array (the prior: its records, read only); null: none
+  int capacity = 0;                  // records it holds
+  msfl_mem mem = MSFL_MEM_HOST;
+  DevBuf dev;                        // device staging of a host array
+  void set(const void* p, int n, msfl_mem m) { out = const_cast<void*>(p); capacity = p ? n : 0; mem = m; }
+  bool host() const { return out && mem == MSFL_MEM_HOST; }
+};
+
 }  // namespace
 
 struct msfl_handle_s {
@@ -185,32 +209,11 @@ struct msfl_handle_s {
   DevBuf pr[5];   // batched (map, scan) pairs: map offsets and cell-table bases per cloud kind, preset status
   DevBuf sc[8];   // msfl_score_poses*: staged clouds and poses, offset table, records, per-feature outputs, scan of each hypothesis (no other call touches them)
 
-  // msfl_set_uncertainty: where every matcher call writes one msfl_match_uncertainty per registration (null: feature off)
-  msfl_match_uncertainty* unc_out = nullptr;
-  int unc_capacity = 0;
-  msfl_mem unc_mem = MSFL_MEM_HOST;
-  double unc_min_eigenvalue = 0.0;
-  DevBuf unc_dev;                         // device staging of a host sink
-  // msfl_set_pose_prior: priors[b] joins the problem of registration b of every matcher call (null: feature off)
-  const msfl_pose_prior* prior_in = nullptr;
-  int prior_count = 0;
-  msfl_mem prior_mem = MSFL_MEM_HOST;
-  DevBuf prior_dev;                       // device staging of host records
-  // msfl_set_degeneracy: every solve holds the eigen-directions of its entry matrix below the threshold (0: feature off)
-  int degen_on = 0;
-  double degen_min_eigenvalue = 0.0;
-  msfl_degeneracy_record* degen_out = nullptr;   // optional sink, one record per registration
-  int degen_capacity = 0;
-  msfl_mem degen_mem = MSFL_MEM_HOST;
-  DevBuf degen_dev;                       // device staging of a host sink
-  // msfl_set_outlier_rejection: records are rejected between association and solve (mode MSFL_REJECT_OFF: feature off)
-  int rej_mode = MSFL_REJECT_OFF;
-  double rej_thr2 = 0.0, rej_fraction = 0.0;     // threshold squared; fraction
-  int rej_which = MSFL_REJECT_LAST_OUTER;
-  msfl_rejection_record* rej_out = nullptr;      // optional sink, one record per registration
-  int rej_capacity = 0;
-  msfl_mem rej_mem = MSFL_MEM_HOST;
-  DevBuf rej_dev;                         // device staging of a host sink
+  // msfl_set_uncertainty / msfl_set_degeneracy / msfl_set_outlier_rejection: the knobs, and where every matcher call writes one
+  // record per registration.  The uncertainty feature is on while its sink is set; a degeneracy or rejection sink is optional and
+  // null while its feature is off.  msfl_set_pose_prior: prior.out[b] joins the problem of registration b (null: feature off).
+  RegOptions opt;
+  RecordSink unc, degen, rej, prior;
   DevBuf rej_keys;                        // fraction mode: one u64 per record of the call
 
   PinRing pin;
@@ -311,43 +314,82 @@ static_assert(sizeof(DevMatchInfo) == sizeof(msfl_match_info), "info layout");
 static_assert(sizeof(DegenRecord) == sizeof(msfl_degeneracy_record), "degeneracy record layout");
 static_assert(sizeof(RejectRecord) == sizeof(msfl_rejection_record) && sizeof(RejectRecord) == 56, "rejection record layout");
 struct RegSinks {
+  RegOptions opt;
   DevMatchInfo* info = nullptr;      // never null when `unc` is not: the uncertainty record takes sigma2 from the solve's own final cost
   UncRecord* unc = nullptr;          // null: feature off
   const PosePrior* prior = nullptr;  // null: feature off
-  double unc_min_eig = 0.0;
-  int degen_on = 0;                  // msfl_set_degeneracy: 0 = feature off
-  double degen_min_eig = 0.0;
   DegenRecord* degen = nullptr;      // optional record sink of the feature (zeroed before the first solve)
-  int rej_mode = MSFL_REJECT_OFF;    // msfl_set_outlier_rejection: MSFL_REJECT_OFF = feature off
-  double rej_thr2 = 0.0, rej_fraction = 0.0;
-  int rej_which = MSFL_REJECT_LAST_OUTER;
   RejectRecord* rej = nullptr;       // optional record sink of the feature (zeroed before the first solve)
   RegSinks at(int b) const {         // a part of a batch
-    return {info ? info + b : nullptr, unc ? unc + b : nullptr, prior ? prior + b : nullptr, unc_min_eig, degen_on, degen_min_eig,
-            degen ? degen + b : nullptr, rej_mode, rej_thr2, rej_fraction, rej_which, rej ? rej + b : nullptr};
+    RegSinks k = *this;
+    if (info) k.info += b;
+    if (unc) k.unc += b;
+    if (prior) k.prior += b;
+    if (degen) k.degen += b;
+    if (rej) k.rej += b;
+    return k;
   }
 };
+
+// msfl_outlier_rejection as the solve takes it, for msfl_set_outlier_rejection and each matcher of msfl_slam_set_outlier_rejection
+// (`who`: the caller's name).  Null or MSFL_REJECT_OFF gives the defaults; a bad field gives MSFL_BAD_ARG and *err says which.
+msfl_status reject_options(const msfl_outlier_rejection* cfg, const char* who, RejectOptions* out, std::string* err) {
+  *out = RejectOptions{};
+  if (!cfg || cfg->mode == MSFL_REJECT_OFF) return MSFL_OK;
+  const char* bad = nullptr;
+  if (cfg->mode != MSFL_REJECT_THRESHOLD && cfg->mode != MSFL_REJECT_FRACTION) bad = "unknown mode";
+  else if (cfg->which != MSFL_REJECT_LAST_OUTER && cfg->which != MSFL_REJECT_EVERY_OUTER)
+    bad = "`which` is neither MSFL_REJECT_LAST_OUTER nor MSFL_REJECT_EVERY_OUTER";
+  else if (cfg->mode == MSFL_REJECT_THRESHOLD && !(cfg->threshold >= 0.0 && std::isfinite(cfg->threshold))) bad = "threshold negative or not finite";
+  else if (cfg->mode == MSFL_REJECT_FRACTION && !(cfg->fraction >= 0.0 && cfg->fraction <= 1.0)) bad = "fraction outside [0, 1]";
+  if (bad) { *err = std::string(who) + ": " + bad; return MSFL_BAD_ARG; }
+  out->mode = cfg->mode;
+  out->which = cfg->which;
+  if (cfg->mode == MSFL_REJECT_THRESHOLD) out->thr2 = cfg->threshold * cfg->threshold;
+  else out->fraction = cfg->fraction;
+  return MSFL_OK;
+}
+
+// The three RecordSink helpers of reg_check / reg_open / reg_close.  sink_fits: does the sink hold n records (`what`: how the error
+// names it)?
+msfl_status sink_fits(msfl_handle* h, const RecordSink& k, int n, const char* who, const char* what) {
+  if (!k.out || n <= k.capacity) return MSFL_OK;
+  return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, " + what + std::to_string(k.capacity));
+}
+// Where the kernels write the n records: the caller's device array, or device staging of its host one (null: no sink); zero = cleared on st.
+template <class T>
+msfl_status sink_open(msfl_handle* h, RecordSink& k, int n, hipStream_t st, bool zero, T** d) {
+  *d = nullptr;
+  if (!k.out) return MSFL_OK;
+  if (k.mem == MSFL_MEM_DEVICE) *d = static_cast<T*>(k.out);
+  else {
+    HIPCHK(h, k.dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(T)));
+    *d = k.dev.as<T>();
+  }
+  if (zero && n > 0) HIPCHK(h, hipMemsetAsync(*d, 0, (size_t)n * sizeof(T), st));
+  return MSFL_OK;
+}
+// The n records go back to a host sink.
+template <class T>
+msfl_status sink_close(msfl_handle* h, const RecordSink& k, const T* d, int n, hipStream_t st) {
+  if (k.host() && d && n > 0) HIPCHK(h, hipMemcpyAsync(k.out, d, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st));
+  return MSFL_OK;
+}
 
 // First thing a matcher call does, before it stages or launches anything: refuse a call with more registrations than the sink holds or
 // than there are prior records, and host prior records with a non-finite entry (device records are checked by the solve kernel:
 // per-scan status MSFL_BAD_ARG).
 msfl_status reg_check(msfl_handle* h, int n, const char* who) {
-  if (h->unc_out && n > h->unc_capacity)
-    return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_uncertainty sink holds " +
-                                      std::to_string(h->unc_capacity));
-  if (h->degen_on && h->degen_out && n > h->degen_capacity)
-    return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_degeneracy sink holds " +
-                                      std::to_string(h->degen_capacity));
-  if (h->rej_mode != MSFL_REJECT_OFF && h->rej_out && n > h->rej_capacity)
-    return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, the msfl_set_outlier_rejection sink holds " +
-                                      std::to_string(h->rej_capacity));
-  if (!h->prior_in) return MSFL_OK;
-  if (n > h->prior_count)
+  msfl_status s = sink_fits(h, h->unc, n, who, "the msfl_set_uncertainty sink holds "); if (s) return s;
+  s = sink_fits(h, h->degen, n, who, "the msfl_set_degeneracy sink holds "); if (s) return s;
+  s = sink_fits(h, h->rej, n, who, "the msfl_set_outlier_rejection sink holds "); if (s) return s;
+  if (!h->prior.out) return MSFL_OK;
+  if (n > h->prior.capacity)
     return fail(h, MSFL_CAPACITY, std::string(who) + ": " + std::to_string(n) + " registrations, msfl_set_pose_prior gave " +
-                                      std::to_string(h->prior_count) + " records");
-  if (h->prior_mem == MSFL_MEM_HOST) {
+                                      std::to_string(h->prior.capacity) + " records");
+  if (h->prior.mem == MSFL_MEM_HOST) {
     for (int b = 0; b < n; b++) {
-      const double* w = reinterpret_cast<const double*>(h->prior_in + b);
+      const double* w = reinterpret_cast<const double*>(static_cast<const msfl_pose_prior*>(h->prior.out) + b);
       for (int k = 0; k < kPriorWords; k++)
         if (!std::isfinite(w[k]))
           return fail(h, MSFL_BAD_ARG, std::string(who) + ": the pose prior of registration " + std::to_string(b) + " has a non-finite entry (" +
@@ -357,47 +399,21 @@ msfl_status reg_check(msfl_handle* h, int n, const char* who) {
   return MSFL_OK;
 }
 
-inline bool unc_host(const msfl_handle* h) { return h->unc_out && h->unc_mem == MSFL_MEM_HOST; }
-inline bool degen_host(const msfl_handle* h) { return h->degen_on && h->degen_out && h->degen_mem == MSFL_MEM_HOST; }
-inline bool rej_host(const msfl_handle* h) { return h->rej_mode != MSFL_REJECT_OFF && h->rej_out && h->rej_mem == MSFL_MEM_HOST; }
-
 // Where the kernels of this call of n registrations find their sinks: the caller's device pointers, or device staging of its host ones
 // (the prior records are copied on stream st, ahead of the clearing of the info records).  want_info: the caller asked for the info records.
 msfl_status reg_open(msfl_handle* h, int n, hipStream_t st, bool want_info, RegSinks* k) {
   *k = RegSinks{};
-  k->unc_min_eig = h->unc_min_eigenvalue;
-  if (h->unc_out && h->unc_mem == MSFL_MEM_DEVICE) k->unc = reinterpret_cast<UncRecord*>(h->unc_out);
-  else if (h->unc_out) {
-    HIPCHK(h, h->unc_dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(UncRecord)));
-    k->unc = h->unc_dev.as<UncRecord>();
+  k->opt = h->opt;
+  msfl_status s = sink_open(h, h->unc, n, st, false, &k->unc); if (s) return s;
+  if (n > 0) {
+    PosePrior* prior;
+    s = sink_open(h, h->prior, n, st, false, &prior); if (s) return s;
+    if (h->prior.host()) HIPCHK(h, h->pin.upload(prior, h->prior.out, (size_t)n * sizeof(PosePrior), st));
+    k->prior = prior;
   }
-  if (h->prior_in && n > 0 && h->prior_mem == MSFL_MEM_DEVICE) k->prior = reinterpret_cast<const PosePrior*>(h->prior_in);
-  else if (h->prior_in && n > 0) {
-    HIPCHK(h, h->prior_dev.reserve((size_t)n * sizeof(PosePrior)));
-    HIPCHK(h, h->pin.upload(h->prior_dev.p, h->prior_in, (size_t)n * sizeof(PosePrior), st));
-    k->prior = h->prior_dev.as<PosePrior>();
-  }
-  if (h->degen_on) {
-    k->degen_on = 1;
-    k->degen_min_eig = h->degen_min_eigenvalue;
-    if (h->degen_out && h->degen_mem == MSFL_MEM_DEVICE) k->degen = reinterpret_cast<DegenRecord*>(h->degen_out);
-    else if (h->degen_out) {
-      HIPCHK(h, h->degen_dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(DegenRecord)));
-      k->degen = h->degen_dev.as<DegenRecord>();
-    }
-    // the solve kernel writes a slice only where it solves: every other slice stays all zero (valid = 0)
-    if (k->degen && n > 0) HIPCHK(h, hipMemsetAsync(k->degen, 0, (size_t)n * sizeof(DegenRecord), st));
-  }
-  if (h->rej_mode != MSFL_REJECT_OFF) {
-    k->rej_mode = h->rej_mode; k->rej_thr2 = h->rej_thr2; k->rej_fraction = h->rej_fraction; k->rej_which = h->rej_which;
-    if (h->rej_out && h->rej_mem == MSFL_MEM_DEVICE) k->rej = reinterpret_cast<RejectRecord*>(h->rej_out);
-    else if (h->rej_out) {
-      HIPCHK(h, h->rej_dev.reserve(std::max<size_t>(1, (size_t)n) * sizeof(RejectRecord)));
-      k->rej = h->rej_dev.as<RejectRecord>();
-    }
-    // the kernels write a slice only where a solve follows: every other slice stays all zero (valid = 0)
-    if (k->rej && n > 0) HIPCHK(h, hipMemsetAsync(k->rej, 0, (size_t)n * sizeof(RejectRecord), st));
-  }
+  // the kernels write a degeneracy or rejection slice only where they solve: every other slice stays all zero (valid = 0)
+  s = sink_open(h, h->degen, n, st, true, &k->degen); if (s) return s;
+  s = sink_open(h, h->rej, n, st, true, &k->rej); if (s) return s;
   if (want_info || k->unc) {
     HIPCHK(h, h->info.reserve((size_t)n * sizeof(DevMatchInfo)));
     HIPCHK(h, hipMemsetAsync(h->info.p, 0, (size_t)n * sizeof(DevMatchInfo), st));
@@ -406,7 +422,7 @@ msfl_status reg_open(msfl_handle* h, int n, hipStream_t st, bool want_info, RegS
   return MSFL_OK;
 }
 
-// What goes back to the caller: poses and status of a host-memory call, the info records, a host uncertainty sink; then the stream is
+// What goes back to the caller: poses and status of a host-memory call, the info records, the host record sinks; then the stream is
 // waited for if anything went to host memory.
 msfl_status reg_close(msfl_handle* h, int n, msfl_mem mem, double* poses_io, const double* d_poses, int* status, const int* d_status,
                       msfl_match_info* info, const RegSinks& k) {
@@ -416,12 +432,10 @@ msfl_status reg_close(msfl_handle* h, int n, msfl_mem mem, double* poses_io, con
     if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
   }
   if (info) HIPCHK(h, hipMemcpyAsync(info, k.info, (size_t)n * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
-  if (unc_host(h) && k.unc && n > 0) HIPCHK(h, hipMemcpyAsync(h->unc_out, k.unc, (size_t)n * sizeof(UncRecord), hipMemcpyDeviceToHost, st));
-  if (degen_host(h) && k.degen && n > 0)
-    HIPCHK(h, hipMemcpyAsync(h->degen_out, k.degen, (size_t)n * sizeof(DegenRecord), hipMemcpyDeviceToHost, st));
-  if (rej_host(h) && k.rej && n > 0)
-    HIPCHK(h, hipMemcpyAsync(h->rej_out, k.rej, (size_t)n * sizeof(RejectRecord), hipMemcpyDeviceToHost, st));
-  if (mem == MSFL_MEM_HOST || info || unc_host(h) || degen_host(h) || rej_host(h)) HIPCHK(h, hipStreamSynchronize(st));
+  msfl_status s = sink_close(h, h->unc, k.unc, n, st); if (s) return s;
+  s = sink_close(h, h->degen, k.degen, n, st); if (s) return s;
+  s = sink_close(h, h->rej, k.rej, n, st); if (s) return s;
+  if (mem == MSFL_MEM_HOST || info || h->unc.host() || h->degen.host() || h->rej.host()) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 
@@ -434,16 +448,16 @@ msfl_status solve_outer(msfl_handle* h, int n, const BatchView& bv, const double
                         const SolverParams& sp, int n_outer, Assoc&& assoc, int longest = -1) {
   hipStream_t st = h->stream;
   const double* records = h->records.as<double>();
-  if (k.rej_mode == MSFL_REJECT_FRACTION) HIPCHK(h, h->rej_keys.reserve(std::max<size_t>(1, (size_t)bv.n_records) * sizeof(unsigned long long)));
+  if (k.opt.rej.mode == MSFL_REJECT_FRACTION) HIPCHK(h, h->rej_keys.reserve(std::max<size_t>(1, (size_t)bv.n_records) * sizeof(unsigned long long)));
   for (int it = 0; it < n_outer; it++) {
     { const msfl_status as = assoc(it); if (as) return as; }
-    if (k.rej_mode != MSFL_REJECT_OFF && (k.rej_which == MSFL_REJECT_EVERY_OUTER || it == n_outer - 1))
-      launch_reject(st, k.rej_mode, n, longest < 0 ? bv.n_records : longest, bv, pprime, h->records.as<double>(), d_poses, d_status, k.rej, it,
-                    k.rej_thr2, k.rej_fraction, h->rej_keys.as<unsigned long long>());
+    if (k.opt.rej.mode != MSFL_REJECT_OFF && (k.opt.rej.which == MSFL_REJECT_EVERY_OUTER || it == n_outer - 1))
+      launch_reject(st, k.opt.rej.mode, n, longest < 0 ? bv.n_records : longest, bv, pprime, h->records.as<double>(), d_poses, d_status, k.rej, it,
+                    k.opt.rej.thr2, k.opt.rej.fraction, h->rej_keys.as<unsigned long long>());
     ScopedTimer timer(h, T_SOLVE);
-    launch_lm_solve<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, it, sp, k.prior, k.degen_on, k.degen_min_eig, k.degen);
+    launch_lm_solve<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, it, sp, k.prior, k.opt.degen_on, k.opt.degen_min_eig, k.degen);
   }
-  launch_uncertainty<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, n_outer - 1, sp, k.unc_min_eig, k.unc, k.prior);
+  launch_uncertainty<BLOCK>(st, n, bv, pprime, records, d_poses, d_status, k.info, n_outer - 1, sp, k.opt.unc_min_eig, k.unc, k.prior);
   HIPCHK(h, hipGetLastError());
   return MSFL_OK;
 }
@@ -841,10 +855,8 @@ msfl_status msfl_set_uncertainty(msfl_handle* h, msfl_match_uncertainty* out, in
   msfl_status s = enter(h); if (s) return s;
   if (out && (capacity < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE) || !(min_eigenvalue >= 0.0)))
     return fail(h, MSFL_BAD_ARG, "msfl_set_uncertainty: capacity < 1, unknown memory kind or a negative / NaN min_eigenvalue");
-  h->unc_out = out;
-  h->unc_capacity = out ? capacity : 0;
-  h->unc_mem = mem;
-  h->unc_min_eigenvalue = out ? min_eigenvalue : 0.0;
+  h->unc.set(out, capacity, mem);
+  h->opt.unc_min_eig = out ? min_eigenvalue : 0.0;
   return MSFL_OK;
 }
 
@@ -854,36 +866,22 @@ msfl_status msfl_set_degeneracy(msfl_handle* h, int enabled, double min_eigenval
     return fail(h, MSFL_BAD_ARG, "msfl_set_degeneracy: min_eigenvalue negative or not finite");
   if (enabled && out && (capacity < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE)))
     return fail(h, MSFL_BAD_ARG, "msfl_set_degeneracy: capacity < 1 or unknown memory kind");
-  h->degen_on = enabled != 0;
-  h->degen_min_eigenvalue = enabled ? min_eigenvalue : 0.0;
-  h->degen_out = enabled ? out : nullptr;
-  h->degen_capacity = enabled && out ? capacity : 0;
-  h->degen_mem = mem;
+  h->opt.degen_on = enabled != 0;
+  h->opt.degen_min_eig = enabled ? min_eigenvalue : 0.0;
+  h->degen.set(enabled ? out : nullptr, capacity, mem);
   return MSFL_OK;
 }
 
 msfl_status msfl_set_outlier_rejection(msfl_handle* h, const msfl_outlier_rejection* cfg, msfl_rejection_record* out, int capacity, msfl_mem mem) {
   msfl_status s = enter(h); if (s) return s;
-  const bool on = cfg && cfg->mode != MSFL_REJECT_OFF;
-  if (on) {
-    if (cfg->mode != MSFL_REJECT_THRESHOLD && cfg->mode != MSFL_REJECT_FRACTION)
-      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: unknown mode");
-    if (cfg->which != MSFL_REJECT_LAST_OUTER && cfg->which != MSFL_REJECT_EVERY_OUTER)
-      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: `which` is neither MSFL_REJECT_LAST_OUTER nor MSFL_REJECT_EVERY_OUTER");
-    if (cfg->mode == MSFL_REJECT_THRESHOLD && (!(cfg->threshold >= 0.0) || !std::isfinite(cfg->threshold)))
-      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: threshold negative or not finite");
-    if (cfg->mode == MSFL_REJECT_FRACTION && !(cfg->fraction >= 0.0 && cfg->fraction <= 1.0))
-      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: fraction outside [0, 1]");
-    if (out && (capacity < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE)))
-      return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: capacity < 1 or unknown memory kind");
-  }
-  h->rej_mode = on ? cfg->mode : MSFL_REJECT_OFF;
-  h->rej_thr2 = on && cfg->mode == MSFL_REJECT_THRESHOLD ? cfg->threshold * cfg->threshold : 0.0;
-  h->rej_fraction = on && cfg->mode == MSFL_REJECT_FRACTION ? cfg->fraction : 0.0;
-  h->rej_which = on ? cfg->which : MSFL_REJECT_LAST_OUTER;
-  h->rej_out = on ? out : nullptr;
-  h->rej_capacity = on && out ? capacity : 0;
-  h->rej_mem = mem;
+  RejectOptions rej;
+  std::string err;
+  s = reject_options(cfg, "msfl_set_outlier_rejection", &rej, &err); if (s) return fail(h, s, err);
+  const bool on = rej.mode != MSFL_REJECT_OFF;
+  if (on && out && (capacity < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE)))
+    return fail(h, MSFL_BAD_ARG, "msfl_set_outlier_rejection: capacity < 1 or unknown memory kind");
+  h->opt.rej = rej;
+  h->rej.set(on ? out : nullptr, capacity, mem);
   return MSFL_OK;
 }
 
@@ -891,9 +889,7 @@ msfl_status msfl_set_pose_prior(msfl_handle* h, const msfl_pose_prior* priors, i
   msfl_status s = enter(h); if (s) return s;
   if (priors && (count < 1 || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE)))
     return fail(h, MSFL_BAD_ARG, "msfl_set_pose_prior: count < 1 or unknown memory kind");
-  h->prior_in = priors;
-  h->prior_count = priors ? count : 0;
-  h->prior_mem = mem;
+  h->prior.set(priors, count, mem);
   return MSFL_OK;
 }
 

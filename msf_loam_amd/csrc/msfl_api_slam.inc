@@ -35,7 +35,53 @@ struct SlamScanBuf {                    // everything derived from ONE scan that
 };
 
 constexpr int kSlamSlots = 4;
-struct SlamJob { int k, n, imu_mode; bool unc; double unc_min_eig; bool prior_map; bool crop; int half[3]; bool degen, degen_map; double degen_map_min_eig; bool rej; msfl_outlier_rejection rej_map; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
+// What the msfl_slam_set_* calls said when a scan was fed: read once, at the top of slam_add_scan_impl; scans already fed keep theirs.
+struct SlamScanOptions {
+  RegOptions odo, map;                  // the two matchers' knobs
+  bool unc = false, degen_any = false, rej_any = false;   // the slot's record pairs travel with its result
+  bool prior_odo = false, prior_map = false;              // msfl_slam_set_next_prior gave this scan a record
+  bool crop = false;                    // msfl_slam_set_map_window: the stores are cropped after this scan's inserts
+  int half[3] = {};
+};
+struct SlamJob { int k = 0, n = 0, imu_mode = 0; SlamScanOptions o; };  // one scan's mapping chain, handed to the mapping thread once its odometry chain is enqueued
+
+// One optional feature's records: a pair per slot ({odometry, mapping}; the map window's: {corner, surf}) that the scan's chains
+// write on the device and that travels to the host with the slot's result copy.
+struct SlotRecords {
+  DevBuf dev[kSlamSlots];
+  PinBuf host;                          // kSlamSlots pairs
+  bool held[kSlamSlots] = {};           // the scan in this slot was fed with the feature on (the window: a crop ran on it)
+  size_t bytes = 0;                     // of one pair
+  hipError_t ensure(size_t pair_bytes) {                   // reserved when the feature is first turned on
+    if (host.p) return hipSuccess;
+    bytes = pair_bytes;
+    for (auto& b : dev) { const hipError_t e = b.reserve(bytes); if (e != hipSuccess) return e; }
+    return host.reserve(kSlamSlots * bytes);
+  }
+  hipError_t arm(int slot, bool on, bool zero, hipStream_t st) {   // a scan takes the slot; zero: a slice stays zero where no solve runs
+    held[slot] = on;
+    return on && zero ? hipMemsetAsync(dev[slot].p, 0, bytes, st) : hipSuccess;
+  }
+  hipError_t fetch(int slot, hipStream_t st) const {
+    return held[slot] ? hipMemcpyAsync(host.as<char>() + slot * bytes, dev[slot].p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+  }
+  template <class T> const T* host_at(int slot) const { return reinterpret_cast<const T*>(host.as<char>() + slot * bytes); }
+};
+
+// MSFL_SLAM_HOST_PROFILE: the wall clock of one thread's enqueue, by segment of the chain in order of first appearance.
+struct SegClock {
+  bool on;                              // (the first scans allocate: left out)
+  std::vector<std::pair<const char*, double>>* into;
+  std::chrono::steady_clock::time_point t;
+  void operator()(const char* what) {   // close the segment that ends here
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    const double dt = std::chrono::duration<double>(now - t).count();
+    t = now;
+    for (auto& e : *into) if (e.first == what) { e.second += dt; return; }
+    into->emplace_back(what, dt);
+  }
+};
 constexpr int kSlamProfileSkip = 20;                    // MSFL_SLAM_HOST_PROFILE leaves the first scans (allocations) out
 #ifndef MSFL_SLAM_ODOM_LANES
 #define MSFL_SLAM_ODOM_LANES 64
@@ -72,25 +118,11 @@ struct msfl_slam_s {
   DevBuf map_c, map_s;                  // surrounded map clouds
   DevBuf rec[kSlamSlots];               // device result records
   PinBuf rec_host;                      // kSlamSlots records
-  // msfl_slam_set_uncertainty: two msfl_match_uncertainty per slot {odometry, mapping}; they travel with the slot's result copy
+  // msfl_slam_set_uncertainty / _set_degeneracy / _set_outlier_rejection: the knobs of the two matchers {odometry, mapping} (both get the
+  // uncertainty's min_eigenvalue) and a record pair per slot and feature
   bool unc_on = false;
-  double unc_min_eigenvalue = 0.0;
-  DevBuf unc[kSlamSlots];
-  PinBuf unc_host;                      // kSlamSlots x 2 records
-  bool unc_held[kSlamSlots] = {};       // the scan in this slot was fed with the feature on
-  // msfl_slam_set_degeneracy: the two matchers' switches and thresholds; two msfl_degeneracy_record per slot {odometry, mapping},
-  // which travel with the slot's result copy like the uncertainty records
-  bool degen_on[2] = {};
-  double degen_min_eigenvalue[2] = {};
-  DevBuf degen[kSlamSlots];
-  PinBuf degen_host;                    // kSlamSlots x 2 records
-  bool degen_held[kSlamSlots] = {};     // the scan in this slot was fed with the feature on (either matcher)
-  // msfl_slam_set_outlier_rejection: the two matchers' configurations {odometry, mapping} (mode MSFL_REJECT_OFF: off); two
-  // msfl_rejection_record per slot, which travel with the slot's result copy like the degeneracy records
-  msfl_outlier_rejection rej_cfg[2] = {};
-  DevBuf rej[kSlamSlots];
-  PinBuf rej_host;                      // kSlamSlots x 2 records
-  bool rej_held[kSlamSlots] = {};       // the scan in this slot was fed with the feature on (either matcher)
+  RegOptions opt[2];
+  SlotRecords unc, degen, rej;
   // msfl_slam_set_next_prior: {odometry, mapping} records for the NEXT scan only.  They are copied to the slot of the scan that
   // consumes them (on its odometry stream, ahead of ev_odo), so a later msfl_slam_add_scan cannot overwrite what a queued
   // mapping chain has not read yet: a slot is reused only after its scan's record is out.
@@ -101,9 +133,7 @@ struct msfl_slam_s {
   // Two msfl_grid_crop_info {corner, surf} per slot; they travel with the slot's result copy.
   bool win_on = false;
   int win_half[3] = {}, win_every = 1;
-  DevBuf win[kSlamSlots];
-  PinBuf win_host;                      // kSlamSlots x 2 records
-  bool win_held[kSlamSlots] = {};       // a crop ran on the scan in this slot
+  SlotRecords win;
   hipEvent_t ev_done[kSlamSlots] = {};
   long long seq_c[kSlamSlots] = {}, seq_s[kSlamSlots] = {};   // map-store insert sequence numbers of the scan in each slot
   bool applied[kSlamSlots] = {};        // the slot's grid reports have been folded into the stores' host-side bounds
@@ -143,6 +173,7 @@ namespace {
 
 void slam_worker_main(msfl_slam* s);
 msfl_status slam_wait_mapped(msfl_slam* s, int k);
+msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb);
 
 enum { META_NMC = 0, META_NMS, META_STATUS, META_OFF, META_WORDS = 12 };
 enum { VM_MC = 0, VM_FC, VM_MS, VM_FS, VM_WORDS = 4 };
@@ -168,6 +199,34 @@ msfl_status slam_slot_ready(msfl_slam* s, int scan_index) {
   { const msfl_status ws = slam_wait_mapped(s, scan_index); if (ws) return ws; }
   SHIP(s, hipEventSynchronize(s->ev_done[scan_index % kSlamSlots]));
   return MSFL_OK;
+}
+// The getter `who` of a feature's record pair; refused for a scan that was fed while `setter` had the feature off.
+template <class T>
+msfl_status slam_get_pair(msfl_slam* s, SlotRecords msfl_slam_s::*feature, int scan_index, const char* who, const char* setter, T* odometry, T* mapping) {
+  if (!s) return MSFL_BAD_ARG;
+  const SlotRecords& r = s->*feature;
+  int slot;
+  { const msfl_status rs = slam_slot_of(s, scan_index, who, &slot); if (rs) return rs; }
+  if (!r.held[slot]) return sfail(s, MSFL_BAD_ARG, std::string(who) + ": that scan was fed with " + setter + " off");
+  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
+  const T* d = r.host_at<T>(slot);
+  if (odometry) *odometry = d[0];
+  if (mapping) *mapping = d[1];
+  return MSFL_OK;
+}
+
+// What matcher m (0 odometry, 1 mapping) of the scan in `slot` carries: the slot's first / second records.  A matcher whose feature is
+// off gets no record pointer even where the other matcher holds the pair.  (The prior was uploaded ahead of the scan's ev_odo.)
+RegSinks slam_sinks(msfl_slam* s, int slot, int m, const SlamScanOptions& o) {
+  msfl_slam_result* rec = s->rec[slot].as<msfl_slam_result>();
+  RegSinks k;
+  k.opt = m ? o.map : o.odo;
+  k.info = reinterpret_cast<DevMatchInfo*>(m ? &rec->mapping : &rec->odometry);
+  if (o.unc) k.unc = s->unc.dev[slot].as<UncRecord>() + m;
+  if (m ? o.prior_map : o.prior_odo) k.prior = s->prior[slot].as<PosePrior>() + m;
+  if (k.opt.degen_on) k.degen = s->degen.dev[slot].as<DegenRecord>() + m;
+  if (k.opt.rej.mode != MSFL_REJECT_OFF) k.rej = s->rej.dev[slot].as<RejectRecord>() + m;
+  return k;
 }
 
 __global__ void slam_result_kernel(msfl_slam_result* __restrict__ r, int scan_index, int* __restrict__ cnt, const double* __restrict__ poses_k,
@@ -479,12 +538,9 @@ msfl_status msfl_slam_set_uncertainty(msfl_slam* s, int enabled, double min_eige
   if (!s) return MSFL_BAD_ARG;
   if (enabled && !(min_eigenvalue >= 0.0)) return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_uncertainty: negative or NaN min_eigenvalue");
   SHIP(s, hipSetDevice(s->ho->device));
-  if (enabled && !s->unc_host.p) {
-    for (auto& b : s->unc) SHIP(s, b.reserve(2 * sizeof(UncRecord)));
-    SHIP(s, s->unc_host.reserve(kSlamSlots * 2 * sizeof(UncRecord)));
-  }
+  if (enabled) SHIP(s, s->unc.ensure(2 * sizeof(UncRecord)));
   s->unc_on = enabled != 0;             // read once per msfl_slam_add_scan: scans already fed keep what they were fed with
-  s->unc_min_eigenvalue = enabled ? min_eigenvalue : 0.0;
+  s->opt[0].unc_min_eig = s->opt[1].unc_min_eig = enabled ? min_eigenvalue : 0.0;
   return MSFL_OK;
 }
 
@@ -493,64 +549,36 @@ msfl_status msfl_slam_set_degeneracy(msfl_slam* s, int odometry, int mapping, do
   if ((odometry && !(min_eig_odometry >= 0.0 && std::isfinite(min_eig_odometry))) || (mapping && !(min_eig_mapping >= 0.0 && std::isfinite(min_eig_mapping))))
     return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_degeneracy: a threshold is negative or not finite");
   SHIP(s, hipSetDevice(s->ho->device));
-  if ((odometry || mapping) && !s->degen_host.p) {
-    for (auto& b : s->degen) SHIP(s, b.reserve(2 * sizeof(DegenRecord)));
-    SHIP(s, s->degen_host.reserve(kSlamSlots * 2 * sizeof(DegenRecord)));
-  }
-  s->degen_on[0] = odometry != 0;       // read once per msfl_slam_add_scan, like msfl_slam_set_uncertainty
-  s->degen_on[1] = mapping != 0;
-  s->degen_min_eigenvalue[0] = odometry ? min_eig_odometry : 0.0;
-  s->degen_min_eigenvalue[1] = mapping ? min_eig_mapping : 0.0;
+  if (odometry || mapping) SHIP(s, s->degen.ensure(2 * sizeof(DegenRecord)));
+  s->opt[0].degen_on = odometry != 0;   // read once per msfl_slam_add_scan, like msfl_slam_set_uncertainty
+  s->opt[1].degen_on = mapping != 0;
+  s->opt[0].degen_min_eig = odometry ? min_eig_odometry : 0.0;
+  s->opt[1].degen_min_eig = mapping ? min_eig_mapping : 0.0;
   return MSFL_OK;
 }
 
 msfl_status msfl_slam_get_degeneracy(msfl_slam* s, int scan_index, msfl_degeneracy_record* odometry, msfl_degeneracy_record* mapping) {
-  if (!s) return MSFL_BAD_ARG;
-  int slot;
-  { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_degeneracy", &slot); if (rs) return rs; }
-  if (!s->degen_held[slot]) return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_degeneracy: that scan was fed with msfl_slam_set_degeneracy off");
-  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
-  const msfl_degeneracy_record* d = s->degen_host.as<msfl_degeneracy_record>() + 2 * slot;
-  if (odometry) *odometry = d[0];
-  if (mapping) *mapping = d[1];
-  return MSFL_OK;
+  return slam_get_pair(s, &msfl_slam_s::degen, scan_index, "msfl_slam_get_degeneracy", "msfl_slam_set_degeneracy", odometry, mapping);
 }
 
 msfl_status msfl_slam_set_outlier_rejection(msfl_slam* s, const msfl_outlier_rejection* odometry, const msfl_outlier_rejection* mapping) {
   if (!s) return MSFL_BAD_ARG;
   const msfl_outlier_rejection* in[2] = {odometry, mapping};
-  msfl_outlier_rejection cfg[2] = {};
+  RejectOptions rej[2];
   for (int a = 0; a < 2; a++) {
-    if (!in[a] || in[a]->mode == MSFL_REJECT_OFF) continue;
-    const msfl_outlier_rejection& c = *in[a];
-    if ((c.mode != MSFL_REJECT_THRESHOLD && c.mode != MSFL_REJECT_FRACTION) || (c.which != MSFL_REJECT_LAST_OUTER && c.which != MSFL_REJECT_EVERY_OUTER))
-      return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_outlier_rejection: unknown mode or `which`");
-    if (c.mode == MSFL_REJECT_THRESHOLD && !(c.threshold >= 0.0 && std::isfinite(c.threshold)))
-      return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_outlier_rejection: a threshold is negative or not finite");
-    if (c.mode == MSFL_REJECT_FRACTION && !(c.fraction >= 0.0 && c.fraction <= 1.0))
-      return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_outlier_rejection: a fraction is outside [0, 1]");
-    cfg[a] = c;
+    std::string err;
+    const msfl_status rs = reject_options(in[a], a ? "msfl_slam_set_outlier_rejection (mapping)" : "msfl_slam_set_outlier_rejection (odometry)", &rej[a], &err);
+    if (rs) return sfail(s, rs, err);
   }
   SHIP(s, hipSetDevice(s->ho->device));
-  if ((cfg[0].mode || cfg[1].mode) && !s->rej_host.p) {
-    for (auto& b : s->rej) SHIP(s, b.reserve(2 * sizeof(RejectRecord)));
-    SHIP(s, s->rej_host.reserve(kSlamSlots * 2 * sizeof(RejectRecord)));
-  }
-  s->rej_cfg[0] = cfg[0];               // read once per msfl_slam_add_scan, like msfl_slam_set_degeneracy
-  s->rej_cfg[1] = cfg[1];
+  if (rej[0].mode || rej[1].mode) SHIP(s, s->rej.ensure(2 * sizeof(RejectRecord)));
+  s->opt[0].rej = rej[0];               // read once per msfl_slam_add_scan, like msfl_slam_set_degeneracy
+  s->opt[1].rej = rej[1];
   return MSFL_OK;
 }
 
 msfl_status msfl_slam_get_rejection(msfl_slam* s, int scan_index, msfl_rejection_record* odometry, msfl_rejection_record* mapping) {
-  if (!s) return MSFL_BAD_ARG;
-  int slot;
-  { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_rejection", &slot); if (rs) return rs; }
-  if (!s->rej_held[slot]) return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_rejection: that scan was fed with msfl_slam_set_outlier_rejection off");
-  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
-  const msfl_rejection_record* d = s->rej_host.as<msfl_rejection_record>() + 2 * slot;
-  if (odometry) *odometry = d[0];
-  if (mapping) *mapping = d[1];
-  return MSFL_OK;
+  return slam_get_pair(s, &msfl_slam_s::rej, scan_index, "msfl_slam_get_rejection", "msfl_slam_set_outlier_rejection", odometry, mapping);
 }
 
 msfl_status msfl_slam_set_next_prior(msfl_slam* s, const msfl_pose_prior* odometry, const msfl_pose_prior* mapping) {
@@ -579,10 +607,7 @@ msfl_status msfl_slam_set_map_window(msfl_slam* s, const int half_cells[3], int 
   if (half_cells[0] < 0 || half_cells[1] < 0 || half_cells[2] < 0 || every_n_scans < 1)
     return sfail(s, MSFL_BAD_ARG, "msfl_slam_set_map_window: negative half_cells or every_n_scans < 1");
   SHIP(s, hipSetDevice(s->ho->device));
-  if (!s->win_host.p) {
-    for (auto& b : s->win) SHIP(s, b.reserve(2 * CROP_WORDS * sizeof(int)));
-    SHIP(s, s->win_host.reserve(kSlamSlots * 2 * CROP_WORDS * sizeof(int)));
-  }
+  SHIP(s, s->win.ensure(2 * CROP_WORDS * sizeof(int)));
   for (int a = 0; a < 3; a++) s->win_half[a] = half_cells[a];
   s->win_every = every_n_scans;
   s->win_on = true;
@@ -595,24 +620,16 @@ msfl_status msfl_slam_get_map_window(msfl_slam* s, int scan_index, msfl_grid_cro
   { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_map_window", &slot); if (rs) return rs; }
   if (corner) std::memset(corner, 0, sizeof(*corner));
   if (surf) std::memset(surf, 0, sizeof(*surf));
-  if (!s->win_held[slot]) return MSFL_OK;                           // no crop ran on that scan
+  if (!s->win.held[slot]) return MSFL_OK;                           // no crop ran on that scan
   { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
-  const msfl_grid_crop_info* w = s->win_host.as<msfl_grid_crop_info>() + 2 * slot;
+  const msfl_grid_crop_info* w = s->win.host_at<msfl_grid_crop_info>(slot);
   if (corner) *corner = w[0];
   if (surf) *surf = w[1];
   return MSFL_OK;
 }
 
 msfl_status msfl_slam_get_uncertainty(msfl_slam* s, int scan_index, msfl_match_uncertainty* odometry, msfl_match_uncertainty* mapping) {
-  if (!s) return MSFL_BAD_ARG;
-  int slot;
-  { const msfl_status rs = slam_slot_of(s, scan_index, "msfl_slam_get_uncertainty", &slot); if (rs) return rs; }
-  if (!s->unc_held[slot]) return sfail(s, MSFL_BAD_ARG, "msfl_slam_get_uncertainty: that scan was fed with msfl_slam_set_uncertainty off");
-  { const msfl_status rs = slam_slot_ready(s, scan_index); if (rs) return rs; }
-  const msfl_match_uncertainty* u = s->unc_host.as<msfl_match_uncertainty>() + 2 * slot;
-  if (odometry) *odometry = u[0];
-  if (mapping) *mapping = u[1];
-  return MSFL_OK;
+  return slam_get_pair(s, &msfl_slam_s::unc, scan_index, "msfl_slam_get_uncertainty", "msfl_slam_set_uncertainty", odometry, mapping);
 }
 
 msfl_status msfl_slam_get_clouds(msfl_slam* s, int scan_index, msfl_slam_clouds* c, msfl_mem mem) {
@@ -679,9 +696,6 @@ msfl_status slam_wait_mapped(msfl_slam* s, int k) {
   return MSFL_OK;
 }
 
-msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb);
-msfl_status slam_wait_mapped(msfl_slam* s, int k);
-
 void slam_worker_main(msfl_slam* s) {
   for (;;) {
     SlamJob jb;
@@ -717,23 +731,10 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   SlamScanBuf& cur = s->sb[p];
   hipStream_t sm = hm->stream;
   const auto t_start = std::chrono::steady_clock::now();
-  auto t_seg = t_start;
-  auto seg = [&](const char* what) {                               // host profile of this thread
-    if (!s->host_profile || k < kSlamProfileSkip) return;
-    const auto now = std::chrono::steady_clock::now();
-    const double dt = std::chrono::duration<double>(now - t_seg).count();
-    t_seg = now;
-    for (auto& e : s->host_seg_map) if (e.first == what) { e.second += dt; return; }
-    s->host_seg_map.emplace_back(what, dt);
-  };
+  SegClock seg{s->host_profile && k >= kSlamProfileSkip, &s->host_seg_map, t_start};   // host profile of this thread
   slam_harvest(s, false);
   msfl_slam_result* rec = s->rec[slot].as<msfl_slam_result>();
-  // the slot's second records are the mapping match's (the prior was uploaded ahead of cur.ev_odo)
-  const RegSinks map_sinks{reinterpret_cast<DevMatchInfo*>(&rec->mapping), jb.unc ? s->unc[slot].as<UncRecord>() + 1 : nullptr,
-                           jb.prior_map ? s->prior[slot].as<PosePrior>() + 1 : nullptr, jb.unc_min_eig,
-                           jb.degen_map ? 1 : 0, jb.degen_map_min_eig, jb.degen_map ? s->degen[slot].as<DegenRecord>() + 1 : nullptr,
-                           jb.rej_map.mode, jb.rej_map.threshold * jb.rej_map.threshold, jb.rej_map.fraction, jb.rej_map.which,
-                           jb.rej_map.mode ? s->rej[slot].as<RejectRecord>() + 1 : nullptr};
+  const RegSinks map_sinks = slam_sinks(s, slot, 1, jb.o);
   const SlamImuDev* d_imu = cur.imu.as<SlamImuDev>();
   const int cap_ls = std::min(n, s->caps.less_sharp), cap_lf = std::min(n, s->caps.less_flat);
   double* chain = s->chain.as<double>();
@@ -803,12 +804,12 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   const long long seq_c0 = s->gc->last_seq, seq_s0 = s->gs->last_seq;
   SHIP(s, hipStreamWaitEvent(sc, cur.ev_match, 0));
   SCHK(s, hc, grid_insert_enqueue(s->gc, cur.map_ls.as<float4>(), cap_ls, cnt + SC_USE_LS, pose_map, rec->grid_corner));
-  int* win = jb.crop ? s->win[slot].as<int>() : nullptr;          // msfl_slam_set_map_window: each store forgets what lies outside the window
-  if (jb.crop) SCHK(s, hc, grid_crop_enqueue(s->gc, pose_map, jb.half, nullptr, 0, win, rec->grid_corner, true));
+  int* win = jb.o.crop ? s->win.dev[slot].as<int>() : nullptr;          // msfl_slam_set_map_window: each store forgets what lies outside the window
+  if (jb.o.crop) SCHK(s, hc, grid_crop_enqueue(s->gc, pose_map, jb.o.half, nullptr, 0, win, rec->grid_corner, true));
   SHIP(s, hipEventRecord(cur.ev_cdone, sc));
   seg("corner insert");
   SCHK(s, hm, grid_insert_enqueue(s->gs, cur.map_lf.as<float4>(), cap_lf, cnt + SC_USE_LF, pose_map, rec->grid_surf));
-  if (jb.crop) SCHK(s, hm, grid_crop_enqueue(s->gs, pose_map, jb.half, nullptr, 0, win + CROP_WORDS, rec->grid_surf, true));
+  if (jb.o.crop) SCHK(s, hm, grid_crop_enqueue(s->gs, pose_map, jb.o.half, nullptr, 0, win + CROP_WORDS, rec->grid_surf, true));
   SHIP(s, hipStreamWaitEvent(sm, cur.ev_cdone, 0));
   seg("surf insert");
   s->seq_c[slot] = s->gc->last_seq != seq_c0 ? s->gc->last_seq : 0;
@@ -817,14 +818,7 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
                      (const int*)cur.odo_status.as<int>());
   SHIP(s, hipGetLastError());
   SHIP(s, hipMemcpyAsync(s->rec_host.as<msfl_slam_result>() + slot, rec, sizeof(msfl_slam_result), hipMemcpyDeviceToHost, sm));
-  if (jb.unc)
-    SHIP(s, hipMemcpyAsync(s->unc_host.as<UncRecord>() + 2 * slot, s->unc[slot].p, 2 * sizeof(UncRecord), hipMemcpyDeviceToHost, sm));
-  if (jb.degen)
-    SHIP(s, hipMemcpyAsync(s->degen_host.as<DegenRecord>() + 2 * slot, s->degen[slot].p, 2 * sizeof(DegenRecord), hipMemcpyDeviceToHost, sm));
-  if (jb.rej)
-    SHIP(s, hipMemcpyAsync(s->rej_host.as<RejectRecord>() + 2 * slot, s->rej[slot].p, 2 * sizeof(RejectRecord), hipMemcpyDeviceToHost, sm));
-  if (jb.crop)
-    SHIP(s, hipMemcpyAsync(s->win_host.as<int>() + 2 * CROP_WORDS * slot, s->win[slot].p, 2 * CROP_WORDS * sizeof(int), hipMemcpyDeviceToHost, sm));
+  for (const SlotRecords* r : {&s->unc, &s->degen, &s->rej, &s->win}) SHIP(s, r->fetch(slot, sm));   // what the scan was fed with travels along
   SHIP(s, hipEventRecord(s->ev_done[slot], sm));
   seg("record");
   s->applied[slot] = false;
@@ -860,34 +854,24 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
     SHIP(s, hipEventSynchronize(s->ev_done[(k - 2) % kSlamSlots]));
   }
   const auto t_free = std::chrono::steady_clock::now();
-  auto t_seg = t_free;
-  auto seg = [&](const char* what) {                               // host profile: close the segment that ends here
-    if (!s->host_profile || k < kSlamProfileSkip) return;           // the first scans allocate
-    const auto now = std::chrono::steady_clock::now();
-    const double dt = std::chrono::duration<double>(now - t_seg).count();
-    t_seg = now;
-    for (auto& e : s->host_seg) if (e.first == what) { e.second += dt; return; }
-    s->host_seg.emplace_back(what, dt);
-  };
+  SegClock seg{s->host_profile && k >= kSlamProfileSkip, &s->host_seg, t_free};
   msfl_slam_result* rec = s->rec[slot].as<msfl_slam_result>();
   s->enqueueing = true;                 // from here on a failure leaves work of this scan on the streams: the pipeline is poisoned
   SHIP(s, hipMemsetAsync(rec, 0, sizeof(msfl_slam_result), so));
-  const bool unc = s->unc_on;
-  const double unc_min_eig = s->unc_min_eigenvalue;
-  s->unc_held[slot] = unc;
-  if (unc) SHIP(s, hipMemsetAsync(s->unc[slot].p, 0, 2 * sizeof(UncRecord), so));      // scan 0 has no odometry match, a closed gate no mapping match
-  const bool degen_odo = s->degen_on[0], degen_map = s->degen_on[1];
-  const double degen_odo_min_eig = s->degen_min_eigenvalue[0], degen_map_min_eig = s->degen_min_eigenvalue[1];
-  s->degen_held[slot] = degen_odo || degen_map;
-  if (degen_odo || degen_map) SHIP(s, hipMemsetAsync(s->degen[slot].p, 0, 2 * sizeof(DegenRecord), so));   // a slice stays zero where no solve runs
-  const msfl_outlier_rejection rej_odo = s->rej_cfg[0], rej_map = s->rej_cfg[1];
-  const bool rej_any = rej_odo.mode != MSFL_REJECT_OFF || rej_map.mode != MSFL_REJECT_OFF;
-  s->rej_held[slot] = rej_any;
-  if (rej_any) SHIP(s, hipMemsetAsync(s->rej[slot].p, 0, 2 * sizeof(RejectRecord), so));   // a slice stays zero where no solve runs
-  // msfl_slam_set_next_prior: consumed by this scan, whatever becomes of it
-  const bool prior_odo = s->next_prior_set[0], prior_map = s->next_prior_set[1];
+  SlamScanOptions o;
+  o.odo = s->opt[0]; o.map = s->opt[1];
+  o.unc = s->unc_on;
+  o.degen_any = o.odo.degen_on || o.map.degen_on;
+  o.rej_any = o.odo.rej.mode != MSFL_REJECT_OFF || o.map.rej.mode != MSFL_REJECT_OFF;
+  o.prior_odo = s->next_prior_set[0]; o.prior_map = s->next_prior_set[1];   // msfl_slam_set_next_prior: consumed by this scan, whatever becomes of it
   s->next_prior_set[0] = s->next_prior_set[1] = false;
-  if (prior_odo || prior_map) SHIP(s, ho->pin.upload(s->prior[slot].p, s->next_prior, 2 * sizeof(PosePrior), so));
+  o.crop = s->win_on && (k + 1) % s->win_every == 0;
+  for (int a = 0; a < 3; a++) o.half[a] = s->win_half[a];
+  SHIP(s, s->unc.arm(slot, o.unc, true, so));         // scan 0 has no odometry match, a closed gate no mapping match
+  SHIP(s, s->degen.arm(slot, o.degen_any, true, so));
+  SHIP(s, s->rej.arm(slot, o.rej_any, true, so));
+  SHIP(s, s->win.arm(slot, o.crop, false, so));       // (a crop will run on this scan; its reports are not cleared first)
+  if (o.prior_odo || o.prior_map) SHIP(s, ho->pin.upload(s->prior[slot].p, s->next_prior, 2 * sizeof(PosePrior), so));
   if (imu_mode != 0 || cur.imu_mode != 0) {
     // SlamImuDev header + [sum_dt n | delta_q 4n | delta_p 3n] in one copy (pinned ring slot: the caller's arrays are free on return)
     const size_t np = pre ? (size_t)pre->n : 0, head = offsetof(SlamImuDev, data) / sizeof(double);
@@ -960,12 +944,7 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
   double* chain = s->chain.as<double>();
   double* poses_k = cur.poses.as<double>();
   if (k > 0) {                                                   // laser_odometry.cc:72-75: the first scan only initialises
-    const RegSinks odo_sinks{reinterpret_cast<DevMatchInfo*>(&rec->odometry), unc ? s->unc[slot].as<UncRecord>() : nullptr,
-                             prior_odo ? s->prior[slot].as<PosePrior>() : nullptr, unc_min_eig,
-                             degen_odo ? 1 : 0, degen_odo_min_eig, degen_odo ? s->degen[slot].as<DegenRecord>() : nullptr,
-                             rej_odo.mode, rej_odo.threshold * rej_odo.threshold, rej_odo.fraction, rej_odo.which,
-                             rej_odo.mode ? s->rej[slot].as<RejectRecord>() : nullptr};
-    SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, odo_sinks));
+    SCHK(s, ho, scan2scan_dyn(ho, last, cur, s->caps, chain, slam_sinks(s, slot, 0, o)));
   }
   hipLaunchKernelGGL(slam_odom_pose_kernel, dim3(1), dim3(1), 0, so, (const double*)chain, chain + 7, poses_k, poses_k + 14,
                      (const int*)cur.cnt.as<int>(), k == 0 ? 1 : 0);
@@ -978,9 +957,8 @@ msfl_status slam_add_scan_impl(msfl_slam* s, const msfl_point* pts, const uint16
     s->host_wait_s += std::chrono::duration<double>(t_free - t_call).count();
     s->host_enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_free).count();
   }
-  const bool crop = s->win_on && (k + 1) % s->win_every == 0;
-  s->win_held[slot] = crop;
-  const SlamJob job{k, n, imu_mode, unc, unc_min_eig, prior_map, crop, {s->win_half[0], s->win_half[1], s->win_half[2]}, degen_odo || degen_map, degen_map, degen_map_min_eig, rej_any, rej_map};
+  SlamJob job;
+  job.k = k; job.n = n; job.imu_mode = imu_mode; job.o = o;
   if (s->threaded) {
     std::unique_lock<std::mutex> lk(s->mu);
     s->cv_done.wait(lk, [&] { return !s->has_job; });            // the mapping thread is at most one scan behind
