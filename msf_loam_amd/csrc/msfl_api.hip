@@ -135,6 +135,81 @@ struct MapIndex {
   int n_input = 0;    // points handed to msfl_set_map
 };
 
+// ---- The handle's scratch, one set per family of calls.  Host-memory calls stage their arrays into these (stage_in / stage_out);
+// device-memory calls use only the tables and work areas.  A buffer keeps its contents only until the next call that reserves it.
+struct ExtractScratch {      // msfl_extract_features*: extract_device / extract_batch_impl
+  DevBuf in_pts;             // float4[n_total]: staged input points (host mode)
+  DevBuf in_ring;            // u16[n_total]: staged input rings (host mode)
+  DevBuf off;                // int[B + 1]: scan offsets relative to the first scan, uploaded by extract_device
+  DevBuf pack;               // bytes: ALL outputs of a host-mode call, carved by extract_batch_impl (one read-back for a small call)
+  DevBuf status;             // int[B]: per-scan status of a device-mode call whose caller passed none
+  DevBuf gap;                // u8[n_total]: neighbour-gap flags, written by the prepare kernels
+  DevBuf ring_tab;           // int[B x (kMaxRings + 1)]: ring starts per scan, written by the prepare kernels
+  DevBuf tmp_idx;            // int[4 n_total]: candidate lists of the pick kernel
+  DevBuf ring_cnt;           // int[B x kMaxRings x 4]: picks per ring and list
+  DevBuf split;              // bytes: PrepSplitView of the several-workgroups ring split (prep_split_bytes)
+};
+struct OdomIndexBufs {       // the column index over the previous scans of one feature family (OdomIndex, built by launch_odom_bin)
+  DevBuf tab;                // unsigned[B x kOdomTabStride]: column tables
+  DevBuf sorted;             // float4[points]: the clouds in column order
+  DevBuf desc;               // OdomPairDesc[B]
+  DevBuf mode;               // int[B]: 0 = the pair's queries walk the index, else they stay on the brute-force kernel
+};
+struct OdomScratch {         // msfl_match_scan2scan*, and the index sets of the SLAM step's scan-to-scan
+  DevBuf pts[4];             // float4: staged last less-sharp, last less-flat, current sharp, current flat (host mode)
+  DevBuf ring[2];            // u16: staged rings of the two last-scan clouds (host mode)
+  DevBuf offs;               // int[5 (B + 1)]: [less-sharp | less-flat | sharp | flat | record] offsets
+  DevBuf poses;              // double[7 B]: staged poses (host mode)
+  DevBuf status;             // int[B]: status of a host-mode call, or of a device-mode call whose caller passed none
+  DevBuf split;              // the several-workgroups index build: unsigned cursors [jobs x kOdomTabStride], then int partials [jobs x G x 8]
+  OdomIndexBufs planes;      // over the last less-flat clouds
+  OdomIndexBufs edges;       // over the last less-sharp clouds
+};
+struct VoxelLdsSet {         // what one list of the per-cloud LDS form (and the big form behind it) works in
+  DevBuf staging;            // float4[n_total]: centroids per cloud before compaction.  Device-wide form (`set` only): int[3 runs], voxel-head
+                             // flags, their scan, head positions
+  DevBuf run_sums;           // float4[n_total]: per-run sums.  Device-wide form (`set` only): int[runs + 1], first slot of every run (run_first)
+  DevBuf tables;             // int[3 B + 3]: [voxels per cloud B | flags B | out_off B + 1].  Device-wide form (`set` only):
+                             // [n_valid B | in_off B + 1 | out_off B + 1 | max_cells 1]
+};
+struct VoxelScratch {        // msfl_voxel_downsample*
+  DevBuf pts, idx, cnt;      // float4[n_total], int[n_total], int[B]: staged points, index list, per-cloud counts (host mode)
+  DevBuf off;                // int[B + 1]: cloud offsets
+  DevBuf desc;               // VoxelCloudDesc[B]: device-wide form
+  DevBuf keys[2], vals[2];   // u64[runs], unsigned[runs], in and out of the radix sort: device-wide form
+  DevBuf flag;               // int[2 n_valid]: run-head flags and their scan: device-wide form
+  DevBuf out;                // float4: filtered points of a host-mode call before they go back
+  VoxelLdsSet set;           // the single-list call, and list b of the pair form
+  VoxelLdsSet set_a;         // list a of the pair form
+  DevBuf off_a;              // int[B + 1]: the pair form's cloud offsets
+  DevBuf big_scratch;        // the one-workgroup form for lists of 65 536 .. 131 071 points: per-workgroup record areas, then order areas
+  DevBuf big_list;           // int[refused clouds]: the clouds that form walks
+};
+struct PointPassScratch {    // msfl_delta_qp, msfl_deskew_cloud, msfl_undistort_cloud, msfl_transform_cloud; msfl_voxel_downsample's fallback
+  DevBuf pre;                // double[8 n]: pre-integration samples [sum_dt | dq | dp] (stage_preintegration); msfl_transform_cloud: its pose, double[7]
+  DevBuf pts;                // float4[n]: staged points (host mode); the fallback's compacted finite points
+  DevBuf dq;                 // double[4 n]: msfl_delta_qp's staged output (host mode); the fallback's filtered points, float4[n]
+  DevBuf dp;                 // double[3 n]: msfl_delta_qp's staged output (host mode)
+  DevBuf flag;               // one int: a time outside the pre-integration span was seen; the fallback's count of finite points
+};
+struct DeskewScratch {       // msfl_match_scan2map_deskew*: the staged msfl_deskew_batch arrays (host mode)
+  DevBuf corner_dq, corner_dp, surf_dq, surf_dp;   // double[4 n_corner], [3 n_corner], [4 n_surf], [3 n_surf]
+  DevBuf velocity;           // double[3 B]
+};
+struct PairScratch {         // msfl_match_pairs_batch: build_pair_index
+  DevBuf off_c, base_c;      // int[P + 1] each: corner-map offsets and cell-table bases
+  DevBuf off_s, base_s;      // ... of the surf maps
+  DevBuf bbox;               // int[6 P]: per-pair bounding boxes (not MapIndex::bbox: that one is the single-map build's)
+};
+struct ScoreScratch {        // msfl_score_poses*: no other call touches these, so a matcher call after it finds the handle as it left it
+  DevBuf corner, surf;       // float4: staged clouds (host mode)
+  DevBuf poses;              // double[7 H]: staged hypotheses (host mode)
+  DevBuf off;                // int[3 (n_scans + 1)]: [corner | surf | pose] offsets
+  DevBuf rec;                // ScoreRec[H]: staged results (host mode)
+  DevBuf d2, nn;             // float / int [H x features]: staged per-feature outputs (host mode, single scan)
+  DevBuf scan;               // int[H]: scan of every hypothesis (batch form), written by score_init_kernel
+};
+
 enum TimerClass { T_ASSOC = 0, T_SOLVE, T_INDEX, T_EXTRACT, T_ODOM, T_FIT, T_ASSOC_SEEDED /* a subset of T_ASSOC */, T_COUNT };
 
 struct TimedSpan { hipEvent_t a, b; int cls; };
@@ -192,22 +267,21 @@ struct msfl_handle_s {
   int knn_form = 0;                       // MSFL_KNN_FORM: 0 auto (row-parallel latency form for launches of <= kKnnRowsMaxRecords queries),
                                           // 1 "lane" (one lane per query always), 2 "rows" (row-parallel always); results are identical
 
-  // scratch
+  // scratch of the map matchers (scan-to-map, pairs, records): staged feature clouds, offset table, poses, per-registration status and
+  // info, association records, deskewed points / host-format records, 5-NN lists.  `poses` also holds msfl_extract_features' extrinsic.
   DevBuf in_corner, in_surf, in_off, poses, status, info, records, pprime, nn;
   std::vector<int> in_off_host; const void* in_off_host_ptr = nullptr;   // what in_off holds on the device (upload_in_off)
   DevBuf idx_cell_of, idx_count, idx_scanned, idx_bbox, idx_cub, idx_stage;
   bool index_single = false;   // MSFL_INDEX_SINGLE=1: msfl_set_map builds its two indexes one after the other (the rounds 1-5 form; A/B and parity of the pair build)
   DevBuf knn_count;            // one u64: candidates evaluated by the counting 5-NN instantiation (timing mode 3)
   size_t idx_count_zero = 0;   // leading ints of idx_count known to be zero on the stream
-  DevBuf dk[5];
-  DevBuf ex[16];
-  DevBuf od[20];
-  DevBuf vb[14];  // batched voxel filter
-  DevBuf vox_big_scratch, vox_big_list;   // the one-workgroup form for lists of 65 536 .. 131 071 points (round 5): per-workgroup run scratch, list of refused clouds
-  DevBuf vb2[6];  // second scratch set of the pair form: staging, run sums, counts/flags/offsets, offsets
-  DevBuf pp[5];   // per-point passes: pre-integration samples, staged points, dq, dp, flag
-  DevBuf pr[5];   // batched (map, scan) pairs: map offsets and cell-table bases per cloud kind, preset status
-  DevBuf sc[8];   // msfl_score_poses*: staged clouds and poses, offset table, records, per-feature outputs, scan of each hypothesis (no other call touches them)
+  DeskewScratch dk;
+  ExtractScratch ex;
+  OdomScratch od;
+  VoxelScratch vox;
+  PointPassScratch pp;
+  PairScratch pr;
+  ScoreScratch sc;
 
   // msfl_set_uncertainty / msfl_set_degeneracy / msfl_set_outlier_rejection: the knobs, and where every matcher call writes one
   // record per registration.  The uncertainty feature is on while its sink is set; a degeneracy or rejection sink is optional and
@@ -242,6 +316,26 @@ msfl_status fail(msfl_handle* h, msfl_status s, const std::string& msg) {
     if (e__ != hipSuccess)                                                                         \
       return fail(h, MSFL_HIP_ERROR, std::string(#expr) + ": " + hipGetErrorString(e__));          \
   } while (0)
+
+msfl_status fail(msfl_places* p, msfl_status s, const std::string& msg);   // msfl_api_place.inc
+
+// The two halves of a host-memory call's staging (`h`: the handle or the places object).  stage_in: where the kernels read the n
+// elements of `src` -- a host array is copied into `buf` on `st` (which holds one element at least), a device array is read in place.
+// The caller's array is typed by the pointer the kernels take (msfl_point arrives as float4).
+template <class H, class T>
+msfl_status stage_in(H* h, DevBuf& buf, const void* src, size_t n, msfl_mem mem, hipStream_t st, T** d) {
+  if (mem != MSFL_MEM_HOST) { *d = static_cast<T*>(const_cast<void*>(src)); return MSFL_OK; }
+  HIPCHK(h, buf.reserve(std::max<size_t>(1, n) * sizeof(T)));
+  if (n > 0) HIPCHK(h, hipMemcpyAsync(buf.p, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+  *d = buf.as<T>();
+  return MSFL_OK;
+}
+// stage_out: the n elements the kernels left at `d_src` go back to a host array on `st`; a device array was written in place.
+template <class H, class T>
+msfl_status stage_out(H* h, void* dst, const T* d_src, size_t n, msfl_mem mem, hipStream_t st) {
+  if (mem == MSFL_MEM_HOST && n > 0) HIPCHK(h, hipMemcpyAsync(dst, d_src, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  return MSFL_OK;
+}
 
 hipEvent_t get_event(msfl_handle* h) {
   if (!h->free_events.empty()) { hipEvent_t e = h->free_events.back(); h->free_events.pop_back(); return e; }
@@ -427,12 +521,10 @@ msfl_status reg_open(msfl_handle* h, int n, hipStream_t st, bool want_info, RegS
 msfl_status reg_close(msfl_handle* h, int n, msfl_mem mem, double* poses_io, const double* d_poses, int* status, const int* d_status,
                       msfl_match_info* info, const RegSinks& k) {
   hipStream_t st = h->stream;
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, hipMemcpyAsync(poses_io, d_poses, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
-  }
+  msfl_status s = stage_out(h, poses_io, d_poses, (size_t)n * 7, mem, st); if (s) return s;
+  if (status) { s = stage_out(h, status, d_status, (size_t)n, mem, st); if (s) return s; }
   if (info) HIPCHK(h, hipMemcpyAsync(info, k.info, (size_t)n * sizeof(DevMatchInfo), hipMemcpyDeviceToHost, st));
-  msfl_status s = sink_close(h, h->unc, k.unc, n, st); if (s) return s;
+  s = sink_close(h, h->unc, k.unc, n, st); if (s) return s;
   s = sink_close(h, h->degen, k.degen, n, st); if (s) return s;
   s = sink_close(h, h->rej, k.rej, n, st); if (s) return s;
   if (mem == MSFL_MEM_HOST || info || h->unc.host() || h->degen.host() || h->rej.host()) HIPCHK(h, hipStreamSynchronize(st));
@@ -1024,16 +1116,12 @@ static msfl_status match_batch_impl(msfl_handle* h, int B, const msfl_point* cor
     const double* src[5] = {deskew->corner_dq, deskew->corner_dp, deskew->surf_dq, deskew->surf_dp, deskew->velocity};
     const size_t nb[5] = {(size_t)ncp * 4, (size_t)ncp * 3, (size_t)nsp * 4, (size_t)nsp * 3, (size_t)B * 3};
     const size_t skip[5] = {(size_t)c0 * 4, (size_t)c0 * 3, (size_t)s0 * 4, (size_t)s0 * 3, 0};
+    DevBuf* const buf[5] = {&h->dk.corner_dq, &h->dk.corner_dp, &h->dk.surf_dq, &h->dk.surf_dp, &h->dk.velocity};
     const double* dev[5];
     for (int k = 0; k < 5; k++) {
       if (nb[k] && !src[k]) return fail(h, MSFL_BAD_ARG, "msfl_match_scan2map_deskew: null deskew array");
-      if (mem == MSFL_MEM_HOST) {
-        HIPCHK(h, h->dk[k].reserve(std::max<size_t>(1, nb[k]) * sizeof(double)));
-        if (nb[k]) HIPCHK(h, hipMemcpyAsync(h->dk[k].p, src[k] + skip[k], nb[k] * sizeof(double), hipMemcpyHostToDevice, st));
-        dev[k] = h->dk[k].as<double>();
-      } else {
-        dev[k] = src[k];
-      }
+      const double* used = mem == MSFL_MEM_HOST && src[k] ? src[k] + skip[k] : src[k];   // a host array's used part is what is staged
+      s = stage_in(h, *buf[k], used, nb[k], mem, st, &dev[k]); if (s) return s;
     }
     dv.corner_dq = dev[0]; dv.corner_dp = dev[1]; dv.surf_dq = dev[2]; dv.surf_dp = dev[3]; dv.V = dev[4];
     for (int a = 0; a < 3; a++) dv.G[a] = deskew->gravity[a];
@@ -1122,21 +1210,19 @@ msfl_status msfl_match_scan2map_deskew_batch(msfl_handle* h, int n_scans, const 
 static msfl_status stage_single(msfl_handle* h, const msfl_point* corner, int n_corner, const msfl_point* surf, int n_surf,
                                 const double* pose, BatchView& bv) {
   hipStream_t st = h->stream;
-  HIPCHK(h, h->in_corner.reserve(std::max<size_t>(1, (size_t)n_corner) * sizeof(float4)));
-  HIPCHK(h, h->in_surf.reserve(std::max<size_t>(1, (size_t)n_surf) * sizeof(float4)));
   HIPCHK(h, h->poses.reserve(7 * sizeof(double)));
   HIPCHK(h, h->status.reserve(sizeof(int)));
-
   HIPCHK(h, h->records.reserve(record_bytes((size_t)n_corner + (size_t)n_surf, (size_t)n_surf)));
   HIPCHK(h, h->nn.reserve(std::max<size_t>(1, (size_t)(n_corner + n_surf)) * 5 * sizeof(int)));
-  if (n_corner) HIPCHK(h, hipMemcpyAsync(h->in_corner.p, corner, (size_t)n_corner * sizeof(float4), hipMemcpyHostToDevice, st));
-  if (n_surf) HIPCHK(h, hipMemcpyAsync(h->in_surf.p, surf, (size_t)n_surf * sizeof(float4), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipMemcpyAsync(h->poses.p, pose, 7 * sizeof(double), hipMemcpyHostToDevice, st));
+  const float4 *d_corner, *d_surf;
+  msfl_status s = stage_in(h, h->in_corner, corner, (size_t)n_corner, MSFL_MEM_HOST, st, &d_corner); if (s) return s;
+  s = stage_in(h, h->in_surf, surf, (size_t)n_surf, MSFL_MEM_HOST, st, &d_surf); if (s) return s;
+  HIPCHK(h, hipMemcpyAsync(h->poses.p, pose, 7 * sizeof(double), hipMemcpyHostToDevice, st));     // (the callers read h->poses and h->status)
   HIPCHK(h, hipMemsetAsync(h->status.p, 0, sizeof(int), st));
   const int co[2] = {0, n_corner}, so[2] = {0, n_surf};
   int n_rec = 0;
-  { const msfl_status us = upload_batch_offsets(h, 1, co, so, &n_rec); if (us) return us; }
-  bv = batch_view(h->in_corner.as<float4>(), h->in_surf.as<float4>(), h->in_off.as<int>(), 2, 1, n_rec, 0, 0, n_surf);
+  s = upload_batch_offsets(h, 1, co, so, &n_rec); if (s) return s;
+  bv = batch_view(d_corner, d_surf, h->in_off.as<int>(), 2, 1, n_rec, 0, 0, n_surf);
   return MSFL_OK;
 }
 

@@ -3,8 +3,6 @@
 
 namespace {
 
-enum { PP_PRE = 0, PP_PTS, PP_DQ, PP_DP, PP_FLAG };
-
 // stage the pre-integration samples as [sum_dt n | dq 4n | dp 3n] doubles
 msfl_status stage_preintegration(msfl_handle* h, const msfl_preintegration* pre, PreintView& pv, const char* who) {
   if (!pre || pre->n < 2 || !pre->sum_dt || !pre->delta_q || !pre->delta_p)
@@ -16,12 +14,12 @@ msfl_status stage_preintegration(msfl_handle* h, const msfl_preintegration* pre,
   std::memcpy(buf.data(), pre->sum_dt, n * sizeof(double));
   std::memcpy(buf.data() + n, pre->delta_q, 4 * n * sizeof(double));
   std::memcpy(buf.data() + 5 * n, pre->delta_p, 3 * n * sizeof(double));
-  HIPCHK(h, h->pp[PP_PRE].reserve(buf.size() * sizeof(double)));
-  HIPCHK(h, h->pin.upload(h->pp[PP_PRE].p, buf.data(), buf.size() * sizeof(double), h->stream));
-  const double* d = h->pp[PP_PRE].as<double>();
+  HIPCHK(h, h->pp.pre.reserve(buf.size() * sizeof(double)));
+  HIPCHK(h, h->pin.upload(h->pp.pre.p, buf.data(), buf.size() * sizeof(double), h->stream));
+  const double* d = h->pp.pre.as<double>();
   pv.sum_dt = d; pv.dq = d + n; pv.dp = d + 5 * n; pv.n = pre->n;
-  HIPCHK(h, h->pp[PP_FLAG].reserve(sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(h->pp[PP_FLAG].p, 0, sizeof(int), h->stream));
+  HIPCHK(h, h->pp.flag.reserve(sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(h->pp.flag.p, 0, sizeof(int), h->stream));
   return MSFL_OK;
 }
 
@@ -29,22 +27,16 @@ msfl_status stage_preintegration(msfl_handle* h, const msfl_preintegration* pre,
 template <class Launch>
 msfl_status cloud_pass(msfl_handle* h, msfl_point* pts_io, int n, msfl_mem mem, bool has_flag, const char* who, Launch&& launch) {
   hipStream_t st = h->stream;
-  float4* d_pts = reinterpret_cast<float4*>(pts_io);
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, h->pp[PP_PTS].reserve((size_t)n * sizeof(float4)));
-    HIPCHK(h, hipMemcpyAsync(h->pp[PP_PTS].p, pts_io, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, st));
-    d_pts = h->pp[PP_PTS].as<float4>();
-  }
+  float4* d_pts;
+  msfl_status s = stage_in(h, h->pp.pts, pts_io, (size_t)n, mem, st, &d_pts); if (s) return s;
   launch(d_pts);
   HIPCHK(h, hipGetLastError());
   int bad = 0;
-  if (has_flag) HIPCHK(h, hipMemcpyAsync(&bad, h->pp[PP_FLAG].p, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (has_flag) HIPCHK(h, hipMemcpyAsync(&bad, h->pp.flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
   if (has_flag || mem == MSFL_MEM_HOST) HIPCHK(h, hipStreamSynchronize(st));
   if (bad) return fail(h, MSFL_BAD_ARG, std::string(who) + ": a point's relative time lies outside the pre-integration span (scan_undistortion.cc:26-30)");
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, hipMemcpyAsync(pts_io, d_pts, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
+  s = stage_out(h, pts_io, d_pts, (size_t)n, mem, st); if (s) return s;
+  if (mem == MSFL_MEM_HOST) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 
@@ -60,23 +52,20 @@ msfl_status msfl_delta_qp(msfl_handle* h, const msfl_preintegration* pre, const 
   s = stage_preintegration(h, pre, pv, "msfl_delta_qp"); if (s) return s;
   if (n == 0) return MSFL_OK;
   hipStream_t st = h->stream;
-  const float4* d_pts = reinterpret_cast<const float4*>(pts);
+  const float4* d_pts;
+  s = stage_in(h, h->pp.pts, pts, (size_t)n, mem, st, &d_pts); if (s) return s;
   double *d_dq = dq, *d_dp = dp;
   if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, h->pp[PP_PTS].reserve((size_t)n * sizeof(float4)));
-    HIPCHK(h, h->pp[PP_DQ].reserve((size_t)n * 4 * sizeof(double)));
-    HIPCHK(h, h->pp[PP_DP].reserve((size_t)n * 3 * sizeof(double)));
-    HIPCHK(h, hipMemcpyAsync(h->pp[PP_PTS].p, pts, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, st));
-    d_pts = h->pp[PP_PTS].as<float4>(); d_dq = h->pp[PP_DQ].as<double>(); d_dp = h->pp[PP_DP].as<double>();
+    HIPCHK(h, h->pp.dq.reserve((size_t)n * 4 * sizeof(double)));
+    HIPCHK(h, h->pp.dp.reserve((size_t)n * 3 * sizeof(double)));
+    d_dq = h->pp.dq.as<double>(); d_dp = h->pp.dp.as<double>();
   }
-  hipLaunchKernelGGL(delta_qp_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, pv, d_pts, n, d_dq, d_dp, h->pp[PP_FLAG].as<int>());
+  hipLaunchKernelGGL(delta_qp_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, pv, d_pts, n, d_dq, d_dp, h->pp.flag.as<int>());
   HIPCHK(h, hipGetLastError());
   int bad = 0;
-  HIPCHK(h, hipMemcpyAsync(&bad, h->pp[PP_FLAG].p, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, hipMemcpyAsync(dq, d_dq, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(dp, d_dp, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
+  HIPCHK(h, hipMemcpyAsync(&bad, h->pp.flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  s = stage_out(h, dq, d_dq, (size_t)n * 4, mem, st); if (s) return s;
+  s = stage_out(h, dp, d_dp, (size_t)n * 3, mem, st); if (s) return s;
   HIPCHK(h, hipStreamSynchronize(st));
   if (bad) return fail(h, MSFL_BAD_ARG, "msfl_delta_qp: a point's relative time lies outside the pre-integration span (scan_undistortion.cc:26-30)");
   return MSFL_OK;
@@ -94,8 +83,8 @@ msfl_status msfl_deskew_cloud(msfl_handle* h, const msfl_preintegration* pre, ms
   c.v.x = velocity[0]; c.v.y = velocity[1]; c.v.z = velocity[2];
   c.g.x = gravity[0]; c.g.y = gravity[1]; c.g.z = gravity[2];
   return cloud_pass(h, pts_io, n, mem, true, "msfl_deskew_cloud", [&](float4* d_pts) {
-    hipLaunchKernelGGL(cloud_times_check_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, pv, (const float4*)d_pts, n, 0, h->pp[PP_FLAG].as<int>());
-    hipLaunchKernelGGL(deskew_cloud_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, pv, c, d_pts, n, (const int*)h->pp[PP_FLAG].as<int>());
+    hipLaunchKernelGGL(cloud_times_check_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, pv, (const float4*)d_pts, n, 0, h->pp.flag.as<int>());
+    hipLaunchKernelGGL(deskew_cloud_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, pv, c, d_pts, n, (const int*)h->pp.flag.as<int>());
   });
 }
 
@@ -106,8 +95,8 @@ msfl_status msfl_undistort_cloud(msfl_handle* h, const msfl_preintegration* pre,
   s = stage_preintegration(h, pre, pv, "msfl_undistort_cloud"); if (s) return s;
   if (n == 0) return MSFL_OK;
   return cloud_pass(h, pts_io, n, mem, true, "msfl_undistort_cloud", [&](float4* d_pts) {
-    hipLaunchKernelGGL(cloud_times_check_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, pv, (const float4*)d_pts, n, 1, h->pp[PP_FLAG].as<int>());
-    hipLaunchKernelGGL(undistort_cloud_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, pv, d_pts, n, (const int*)h->pp[PP_FLAG].as<int>());
+    hipLaunchKernelGGL(cloud_times_check_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, pv, (const float4*)d_pts, n, 1, h->pp.flag.as<int>());
+    hipLaunchKernelGGL(undistort_cloud_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, pv, d_pts, n, (const int*)h->pp.flag.as<int>());
   });
 }
 
@@ -116,21 +105,15 @@ msfl_status msfl_transform_cloud(msfl_handle* h, const msfl_point* in, int n, co
   if (n < 0 || !pose7 || (n > 0 && (!in || !out))) return fail(h, MSFL_BAD_ARG, "msfl_transform_cloud: bad argument");
   if (n == 0) return MSFL_OK;
   hipStream_t st = h->stream;
-  HIPCHK(h, h->pp[PP_PRE].reserve(7 * sizeof(double)));
-  HIPCHK(h, h->pin.upload(h->pp[PP_PRE].p, pose7, 7 * sizeof(double), st));      // the pose is always a host array
-  const float4* d_in = reinterpret_cast<const float4*>(in);
-  float4* d_out = reinterpret_cast<float4*>(out);
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, h->pp[PP_PTS].reserve((size_t)n * sizeof(float4)));
-    HIPCHK(h, hipMemcpyAsync(h->pp[PP_PTS].p, in, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, st));
-    d_in = d_out = h->pp[PP_PTS].as<float4>();
-  }
-  hipLaunchKernelGGL(transform_cloud_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, d_in, n, (const double*)h->pp[PP_PRE].as<double>(), d_out);
+  HIPCHK(h, h->pp.pre.reserve(7 * sizeof(double)));                           // (pp.pre's second role: PointPassScratch)
+  HIPCHK(h, h->pin.upload(h->pp.pre.p, pose7, 7 * sizeof(double), st));      // the pose is always a host array
+  const float4* d_in;
+  s = stage_in(h, h->pp.pts, in, (size_t)n, mem, st, &d_in); if (s) return s;
+  float4* d_out = mem == MSFL_MEM_HOST ? h->pp.pts.as<float4>() : reinterpret_cast<float4*>(out);      // a staged cloud is transformed in place
+  hipLaunchKernelGGL(transform_cloud_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, d_in, n, (const double*)h->pp.pre.as<double>(), d_out);
   HIPCHK(h, hipGetLastError());
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
+  s = stage_out(h, out, d_out, (size_t)n, mem, st); if (s) return s;
+  if (mem == MSFL_MEM_HOST) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 

@@ -413,12 +413,8 @@ msfl_status msfl_grid_insert_scan(msfl_grid* g, const msfl_point* pts, int n, ms
   msfl_status s = enter(h); if (s) return s;
   if (n < 0 || (n > 0 && !pts)) return fail(h, MSFL_BAD_ARG, "msfl_grid_insert_scan: bad argument");
   if (n == 0) return MSFL_OK;                                    // :504
-  const float4* d_pts = reinterpret_cast<const float4*>(pts);
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, g->stage.reserve((size_t)n * sizeof(float4)));
-    HIPCHK(h, hipMemcpyAsync(g->stage.p, pts, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
-    d_pts = g->stage.as<float4>();
-  }
+  const float4* d_pts;
+  s = stage_in(h, g->stage, pts, (size_t)n, mem, h->stream, &d_pts); if (s) return s;
   s = grid_insert_enqueue(g, d_pts, n, nullptr, nullptr); if (s) return s;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return grid_read_report(g);
@@ -478,7 +474,7 @@ msfl_status msfl_grid_dump(msfl_grid* g, msfl_point* out, int capacity, int* n_o
     float4* d_out = reinterpret_cast<float4*>(out);
     if (mem == MSFL_MEM_HOST) { HIPCHK(h, g->stage.reserve((size_t)m * sizeof(float4))); d_out = g->stage.as<float4>(); }
     s = grid_pack(g, d_out, m, false); if (s) return s;
-    if (mem == MSFL_MEM_HOST) HIPCHK(h, hipMemcpyAsync(out, d_out, (size_t)m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    s = stage_out(h, out, d_out, (size_t)m, mem, h->stream); if (s) return s;
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
   return g->n_points > capacity ? MSFL_CAPACITY : MSFL_OK;
@@ -573,12 +569,8 @@ msfl_status msfl_grid_load_cells(msfl_grid* g, const int* cells, int n_cells, co
   const size_t n = (size_t)n_cells;
   HIPCHK(h, g->load.reserve(n * (16 + 8 + 4 * 4)));
   HIPCHK(h, hipMemcpyAsync(g->load.p, cells, n * 16, hipMemcpyHostToDevice, st));
-  const float4* d_pts = reinterpret_cast<const float4*>(pts);
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, g->stage.reserve((size_t)n_points * sizeof(float4)));
-    HIPCHK(h, hipMemcpyAsync(g->stage.p, pts, (size_t)n_points * sizeof(float4), hipMemcpyHostToDevice, st));
-    d_pts = g->stage.as<float4>();
-  }
+  const float4* d_pts;
+  s = stage_in(h, g->stage, pts, (size_t)n_points, mem, st, &d_pts); if (s) return s;
   int* d_info = g->report_dev.as<int>() + 8;
   s = grid_load_enqueue(g, g->load.as<int>(), n_cells, d_pts, n_points, d_info); if (s) return s;
   HIPCHK(h, hipStreamSynchronize(st));

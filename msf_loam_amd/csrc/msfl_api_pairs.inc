@@ -7,8 +7,6 @@
 
 namespace {
 
-enum { PR_OFF_C = 0, PR_BASE_C, PR_OFF_S, PR_BASE_S, PR_BBOX };
-
 // One grid per pair over the concatenated clouds `d_pts` (device; pair p owns [off[p], off[p + 1])), into `mi`.
 msfl_status build_pair_index(msfl_handle* h, const float4* d_pts, const int* off, int P, MapIndex& mi, DevBuf& d_off, DevBuf& d_base) {
   ScopedTimer timer(h, T_INDEX);
@@ -44,7 +42,7 @@ msfl_status build_pair_index(msfl_handle* h, const float4* d_pts, const int* off
   h->idx_count_zero = 0;
   if (span > zeroed) HIPCHK(h, hipMemsetAsync(h->idx_count.p, 0, span * sizeof(int), st));     // the scatter counts every cell back to zero
   const double radius = std::sqrt((double)h->prm.map_knn_max_sq_dist);
-  DevBuf& bb = h->pr[PR_BBOX];            // not MapIndex::bbox: that one is the single-map build's, armed once and re-armed by its scatter kernel
+  DevBuf& bb = h->pr.bbox;                // not MapIndex::bbox: that one is the single-map build's, armed once and re-armed by its scatter kernel
   HIPCHK(h, bb.reserve((size_t)6 * P * sizeof(int)));
   hipLaunchKernelGGL(pairs_arm_kernel, dim3(div_up(6 * P, 256)), dim3(256), 0, st, bb.as<int>(), P);
   int longest = 0;
@@ -108,23 +106,17 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
     for (int p = 0; p <= P; p++) { mco[p] -= a; mso[p] -= b; }
     d_mc = stage; d_ms = stage + nmc;
   }
-  s = build_pair_index(h, d_mc, mco.data(), P, h->map_c, h->pr[PR_OFF_C], h->pr[PR_BASE_C]); if (s) return s;
-  s = build_pair_index(h, d_ms, mso.data(), P, h->map_s, h->pr[PR_OFF_S], h->pr[PR_BASE_S]); if (s) return s;
+  s = build_pair_index(h, d_mc, mco.data(), P, h->map_c, h->pr.off_c, h->pr.base_c); if (s) return s;
+  s = build_pair_index(h, d_ms, mso.data(), P, h->map_s, h->pr.off_s, h->pr.base_s); if (s) return s;
   // ---- the P scans
   std::vector<int> co(corner_off, corner_off + P + 1), so(surf_off, surf_off + P + 1);
-  const float4* d_corner = reinterpret_cast<const float4*>(corner);
-  const float4* d_surf = reinterpret_cast<const float4*>(surf);
-  double* d_poses = poses_io;
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, h->in_corner.reserve(std::max<size_t>(1, (size_t)ncp) * sizeof(float4)));
-    HIPCHK(h, h->in_surf.reserve(std::max<size_t>(1, (size_t)nsp) * sizeof(float4)));
-    HIPCHK(h, h->poses.reserve((size_t)P * 7 * sizeof(double)));
-    if (ncp) HIPCHK(h, hipMemcpyAsync(h->in_corner.p, corner + c0, (size_t)ncp * sizeof(float4), hipMemcpyHostToDevice, st));
-    if (nsp) HIPCHK(h, hipMemcpyAsync(h->in_surf.p, surf + s0, (size_t)nsp * sizeof(float4), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->poses.p, poses_io, (size_t)P * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-    for (int p = 0; p <= P; p++) { co[p] -= c0; so[p] -= s0; }
-    d_corner = h->in_corner.as<float4>(); d_surf = h->in_surf.as<float4>(); d_poses = h->poses.as<double>();
-  }
+  const float4 *d_corner, *d_surf;
+  double* d_poses;
+  const bool host = mem == MSFL_MEM_HOST;          // host clouds are staged from their first used point, and the offsets follow
+  s = stage_in(h, h->in_corner, host && ncp ? corner + c0 : corner, (size_t)ncp, mem, st, &d_corner); if (s) return s;
+  s = stage_in(h, h->in_surf, host && nsp ? surf + s0 : surf, (size_t)nsp, mem, st, &d_surf); if (s) return s;
+  s = stage_in(h, h->poses, poses_io, (size_t)P * 7, mem, st, &d_poses); if (s) return s;
+  if (host) for (int p = 0; p <= P; p++) { co[p] -= c0; so[p] -= s0; }
   // per-pair status, preset on the host: a pair whose map cloud has fewer than 5 points is not matched
   // (mapping_scan_matcher.cc:128,198 would index pointSearchSqDis[4] out of bounds; the reference's caller gates, laser_mapping.cc:284-285)
   std::vector<int> st0(P, 0);
@@ -149,7 +141,7 @@ msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
     {
       ScopedTimer timer(h, it > 0 ? T_ASSOC_SEEDED : T_ASSOC);
       launch_knn5(h, knn5_scan2map_kernel<false, false, true>, grid, block, bv, d_poses, d_status, dv, h->nn.as<int>(),
-                  nullptr, h->pr[PR_BASE_C].as<int>(), h->pr[PR_BASE_S].as<int>());
+                  nullptr, h->pr.base_c.as<int>(), h->pr.base_s.as<int>());
     }
     ScopedTimer timer(h, T_FIT);       // nn holds positions in the concatenated sorted maps: the fit gathers as ever
     hipLaunchKernelGGL(fit_scan2map_kernel<false>, grid, block, 0, st, bv, h->map_c.sorted.as<float4>(), h->map_s.sorted.as<float4>(),

@@ -6,10 +6,6 @@
 
 static_assert(sizeof(PlaceRec) == sizeof(msfl_place_match) && sizeof(msfl_place_match) == 24, "place match record layout");
 
-namespace {
-enum { PL_PTS = 0, PL_OFF, PL_PART, PL_QDESC, PL_QKEY, PL_QNRM, PL_META, PL_KEYS, PL_LIST, PL_REC, PL_OUT, PL_STAGE, PL_FLAG, PL_COUNT };
-}
-
 struct msfl_places_s {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -19,7 +15,17 @@ struct msfl_places_s {
   int size = 0;                 // entries added so far
   DevBuf tab;                   // e2[n_ring + 1], lo2, bc[n_sector / 2], bs[n_sector / 2]
   DevBuf desc, rkey, nrm;       // capacity x (n_ring x n_sector f32, n_ring int, n_sector f64)
-  DevBuf sp[PL_COUNT];          // staged points, offsets, chunk partials, query entries, query meta, prefilter keys and list, pair records, staged results
+  // scratch of place_describe
+  DevBuf pts;                   // float4[points]: staged scans (host mode)
+  DevBuf off;                   // int[2 (n_scans + 1)]: [point offsets | chunk offsets]
+  DevBuf part;                  // unsigned[chunks x n_ring x n_sector]: per-chunk partial descriptors of scans longer than one chunk
+  // scratch of the queries
+  DevBuf q_desc, q_rkey, q_nrm; // the described query scans of msfl_places_query, laid out like desc / rkey / nrm
+  DevBuf meta;                  // int[3 Q]: [entry of each query | candidates | compared candidates]
+  DevBuf keys, list;            // u64[queries per launch x candidates], int[queries per launch x pitch]: the prefilter's keys and its survivors
+  DevBuf rec;                   // PlaceRec[queries per launch x pitch]: one record per compared pair
+  DevBuf out;                   // PlaceRec[Q x k]: staged results (host mode)
+  DevBuf flag;                  // one int: msfl_places_add_descriptors saw a bad value on the device
   PinRing pin;
   PinBuf readback;
 };
@@ -68,23 +74,19 @@ msfl_status place_describe(msfl_places* p, const msfl_point* pts, const int* off
     co[b] = co[b - 1] + chunks;
     widest = std::max(widest, chunks);
   }
-  HIPCHK(p, p->sp[PL_OFF].reserve(offs.size() * sizeof(int)));
-  HIPCHK(p, p->pin.upload(p->sp[PL_OFF].p, offs.data(), offs.size() * sizeof(int), st));
-  const float4* d_pts = reinterpret_cast<const float4*>(pts) + p0;
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(p, p->sp[PL_PTS].reserve(std::max<size_t>(1, (size_t)total) * sizeof(float4)));
-    if (total) HIPCHK(p, hipMemcpyAsync(p->sp[PL_PTS].p, pts + p0, (size_t)total * sizeof(float4), hipMemcpyHostToDevice, st));
-    d_pts = p->sp[PL_PTS].as<float4>();
-  }
-  if (widest > 1) HIPCHK(p, p->sp[PL_PART].reserve((size_t)co[n_scans] * ds * sizeof(unsigned)));
+  HIPCHK(p, p->off.reserve(offs.size() * sizeof(int)));
+  HIPCHK(p, p->pin.upload(p->off.p, offs.data(), offs.size() * sizeof(int), st));
+  const float4* d_pts;
+  { const msfl_status s = stage_in(p, p->pts, total ? pts + p0 : pts, (size_t)total, mem, st, &d_pts); if (s) return s; }
+  if (widest > 1) HIPCHK(p, p->part.reserve((size_t)co[n_scans] * ds * sizeof(unsigned)));
   const PlaceCfg c = place_cfg(p);
   const size_t lds = ((size_t)ds + place_tab_size(c.nr, c.ns)) * sizeof(unsigned);
-  const int* d_off = p->sp[PL_OFF].as<int>();
+  const int* d_off = p->off.as<int>();
   for (int row0 = 0; row0 < n_scans; row0 += 65535)
     hipLaunchKernelGGL(place_describe_kernel, dim3(widest, std::min(65535, n_scans - row0)), dim3(kPlaceBlock), lds, st, c, d_pts, d_off, n_scans,
-                       row0, desc, p->sp[PL_PART].as<unsigned>());
+                       row0, desc, p->part.as<unsigned>());
   hipLaunchKernelGGL(place_finish_kernel, dim3(n_scans), dim3(kPlaceFinishBlock), (size_t)ds * sizeof(float), st, c, d_off, n_scans,
-                     (const unsigned*)p->sp[PL_PART].as<unsigned>(), desc, rkey, nrm);
+                     (const unsigned*)p->part.as<unsigned>(), desc, rkey, nrm);
   HIPCHK(p, hipGetLastError());
   return MSFL_OK;
 }
@@ -114,45 +116,43 @@ msfl_status place_query(msfl_places* p, const char* who, const float* q_desc, co
     m_count[i] = n_prefilter > 0 ? std::min(n_prefilter, m_cand[i]) : m_cand[i];
     widest = std::max(widest, m_count[i]); most = std::max(most, m_cand[i]);
   }
-  HIPCHK(p, p->sp[PL_META].reserve(meta.size() * sizeof(int)));
-  HIPCHK(p, p->pin.upload(p->sp[PL_META].p, meta.data(), meta.size() * sizeof(int), st));
+  HIPCHK(p, p->meta.reserve(meta.size() * sizeof(int)));
+  HIPCHK(p, p->pin.upload(p->meta.p, meta.data(), meta.size() * sizeof(int), st));
   // queries per launch: the pair records (and the prefilter's keys) of one launch stay within ~4 M entries
   const int per_query = std::max(1, std::max(widest, n_prefilter > 0 ? most : 0));
   const int qb = std::max(1, std::min(std::min(Q, 65535), (1 << 22) / per_query));
   const int pitch = std::max(1, widest);
-  HIPCHK(p, p->sp[PL_REC].reserve((size_t)qb * pitch * sizeof(PlaceRec)));
+  HIPCHK(p, p->rec.reserve((size_t)qb * pitch * sizeof(PlaceRec)));
   if (n_prefilter > 0) {
-    HIPCHK(p, p->sp[PL_KEYS].reserve((size_t)qb * std::max(1, most) * sizeof(unsigned long long)));
-    HIPCHK(p, p->sp[PL_LIST].reserve((size_t)qb * pitch * sizeof(int)));
+    HIPCHK(p, p->keys.reserve((size_t)qb * std::max(1, most) * sizeof(unsigned long long)));
+    HIPCHK(p, p->list.reserve((size_t)qb * pitch * sizeof(int)));
   }
   PlaceRec* d_out = reinterpret_cast<PlaceRec*>(out);
   if (mem == MSFL_MEM_HOST) {
-    HIPCHK(p, p->sp[PL_OUT].reserve((size_t)Q * k * sizeof(PlaceRec)));
-    d_out = p->sp[PL_OUT].as<PlaceRec>();
+    HIPCHK(p, p->out.reserve((size_t)Q * k * sizeof(PlaceRec)));
+    d_out = p->out.as<PlaceRec>();
   }
   const PlaceCfg c = place_cfg(p);
   PlaceQuery j{};
   j.q_desc = q_desc; j.q_rkey = q_rkey; j.q_nrm = q_nrm;
   j.db_desc = p->desc.as<float>(); j.db_rkey = p->rkey.as<int>(); j.db_nrm = p->nrm.as<double>();
-  j.qidx = p->sp[PL_META].as<int>(); j.ncand = j.qidx + Q; j.count = j.ncand + Q;
+  j.qidx = p->meta.as<int>(); j.ncand = j.qidx + Q; j.count = j.ncand + Q;
   j.pitch = pitch;
-  j.list = n_prefilter > 0 ? p->sp[PL_LIST].as<int>() : nullptr;
+  j.list = n_prefilter > 0 ? p->list.as<int>() : nullptr;
   const size_t lds = ((size_t)(2 + kPlaceShiftTile) * c.ns) * sizeof(double) + 2 * (size_t)c.nr * c.ns * sizeof(float);
   for (int q0 = 0; q0 < Q; q0 += qb) {
     const int nq = std::min(qb, Q - q0);
     j.q0 = q0;
     if (n_prefilter > 0 && widest > 0)
-      hipLaunchKernelGGL(place_prefilter_kernel, dim3(nq), dim3(kPlaceBlock), 0, st, c, j, p->sp[PL_KEYS].as<unsigned long long>(), std::max(1, most),
-                         p->sp[PL_LIST].as<int>());
+      hipLaunchKernelGGL(place_prefilter_kernel, dim3(nq), dim3(kPlaceBlock), 0, st, c, j, p->keys.as<unsigned long long>(), std::max(1, most),
+                         p->list.as<int>());
     if (widest > 0)
-      hipLaunchKernelGGL(place_match_kernel, dim3(widest, nq), dim3(kPlaceBlock), lds, st, c, j, p->sp[PL_REC].as<PlaceRec>());
-    hipLaunchKernelGGL(place_topk_kernel, dim3(nq), dim3(kPlaceBlock), 0, st, j, (const PlaceRec*)p->sp[PL_REC].as<PlaceRec>(), k, d_out);
+      hipLaunchKernelGGL(place_match_kernel, dim3(widest, nq), dim3(kPlaceBlock), lds, st, c, j, p->rec.as<PlaceRec>());
+    hipLaunchKernelGGL(place_topk_kernel, dim3(nq), dim3(kPlaceBlock), 0, st, j, (const PlaceRec*)p->rec.as<PlaceRec>(), k, d_out);
   }
   HIPCHK(p, hipGetLastError());
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(p, hipMemcpyAsync(out, d_out, (size_t)Q * k * sizeof(PlaceRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(p, hipStreamSynchronize(st));
-  }
+  { const msfl_status s = stage_out(p, out, d_out, (size_t)Q * k, mem, st); if (s) return s; }
+  if (mem == MSFL_MEM_HOST) HIPCHK(p, hipStreamSynchronize(st));
   (void)who;
   return MSFL_OK;
 }
@@ -205,7 +205,7 @@ msfl_status msfl_places_create(const msfl_place_config* cfg, int device, msfl_pl
   bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) == hipSuccess;
   ok = ok && p->tab.reserve(tab.size() * sizeof(float)) == hipSuccess && p->desc.reserve((size_t)c.capacity * ds * sizeof(float)) == hipSuccess &&
        p->rkey.reserve((size_t)c.capacity * nr * sizeof(int)) == hipSuccess && p->nrm.reserve((size_t)c.capacity * ns * sizeof(double)) == hipSuccess &&
-       p->sp[PL_FLAG].reserve(sizeof(int)) == hipSuccess && p->readback.reserve(sizeof(int)) == hipSuccess;
+       p->flag.reserve(sizeof(int)) == hipSuccess && p->readback.reserve(sizeof(int)) == hipSuccess;
   ok = ok && hipMemcpy(p->tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) { msfl_places_destroy(p); return MSFL_HIP_ERROR; }
   p->stream = p->own_stream;
@@ -267,7 +267,7 @@ msfl_status msfl_places_add_descriptors(msfl_places* p, const float* desc, int n
     for (size_t i = 0; i < count; i++)
       if (!(desc[i] >= 0.f && std::isfinite(desc[i]))) return fail(p, MSFL_BAD_ARG, "msfl_places_add_descriptors: a value is negative or not finite; nothing added");
   } else {                                // checked on the device before anything is stored: the whole add is refused
-    int* flag = p->sp[PL_FLAG].as<int>();
+    int* flag = p->flag.as<int>();
     hipLaunchKernelGGL(place_zero_kernel, dim3(1), dim3(64), 0, st, flag, 1);
     hipLaunchKernelGGL(place_check_kernel, dim3((unsigned)((count + kPlaceBlock - 1) / kPlaceBlock)), dim3(kPlaceBlock), 0, st, desc, count, flag);
     HIPCHK(p, hipGetLastError());
@@ -306,12 +306,12 @@ msfl_status msfl_places_query(msfl_places* p, const msfl_point* pts, const int* 
   s = place_check_scans(p, "msfl_places_query", pts, off, n_queries, mem); if (s) return s;
   if (n_queries == 0) return MSFL_OK;
   const size_t ds = (size_t)p->cfg.n_ring * p->cfg.n_sector;
-  HIPCHK(p, p->sp[PL_QDESC].reserve((size_t)n_queries * ds * sizeof(float)));
-  HIPCHK(p, p->sp[PL_QKEY].reserve((size_t)n_queries * p->cfg.n_ring * sizeof(int)));
-  HIPCHK(p, p->sp[PL_QNRM].reserve((size_t)n_queries * p->cfg.n_sector * sizeof(double)));
-  s = place_describe(p, pts, off, n_queries, mem, p->sp[PL_QDESC].as<float>(), p->sp[PL_QKEY].as<int>(), p->sp[PL_QNRM].as<double>());
+  HIPCHK(p, p->q_desc.reserve((size_t)n_queries * ds * sizeof(float)));
+  HIPCHK(p, p->q_rkey.reserve((size_t)n_queries * p->cfg.n_ring * sizeof(int)));
+  HIPCHK(p, p->q_nrm.reserve((size_t)n_queries * p->cfg.n_sector * sizeof(double)));
+  s = place_describe(p, pts, off, n_queries, mem, p->q_desc.as<float>(), p->q_rkey.as<int>(), p->q_nrm.as<double>());
   if (s) return s;
-  return place_query(p, "msfl_places_query", p->sp[PL_QDESC].as<float>(), p->sp[PL_QKEY].as<int>(), p->sp[PL_QNRM].as<double>(), nullptr, n_queries,
+  return place_query(p, "msfl_places_query", p->q_desc.as<float>(), p->q_rkey.as<int>(), p->q_nrm.as<double>(), nullptr, n_queries,
                      max_index, n_prefilter, k, out, mem);
 }
 

@@ -9,8 +9,6 @@ namespace {
 
 static_assert(sizeof(ScoreRec) == sizeof(msfl_pose_score) && sizeof(msfl_pose_score) == 32, "pose score record layout");
 
-enum { SC_CORNER = 0, SC_SURF, SC_POSES, SC_OFF, SC_REC, SC_D2, SC_NN, SC_SCAN };
-
 // d2_out / nn_out: only with n_scans == 1 (their layout is one row of F values per hypothesis).
 msfl_status score_impl(msfl_handle* h, const char* who, int n_scans, const msfl_point* corner, const int* corner_off, const msfl_point* surf,
                        const int* surf_off, const double* poses, const int* pose_off, double max_dist, msfl_pose_score* scores, float* d2_out,
@@ -43,32 +41,27 @@ msfl_status score_impl(msfl_handle* h, const char* who, int n_scans, const msfl_
   const size_t n_out = (size_t)H * (size_t)(ncp + nsp);     // (single scan) per-feature outputs
   hipStream_t st = h->stream;
   ScoreJob j{};
-  HIPCHK(h, h->sc[SC_OFF].reserve(offs.size() * sizeof(int)));
-  HIPCHK(h, h->pin.upload(h->sc[SC_OFF].p, offs.data(), offs.size() * sizeof(int), st));
-  j.corner_off = h->sc[SC_OFF].as<int>(); j.surf_off = j.corner_off + (n_scans + 1); j.pose_off = j.surf_off + (n_scans + 1);
+  HIPCHK(h, h->sc.off.reserve(offs.size() * sizeof(int)));
+  HIPCHK(h, h->pin.upload(h->sc.off.p, offs.data(), offs.size() * sizeof(int), st));
+  j.corner_off = h->sc.off.as<int>(); j.surf_off = j.corner_off + (n_scans + 1); j.pose_off = j.surf_off + (n_scans + 1);
   j.n_scans = n_scans;
   if (n_scans > 1) {
-    HIPCHK(h, h->sc[SC_SCAN].reserve((size_t)H * sizeof(int)));
-    j.scan_of = h->sc[SC_SCAN].as<int>();
+    HIPCHK(h, h->sc.scan.reserve((size_t)H * sizeof(int)));
+    j.scan_of = h->sc.scan.as<int>();
   }
   j.thr = (float)thr_d;
+  // (both memory kinds read from the first used element on: the offsets are relative to it)
+  msfl_status s = stage_in(h, h->sc.corner, ncp ? corner + c0 : corner, (size_t)ncp, mem, st, &j.corner); if (s) return s;
+  s = stage_in(h, h->sc.surf, nsp ? surf + s0 : surf, (size_t)nsp, mem, st, &j.surf); if (s) return s;
+  s = stage_in(h, h->sc.poses, poses + 7 * (size_t)p0, (size_t)H * 7, mem, st, &j.poses); if (s) return s;
   if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, h->sc[SC_CORNER].reserve(std::max<size_t>(1, (size_t)ncp) * sizeof(float4)));
-    HIPCHK(h, h->sc[SC_SURF].reserve(std::max<size_t>(1, (size_t)nsp) * sizeof(float4)));
-    HIPCHK(h, h->sc[SC_POSES].reserve((size_t)H * 7 * sizeof(double)));
-    HIPCHK(h, h->sc[SC_REC].reserve((size_t)H * sizeof(ScoreRec)));
-    if (d2_out && n_out) HIPCHK(h, h->sc[SC_D2].reserve(n_out * sizeof(float)));
-    if (nn_out && n_out) HIPCHK(h, h->sc[SC_NN].reserve(n_out * sizeof(int)));
-    if (ncp) HIPCHK(h, hipMemcpyAsync(h->sc[SC_CORNER].p, corner + c0, (size_t)ncp * sizeof(float4), hipMemcpyHostToDevice, st));
-    if (nsp) HIPCHK(h, hipMemcpyAsync(h->sc[SC_SURF].p, surf + s0, (size_t)nsp * sizeof(float4), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->sc[SC_POSES].p, poses + 7 * (size_t)p0, (size_t)H * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-    j.corner = h->sc[SC_CORNER].as<float4>(); j.surf = h->sc[SC_SURF].as<float4>(); j.poses = h->sc[SC_POSES].as<double>();
-    j.rec = h->sc[SC_REC].as<ScoreRec>();
-    j.d2_out = d2_out && n_out ? h->sc[SC_D2].as<float>() : nullptr;
-    j.nn_out = nn_out && n_out ? h->sc[SC_NN].as<int>() : nullptr;
+    HIPCHK(h, h->sc.rec.reserve((size_t)H * sizeof(ScoreRec)));
+    if (d2_out && n_out) HIPCHK(h, h->sc.d2.reserve(n_out * sizeof(float)));
+    if (nn_out && n_out) HIPCHK(h, h->sc.nn.reserve(n_out * sizeof(int)));
+    j.rec = h->sc.rec.as<ScoreRec>();
+    j.d2_out = d2_out && n_out ? h->sc.d2.as<float>() : nullptr;
+    j.nn_out = nn_out && n_out ? h->sc.nn.as<int>() : nullptr;
   } else {
-    j.corner = reinterpret_cast<const float4*>(corner) + c0; j.surf = reinterpret_cast<const float4*>(surf) + s0;
-    j.poses = poses + 7 * (size_t)p0;
     j.rec = reinterpret_cast<ScoreRec*>(scores) + p0;
     j.d2_out = d2_out; j.nn_out = nn_out;
   }
@@ -84,12 +77,10 @@ msfl_status score_impl(msfl_handle* h, const char* who, int n_scans, const msfl_
     }
   }
   HIPCHK(h, hipGetLastError());
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, hipMemcpyAsync(scores + p0, j.rec, (size_t)H * sizeof(ScoreRec), hipMemcpyDeviceToHost, st));
-    if (j.d2_out) HIPCHK(h, hipMemcpyAsync(d2_out, j.d2_out, n_out * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (j.nn_out) HIPCHK(h, hipMemcpyAsync(nn_out, j.nn_out, n_out * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-  }
+  s = stage_out(h, scores + p0, j.rec, (size_t)H, mem, st); if (s) return s;
+  if (j.d2_out) { s = stage_out(h, d2_out, j.d2_out, n_out, mem, st); if (s) return s; }
+  if (j.nn_out) { s = stage_out(h, nn_out, j.nn_out, n_out, mem, st); if (s) return s; }
+  if (mem == MSFL_MEM_HOST) HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 

@@ -270,31 +270,17 @@ msfl_status scan2scan_dyn(msfl_handle* h, const SlamScanBuf& last, const SlamSca
   const bool use_grid = gate_fits_grid && !h->odom_force_brute;
   // one pair per call: the machine is empty, so a query gets a whole wavefront (kSlamOdomLanes lanes walk its column runs;
   // the minima are order-free lexicographic keys, results do not depend on the lane count) instead of the batch's 16 lanes
-  OdomIndex oix{nullptr, nullptr, nullptr, nullptr, std::max(1, div_up(caps.flat, kOdomBlock / kSlamOdomLanes))};
-  OdomIndex oie{nullptr, nullptr, nullptr, nullptr, std::max(1, div_up(caps.sharp, kOdomBlock / kSlamOdomLanes))};
+  OdomIndex oix, oie;
+  { msfl_status is = odom_index(h, h->od.planes, use_grid, B, (size_t)caps.less_flat, caps.flat, kOdomBlock / kSlamOdomLanes, &oix); if (is) return is;
+    is = odom_index(h, h->od.edges, use_grid, B, (size_t)caps.less_sharp, caps.sharp, kOdomBlock / kSlamOdomLanes, &oie); if (is) return is; }
   if (use_grid) {
     ScopedTimer timer(h, T_ODOM);
-    HIPCHK(h, h->od[OD_TAB].reserve((size_t)B * kOdomTabStride * sizeof(unsigned)));
-    HIPCHK(h, h->od[OD_SORTED].reserve((size_t)caps.less_flat * sizeof(float4)));
-    HIPCHK(h, h->od[OD_DESC].reserve((size_t)B * sizeof(OdomPairDesc)));
-    HIPCHK(h, h->od[OD_MODE].reserve((size_t)B * sizeof(int)));
-    HIPCHK(h, h->od[OD_TAB_E].reserve((size_t)B * kOdomTabStride * sizeof(unsigned)));
-    HIPCHK(h, h->od[OD_SORTED_E].reserve((size_t)caps.less_sharp * sizeof(float4)));
-    HIPCHK(h, h->od[OD_DESC_E].reserve((size_t)B * sizeof(OdomPairDesc)));
-    HIPCHK(h, h->od[OD_MODE_E].reserve((size_t)B * sizeof(int)));
-    oix.tab = h->od[OD_TAB].as<unsigned>(); oix.sorted = h->od[OD_SORTED].as<float4>();
-    oix.desc = h->od[OD_DESC].as<OdomPairDesc>(); oix.mode = h->od[OD_MODE].as<int>();
-    oie.tab = h->od[OD_TAB_E].as<unsigned>(); oie.sorted = h->od[OD_SORTED_E].as<float4>();
-    oie.desc = h->od[OD_DESC_E].as<OdomPairDesc>(); oie.mode = h->od[OD_MODE_E].as<int>();
-    const OdomBinJob job_lf{ov.last_lf, ov.last_lf_ring, ov.last_lf_off, const_cast<unsigned*>(oix.tab), const_cast<float4*>(oix.sorted),
-                            const_cast<OdomPairDesc*>(oix.desc), const_cast<int*>(oix.mode)};
-    const OdomBinJob job_ls{ov.last_ls, ov.last_ls_ring, ov.last_ls_off, const_cast<unsigned*>(oie.tab), const_cast<float4*>(oie.sorted),
-                            const_cast<OdomPairDesc*>(oie.desc), const_cast<int*>(oie.mode)};
     // a LAST scan of more than 32 768 points (a 64-beam sensor) takes the several-workgroups form of the index build (three more launches).
     // Decided by the points that scan actually had (known on the host since its msfl_slam_add_scan; its less-flat list is a subset), not by
     // the session's capacity: with the default max_scan_points = 200 000 every 16-beam scan used to take the split form too (ADVICE r05).
     // Both forms build the same index bit for bit (test_binning_a_64_beam_sized_cloud_...), so the choice cannot change a result.
-    msfl_status bs = launch_odom_bin(h, st, job_lf, job_ls, 2 * B, B, std::min<long long>(caps.less_flat, last.n));
+    msfl_status bs = launch_odom_bin(h, st, odom_bin_job(ov.last_lf, ov.last_lf_ring, ov.last_lf_off, oix),
+                                     odom_bin_job(ov.last_ls, ov.last_ls_ring, ov.last_ls_off, oie), 2 * B, B, std::min<long long>(caps.less_flat, last.n));
     if (bs != MSFL_OK) return bs;
   }
   // one solve on an empty machine: the wide workgroup of the mapping solve (~570 records: one per thread and pass)

@@ -29,31 +29,27 @@ ExtractParams extract_params(const msfl_params& p) {
   return e;
 }
 
-// ex[] slot assignment
-enum { EX_IN_PTS = 0, EX_IN_RING, EX_OFF, EX_FULL, EX_RING, EX_CURV, EX_LABEL, EX_IDX, EX_CNT, EX_STATUS, EX_GAP,
-       EX_TAB, EX_TMP, EX_RCNT, EX_SPLIT };
-
 // All array pointers are device pointers; `h_off` is the host offset table.
 msfl_status extract_device(msfl_handle* h, int B, const float4* d_pts, const uint16_t* d_ring, const int* h_off,
                            const double* d_extrinsic, ExtractView& v) {
   hipStream_t st = h->stream;
   const int o0 = h_off[0];
   const int n_total = h_off[B] - o0;
-  HIPCHK(h, h->ex[EX_OFF].reserve((size_t)(B + 1) * sizeof(int)));
+  HIPCHK(h, h->ex.off.reserve((size_t)(B + 1) * sizeof(int)));
   std::vector<int> offs(B + 1);
   for (int b = 0; b <= B; b++) {
     offs[b] = h_off[b] - o0;
     if (b > 0 && offs[b] < offs[b - 1]) return fail(h, MSFL_BAD_ARG, "extract: offsets must be non-decreasing");
   }
-  HIPCHK(h, h->pin.upload(h->ex[EX_OFF].p, offs.data(), offs.size() * sizeof(int), st));
+  HIPCHK(h, h->pin.upload(h->ex.off.p, offs.data(), offs.size() * sizeof(int), st));
   const size_t nt = std::max<size_t>(1, (size_t)n_total);
-  HIPCHK(h, h->ex[EX_GAP].reserve(nt));
-  HIPCHK(h, h->ex[EX_TAB].reserve((size_t)B * (kMaxRings + 1) * sizeof(int)));
-  HIPCHK(h, h->ex[EX_TMP].reserve(nt * 4 * sizeof(int)));
-  HIPCHK(h, h->ex[EX_RCNT].reserve((size_t)B * kMaxRings * 4 * sizeof(int)));
-  v.in_pts = d_pts + o0; v.in_ring = d_ring + o0; v.off = h->ex[EX_OFF].as<int>(); v.n_scans = B; v.n_total = n_total;
-  v.gap = h->ex[EX_GAP].as<uint8_t>(); v.ring_tab = h->ex[EX_TAB].as<int>();
-  v.tmp_idx = h->ex[EX_TMP].as<int>(); v.ring_cnt = h->ex[EX_RCNT].as<int>();
+  HIPCHK(h, h->ex.gap.reserve(nt));
+  HIPCHK(h, h->ex.ring_tab.reserve((size_t)B * (kMaxRings + 1) * sizeof(int)));
+  HIPCHK(h, h->ex.tmp_idx.reserve(nt * 4 * sizeof(int)));
+  HIPCHK(h, h->ex.ring_cnt.reserve((size_t)B * kMaxRings * 4 * sizeof(int)));
+  v.in_pts = d_pts + o0; v.in_ring = d_ring + o0; v.off = h->ex.off.as<int>(); v.n_scans = B; v.n_total = n_total;
+  v.gap = h->ex.gap.as<uint8_t>(); v.ring_tab = h->ex.ring_tab.as<int>();
+  v.tmp_idx = h->ex.tmp_idx.as<int>(); v.ring_cnt = h->ex.ring_cnt.as<int>();
   HIPCHK(h, hipMemsetAsync(v.status, 0, (size_t)B * sizeof(int), st));
   const ExtractParams ep = extract_params(h->prm);
   ScopedTimer timer(h, T_EXTRACT);
@@ -65,8 +61,8 @@ msfl_status extract_device(msfl_handle* h, int B, const float4* d_pts, const uin
   if (h->prep_split <= 0 && G == 1 && B > 0 && (long long)n_total / B > 65536) G = 2;
   if ((long long)B * G > 65535) G = 1;
   if (G > 1) {
-    HIPCHK(h, h->ex[EX_SPLIT].reserve(prep_split_bytes(B, G)));
-    const PrepSplitView sv = prep_split_view(h->ex[EX_SPLIT].p, B, G);
+    HIPCHK(h, h->ex.split.reserve(prep_split_bytes(B, G)));
+    const PrepSplitView sv = prep_split_view(h->ex.split.p, B, G);
     hipLaunchKernelGGL(extract_prepare_count_kernel, dim3(G, B), dim3(1024), 0, st, v, ep, sv);
     hipLaunchKernelGGL(extract_prepare_scatter_kernel, dim3(G, B), dim3(1024), 0, st, v, ep, sv);
     hipLaunchKernelGGL(extract_prepare_finish_kernel, dim3(G, B), dim3(1024), 0, st, v, ep, sv);
@@ -108,12 +104,13 @@ msfl_status extract_batch_impl(msfl_handle* h, int B, const msfl_point* pts, con
     v.n_full = out->n_full; v.n_sharp = out->n_sharp; v.n_less_sharp = out->n_less_sharp; v.n_flat = out->n_flat;
     v.n_less_flat = out->n_less_flat;
     if (status) v.status = status;
-    else { HIPCHK(h, h->ex[EX_STATUS].reserve((size_t)B * sizeof(int))); v.status = h->ex[EX_STATUS].as<int>(); }
+    else { HIPCHK(h, h->ex.status.reserve((size_t)B * sizeof(int))); v.status = h->ex.status.as<int>(); }
     return extract_device(h, B, reinterpret_cast<const float4*>(pts), ring, off, d_ext, v);
   }
   // host mode: stage in, run, stage out
-  HIPCHK(h, h->ex[EX_IN_PTS].reserve(nt * sizeof(float4)));
-  HIPCHK(h, h->ex[EX_IN_RING].reserve(nt * sizeof(uint16_t)));
+  const float4* d_pts; const uint16_t* d_ring;
+  msfl_status s = stage_in(h, h->ex.in_pts, n_total ? pts + o0 : pts, (size_t)n_total, mem, st, &d_pts); if (s) return s;
+  s = stage_in(h, h->ex.in_ring, n_total ? ring + o0 : ring, (size_t)n_total, mem, st, &d_ring); if (s) return s;
   // All outputs live in ONE device buffer.  A small call (one scan is ~1 MB of outputs) brings them back with one copy
   // into pinned memory and hands them out with memcpy: fourteen separate transfers of 24 B .. 380 KB were 0.25 ms of a
   // single scan's 0.45.  A large batch keeps one transfer per array straight into the caller's memory.
@@ -121,12 +118,8 @@ msfl_status extract_batch_impl(msfl_handle* h, int B, const msfl_point* pts, con
   const size_t o_full = 0, o_idx = o_full + up(nt * sizeof(float4)), o_curv = o_idx + up(nt * 4 * sizeof(int)),
                o_ring = o_curv + up(nt * sizeof(float)), o_label = o_ring + up(nt * sizeof(uint16_t)),
                o_cnt = o_label + up(nt), o_status = o_cnt + up((size_t)B * 5 * sizeof(int)), pack_bytes = o_status + up((size_t)B * sizeof(int));
-  HIPCHK(h, h->ex[EX_FULL].reserve(pack_bytes));
-  char* pack = h->ex[EX_FULL].as<char>();
-  if (n_total) {
-    HIPCHK(h, hipMemcpyAsync(h->ex[EX_IN_PTS].p, pts + o0, (size_t)n_total * sizeof(float4), hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->ex[EX_IN_RING].p, ring + o0, (size_t)n_total * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-  }
+  HIPCHK(h, h->ex.pack.reserve(pack_bytes));
+  char* pack = h->ex.pack.as<char>();
   v.full_pts = reinterpret_cast<float4*>(pack + o_full); v.full_ring = reinterpret_cast<uint16_t*>(pack + o_ring);
   v.curvature = reinterpret_cast<float*>(pack + o_curv); v.label = reinterpret_cast<uint8_t*>(pack + o_label);
   int* idx = reinterpret_cast<int*>(pack + o_idx);
@@ -136,10 +129,11 @@ msfl_status extract_batch_impl(msfl_handle* h, int B, const msfl_point* pts, con
   v.status = reinterpret_cast<int*>(pack + o_status);
   std::vector<int> rel_off(B + 1);
   for (int b = 0; b <= B; b++) rel_off[b] = off[b] - o0;
-  msfl_status s = extract_device(h, B, h->ex[EX_IN_PTS].as<float4>(), h->ex[EX_IN_RING].as<uint16_t>(), rel_off.data(), d_ext, v);
+  s = extract_device(h, B, d_pts, d_ring, rel_off.data(), d_ext, v);
   if (s) return s;
   const size_t n = (size_t)n_total;
   int* out_cnt[5] = {out->n_full, out->n_sharp, out->n_less_sharp, out->n_flat, out->n_less_flat};
+  int* lists[4] = {out->sharp_idx, out->less_sharp_idx, out->flat_idx, out->less_flat_idx};
   if (pack_bytes <= (size_t)4 << 20) {
     HIPCHK(h, h->readback.reserve(pack_bytes));
     const char* hp = h->readback.as<char>();
@@ -150,32 +144,40 @@ msfl_status extract_batch_impl(msfl_handle* h, int B, const msfl_point* pts, con
       std::memcpy(out->full_ring + o0, hp + o_ring, n * sizeof(uint16_t));
       std::memcpy(out->curvature + o0, hp + o_curv, n * sizeof(float));
       std::memcpy(out->label + o0, hp + o_label, n);
-      int* lists[4] = {out->sharp_idx, out->less_sharp_idx, out->flat_idx, out->less_flat_idx};
       for (int k = 0; k < 4; k++) std::memcpy(lists[k] + o0, hp + o_idx + (size_t)k * nt * sizeof(int), n * sizeof(int));
     }
     for (int k = 0; k < 5; k++) std::memcpy(out_cnt[k], hp + o_cnt + (size_t)k * B * sizeof(int), (size_t)B * sizeof(int));
     if (status) std::memcpy(status, hp + o_status, (size_t)B * sizeof(int));
     return MSFL_OK;
   }
-  if (n) {
-    HIPCHK(h, hipMemcpyAsync(out->full_pts + o0, v.full_pts, n * sizeof(float4), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out->full_ring + o0, v.full_ring, n * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out->curvature + o0, v.curvature, n * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out->label + o0, v.label, n, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out->sharp_idx + o0, v.sharp_idx, n * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out->less_sharp_idx + o0, v.less_sharp_idx, n * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out->flat_idx + o0, v.flat_idx, n * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out->less_flat_idx + o0, v.less_flat_idx, n * sizeof(int), hipMemcpyDeviceToHost, st));
-  }
-  for (int k = 0; k < 5; k++) HIPCHK(h, hipMemcpyAsync(out_cnt[k], cnt + (size_t)k * B, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
-  if (status) HIPCHK(h, hipMemcpyAsync(status, v.status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st));
+  s = stage_out(h, out->full_pts + o0, v.full_pts, n, mem, st); if (s) return s;
+  s = stage_out(h, out->full_ring + o0, v.full_ring, n, mem, st); if (s) return s;
+  s = stage_out(h, out->curvature + o0, v.curvature, n, mem, st); if (s) return s;
+  s = stage_out(h, out->label + o0, v.label, n, mem, st); if (s) return s;
+  for (int k = 0; k < 4; k++) { s = stage_out(h, lists[k] + o0, idx + (size_t)k * nt, n, mem, st); if (s) return s; }
+  for (int k = 0; k < 5; k++) { s = stage_out(h, out_cnt[k], cnt + (size_t)k * B, (size_t)B, mem, st); if (s) return s; }
+  if (status) { s = stage_out(h, status, v.status, (size_t)B, mem, st); if (s) return s; }
   HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 
-// od[] slot assignment
-enum { OD_PTS0 = 0, OD_PTS1, OD_PTS2, OD_PTS3, OD_RING0, OD_RING1, OD_OFFS, OD_POSES, OD_STATUS,
-       OD_TAB, OD_SORTED, OD_DESC, OD_MODE, OD_TAB_E, OD_SORTED_E, OD_DESC_E, OD_MODE_E, OD_SPLIT };
+// The column index of one feature family as the association kernel takes it: a pair's queries (`longest_query` in the pair with the
+// most) go `queries_per_block` to a workgroup.  use = false: no index, the family's queries stay on the brute-force kernel.  Else `b` is
+// reserved for B pairs whose previous-scan clouds end at point `n_sorted` of their array.
+msfl_status odom_index(msfl_handle* h, OdomIndexBufs& b, bool use, int B, size_t n_sorted, int longest_query, int queries_per_block, OdomIndex* ix) {
+  *ix = OdomIndex{nullptr, nullptr, nullptr, nullptr, std::max(1, div_up(longest_query, queries_per_block))};
+  if (!use) return MSFL_OK;
+  HIPCHK(h, b.tab.reserve((size_t)B * kOdomTabStride * sizeof(unsigned)));
+  HIPCHK(h, b.sorted.reserve(n_sorted * sizeof(float4)));
+  HIPCHK(h, b.desc.reserve((size_t)B * sizeof(OdomPairDesc)));
+  HIPCHK(h, b.mode.reserve((size_t)B * sizeof(int)));
+  ix->tab = b.tab.as<unsigned>(); ix->sorted = b.sorted.as<float4>(); ix->desc = b.desc.as<OdomPairDesc>(); ix->mode = b.mode.as<int>();
+  return MSFL_OK;
+}
+// The build job of that index over the family's clouds (the build writes what the queries only read).
+OdomBinJob odom_bin_job(const float4* pts, const uint16_t* ring, const int* off, const OdomIndex& ix) {
+  return OdomBinJob{pts, ring, off, const_cast<unsigned*>(ix.tab), const_cast<float4*>(ix.sorted), const_cast<OdomPairDesc*>(ix.desc), const_cast<int*>(ix.mode)};
+}
 
 // The index build of `jobs` clouds (n_pairs less-flat clouds, then -- jobs = 2 n_pairs -- the less-sharp ones): one workgroup per cloud,
 // or, when the call holds few pairs and a cloud is long (`longest` points: a 64-beam less-flat list), 64 workgroups per cloud in four launches.
@@ -188,9 +190,9 @@ msfl_status launch_odom_bin(msfl_handle* h, hipStream_t st, const OdomBinJob& jo
   OdomBinSplit sp;
   sp.G = 64;
   const size_t cur_bytes = (size_t)jobs * kOdomTabStride * sizeof(unsigned);
-  HIPCHK(h, h->od[OD_SPLIT].reserve(cur_bytes + (size_t)jobs * sp.G * 8 * sizeof(int)));
-  sp.cur = h->od[OD_SPLIT].as<unsigned>();
-  sp.part = reinterpret_cast<int*>(h->od[OD_SPLIT].as<char>() + cur_bytes);
+  HIPCHK(h, h->od.split.reserve(cur_bytes + (size_t)jobs * sp.G * 8 * sizeof(int)));
+  sp.cur = h->od.split.as<unsigned>();
+  sp.part = reinterpret_cast<int*>(h->od.split.as<char>() + cur_bytes);
   hipLaunchKernelGGL(odom_bin_box_kernel, dim3(sp.G, jobs), dim3(kOdomSplitThreads), 0, st, job_lf, job_ls, n_pairs, sp);
   hipLaunchKernelGGL(odom_bin_count_kernel, dim3(sp.G, jobs), dim3(kOdomSplitThreads), 0, st, job_lf, job_ls, n_pairs, sp);
   hipLaunchKernelGGL(odom_bin_scan_kernel, dim3(jobs), dim3(1024), 0, st, job_lf, job_ls, n_pairs, sp);
@@ -221,33 +223,19 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
     offs[4 * (B + 1) + b] = (cl[2]->off[b] - base[2]) + (cl[3]->off[b] - base[3]);
   }
   const int n_rec = offs[4 * (B + 1) + B];
-  HIPCHK(h, h->od[OD_OFFS].reserve(offs.size() * sizeof(int)));
-  HIPCHK(h, h->pin.upload(h->od[OD_OFFS].p, offs.data(), offs.size() * sizeof(int), st));
-  const int* d_off = h->od[OD_OFFS].as<int>();
+  HIPCHK(h, h->od.offs.reserve(offs.size() * sizeof(int)));
+  HIPCHK(h, h->pin.upload(h->od.offs.p, offs.data(), offs.size() * sizeof(int), st));
+  const int* d_off = h->od.offs.as<int>();
   const float4* d_pts[4]; const uint16_t* d_ring[2];
   double* d_poses; int* d_status;
-  if (mem == MSFL_MEM_HOST) {
-    for (int k = 0; k < 4; k++) {
-      const int n = cl[k]->off[B] - base[k];
-      HIPCHK(h, h->od[OD_PTS0 + k].reserve(std::max<size_t>(1, (size_t)n) * sizeof(float4)));
-      if (n) HIPCHK(h, hipMemcpyAsync(h->od[OD_PTS0 + k].p, cl[k]->pts + base[k], (size_t)n * sizeof(float4), hipMemcpyHostToDevice, st));
-      d_pts[k] = h->od[OD_PTS0 + k].as<float4>();
-      if (k < 2) {
-        HIPCHK(h, h->od[OD_RING0 + k].reserve(std::max<size_t>(1, (size_t)n) * sizeof(uint16_t)));
-        if (n) HIPCHK(h, hipMemcpyAsync(h->od[OD_RING0 + k].p, cl[k]->ring + base[k], (size_t)n * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-        d_ring[k] = h->od[OD_RING0 + k].as<uint16_t>();
-      }
-    }
-    HIPCHK(h, h->od[OD_POSES].reserve((size_t)B * 7 * sizeof(double)));
-    HIPCHK(h, hipMemcpyAsync(h->od[OD_POSES].p, poses_io, (size_t)B * 7 * sizeof(double), hipMemcpyHostToDevice, st));
-    d_poses = h->od[OD_POSES].as<double>();
-  } else {
-    for (int k = 0; k < 4; k++) d_pts[k] = reinterpret_cast<const float4*>(cl[k]->pts);
-    d_ring[0] = cl[0]->ring; d_ring[1] = cl[1]->ring;
-    d_poses = poses_io;
+  for (int k = 0; k < 4; k++) {          // a host cloud is staged from its first used point (the offsets above are relative to it)
+    const size_t n = (size_t)(cl[k]->off[B] - base[k]), skip = mem == MSFL_MEM_HOST && n ? (size_t)base[k] : 0;
+    msfl_status us = stage_in(h, h->od.pts[k], cl[k]->pts + skip, n, mem, st, &d_pts[k]); if (us) return us;
+    if (k < 2) { us = stage_in(h, h->od.ring[k], cl[k]->ring + skip, n, mem, st, &d_ring[k]); if (us) return us; }
   }
+  { const msfl_status us = stage_in(h, h->od.poses, poses_io, (size_t)B * 7, mem, st, &d_poses); if (us) return us; }
   if (mem == MSFL_MEM_DEVICE && status) d_status = status;
-  else { HIPCHK(h, h->od[OD_STATUS].reserve((size_t)B * sizeof(int))); d_status = h->od[OD_STATUS].as<int>(); }
+  else { HIPCHK(h, h->od.status.reserve((size_t)B * sizeof(int))); d_status = h->od.status.as<int>(); }
   HIPCHK(h, hipMemsetAsync(d_status, 0, (size_t)B * sizeof(int), st));
   RegSinks sinks;
   { const msfl_status us = reg_open(h, B, st, info != nullptr, &sinks); if (us) return us; }
@@ -277,36 +265,19 @@ msfl_status scan2scan_batch_impl(msfl_handle* h, int B, const msfl_ring_cloud_ba
   // only exhaustive for gates below 36 m^2: a larger odom_distance_sq_threshold keeps the brute-force kernel (exact for any gate).
   const bool gate_fits_grid = h->prm.odom_distance_sq_threshold <= 35.9;
   const bool use_grid = !latency_path && max_flat > 0 && n_lf > 0 && !h->odom_force_brute && B <= 16384 && gate_fits_grid;
-  OdomIndex oix{nullptr, nullptr, nullptr, nullptr, std::max(1, div_up(max_flat, kOdomBlock / kOdomLanes))};
   int max_sharp = 0;
   for (int b = 0; b < B; b++) max_sharp = std::max(max_sharp, offs[2 * (B + 1) + b + 1] - offs[2 * (B + 1) + b]);
   const int n_ls_end = offs[B];
-  const bool use_grid_e = use_grid && max_sharp > 0 && n_ls_end > offs[0];
-  OdomIndex oie{nullptr, nullptr, nullptr, nullptr, std::max(1, div_up(max_sharp, kOdomBlock / kOdomLanes))};
+  const bool use_grid_e = use_grid && max_sharp > 0 && n_ls_end > offs[0];   // the same index over the (small) less-sharp clouds for the edge queries
+  OdomIndex oix, oie;
+  { msfl_status is = odom_index(h, h->od.planes, use_grid, B, (size_t)lf_first + (size_t)n_lf, max_flat, kOdomBlock / kOdomLanes, &oix); if (is) return is;
+    is = odom_index(h, h->od.edges, use_grid_e, B, (size_t)n_ls_end, max_sharp, kOdomBlock / kOdomLanes, &oie); if (is) return is; }
   if (use_grid) {
     ScopedTimer timer(h, T_ODOM);
-    const size_t n_end = (size_t)lf_first + (size_t)n_lf;
-    HIPCHK(h, h->od[OD_TAB].reserve((size_t)B * kOdomTabStride * sizeof(unsigned)));
-    HIPCHK(h, h->od[OD_SORTED].reserve(n_end * sizeof(float4)));
-    HIPCHK(h, h->od[OD_DESC].reserve((size_t)B * sizeof(OdomPairDesc)));
-    HIPCHK(h, h->od[OD_MODE].reserve((size_t)B * sizeof(int)));
-    oix.tab = h->od[OD_TAB].as<unsigned>(); oix.sorted = h->od[OD_SORTED].as<float4>();
-    oix.desc = h->od[OD_DESC].as<OdomPairDesc>(); oix.mode = h->od[OD_MODE].as<int>();
-    if (use_grid_e) {                         // the same index over the (small) less-sharp clouds for the edge queries
-      HIPCHK(h, h->od[OD_TAB_E].reserve((size_t)B * kOdomTabStride * sizeof(unsigned)));
-      HIPCHK(h, h->od[OD_SORTED_E].reserve((size_t)n_ls_end * sizeof(float4)));
-      HIPCHK(h, h->od[OD_DESC_E].reserve((size_t)B * sizeof(OdomPairDesc)));
-      HIPCHK(h, h->od[OD_MODE_E].reserve((size_t)B * sizeof(int)));
-      oie.tab = h->od[OD_TAB_E].as<unsigned>(); oie.sorted = h->od[OD_SORTED_E].as<float4>();
-      oie.desc = h->od[OD_DESC_E].as<OdomPairDesc>(); oie.mode = h->od[OD_MODE_E].as<int>();
-    }
-    const OdomBinJob job_lf{ov.last_lf, ov.last_lf_ring, ov.last_lf_off, const_cast<unsigned*>(oix.tab), const_cast<float4*>(oix.sorted),
-                            const_cast<OdomPairDesc*>(oix.desc), const_cast<int*>(oix.mode)};
-    const OdomBinJob job_ls{ov.last_ls, ov.last_ls_ring, ov.last_ls_off, const_cast<unsigned*>(oie.tab), const_cast<float4*>(oie.sorted),
-                            const_cast<OdomPairDesc*>(oie.desc), const_cast<int*>(oie.mode)};
     int longest = 0;
     for (int b = 0; b < B; b++) longest = std::max(longest, offs[(B + 1) + b + 1] - offs[(B + 1) + b]);
-    msfl_status bs = launch_odom_bin(h, st, job_lf, job_ls, use_grid_e ? 2 * B : B, B, longest);     // both families in one launch
+    msfl_status bs = launch_odom_bin(h, st, odom_bin_job(ov.last_lf, ov.last_lf_ring, ov.last_lf_off, oix),
+                                     odom_bin_job(ov.last_ls, ov.last_ls_ring, ov.last_ls_off, oie), use_grid_e ? 2 * B : B, B, longest);     // both families in one launch
     if (bs != MSFL_OK) return bs;
   }
   const msfl_status ss = solve_outer<kOdomLmBlock>(h, B, bv, nullptr, d_poses, d_status, sinks, sp, h->prm.outer_iterations, [&](int) {
@@ -417,28 +388,28 @@ msfl_status msfl_voxel_downsample(msfl_handle* h, const msfl_point* pts, int n, 
   // if (!pcl_isfinite(x) ...) continue;`).  Rare path, entirely on the device: stable compaction of the finite points, then the
   // same filter on what is left.  (The batch forms keep refusing such a cloud: their clouds are the extraction's outputs,
   // which cannot hold one, msf_loam_node.cc:85-111.)
-  enum { PP_PTS = 1, PP_DQ = 2, PP_FLAG = 4 };                                    // the per-point passes' scratch slots (msfl_api_deskew.inc)
+  // It works in the per-point passes' scratch: pp.pts takes the finite points, pp.dq the filtered ones, pp.flag their count.
   hipStream_t st = h->stream;
   const float4* d_in = h->vox_staged_pts;                                       // where the batch call left (or found) this cloud on the device
-  HIPCHK(h, h->pp[PP_PTS].reserve((size_t)n * sizeof(float4)));
-  HIPCHK(h, h->pp[PP_DQ].reserve((size_t)n * sizeof(float4)));
-  HIPCHK(h, h->pp[PP_FLAG].reserve(sizeof(unsigned int)));
+  HIPCHK(h, h->pp.pts.reserve((size_t)n * sizeof(float4)));
+  HIPCHK(h, h->pp.dq.reserve((size_t)n * sizeof(float4)));
+  HIPCHK(h, h->pp.flag.reserve(sizeof(unsigned int)));
   size_t tb = 0;
-  HIPCHK(h, rocprim::select(nullptr, tb, d_in, h->pp[PP_PTS].as<float4>(), h->pp[PP_FLAG].as<unsigned int>(), (size_t)n, FinitePoint(), st));
+  HIPCHK(h, rocprim::select(nullptr, tb, d_in, h->pp.pts.as<float4>(), h->pp.flag.as<unsigned int>(), (size_t)n, FinitePoint(), st));
   HIPCHK(h, h->idx_cub.reserve(tb));
-  HIPCHK(h, rocprim::select(h->idx_cub.p, tb, d_in, h->pp[PP_PTS].as<float4>(), h->pp[PP_FLAG].as<unsigned int>(), (size_t)n, FinitePoint(), st));
+  HIPCHK(h, rocprim::select(h->idx_cub.p, tb, d_in, h->pp.pts.as<float4>(), h->pp.flag.as<unsigned int>(), (size_t)n, FinitePoint(), st));
   unsigned int m = 0;
-  HIPCHK(h, hipMemcpyAsync(&m, h->pp[PP_FLAG].p, sizeof(m), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipMemcpyAsync(&m, h->pp.flag.p, sizeof(m), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
   *n_out = 0;
   h->last_error.clear();
   if (m == 0) return MSFL_OK;
   const int off2[2] = {0, (int)m};
-  s = msfl_voxel_downsample_batch(h, 1, reinterpret_cast<const msfl_point*>(h->pp[PP_PTS].p), nullptr, off2, nullptr, leaf,
-                                  reinterpret_cast<msfl_point*>(h->pp[PP_DQ].p), out_off, MSFL_MEM_DEVICE);
+  s = msfl_voxel_downsample_batch(h, 1, reinterpret_cast<const msfl_point*>(h->pp.pts.p), nullptr, off2, nullptr, leaf,
+                                  reinterpret_cast<msfl_point*>(h->pp.dq.p), out_off, MSFL_MEM_DEVICE);
   if (s) return s;
   *n_out = out_off[1];
-  HIPCHK(h, hipMemcpyAsync(out, h->pp[PP_DQ].p, (size_t)out_off[1] * sizeof(float4), mem == MSFL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+  HIPCHK(h, hipMemcpyAsync(out, h->pp.dq.p, (size_t)out_off[1] * sizeof(float4), mem == MSFL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
   HIPCHK(h, hipStreamSynchronize(st));
   return MSFL_OK;
 }
@@ -457,50 +428,35 @@ msfl_status msfl_voxel_downsample_batch(msfl_handle* h, int n_clouds, const msfl
   if (n_total == 0) return MSFL_OK;
   if (!pts || !out) return fail(h, MSFL_BAD_ARG, "msfl_voxel_downsample_batch: null cloud");
   hipStream_t st = h->stream;
-  // vb[] slots: points, index list, counts, offsets, desc, keys x2, vals x2, flag+pos, out, out_count+out_off
-  enum { VB_PTS = 0, VB_IDX, VB_CNT, VB_OFF, VB_DESC, VB_K1, VB_K2, VB_V1, VB_V2, VB_FLAG, VB_OUT, VB_OCNT, VB_PC, VB_SP };
-  DevBuf* vb = h->vb;
+  VoxelScratch& vox = h->vox;
+  const int skip = mem == MSFL_MEM_HOST ? o0 : 0;       // a host batch is staged from its first used point
   std::vector<int> offs(B + 1);
-  for (int b = 0; b <= B; b++) offs[b] = off[b] - (mem == MSFL_MEM_HOST ? o0 : 0);
-  HIPCHK(h, vb[VB_OFF].reserve(offs.size() * sizeof(int)));
-  HIPCHK(h, h->pin.upload(vb[VB_OFF].p, offs.data(), offs.size() * sizeof(int), st));
+  for (int b = 0; b <= B; b++) offs[b] = off[b] - skip;
+  HIPCHK(h, vox.off.reserve(offs.size() * sizeof(int)));
+  HIPCHK(h, h->pin.upload(vox.off.p, offs.data(), offs.size() * sizeof(int), st));
   VoxelBatchView v;
-  v.off = vb[VB_OFF].as<int>(); v.n_clouds = B; v.n_total = n_total; v.inv_leaf = 1.0f / leaf;
-  if (mem == MSFL_MEM_HOST) {
-    HIPCHK(h, vb[VB_PTS].reserve((size_t)n_total * sizeof(float4)));
-    HIPCHK(h, hipMemcpyAsync(vb[VB_PTS].p, pts + o0, (size_t)n_total * sizeof(float4), hipMemcpyHostToDevice, st));
-    v.pts = vb[VB_PTS].as<float4>();
-    v.idx = nullptr; v.count = nullptr;
-    if (idx) {
-      HIPCHK(h, vb[VB_IDX].reserve((size_t)n_total * sizeof(int)));
-      HIPCHK(h, hipMemcpyAsync(vb[VB_IDX].p, idx + o0, (size_t)n_total * sizeof(int), hipMemcpyHostToDevice, st));
-      v.idx = vb[VB_IDX].as<int>();
-    }
-    if (count) {
-      HIPCHK(h, vb[VB_CNT].reserve((size_t)B * sizeof(int)));
-      HIPCHK(h, hipMemcpyAsync(vb[VB_CNT].p, count, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
-      v.count = vb[VB_CNT].as<int>();
-    }
-  } else {
-    v.pts = reinterpret_cast<const float4*>(pts); v.idx = idx; v.count = count;
-  }
+  v.off = vox.off.as<int>(); v.n_clouds = B; v.n_total = n_total; v.inv_leaf = 1.0f / leaf;
+  v.idx = nullptr; v.count = nullptr;
+  s = stage_in(h, vox.pts, pts + skip, (size_t)n_total, mem, st, &v.pts); if (s) return s;
+  if (idx) { s = stage_in(h, vox.idx, idx + skip, (size_t)n_total, mem, st, &v.idx); if (s) return s; }
+  if (count) { s = stage_in(h, vox.cnt, count, (size_t)B, mem, st, &v.count); if (s) return s; }
   h->vox_staged_pts = v.pts;
   // ---- fast form: one workgroup per cloud, runs sorted in LDS (voxel_cloud_lds_kernel) ----
   if (!h->voxel_force_global) {
-    HIPCHK(h, vb[VB_SP].reserve((size_t)n_total * sizeof(float4)));
-    HIPCHK(h, vb[VB_PC].reserve((size_t)n_total * sizeof(float4)));       // per-run sums (a slice has no more runs than points)
-    HIPCHK(h, vb[VB_OCNT].reserve((size_t)(3 * B + 3) * sizeof(int)));
-    int* d_m = vb[VB_OCNT].as<int>();               // [voxels per cloud B | flags B | out_off B+1]
+    HIPCHK(h, vox.set.staging.reserve((size_t)n_total * sizeof(float4)));
+    HIPCHK(h, vox.set.run_sums.reserve((size_t)n_total * sizeof(float4)));       // per-run sums (a slice has no more runs than points)
+    HIPCHK(h, vox.set.tables.reserve((size_t)(3 * B + 3) * sizeof(int)));
+    int* d_m = vox.set.tables.as<int>();               // [voxels per cloud B | flags B | out_off B+1]
     int* d_flags = d_m + B;
     int* d_oo = d_flags + B;
     float4* d_out = reinterpret_cast<float4*>(out);
-    if (mem == MSFL_MEM_HOST) { HIPCHK(h, vb[VB_OUT].reserve((size_t)n_total * sizeof(float4))); d_out = vb[VB_OUT].as<float4>(); }
+    if (mem == MSFL_MEM_HOST) { HIPCHK(h, vox.out.reserve((size_t)n_total * sizeof(float4))); d_out = vox.out.as<float4>(); }
     // small clouds (corner lists: the point COUNT lives on the device, so the choice is made there) are served by the
     // 256-thread instantiation at six workgroups per CU; what it escalates goes to the 1024-thread one
-    hipLaunchKernelGGL((voxel_cloud_lds_kernel<4, 512>), dim3(B), dim3(256), 0, st, v, vb[VB_SP].as<float4>(), vb[VB_PC].as<float4>(), d_m, d_flags, 0);
-    hipLaunchKernelGGL((voxel_cloud_lds_kernel<16, 768>), dim3(B), dim3(1024), 0, st, v, vb[VB_SP].as<float4>(), vb[VB_PC].as<float4>(), d_m, d_flags, 1);
+    hipLaunchKernelGGL((voxel_cloud_lds_kernel<4, 512>), dim3(B), dim3(256), 0, st, v, vox.set.staging.as<float4>(), vox.set.run_sums.as<float4>(), d_m, d_flags, 0);
+    hipLaunchKernelGGL((voxel_cloud_lds_kernel<16, 768>), dim3(B), dim3(1024), 0, st, v, vox.set.staging.as<float4>(), vox.set.run_sums.as<float4>(), d_m, d_flags, 1);
     hipLaunchKernelGGL(voxel_batch_offsets_kernel, dim3(1), dim3(1024), 0, st, (const int*)d_m, B, d_oo);
-    hipLaunchKernelGGL(voxel_batch_compact_kernel, dim3(div_up(n_total, 256)), dim3(256), 0, st, (const float4*)vb[VB_SP].as<float4>(),
+    hipLaunchKernelGGL(voxel_batch_compact_kernel, dim3(div_up(n_total, 256)), dim3(256), 0, st, (const float4*)vox.set.staging.as<float4>(),
                        (const int*)v.off, (const int*)d_oo, B, d_out);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, h->readback.reserve((size_t)(2 * B + 2) * sizeof(int)));
@@ -515,14 +471,14 @@ msfl_status msfl_voxel_downsample_batch(msfl_handle* h, int n_clouds, const msfl
       std::vector<int> list;
       for (int b = 0; b < B; b++) if (rb[b] == 4) list.push_back(b);
       const int n_list = (int)list.size(), grid = std::min(n_list, 512);
-      HIPCHK(h, h->vox_big_scratch.reserve((size_t)grid * kVoxBigScratchBytes));
-      HIPCHK(h, h->vox_big_list.reserve((size_t)n_list * sizeof(int)));
-      HIPCHK(h, h->pin.upload(h->vox_big_list.p, list.data(), (size_t)n_list * sizeof(int), st));
-      hipLaunchKernelGGL(voxel_cloud_big_kernel, dim3(grid), dim3(1024), 0, st, v, vb[VB_SP].as<float4>(), vb[VB_PC].as<float4>(), d_m, d_flags,
-                         (const int*)h->vox_big_list.as<int>(), n_list, reinterpret_cast<unsigned long long*>(h->vox_big_scratch.p),
-                         reinterpret_cast<unsigned short*>(h->vox_big_scratch.as<char>() + (size_t)grid * 65536 * 8));   // all record areas, then all order areas
+      HIPCHK(h, vox.big_scratch.reserve((size_t)grid * kVoxBigScratchBytes));
+      HIPCHK(h, vox.big_list.reserve((size_t)n_list * sizeof(int)));
+      HIPCHK(h, h->pin.upload(vox.big_list.p, list.data(), (size_t)n_list * sizeof(int), st));
+      hipLaunchKernelGGL(voxel_cloud_big_kernel, dim3(grid), dim3(1024), 0, st, v, vox.set.staging.as<float4>(), vox.set.run_sums.as<float4>(), d_m, d_flags,
+                         (const int*)vox.big_list.as<int>(), n_list, reinterpret_cast<unsigned long long*>(vox.big_scratch.p),
+                         reinterpret_cast<unsigned short*>(vox.big_scratch.as<char>() + (size_t)grid * 65536 * 8));   // all record areas, then all order areas
       hipLaunchKernelGGL(voxel_batch_offsets_kernel, dim3(1), dim3(1024), 0, st, (const int*)d_m, B, d_oo);
-      hipLaunchKernelGGL(voxel_batch_compact_kernel, dim3(div_up(n_total, 256)), dim3(256), 0, st, (const float4*)vb[VB_SP].as<float4>(),
+      hipLaunchKernelGGL(voxel_batch_compact_kernel, dim3(div_up(n_total, 256)), dim3(256), 0, st, (const float4*)vox.set.staging.as<float4>(),
                          (const int*)v.off, (const int*)d_oo, B, d_out);
       HIPCHK(h, hipGetLastError());
       HIPCHK(h, hipMemcpyAsync(rb, d_flags, (size_t)(2 * B + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -544,13 +500,13 @@ msfl_status msfl_voxel_downsample_batch(msfl_handle* h, int n_clouds, const msfl
     }
     // a cloud does not fit the LDS form (more than 65 535 points, too many runs, coordinates beyond +-8191 voxels): device-wide form
   }
-  HIPCHK(h, vb[VB_DESC].reserve((size_t)B * sizeof(VoxelCloudDesc)));
-  HIPCHK(h, vb[VB_OCNT].reserve((size_t)(3 * B + 3) * sizeof(int)));
-  int* d_nvalid = vb[VB_OCNT].as<int>();          // [n_valid B | in_off B+1 | out_off B+1 | max_cells 1]
+  HIPCHK(h, vox.desc.reserve((size_t)B * sizeof(VoxelCloudDesc)));
+  HIPCHK(h, vox.set.tables.reserve((size_t)(3 * B + 3) * sizeof(int)));
+  int* d_nvalid = vox.set.tables.as<int>();          // [n_valid B | in_off B+1 | out_off B+1 | max_cells 1]
   int* d_inoff = d_nvalid + B;
   int* d_ooff = d_inoff + (B + 1);
   int* d_maxc = d_ooff + (B + 1);
-  VoxelCloudDesc* d_desc = vb[VB_DESC].as<VoxelCloudDesc>();
+  VoxelCloudDesc* d_desc = vox.desc.as<VoxelCloudDesc>();
   HIPCHK(h, hipMemsetAsync(d_ooff, 0, (size_t)(B + 2) * sizeof(int), st));       // out_off and max_cells
   hipLaunchKernelGGL(voxel_batch_desc_kernel, dim3(B), dim3(kVoxDescThreads), 0, st, v, d_desc, d_nvalid, d_maxc);
   hipLaunchKernelGGL(voxel_batch_offsets_kernel, dim3(1), dim3(1024), 0, st, (const int*)d_nvalid, B, d_inoff);
@@ -566,8 +522,8 @@ msfl_status msfl_voxel_downsample_batch(msfl_handle* h, int n_clouds, const msfl
   const int nv = head[0];
   if (nv > 0) {
     // runs of consecutive same-voxel points, numbered in arrival order
-    HIPCHK(h, vb[VB_FLAG].reserve((size_t)nv * 2 * sizeof(int)));
-    int* flag = vb[VB_FLAG].as<int>(); int* pos = flag + nv;
+    HIPCHK(h, vox.flag.reserve((size_t)nv * 2 * sizeof(int)));
+    int* flag = vox.flag.as<int>(); int* pos = flag + nv;
     const dim3 grid(div_up(nv, 256)), block(256);
     hipLaunchKernelGGL(voxel_batch_head_kernel, grid, block, 0, st, v, (const VoxelCloudDesc*)d_desc, (const int*)d_inoff, nv, flag);
     size_t tb2 = 0;
@@ -577,18 +533,19 @@ msfl_status msfl_voxel_downsample_batch(msfl_handle* h, int n_clouds, const msfl
     HIPCHK(h, hipMemcpyAsync(&head[0], pos + (nv - 1), sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     const int nr = head[0];                                            // runs in the batch (>= 1)
-    HIPCHK(h, vb[VB_K1].reserve((size_t)nr * sizeof(unsigned long long)));
-    HIPCHK(h, vb[VB_K2].reserve((size_t)nr * sizeof(unsigned long long)));
-    HIPCHK(h, vb[VB_V1].reserve((size_t)nr * sizeof(unsigned)));
-    HIPCHK(h, vb[VB_V2].reserve((size_t)nr * sizeof(unsigned)));
-    HIPCHK(h, vb[VB_PC].reserve(((size_t)nr + 1) * sizeof(int)));       // first slot of every run
-    HIPCHK(h, vb[VB_SP].reserve((size_t)nr * 3 * sizeof(int)));         // voxel-head flags, their scan, head positions
-    unsigned long long *k1 = vb[VB_K1].as<unsigned long long>(), *k2 = vb[VB_K2].as<unsigned long long>();
-    unsigned *v1 = vb[VB_V1].as<unsigned>(), *v2 = vb[VB_V2].as<unsigned>();
-    int* run_first = vb[VB_PC].as<int>();
-    int* vflag = vb[VB_SP].as<int>(); int* vpos = vflag + nr; int* head_pos = vpos + nr;
+    HIPCHK(h, vox.keys[0].reserve((size_t)nr * sizeof(unsigned long long)));
+    HIPCHK(h, vox.keys[1].reserve((size_t)nr * sizeof(unsigned long long)));
+    HIPCHK(h, vox.vals[0].reserve((size_t)nr * sizeof(unsigned)));
+    HIPCHK(h, vox.vals[1].reserve((size_t)nr * sizeof(unsigned)));
+    // (this form borrows the LDS form's two large buffers for its int tables: VoxelLdsSet)
+    HIPCHK(h, vox.set.run_sums.reserve(((size_t)nr + 1) * sizeof(int)));       // first slot of every run
+    HIPCHK(h, vox.set.staging.reserve((size_t)nr * 3 * sizeof(int)));         // voxel-head flags, their scan, head positions
+    unsigned long long *k1 = vox.keys[0].as<unsigned long long>(), *k2 = vox.keys[1].as<unsigned long long>();
+    unsigned *v1 = vox.vals[0].as<unsigned>(), *v2 = vox.vals[1].as<unsigned>();
+    int* run_first = vox.set.run_sums.as<int>();
+    int* vflag = vox.set.staging.as<int>(); int* vpos = vflag + nr; int* head_pos = vpos + nr;
     float4* d_out = reinterpret_cast<float4*>(out);
-    if (mem == MSFL_MEM_HOST) { HIPCHK(h, vb[VB_OUT].reserve((size_t)nr * sizeof(float4))); d_out = vb[VB_OUT].as<float4>(); }
+    if (mem == MSFL_MEM_HOST) { HIPCHK(h, vox.out.reserve((size_t)nr * sizeof(float4))); d_out = vox.out.as<float4>(); }
     int cell_bits = 1, cloud_bits = 1;
     while ((1ll << cell_bits) < (long long)head[1]) cell_bits++;
     while ((1ll << cloud_bits) < (long long)B) cloud_bits++;
@@ -651,23 +608,22 @@ msfl_status msfl_voxel_downsample_batch_pair(msfl_handle* h, int n_clouds, const
     const int* idx[2] = {idx_a, idx_b}; const int* cnt[2] = {count_a, count_b};
     const float leaf[2] = {leaf_a, leaf_b};
     msfl_point* out[2] = {out_a, out_b}; int* out_off[2] = {out_off_a, out_off_b};
-    enum { P_SP = 0, P_PC, P_OCNT, P_OFF };
+    VoxelScratch& vox = h->vox;
     std::vector<int> offs(off, off + B + 1);
-    HIPCHK(h, h->vb2[P_OFF].reserve(offs.size() * sizeof(int)));
-    HIPCHK(h, h->pin.upload(h->vb2[P_OFF].p, offs.data(), offs.size() * sizeof(int), st));
+    HIPCHK(h, vox.off_a.reserve(offs.size() * sizeof(int)));
+    HIPCHK(h, h->pin.upload(vox.off_a.p, offs.data(), offs.size() * sizeof(int), st));
     HIPCHK(h, h->readback.reserve((size_t)2 * (2 * B + 2) * sizeof(int)));
     int* rb = h->readback.as<int>();                 // per list: [flags B | out_off B+1]
     for (int k = 0; k < 2; k++) {
       VoxelBatchView v;
-      v.off = h->vb2[P_OFF].as<int>(); v.n_clouds = B; v.n_total = n_total; v.inv_leaf = 1.0f / leaf[k];
+      v.off = vox.off_a.as<int>(); v.n_clouds = B; v.n_total = n_total; v.inv_leaf = 1.0f / leaf[k];
       v.pts = reinterpret_cast<const float4*>(pts); v.idx = idx[k]; v.count = cnt[k];
-      DevBuf& sp = k == 0 ? h->vb2[P_SP] : h->vb[13];     // list b uses the single-list scratch (VB_SP / VB_PC / VB_OCNT)
-      DevBuf& pc = k == 0 ? h->vb2[P_PC] : h->vb[12];
-      DevBuf& oc = k == 0 ? h->vb2[P_OCNT] : h->vb[11];
+      VoxelLdsSet& set = k == 0 ? vox.set_a : vox.set;    // list b works where the single-list call does
+      DevBuf &sp = set.staging, &pc = set.run_sums;
       HIPCHK(h, sp.reserve((size_t)n_total * sizeof(float4)));
       HIPCHK(h, pc.reserve((size_t)n_total * sizeof(float4)));
-      HIPCHK(h, oc.reserve((size_t)(3 * B + 3) * sizeof(int)));
-      int* d_m = oc.as<int>(); int* d_flags = d_m + B; int* d_oo = d_flags + B;
+      HIPCHK(h, set.tables.reserve((size_t)(3 * B + 3) * sizeof(int)));
+      int* d_m = set.tables.as<int>(); int* d_flags = d_m + B; int* d_oo = d_flags + B;
       hipLaunchKernelGGL((voxel_cloud_lds_kernel<4, 512>), dim3(B), dim3(256), 0, st, v, sp.as<float4>(), pc.as<float4>(), d_m, d_flags, 0);
       hipLaunchKernelGGL((voxel_cloud_lds_kernel<16, 768>), dim3(B), dim3(1024), 0, st, v, sp.as<float4>(), pc.as<float4>(), d_m, d_flags, 1);
       hipLaunchKernelGGL(voxel_batch_offsets_kernel, dim3(1), dim3(1024), 0, st, (const int*)d_m, B, d_oo);
