@@ -1,0 +1,124 @@
+"""Closing a loop end to end: places -> score -> match -> pose graph -> corrected trajectory.
+
+    python examples/close_loop.py [--scans 151] [--gap 50] [--every 1] [--max-distance 0.1] [--min-fitness 0.99]
+
+The figure of eight of examples/loop_candidates.py.  Every scan goes through the device-resident SLAM step (keep_clouds) and into a
+capi.Places.  The odometry the graph starts from is made to drift: the session's consecutive relative poses with a yaw bias and
+noise on every step, integrated from the first pose.  Every --every-th scan is queried against the entries more than --gap scans
+older; the candidate becomes a pose guess (the matched scan's map pose turned by the shift's yaw), msfl_score_poses grades it,
+msfl_match_scan2map refines it, and a candidate with descriptor distance <= --max-distance whose refined pose has fitness >=
+--min-fitness and lies within 1.5 m of the guess becomes a long edge whose measurement is the matched scan's map pose^-1 times
+the refined pose (the room repeats itself, so looser rules let wrong closures in; on this path only its end closes).  capi.PoseGraph optimises the chain (first node fixed) and the absolute
+trajectory error against the truth is printed before and after.  A demonstration; the acceptance rule here is the example's, not
+the library's."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+from msf_loam_amd import capi, synth
+
+
+def figure_of_eight(n):
+    poses = []
+    for k in range(n):
+        t = np.pi * k / (n - 1)
+        x, y = 9.0 * np.sin(t), 5.0 * np.sin(2.0 * t)
+        yaw = np.arctan2(10.0 * np.cos(2.0 * t), 9.0 * np.cos(t))
+        poses.append(np.r_[x, y, 1.8 + 0.02 * np.sin(3.0 * t), synth.quat_from_euler(0.01 * np.sin(2.0 * t), 0.01 * np.cos(t), yaw)])
+    return np.array(poses)
+
+
+def turned(pose, yaw):
+    """pose * Rz(yaw): the same position, the heading turned about the scan's own z axis."""
+    q = synth.quat_mul(pose[3:], np.array([0.0, 0.0, np.sin(yaw / 2.0), np.cos(yaw / 2.0)]))
+    return np.r_[pose[:3], q / np.linalg.norm(q)]
+
+
+def drifting(pose_map, rng, yaw_bias=0.004, sigma_t=0.01, sigma_r=0.002):
+    """Relative poses of the session with a yaw bias and noise on every step, and the trajectory they integrate to."""
+    rel, out = [], [np.array(pose_map[0])]
+    for a, b in zip(pose_map[:-1], pose_map[1:]):
+        z = capi.relative_pose(a, b)
+        z[:3] += rng.normal(0.0, sigma_t, 3)
+        w = np.r_[rng.normal(0.0, sigma_r, 2), yaw_bias + rng.normal(0.0, sigma_r)] * 0.5
+        q = synth.quat_mul(z[3:], np.r_[w, 1.0])
+        z[3:] = q / np.linalg.norm(q)
+        rel.append(z)
+        p, qa = out[-1][:3], out[-1][3:]
+        qn = synth.quat_mul(qa, z[3:])
+        out.append(np.r_[p + synth.quat_to_matrix(qa) @ z[:3], qn / np.linalg.norm(qn)])
+    return np.array(rel), np.array(out)
+
+
+def ate(poses, truth):
+    return float(np.sqrt(np.mean(np.sum((np.asarray(poses)[:, :3] - truth[:, :3]) ** 2, axis=1))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scans", type=int, default=151)
+    ap.add_argument("--gap", type=int, default=50, help="a scan is only compared with entries more than this many scans older")
+    ap.add_argument("--every", type=int, default=1, help="query every n-th scan")
+    ap.add_argument("--max-distance", type=float, default=0.1, help="descriptor distance up to which a candidate is verified")
+    ap.add_argument("--max-dist", type=float, default=1.0)
+    ap.add_argument("--min-fitness", type=float, default=0.99)
+    args = ap.parse_args()
+
+    world = synth.World()
+    truth = figure_of_eight(args.scans)
+    scans = [synth.make_scan(world, truth[k], synth.SEED + 7000 + k) for k in range(args.scans)]
+    slam = capi.Slam(0, max_scan_points=max(len(p) for p, _ in scans), max_rings=16, pose_odom2map=truth[0], keep_clouds=1)
+    places = capi.Places(0, capacity=max(args.scans, 1))
+    pose_map, candidates = [], []
+    for k, (pts, ring) in enumerate(scans):
+        r = slam.add_scan(pts, ring)
+        pose_map.append(np.array(r.pose_map[:]))
+        cl = slam.clouds(k)
+        assert places.add(cl["full_scan"]) == k
+        if k > args.gap and k % args.every == 0:
+            m = places.query_entries(k, max_index=k - args.gap, k=1)[0, 0]
+            if m["index"] >= 0 and m["distance"] <= args.max_distance:
+                candidates.append((k, m.copy(), cl["full_scan"][cl["less_sharp"]], cl["full_scan"][cl["less_flat"]]))
+
+    rel, drifted = drifting(pose_map, np.random.default_rng(synth.SEED))
+    grid_c, grid_s = slam.grids()
+    h = capi.Handle(0)
+    h.set_map(grid_c.dump(), grid_s.dump())
+    closures = []
+    for k, m, sharp, flat in candidates:
+        j, yaw = int(m["index"]), float(capi.place_yaw(m["shift"], places.n_sector))
+        corner, surf = h.voxel_downsample(sharp, 0.2), h.voxel_downsample(flat, 0.4)
+        guess = turned(pose_map[j], yaw)
+        status, refined, _ = h.match_scan2map(corner, surf, guess)
+        fit = capi.fitness(h.score_poses(corner, surf, [refined], args.max_dist), len(corner), len(surf))[0]
+        ok = status == 0 and fit >= args.min_fitness and np.linalg.norm(np.asarray(refined)[:3] - guess[:3]) <= 1.5
+        z = capi.relative_pose(pose_map[j], np.asarray(refined))
+        dt, dr = synth.pose_error(z, capi.relative_pose(truth[j], truth[k]))
+        print("scan %3d ~ scan %3d: distance %.3f, yaw %+6.1f deg, refined fitness %.3f -> %s (measurement off the truth by %.3f m, %.2f deg)"
+              % (k, j, m["distance"], np.degrees(yaw), fit, "edge" if ok else "dropped", dt, np.degrees(dr)))
+        if ok:
+            closures.append((j, k, z))
+
+    n = args.scans
+    g = capi.PoseGraph(0, max_nodes=n, max_edges=n + len(closures), max_fixes=1)
+    g.add_nodes(drifted)
+    g.set_fixed(0)
+    g.add_edges(g.edges(np.arange(n - 1), np.arange(1, n), rel, sr=0.01, st=0.1))
+    if closures:
+        g.add_edges(g.edges([c[0] for c in closures], [c[1] for c in closures], np.array([c[2] for c in closures]), sr=0.005, st=0.05))
+    s = g.optimize()
+    print("%d closure edges (%d of them long: both ends free, more than one apart); %s after %d iterations (%d CG iterations, %d unconverged); cost %.4g -> %.4g"
+          % (len(closures), s.n_long_edges, capi.GRAPH_TERMINATION[s.termination], s.iterations, s.cg_iterations, s.cg_unconverged, s.initial_cost, s.final_cost))
+    print("ATE against the truth: session %.3f m, drifting odometry %.3f m, after the optimisation %.3f m"
+          % (ate(pose_map, truth), ate(drifted, truth), ate(g.poses(), truth)))
+    g.close()
+    h.close()
+    places.close()
+    slam.close()
+
+
+if __name__ == "__main__":
+    main()

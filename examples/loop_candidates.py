@@ -7,7 +7,7 @@ degrees off its first heading.  Every scan goes through the device-resident SLAM
 capi.Places, and the scan is queried against the entries more than --gap scans older.  The best candidate of the run becomes a
 pose guess: the stored map pose of the matched scan, turned by the yaw the column shift stands for.  msfl_score_poses grades the
 guess against the map the session built, msfl_match_scan2map refines it, and the refined pose is graded again.  A demonstration of
-how the primitives compose; no pose graph and no acceptance policy lives in the library."""
+how the primitives compose; examples/close_loop.py goes on from here to the pose graph.  No acceptance policy lives in the library."""
 import argparse
 import os
 import sys

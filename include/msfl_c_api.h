@@ -992,6 +992,96 @@ msfl_status msfl_places_query(msfl_places* p, const msfl_point* pts, const int* 
 msfl_status msfl_places_query_entries(msfl_places* p, const int* entries /* HOST */, int n_queries, const int* max_index,
                                       int n_prefilter, int k, msfl_place_match* out, msfl_mem mem);
 
+/* ------------------------------------------------------------------------------------------------------------------
+   Pose-graph optimisation: what GpsFusion::Optimize (src/slam/gps_fusion/gps_fusion.cc:27-97) does with Ceres, and
+   what a loop closer does with an accepted closure (loop_closure/pose_graph_factor.h), on the device.
+   docs/kernels/graph.md holds the full definition; in short, all f64:
+     - nodes are poses [t(3), qx qy qz qw];
+     - a relative-pose edge {i, j, z, sr, st} (RelativePoseFactor, gps_factor.h:36-48): T_ij = T_i^-1 T_j, E = T_ij^-1 Z,
+       r = [E.t / st ; vec(E.q) / sr], 6 rows; the quaternion is used as it comes out, without sign normalisation;
+     - a position fix {i, j, t, p, st} (GpsFactor, gps_factor.h:12-17): r = ((1 - t) t_i + t t_j - p) / st, 3 rows;
+     - HuberLoss(huber_delta) on each block's squared norm through Ceres' corrector (rho'' <= 0 branch); 0 = no loss;
+     - per free node t + dt and EigenQuaternionParameterization, q <- dq (x) q, dq = [sin|d| d/|d| ; cos|d|] (identity at
+       d = 0); nodes marked fixed are no variables and enter neither the tangent vector nor x_norm;
+     - the solve is Ceres 1.14's TrustRegionMinimizer with LEVENBERG_MARQUARDT over the stacked tangent of all free nodes:
+       Jacobi scaling fixed after iteration 0, LM diagonal clipped to [min_lm_diagonal, max_lm_diagonal], the step the
+       solution of (Js^T Js + D^2) s = -Js^T r;
+     - that system is solved by conjugate gradients to cg_tolerance (relative, in the preconditioner norm), preconditioned
+       by the exact solve of its block-tridiagonal part (block pairs |i - j| <= 1 in the numbering of the free nodes); the
+       remaining blocks, those of the LONG factors (both ends free, more than one apart), enter through the mat-vec.
+       Without a long factor the preconditioner's solve is the step and exactly one CG iteration runs per LM iteration.
+       With long factors at most max_cg_iterations run (0: 16 n_long + 8); a solve that ends there hands over its iterate
+       and counts in cg_unconverged.
+   Every sum has one stated order (factors per node in the order edges were added, then fixes; totals over fixed-size
+   partials in index order) and there are no floating-point atomics: the same records in the same order give the same
+   bits, however the add_* calls were chunked.  The object owns a stream and its memory, like msfl_places. */
+typedef struct msfl_graph_config {
+  int max_nodes, max_edges, max_fixes;      /* capacities, fixed at creation (defaults 16384, 32768, 16384) */
+  int max_num_iterations;                   /* 10 (gps_fusion.cc:45) */
+  int max_consecutive_invalid_steps;        /* 5 */
+  int jacobi_scaling;                       /* 1 */
+  int max_cg_iterations;                    /* 0 = 16 n_long + 8 */
+  int reserved;
+  double huber_delta;                       /* 1.0 (gps_fusion.cc:48); 0 = no loss */
+  double initial_trust_region_radius, max_trust_region_radius, min_trust_region_radius;   /* 1e4, 1e16, 1e-32 */
+  double min_relative_decrease;             /* 1e-3 */
+  double min_lm_diagonal, max_lm_diagonal;  /* 1e-6, 1e32 */
+  double function_tolerance, gradient_tolerance, parameter_tolerance;                      /* 1e-6, 1e-10, 1e-8 */
+  double cg_tolerance;                      /* 1e-12 */
+} msfl_graph_config;
+
+typedef struct msfl_graph_edge { int i, j; double z[7]; double sr, st; } msfl_graph_edge;          /* z = the measured T_i^-1 T_j */
+typedef struct msfl_graph_fix { int i, j; double t; double p[3]; double st; } msfl_graph_fix;
+
+enum { MSFL_GRAPH_EMPTY = 0, MSFL_GRAPH_GRADIENT = 1, MSFL_GRAPH_MAX_ITERATIONS = 2, MSFL_GRAPH_MIN_RADIUS = 3,
+       MSFL_GRAPH_INVALID_STEPS = 4, MSFL_GRAPH_PARAMETER = 5, MSFL_GRAPH_FUNCTION = 6 };
+
+typedef struct msfl_graph_summary {
+  int status;                /* msfl_status of the solve */
+  int termination;           /* MSFL_GRAPH_*: why the minimizer stopped */
+  int iterations;            /* LM iterations (steps tried) */
+  int successful_steps;
+  double initial_cost, final_cost;
+  int cg_iterations;         /* in total over all LM iterations */
+  int cg_unconverged;        /* step solves that ended at max_cg_iterations */
+  int n_long_edges;          /* long factors (edges or fixes) */
+  int n_free;                /* free nodes */
+} msfl_graph_summary;
+
+typedef struct msfl_graph_s msfl_graph;
+/* MSFL_BAD_ARG for a config with a negative or non-finite value or max_nodes < 1.  NULL config = defaults. */
+void        msfl_graph_default_config(msfl_graph_config* c);
+msfl_status msfl_graph_create(const msfl_graph_config* c, int device, msfl_graph** out);
+void        msfl_graph_destroy(msfl_graph* g);
+msfl_status msfl_graph_set_stream(msfl_graph* g, void* hip_stream);   /* as msfl_set_stream */
+msfl_status msfl_graph_synchronize(msfl_graph* g);
+const char* msfl_graph_last_error(const msfl_graph* g);
+msfl_status msfl_graph_clear(msfl_graph* g);                          /* no nodes, edges or fixes; capacities stay */
+int         msfl_graph_num_nodes(const msfl_graph* g);
+/* Building.  Refusals leave the graph as it was and set last_error:
+     - MSFL_BAD_ARG: a node index out of range; i == j; a non-finite value; sr, st <= 0; t outside [0, 1]; a zero quaternion
+       (in a pose or in z);
+     - MSFL_CAPACITY: the call would exceed max_nodes / max_edges / max_fixes; the whole call is refused, not part of it.
+   Edge and fix records are HOST arrays (the host keeps the structure: adjacency lists and launch sizes).  Poses may be
+   device memory (MSFL_MEM_DEVICE: double[7] per node; the call checks them on the host, so it waits for the stream);
+   msfl_slam results can be handed over as they are. */
+msfl_status msfl_graph_add_nodes(msfl_graph* g, const double* poses, int n, msfl_mem mem, int* first_index);
+msfl_status msfl_graph_add_edges(msfl_graph* g, const msfl_graph_edge* edges /* HOST */, int n);
+msfl_status msfl_graph_add_fixes(msfl_graph* g, const msfl_graph_fix* fixes /* HOST */, int n);
+msfl_status msfl_graph_set_fixed(msfl_graph* g, int node, int flag);  /* SetParameterBlockConstant / ...Variable */
+msfl_status msfl_graph_set_poses(msfl_graph* g, int first, int n, const double* poses, msfl_mem mem);
+msfl_status msfl_graph_get_poses(msfl_graph* g, int first, int n, double* out, msfl_mem mem);
+/* cost = 1/2 sum rho(|r|^2) at the current poses; changes nothing */
+msfl_status msfl_graph_cost(msfl_graph* g, double* cost);
+/* Synchronous.  Reads one small record from the device per LM iteration, none per CG iteration or reduction level.  The
+   poses afterwards are the last accepted iterate.  Without a free node or without a factor: termination
+   MSFL_GRAPH_EMPTY, poses untouched. */
+msfl_status msfl_graph_optimize(msfl_graph* g, msfl_graph_summary* summary);
+/* the last optimize, per LM iteration: accepted[k] = 1 accepted, 0 rejected (or the tolerance test that ended the solve), -1 an
+   invalid step; cost[k] = the candidate's cost.  *n_out = iterations recorded; MSFL_CAPACITY if that exceeds `capacity`
+   (the first `capacity` are written).  Either array may be NULL. */
+msfl_status msfl_graph_get_trace(msfl_graph* g, int* accepted, double* cost, int capacity, int* n_out);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

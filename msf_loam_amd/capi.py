@@ -38,6 +38,10 @@ EXPORTED = [
     "msfl_places_default_config", "msfl_places_create", "msfl_places_destroy", "msfl_places_set_stream", "msfl_places_synchronize",
     "msfl_places_size", "msfl_places_last_error", "msfl_places_add", "msfl_places_add_descriptors", "msfl_places_get",
     "msfl_places_query", "msfl_places_query_entries",
+    "msfl_graph_default_config", "msfl_graph_create", "msfl_graph_destroy", "msfl_graph_set_stream", "msfl_graph_synchronize",
+    "msfl_graph_last_error", "msfl_graph_clear", "msfl_graph_num_nodes", "msfl_graph_add_nodes", "msfl_graph_add_edges",
+    "msfl_graph_add_fixes", "msfl_graph_set_fixed", "msfl_graph_set_poses", "msfl_graph_get_poses", "msfl_graph_cost",
+    "msfl_graph_optimize", "msfl_graph_get_trace",
 ]
 
 
@@ -1327,3 +1331,174 @@ class Places:
         return self._check(self.lib.msfl_places_query_entries(self.p, _vp(e), C.c_int(len(e)), _vp(mi), C.c_int(int(n_prefilter)),
                                                               C.c_int(int(k)), _vp(out), C.c_int(MEM_DEVICE)),
                            "msfl_places_query_entries(device)", allow)
+
+
+class GraphConfig(C.Structure):
+    """msfl_graph_config: capacities and the options of the trust-region solve and of its CG step solver."""
+    _fields_ = [("max_nodes", C.c_int), ("max_edges", C.c_int), ("max_fixes", C.c_int), ("max_num_iterations", C.c_int),
+                ("max_consecutive_invalid_steps", C.c_int), ("jacobi_scaling", C.c_int), ("max_cg_iterations", C.c_int), ("reserved", C.c_int),
+                ("huber_delta", C.c_double), ("initial_trust_region_radius", C.c_double), ("max_trust_region_radius", C.c_double),
+                ("min_trust_region_radius", C.c_double), ("min_relative_decrease", C.c_double), ("min_lm_diagonal", C.c_double),
+                ("max_lm_diagonal", C.c_double), ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+                ("parameter_tolerance", C.c_double), ("cg_tolerance", C.c_double)]
+
+
+class GraphSummary(C.Structure):
+    """msfl_graph_summary: how the last msfl_graph_optimize ended."""
+    _fields_ = [("status", C.c_int), ("termination", C.c_int), ("iterations", C.c_int), ("successful_steps", C.c_int),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("cg_iterations", C.c_int), ("cg_unconverged", C.c_int),
+                ("n_long_edges", C.c_int), ("n_free", C.c_int)]
+
+
+# msfl_graph_edge / msfl_graph_fix as numpy structured dtypes (PoseGraph.add_edges, PoseGraph.add_fixes)
+GRAPH_EDGE_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("z", np.float64, (7,)), ("sr", np.float64), ("st", np.float64)])
+GRAPH_FIX_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("t", np.float64), ("p", np.float64, (3,)), ("st", np.float64)])
+assert GRAPH_EDGE_DTYPE.itemsize == 80 and GRAPH_FIX_DTYPE.itemsize == 48 and C.sizeof(GraphSummary) == 48
+
+GRAPH_TERMINATION = ("empty", "gradient", "max_iterations", "min_radius", "invalid_steps", "parameter", "function")
+
+
+def relative_pose(Ti, Tj):
+    """T_i^-1 T_j of two poses [t, qx qy qz qw] (unit quaternions): the measurement z of a graph edge (i, j)."""
+    Ti, Tj = np.asarray(Ti, np.float64), np.asarray(Tj, np.float64)
+
+    def rot(q, v):
+        u, w = q[:3], q[3]
+        uv = np.cross(u, v)
+        return v + 2.0 * (w * uv + np.cross(u, uv))
+
+    qi = np.array([-Ti[3], -Ti[4], -Ti[5], Ti[6]])
+    qj = Tj[3:]
+    q = np.concatenate([qi[3] * qj[:3] + qj[3] * qi[:3] + np.cross(qi[:3], qj[:3]), [qi[3] * qj[3] - qi[:3] @ qj[:3]]])
+    return np.concatenate([rot(qi, Tj[:3] - Ti[:3]), q])
+
+
+class PoseGraph:
+    """Owns one msfl_graph: poses on the device, relative-pose edges and position fixes, and the trust-region solve over them
+    (msfl_graph_*), independent of any Handle.  Keyword arguments are the fields of msfl_graph_config."""
+
+    def __init__(self, device=0, **cfg):
+        self.lib = load()
+        self.lib.msfl_graph_last_error.restype = C.c_char_p
+        self.lib.msfl_graph_last_error.argtypes = [C.c_void_p]
+        self.lib.msfl_graph_num_nodes.argtypes = [C.c_void_p]
+        self.config = GraphConfig()
+        self.lib.msfl_graph_default_config(C.byref(self.config))
+        for k, v in cfg.items():
+            if k not in dict(GraphConfig._fields_):
+                raise TypeError("unknown msfl_graph_config field %r" % (k,))
+            setattr(self.config, k, v)
+        self.p = C.c_void_p()
+        s = self.lib.msfl_graph_create(C.byref(self.config), C.c_int(device), C.byref(self.p))
+        if s != OK:
+            raise MsflError(s, "msfl_graph_create", "(a config outside its limits, or no GPU: there is no CPU fallback)")
+
+    def close(self):
+        if self.p:
+            self.lib.msfl_graph_destroy(self.p)
+            self.p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, s, what, allow=()):
+        if s != OK and s not in allow:
+            raise MsflError(s, what, (self.lib.msfl_graph_last_error(self.p) or b"").decode())
+        return s
+
+    def last_error(self):
+        return (self.lib.msfl_graph_last_error(self.p) or b"").decode()
+
+    def set_stream(self, stream_ptr):
+        self._check(self.lib.msfl_graph_set_stream(self.p, C.c_void_p(stream_ptr)), "msfl_graph_set_stream")
+
+    def synchronize(self):
+        self._check(self.lib.msfl_graph_synchronize(self.p), "msfl_graph_synchronize")
+
+    def clear(self):
+        self._check(self.lib.msfl_graph_clear(self.p), "msfl_graph_clear")
+
+    def num_nodes(self):
+        return int(self.lib.msfl_graph_num_nodes(self.p))
+
+    def __len__(self):
+        return self.num_nodes()
+
+    def add_nodes(self, poses, allow=()):
+        """Appends poses: an (n, 7) array, or a CUDA tensor of n x 7 float64 (read in place).  Returns the index of the first new node
+        (or the refusing status when it is in `allow`)."""
+        first = C.c_int(-1)
+        if _on_device(poses):
+            n, ptr, mem = int(poses.numel() // 7), C.c_void_p(poses.data_ptr()), MEM_DEVICE
+        else:
+            poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
+            n, ptr, mem = len(poses), _vp(poses), MEM_HOST
+        s = self._check(self.lib.msfl_graph_add_nodes(self.p, ptr, C.c_int(n), C.c_int(mem), C.byref(first)), "msfl_graph_add_nodes", allow)
+        return first.value if s == OK else s
+
+    @staticmethod
+    def edges(i, j, z, sr=0.01, st=0.1):
+        """Records of GRAPH_EDGE_DTYPE from index arrays, (n, 7) measurements and scalar or per-edge sr / st."""
+        i = np.atleast_1d(np.asarray(i, np.int32))
+        rec = np.zeros(len(i), GRAPH_EDGE_DTYPE)
+        rec["i"], rec["j"], rec["z"], rec["sr"], rec["st"] = i, j, np.asarray(z, np.float64).reshape(len(i), 7), sr, st
+        return rec
+
+    @staticmethod
+    def fixes(i, j, t, p, st=0.01):
+        """Records of GRAPH_FIX_DTYPE."""
+        i = np.atleast_1d(np.asarray(i, np.int32))
+        rec = np.zeros(len(i), GRAPH_FIX_DTYPE)
+        rec["i"], rec["j"], rec["t"], rec["p"], rec["st"] = i, j, t, np.asarray(p, np.float64).reshape(len(i), 3), st
+        return rec
+
+    def add_edges(self, rec, allow=()):
+        rec = np.ascontiguousarray(rec, GRAPH_EDGE_DTYPE)
+        return self._check(self.lib.msfl_graph_add_edges(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_edges", allow)
+
+    def add_fixes(self, rec, allow=()):
+        rec = np.ascontiguousarray(rec, GRAPH_FIX_DTYPE)
+        return self._check(self.lib.msfl_graph_add_fixes(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_fixes", allow)
+
+    def set_fixed(self, node, flag=True, allow=()):
+        return self._check(self.lib.msfl_graph_set_fixed(self.p, C.c_int(int(node)), C.c_int(1 if flag else 0)), "msfl_graph_set_fixed", allow)
+
+    def set_poses(self, poses, first=0, allow=()):
+        if _on_device(poses):
+            n, ptr, mem = int(poses.numel() // 7), C.c_void_p(poses.data_ptr()), MEM_DEVICE
+        else:
+            poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
+            n, ptr, mem = len(poses), _vp(poses), MEM_HOST
+        return self._check(self.lib.msfl_graph_set_poses(self.p, C.c_int(int(first)), C.c_int(n), ptr, C.c_int(mem)), "msfl_graph_set_poses", allow)
+
+    def poses(self, first=0, n=None, out=None):
+        """(n, 7) poses from node `first` on; `out`: a CUDA float64 tensor to fill on the device instead (asynchronous)."""
+        n = self.num_nodes() - int(first) if n is None else int(n)
+        if out is not None:
+            self._check(self.lib.msfl_graph_get_poses(self.p, C.c_int(int(first)), C.c_int(n), C.c_void_p(out.data_ptr()), C.c_int(MEM_DEVICE)),
+                        "msfl_graph_get_poses(device)")
+            return out
+        a = np.zeros((n, 7), np.float64)
+        self._check(self.lib.msfl_graph_get_poses(self.p, C.c_int(int(first)), C.c_int(n), _vp(a), C.c_int(MEM_HOST)), "msfl_graph_get_poses")
+        return a
+
+    def cost(self):
+        c = C.c_double(0.0)
+        self._check(self.lib.msfl_graph_cost(self.p, C.byref(c)), "msfl_graph_cost")
+        return c.value
+
+    def optimize(self):
+        """Runs the solve; returns the GraphSummary (termination as a code: GRAPH_TERMINATION names it)."""
+        s = GraphSummary()
+        self._check(self.lib.msfl_graph_optimize(self.p, C.byref(s)), "msfl_graph_optimize")
+        return s
+
+    def trace(self):
+        """(accept list, candidate costs) of the last optimize, one entry per LM iteration."""
+        cap = max(1, int(self.config.max_num_iterations))
+        acc, cost, n = np.zeros(cap, np.int32), np.zeros(cap, np.float64), C.c_int(0)
+        self._check(self.lib.msfl_graph_get_trace(self.p, _vp(acc), _vp(cost), C.c_int(cap), C.byref(n)), "msfl_graph_get_trace")
+        return acc[:n.value].copy(), cost[:n.value].copy()

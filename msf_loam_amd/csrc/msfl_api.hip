@@ -1298,3 +1298,4 @@ msfl_status solve_given_records(msfl_handle* h, const BatchView& bv, const RegSi
 }
 
 }  // namespace
+#include "msfl_api_graph.inc"

@@ -1,0 +1,417 @@
+// Pose-graph optimisation — C-ABI entry points msfl_graph_*: poses on the device, the graph's structure on the host, Ceres' trust-region
+// loop enqueued as a fixed launch pattern per LM iteration.  Included at the end of msfl_api.hip (shares DevBuf, PinRing, PinBuf and
+// the helper macros); kernels: msfl_graph.cuh.  The object owns its stream and all its memory, like msfl_places.
+
+#include "msfl_graph.cuh"   // includes msfl_graph_host.h: GraphStructure, graph_build_structure, graph_levels
+
+static_assert(sizeof(msfl_graph_edge) == 80 && sizeof(msfl_graph_fix) == 48 && sizeof(msfl_graph_summary) == 48, "graph record layout");
+static_assert(sizeof(GraphState) % 8 == 0, "the trace follows the state record");
+
+struct msfl_graph_s {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  msfl_graph_config cfg{};
+  std::string last_error;
+  int n_nodes = 0;
+  std::vector<unsigned char> fixed;
+  std::vector<msfl_graph_edge> edges;
+  std::vector<msfl_graph_fix> fixes;
+  bool dirty = true;             // the structure changed since the device copy was built
+  GraphStructure gs;
+  GraphLevels lv{};
+  GraphDev dev{};
+  std::vector<int> tr_accepted;  // the last optimize's trace
+  std::vector<double> tr_cost;
+  DevBuf x, cand;                // double[max_nodes x 7]
+  DevBuf ints, data, work;       // structure, factor data, everything the solve works in
+  DevBuf state;                  // GraphState, double[max_iter] candidate costs, one double (msfl_graph_cost), int[max_iter] accept list
+  PinRing pin;
+  PinBuf readback;
+};
+
+namespace {
+
+msfl_status fail(msfl_graph* g, msfl_status s, const std::string& msg) {
+  if (g) g->last_error = msg;
+  return s;
+}
+
+msfl_status enter(msfl_graph* g) {
+  if (!g) return MSFL_BAD_ARG;
+  HIPCHK(g, hipSetDevice(g->device));
+  return MSFL_OK;
+}
+
+bool graph_config_ok(const msfl_graph_config& c) {
+  const double d[] = {c.huber_delta, c.initial_trust_region_radius, c.max_trust_region_radius, c.min_trust_region_radius, c.min_relative_decrease,
+                      c.min_lm_diagonal, c.max_lm_diagonal, c.function_tolerance, c.gradient_tolerance, c.parameter_tolerance, c.cg_tolerance};
+  for (double v : d)
+    if (!std::isfinite(v) || v < 0.0) return false;
+  return c.max_nodes >= 1 && c.max_edges >= 0 && c.max_fixes >= 0 && c.max_num_iterations >= 0 && c.max_num_iterations <= 10000 &&
+         c.max_consecutive_invalid_steps >= 1 && c.max_cg_iterations >= 0 && c.initial_trust_region_radius > 0.0 &&
+         c.min_lm_diagonal <= c.max_lm_diagonal;
+}
+
+GraphOpt graph_opt(const msfl_graph_config& c) {
+  GraphOpt o{};
+  o.max_iter = c.max_num_iterations; o.max_invalid = c.max_consecutive_invalid_steps; o.jacobi = c.jacobi_scaling;
+  o.huber = c.huber_delta; o.radius0 = c.initial_trust_region_radius; o.radius_max = c.max_trust_region_radius;
+  o.radius_min = c.min_trust_region_radius; o.min_rel = c.min_relative_decrease; o.lm_min = c.min_lm_diagonal; o.lm_max = c.max_lm_diagonal;
+  o.ftol = c.function_tolerance; o.gtol = c.gradient_tolerance; o.ptol = c.parameter_tolerance; o.cg_tol = c.cg_tolerance;
+  return o;
+}
+
+bool graph_pose_ok(const double* p) {
+  for (int c = 0; c < 7; c++)
+    if (!std::isfinite(p[c])) return false;
+  return p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6] > 0.0;
+}
+
+size_t graph_state_bytes(const msfl_graph* g) {
+  const size_t n = (size_t)std::max(1, g->cfg.max_num_iterations);   // state | double[n] candidate costs | one double (msfl_graph_cost) | int[n] accept list
+  return sizeof(GraphState) + (n + 1) * sizeof(double) + ((n + 1) & ~size_t(1)) * sizeof(int);
+}
+
+// Builds the device copy of the structure and carves the work area; nothing to do while the structure is unchanged.
+msfl_status graph_prepare(msfl_graph* g) {
+  if (!g->dirty) return MSFL_OK;
+  hipStream_t st = g->stream;
+  const int ne = (int)g->edges.size(), nx = (int)g->fixes.size(), nf = ne + nx;
+  std::vector<int> ij(2 * (size_t)nf);
+  std::vector<double> data(9 * (size_t)std::max(1, nf));
+  for (int k = 0; k < ne; k++) {
+    const msfl_graph_edge& e = g->edges[k];
+    ij[2 * k] = e.i; ij[2 * k + 1] = e.j;
+    double* d = data.data() + 9 * (size_t)k;
+    for (int c = 0; c < 7; c++) d[c] = e.z[c];
+    d[7] = e.sr; d[8] = e.st;
+  }
+  for (int k = 0; k < nx; k++) {
+    const msfl_graph_fix& f = g->fixes[k];
+    ij[2 * (ne + k)] = f.i; ij[2 * (ne + k) + 1] = f.j;
+    double* d = data.data() + 9 * (size_t)(ne + k);
+    d[0] = f.t; d[1] = f.p[0]; d[2] = f.p[1]; d[3] = f.p[2]; d[4] = f.st; d[5] = d[6] = d[7] = d[8] = 0.0;
+  }
+  GraphStructure& s = g->gs;
+  graph_build_structure(g->n_nodes, g->fixed.data(), ij, &s);
+  const int F = s.n_free, N = g->n_nodes;
+  g->lv = graph_levels(std::max(1, F));
+  // ints: free_of | node_of | adj_off | adj | ladj_off | ladj | fac_ij
+  std::vector<int> ints;
+  size_t at[7]; int q = 0;
+  for (const std::vector<int>* v : {&s.free_of, &s.node_of, &s.adj_off, &s.adj, &s.ladj_off, &s.ladj, &s.fac_ij}) {
+    at[q++] = ints.size();
+    ints.insert(ints.end(), v->begin(), v->end());
+  }
+  ints.push_back(0);
+  HIPCHK(g, g->ints.reserve(ints.size() * sizeof(int)));
+  HIPCHK(g, g->pin.upload(g->ints.p, ints.data(), ints.size() * sizeof(int), st));
+  HIPCHK(g, g->data.reserve(data.size() * sizeof(double)));
+  HIPCHK(g, g->pin.upload(g->data.p, data.data(), data.size() * sizeof(double), st));
+  const GraphLevels& v = g->lv;
+  const size_t blocks = (size_t)v.off[v.count - 1] + 1, inv = (size_t)v.ioff[v.count - 1] + 1, Fz = (size_t)std::max(1, F), nfz = (size_t)std::max(1, nf);
+  const size_t n_part = (Fz + kGraphVec - 1) / kGraphVec;
+  const size_t want = nfz * (kGraphJ + 2) + Fz * (36 + 36 + 6 + 6 + 3) + blocks * (36 + 36 + 6 + 6) + inv * 36 + Fz * 6 * 7 + 2 * n_part;
+  HIPCHK(g, g->work.reserve(want * sizeof(double)));
+  GraphDev& d = g->dev;
+  d = GraphDev{};
+  d.n_nodes = N; d.n_free = F; d.n_edges = ne; d.n_factors = nf;
+  const int* ip = g->ints.as<int>();
+  d.free_of = ip + at[0]; d.node_of = ip + at[1]; d.adj_off = ip + at[2]; d.adj = ip + at[3]; d.ladj_off = ip + at[4]; d.ladj = ip + at[5];
+  d.fac_ij = ip + at[6];
+  d.fac_data = g->data.as<double>();
+  d.x = g->x.as<double>(); d.cand = g->cand.as<double>();
+  double* w = g->work.as<double>();
+  auto carve = [&w](size_t n) { double* p = w; w += n; return p; };
+  d.J = carve(nfz * kGraphJ); d.fcost = carve(nfz); d.fmodel = carve(nfz);
+  d.H = carve(Fz * 36); d.Lb = carve(Fz * 36); d.g = carve(Fz * 6); d.scale = carve(Fz * 6);
+  d.nxx = carve(Fz); d.ngmax = carve(Fz); d.nstep = carve(Fz);
+  d.D = carve(blocks * 36); d.L = carve(blocks * 36); d.rhs = carve(blocks * 6); d.sol = carve(blocks * 6);
+  d.Dinv = carve(inv * 36);
+  d.b = carve(Fz * 6); d.xs = carve(Fz * 6); d.r = carve(Fz * 6); d.z = carve(Fz * 6); d.p[0] = carve(Fz * 6); d.p[1] = carve(Fz * 6); d.q = carve(Fz * 6);
+  d.part = carve(2 * n_part);
+  char* sp = g->state.as<char>();
+  d.st = reinterpret_cast<GraphState*>(sp);
+  d.tr_cost = reinterpret_cast<double*>(sp + sizeof(GraphState));
+  d.tr_accepted = reinterpret_cast<int*>(sp + sizeof(GraphState) + ((size_t)std::max(1, g->cfg.max_num_iterations) + 1) * sizeof(double));
+  g->dirty = false;
+  return MSFL_OK;
+}
+
+template <class K, class... A>
+void graph_launch(hipStream_t st, K kernel, int items, int block, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1, div_up(items, block))), dim3(block), 0, st, args...);
+}
+
+// z = T^-1 r: the right-hand-side half of the cyclic reduction
+void graph_enqueue_solve(msfl_graph* g) {
+  hipStream_t st = g->stream;
+  const GraphLevels& v = g->lv;
+  for (int l = 0; l < v.tail; l++) graph_launch(st, graph_cr_rhs_kernel, v.n[l + 1], kGraphVec, g->dev, v, l);
+  graph_launch(st, graph_cr_tail_kernel, 1, kGraphVec, g->dev, v);
+  for (int l = v.tail - 1; l >= 0; l--) graph_launch(st, graph_cr_back_kernel, v.n[l], kGraphVec, g->dev, v, l);
+}
+
+msfl_status graph_read_state(msfl_graph* g, GraphState* out) {
+  HIPCHK(g, hipMemcpyAsync(g->readback.p, g->state.p, graph_state_bytes(g), hipMemcpyDeviceToHost, g->stream));
+  HIPCHK(g, hipStreamSynchronize(g->stream));
+  std::memcpy(out, g->readback.p, sizeof(GraphState));
+  return MSFL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void msfl_graph_default_config(msfl_graph_config* c) {
+  if (!c) return;
+  c->max_nodes = 16384; c->max_edges = 32768; c->max_fixes = 16384;
+  c->max_num_iterations = 10; c->max_consecutive_invalid_steps = 5; c->jacobi_scaling = 1; c->max_cg_iterations = 0; c->reserved = 0;
+  c->huber_delta = 1.0;
+  c->initial_trust_region_radius = 1e4; c->max_trust_region_radius = 1e16; c->min_trust_region_radius = 1e-32;
+  c->min_relative_decrease = 1e-3; c->min_lm_diagonal = 1e-6; c->max_lm_diagonal = 1e32;
+  c->function_tolerance = 1e-6; c->gradient_tolerance = 1e-10; c->parameter_tolerance = 1e-8;
+  c->cg_tolerance = 1e-12;
+}
+
+msfl_status msfl_graph_create(const msfl_graph_config* cfg, int device, msfl_graph** out) {
+  if (!out) return MSFL_BAD_ARG;
+  *out = nullptr;
+  msfl_graph_config c;
+  if (cfg) c = *cfg; else msfl_graph_default_config(&c);
+  if (!graph_config_ok(c)) return MSFL_BAD_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MSFL_HIP_ERROR;   // no GPU: fail loudly, no fallback
+  if (device < 0 || device >= ndev) return MSFL_BAD_ARG;
+  msfl_graph* g = new msfl_graph_s();
+  g->device = device; g->cfg = c;
+  const size_t pose_bytes = (size_t)c.max_nodes * 7 * sizeof(double);
+  bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&g->own_stream, hipStreamNonBlocking) == hipSuccess;
+  ok = ok && g->x.reserve(pose_bytes) == hipSuccess && g->cand.reserve(pose_bytes) == hipSuccess &&
+       g->state.reserve(graph_state_bytes(g)) == hipSuccess && g->readback.reserve(std::max(graph_state_bytes(g), (size_t)4096)) == hipSuccess;
+  if (!ok) { msfl_graph_destroy(g); return MSFL_HIP_ERROR; }
+  g->stream = g->own_stream;
+  *out = g;
+  return MSFL_OK;
+}
+
+void msfl_graph_destroy(msfl_graph* g) {
+  if (!g) return;
+  (void)hipSetDevice(g->device);
+  if (g->stream) (void)hipStreamSynchronize(g->stream);
+  if (g->own_stream) (void)hipStreamDestroy(g->own_stream);
+  delete g;
+}
+
+msfl_status msfl_graph_set_stream(msfl_graph* g, void* hip_stream) {
+  msfl_status s = enter(g); if (s) return s;
+  HIPCHK(g, hipStreamSynchronize(g->stream));
+  g->stream = reinterpret_cast<hipStream_t>(hip_stream);
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_synchronize(msfl_graph* g) {
+  msfl_status s = enter(g); if (s) return s;
+  HIPCHK(g, hipStreamSynchronize(g->stream));
+  return MSFL_OK;
+}
+
+const char* msfl_graph_last_error(const msfl_graph* g) { return g ? g->last_error.c_str() : "null graph object"; }
+
+int msfl_graph_num_nodes(const msfl_graph* g) { return g ? g->n_nodes : 0; }
+
+msfl_status msfl_graph_clear(msfl_graph* g) {
+  msfl_status s = enter(g); if (s) return s;
+  HIPCHK(g, hipStreamSynchronize(g->stream));
+  g->n_nodes = 0; g->fixed.clear(); g->edges.clear(); g->fixes.clear(); g->tr_accepted.clear(); g->tr_cost.clear();
+  g->dirty = true;
+  return MSFL_OK;
+}
+
+// poses in host or device memory are checked on the host before anything is stored (a device array is read back first)
+static msfl_status graph_store_poses(msfl_graph* g, const char* who, const double* poses, int first, int n, msfl_mem mem) {
+  const std::string w(who);
+  std::vector<double> host;
+  const double* hp = poses;
+  if (mem == MSFL_MEM_DEVICE) {
+    host.resize((size_t)n * 7);
+    HIPCHK(g, hipStreamSynchronize(g->stream));
+    HIPCHK(g, hipMemcpy(host.data(), poses, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    hp = host.data();
+  }
+  for (int i = 0; i < n; i++)
+    if (!graph_pose_ok(hp + 7 * (size_t)i)) return fail(g, MSFL_BAD_ARG, w + ": a pose with a non-finite value or a zero quaternion; nothing stored");
+  double* dst = g->x.as<double>() + (size_t)first * 7;
+  if (mem == MSFL_MEM_HOST) {
+    HIPCHK(g, g->pin.upload(dst, poses, (size_t)n * 7 * sizeof(double), g->stream));
+  } else {
+    HIPCHK(g, hipMemcpyAsync(dst, poses, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
+  }
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_add_nodes(msfl_graph* g, const double* poses, int n, msfl_mem mem, int* first_index) {
+  msfl_status s = enter(g); if (s) return s;
+  if (n < 0 || (n > 0 && !poses) || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE))
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_add_nodes: null array, negative count or unknown memory kind");
+  if ((long long)g->n_nodes + n > g->cfg.max_nodes) return fail(g, MSFL_CAPACITY, "msfl_graph_add_nodes: the batch does not fit max_nodes; nothing added");
+  if (first_index) *first_index = g->n_nodes;
+  if (n == 0) return MSFL_OK;
+  s = graph_store_poses(g, "msfl_graph_add_nodes", poses, g->n_nodes, n, mem); if (s) return s;
+  g->n_nodes += n; g->fixed.resize((size_t)g->n_nodes, 0);
+  g->dirty = true;
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_add_edges(msfl_graph* g, const msfl_graph_edge* edges, int n) {
+  msfl_status s = enter(g); if (s) return s;
+  if (n < 0 || (n > 0 && !edges)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges: null array or negative count");
+  if ((long long)g->edges.size() + n > g->cfg.max_edges) return fail(g, MSFL_CAPACITY, "msfl_graph_add_edges: the batch does not fit max_edges; nothing added");
+  for (int k = 0; k < n; k++) {
+    const msfl_graph_edge& e = edges[k];
+    if (e.i < 0 || e.j < 0 || e.i >= g->n_nodes || e.j >= g->n_nodes || e.i == e.j)
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges: a node index out of range or i == j; nothing added");
+    if (!graph_pose_ok(e.z) || !std::isfinite(e.sr) || !std::isfinite(e.st) || !(e.sr > 0.0) || !(e.st > 0.0))
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges: a non-finite value, a zero quaternion or sr, st <= 0; nothing added");
+  }
+  g->edges.insert(g->edges.end(), edges, edges + n);
+  if (n) g->dirty = true;
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_add_fixes(msfl_graph* g, const msfl_graph_fix* fixes, int n) {
+  msfl_status s = enter(g); if (s) return s;
+  if (n < 0 || (n > 0 && !fixes)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes: null array or negative count");
+  if ((long long)g->fixes.size() + n > g->cfg.max_fixes) return fail(g, MSFL_CAPACITY, "msfl_graph_add_fixes: the batch does not fit max_fixes; nothing added");
+  for (int k = 0; k < n; k++) {
+    const msfl_graph_fix& f = fixes[k];
+    if (f.i < 0 || f.j < 0 || f.i >= g->n_nodes || f.j >= g->n_nodes || f.i == f.j)
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes: a node index out of range or i == j; nothing added");
+    if (!std::isfinite(f.t) || !std::isfinite(f.p[0]) || !std::isfinite(f.p[1]) || !std::isfinite(f.p[2]) || !std::isfinite(f.st) || !(f.st > 0.0) ||
+        !(f.t >= 0.0 && f.t <= 1.0))
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes: a non-finite value, st <= 0 or t outside [0, 1]; nothing added");
+  }
+  g->fixes.insert(g->fixes.end(), fixes, fixes + n);
+  if (n) g->dirty = true;
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_set_fixed(msfl_graph* g, int node, int flag) {
+  msfl_status s = enter(g); if (s) return s;
+  if (node < 0 || node >= g->n_nodes) return fail(g, MSFL_BAD_ARG, "msfl_graph_set_fixed: node index out of range");
+  const unsigned char f = flag ? 1 : 0;
+  if (g->fixed[node] != f) { g->fixed[node] = f; g->dirty = true; }
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_set_poses(msfl_graph* g, int first, int n, const double* poses, msfl_mem mem) {
+  msfl_status s = enter(g); if (s) return s;
+  if (first < 0 || n < 0 || (long long)first + n > g->n_nodes || (n > 0 && !poses) || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE))
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_set_poses: range outside the nodes, null array or unknown memory kind");
+  if (n == 0) return MSFL_OK;
+  return graph_store_poses(g, "msfl_graph_set_poses", poses, first, n, mem);
+}
+
+msfl_status msfl_graph_get_poses(msfl_graph* g, int first, int n, double* out, msfl_mem mem) {
+  msfl_status s = enter(g); if (s) return s;
+  if (first < 0 || n < 0 || (long long)first + n > g->n_nodes || (n > 0 && !out) || (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE))
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_get_poses: range outside the nodes, null array or unknown memory kind");
+  if (n == 0) return MSFL_OK;
+  HIPCHK(g, hipMemcpyAsync(out, g->x.as<double>() + (size_t)first * 7, (size_t)n * 7 * sizeof(double),
+                           mem == MSFL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, g->stream));
+  if (mem == MSFL_MEM_HOST) HIPCHK(g, hipStreamSynchronize(g->stream));
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_cost(msfl_graph* g, double* cost) {
+  msfl_status s = enter(g); if (s) return s;
+  if (!cost) return fail(g, MSFL_BAD_ARG, "msfl_graph_cost: null result");
+  *cost = 0.0;
+  s = graph_prepare(g); if (s) return s;
+  if (g->dev.n_factors == 0) return MSFL_OK;
+  hipStream_t st = g->stream;
+  double* d_out = g->dev.tr_cost + std::max(1, g->cfg.max_num_iterations);
+  graph_launch(st, graph_cost_kernel<false>, g->dev.n_factors, kGraphBlock, g->dev, (const double*)g->dev.x, g->cfg.huber_delta);
+  graph_launch(st, graph_cost_total_kernel, 1, kGraphVec, g->dev, d_out);
+  HIPCHK(g, hipGetLastError());
+  HIPCHK(g, hipMemcpyAsync(g->readback.p, d_out, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(g, hipStreamSynchronize(st));
+  *cost = *g->readback.as<double>();
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_optimize(msfl_graph* g, msfl_graph_summary* summary) {
+  msfl_status s = enter(g); if (s) return s;
+  if (!summary) return fail(g, MSFL_BAD_ARG, "msfl_graph_optimize: null summary");
+  std::memset(summary, 0, sizeof(*summary));
+  s = graph_prepare(g); if (s) return s;
+  g->tr_accepted.clear(); g->tr_cost.clear();
+  const GraphDev& d = g->dev;
+  const GraphLevels& v = g->lv;
+  summary->n_free = d.n_free; summary->n_long_edges = g->gs.n_long;
+  if (d.n_free == 0 || d.n_factors == 0) { summary->termination = MSFL_GRAPH_EMPTY; return MSFL_OK; }
+  hipStream_t st = g->stream;
+  const GraphOpt o = graph_opt(g->cfg);
+  GraphState init{};
+  init.radius = o.radius0; init.decrease_factor = 2.0; init.step_successful = 1; init.first = 1;
+  HIPCHK(g, g->pin.upload(g->state.p, &init, sizeof(init), st));
+  HIPCHK(g, hipMemcpyAsync(d.cand, d.x, (size_t)d.n_nodes * 7 * sizeof(double), hipMemcpyDeviceToDevice, st));
+  const int F = d.n_free, nf = d.n_factors, n_part = div_up(F, kGraphVec);
+  const int direct = g->gs.n_long == 0;      // A == T: the preconditioner's solve is the step, one CG iteration
+  const int cap = direct ? 1 : (g->cfg.max_cg_iterations > 0 ? g->cfg.max_cg_iterations : 16 * g->gs.n_long + 8);
+  GraphState now{};
+  for (int it = 0;; it++) {
+    graph_launch(st, graph_commit_kernel, d.n_nodes * 7, kGraphVec, d);
+    graph_launch(st, graph_linearize_kernel, nf, kGraphBlock, d, o.huber);
+    graph_launch(st, graph_assemble_kernel, F, kGraphBlock, d);
+    if (it == 0) graph_launch(st, graph_scale_kernel, F * 6, kGraphVec, d, o.jacobi);
+    graph_launch(st, graph_tr_begin_kernel, 1, kGraphVec, d, o);
+    if (it < o.max_iter) {
+      graph_launch(st, graph_damp_kernel, F, kGraphVec, d, o);
+      for (int l = 0; l < v.tail; l++) {
+        graph_launch(st, graph_cr_invert_kernel, v.n[l] / 2, kGraphBlock, d, v, l);
+        graph_launch(st, graph_cr_reduce_kernel, v.n[l + 1], kGraphBlock, d, v, l);
+      }
+      graph_launch(st, graph_cr_factor_tail_kernel, 1, kGraphVec, d, v);
+      graph_enqueue_solve(g);
+      graph_launch(st, graph_dot_kernel, F, kGraphVec, d, n_part);
+      for (int c = 0; c < cap; c++) {
+        graph_launch(st, graph_matvec_kernel, F, kGraphVec, d, c, n_part, o.cg_tol, direct);
+        graph_launch(st, graph_cg_update_kernel, F, kGraphVec, d, c, n_part);
+        graph_enqueue_solve(g);
+        graph_launch(st, graph_dot_kernel, F, kGraphVec, d, n_part);
+      }
+      graph_launch(st, graph_cg_end_kernel, 1, kGraphVec, d, n_part, o.cg_tol, direct);
+      graph_launch(st, graph_plus_kernel, F, kGraphVec, d);
+      graph_launch(st, graph_cost_kernel<true>, nf, kGraphBlock, d, (const double*)d.cand, o.huber);
+      graph_launch(st, graph_tr_kernel, 1, kGraphVec, d, o);
+    }
+    HIPCHK(g, hipGetLastError());
+    s = graph_read_state(g, &now); if (s) return s;          // the one read per LM iteration
+    if (now.done) break;
+    if (it >= o.max_iter) return fail(g, MSFL_HIP_ERROR, "msfl_graph_optimize: the device-side loop did not terminate");
+  }
+  summary->termination = now.termination; summary->iterations = now.iterations; summary->successful_steps = now.successful;
+  summary->initial_cost = now.initial_cost; summary->final_cost = now.final_cost;
+  summary->cg_iterations = now.cg_total; summary->cg_unconverged = now.cg_unconverged;
+  const char* rb = g->readback.as<char>();
+  const double* tc = reinterpret_cast<const double*>(rb + sizeof(GraphState));
+  const int* ta = reinterpret_cast<const int*>(rb + sizeof(GraphState) + ((size_t)std::max(1, o.max_iter) + 1) * sizeof(double));
+  g->tr_cost.assign(tc, tc + now.n_trace); g->tr_accepted.assign(ta, ta + now.n_trace);
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_get_trace(msfl_graph* g, int* accepted, double* cost, int capacity, int* n_out) {
+  if (!g) return MSFL_BAD_ARG;
+  if (capacity < 0 || !n_out) return fail(g, MSFL_BAD_ARG, "msfl_graph_get_trace: negative capacity or null count");
+  const int n = (int)g->tr_accepted.size();
+  *n_out = n;
+  for (int i = 0; i < std::min(n, capacity); i++) {
+    if (accepted) accepted[i] = g->tr_accepted[i];
+    if (cost) cost[i] = g->tr_cost[i];
+  }
+  return n > capacity ? fail(g, MSFL_CAPACITY, "msfl_graph_get_trace: the trace holds more iterations than `capacity`") : MSFL_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,702 @@
+// Pose-graph optimisation (msfl_graph_*): Ceres' trust-region / LM loop over a chain of poses with a few long edges, all f64.
+// docs/kernels/graph.md holds the definition.  The step (Js^T Js + D^2) s = -Js^T r is solved by PCG whose preconditioner is the
+// exact solve of the block-tridiagonal part T (block cyclic reduction); long edges enter through the mat-vec only.
+//
+// Rules every kernel here keeps:
+//   - no floating-point atomics: factors are gathered per node in adjacency order, sums over nodes / factors go through
+//     graph_block_sum (a fixed LDS tree) into one partial per workgroup and graph_total (the same tree over the partials);
+//   - no grid-wide barrier: a reduction level is a launch, the tail of the reduction is one workgroup;
+//   - a kernel that finds GraphState::done (or cg_done) set returns at once: the host enqueues a fixed launch pattern.
+// One lane owns one factor or one node; 6 x 6 blocks live in registers (fully unrolled loops), so the block kernels run 64 lanes
+// per workgroup and take what VGPRs they need.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "msfl_graph_host.h"
+
+namespace msfl {
+
+constexpr int kGraphBlock = 64;      // block kernels: one factor / node per lane
+constexpr int kGraphVec = 256;       // vector kernels: one node (6 values) per lane; also the partial size of every sum
+constexpr int kGraphJ = 78;          // doubles per linearised factor: Ji (36, row-major), Jj (36), r (6), after the corrector
+
+enum { kGraphEmpty = 0, kGraphGradient, kGraphMaxIter, kGraphMinRadius, kGraphInvalid, kGraphParameter, kGraphFunction };
+
+struct GraphOpt {
+  int max_iter, max_invalid, jacobi;
+  double huber, radius0, radius_max, radius_min, min_rel, lm_min, lm_max, ftol, gtol, ptol, cg_tol;
+};
+
+struct GraphState {                  // one record; the host reads it once per LM iteration
+  double radius, decrease_factor, cost, x_norm, gmax, initial_cost, final_cost;
+  double rz[2], rz0;
+  int iterations, successful, invalid, step_successful, termination, done, commit, first;
+  int cg_done, cg_it, cg_total, cg_unconverged, n_trace, pad;
+};
+
+struct GraphDev {
+  int n_nodes, n_free, n_edges, n_factors;
+  const int* free_of;                // [nodes]: free index or -1
+  const int* node_of;                // [free]
+  const int* adj_off; const int* adj;       // per free node: 2 * factor + side, edges in insertion order, then fixes
+  const int* ladj_off; const int* ladj;     // the long factors among them
+  const int* fac_ij;                 // [factors x 2]: node indices
+  const double* fac_data;            // [factors x 9]: edge z[7], sr, st; fix t, p[3], st
+  double* x; double* cand;           // [nodes x 7]
+  double* J;                         // [factors x kGraphJ]
+  double* fcost; double* fmodel;     // [factors]: rho / 2 per block; the block's share of the model cost change
+  double* H; double* Lb; double* g; double* scale;   // [free x 36, 36, 6, 6]: unscaled diagonal block, block (f, f-1), gradient, Jacobi scale
+  double* nxx; double* ngmax; double* nstep;         // [free]: |x|^2, max |x - Plus(x, -g)|, |x - cand|^2
+  double* D; double* L; double* Dinv;                // cyclic reduction levels; level 0 of D, L is the damped scaled T
+  double* rhs; double* sol;          // levels 1.. of the right-hand side / solution (level 0: r and z)
+  double* b; double* xs; double* r; double* z; double* p[2]; double* q;   // [free x 6]
+  double* part;                      // [2 x workgroups]: partials of p.q, of r.z
+  GraphState* st;
+  int* tr_accepted; double* tr_cost; // [max_iter]
+};
+
+// ---- sums with one stated order --------------------------------------------------------------------------------------
+template <int kThreads, bool kMax>
+__device__ __forceinline__ double graph_block_sum(double v, double* lds) {
+  const int t = (int)threadIdx.x;
+  lds[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (t < s) lds[t] = kMax ? fmax(lds[t], lds[t + s]) : lds[t] + lds[t + s];
+    __syncthreads();
+  }
+  const double out = lds[0];
+  __syncthreads();
+  return out;
+}
+// every lane of the workgroup gets the total of a[0 .. n): lane t adds a[t], a[t + kThreads], ... in that order, then the tree
+template <int kThreads, bool kMax>
+__device__ __forceinline__ double graph_total(const double* __restrict__ a, int n, double* lds) {
+  double v = 0.0;
+  for (int i = (int)threadIdx.x; i < n; i += kThreads) v = kMax ? fmax(v, a[i]) : v + a[i];
+  return graph_block_sum<kThreads, kMax>(v, lds);
+}
+
+// ---- quaternions [x y z w] and 6 x 6 blocks (row-major) ------------------------------------------------------------------
+__device__ __forceinline__ void gq_mul(const double* a, const double* b, double* o) {
+  o[0] = a[3] * b[0] + b[3] * a[0] + (a[1] * b[2] - a[2] * b[1]);
+  o[1] = a[3] * b[1] + b[3] * a[1] + (a[2] * b[0] - a[0] * b[2]);
+  o[2] = a[3] * b[2] + b[3] * a[2] + (a[0] * b[1] - a[1] * b[0]);
+  o[3] = a[3] * b[3] - (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]);
+}
+// Eigen's unit-quaternion q * v = v + 2 w (u x v) + 2 u x (u x v)
+__device__ __forceinline__ void gq_rot(const double* q, const double* v, double* o) {
+  const double c0 = q[1] * v[2] - q[2] * v[1], c1 = q[2] * v[0] - q[0] * v[2], c2 = q[0] * v[1] - q[1] * v[0];
+  o[0] = v[0] + 2.0 * (q[3] * c0 + (q[1] * c2 - q[2] * c1));
+  o[1] = v[1] + 2.0 * (q[3] * c1 + (q[2] * c0 - q[0] * c2));
+  o[2] = v[2] + 2.0 * (q[3] * c2 + (q[0] * c1 - q[1] * c0));
+}
+__device__ __forceinline__ void gq_to_R(const double* q, double* R) {
+  const double x = q[0], y = q[1], z = q[2], w = q[3];
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
+  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
+}
+// EigenQuaternionParameterization::Plus on the rotation, t + dt on the translation
+__device__ __forceinline__ void graph_plus(const double* x, const double* d, double* o) {
+  o[0] = x[0] + d[0]; o[1] = x[1] + d[1]; o[2] = x[2] + d[2];
+  const double n = sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
+  if (n > 0.0) {
+    const double k = sin(n) / n;
+    const double dq[4] = {k * d[3], k * d[4], k * d[5], cos(n)};
+    gq_mul(dq, x + 3, o + 3);
+  } else {
+    o[3] = x[3]; o[4] = x[4]; o[5] = x[5]; o[6] = x[6];
+  }
+}
+
+__device__ __forceinline__ void g6_load(const double* __restrict__ p, double* a) {
+#pragma unroll
+  for (int i = 0; i < 36; i++) a[i] = p[i];
+}
+__device__ __forceinline__ void g6_store(double* __restrict__ p, const double* a) {
+#pragma unroll
+  for (int i = 0; i < 36; i++) p[i] = a[i];
+}
+// y (+)= A x, y (+)= A^T x
+template <bool kAcc, bool kTrans>
+__device__ __forceinline__ void g6_mv(const double* A, const double* x, double* y) {
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    double s = kAcc ? y[i] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) s += (kTrans ? A[k * 6 + i] : A[i * 6 + k]) * x[k];
+    y[i] = s;
+  }
+}
+// C += sign * op(A) op(B): kTA / kTB transpose the operand
+template <bool kTA, bool kTB>
+__device__ __forceinline__ void g6_mma(const double* A, const double* B, double* Cm, double sign) {
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; k++) s += (kTA ? A[k * 6 + i] : A[i * 6 + k]) * (kTB ? B[j * 6 + k] : B[k * 6 + j]);
+      Cm[i * 6 + j] += sign * s;
+    }
+}
+// inverse of a symmetric positive definite block through its Cholesky factor (a block that is not gives NaN: an invalid step)
+__device__ __forceinline__ void g6_inv_spd(double* a) {
+#pragma unroll
+  for (int j = 0; j < 6; j++) {                    // A = C C^T, C lower, in place
+    double d = a[j * 6 + j];
+#pragma unroll
+    for (int k = 0; k < j; k++) d -= a[j * 6 + k] * a[j * 6 + k];
+    d = sqrt(d);
+    a[j * 6 + j] = d;
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double s = a[i * 6 + j];
+#pragma unroll
+      for (int k = 0; k < j; k++) s -= a[i * 6 + k] * a[j * 6 + k];
+      a[i * 6 + j] = s / d;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 6; j++) {                    // W = C^-1, lower, into the upper triangle's mirror: w(i, j) kept at a[j * 6 + i], i > j
+    a[j * 6 + j] = 1.0 / a[j * 6 + j];
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = j; k < i; k++) s -= a[i * 6 + k] * (k == j ? a[j * 6 + j] : a[j * 6 + k]);
+      a[j * 6 + i] = s / a[i * 6 + i];
+    }
+  }
+  double w[36];
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j < 6; j++) w[i * 6 + j] = i == j ? a[i * 6 + i] : (i > j ? a[j * 6 + i] : 0.0);
+#pragma unroll
+  for (int i = 0; i < 6; i++)                      // A^-1 = W^T W
+#pragma unroll
+    for (int j = 0; j <= i; j++) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = i; k < 6; k++) s += w[k * 6 + i] * w[k * 6 + j];
+      a[i * 6 + j] = s; a[j * 6 + i] = s;
+    }
+}
+
+// ---- factors -----------------------------------------------------------------------------------------------------------
+// residual of factor k at poses `x` (before the corrector); rows 3..5 of a fix are zero.  With kJac also Ji, Jj (row-major 6 x 6).
+template <bool kJac>
+__device__ __forceinline__ void graph_factor(const GraphDev& G, const double* __restrict__ x, int k, double* r, double* Ji, double* Jj) {
+  const int ni = G.fac_ij[2 * k], nj = G.fac_ij[2 * k + 1];
+  const double* d = G.fac_data + (size_t)k * 9;
+  const double* xi = x + (size_t)ni * 7; const double* xj = x + (size_t)nj * 7;
+  if (kJac) {
+#pragma unroll
+    for (int i = 0; i < 36; i++) { Ji[i] = 0.0; Jj[i] = 0.0; }
+  }
+  if (k >= G.n_edges) {                            // position fix: t, p[3], st
+    const double t = d[0], st = d[4];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      r[c] = ((1.0 - t) * xi[c] + t * xj[c] - d[1 + c]) / st;
+      r[3 + c] = 0.0;
+      if (kJac) { Ji[c * 6 + c] = (1.0 - t) / st; Jj[c * 6 + c] = t / st; }
+    }
+    return;
+  }
+  const double sr = d[7], st = d[8];
+  const double qi[4] = {xi[3], xi[4], xi[5], xi[6]}, qz[4] = {d[3], d[4], d[5], d[6]};
+  const double A[4] = {-xj[3], -xj[4], -xj[5], xj[6]};
+  double a[3], v[3], B[4], e[3], qe[4];
+  gq_rot(qi, d, a);                                // R_i t_z
+#pragma unroll
+  for (int c = 0; c < 3; c++) v[c] = a[c] + xi[c] - xj[c];
+  gq_mul(qi, qz, B);
+  gq_rot(A, v, e);
+  gq_mul(A, B, qe);
+#pragma unroll
+  for (int c = 0; c < 3; c++) { r[c] = e[c] / st; r[3 + c] = qe[c] / sr; }
+  if (!kJac) return;
+  double R[9];
+  gq_to_R(xj + 3, R);
+  // translation rows: d/dt_i = R_j^T / st, d/dd_i = R_j^T (-2 [a]x) / st, d/dt_j = -R_j^T / st, d/dd_j = R_j^T (2 [v]x) / st
+  const double Sa[9] = {0.0, 2.0 * a[2], -2.0 * a[1], -2.0 * a[2], 0.0, 2.0 * a[0], 2.0 * a[1], -2.0 * a[0], 0.0};     // -2 [a]x
+  const double Sv[9] = {0.0, -2.0 * v[2], 2.0 * v[1], 2.0 * v[2], 0.0, -2.0 * v[0], -2.0 * v[1], 2.0 * v[0], 0.0};     //  2 [v]x
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const double rt = R[j * 3 + i];               // R_j^T (i, j)
+      Ji[i * 6 + j] = rt / st; Jj[i * 6 + j] = -rt / st;
+      double sa = 0.0, sv = 0.0;
+#pragma unroll
+      for (int m = 0; m < 3; m++) { sa += R[m * 3 + i] * Sa[m * 3 + j]; sv += R[m * 3 + i] * Sv[m * 3 + j]; }
+      Ji[i * 6 + 3 + j] = sa / st; Jj[i * 6 + 3 + j] = sv / st;
+    }
+  // rotation rows: column c of M is vec(A (x) [e_c, 0] (x) B); d/dd_i = M / sr, d/dd_j = -M / sr
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const double ec[4] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0, 0.0};
+    double t1[4], t2[4];
+    gq_mul(A, ec, t1);
+    gq_mul(t1, B, t2);
+#pragma unroll
+    for (int i = 0; i < 3; i++) { Ji[(3 + i) * 6 + 3 + c] = t2[i] / sr; Jj[(3 + i) * 6 + 3 + c] = -(t2[i] / sr); }
+  }
+}
+
+// HuberLoss through the rho'' <= 0 corrector: *half_rho = rho / 2, returns sqrt(rho')
+__device__ __forceinline__ double graph_huber(const double* r, double a, double* half_rho) {
+  double sq = 0.0;
+#pragma unroll
+  for (int c = 0; c < 6; c++) sq += r[c] * r[c];
+  const double b = a * a;
+  if (a > 0.0 && sq > b) {
+    const double n = sqrt(sq);
+    *half_rho = 0.5 * (2.0 * a * n - b);
+    return sqrt(fmax(2.2250738585072014e-308, a / n));
+  }
+  *half_rho = 0.5 * sq;
+  return 1.0;
+}
+
+__global__ __launch_bounds__(kGraphVec) void graph_commit_kernel(GraphDev G) {
+  if (!G.st->commit) return;
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < G.n_nodes * 7) G.x[i] = G.cand[i];
+}
+
+__global__ __launch_bounds__(kGraphBlock) void graph_linearize_kernel(GraphDev G, double huber) {
+  if (G.st->done) return;
+  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (k >= G.n_factors) return;
+  double r[6], Ji[36], Jj[36], hr;
+  graph_factor<true>(G, G.x, k, r, Ji, Jj);
+  const double s = graph_huber(r, huber, &hr);
+  double* o = G.J + (size_t)k * kGraphJ;
+#pragma unroll
+  for (int i = 0; i < 36; i++) { o[i] = s * Ji[i]; o[36 + i] = s * Jj[i]; }
+#pragma unroll
+  for (int i = 0; i < 6; i++) o[72 + i] = s * r[i];
+  G.fcost[k] = hr;
+}
+
+// cost of every block at `x` into fcost; with kModel also the block's share of -m . (r + m / 2), m = Js step
+template <bool kModel>
+__global__ __launch_bounds__(kGraphBlock) void graph_cost_kernel(GraphDev G, const double* __restrict__ x, double huber) {
+  if (kModel && G.st->done) return;
+  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (k >= G.n_factors) return;
+  double r[6], hr;
+  graph_factor<false>(G, x, k, r, nullptr, nullptr);
+  (void)graph_huber(r, huber, &hr);
+  G.fcost[k] = hr;
+  if (!kModel) return;
+  const double* Jk = G.J + (size_t)k * kGraphJ;
+  double m[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int side = 0; side < 2; side++) {
+    const int f = G.free_of[G.fac_ij[2 * k + side]];
+    if (f < 0) continue;
+    double sx[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) sx[c] = G.scale[(size_t)f * 6 + c] * G.xs[(size_t)f * 6 + c];
+    g6_mv<true, false>(Jk + 36 * side, sx, m);
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int c = 0; c < 6; c++) s += m[c] * (Jk[72 + c] + 0.5 * m[c]);
+  G.fmodel[k] = -s;
+}
+
+// one free node per lane: gathers its factors in adjacency order into the unscaled diagonal block, the block towards f - 1 and the gradient
+__global__ __launch_bounds__(kGraphBlock) void graph_assemble_kernel(GraphDev G) {
+  if (G.st->done) return;
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (f >= G.n_free) return;
+  double H[36], Lb[36], g[6];
+#pragma unroll
+  for (int i = 0; i < 36; i++) { H[i] = 0.0; Lb[i] = 0.0; }
+#pragma unroll
+  for (int i = 0; i < 6; i++) g[i] = 0.0;
+  for (int e = G.adj_off[f]; e < G.adj_off[f + 1]; e++) {
+    const int k = G.adj[e] >> 1, side = G.adj[e] & 1;
+    const double* Jk = G.J + (size_t)k * kGraphJ;
+    double Js[36];
+    g6_load(Jk + 36 * side, Js);
+    g6_mma<true, false>(Js, Js, H, 1.0);
+    g6_mv<true, true>(Js, Jk + 72, g);
+    const int fo = G.free_of[G.fac_ij[2 * k + (side ^ 1)]];
+    if (fo >= 0 && fo == f - 1) {
+      double Jo[36];
+      g6_load(Jk + 36 * (side ^ 1), Jo);
+      g6_mma<true, false>(Js, Jo, Lb, 1.0);
+    }
+  }
+  g6_store(G.H + (size_t)f * 36, H);
+  g6_store(G.Lb + (size_t)f * 36, Lb);
+  const double* x = G.x + (size_t)G.node_of[f] * 7;
+  double mg[6], xm[7], xx = 0.0, gm = 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) { G.g[(size_t)f * 6 + i] = g[i]; mg[i] = -g[i]; }
+  graph_plus(x, mg, xm);
+#pragma unroll
+  for (int i = 0; i < 7; i++) { xx += x[i] * x[i]; gm = fmax(gm, fabs(x[i] - xm[i])); }
+  G.nxx[f] = xx; G.ngmax[f] = gm;
+}
+
+__global__ __launch_bounds__(kGraphVec) void graph_scale_kernel(GraphDev G, int jacobi) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= G.n_free * 6) return;
+  const int f = i / 6, c = i - 6 * f;
+  G.scale[i] = jacobi ? 1.0 / (1.0 + sqrt(G.H[(size_t)f * 36 + c * 7])) : 1.0;
+}
+
+// the top of TrustRegionMinimizer's loop: iteration 0's bookkeeping, then FinalizeIterationAndCheckIfMinimizerCanContinue
+__global__ __launch_bounds__(kGraphVec) void graph_tr_begin_kernel(GraphDev G, GraphOpt o) {
+  __shared__ double lds[kGraphVec];
+  GraphState* s = G.st;
+  if (s->done) return;
+  const double xx = graph_total<kGraphVec, false>(G.nxx, G.n_free, lds);
+  const double gmax = graph_total<kGraphVec, true>(G.ngmax, G.n_free, lds);
+  const double cost = s->first ? graph_total<kGraphVec, false>(G.fcost, G.n_factors, lds) : 0.0;
+  if (threadIdx.x != 0) return;
+  s->commit = 0;
+  s->x_norm = sqrt(xx); s->gmax = gmax;
+  if (s->first) {
+    s->first = 0;
+    s->cost = s->initial_cost = s->final_cost = cost;
+    if (gmax <= o.gtol) { s->termination = kGraphGradient; s->done = 1; return; }
+  }
+  if (s->iterations >= o.max_iter) { s->termination = kGraphMaxIter; s->done = 1; return; }
+  if (s->step_successful && gmax <= o.gtol) { s->termination = kGraphGradient; s->done = 1; return; }
+  if (s->radius < o.radius_min) { s->termination = kGraphMinRadius; s->done = 1; return; }
+  s->iterations += 1;
+  s->cg_done = 0; s->cg_it = 0;
+}
+
+// level 0 of the reduction: T = the scaled blocks plus the LM diagonal; b = -(scale . g); r = b, step = 0
+__global__ __launch_bounds__(kGraphVec) void graph_damp_kernel(GraphDev G, GraphOpt o) {
+  if (G.st->done) return;
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (f >= G.n_free) return;
+  const double radius = G.st->radius;
+  const double* s = G.scale + (size_t)f * 6;
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) {
+      double h = s[i] * s[j] * G.H[(size_t)f * 36 + i * 6 + j];
+      if (i == j) h += fmin(fmax(h, o.lm_min), o.lm_max) / radius;
+      G.D[(size_t)f * 36 + i * 6 + j] = h;
+      G.L[(size_t)f * 36 + i * 6 + j] = f > 0 ? s[i] * G.scale[(size_t)(f - 1) * 6 + j] * G.Lb[(size_t)f * 36 + i * 6 + j] : 0.0;
+    }
+  for (int i = 0; i < 6; i++) {
+    const double b = -(s[i] * G.g[(size_t)f * 6 + i]);
+    G.b[(size_t)f * 6 + i] = b; G.r[(size_t)f * 6 + i] = b; G.xs[(size_t)f * 6 + i] = 0.0;
+  }
+}
+
+// ---- block cyclic reduction of T x = y: level l keeps its even blocks; odd block k is x_k = D_k^-1 (y_k - L_k x_k-1 - L_k+1^T x_k+1) ----
+__device__ __forceinline__ void graph_cr_invert_node(const GraphDev& G, const GraphLevels& V, int l, int j) {
+  const int k = V.n[l] == 1 ? 0 : 2 * j + 1;       // the last level's single block is inverted too
+  double a[36];
+  g6_load(G.D + (size_t)(V.off[l] + k) * 36, a);
+  g6_inv_spd(a);
+  g6_store(G.Dinv + (size_t)(V.ioff[l] + j) * 36, a);
+}
+// block m of level l + 1 from block k = 2 m of level l:
+//   D' = D_k - L_k Dinv_k-1 L_k^T - L_k+1^T Dinv_k+1 L_k+1,   L' = -L_k Dinv_k-1 L_k-1
+__device__ __forceinline__ void graph_cr_reduce_node(const GraphDev& G, const GraphLevels& V, int l, int m) {
+  const int k = 2 * m, n = V.n[l];
+  const double* Dl = G.D + (size_t)V.off[l] * 36; const double* Ll = G.L + (size_t)V.off[l] * 36;
+  const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
+  double Dn[36], Ln[36], A[36], W[36], T[36];
+  g6_load(Dl + (size_t)k * 36, Dn);
+#pragma unroll
+  for (int i = 0; i < 36; i++) Ln[i] = 0.0;
+  if (k >= 1) {
+    g6_load(Ll + (size_t)k * 36, A);
+    g6_load(Il + (size_t)(m - 1) * 36, W);
+#pragma unroll
+    for (int i = 0; i < 36; i++) T[i] = 0.0;
+    g6_mma<false, false>(A, W, T, 1.0);            // L_k Dinv_k-1
+    g6_mma<false, true>(T, A, Dn, -1.0);
+    if (k >= 2) {
+      g6_load(Ll + (size_t)(k - 1) * 36, W);
+      g6_mma<false, false>(T, W, Ln, -1.0);
+    }
+  }
+  if (k + 1 < n) {
+    g6_load(Ll + (size_t)(k + 1) * 36, A);
+    g6_load(Il + (size_t)m * 36, W);
+#pragma unroll
+    for (int i = 0; i < 36; i++) T[i] = 0.0;
+    g6_mma<true, false>(A, W, T, 1.0);             // L_k+1^T Dinv_k+1
+    g6_mma<false, false>(T, A, Dn, -1.0);
+  }
+  g6_store(G.D + (size_t)(V.off[l + 1] + m) * 36, Dn);
+  g6_store(G.L + (size_t)(V.off[l + 1] + m) * 36, Ln);
+}
+// right-hand side of block m of level l + 1: y' = y_k - L_k Dinv_k-1 y_k-1 - L_k+1^T Dinv_k+1 y_k+1
+__device__ __forceinline__ void graph_cr_rhs_node(const GraphDev& G, const GraphLevels& V, int l, int m, const double* __restrict__ y,
+                                                  double* __restrict__ yn) {
+  const int k = 2 * m, n = V.n[l];
+  const double* Ll = G.L + (size_t)V.off[l] * 36; const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
+  double o[6], t[6], u[6];
+#pragma unroll
+  for (int i = 0; i < 6; i++) o[i] = y[(size_t)k * 6 + i];
+  if (k >= 1) {
+    g6_mv<false, false>(Il + (size_t)(m - 1) * 36, y + (size_t)(k - 1) * 6, t);
+    g6_mv<false, false>(Ll + (size_t)k * 36, t, u);
+#pragma unroll
+    for (int i = 0; i < 6; i++) o[i] -= u[i];
+  }
+  if (k + 1 < n) {
+    g6_mv<false, false>(Il + (size_t)m * 36, y + (size_t)(k + 1) * 6, t);
+    g6_mv<false, true>(Ll + (size_t)(k + 1) * 36, t, u);
+#pragma unroll
+    for (int i = 0; i < 6; i++) o[i] -= u[i];
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) yn[(size_t)m * 6 + i] = o[i];
+}
+// solution of block k of level l from the solution xn of level l + 1 (even blocks copy, odd blocks substitute)
+__device__ __forceinline__ void graph_cr_back_node(const GraphDev& G, const GraphLevels& V, int l, int k, const double* __restrict__ y,
+                                                   const double* __restrict__ xn, double* __restrict__ x) {
+  const int n = V.n[l], m = k >> 1;
+  if (!(k & 1)) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) x[(size_t)k * 6 + i] = xn[(size_t)m * 6 + i];
+    return;
+  }
+  const double* Ll = G.L + (size_t)V.off[l] * 36; const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
+  double t[6], o[6];
+#pragma unroll
+  for (int i = 0; i < 6; i++) t[i] = y[(size_t)k * 6 + i];
+  g6_mv<false, false>(Ll + (size_t)k * 36, xn + (size_t)m * 6, o);
+#pragma unroll
+  for (int i = 0; i < 6; i++) t[i] -= o[i];
+  if (k + 1 < n) {
+    g6_mv<false, true>(Ll + (size_t)(k + 1) * 36, xn + (size_t)(m + 1) * 6, o);
+#pragma unroll
+    for (int i = 0; i < 6; i++) t[i] -= o[i];
+  }
+  g6_mv<false, false>(Il + (size_t)m * 36, t, o);
+#pragma unroll
+  for (int i = 0; i < 6; i++) x[(size_t)k * 6 + i] = o[i];
+}
+__device__ __forceinline__ const double* graph_level_rhs(const GraphDev& G, const GraphLevels& V, int l) { return l == 0 ? G.r : G.rhs + (size_t)V.off[l] * 6; }
+__device__ __forceinline__ double* graph_level_sol(const GraphDev& G, const GraphLevels& V, int l) { return l == 0 ? G.z : G.sol + (size_t)V.off[l] * 6; }
+
+// the factor half, once per LM iteration: invert the odd blocks of level l, then form level l + 1
+__global__ __launch_bounds__(kGraphBlock) void graph_cr_invert_kernel(GraphDev G, GraphLevels V, int l) {
+  if (G.st->done) return;
+  const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (j < V.n[l] / 2) graph_cr_invert_node(G, V, l, j);
+}
+__global__ __launch_bounds__(kGraphBlock) void graph_cr_reduce_kernel(GraphDev G, GraphLevels V, int l) {
+  if (G.st->done) return;
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m < V.n[l + 1]) graph_cr_reduce_node(G, V, l, m);
+}
+// one workgroup finishes the factor half from level V.tail on
+__global__ __launch_bounds__(kGraphVec) void graph_cr_factor_tail_kernel(GraphDev G, GraphLevels V) {
+  if (G.st->done) return;
+  for (int l = V.tail; l < V.count; l++) {
+    const int inv = V.n[l] == 1 ? 1 : V.n[l] / 2;
+    for (int j = (int)threadIdx.x; j < inv; j += kGraphVec) graph_cr_invert_node(G, V, l, j);
+    __syncthreads();
+    if (l + 1 < V.count)
+      for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec) graph_cr_reduce_node(G, V, l, m);
+    __syncthreads();
+  }
+}
+// the right-hand-side half, once per CG iteration: z = T^-1 r
+__global__ __launch_bounds__(kGraphVec) void graph_cr_rhs_kernel(GraphDev G, GraphLevels V, int l) {
+  if (G.st->done || G.st->cg_done) return;
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m < V.n[l + 1]) graph_cr_rhs_node(G, V, l, m, graph_level_rhs(G, V, l), G.rhs + (size_t)V.off[l + 1] * 6);
+}
+__global__ __launch_bounds__(kGraphVec) void graph_cr_tail_kernel(GraphDev G, GraphLevels V) {
+  if (G.st->done || G.st->cg_done) return;
+  const int last = V.count - 1;
+  for (int l = V.tail; l < last; l++) {
+    for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec) graph_cr_rhs_node(G, V, l, m, graph_level_rhs(G, V, l), G.rhs + (size_t)V.off[l + 1] * 6);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) g6_mv<false, false>(G.Dinv + (size_t)V.ioff[last] * 36, graph_level_rhs(G, V, last), graph_level_sol(G, V, last));
+  __syncthreads();
+  for (int l = last - 1; l >= V.tail; l--) {
+    for (int k = (int)threadIdx.x; k < V.n[l]; k += kGraphVec)
+      graph_cr_back_node(G, V, l, k, graph_level_rhs(G, V, l), graph_level_sol(G, V, l + 1), graph_level_sol(G, V, l));
+    __syncthreads();
+  }
+}
+__global__ __launch_bounds__(kGraphVec) void graph_cr_back_kernel(GraphDev G, GraphLevels V, int l) {
+  if (G.st->done || G.st->cg_done) return;
+  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (k < V.n[l]) graph_cr_back_node(G, V, l, k, graph_level_rhs(G, V, l), graph_level_sol(G, V, l + 1), graph_level_sol(G, V, l));
+}
+
+// ---- PCG ---------------------------------------------------------------------------------------------------------------
+// partial of r . z per workgroup
+__global__ __launch_bounds__(kGraphVec) void graph_dot_kernel(GraphDev G, int n_part) {
+  __shared__ double lds[kGraphVec];
+  if (G.st->done || G.st->cg_done) return;
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  double s = 0.0;
+  if (f < G.n_free)
+    for (int i = 0; i < 6; i++) s += G.r[(size_t)f * 6 + i] * G.z[(size_t)f * 6 + i];
+  s = graph_block_sum<kGraphVec, false>(s, lds);
+  if (threadIdx.x == 0) G.part[n_part + blockIdx.x] = s;
+}
+
+// CG iteration `it`: the convergence test on r . z, p = z + beta p (written to p[it & 1], read from the other), q = A p, partial p . q
+__global__ __launch_bounds__(kGraphVec) void graph_matvec_kernel(GraphDev G, int it, int n_part, double cg_tol, int direct) {
+  __shared__ double lds[kGraphVec];
+  GraphState* s = G.st;
+  if (s->done || s->cg_done) return;
+  const int c = it & 1;
+  const double rz = graph_total<kGraphVec, false>(G.part + n_part, n_part, lds);
+  const double rz0 = it == 0 ? rz : s->rz0;
+  const bool stop = it == 0 ? !(rz > 0.0) : (!direct && sqrt(rz) <= cg_tol * sqrt(rz0));
+  if (stop) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) s->cg_done = 1;
+    return;
+  }
+  const double beta = it == 0 ? 0.0 : rz / s->rz[c ^ 1];
+  if (blockIdx.x == 0 && threadIdx.x == 0) { s->rz[c] = rz; if (it == 0) s->rz0 = rz; }
+  const double* po = G.p[c ^ 1]; double* pn = G.p[c];
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  double pq = 0.0;
+  if (f < G.n_free) {
+    double pf[6], pm[6], q[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) pf[i] = G.z[(size_t)f * 6 + i] + (it == 0 ? 0.0 : beta * po[(size_t)f * 6 + i]);
+    g6_mv<false, false>(G.D + (size_t)f * 36, pf, q);
+    if (f > 0) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) pm[i] = G.z[(size_t)(f - 1) * 6 + i] + (it == 0 ? 0.0 : beta * po[(size_t)(f - 1) * 6 + i]);
+      g6_mv<true, false>(G.L + (size_t)f * 36, pm, q);
+    }
+    if (f + 1 < G.n_free) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) pm[i] = G.z[(size_t)(f + 1) * 6 + i] + (it == 0 ? 0.0 : beta * po[(size_t)(f + 1) * 6 + i]);
+      g6_mv<true, true>(G.L + (size_t)(f + 1) * 36, pm, q);
+    }
+    const double* sf = G.scale + (size_t)f * 6;
+    for (int e = G.ladj_off[f]; e < G.ladj_off[f + 1]; e++) {       // long factors: s_f . Jf^T (Jo (s_o . p_o)), in adjacency order
+      const int k = G.ladj[e] >> 1, side = G.ladj[e] & 1;
+      const int fo = G.free_of[G.fac_ij[2 * k + (side ^ 1)]];
+      const double* Jk = G.J + (size_t)k * kGraphJ;
+      double t[6], u[6];
+#pragma unroll
+      for (int i = 0; i < 6; i++) pm[i] = G.scale[(size_t)fo * 6 + i] * (G.z[(size_t)fo * 6 + i] + (it == 0 ? 0.0 : beta * po[(size_t)fo * 6 + i]));
+      g6_mv<false, false>(Jk + 36 * (side ^ 1), pm, t);
+      g6_mv<false, true>(Jk + 36 * side, t, u);
+#pragma unroll
+      for (int i = 0; i < 6; i++) q[i] += sf[i] * u[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) { pn[(size_t)f * 6 + i] = pf[i]; G.q[(size_t)f * 6 + i] = q[i]; pq += pf[i] * q[i]; }
+  }
+  pq = graph_block_sum<kGraphVec, false>(pq, lds);
+  if (threadIdx.x == 0) G.part[blockIdx.x] = pq;
+}
+
+// step += alpha p, r -= alpha q, alpha = r . z / p . q
+__global__ __launch_bounds__(kGraphVec) void graph_cg_update_kernel(GraphDev G, int it, int n_part) {
+  __shared__ double lds[kGraphVec];
+  GraphState* s = G.st;
+  if (s->done || s->cg_done) return;
+  const double pq = graph_total<kGraphVec, false>(G.part, n_part, lds);
+  const double alpha = s->rz[it & 1] / pq;
+  const double* p = G.p[it & 1];
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (f < G.n_free)
+    for (int i = 0; i < 6; i++) {
+      G.xs[(size_t)f * 6 + i] += alpha * p[(size_t)f * 6 + i];
+      G.r[(size_t)f * 6 + i] -= alpha * G.q[(size_t)f * 6 + i];
+    }
+  if (blockIdx.x == 0 && threadIdx.x == 0) s->cg_it = it + 1;
+}
+
+// after the last enqueued iteration: a solve that has not met the tolerance hands over its iterate and is counted
+__global__ __launch_bounds__(kGraphVec) void graph_cg_end_kernel(GraphDev G, int n_part, double cg_tol, int direct) {
+  __shared__ double lds[kGraphVec];
+  GraphState* s = G.st;
+  if (s->done) return;
+  const double rz = graph_total<kGraphVec, false>(G.part + n_part, n_part, lds);
+  if (threadIdx.x != 0) return;
+  if (!s->cg_done && !direct && !(sqrt(rz) <= cg_tol * sqrt(s->rz0))) s->cg_unconverged += 1;
+  s->cg_total += s->cg_it;
+  s->cg_done = 0;
+}
+
+// candidate = Plus(x, scale . step) per free node, and |x - candidate|^2
+__global__ __launch_bounds__(kGraphVec) void graph_plus_kernel(GraphDev G) {
+  if (G.st->done) return;
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (f >= G.n_free) return;
+  const double* x = G.x + (size_t)G.node_of[f] * 7;
+  double d[6], o[7], s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) d[i] = G.xs[(size_t)f * 6 + i] * G.scale[(size_t)f * 6 + i];
+  graph_plus(x, d, o);
+#pragma unroll
+  for (int i = 0; i < 7; i++) { G.cand[(size_t)G.node_of[f] * 7 + i] = o[i]; s += (x[i] - o[i]) * (x[i] - o[i]); }
+  G.nstep[f] = s;
+}
+
+// the rest of one TrustRegionMinimizer iteration, in the order of tests/ceres_numpy.solve
+__global__ __launch_bounds__(kGraphVec) void graph_tr_kernel(GraphDev G, GraphOpt o) {
+  __shared__ double lds[kGraphVec];
+  GraphState* s = G.st;
+  if (s->done) return;
+  const double model = graph_total<kGraphVec, false>(G.fmodel, G.n_factors, lds);
+  const double cand_cost = graph_total<kGraphVec, false>(G.fcost, G.n_factors, lds);
+  const double step2 = graph_total<kGraphVec, false>(G.nstep, G.n_free, lds);
+  if (threadIdx.x != 0) return;
+  const int slot = s->n_trace++;
+  const bool valid = isfinite(model) && isfinite(step2) && model > 0.0;
+  if (!valid) {
+    G.tr_accepted[slot] = -1; G.tr_cost[slot] = s->cost;
+    s->invalid += 1;
+    if (s->invalid >= o.max_invalid) { s->termination = kGraphInvalid; s->done = 1; return; }
+    s->radius *= 0.5;
+    s->step_successful = 0;
+    return;
+  }
+  s->invalid = 0;
+  G.tr_cost[slot] = cand_cost;
+  const double step_norm = sqrt(step2);
+  if (step_norm <= o.ptol * (s->x_norm + o.ptol)) { G.tr_accepted[slot] = 0; s->termination = kGraphParameter; s->done = 1; return; }
+  const double change = s->cost - cand_cost;
+  if (fabs(change) <= o.ftol * s->cost) { G.tr_accepted[slot] = 0; s->termination = kGraphFunction; s->done = 1; return; }
+  const double rel = change / model;
+  const bool ok = rel > o.min_rel;
+  G.tr_accepted[slot] = ok ? 1 : 0;
+  if (ok) {
+    s->commit = 1;
+    s->cost = s->final_cost = cand_cost;
+    const double w = 2.0 * rel - 1.0;
+    s->radius = fmin(s->radius / fmax(1.0 / 3.0, 1.0 - w * w * w), o.radius_max);
+    s->decrease_factor = 2.0; s->step_successful = 1; s->successful += 1;
+  } else {
+    s->radius /= s->decrease_factor;
+    s->decrease_factor *= 2.0;
+    s->step_successful = 0;
+  }
+}
+
+// msfl_graph_cost: the total of fcost into out[0]
+__global__ __launch_bounds__(kGraphVec) void graph_cost_total_kernel(GraphDev G, double* out) {
+  __shared__ double lds[kGraphVec];
+  const double c = graph_total<kGraphVec, false>(G.fcost, G.n_factors, lds);
+  if (threadIdx.x == 0) out[0] = c;
+}
+
+}  // namespace msfl
