@@ -1,6 +1,6 @@
 """Closing a loop end to end: places -> score -> match -> pose graph -> corrected trajectory.
 
-    python examples/close_loop.py [--scans 151] [--gap 50] [--every 1] [--max-distance 0.1] [--min-fitness 0.99]
+    python examples/close_loop.py [--scans 151] [--gap 50] [--every 1] [--max-distance 0.1] [--min-fitness 0.99] [--weights scalar|information]
 
 The figure of eight of examples/loop_candidates.py.  Every scan goes through the device-resident SLAM step (keep_clouds) and into a
 capi.Places.  The odometry the graph starts from is made to drift: the session's consecutive relative poses with a yaw bias and
@@ -9,7 +9,10 @@ older; the candidate becomes a pose guess (the matched scan's map pose turned by
 msfl_match_scan2map refines it, and a candidate with descriptor distance <= --max-distance whose refined pose has fitness >=
 --min-fitness and lies within 1.5 m of the guess becomes a long edge whose measurement is the matched scan's map pose^-1 times
 the refined pose (the room repeats itself, so looser rules let wrong closures in; on this path only its end closes).  capi.PoseGraph optimises the chain (first node fixed) and the absolute
-trajectory error against the truth is printed before and after.  A demonstration; the acceptance rule here is the example's, not
+trajectory error against the truth is printed before and after.  --weights information: the refinement runs with set_uncertainty, a
+closure becomes the information edge of its registration (capi.edge_from_uncertainty: the registration's information matrix scaled by its
+variance factor, without the directions it counts degenerate) in place of the hand-picked sr = 0.005 / st = 0.05, and the chi-square of
+every closure is printed after the optimisation.  A demonstration; the acceptance rule here is the example's, not
 the library's."""
 import argparse
 import os
@@ -65,6 +68,8 @@ def main():
     ap.add_argument("--max-distance", type=float, default=0.1, help="descriptor distance up to which a candidate is verified")
     ap.add_argument("--max-dist", type=float, default=1.0)
     ap.add_argument("--min-fitness", type=float, default=0.99)
+    ap.add_argument("--weights", choices=("scalar", "information"), default="scalar", help="how a closure edge is weighted")
+    ap.add_argument("--min-eigenvalue", type=float, default=150.0, help="information: eigenvalues of a registration below this are degenerate")
     args = ap.parse_args()
 
     world = synth.World()
@@ -87,12 +92,15 @@ def main():
     grid_c, grid_s = slam.grids()
     h = capi.Handle(0)
     h.set_map(grid_c.dump(), grid_s.dump())
+    if args.weights == "information":
+        h.set_uncertainty(1, args.min_eigenvalue)
     closures = []
     for k, m, sharp, flat in candidates:
         j, yaw = int(m["index"]), float(capi.place_yaw(m["shift"], places.n_sector))
         corner, surf = h.voxel_downsample(sharp, 0.2), h.voxel_downsample(flat, 0.4)
         guess = turned(pose_map[j], yaw)
         status, refined, _ = h.match_scan2map(corner, surf, guess)
+        unc = h.uncertainty(1)[0] if args.weights == "information" else None
         fit = capi.fitness(h.score_poses(corner, surf, [refined], args.max_dist), len(corner), len(surf))[0]
         ok = status == 0 and fit >= args.min_fitness and np.linalg.norm(np.asarray(refined)[:3] - guess[:3]) <= 1.5
         z = capi.relative_pose(pose_map[j], np.asarray(refined))
@@ -100,20 +108,30 @@ def main():
         print("scan %3d ~ scan %3d: distance %.3f, yaw %+6.1f deg, refined fitness %.3f -> %s (measurement off the truth by %.3f m, %.2f deg)"
               % (k, j, m["distance"], np.degrees(yaw), fit, "edge" if ok else "dropped", dt, np.degrees(dr)))
         if ok:
-            closures.append((j, k, z))
+            closures.append((j, k, z, unc, np.asarray(refined, np.float64)))
 
     n = args.scans
     g = capi.PoseGraph(0, max_nodes=n, max_edges=n + len(closures), max_fixes=1)
     g.add_nodes(drifted)
     g.set_fixed(0)
     g.add_edges(g.edges(np.arange(n - 1), np.arange(1, n), rel, sr=0.01, st=0.1))
-    if closures:
+    if closures and args.weights == "scalar":
         g.add_edges(g.edges([c[0] for c in closures], [c[1] for c in closures], np.array([c[2] for c in closures]), sr=0.005, st=0.05))
+    for j, k, _, unc, refined in closures if args.weights == "information" else []:
+        status, rec = capi.edge_from_uncertainty(j, k, pose_map[j], refined, unc, unc["sigma2"] if unc["sigma2"] > 0.0 else 1.0)
+        if status != capi.OK:
+            raise SystemExit("scan %d ~ scan %d: the registration left no usable uncertainty record" % (k, j))
+        print("scan %3d ~ scan %3d: information edge of rank %d, sigma2 %.3g, sqrt of the kept eigenvalues / sigma2: %s"
+              % (k, j, 6 - unc["n_degenerate"], unc["sigma2"], np.array2string(np.linalg.norm(rec["sqrt_information"][0], axis=1), precision=1)))
+        g.add_edges_info(rec)
     s = g.optimize()
     print("%d closure edges (%d of them long: both ends free, more than one apart); %s after %d iterations (%d CG iterations, %d unconverged); cost %.4g -> %.4g"
           % (len(closures), s.n_long_edges, capi.GRAPH_TERMINATION[s.termination], s.iterations, s.cg_iterations, s.cg_unconverged, s.initial_cost, s.final_cost))
     print("ATE against the truth: session %.3f m, drifting odometry %.3f m, after the optimisation %.3f m"
           % (ate(pose_map, truth), ate(drifted, truth), ate(g.poses(), truth)))
+    if args.weights == "information":
+        for (j, k, _, _, _), c in zip(closures, g.chi2(capi.GRAPH_FACTOR_EDGE_INFO)):
+            print("closure scan %3d ~ scan %3d: chi-square %.3g (6 degrees of freedom under the model)" % (k, j, c))
     g.close()
     h.close()
     places.close()

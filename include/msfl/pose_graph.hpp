@@ -1,6 +1,7 @@
 // msfl/pose_graph.hpp — C++ face of msfl_graph_* (include/msfl_c_api.h, docs/kernels/graph.md):
 //   msfl::PoseGraph      RAII over the C ABI
 //   msfl::PoseGraphEdge  the record of a loop-closure edge, the role of PoseGraphEdgeFactor (loop_closure/pose_graph_factor.h)
+//   msfl::PoseGraphEdgeInfo  the same edge weighted by the information matrix of the registration that measured it
 //   msfl::GpsFusion      the reference's class (slam/gps_fusion/gps_fusion.h, gps_fusion.cc:16-97): AddFixedPoint, AddLocalPose, Optimize
 // Header only, C++14.
 #ifndef MSFL_POSE_GRAPH_HPP_
@@ -32,6 +33,17 @@ inline msfl_graph_edge PoseGraphEdge(int i, int j, const Rigid3d& pose_ij, doubl
   const std::array<double, 7> z = pose_ij.ToVector7();
   std::copy(z.begin(), z.end(), e.z);
   e.sr = sr; e.st = st;
+  return e;
+}
+
+// The information-weighted edge a registration gives: pose_j is the registered pose, `unc` its record (msfl_set_uncertainty), `scale` the
+// variance factor (unc.sigma2, or a sensor model's); pose_i is taken as exact.  Directions the record counts degenerate get no weight.
+inline msfl_graph_edge_info PoseGraphEdgeInfo(int i, int j, const Rigid3d& pose_i, const Rigid3d& pose_j, const msfl_match_uncertainty& unc,
+                                              double scale) {
+  msfl_graph_edge_info e{};
+  const std::array<double, 7> a = pose_i.ToVector7(), b = pose_j.ToVector7();
+  const msfl_status st = msfl_graph_edge_from_uncertainty(i, j, a.data(), b.data(), &unc, scale, &e);
+  if (st != MSFL_OK) throw std::invalid_argument(std::string("msfl_graph_edge_from_uncertainty: ") + msfl_status_string(st));
   return e;
 }
 
@@ -68,6 +80,18 @@ class PoseGraph {
   void AddEdges(const std::vector<msfl_graph_edge>& e) { Check(msfl_graph_add_edges(g_, e.data(), static_cast<int>(e.size())), "msfl_graph_add_edges"); }
   void AddEdge(const msfl_graph_edge& e) { Check(msfl_graph_add_edges(g_, &e, 1), "msfl_graph_add_edges"); }
   void AddFixes(const std::vector<msfl_graph_fix>& f) { Check(msfl_graph_add_fixes(g_, f.data(), static_cast<int>(f.size())), "msfl_graph_add_fixes"); }
+  void AddEdgesInfo(const std::vector<msfl_graph_edge_info>& e) {
+    Check(msfl_graph_add_edges_info(g_, e.data(), static_cast<int>(e.size())), "msfl_graph_add_edges_info");
+  }
+  void AddFixesInfo(const std::vector<msfl_graph_fix_info>& f) {
+    Check(msfl_graph_add_fixes_info(g_, f.data(), static_cast<int>(f.size())), "msfl_graph_add_fixes_info");
+  }
+  // |r|^2 of n factors of one kind (MSFL_GRAPH_FACTOR_*) from `first` on, at the current poses, before the loss
+  std::vector<double> Chi2(int kind, int first, int n) {
+    std::vector<double> out(static_cast<std::size_t>(n > 0 ? n : 0));
+    Check(msfl_graph_factor_chi2(g_, kind, first, n, out.data()), "msfl_graph_factor_chi2");
+    return out;
+  }
   void SetFixed(int node, bool fixed = true) { Check(msfl_graph_set_fixed(g_, node, fixed ? 1 : 0), "msfl_graph_set_fixed"); }   // SetParameterBlockConstant
   int size() const { return msfl_graph_num_nodes(g_); }
   void Clear() { Check(msfl_graph_clear(g_), "msfl_graph_clear"); }

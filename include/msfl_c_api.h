@@ -1012,7 +1012,11 @@ msfl_status msfl_places_query_entries(msfl_places* p, const int* entries /* HOST
        Without a long factor the preconditioner's solve is the step and exactly one CG iteration runs per LM iteration.
        With long factors at most max_cg_iterations run (0: 16 n_long + 8); a solve that ends there hands over its iterate
        and counts in cg_unconverged.
-   Every sum has one stated order (factors per node in the order edges were added, then fixes; totals over fixed-size
+     - information-weighted forms of both factors (msfl_graph_edge_info, msfl_graph_fix_info, further down) carry a full
+       square-root information matrix, built from a registration's msfl_match_uncertainty or a 3 x 3 covariance by
+       msfl_graph_edge_from_uncertainty / msfl_graph_fix_from_covariance; msfl_graph_factor_chi2 reads |r|^2 per factor back.
+   Every sum has one stated order (factors per node in the order edges were added, then fixes, then information edges, then
+   information fixes; totals over fixed-size
    partials in index order) and there are no floating-point atomics: the same records in the same order give the same
    bits, however the add_* calls were chunked.  The object owns a stream and its memory, like msfl_places. */
 typedef struct msfl_graph_config {
@@ -1081,6 +1085,43 @@ msfl_status msfl_graph_optimize(msfl_graph* g, msfl_graph_summary* summary);
    invalid step; cost[k] = the candidate's cost.  *n_out = iterations recorded; MSFL_CAPACITY if that exceeds `capacity`
    (the first `capacity` are written).  Either array may be NULL. */
 msfl_status msfl_graph_get_trace(msfl_graph* g, int* accepted, double* cost, int capacity, int* n_out);
+
+/* Information-weighted factors: the two kinds above with a full square-root information matrix L (row-major, information =
+   L^T L, any rank but zero) in place of the scalar sigmas.  The residual is the pose prior's (msfl_pose_prior) applied to the
+   relative pose:
+     edge: T_ij = T_i^-1 T_j;  qe = conj(z.q) (x) q_ij, negated when qe.w < 0;  e = [t_ij - z.t ; 2 qe.xyz];  r = L e   (6 rows)
+     fix:  r = L3 ((1 - t) t_i + t t_j - p)                                                                          (3 rows)
+   so L^T L is the inverse covariance of the measurement z in the tangent [dt ; dtheta] with z.t + dt, z.q (x) dq(dtheta): the
+   tangent convention of msfl_match_uncertainty.information.  A zero row of L is a direction the factor does not pull along.
+   HuberLoss(huber_delta) applies to |r|^2 as for the other kinds.  With L = diag(1/st x 3, 1/(2 sr) x 3) the cost of an
+   information edge equals that of msfl_graph_edge {sr, st} at any poses (the Jacobians differ: the old residual is T_ij^-1 Z,
+   this one Z^-1 T_ij).
+   Factors are numbered edges, fixes, information edges, information fixes, each kind in the order added; sums per node follow
+   that numbering.  Information edges count against max_edges together with plain edges, information fixes against max_fixes
+   together with plain fixes.  A graph without an information factor launches and allocates nothing more than before.
+   Refusals as for the plain adders; an L whose entries are all zero is MSFL_BAD_ARG too. */
+typedef struct msfl_graph_edge_info { int i, j; double z[7]; double sqrt_information[36]; } msfl_graph_edge_info;   /* 352 bytes */
+typedef struct msfl_graph_fix_info { int i, j; double t; double p[3]; double sqrt_information[9]; } msfl_graph_fix_info; /* 112 bytes */
+msfl_status msfl_graph_add_edges_info(msfl_graph* g, const msfl_graph_edge_info* edges /* HOST */, int n);
+msfl_status msfl_graph_add_fixes_info(msfl_graph* g, const msfl_graph_fix_info* fixes /* HOST */, int n);
+/* From a registration to an edge; pure host arithmetic, no GPU call.  pose_j is the registered pose and `unc` its record
+   (information about pose_j: t += dt in the parent frame, q = q dq(dtheta) in the body frame); pose_i is taken as exact.
+   z = T_i^-1 T_j; row k of L is sqrt(eigenvalues[k] / scale) v_k^T diag(R_i, I) for k >= n_degenerate and zero below, so
+   L^T L = diag(R_i^T, I) H_kept diag(R_i, I) / scale: a registration that is blind along a corridor gives an edge that does not
+   pull along it.  `scale` is the variance factor (unc->sigma2, or a sensor model's), finite and > 0.  For a registration whose
+   record is about the relative pose itself pass pose_i = identity and pose_j = the relative pose.  MSFL_BAD_ARG, *out
+   untouched: unc->valid == 0, n_degenerate == 6, a non-finite input, a zero quaternion, i == j or a negative index. */
+msfl_status msfl_graph_edge_from_uncertainty(int i, int j, const double pose_i[7], const double pose_j[7],
+                                             const msfl_match_uncertainty* unc, double scale, msfl_graph_edge_info* out);
+/* L3 = the upper Cholesky factor of covariance^-1 (row-major 3 x 3, as a GPS receiver reports it).  MSFL_BAD_ARG, *out
+   untouched: a covariance that is not finite or not symmetric positive definite, t outside [0, 1], i == j. */
+msfl_status msfl_graph_fix_from_covariance(int i, int j, double t, const double p[3], const double covariance[9],
+                                           msfl_graph_fix_info* out);
+/* |r|^2 of factors first .. first + n of one kind at the current poses, before the loss; changes nothing, like msfl_graph_cost.
+   With information weights this is a chi-square with 6 (3 for a fix) degrees of freedom under the model: the number a loop
+   closer thresholds on.  MSFL_BAD_ARG for an unknown kind or a range outside that kind's factors. */
+enum { MSFL_GRAPH_FACTOR_EDGE = 0, MSFL_GRAPH_FACTOR_FIX = 1, MSFL_GRAPH_FACTOR_EDGE_INFO = 2, MSFL_GRAPH_FACTOR_FIX_INFO = 3 };
+msfl_status msfl_graph_factor_chi2(msfl_graph* g, int kind, int first, int n, double* out /* HOST */);
 
 #ifdef __cplusplus
 } /* extern "C" */

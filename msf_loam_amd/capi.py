@@ -42,6 +42,8 @@ EXPORTED = [
     "msfl_graph_last_error", "msfl_graph_clear", "msfl_graph_num_nodes", "msfl_graph_add_nodes", "msfl_graph_add_edges",
     "msfl_graph_add_fixes", "msfl_graph_set_fixed", "msfl_graph_set_poses", "msfl_graph_get_poses", "msfl_graph_cost",
     "msfl_graph_optimize", "msfl_graph_get_trace",
+    "msfl_graph_add_edges_info", "msfl_graph_add_fixes_info", "msfl_graph_edge_from_uncertainty", "msfl_graph_fix_from_covariance",
+    "msfl_graph_factor_chi2",
 ]
 
 
@@ -1355,6 +1357,12 @@ GRAPH_EDGE_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("z", np.float64,
 GRAPH_FIX_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("t", np.float64), ("p", np.float64, (3,)), ("st", np.float64)])
 assert GRAPH_EDGE_DTYPE.itemsize == 80 and GRAPH_FIX_DTYPE.itemsize == 48 and C.sizeof(GraphSummary) == 48
 
+# msfl_graph_edge_info / msfl_graph_fix_info: the same factors with a full square-root information matrix (row-major)
+GRAPH_EDGE_INFO_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("z", np.float64, (7,)), ("sqrt_information", np.float64, (6, 6))])
+GRAPH_FIX_INFO_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("t", np.float64), ("p", np.float64, (3,)), ("sqrt_information", np.float64, (3, 3))])
+assert GRAPH_EDGE_INFO_DTYPE.itemsize == 352 and GRAPH_FIX_INFO_DTYPE.itemsize == 112
+GRAPH_FACTOR_EDGE, GRAPH_FACTOR_FIX, GRAPH_FACTOR_EDGE_INFO, GRAPH_FACTOR_FIX_INFO = range(4)
+
 GRAPH_TERMINATION = ("empty", "gradient", "max_iterations", "min_radius", "invalid_steps", "parameter", "function")
 
 
@@ -1373,6 +1381,31 @@ def relative_pose(Ti, Tj):
     return np.concatenate([rot(qi, Tj[:3] - Ti[:3]), q])
 
 
+def edge_from_uncertainty(i, j, pose_i, pose_j, unc, scale, out=None):
+    """msfl_graph_edge_from_uncertainty: the information edge (one record of GRAPH_EDGE_INFO_DTYPE) a registration gives.  pose_j is the
+    registered pose, `unc` its record (a MatchUncertainty or one element of UNCERTAINTY_DTYPE), `scale` the variance factor (unc's
+    sigma2, or a sensor model's).  Host arithmetic only.  Returns (status, record); a refusal leaves the record (`out`) untouched."""
+    lib = load()
+    rec = np.zeros(1, GRAPH_EDGE_INFO_DTYPE) if out is None else out
+    if not isinstance(unc, MatchUncertainty):
+        u = np.ascontiguousarray(np.asarray(unc, UNCERTAINTY_DTYPE).reshape(1))
+        unc = MatchUncertainty.from_buffer_copy(u.tobytes())
+    pi, pj = (np.ascontiguousarray(np.asarray(p, np.float64).reshape(7)) for p in (pose_i, pose_j))
+    s = lib.msfl_graph_edge_from_uncertainty(C.c_int(int(i)), C.c_int(int(j)), _vp(pi), _vp(pj), C.byref(unc), C.c_double(float(scale)), _vp(rec))
+    return int(s), rec
+
+
+def fix_from_covariance(i, j, t, p, covariance, out=None):
+    """msfl_graph_fix_from_covariance: the information fix (one record of GRAPH_FIX_INFO_DTYPE) of a position with a 3 x 3 covariance.
+    Returns (status, record); a refusal leaves the record (`out`) untouched."""
+    lib = load()
+    rec = np.zeros(1, GRAPH_FIX_INFO_DTYPE) if out is None else out
+    pp = np.ascontiguousarray(np.asarray(p, np.float64).reshape(3))
+    cov = np.ascontiguousarray(np.asarray(covariance, np.float64).reshape(9))
+    s = lib.msfl_graph_fix_from_covariance(C.c_int(int(i)), C.c_int(int(j)), C.c_double(float(t)), _vp(pp), _vp(cov), _vp(rec))
+    return int(s), rec
+
+
 class PoseGraph:
     """Owns one msfl_graph: poses on the device, relative-pose edges and position fixes, and the trust-region solve over them
     (msfl_graph_*), independent of any Handle.  Keyword arguments are the fields of msfl_graph_config."""
@@ -1389,6 +1422,7 @@ class PoseGraph:
                 raise TypeError("unknown msfl_graph_config field %r" % (k,))
             setattr(self.config, k, v)
         self.p = C.c_void_p()
+        self._count = [0, 0, 0, 0]               # factors per kind (GRAPH_FACTOR_*), for chi2's default range
         s = self.lib.msfl_graph_create(C.byref(self.config), C.c_int(device), C.byref(self.p))
         if s != OK:
             raise MsflError(s, "msfl_graph_create", "(a config outside its limits, or no GPU: there is no CPU fallback)")
@@ -1420,6 +1454,7 @@ class PoseGraph:
 
     def clear(self):
         self._check(self.lib.msfl_graph_clear(self.p), "msfl_graph_clear")
+        self._count = [0, 0, 0, 0]
 
     def num_nodes(self):
         return int(self.lib.msfl_graph_num_nodes(self.p))
@@ -1455,13 +1490,60 @@ class PoseGraph:
         rec["i"], rec["j"], rec["t"], rec["p"], rec["st"] = i, j, t, np.asarray(p, np.float64).reshape(len(i), 3), st
         return rec
 
+    @staticmethod
+    def edges_info(i, j, z, sqrt_information):
+        """Records of GRAPH_EDGE_INFO_DTYPE from index arrays, (n, 7) measurements and (n, 6, 6) (or one 6 x 6) square-root information."""
+        i = np.atleast_1d(np.asarray(i, np.int32))
+        rec = np.zeros(len(i), GRAPH_EDGE_INFO_DTYPE)
+        rec["i"], rec["j"], rec["z"] = i, j, np.asarray(z, np.float64).reshape(len(i), 7)
+        rec["sqrt_information"] = np.broadcast_to(np.asarray(sqrt_information, np.float64), (len(i), 6, 6))
+        return rec
+
+    @staticmethod
+    def fixes_info(i, j, t, p, sqrt_information):
+        """Records of GRAPH_FIX_INFO_DTYPE."""
+        i = np.atleast_1d(np.asarray(i, np.int32))
+        rec = np.zeros(len(i), GRAPH_FIX_INFO_DTYPE)
+        rec["i"], rec["j"], rec["t"], rec["p"] = i, j, t, np.asarray(p, np.float64).reshape(len(i), 3)
+        rec["sqrt_information"] = np.broadcast_to(np.asarray(sqrt_information, np.float64), (len(i), 3, 3))
+        return rec
+
+    def add_edges_info(self, rec, allow=()):
+        rec = np.ascontiguousarray(rec, GRAPH_EDGE_INFO_DTYPE)
+        s = self._check(self.lib.msfl_graph_add_edges_info(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_edges_info", allow)
+        if s == OK:
+            self._count[GRAPH_FACTOR_EDGE_INFO] += len(rec)
+        return s
+
+    def add_fixes_info(self, rec, allow=()):
+        rec = np.ascontiguousarray(rec, GRAPH_FIX_INFO_DTYPE)
+        s = self._check(self.lib.msfl_graph_add_fixes_info(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_fixes_info", allow)
+        if s == OK:
+            self._count[GRAPH_FACTOR_FIX_INFO] += len(rec)
+        return s
+
+    def chi2(self, kind, first=0, n=None, allow=()):
+        """|r|^2 of factors first .. first + n (default: to the last) of one kind (GRAPH_FACTOR_*) at the current poses, before the loss."""
+        if n is None:
+            n = self._count[int(kind)] - int(first)
+        out = np.zeros(max(0, int(n)), np.float64)
+        s = self._check(self.lib.msfl_graph_factor_chi2(self.p, C.c_int(int(kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(out)),
+                        "msfl_graph_factor_chi2", allow)
+        return out if s == OK else s
+
     def add_edges(self, rec, allow=()):
         rec = np.ascontiguousarray(rec, GRAPH_EDGE_DTYPE)
-        return self._check(self.lib.msfl_graph_add_edges(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_edges", allow)
+        s = self._check(self.lib.msfl_graph_add_edges(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_edges", allow)
+        if s == OK:
+            self._count[GRAPH_FACTOR_EDGE] += len(rec)
+        return s
 
     def add_fixes(self, rec, allow=()):
         rec = np.ascontiguousarray(rec, GRAPH_FIX_DTYPE)
-        return self._check(self.lib.msfl_graph_add_fixes(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_fixes", allow)
+        s = self._check(self.lib.msfl_graph_add_fixes(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_fixes", allow)
+        if s == OK:
+            self._count[GRAPH_FACTOR_FIX] += len(rec)
+        return s
 
     def set_fixed(self, node, flag=True, allow=()):
         return self._check(self.lib.msfl_graph_set_fixed(self.p, C.c_int(int(node)), C.c_int(1 if flag else 0)), "msfl_graph_set_fixed", allow)

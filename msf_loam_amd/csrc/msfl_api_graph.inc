@@ -5,6 +5,7 @@
 #include "msfl_graph.cuh"   // includes msfl_graph_host.h: GraphStructure, graph_build_structure, graph_levels
 
 static_assert(sizeof(msfl_graph_edge) == 80 && sizeof(msfl_graph_fix) == 48 && sizeof(msfl_graph_summary) == 48, "graph record layout");
+static_assert(sizeof(msfl_graph_edge_info) == 352 && sizeof(msfl_graph_fix_info) == 112, "information factor record layout");
 static_assert(sizeof(GraphState) % 8 == 0, "the trace follows the state record");
 
 struct msfl_graph_s {
@@ -17,6 +18,8 @@ struct msfl_graph_s {
   std::vector<unsigned char> fixed;
   std::vector<msfl_graph_edge> edges;
   std::vector<msfl_graph_fix> fixes;
+  std::vector<msfl_graph_edge_info> edges_info;    // count against max_edges together with `edges`
+  std::vector<msfl_graph_fix_info> fixes_info;     // count against max_fixes together with `fixes`
   bool dirty = true;             // the structure changed since the device copy was built
   GraphStructure gs;
   GraphLevels lv{};
@@ -25,6 +28,8 @@ struct msfl_graph_s {
   std::vector<double> tr_cost;
   DevBuf x, cand;                // double[max_nodes x 7]
   DevBuf ints, data, work;       // structure, factor data, everything the solve works in
+  DevBuf linfo;                  // double[information factors x 36]: their L; allocated by the first call that adds one
+  DevBuf chi;                    // msfl_graph_factor_chi2's result before it goes to the host
   DevBuf state;                  // GraphState, double[max_iter] candidate costs, one double (msfl_graph_cost), int[max_iter] accept list
   PinRing pin;
   PinBuf readback;
@@ -77,7 +82,8 @@ size_t graph_state_bytes(const msfl_graph* g) {
 msfl_status graph_prepare(msfl_graph* g) {
   if (!g->dirty) return MSFL_OK;
   hipStream_t st = g->stream;
-  const int ne = (int)g->edges.size(), nx = (int)g->fixes.size(), nf = ne + nx;
+  const int ne = (int)g->edges.size(), nx = (int)g->fixes.size(), nei = (int)g->edges_info.size(), nxi = (int)g->fixes_info.size();
+  const int np = ne + nx, ni = nei + nxi, nf = np + ni;      // factor numbering: edges, fixes, information edges, information fixes
   std::vector<int> ij(2 * (size_t)nf);
   std::vector<double> data(9 * (size_t)std::max(1, nf));
   for (int k = 0; k < ne; k++) {
@@ -92,6 +98,20 @@ msfl_status graph_prepare(msfl_graph* g) {
     ij[2 * (ne + k)] = f.i; ij[2 * (ne + k) + 1] = f.j;
     double* d = data.data() + 9 * (size_t)(ne + k);
     d[0] = f.t; d[1] = f.p[0]; d[2] = f.p[1]; d[3] = f.p[2]; d[4] = f.st; d[5] = d[6] = d[7] = d[8] = 0.0;
+  }
+  std::vector<double> linfo(36 * (size_t)ni, 0.0);
+  for (int k = 0; k < nei; k++) {
+    const msfl_graph_edge_info& e = g->edges_info[k];
+    ij[2 * (np + k)] = e.i; ij[2 * (np + k) + 1] = e.j;
+    std::copy(e.z, e.z + 7, data.data() + 9 * (size_t)(np + k));
+    std::copy(e.sqrt_information, e.sqrt_information + 36, linfo.data() + 36 * (size_t)k);
+  }
+  for (int k = 0; k < nxi; k++) {
+    const msfl_graph_fix_info& f = g->fixes_info[k];
+    ij[2 * (np + nei + k)] = f.i; ij[2 * (np + nei + k) + 1] = f.j;
+    double* d = data.data() + 9 * (size_t)(np + nei + k);
+    d[0] = f.t; d[1] = f.p[0]; d[2] = f.p[1]; d[3] = f.p[2];
+    std::copy(f.sqrt_information, f.sqrt_information + 9, linfo.data() + 36 * (size_t)(nei + k));
   }
   GraphStructure& s = g->gs;
   graph_build_structure(g->n_nodes, g->fixed.data(), ij, &s);
@@ -109,6 +129,10 @@ msfl_status graph_prepare(msfl_graph* g) {
   HIPCHK(g, g->pin.upload(g->ints.p, ints.data(), ints.size() * sizeof(int), st));
   HIPCHK(g, g->data.reserve(data.size() * sizeof(double)));
   HIPCHK(g, g->pin.upload(g->data.p, data.data(), data.size() * sizeof(double), st));
+  if (ni) {
+    HIPCHK(g, g->linfo.reserve(linfo.size() * sizeof(double)));
+    HIPCHK(g, g->pin.upload(g->linfo.p, linfo.data(), linfo.size() * sizeof(double), st));
+  }
   const GraphLevels& v = g->lv;
   const size_t blocks = (size_t)v.off[v.count - 1] + 1, inv = (size_t)v.ioff[v.count - 1] + 1, Fz = (size_t)std::max(1, F), nfz = (size_t)std::max(1, nf);
   const size_t n_part = (Fz + kGraphVec - 1) / kGraphVec;
@@ -116,7 +140,8 @@ msfl_status graph_prepare(msfl_graph* g) {
   HIPCHK(g, g->work.reserve(want * sizeof(double)));
   GraphDev& d = g->dev;
   d = GraphDev{};
-  d.n_nodes = N; d.n_free = F; d.n_edges = ne; d.n_factors = nf;
+  d.n_nodes = N; d.n_free = F; d.n_edges = ne; d.n_factors = nf; d.n_plain = np; d.n_einfo = nei;
+  d.fac_L = g->linfo.as<double>();
   const int* ip = g->ints.as<int>();
   d.free_of = ip + at[0]; d.node_of = ip + at[1]; d.adj_off = ip + at[2]; d.adj = ip + at[3]; d.ladj_off = ip + at[4]; d.ladj = ip + at[5];
   d.fac_ij = ip + at[6];
@@ -142,6 +167,19 @@ msfl_status graph_prepare(msfl_graph* g) {
 template <class K, class... A>
 void graph_launch(hipStream_t st, K kernel, int items, int block, A... args) {
   hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1, div_up(items, block))), dim3(block), 0, st, args...);
+}
+
+// the factor kernels: the plain kinds and, only when the graph holds one, the information kinds
+void graph_enqueue_linearize(msfl_graph* g, double huber) {
+  const GraphDev& d = g->dev;
+  if (d.n_plain) graph_launch(g->stream, graph_linearize_kernel, d.n_plain, kGraphBlock, d, huber);
+  if (d.n_factors > d.n_plain) graph_launch(g->stream, graph_linearize_info_kernel, d.n_factors - d.n_plain, kGraphBlock, d, huber);
+}
+template <bool kModel>
+void graph_enqueue_cost(msfl_graph* g, const double* x, double huber) {
+  const GraphDev& d = g->dev;
+  if (d.n_plain) graph_launch(g->stream, graph_cost_kernel<kModel>, d.n_plain, kGraphBlock, d, x, huber);
+  if (d.n_factors > d.n_plain) graph_launch(g->stream, graph_cost_info_kernel<kModel>, d.n_factors - d.n_plain, kGraphBlock, d, x, huber);
 }
 
 // z = T^-1 r: the right-hand-side half of the cyclic reduction
@@ -224,7 +262,7 @@ int msfl_graph_num_nodes(const msfl_graph* g) { return g ? g->n_nodes : 0; }
 msfl_status msfl_graph_clear(msfl_graph* g) {
   msfl_status s = enter(g); if (s) return s;
   HIPCHK(g, hipStreamSynchronize(g->stream));
-  g->n_nodes = 0; g->fixed.clear(); g->edges.clear(); g->fixes.clear(); g->tr_accepted.clear(); g->tr_cost.clear();
+  g->n_nodes = 0; g->fixed.clear(); g->edges.clear(); g->fixes.clear(); g->edges_info.clear(); g->fixes_info.clear(); g->tr_accepted.clear(); g->tr_cost.clear();
   g->dirty = true;
   return MSFL_OK;
 }
@@ -267,7 +305,8 @@ msfl_status msfl_graph_add_nodes(msfl_graph* g, const double* poses, int n, msfl
 msfl_status msfl_graph_add_edges(msfl_graph* g, const msfl_graph_edge* edges, int n) {
   msfl_status s = enter(g); if (s) return s;
   if (n < 0 || (n > 0 && !edges)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges: null array or negative count");
-  if ((long long)g->edges.size() + n > g->cfg.max_edges) return fail(g, MSFL_CAPACITY, "msfl_graph_add_edges: the batch does not fit max_edges; nothing added");
+  if ((long long)g->edges.size() + (long long)g->edges_info.size() + n > g->cfg.max_edges)
+    return fail(g, MSFL_CAPACITY, "msfl_graph_add_edges: the batch does not fit max_edges; nothing added");
   for (int k = 0; k < n; k++) {
     const msfl_graph_edge& e = edges[k];
     if (e.i < 0 || e.j < 0 || e.i >= g->n_nodes || e.j >= g->n_nodes || e.i == e.j)
@@ -283,7 +322,8 @@ msfl_status msfl_graph_add_edges(msfl_graph* g, const msfl_graph_edge* edges, in
 msfl_status msfl_graph_add_fixes(msfl_graph* g, const msfl_graph_fix* fixes, int n) {
   msfl_status s = enter(g); if (s) return s;
   if (n < 0 || (n > 0 && !fixes)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes: null array or negative count");
-  if ((long long)g->fixes.size() + n > g->cfg.max_fixes) return fail(g, MSFL_CAPACITY, "msfl_graph_add_fixes: the batch does not fit max_fixes; nothing added");
+  if ((long long)g->fixes.size() + (long long)g->fixes_info.size() + n > g->cfg.max_fixes)
+    return fail(g, MSFL_CAPACITY, "msfl_graph_add_fixes: the batch does not fit max_fixes; nothing added");
   for (int k = 0; k < n; k++) {
     const msfl_graph_fix& f = fixes[k];
     if (f.i < 0 || f.j < 0 || f.i >= g->n_nodes || f.j >= g->n_nodes || f.i == f.j)
@@ -294,6 +334,66 @@ msfl_status msfl_graph_add_fixes(msfl_graph* g, const msfl_graph_fix* fixes, int
   }
   g->fixes.insert(g->fixes.end(), fixes, fixes + n);
   if (n) g->dirty = true;
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_add_edges_info(msfl_graph* g, const msfl_graph_edge_info* edges, int n) {
+  msfl_status s = enter(g); if (s) return s;
+  if (n < 0 || (n > 0 && !edges)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges_info: null array or negative count");
+  if ((long long)g->edges.size() + (long long)g->edges_info.size() + n > g->cfg.max_edges)
+    return fail(g, MSFL_CAPACITY, "msfl_graph_add_edges_info: plain and information edges together do not fit max_edges; nothing added");
+  for (int k = 0; k < n; k++) {
+    const msfl_graph_edge_info& e = edges[k];
+    if (e.i < 0 || e.j < 0 || e.i >= g->n_nodes || e.j >= g->n_nodes || e.i == e.j)
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges_info: a node index out of range or i == j; nothing added");
+    if (!graph_pose_ok(e.z) || !graph_sqrt_information_ok(e.sqrt_information, 36))
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges_info: a non-finite value, a zero quaternion or an all-zero sqrt_information; nothing added");
+  }
+  if (n == 0) return MSFL_OK;
+  HIPCHK(g, g->linfo.reserve(36 * sizeof(double) * (g->edges_info.size() + g->fixes_info.size() + (size_t)n)));
+  g->edges_info.insert(g->edges_info.end(), edges, edges + n);
+  g->dirty = true;
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_add_fixes_info(msfl_graph* g, const msfl_graph_fix_info* fixes, int n) {
+  msfl_status s = enter(g); if (s) return s;
+  if (n < 0 || (n > 0 && !fixes)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes_info: null array or negative count");
+  if ((long long)g->fixes.size() + (long long)g->fixes_info.size() + n > g->cfg.max_fixes)
+    return fail(g, MSFL_CAPACITY, "msfl_graph_add_fixes_info: plain and information fixes together do not fit max_fixes; nothing added");
+  for (int k = 0; k < n; k++) {
+    const msfl_graph_fix_info& f = fixes[k];
+    if (f.i < 0 || f.j < 0 || f.i >= g->n_nodes || f.j >= g->n_nodes || f.i == f.j)
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes_info: a node index out of range or i == j; nothing added");
+    if (!std::isfinite(f.t) || !std::isfinite(f.p[0]) || !std::isfinite(f.p[1]) || !std::isfinite(f.p[2]) || !(f.t >= 0.0 && f.t <= 1.0) ||
+        !graph_sqrt_information_ok(f.sqrt_information, 9))
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes_info: a non-finite value, t outside [0, 1] or an all-zero sqrt_information; nothing added");
+  }
+  if (n == 0) return MSFL_OK;
+  HIPCHK(g, g->linfo.reserve(36 * sizeof(double) * (g->edges_info.size() + g->fixes_info.size() + (size_t)n)));
+  g->fixes_info.insert(g->fixes_info.end(), fixes, fixes + n);
+  g->dirty = true;
+  return MSFL_OK;
+}
+
+// pure host arithmetic (msfl_graph_host.h): no graph object, no GPU call
+msfl_status msfl_graph_edge_from_uncertainty(int i, int j, const double* pose_i, const double* pose_j, const msfl_match_uncertainty* unc,
+                                             double scale, msfl_graph_edge_info* out) {
+  if (!pose_i || !pose_j || !unc || !out || i < 0 || j < 0 || i == j || !unc->valid) return MSFL_BAD_ARG;
+  msfl_graph_edge_info e{};
+  e.i = i; e.j = j;
+  if (!graph_edge_from_eigen(pose_i, pose_j, unc->eigenvalues, unc->eigenvectors, unc->n_degenerate, scale, e.z, e.sqrt_information))
+    return MSFL_BAD_ARG;
+  *out = e;
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_fix_from_covariance(int i, int j, double t, const double* p, const double* covariance, msfl_graph_fix_info* out) {
+  if (!p || !covariance || !out || i < 0 || j < 0 || i == j || !(t >= 0.0 && t <= 1.0) || !graph_all_finite(p, 3)) return MSFL_BAD_ARG;
+  msfl_graph_fix_info f{};
+  f.i = i; f.j = j; f.t = t; f.p[0] = p[0]; f.p[1] = p[1]; f.p[2] = p[2];
+  if (!graph_fix_from_covariance(covariance, f.sqrt_information)) return MSFL_BAD_ARG;
+  *out = f;
   return MSFL_OK;
 }
 
@@ -332,12 +432,30 @@ msfl_status msfl_graph_cost(msfl_graph* g, double* cost) {
   if (g->dev.n_factors == 0) return MSFL_OK;
   hipStream_t st = g->stream;
   double* d_out = g->dev.tr_cost + std::max(1, g->cfg.max_num_iterations);
-  graph_launch(st, graph_cost_kernel<false>, g->dev.n_factors, kGraphBlock, g->dev, (const double*)g->dev.x, g->cfg.huber_delta);
+  graph_enqueue_cost<false>(g, g->dev.x, g->cfg.huber_delta);
   graph_launch(st, graph_cost_total_kernel, 1, kGraphVec, g->dev, d_out);
   HIPCHK(g, hipGetLastError());
   HIPCHK(g, hipMemcpyAsync(g->readback.p, d_out, sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(g, hipStreamSynchronize(st));
   *cost = *g->readback.as<double>();
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_factor_chi2(msfl_graph* g, int kind, int first, int n, double* out) {
+  msfl_status s = enter(g); if (s) return s;
+  const int count[4] = {(int)g->edges.size(), (int)g->fixes.size(), (int)g->edges_info.size(), (int)g->fixes_info.size()};
+  if (kind < 0 || kind > 3 || first < 0 || n < 0 || (long long)first + n > count[kind] || (n > 0 && !out))
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_factor_chi2: unknown kind, range outside the factors of that kind or null result");
+  if (n == 0) return MSFL_OK;
+  s = graph_prepare(g); if (s) return s;
+  int k0 = first;
+  for (int c = 0; c < kind; c++) k0 += count[c];
+  hipStream_t st = g->stream;
+  HIPCHK(g, g->chi.reserve((size_t)n * sizeof(double)));
+  graph_launch(st, graph_chi2_kernel, n, kGraphBlock, g->dev, k0, n, g->chi.as<double>());
+  HIPCHK(g, hipGetLastError());
+  HIPCHK(g, hipMemcpyAsync(out, g->chi.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(g, hipStreamSynchronize(st));
   return MSFL_OK;
 }
 
@@ -357,13 +475,13 @@ msfl_status msfl_graph_optimize(msfl_graph* g, msfl_graph_summary* summary) {
   init.radius = o.radius0; init.decrease_factor = 2.0; init.step_successful = 1; init.first = 1;
   HIPCHK(g, g->pin.upload(g->state.p, &init, sizeof(init), st));
   HIPCHK(g, hipMemcpyAsync(d.cand, d.x, (size_t)d.n_nodes * 7 * sizeof(double), hipMemcpyDeviceToDevice, st));
-  const int F = d.n_free, nf = d.n_factors, n_part = div_up(F, kGraphVec);
+  const int F = d.n_free, n_part = div_up(F, kGraphVec);
   const int direct = g->gs.n_long == 0;      // A == T: the preconditioner's solve is the step, one CG iteration
   const int cap = direct ? 1 : (g->cfg.max_cg_iterations > 0 ? g->cfg.max_cg_iterations : 16 * g->gs.n_long + 8);
   GraphState now{};
   for (int it = 0;; it++) {
     graph_launch(st, graph_commit_kernel, d.n_nodes * 7, kGraphVec, d);
-    graph_launch(st, graph_linearize_kernel, nf, kGraphBlock, d, o.huber);
+    graph_enqueue_linearize(g, o.huber);
     graph_launch(st, graph_assemble_kernel, F, kGraphBlock, d);
     if (it == 0) graph_launch(st, graph_scale_kernel, F * 6, kGraphVec, d, o.jacobi);
     graph_launch(st, graph_tr_begin_kernel, 1, kGraphVec, d, o);
@@ -384,7 +502,7 @@ msfl_status msfl_graph_optimize(msfl_graph* g, msfl_graph_summary* summary) {
       }
       graph_launch(st, graph_cg_end_kernel, 1, kGraphVec, d, n_part, o.cg_tol, direct);
       graph_launch(st, graph_plus_kernel, F, kGraphVec, d);
-      graph_launch(st, graph_cost_kernel<true>, nf, kGraphBlock, d, (const double*)d.cand, o.huber);
+      graph_enqueue_cost<true>(g, d.cand, o.huber);
       graph_launch(st, graph_tr_kernel, 1, kGraphVec, d, o);
     }
     HIPCHK(g, hipGetLastError());

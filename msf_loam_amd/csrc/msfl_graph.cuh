@@ -9,6 +9,10 @@
 //   - a kernel that finds GraphState::done (or cg_done) set returns at once: the host enqueues a fixed launch pattern.
 // One lane owns one factor or one node; 6 x 6 blocks live in registers (fully unrolled loops), so the block kernels run 64 lanes
 // per workgroup and take what VGPRs they need.
+//
+// Factors are numbered edges, fixes, information edges, information fixes.  The first two kinds (k < n_plain) are the reference's and
+// keep their kernels; the information kinds (a full square-root information matrix L per factor) have kernels of their own over
+// [n_plain, n_factors), launched only when the graph holds one.  Everything behind the 78-double linearised record is generic.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,7 +42,7 @@ struct GraphDev {
   int n_nodes, n_free, n_edges, n_factors;
   const int* free_of;                // [nodes]: free index or -1
   const int* node_of;                // [free]
-  const int* adj_off; const int* adj;       // per free node: 2 * factor + side, edges in insertion order, then fixes
+  const int* adj_off; const int* adj;       // per free node: 2 * factor + side, in the factor numbering (each kind in insertion order)
   const int* ladj_off; const int* ladj;     // the long factors among them
   const int* fac_ij;                 // [factors x 2]: node indices
   const double* fac_data;            // [factors x 9]: edge z[7], sr, st; fix t, p[3], st
@@ -53,6 +57,8 @@ struct GraphDev {
   double* part;                      // [2 x workgroups]: partials of p.q, of r.z
   GraphState* st;
   int* tr_accepted; double* tr_cost; // [max_iter]
+  int n_plain, n_einfo;              // edges + fixes; information edges (factors n_plain + n_einfo .. are information fixes)
+  const double* fac_L;               // [information factors x 36]: L row-major (6 x 6; a fix's 3 x 3 in the first 9); their fac_data: edge z[7]; fix t, p[3]
 };
 
 // ---- sums with one stated order --------------------------------------------------------------------------------------
@@ -273,7 +279,7 @@ __global__ __launch_bounds__(kGraphVec) void graph_commit_kernel(GraphDev G) {
 __global__ __launch_bounds__(kGraphBlock) void graph_linearize_kernel(GraphDev G, double huber) {
   if (G.st->done) return;
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k >= G.n_factors) return;
+  if (k >= G.n_plain) return;
   double r[6], Ji[36], Jj[36], hr;
   graph_factor<true>(G, G.x, k, r, Ji, Jj);
   const double s = graph_huber(r, huber, &hr);
@@ -285,12 +291,12 @@ __global__ __launch_bounds__(kGraphBlock) void graph_linearize_kernel(GraphDev G
   G.fcost[k] = hr;
 }
 
-// cost of every block at `x` into fcost; with kModel also the block's share of -m . (r + m / 2), m = Js step
+// cost of every plain block at `x` into fcost; with kModel also the block's share of -m . (r + m / 2), m = Js step
 template <bool kModel>
 __global__ __launch_bounds__(kGraphBlock) void graph_cost_kernel(GraphDev G, const double* __restrict__ x, double huber) {
   if (kModel && G.st->done) return;
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k >= G.n_factors) return;
+  if (k >= G.n_plain) return;
   double r[6], hr;
   graph_factor<false>(G, x, k, r, nullptr, nullptr);
   (void)graph_huber(r, huber, &hr);
@@ -311,6 +317,182 @@ __global__ __launch_bounds__(kGraphBlock) void graph_cost_kernel(GraphDev G, con
 #pragma unroll
   for (int c = 0; c < 6; c++) s += m[c] * (Jk[72 + c] + 0.5 * m[c]);
   G.fmodel[k] = -s;
+}
+
+// ---- information factors (docs/kernels/graph.md): r = L e with a full square-root information matrix per factor -----------------------
+// information edge k: e = [R_i^T (t_j - t_i) - z.t ; 2 s vec(qe)], qe = conj(z.q) (x) conj(q_i) (x) q_j, s = -1 when qe.w < 0.
+// With kJac also the three 3 x 3 blocks de/d. is made of (row-major): Rt = R_i^T, B = 2 R_i^T [t_j - t_i]x and M, whose column c is
+// 2 s vec(conj(z.q) (x) conj(q_i) (x) [e_c, 0] (x) q_j):
+//   de/d(dt_i, d_i) = [-Rt  B ; 0  -M],   de/d(dt_j, d_j) = [Rt  0 ; 0  M].
+// Every product that holds z.q holds it once, so -z.q negates qe and M's columns exactly and s undoes it: the same bits.
+template <bool kJac>
+__device__ __forceinline__ void graph_info_edge_error(const GraphDev& G, const double* __restrict__ x, int k, double* e, double* Rt, double* B, double* M) {
+  const double* d = G.fac_data + (size_t)k * 9;
+  const double* xi = x + (size_t)G.fac_ij[2 * k] * 7; const double* xj = x + (size_t)G.fac_ij[2 * k + 1] * 7;
+  const double ci[4] = {-xi[3], -xi[4], -xi[5], xi[6]}, cz[4] = {-d[3], -d[4], -d[5], d[6]}, qj[4] = {xj[3], xj[4], xj[5], xj[6]};
+  const double u[3] = {xj[0] - xi[0], xj[1] - xi[1], xj[2] - xi[2]};
+  double tij[3], A[4], qe[4];
+  gq_rot(ci, u, tij);
+  gq_mul(cz, ci, A);
+  gq_mul(A, qj, qe);
+  const double s2 = qe[3] < 0.0 ? -2.0 : 2.0;
+#pragma unroll
+  for (int c = 0; c < 3; c++) { e[c] = tij[c] - d[c]; e[3 + c] = s2 * qe[c]; }
+  if (!kJac) return;
+  double R[9];
+  gq_to_R(xi + 3, R);
+  const double S[9] = {0.0, -2.0 * u[2], 2.0 * u[1], 2.0 * u[2], 0.0, -2.0 * u[0], -2.0 * u[1], 2.0 * u[0], 0.0};       // 2 [u]x
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      Rt[i * 3 + j] = R[j * 3 + i];
+      double b = 0.0;
+#pragma unroll
+      for (int m = 0; m < 3; m++) b += R[m * 3 + i] * S[m * 3 + j];
+      B[i * 3 + j] = b;
+    }
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const double ec[4] = {c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0, 0.0};
+    double t1[4], t2[4];
+    gq_mul(A, ec, t1);
+    gq_mul(t1, qj, t2);
+#pragma unroll
+    for (int i = 0; i < 3; i++) M[i * 3 + c] = s2 * t2[i];
+  }
+}
+// information fix k: e = (1 - t) t_i + t t_j - p
+__device__ __forceinline__ void graph_info_fix_error(const GraphDev& G, const double* __restrict__ x, int k, double* e) {
+  const double* d = G.fac_data + (size_t)k * 9;
+  const double* xi = x + (size_t)G.fac_ij[2 * k] * 7; const double* xj = x + (size_t)G.fac_ij[2 * k + 1] * 7;
+#pragma unroll
+  for (int c = 0; c < 3; c++) e[c] = (1.0 - d[0]) * xi[c] + d[0] * xj[c] - d[1 + c];
+}
+// residual of information factor m (factor n_plain + m) at poses `x`, before the corrector; rows 3..5 of a fix are zero
+__device__ __forceinline__ void graph_info_residual(const GraphDev& G, const double* __restrict__ x, int m, double* r) {
+  const int k = G.n_plain + m;
+  const double* __restrict__ L = G.fac_L + (size_t)m * 36;
+  if (m >= G.n_einfo) {
+    double e[3];
+    graph_info_fix_error(G, x, k, e);
+#pragma unroll
+    for (int i = 0; i < 3; i++) { r[i] = L[i * 3] * e[0] + L[i * 3 + 1] * e[1] + L[i * 3 + 2] * e[2]; r[3 + i] = 0.0; }
+    return;
+  }
+  double e[6];
+  graph_info_edge_error<false>(G, x, k, e, nullptr, nullptr, nullptr);
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    double s = 0.0;
+#pragma unroll
+    for (int c = 0; c < 6; c++) s += L[i * 6 + c] * e[c];
+    r[i] = s;
+  }
+}
+
+// graph_linearize_kernel for the information factors.  J = L (de/d.) row by row from L's column halves against the 3 x 3 blocks:
+//   Ji row = [-(l Rt), l B - l' M],  Jj row = [l Rt, l' M],  l = L[row][0:3], l' = L[row][3:6];
+// a row is stored as it completes (L is read a second time for that, after the corrector's scale is known).
+__global__ __launch_bounds__(kGraphBlock) void graph_linearize_info_kernel(GraphDev G, double huber) {
+  if (G.st->done) return;
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m >= G.n_factors - G.n_plain) return;
+  const int k = G.n_plain + m;
+  const double* __restrict__ L = G.fac_L + (size_t)m * 36;
+  double* __restrict__ o = G.J + (size_t)k * kGraphJ;
+  double r[6], hr;
+  if (m >= G.n_einfo) {                            // information fix: Ji = (1 - t) L3, Jj = t L3 in the translation columns
+    const double t = G.fac_data[(size_t)k * 9];
+    double e[3];
+    graph_info_fix_error(G, G.x, k, e);
+#pragma unroll
+    for (int i = 0; i < 3; i++) { r[i] = L[i * 3] * e[0] + L[i * 3 + 1] * e[1] + L[i * 3 + 2] * e[2]; r[3 + i] = 0.0; }
+    const double s = graph_huber(r, huber, &hr);
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+      for (int c = 0; c < 6; c++) {
+        const double l = (i < 3 && c < 3) ? s * L[i * 3 + c] : 0.0;
+        o[i * 6 + c] = (1.0 - t) * l; o[36 + i * 6 + c] = t * l;
+      }
+      o[72 + i] = s * r[i];
+    }
+    G.fcost[k] = hr;
+    return;
+  }
+  double e[6], Rt[9], B[9], M[9];
+  graph_info_edge_error<true>(G, G.x, k, e, Rt, B, M);
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    double a = 0.0;
+#pragma unroll
+    for (int c = 0; c < 6; c++) a += L[i * 6 + c] * e[c];
+    r[i] = a;
+  }
+  const double s = graph_huber(r, huber, &hr);
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    const double l0 = s * L[i * 6], l1 = s * L[i * 6 + 1], l2 = s * L[i * 6 + 2], l3 = s * L[i * 6 + 3], l4 = s * L[i * 6 + 4], l5 = s * L[i * 6 + 5];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const double a = l0 * Rt[c] + l1 * Rt[3 + c] + l2 * Rt[6 + c];
+      const double b = l0 * B[c] + l1 * B[3 + c] + l2 * B[6 + c];
+      const double w = l3 * M[c] + l4 * M[3 + c] + l5 * M[6 + c];
+      o[i * 6 + c] = -a; o[i * 6 + 3 + c] = b - w;
+      o[36 + i * 6 + c] = a; o[36 + i * 6 + 3 + c] = w;
+    }
+    o[72 + i] = s * r[i];
+  }
+  G.fcost[k] = hr;
+}
+
+// factor k's share of the model cost change, as graph_cost_kernel<true> computes it from the linearised record (that kernel keeps its
+// own copy: calling this from it moves its register allocation from 104 to 106 VGPRs)
+__device__ __forceinline__ double graph_model_share(const GraphDev& G, int k) {
+  const double* Jk = G.J + (size_t)k * kGraphJ;
+  double m[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int side = 0; side < 2; side++) {
+    const int f = G.free_of[G.fac_ij[2 * k + side]];
+    if (f < 0) continue;
+    double sx[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) sx[c] = G.scale[(size_t)f * 6 + c] * G.xs[(size_t)f * 6 + c];
+    g6_mv<true, false>(Jk + 36 * side, sx, m);
+  }
+  double s = 0.0;
+#pragma unroll
+  for (int c = 0; c < 6; c++) s += m[c] * (Jk[72 + c] + 0.5 * m[c]);
+  return -s;
+}
+
+// graph_cost_kernel for the information factors
+template <bool kModel>
+__global__ __launch_bounds__(kGraphBlock) void graph_cost_info_kernel(GraphDev G, const double* __restrict__ x, double huber) {
+  if (kModel && G.st->done) return;
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m >= G.n_factors - G.n_plain) return;
+  const int k = G.n_plain + m;
+  double r[6], hr;
+  graph_info_residual(G, x, m, r);
+  (void)graph_huber(r, huber, &hr);
+  G.fcost[k] = hr;
+  if (!kModel) return;
+  G.fmodel[k] = graph_model_share(G, k);
+}
+
+// msfl_graph_factor_chi2: |r|^2 of factors first .. first + n at the current poses, before the loss; writes nothing else
+__global__ __launch_bounds__(kGraphBlock) void graph_chi2_kernel(GraphDev G, int first, int n, double* __restrict__ out) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int k = first + i;
+  double r[6], sq = 0.0;
+  if (k < G.n_plain) graph_factor<false>(G, G.x, k, r, nullptr, nullptr);
+  else graph_info_residual(G, G.x, k - G.n_plain, r);
+#pragma unroll
+  for (int c = 0; c < 6; c++) sq += r[c] * r[c];
+  out[i] = sq;
 }
 
 // one free node per lane: gathers its factors in adjacency order into the unscaled diagonal block, the block towards f - 1 and the gradient

@@ -1,8 +1,10 @@
 // Host-side bookkeeping of the pose graph (msfl_api_graph.inc): free-node numbering, adjacency lists, long / chain classification and
-// the level sizes of the cyclic reduction.  Plain C++ over plain arrays, no HIP: tests/cpp/graph_structure_check.cpp runs it under the
-// host sanitizers.
+// the level sizes of the cyclic reduction, and the arithmetic that turns a registration's eigen-decomposition or a 3 x 3 covariance
+// into an information factor.  Plain C++ over plain arrays, no HIP: tests/cpp/graph_structure_check.cpp and
+// tests/cpp/graph_info_check.cpp run it under the host sanitizers.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <vector>
 
@@ -21,7 +23,7 @@ struct GraphStructure {
   std::vector<int> free_of, node_of, adj_off, adj, ladj_off, ladj, fac_ij;
 };
 
-// factor k (edges first, then fixes) joins nodes ij[2k], ij[2k + 1]; adjacency per free node in factor order; a factor is long when both
+// factor k (edges, fixes, information edges, information fixes) joins nodes ij[2k], ij[2k + 1]; adjacency per free node in factor order; a factor is long when both
 // ends are free and more than one apart in the free numbering
 inline void graph_build_structure(int n_nodes, const unsigned char* fixed, const std::vector<int>& ij, GraphStructure* s) {
   const int nf = (int)(ij.size() / 2);
@@ -65,6 +67,126 @@ inline GraphLevels graph_levels(int n) {
     n = (n + 1) / 2;
   }
   return v;
+}
+
+// ---- information factors: the arithmetic of msfl_graph_edge_from_uncertainty / msfl_graph_fix_from_covariance ----------------
+inline bool graph_all_finite(const double* v, int n) {
+  for (int k = 0; k < n; k++)
+    if (!(v[k] - v[k] == 0.0)) return false;          // NaN and +-inf fail
+  return true;
+}
+// a square-root information matrix the graph accepts: finite, not all zero (any rank but zero)
+inline bool graph_sqrt_information_ok(const double* L, int n) {
+  if (!graph_all_finite(L, n)) return false;
+  for (int k = 0; k < n; k++)
+    if (L[k] != 0.0) return true;
+  return false;
+}
+inline void graph_host_quat_to_R(const double* q, double* R) {
+  const double x = q[0], y = q[1], z = q[2], w = q[3];
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - z * w); R[2] = 2 * (x * z + y * w);
+  R[3] = 2 * (x * y + z * w); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - x * w);
+  R[6] = 2 * (x * z - y * w); R[7] = 2 * (y * z + x * w); R[8] = 1 - 2 * (x * x + y * y);
+}
+// z = T_i^-1 T_j for poses [t, qx qy qz qw] with unit quaternions
+inline void graph_host_relative_pose(const double* pi, const double* pj, double* z) {
+  const double a[4] = {-pi[3], -pi[4], -pi[5], pi[6]}, b[4] = {pj[3], pj[4], pj[5], pj[6]};
+  const double v[3] = {pj[0] - pi[0], pj[1] - pi[1], pj[2] - pi[2]};
+  const double c0 = a[1] * v[2] - a[2] * v[1], c1 = a[2] * v[0] - a[0] * v[2], c2 = a[0] * v[1] - a[1] * v[0];
+  z[0] = v[0] + 2.0 * (a[3] * c0 + (a[1] * c2 - a[2] * c1));
+  z[1] = v[1] + 2.0 * (a[3] * c1 + (a[2] * c0 - a[0] * c2));
+  z[2] = v[2] + 2.0 * (a[3] * c2 + (a[0] * c1 - a[1] * c0));
+  z[3] = a[3] * b[0] + b[3] * a[0] + (a[1] * b[2] - a[2] * b[1]);
+  z[4] = a[3] * b[1] + b[3] * a[1] + (a[2] * b[0] - a[0] * b[2]);
+  z[5] = a[3] * b[2] + b[3] * a[2] + (a[0] * b[1] - a[1] * b[0]);
+  z[6] = a[3] * b[3] - (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]);
+}
+// The edge a registration gives.  `eigenvalues` (ascending) / `eigenvectors` (row k = eigenvector k) decompose the information H of
+// pose_j in the tangent [dt (parent frame) ; dtheta (body frame)]; the first n_degenerate pairs are dropped.  z = T_i^-1 T_j, and row k
+// of L is sqrt(lambda_k / scale) v_k^T diag(R_i, I), so that L^T L = diag(R_i^T, I) H_kept diag(R_i, I) / scale in the tangent of z.
+// false (nothing written): a non-finite input, a zero quaternion, scale <= 0, n_degenerate outside [0, 5], a kept eigenvalue < 0, or
+// an L that came out all zero.
+inline bool graph_edge_from_eigen(const double* pose_i, const double* pose_j, const double* eigenvalues, const double* eigenvectors,
+                                  int n_degenerate, double scale, double* z, double* L) {
+  if (!graph_all_finite(pose_i, 7) || !graph_all_finite(pose_j, 7) || !graph_all_finite(eigenvalues, 6) || !graph_all_finite(eigenvectors, 36) ||
+      !graph_all_finite(&scale, 1) || !(scale > 0.0) || n_degenerate < 0 || n_degenerate > 5)
+    return false;
+  if (!(pose_i[3] * pose_i[3] + pose_i[4] * pose_i[4] + pose_i[5] * pose_i[5] + pose_i[6] * pose_i[6] > 0.0) ||
+      !(pose_j[3] * pose_j[3] + pose_j[4] * pose_j[4] + pose_j[5] * pose_j[5] + pose_j[6] * pose_j[6] > 0.0))
+    return false;
+  double R[9], zz[7], LL[36];
+  graph_host_quat_to_R(pose_i + 3, R);
+  graph_host_relative_pose(pose_i, pose_j, zz);
+  for (int k = 0; k < 6; k++) {
+    const double* v = eigenvectors + 6 * k;
+    if (k < n_degenerate) {
+      for (int c = 0; c < 6; c++) LL[6 * k + c] = 0.0;
+      continue;
+    }
+    if (eigenvalues[k] < 0.0) return false;
+    const double s = std::sqrt(eigenvalues[k] / scale);
+    for (int c = 0; c < 3; c++) {
+      LL[6 * k + c] = s * (v[0] * R[c] + v[1] * R[3 + c] + v[2] * R[6 + c]);
+      LL[6 * k + 3 + c] = s * v[3 + c];
+    }
+  }
+  if (!graph_sqrt_information_ok(LL, 36) || !graph_all_finite(zz, 7)) return false;
+  std::copy(zz, zz + 7, z);
+  std::copy(LL, LL + 36, L);
+  return true;
+}
+// L3 = the upper Cholesky factor of covariance^-1 (L3^T L3 = covariance^-1).  false (nothing written) for a covariance that is not
+// finite, not symmetric (beyond 1e-12 of its largest entry) or not positive definite.
+inline bool graph_fix_from_covariance(const double* cov, double* L3) {
+  if (!graph_all_finite(cov, 9)) return false;
+  double big = 0.0;
+  for (int k = 0; k < 9; k++) big = std::max(big, std::fabs(cov[k]));
+  double c[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      if (std::fabs(cov[3 * i + j] - cov[3 * j + i]) > 1e-12 * big) return false;
+      c[3 * i + j] = 0.5 * (cov[3 * i + j] + cov[3 * j + i]);
+    }
+  // covariance = C C^T, C lower; W = C^-1; P = covariance^-1 = W^T W; P = G G^T, G lower; L3 = G^T
+  double C[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int stage = 0; stage < 2; stage++) {
+    double* a = c;
+    for (int j = 0; j < 3; j++) {
+      double d = a[3 * j + j];
+      for (int k = 0; k < j; k++) d -= C[3 * j + k] * C[3 * j + k];
+      if (!(d > 0.0) || !graph_all_finite(&d, 1)) return false;
+      d = std::sqrt(d);
+      C[3 * j + j] = d;
+      for (int i = j + 1; i < 3; i++) {
+        double s = a[3 * i + j];
+        for (int k = 0; k < j; k++) s -= C[3 * i + k] * C[3 * j + k];
+        C[3 * i + j] = s / d;
+      }
+    }
+    if (stage == 1) break;
+    double W[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int j = 0; j < 3; j++) {
+      W[3 * j + j] = 1.0 / C[3 * j + j];
+      for (int i = j + 1; i < 3; i++) {
+        double s = 0.0;
+        for (int k = j; k < i; k++) s -= C[3 * i + k] * W[3 * k + j];
+        W[3 * i + j] = s / C[3 * i + i];
+      }
+    }
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        double s = 0.0;
+        for (int k = 0; k < 3; k++) s += W[3 * k + i] * W[3 * k + j];
+        c[3 * i + j] = s;
+      }
+    for (int k = 0; k < 9; k++) C[k] = 0.0;
+  }
+  double out[9];
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) out[3 * i + j] = C[3 * j + i];
+  if (!graph_all_finite(out, 9)) return false;
+  std::copy(out, out + 9, L3);
+  return true;
 }
 
 
