@@ -1,6 +1,7 @@
 """Closing a loop end to end: places -> score -> match -> pose graph -> corrected trajectory.
 
     python examples/close_loop.py [--scans 151] [--gap 50] [--every 1] [--max-distance 0.1] [--min-fitness 0.99] [--weights scalar|information]
+                                  [--gate distance|mahalanobis] [--gate-bound 16.81]
 
 The figure of eight of examples/loop_candidates.py.  Every scan goes through the device-resident SLAM step (keep_clouds) and into a
 capi.Places.  The odometry the graph starts from is made to drift: the session's consecutive relative poses with a yaw bias and
@@ -12,8 +13,12 @@ the refined pose (the room repeats itself, so looser rules let wrong closures in
 trajectory error against the truth is printed before and after.  --weights information: the refinement runs with set_uncertainty, a
 closure becomes the information edge of its registration (capi.edge_from_uncertainty: the registration's information matrix scaled by its
 variance factor, without the directions it counts degenerate) in place of the hand-picked sr = 0.005 / st = 0.05, and the chi-square of
-every closure is printed after the optimisation.  A demonstration; the acceptance rule here is the example's, not
-the library's."""
+every closure is printed after the optimisation.  --gate mahalanobis replaces the 1.5 m rule: the chain is optimised with the odometry
+alone first, the joint marginal of the two nodes of a candidate (PoseGraph.marginals) gives the predicted covariance Sigma_rel of their
+relative pose (capi.relative_covariance), and the candidate passes when e^T (Sigma_rel + Sigma_z)^-1 e <= --gate-bound, e being the
+measured relative pose against the predicted one in the edge's tangent and Sigma_z the closure's own covariance (the inverse of the
+weights it would enter the graph with); the distance is printed for every candidate.  A demonstration; the acceptance rule here is the
+example's, not the library's."""
 import argparse
 import os
 import sys
@@ -56,6 +61,33 @@ def drifting(pose_map, rng, yaw_bias=0.004, sigma_t=0.01, sigma_r=0.002):
     return np.array(rel), np.array(out)
 
 
+def closure_information(weights, j, k, pose_j, refined, unc):
+    """L^T L of the edge a closure would enter the graph with: the registration's, or the hand-picked sr = 0.005 / st = 0.05."""
+    if weights == "information":
+        status, rec = capi.edge_from_uncertainty(j, k, pose_j, refined, unc, unc["sigma2"] if unc["sigma2"] > 0.0 else 1.0)
+        if status != capi.OK:
+            return None
+        L = rec["sqrt_information"][0]
+        return L.T @ L
+    return np.diag(np.r_[np.full(3, 1.0 / 0.05 ** 2), np.full(3, 1.0 / (2.0 * 0.005) ** 2)])
+
+
+def mahalanobis(g, x, j, k, z, info):
+    """e^T (Sigma_rel + Sigma_z)^-1 e of the measured relative pose z of nodes (j, k) against the graph's current poses x, through the
+    information form info - info (Sigma_rel^-1 + info)^-1 info, which also holds for a rank-deficient info = Sigma_z^-1."""
+    S, sm = g.marginals([(j, j), (j, k), (k, k)])
+    if sm.singular:
+        return np.inf
+    status, rel_cov = capi.relative_covariance(x[j], x[k], S[0], S[1], S[2])
+    if status != capi.OK:
+        return np.inf
+    pred = capi.relative_pose(x[j], x[k])
+    qe = synth.quat_mul(np.r_[-z[3:6], z[6]], pred[3:])
+    e = np.r_[pred[:3] - z[:3], 2.0 * np.sign(qe[3]) * qe[:3]]
+    W = info - info @ np.linalg.solve(np.linalg.inv(rel_cov) + info, info)
+    return float(e @ W @ e)
+
+
 def ate(poses, truth):
     return float(np.sqrt(np.mean(np.sum((np.asarray(poses)[:, :3] - truth[:, :3]) ** 2, axis=1))))
 
@@ -70,6 +102,9 @@ def main():
     ap.add_argument("--min-fitness", type=float, default=0.99)
     ap.add_argument("--weights", choices=("scalar", "information"), default="scalar", help="how a closure edge is weighted")
     ap.add_argument("--min-eigenvalue", type=float, default=150.0, help="information: eigenvalues of a registration below this are degenerate")
+    ap.add_argument("--gate", choices=("distance", "mahalanobis"), default="distance",
+                    help="accept a verified candidate within 1.5 m of its guess, or by its Mahalanobis distance against the odometry graph's marginals")
+    ap.add_argument("--gate-bound", type=float, default=16.81, help="mahalanobis: the chi-square bound (16.81: 99 %% at 6 degrees of freedom)")
     args = ap.parse_args()
 
     world = synth.World()
@@ -94,6 +129,15 @@ def main():
     h.set_map(grid_c.dump(), grid_s.dump())
     if args.weights == "information":
         h.set_uncertainty(1, args.min_eigenvalue)
+    n = args.scans
+    g = capi.PoseGraph(0, max_nodes=n, max_edges=n + len(candidates), max_fixes=1)
+    g.add_nodes(drifted)
+    g.set_fixed(0)
+    g.add_edges(g.edges(np.arange(n - 1), np.arange(1, n), rel, sr=0.01, st=0.1))
+    if args.gate == "mahalanobis":                    # the odometry alone: what the graph predicts before any closure
+        s = g.optimize()
+        predicted = g.poses()
+        print("odometry graph: %s after %d iterations; the gate reads its marginals" % (capi.GRAPH_TERMINATION[s.termination], s.iterations))
     closures = []
     for k, m, sharp, flat in candidates:
         j, yaw = int(m["index"]), float(capi.place_yaw(m["shift"], places.n_sector))
@@ -102,19 +146,22 @@ def main():
         status, refined, _ = h.match_scan2map(corner, surf, guess)
         unc = h.uncertainty(1)[0] if args.weights == "information" else None
         fit = capi.fitness(h.score_poses(corner, surf, [refined], args.max_dist), len(corner), len(surf))[0]
-        ok = status == 0 and fit >= args.min_fitness and np.linalg.norm(np.asarray(refined)[:3] - guess[:3]) <= 1.5
         z = capi.relative_pose(pose_map[j], np.asarray(refined))
+        if args.gate == "mahalanobis":
+            info = closure_information(args.weights, j, k, pose_map[j], np.asarray(refined, np.float64), unc) if status == 0 else None
+            d2 = mahalanobis(g, predicted, j, k, z, info) if info is not None else np.inf
+            print("scan %3d ~ scan %3d: Mahalanobis distance %.3g against the bound %.3g" % (k, j, d2, args.gate_bound))
+            ok = status == 0 and fit >= args.min_fitness and d2 <= args.gate_bound
+        else:
+            ok = status == 0 and fit >= args.min_fitness and np.linalg.norm(np.asarray(refined)[:3] - guess[:3]) <= 1.5
         dt, dr = synth.pose_error(z, capi.relative_pose(truth[j], truth[k]))
         print("scan %3d ~ scan %3d: distance %.3f, yaw %+6.1f deg, refined fitness %.3f -> %s (measurement off the truth by %.3f m, %.2f deg)"
               % (k, j, m["distance"], np.degrees(yaw), fit, "edge" if ok else "dropped", dt, np.degrees(dr)))
         if ok:
             closures.append((j, k, z, unc, np.asarray(refined, np.float64)))
 
-    n = args.scans
-    g = capi.PoseGraph(0, max_nodes=n, max_edges=n + len(closures), max_fixes=1)
-    g.add_nodes(drifted)
-    g.set_fixed(0)
-    g.add_edges(g.edges(np.arange(n - 1), np.arange(1, n), rel, sr=0.01, st=0.1))
+    if args.gate == "mahalanobis":
+        g.set_poses(drifted)
     if closures and args.weights == "scalar":
         g.add_edges(g.edges([c[0] for c in closures], [c[1] for c in closures], np.array([c[2] for c in closures]), sr=0.005, st=0.05))
     for j, k, _, unc, refined in closures if args.weights == "information" else []:

@@ -2,14 +2,17 @@
 //   msfl::PoseGraph      RAII over the C ABI
 //   msfl::PoseGraphEdge  the record of a loop-closure edge, the role of PoseGraphEdgeFactor (loop_closure/pose_graph_factor.h)
 //   msfl::PoseGraphEdgeInfo  the same edge weighted by the information matrix of the registration that measured it
+//   msfl::PoseGraph::Marginals, msfl::RelativeCovariance  covariance blocks of the solved poses and of a relative pose between two
 //   msfl::GpsFusion      the reference's class (slam/gps_fusion/gps_fusion.h, gps_fusion.cc:16-97): AddFixedPoint, AddLocalPose, Optimize
 // Header only, C++14.
 #ifndef MSFL_POSE_GRAPH_HPP_
 #define MSFL_POSE_GRAPH_HPP_
 
 #include <algorithm>
+#include <array>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "scan_matcher.hpp"
@@ -45,6 +48,17 @@ inline msfl_graph_edge_info PoseGraphEdgeInfo(int i, int j, const Rigid3d& pose_
   const msfl_status st = msfl_graph_edge_from_uncertainty(i, j, a.data(), b.data(), &unc, scale, &e);
   if (st != MSFL_OK) throw std::invalid_argument(std::string("msfl_graph_edge_from_uncertainty: ") + msfl_status_string(st));
   return e;
+}
+
+// Covariance of pose_a^-1 * pose_b in the tangent of an information edge, from the joint marginal PoseGraph::Marginals delivers for
+// (a, a), (a, b), (b, b): what a loop-candidate gate adds to the candidate's own (L^T L)^-1.
+inline std::array<double, 36> RelativeCovariance(const Rigid3d& pose_a, const Rigid3d& pose_b, const std::array<double, 36>& S_aa,
+                                                 const std::array<double, 36>& S_ab, const std::array<double, 36>& S_bb) {
+  const std::array<double, 7> a = pose_a.ToVector7(), b = pose_b.ToVector7();
+  std::array<double, 36> out{};
+  const msfl_status st = msfl_graph_relative_covariance(a.data(), b.data(), S_aa.data(), S_ab.data(), S_bb.data(), out.data());
+  if (st != MSFL_OK) throw std::invalid_argument(std::string("msfl_graph_relative_covariance: ") + msfl_status_string(st));
+  return out;
 }
 
 class PoseGraph {
@@ -90,6 +104,19 @@ class PoseGraph {
   std::vector<double> Chi2(int kind, int first, int n) {
     std::vector<double> out(static_cast<std::size_t>(n > 0 ? n : 0));
     Check(msfl_graph_factor_chi2(g_, kind, first, n, out.data()), "msfl_graph_factor_chi2");
+    return out;
+  }
+  // Covariance blocks Sigma_ab of the node pairs at the current poses (Covariance::GetCovarianceBlockInTangentSpace): blocks[k] is
+  // row-major 6 x 6 in [dt ; dtheta], world frame, rotation on the left; a == b gives a node's marginal.  summary.singular: all NaN.
+  struct MarginalBlocks { std::vector<std::array<double, 36>> blocks; msfl_graph_marginals_summary summary; };
+  MarginalBlocks Marginals(const std::vector<std::pair<int, int>>& pairs, const msfl_graph_marginals_options* options = nullptr) {
+    std::vector<int> flat;
+    for (const std::pair<int, int>& p : pairs) { flat.push_back(p.first); flat.push_back(p.second); }
+    MarginalBlocks out;
+    out.blocks.resize(pairs.size());
+    out.summary = msfl_graph_marginals_summary{};
+    Check(msfl_graph_marginals_with(g_, flat.data(), static_cast<int>(pairs.size()), pairs.empty() ? nullptr : out.blocks[0].data(), MSFL_MEM_HOST,
+                                    options, &out.summary), "msfl_graph_marginals");
     return out;
   }
   void SetFixed(int node, bool fixed = true) { Check(msfl_graph_set_fixed(g_, node, fixed ? 1 : 0), "msfl_graph_set_fixed"); }   // SetParameterBlockConstant

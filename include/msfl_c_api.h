@@ -1123,6 +1123,49 @@ msfl_status msfl_graph_fix_from_covariance(int i, int j, double t, const double 
 enum { MSFL_GRAPH_FACTOR_EDGE = 0, MSFL_GRAPH_FACTOR_FIX = 1, MSFL_GRAPH_FACTOR_EDGE_INFO = 2, MSFL_GRAPH_FACTOR_FIX_INFO = 3 };
 msfl_status msfl_graph_factor_chi2(msfl_graph* g, int kind, int first, int n, double* out /* HOST */);
 
+/* Marginal and cross covariances of the poses (docs/kernels/graph.md, "Marginals"): what Ceres'
+   Covariance::GetCovarianceBlockInTangentSpace gives.  At the current poses every factor is linearised as the solve linearises it
+   (HuberLoss corrector at huber_delta applied), H = J^T J over the free nodes' tangent with NO LM diagonal, Sigma = H^-1.
+   Tangent conventions of this header, all three:
+     - msfl_match_uncertainty: t += dt in the parent frame, q = q dq(dtheta) in the body frame (right rotation);
+     - msfl_graph_edge_info: z.t + dt, z.q (x) dq(dtheta), in the frame of node i;
+     - these blocks: [dt ; dtheta] with t + dt and q <- dq(dtheta) (x) q, BOTH in the world frame (left rotation vector in radians).
+       The solver's own tangent is [dt ; d] with dtheta = 2 d, so a delivered block is diag(I, 2I) Sigma_d diag(I, 2I).
+   `pairs` holds n_pairs node pairs (a, b), any order, duplicates allowed; pair k gives out[36 k ..]: Sigma_ab row-major, rows of a,
+   columns of b.  a == b is the node's marginal, delivered exactly symmetric.  A block with a fixed end is all zeros.
+   MSFL_BAD_ARG, nothing launched or written: an index outside the nodes; a graph with no fixed node and no fix of either kind
+   (structurally unanchored); free nodes but no factor.  An anchored graph can still leave a direction free (position fixes on one
+   line leave the rotation about it): the factorisation's smallest pivot^2 / diagonal falls below min_pivot_ratio, the call returns
+   MSFL_OK with summary.singular = 1 and every block is NaN.  Like msfl_graph_cost the call leaves poses, structure and the last
+   optimize's summary and trace as they were.  The first call allocates its scratch; a graph that never asks allocates nothing. */
+typedef struct msfl_graph_marginals_summary {
+  int n_pairs, n_columns;          /* 6 x distinct free column nodes actually solved */
+  int cg_iterations;               /* largest over the columns; 0 when the graph has no long factor (the solve is direct) */
+  int cg_unconverged;              /* columns that ended at the cap; their blocks are delivered as they are */
+  int singular;                    /* pivot test failed: every block is NaN */
+  int pad;
+  double min_pivot_ratio;          /* smallest Cholesky pivot^2 / block diagonal met in the factorisation; -1: a non-finite pivot */
+} msfl_graph_marginals_summary;
+typedef struct msfl_graph_marginals_options {
+  double min_pivot_ratio;          /* the pivot test's threshold; default 1e-7 (anchored parity cases: 0.12 and above; gauge-free: 4e-10 and below) */
+  int max_cg_iterations;           /* per column; 0: 16 x long factors + 8, as in the solve */
+  int reserved;
+  unsigned long long scratch_bytes;  /* budget of the column blocks (about 8 x 288 B x free nodes per column node); the column nodes
+                                        are solved in chunks that fit, one at a time at the least; default 256 MiB */
+} msfl_graph_marginals_options;
+void        msfl_graph_marginals_default_options(msfl_graph_marginals_options* o);
+msfl_status msfl_graph_marginals(msfl_graph* g, const int* pairs /* HOST, 2 x n_pairs */, int n_pairs,
+                                 double* out /* 36 x n_pairs */, msfl_mem out_mem,
+                                 msfl_graph_marginals_summary* summary /* may be NULL */);
+msfl_status msfl_graph_marginals_with(msfl_graph* g, const int* pairs, int n_pairs, double* out, msfl_mem out_mem,
+                                      const msfl_graph_marginals_options* options /* NULL: the defaults */,
+                                      msfl_graph_marginals_summary* summary);
+/* Covariance of T_ab = T_a^-1 T_b in the tangent of msfl_graph_edge_info (z.t + dt, z.q (x) dq(dtheta)) from the joint marginal
+   [S_aa S_ab; S_ab^T S_bb] msfl_graph_marginals delivers; it can be added to a candidate closure's (L^T L)^-1.  Host arithmetic
+   only.  MSFL_BAD_ARG, out untouched: a null pointer, a non-finite input or a zero quaternion. */
+msfl_status msfl_graph_relative_covariance(const double pose_a[7], const double pose_b[7], const double S_aa[36],
+                                           const double S_ab[36], const double S_bb[36], double out[36]);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -44,6 +44,7 @@ EXPORTED = [
     "msfl_graph_optimize", "msfl_graph_get_trace",
     "msfl_graph_add_edges_info", "msfl_graph_add_fixes_info", "msfl_graph_edge_from_uncertainty", "msfl_graph_fix_from_covariance",
     "msfl_graph_factor_chi2",
+    "msfl_graph_marginals_default_options", "msfl_graph_marginals", "msfl_graph_marginals_with", "msfl_graph_relative_covariance",
 ]
 
 
@@ -1366,6 +1367,31 @@ GRAPH_FACTOR_EDGE, GRAPH_FACTOR_FIX, GRAPH_FACTOR_EDGE_INFO, GRAPH_FACTOR_FIX_IN
 GRAPH_TERMINATION = ("empty", "gradient", "max_iterations", "min_radius", "invalid_steps", "parameter", "function")
 
 
+class GraphMarginalsSummary(C.Structure):
+    """msfl_graph_marginals_summary: how one msfl_graph_marginals call went."""
+    _fields_ = [("n_pairs", C.c_int), ("n_columns", C.c_int), ("cg_iterations", C.c_int), ("cg_unconverged", C.c_int),
+                ("singular", C.c_int), ("pad", C.c_int), ("min_pivot_ratio", C.c_double)]
+
+
+class GraphMarginalsOptions(C.Structure):
+    """msfl_graph_marginals_options: the pivot test's threshold, the CG cap per column and the byte budget of the column blocks."""
+    _fields_ = [("min_pivot_ratio", C.c_double), ("max_cg_iterations", C.c_int), ("reserved", C.c_int), ("scratch_bytes", C.c_ulonglong)]
+
+
+assert C.sizeof(GraphMarginalsSummary) == 32 and C.sizeof(GraphMarginalsOptions) == 24
+
+
+def relative_covariance(pose_a, pose_b, S_aa, S_ab, S_bb, out=None):
+    """msfl_graph_relative_covariance: the 6 x 6 covariance of T_a^-1 T_b in an information edge's tangent from the joint marginal
+    PoseGraph.marginals delivers.  Host arithmetic only.  Returns (status, block); a refusal leaves the block (`out`) untouched."""
+    lib = load()
+    res = np.zeros((6, 6), np.float64) if out is None else out
+    pa, pb = (np.ascontiguousarray(np.asarray(p, np.float64).reshape(7)) for p in (pose_a, pose_b))
+    S = [np.ascontiguousarray(np.asarray(m, np.float64).reshape(36)) for m in (S_aa, S_ab, S_bb)]
+    s = lib.msfl_graph_relative_covariance(_vp(pa), _vp(pb), _vp(S[0]), _vp(S[1]), _vp(S[2]), _vp(res))
+    return int(s), res
+
+
 def relative_pose(Ti, Tj):
     """T_i^-1 T_j of two poses [t, qx qy qz qw] (unit quaternions): the measurement z of a graph edge (i, j)."""
     Ti, Tj = np.asarray(Ti, np.float64), np.asarray(Tj, np.float64)
@@ -1530,6 +1556,30 @@ class PoseGraph:
         s = self._check(self.lib.msfl_graph_factor_chi2(self.p, C.c_int(int(kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(out)),
                         "msfl_graph_factor_chi2", allow)
         return out if s == OK else s
+
+    def marginals(self, pairs, out=None, allow=(), **options):
+        """msfl_graph_marginals: the 6 x 6 covariance blocks Sigma_ab of the node pairs (a, b) at the current poses, in [dt ; dtheta]
+        (world frame, left rotation vector).  Returns ((n, 6, 6) array, GraphMarginalsSummary); `out`: a CUDA float64 tensor of n x 36
+        to fill on the device instead (asynchronous).  Keyword arguments are the fields of msfl_graph_marginals_options.  A refusing
+        status that is in `allow` is returned alone."""
+        pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        n = len(pairs)
+        opt = GraphMarginalsOptions()
+        self.lib.msfl_graph_marginals_default_options(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(GraphMarginalsOptions._fields_):
+                raise TypeError("unknown msfl_graph_marginals_options field %r" % (k,))
+            setattr(opt, k, v)
+        sm = GraphMarginalsSummary()
+        if out is not None and _on_device(out):
+            ptr, mem, res = C.c_void_p(out.data_ptr()), MEM_DEVICE, out
+        else:
+            res = np.zeros((n, 6, 6), np.float64) if out is None else out      # a C-contiguous float64 array of n x 36 values
+            ptr, mem = _vp(res), MEM_HOST
+        call = self.lib.msfl_graph_marginals_with if options else self.lib.msfl_graph_marginals
+        args = (self.p, _vp(pairs), C.c_int(n), ptr, C.c_int(mem)) + ((C.byref(opt),) if options else ()) + (C.byref(sm),)
+        s = self._check(call(*args), "msfl_graph_marginals", allow)
+        return (res, sm) if s == OK else s
 
     def add_edges(self, rec, allow=()):
         rec = np.ascontiguousarray(rec, GRAPH_EDGE_DTYPE)

@@ -7,6 +7,8 @@
 static_assert(sizeof(msfl_graph_edge) == 80 && sizeof(msfl_graph_fix) == 48 && sizeof(msfl_graph_summary) == 48, "graph record layout");
 static_assert(sizeof(msfl_graph_edge_info) == 352 && sizeof(msfl_graph_fix_info) == 112, "information factor record layout");
 static_assert(sizeof(GraphState) % 8 == 0, "the trace follows the state record");
+static_assert(sizeof(msfl_graph_marginals_summary) == 32 && sizeof(msfl_graph_marginals_options) == 24, "marginals record layout");
+static_assert(sizeof(GraphMargCol) == 32 && sizeof(GraphMargState) == 16, "marginals state records, read back as they are");
 
 struct msfl_graph_s {
   int device = 0;
@@ -33,6 +35,12 @@ struct msfl_graph_s {
   DevBuf state;                  // GraphState, double[max_iter] candidate costs, one double (msfl_graph_cost), int[max_iter] accept list
   PinRing pin;
   PinBuf readback;
+  // msfl_graph_marginals; all of it allocated by the first call
+  DevBuf marg_work;              // the column blocks of one chunk, the CG partials, the pivot partials
+  DevBuf marg_state;             // GraphState (zero: the reused kernels' `done`), GraphMargState, GraphMargCol[6 x column nodes]
+  DevBuf marg_ints;              // free index per column node | per pair: free index of a, column index of b
+  DevBuf marg_out;               // the blocks before they go to the host
+  PinBuf marg_read;
 };
 
 namespace {
@@ -530,6 +538,177 @@ msfl_status msfl_graph_get_trace(msfl_graph* g, int* accepted, double* cost, int
     if (cost) cost[i] = g->tr_cost[i];
   }
   return n > capacity ? fail(g, MSFL_CAPACITY, "msfl_graph_get_trace: the trace holds more iterations than `capacity`") : MSFL_OK;
+}
+
+// ---- marginals -----------------------------------------------------------------------------------------------------------------
+void msfl_graph_marginals_default_options(msfl_graph_marginals_options* o) {
+  if (!o) return;
+  o->min_pivot_ratio = 1e-7; o->max_cg_iterations = 0; o->reserved = 0; o->scratch_bytes = 256ull << 20;
+}
+
+msfl_status msfl_graph_relative_covariance(const double* pose_a, const double* pose_b, const double* S_aa, const double* S_ab,
+                                           const double* S_bb, double* out) {
+  if (!pose_a || !pose_b || !S_aa || !S_ab || !S_bb || !out) return MSFL_BAD_ARG;
+  return graph_relative_covariance(pose_a, pose_b, S_aa, S_ab, S_bb, out) ? MSFL_OK : MSFL_BAD_ARG;
+}
+
+msfl_status msfl_graph_marginals(msfl_graph* g, const int* pairs, int n_pairs, double* out, msfl_mem out_mem, msfl_graph_marginals_summary* summary) {
+  return msfl_graph_marginals_with(g, pairs, n_pairs, out, out_mem, nullptr, summary);
+}
+
+msfl_status msfl_graph_marginals_with(msfl_graph* g, const int* pairs, int n_pairs, double* out, msfl_mem out_mem,
+                                      const msfl_graph_marginals_options* options, msfl_graph_marginals_summary* summary) {
+  msfl_status s = enter(g); if (s) return s;
+  msfl_graph_marginals_summary local{};
+  msfl_graph_marginals_summary* sm = summary ? summary : &local;
+  msfl_graph_marginals_options opt;
+  msfl_graph_marginals_default_options(&opt);
+  if (options) opt = *options;
+  if (n_pairs < 0 || (n_pairs > 0 && (!pairs || !out)) || (out_mem != MSFL_MEM_HOST && out_mem != MSFL_MEM_DEVICE))
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_marginals: null array, negative count or unknown memory kind");
+  if (!std::isfinite(opt.min_pivot_ratio) || opt.min_pivot_ratio < 0.0 || opt.max_cg_iterations < 0)
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_marginals: min_pivot_ratio not finite or negative, or a negative max_cg_iterations");
+  for (int k = 0; k < 2 * n_pairs; k++)
+    if (pairs[k] < 0 || pairs[k] >= g->n_nodes) return fail(g, MSFL_BAD_ARG, "msfl_graph_marginals: a node index out of range; nothing written");
+  std::memset(sm, 0, sizeof(*sm));
+  if (n_pairs == 0) return MSFL_OK;
+  // the gauge the host can see: something has to tie the graph to the world, and free nodes need a factor
+  const bool any_fixed = std::find(g->fixed.begin(), g->fixed.end(), (unsigned char)1) != g->fixed.end();
+  const bool any_free = std::find(g->fixed.begin(), g->fixed.end(), (unsigned char)0) != g->fixed.end();
+  const size_t n_fac = g->edges.size() + g->fixes.size() + g->edges_info.size() + g->fixes_info.size();
+  if (!any_fixed && g->fixes.empty() && g->fixes_info.empty())
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_marginals: no fixed node and no fix: the graph is not anchored; nothing written");
+  if (any_free && n_fac == 0) return fail(g, MSFL_BAD_ARG, "msfl_graph_marginals: free nodes but no factor; nothing written");
+  s = graph_prepare(g); if (s) return s;
+  hipStream_t st = g->stream;
+  const GraphLevels& v = g->lv;
+  const int F = g->dev.n_free;
+  sm->n_pairs = n_pairs;
+  const size_t out_bytes = (size_t)n_pairs * 36 * sizeof(double);
+  if (F == 0) {                                            // every node fixed: zero variance everywhere
+    sm->min_pivot_ratio = 1.0;
+    if (out_mem == MSFL_MEM_HOST) std::memset(out, 0, out_bytes);
+    else HIPCHK(g, hipMemsetAsync(out, 0, out_bytes, st));
+    return MSFL_OK;
+  }
+  // the distinct free column nodes in the order they first appear, and per pair where its block lives
+  std::vector<int> col_of((size_t)F, -1), ints;
+  int n_cols = 0;
+  for (int k = 0; k < n_pairs; k++) {
+    const int fa = g->gs.free_of[pairs[2 * k]], fb = g->gs.free_of[pairs[2 * k + 1]];
+    if (fa >= 0 && fb >= 0 && col_of[fb] < 0) { col_of[fb] = n_cols++; ints.push_back(fb); }
+  }
+  for (int k = 0; k < n_pairs; k++) ints.push_back(g->gs.free_of[pairs[2 * k]]);
+  for (int k = 0; k < n_pairs; k++) {
+    const int fa = g->gs.free_of[pairs[2 * k]], fb = g->gs.free_of[pairs[2 * k + 1]];
+    ints.push_back(fa >= 0 && fb >= 0 ? col_of[fb] : -1);
+  }
+  const int n_part = div_up(F, kGraphBlock);
+  const size_t upper = (size_t)v.off[v.count - 1] + 1 - (size_t)F;
+  const size_t per_col = ((size_t)6 * F + 2 * upper) * 36 + (size_t)12 * n_part;             // doubles per column node
+  const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_cols), (size_t)opt.scratch_bytes / (per_col * sizeof(double))));
+  int n_piv = 0;
+  for (int l = 0; l < v.tail; l++) n_piv += std::max(1, div_up(v.n[l] / 2, kGraphBlock));
+  const size_t state_bytes = sizeof(GraphState) + sizeof(GraphMargState) + (size_t)std::max(1, n_cols) * 6 * sizeof(GraphMargCol);
+  HIPCHK(g, g->marg_work.reserve(((size_t)chunk * per_col + (size_t)std::max(1, n_piv)) * sizeof(double)));
+  HIPCHK(g, g->marg_state.reserve(state_bytes));
+  HIPCHK(g, g->marg_ints.reserve(ints.size() * sizeof(int)));
+  HIPCHK(g, g->marg_read.reserve(std::max(sizeof(GraphMargState), (size_t)chunk * 6 * sizeof(GraphMargCol))));
+  if (out_mem == MSFL_MEM_HOST) HIPCHK(g, g->marg_out.reserve(out_bytes));
+  HIPCHK(g, g->pin.upload(g->marg_ints.p, ints.data(), ints.size() * sizeof(int), st));
+  HIPCHK(g, hipMemsetAsync(g->marg_state.p, 0, sizeof(GraphState) + sizeof(GraphMargState), st));
+  GraphDev d = g->dev;                                     // the reused kernels look at st->done, which the last optimize left at 1
+  d.st = g->marg_state.as<GraphState>();
+  GraphMarg M{};
+  M.n_part = n_part;
+  M.st = reinterpret_cast<GraphMargState*>(g->marg_state.as<char>() + sizeof(GraphState));
+  GraphMargCol* cols = reinterpret_cast<GraphMargCol*>(g->marg_state.as<char>() + sizeof(GraphState) + sizeof(GraphMargState));
+  const int* d_ints = g->marg_ints.as<int>();
+  const int* d_pair_fa = d_ints + n_cols; const int* d_pair_col = d_pair_fa + n_pairs;
+  double* d_out = out_mem == MSFL_MEM_HOST ? g->marg_out.as<double>() : out;
+  auto carve_for = [&](int nc) {                           // the work area for a chunk of nc column nodes
+    double* w = g->marg_work.as<double>();
+    auto carve = [&w](size_t n) { double* p = w; w += n; return p; };
+    M.piv = carve((size_t)std::max(1, n_piv));
+    const size_t blk = (size_t)nc * F * 36;
+    M.X = carve(blk); M.R = carve(blk); M.Z = carve(blk); M.P[0] = carve(blk); M.P[1] = carve(blk); M.Q = carve(blk);
+    M.rhs = carve((size_t)nc * upper * 36); M.sol = carve((size_t)nc * upper * 36);
+    M.part = carve((size_t)12 * nc * n_part);
+    M.n_cols = nc;
+  };
+  carve_for(0);
+  // 1. linearise and assemble at the current poses, 2. the undamped level 0, 3. the factor half with the pivot test
+  const double huber = g->cfg.huber_delta;
+  if (d.n_plain) graph_launch(st, graph_linearize_kernel, d.n_plain, kGraphBlock, d, huber);
+  if (d.n_factors > d.n_plain) graph_launch(st, graph_linearize_info_kernel, d.n_factors - d.n_plain, kGraphBlock, d, huber);
+  graph_launch(st, graph_assemble_kernel, F, kGraphBlock, d);
+  graph_launch(st, graph_marg_setup_kernel, F, kGraphVec, d);
+  for (int l = 0, first = 0; l < v.tail; l++) {
+    graph_launch(st, graph_marg_invert_kernel, v.n[l] / 2, kGraphBlock, d, v, l, M, first);
+    first += std::max(1, div_up(v.n[l] / 2, kGraphBlock));
+    graph_launch(st, graph_cr_reduce_kernel, v.n[l + 1], kGraphBlock, d, v, l);
+  }
+  graph_launch(st, graph_marg_factor_tail_kernel, 1, kGraphVec, d, v, M, n_piv, opt.min_pivot_ratio);
+  HIPCHK(g, hipGetLastError());
+  HIPCHK(g, hipMemcpyAsync(g->marg_read.p, M.st, sizeof(GraphMargState), hipMemcpyDeviceToHost, st));
+  HIPCHK(g, hipStreamSynchronize(st));
+  const GraphMargState ms = *g->marg_read.as<GraphMargState>();
+  sm->min_pivot_ratio = ms.min_pivot; sm->singular = ms.singular;
+  const int gather_items = n_pairs * 36;
+  if (ms.singular) {
+    graph_launch(st, graph_marg_gather_kernel, gather_items, kGraphVec, d, M, d_pair_fa, d_pair_col, n_pairs, 0, 1, d_out);
+  } else {
+    const int direct = g->gs.n_long == 0;
+    const int cap = opt.max_cg_iterations > 0 ? opt.max_cg_iterations : 16 * g->gs.n_long + 8;
+    const double tol = g->cfg.cg_tolerance;
+    auto launch2 = [&](auto kernel, int items, int block, int ny, auto... args) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1, div_up(items, block)), (unsigned)ny), dim3(block), 0, st, args...);
+    };
+    auto solve = [&](const double* y0, double* x0) {      // x0 = T^-1 y0 for every column node of the chunk
+      for (int l = 0; l < v.tail; l++) launch2(graph_marg_rhs_kernel, v.n[l + 1], kGraphBlock, M.n_cols, d, v, l, M, y0);
+      launch2(graph_marg_tail_kernel, 1, kGraphVec, M.n_cols, d, v, M, y0, x0);
+      for (int l = v.tail - 1; l >= 0; l--) launch2(graph_marg_back_kernel, v.n[l], kGraphBlock, M.n_cols, d, v, l, M, y0, x0);
+    };
+    if (n_cols == 0) graph_launch(st, graph_marg_gather_kernel, gather_items, kGraphVec, d, M, d_pair_fa, d_pair_col, n_pairs, 0, 0, d_out);
+    for (int first = 0; first < n_cols; first += chunk) {
+      carve_for(std::min(chunk, n_cols - first));
+      M.col_free = d_ints + first; M.col = cols + (size_t)first * 6;
+      launch2(graph_marg_init_kernel, F * 36, kGraphVec, M.n_cols, d, M);
+      if (direct) {
+        solve(M.R, M.X);
+      } else {
+        solve(M.R, M.Z);
+        launch2(graph_marg_dot_kernel, F, kGraphBlock, M.n_cols, d, M);
+        for (int it = 0; it < cap;) {                      // slices of at most 32 iterations, one small read between them
+          for (const int end = std::min(cap, it + 32); it < end; it++) {
+            launch2(graph_marg_matvec_kernel, F, kGraphBlock, M.n_cols, d, M, it, tol);
+            launch2(graph_marg_update_kernel, F, kGraphBlock, M.n_cols, d, M, it);
+            solve(M.R, M.Z);
+            launch2(graph_marg_dot_kernel, F, kGraphBlock, M.n_cols, d, M);
+          }
+          graph_launch(st, graph_marg_check_kernel, M.n_cols * kGraphBlock, kGraphBlock, M, it, tol);
+          HIPCHK(g, hipGetLastError());
+          HIPCHK(g, hipMemcpyAsync(g->marg_read.p, M.col, (size_t)M.n_cols * 6 * sizeof(GraphMargCol), hipMemcpyDeviceToHost, st));
+          HIPCHK(g, hipStreamSynchronize(st));
+          const GraphMargCol* hc = g->marg_read.as<GraphMargCol>();
+          int running = 0;
+          for (int k = 0; k < M.n_cols * 6; k++) running += !hc[k].done;
+          if (running && it < cap) continue;
+          for (int k = 0; k < M.n_cols * 6; k++) sm->cg_iterations = std::max(sm->cg_iterations, hc[k].it);
+          sm->cg_unconverged += running;
+          break;
+        }
+      }
+      graph_launch(st, graph_marg_gather_kernel, gather_items, kGraphVec, d, M, d_pair_fa, d_pair_col, n_pairs, first, 0, d_out);
+    }
+  }
+  sm->n_columns = ms.singular ? 0 : 6 * n_cols;
+  HIPCHK(g, hipGetLastError());
+  if (out_mem == MSFL_MEM_HOST) {
+    HIPCHK(g, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(g, hipStreamSynchronize(st));
+  }
+  return MSFL_OK;
 }
 
 }  // extern "C"

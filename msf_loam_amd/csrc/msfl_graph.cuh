@@ -881,4 +881,425 @@ __global__ __launch_bounds__(kGraphVec) void graph_cost_total_kernel(GraphDev G,
   if (threadIdx.x == 0) out[0] = c;
 }
 
+// ---- marginals (msfl_graph_marginals; docs/kernels/graph.md, "Marginals") -----------------------------------------------------------
+// Sigma = H^-1 at the current poses, H = J^T J undamped.  With the Jacobi scale S of this linearisation Hs = S H S is factored as the
+// solve factors its damped T, and Hs X = E_b is solved for the six unit columns of every requested free column node b by the same PCG
+// (chain part by cyclic reduction, long factors in the mat-vec); Sigma_ab = S_a X_a S_b.  blockIdx.y selects the column node, one lane
+// owns one free node and carries its 6 x 6 block (row = the node's coordinate, column = which of b's six unit vectors) through g6_mma
+// where the single-column kernels use g6_mv, so Dinv and L are loaded once per six columns.  Each of the six columns is a CG of its own
+// (GraphMargCol); sums per (column, workgroup) in index order; a converged column freezes; a workgroup whose six are done returns.
+struct GraphMargCol { double rz[2], rz0; int it, done; };
+struct GraphMargState { double min_pivot; int singular, pad; };
+struct GraphMarg {
+  int n_cols, n_part;                // column nodes of this chunk; workgroups per column node of the node-per-lane kernels
+  const int* col_free;               // [n_cols]: free index of the column node
+  double* X; double* R; double* Z; double* P[2]; double* Q;   // [n_cols x free x 36]
+  double* rhs; double* sol;          // [n_cols x (blocks - free) x 36]: levels 1.. of the reduction
+  double* part;                      // [2 x n_cols x 6 x n_part]: partials of p . q, then of r . z
+  GraphMargCol* col;                 // [n_cols x 6]
+  GraphMargState* st;
+  double* piv;                       // one partial minimum per workgroup of the invert launches, level after level
+};
+
+// g6_inv_spd that also returns the smallest pivot^2 / a_jj of its block (-1 when one is not finite)
+__device__ __forceinline__ double g6_inv_spd_pivot(double* a) {
+  double ratio = 1.0;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    const double ajj = a[j * 6 + j];
+    double d = ajj;
+#pragma unroll
+    for (int k = 0; k < j; k++) d -= a[j * 6 + k] * a[j * 6 + k];
+    const double q = d / ajj;
+    ratio = fmin(ratio, isfinite(q) ? q : -1.0);
+    d = sqrt(d);
+    a[j * 6 + j] = d;
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double s = a[i * 6 + j];
+#pragma unroll
+      for (int k = 0; k < j; k++) s -= a[i * 6 + k] * a[j * 6 + k];
+      a[i * 6 + j] = s / d;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    a[j * 6 + j] = 1.0 / a[j * 6 + j];
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = j; k < i; k++) s -= a[i * 6 + k] * (k == j ? a[j * 6 + j] : a[j * 6 + k]);
+      a[j * 6 + i] = s / a[i * 6 + i];
+    }
+  }
+  double w[36];
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j < 6; j++) w[i * 6 + j] = i == j ? a[i * 6 + i] : (i > j ? a[j * 6 + i] : 0.0);
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j <= i; j++) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = i; k < 6; k++) s += w[k * 6 + i] * w[k * 6 + j];
+      a[i * 6 + j] = s; a[j * 6 + i] = s;
+    }
+  return ratio;
+}
+// the fixed LDS tree of graph_block_sum, taking the minimum
+template <int kThreads>
+__device__ __forceinline__ double graph_block_min(double v, double* lds) {
+  const int t = (int)threadIdx.x;
+  lds[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (t < s) lds[t] = fmin(lds[t], lds[t + s]);
+    __syncthreads();
+  }
+  const double out = lds[0];
+  __syncthreads();
+  return out;
+}
+
+// level 0 of the reduction without the LM diagonal, under the Jacobi scale of this linearisation (written to G.scale for the mat-vec)
+__global__ __launch_bounds__(kGraphVec) void graph_marg_setup_kernel(GraphDev G) {
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (f >= G.n_free) return;
+  double s[6], sp[6];
+#pragma unroll
+  for (int c = 0; c < 6; c++) {
+    s[c] = 1.0 / (1.0 + sqrt(G.H[(size_t)f * 36 + c * 7]));
+    sp[c] = f > 0 ? 1.0 / (1.0 + sqrt(G.H[(size_t)(f - 1) * 36 + c * 7])) : 0.0;
+    G.scale[(size_t)f * 6 + c] = s[c];
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      G.D[(size_t)f * 36 + i * 6 + j] = s[i] * s[j] * G.H[(size_t)f * 36 + i * 6 + j];
+      G.L[(size_t)f * 36 + i * 6 + j] = f > 0 ? s[i] * sp[j] * G.Lb[(size_t)f * 36 + i * 6 + j] : 0.0;
+    }
+}
+
+__device__ __forceinline__ double graph_marg_invert_node(const GraphDev& G, const GraphLevels& V, int l, int j) {
+  const int k = V.n[l] == 1 ? 0 : 2 * j + 1;
+  double a[36];
+  g6_load(G.D + (size_t)(V.off[l] + k) * 36, a);
+  const double ratio = g6_inv_spd_pivot(a);
+  g6_store(G.Dinv + (size_t)(V.ioff[l] + j) * 36, a);
+  return ratio;
+}
+// graph_cr_invert_kernel that also leaves its workgroup's smallest pivot ratio in piv[first + blockIdx.x]
+__global__ __launch_bounds__(kGraphBlock) void graph_marg_invert_kernel(GraphDev G, GraphLevels V, int l, GraphMarg M, int first) {
+  __shared__ double lds[kGraphBlock];
+  const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  double ratio = 1.0;
+  if (j < V.n[l] / 2) ratio = graph_marg_invert_node(G, V, l, j);
+  ratio = graph_block_min<kGraphBlock>(ratio, lds);
+  if (threadIdx.x == 0) M.piv[first + blockIdx.x] = ratio;
+}
+// graph_cr_factor_tail_kernel with the pivot test: the minimum over its own blocks and the n_piv partials of the launches before it
+__global__ __launch_bounds__(kGraphVec) void graph_marg_factor_tail_kernel(GraphDev G, GraphLevels V, GraphMarg M, int n_piv, double min_ratio) {
+  __shared__ double lds[kGraphVec];
+  double ratio = 1.0;
+  for (int l = V.tail; l < V.count; l++) {
+    const int inv = V.n[l] == 1 ? 1 : V.n[l] / 2;
+    for (int j = (int)threadIdx.x; j < inv; j += kGraphVec) ratio = fmin(ratio, graph_marg_invert_node(G, V, l, j));
+    __syncthreads();
+    if (l + 1 < V.count)
+      for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec) graph_cr_reduce_node(G, V, l, m);
+    __syncthreads();
+  }
+  for (int i = (int)threadIdx.x; i < n_piv; i += kGraphVec) ratio = fmin(ratio, M.piv[i]);
+  ratio = graph_block_min<kGraphVec>(ratio, lds);
+  if (threadIdx.x == 0) { M.st->min_pivot = ratio; M.st->singular = ratio >= min_ratio ? 0 : 1; }
+}
+
+// the six columns of column node c are all done
+__device__ __forceinline__ bool graph_marg_all_done(const GraphMarg& M, int c) {
+  int d = 1;
+#pragma unroll
+  for (int j = 0; j < 6; j++) d &= M.col[c * 6 + j].done;
+  return d != 0;
+}
+__device__ __forceinline__ size_t graph_marg_upper(const GraphDev& G, const GraphLevels& V) { return (size_t)(V.off[V.count - 1] + 1 - G.n_free); }
+// level l of column node c: right-hand side / solution blocks (level 0: y0 / x0, [n_cols x free x 36])
+__device__ __forceinline__ const double* graph_marg_level_rhs(const GraphDev& G, const GraphLevels& V, const GraphMarg& M, int c, int l, const double* y0) {
+  return l == 0 ? y0 + (size_t)c * G.n_free * 36 : M.rhs + ((size_t)c * graph_marg_upper(G, V) + (size_t)(V.off[l] - G.n_free)) * 36;
+}
+__device__ __forceinline__ double* graph_marg_level_sol(const GraphDev& G, const GraphLevels& V, const GraphMarg& M, int c, int l, double* x0) {
+  return l == 0 ? x0 + (size_t)c * G.n_free * 36 : M.sol + ((size_t)c * graph_marg_upper(G, V) + (size_t)(V.off[l] - G.n_free)) * 36;
+}
+// graph_cr_rhs_node over 6 x 6 blocks: Y' = Y_k - L_k Dinv_k-1 Y_k-1 - L_k+1^T Dinv_k+1 Y_k+1
+__device__ __forceinline__ void graph_marg_rhs_node(const GraphDev& G, const GraphLevels& V, int l, int m, const double* __restrict__ y,
+                                                    double* __restrict__ yn) {
+  const int k = 2 * m, n = V.n[l];
+  const double* Ll = G.L + (size_t)V.off[l] * 36; const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
+  double o[36], t[36], b[36];
+  g6_load(y + (size_t)k * 36, o);
+  if (k >= 1) {
+    g6_load(y + (size_t)(k - 1) * 36, b);
+#pragma unroll
+    for (int i = 0; i < 36; i++) t[i] = 0.0;
+    g6_mma<false, false>(Il + (size_t)(m - 1) * 36, b, t, 1.0);
+    g6_mma<false, false>(Ll + (size_t)k * 36, t, o, -1.0);
+  }
+  if (k + 1 < n) {
+    g6_load(y + (size_t)(k + 1) * 36, b);
+#pragma unroll
+    for (int i = 0; i < 36; i++) t[i] = 0.0;
+    g6_mma<false, false>(Il + (size_t)m * 36, b, t, 1.0);
+    g6_mma<true, false>(Ll + (size_t)(k + 1) * 36, t, o, -1.0);
+  }
+  g6_store(yn + (size_t)m * 36, o);
+}
+// graph_cr_back_node over 6 x 6 blocks
+__device__ __forceinline__ void graph_marg_back_node(const GraphDev& G, const GraphLevels& V, int l, int k, const double* __restrict__ y,
+                                                     const double* __restrict__ xn, double* __restrict__ x) {
+  const int n = V.n[l], m = k >> 1;
+  double t[36], b[36];
+  if (!(k & 1)) {
+    g6_load(xn + (size_t)m * 36, t);
+    g6_store(x + (size_t)k * 36, t);
+    return;
+  }
+  const double* Ll = G.L + (size_t)V.off[l] * 36; const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
+  g6_load(y + (size_t)k * 36, t);
+  g6_load(xn + (size_t)m * 36, b);
+  g6_mma<false, false>(Ll + (size_t)k * 36, b, t, -1.0);
+  if (k + 1 < n) {
+    g6_load(xn + (size_t)(m + 1) * 36, b);
+    g6_mma<true, false>(Ll + (size_t)(k + 1) * 36, b, t, -1.0);
+  }
+#pragma unroll
+  for (int i = 0; i < 36; i++) b[i] = 0.0;
+  g6_mma<false, false>(Il + (size_t)m * 36, t, b, 1.0);
+  g6_store(x + (size_t)k * 36, b);
+}
+
+// X = 0, R = the unit columns of the column node, every column's CG record cleared
+__global__ __launch_bounds__(kGraphVec) void graph_marg_init_kernel(GraphDev G, GraphMarg M) {
+  const int c = (int)blockIdx.y;
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < 6) { GraphMargCol z{}; M.col[c * 6 + i] = z; }
+  if (i >= G.n_free * 36) return;
+  const int f = i / 36, e = i - 36 * f;
+  const size_t at = (size_t)c * G.n_free * 36 + i;
+  M.X[at] = 0.0;
+  M.R[at] = (f == M.col_free[c] && e % 7 == 0) ? 1.0 : 0.0;
+}
+
+// z = T^-1 y per column node: the right-hand-side half of the reduction, y0 -> x0 at level 0
+__global__ __launch_bounds__(kGraphBlock) void graph_marg_rhs_kernel(GraphDev G, GraphLevels V, int l, GraphMarg M, const double* y0) {
+  const int c = (int)blockIdx.y;
+  if (graph_marg_all_done(M, c)) return;
+  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m < V.n[l + 1]) graph_marg_rhs_node(G, V, l, m, graph_marg_level_rhs(G, V, M, c, l, y0), M.rhs + ((size_t)c * graph_marg_upper(G, V) + (size_t)(V.off[l + 1] - G.n_free)) * 36);
+}
+__global__ __launch_bounds__(kGraphVec) void graph_marg_tail_kernel(GraphDev G, GraphLevels V, GraphMarg M, const double* y0, double* x0) {
+  const int c = (int)blockIdx.y;
+  if (graph_marg_all_done(M, c)) return;
+  const int last = V.count - 1;
+  for (int l = V.tail; l < last; l++) {
+    for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec)
+      graph_marg_rhs_node(G, V, l, m, graph_marg_level_rhs(G, V, M, c, l, y0), M.rhs + ((size_t)c * graph_marg_upper(G, V) + (size_t)(V.off[l + 1] - G.n_free)) * 36);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double b[36], t[36];
+    g6_load(graph_marg_level_rhs(G, V, M, c, last, y0), b);
+#pragma unroll
+    for (int i = 0; i < 36; i++) t[i] = 0.0;
+    g6_mma<false, false>(G.Dinv + (size_t)V.ioff[last] * 36, b, t, 1.0);
+    g6_store(graph_marg_level_sol(G, V, M, c, last, x0), t);
+  }
+  __syncthreads();
+  for (int l = last - 1; l >= V.tail; l--) {
+    for (int k = (int)threadIdx.x; k < V.n[l]; k += kGraphVec)
+      graph_marg_back_node(G, V, l, k, graph_marg_level_rhs(G, V, M, c, l, y0), graph_marg_level_sol(G, V, M, c, l + 1, x0), graph_marg_level_sol(G, V, M, c, l, x0));
+    __syncthreads();
+  }
+}
+__global__ __launch_bounds__(kGraphBlock) void graph_marg_back_kernel(GraphDev G, GraphLevels V, int l, GraphMarg M, const double* y0, double* x0) {
+  const int c = (int)blockIdx.y;
+  if (graph_marg_all_done(M, c)) return;
+  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (k < V.n[l]) graph_marg_back_node(G, V, l, k, graph_marg_level_rhs(G, V, M, c, l, y0), graph_marg_level_sol(G, V, M, c, l + 1, x0), graph_marg_level_sol(G, V, M, c, l, x0));
+}
+
+// partials of r . z, one per (column, workgroup)
+__global__ __launch_bounds__(kGraphBlock) void graph_marg_dot_kernel(GraphDev G, GraphMarg M) {
+  __shared__ double lds[kGraphBlock];
+  const int c = (int)blockIdx.y;
+  if (graph_marg_all_done(M, c)) return;
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  double s[6] = {0, 0, 0, 0, 0, 0};
+  if (f < G.n_free) {
+    const double* r = M.R + ((size_t)c * G.n_free + f) * 36; const double* z = M.Z + ((size_t)c * G.n_free + f) * 36;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = 0; j < 6; j++) s[j] += r[i * 6 + j] * z[i * 6 + j];
+  }
+  double* part = M.part + (size_t)M.n_cols * 6 * M.n_part;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    const double v = graph_block_sum<kGraphBlock, false>(s[j], lds);
+    if (threadIdx.x == 0) part[(size_t)(c * 6 + j) * M.n_part + blockIdx.x] = v;
+  }
+}
+
+// block of the direction of free node f: column j is z + beta_j p_old (z alone at iteration 0)
+__device__ __forceinline__ void graph_marg_dir(const double* __restrict__ z, const double* __restrict__ po, const double* beta, bool first, double* p) {
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j < 6; j++) p[i * 6 + j] = z[i * 6 + j] + (first ? 0.0 : beta[j] * po[i * 6 + j]);
+}
+// graph_matvec_kernel per column node: every column's convergence test on its r . z, p = z + beta p, q = A p, partials of p . q
+__global__ __launch_bounds__(kGraphBlock) void graph_marg_matvec_kernel(GraphDev G, GraphMarg M, int it, double cg_tol) {
+  __shared__ double lds[kGraphBlock];
+  const int c = (int)blockIdx.y;
+  if (graph_marg_all_done(M, c)) return;
+  const int w = it & 1;
+  const double* part_rz = M.part + (size_t)M.n_cols * 6 * M.n_part;
+  double beta[6];
+  int done[6], all = 1;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    GraphMargCol* s = M.col + c * 6 + j;
+    done[j] = s->done;
+    const double rz = graph_total<kGraphBlock, false>(part_rz + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
+    const double rz0 = it == 0 ? rz : s->rz0;
+    const bool stop = it == 0 ? !(rz > 0.0) : sqrt(rz) <= cg_tol * sqrt(rz0);
+    beta[j] = it == 0 ? 0.0 : rz / s->rz[w ^ 1];
+    if (!done[j] && blockIdx.x == 0 && threadIdx.x == 0) {
+      if (stop) s->done = 1;
+      else { s->rz[w] = rz; if (it == 0) s->rz0 = rz; }
+    }
+    done[j] |= stop ? 1 : 0;
+    all &= done[j];
+  }
+  if (all) return;
+  const size_t base = (size_t)c * G.n_free * 36;
+  const double* Z = M.Z + base; const double* po = M.P[w ^ 1] + base; double* pn = M.P[w] + base; double* Q = M.Q + base;
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  double pq[6] = {0, 0, 0, 0, 0, 0};
+  if (f < G.n_free) {
+    double pf[36], pm[36], q[36], t[36];
+    graph_marg_dir(Z + (size_t)f * 36, po + (size_t)f * 36, beta, it == 0, pf);
+#pragma unroll
+    for (int i = 0; i < 36; i++) q[i] = 0.0;
+    g6_mma<false, false>(G.D + (size_t)f * 36, pf, q, 1.0);
+    if (f > 0) {
+      graph_marg_dir(Z + (size_t)(f - 1) * 36, po + (size_t)(f - 1) * 36, beta, it == 0, pm);
+      g6_mma<false, false>(G.L + (size_t)f * 36, pm, q, 1.0);
+    }
+    if (f + 1 < G.n_free) {
+      graph_marg_dir(Z + (size_t)(f + 1) * 36, po + (size_t)(f + 1) * 36, beta, it == 0, pm);
+      g6_mma<true, false>(G.L + (size_t)(f + 1) * 36, pm, q, 1.0);
+    }
+    const double* sf = G.scale + (size_t)f * 6;
+    for (int e = G.ladj_off[f]; e < G.ladj_off[f + 1]; e++) {       // long factors: s_f . Jf^T (Jo (s_o . p_o)), in adjacency order
+      const int k = G.ladj[e] >> 1, side = G.ladj[e] & 1;
+      const int fo = G.free_of[G.fac_ij[2 * k + (side ^ 1)]];
+      const double* Jk = G.J + (size_t)k * kGraphJ;
+      const double* so = G.scale + (size_t)fo * 6;
+      graph_marg_dir(Z + (size_t)fo * 36, po + (size_t)fo * 36, beta, it == 0, pm);
+#pragma unroll
+      for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) { pm[i * 6 + j] *= so[i]; t[i * 6 + j] = 0.0; }
+      g6_mma<false, false>(Jk + 36 * (side ^ 1), pm, t, 1.0);
+#pragma unroll
+      for (int i = 0; i < 36; i++) pm[i] = 0.0;
+      g6_mma<true, false>(Jk + 36 * side, t, pm, 1.0);
+#pragma unroll
+      for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) q[i * 6 + j] += sf[i] * pm[i * 6 + j];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = 0; j < 6; j++)
+        if (!done[j]) {
+          pn[(size_t)f * 36 + i * 6 + j] = pf[i * 6 + j]; Q[(size_t)f * 36 + i * 6 + j] = q[i * 6 + j];
+          pq[j] += pf[i * 6 + j] * q[i * 6 + j];
+        }
+  }
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    const double v = graph_block_sum<kGraphBlock, false>(pq[j], lds);
+    if (threadIdx.x == 0) M.part[(size_t)(c * 6 + j) * M.n_part + blockIdx.x] = v;
+  }
+}
+
+// x += alpha p, r -= alpha q per column that is still running
+__global__ __launch_bounds__(kGraphBlock) void graph_marg_update_kernel(GraphDev G, GraphMarg M, int it) {
+  __shared__ double lds[kGraphBlock];
+  const int c = (int)blockIdx.y;
+  if (graph_marg_all_done(M, c)) return;
+  double alpha[6];
+  int done[6];
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    GraphMargCol* s = M.col + c * 6 + j;
+    done[j] = s->done;
+    const double pq = graph_total<kGraphBlock, false>(M.part + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
+    alpha[j] = s->rz[it & 1] / pq;
+  }
+  const size_t base = (size_t)c * G.n_free * 36;
+  const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (f < G.n_free) {
+    const double* p = M.P[it & 1] + base + (size_t)f * 36; const double* q = M.Q + base + (size_t)f * 36;
+    double* x = M.X + base + (size_t)f * 36; double* r = M.R + base + (size_t)f * 36;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = 0; j < 6; j++)
+        if (!done[j]) { x[i * 6 + j] += alpha[j] * p[i * 6 + j]; r[i * 6 + j] -= alpha[j] * q[i * 6 + j]; }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 6 && !M.col[c * 6 + threadIdx.x].done) M.col[c * 6 + threadIdx.x].it = it + 1;
+}
+
+// the end of a slice of `it` iterations: the test graph_marg_matvec_kernel would make next, so that the host's poll sees a column that
+// converged in the slice's last iteration
+__global__ __launch_bounds__(kGraphBlock) void graph_marg_check_kernel(GraphMarg M, int it, double cg_tol) {
+  __shared__ double lds[kGraphBlock];
+  const int c = (int)blockIdx.x;
+  const double* part_rz = M.part + (size_t)M.n_cols * 6 * M.n_part;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    GraphMargCol* s = M.col + c * 6 + j;
+    const double rz = graph_total<kGraphBlock, false>(part_rz + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
+    if (threadIdx.x == 0 && !s->done && sqrt(rz) <= cg_tol * sqrt(s->rz0)) s->done = 1;
+  }
+}
+
+// one lane per delivered entry: Sigma_ab(i, j) = s_a[i] X_a(i, j) s_b[j], rotational rows and columns doubled; a == b computes the lower
+// triangle and mirrors it; a fixed end gives zeros; `singular` gives NaN.  pair_fa: free index of a (-1: fixed); pair_col: index of b
+// among the column nodes (-1: fixed); this launch writes the pairs whose column lies in [col_first, col_first + M.n_cols).
+__global__ __launch_bounds__(kGraphVec) void graph_marg_gather_kernel(GraphDev G, GraphMarg M, const int* __restrict__ pair_fa, const int* __restrict__ pair_col,
+                                                                      int n_pairs, int col_first, int singular, double* __restrict__ out) {
+  const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (idx >= n_pairs * 36) return;
+  const int k = idx / 36, e = idx - 36 * k;
+  int i = e / 6, j = e - 6 * (e / 6);
+  const int fa = pair_fa[k], col = pair_col[k];
+  if (singular) { out[idx] = __longlong_as_double(0x7ff8000000000000LL); return; }
+  if (fa < 0 || col < 0) { out[idx] = 0.0; return; }
+  const int c = col - col_first;
+  if (c < 0 || c >= M.n_cols) return;
+  const int fb = M.col_free[c];
+  if (fa == fb && i < j) { const int t = i; i = j; j = t; }
+  const double v = M.X[((size_t)c * G.n_free + fa) * 36 + i * 6 + j];
+  const double si = G.scale[(size_t)fa * 6 + i] * (i >= 3 ? 2.0 : 1.0), sj = G.scale[(size_t)fb * 6 + j] * (j >= 3 ? 2.0 : 1.0);
+  out[idx] = (v * si) * sj;
+}
+
 }  // namespace msfl

@@ -1,7 +1,8 @@
 // Host-side bookkeeping of the pose graph (msfl_api_graph.inc): free-node numbering, adjacency lists, long / chain classification and
 // the level sizes of the cyclic reduction, and the arithmetic that turns a registration's eigen-decomposition or a 3 x 3 covariance
-// into an information factor.  Plain C++ over plain arrays, no HIP: tests/cpp/graph_structure_check.cpp and
-// tests/cpp/graph_info_check.cpp run it under the host sanitizers.
+// into an information factor, or a joint marginal into the covariance of a relative pose.  Plain C++ over plain arrays, no HIP:
+// tests/cpp/graph_structure_check.cpp, tests/cpp/graph_info_check.cpp and tests/cpp/graph_marginals_check.cpp run it under the host
+// sanitizers.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -189,5 +190,61 @@ inline bool graph_fix_from_covariance(const double* cov, double* L3) {
   return true;
 }
 
+// ---- marginals: the arithmetic of msfl_graph_relative_covariance ---------------------------------------------------------------
+// Covariance of T_ab = T_a^-1 T_b in the tangent of an information edge (z.t + dt, z.q (x) dq(dtheta)) from the joint marginal of a and
+// b in the delivered coordinates [dt ; dtheta], both world frame, rotation on the left.  With u = t_b - t_a:
+//   J_a = [-R_a^T  R_a^T [u]x ; 0  -R_b^T],   J_b = [R_a^T  0 ; 0  R_b^T],   out = [J_a J_b] [S_aa S_ab; S_ab^T S_bb] [J_a J_b]^T,
+// symmetrised.  false (nothing written): a non-finite input or a zero quaternion.
+inline bool graph_relative_covariance(const double* pose_a, const double* pose_b, const double* Saa, const double* Sab, const double* Sbb,
+                                      double* out) {
+  if (!graph_all_finite(pose_a, 7) || !graph_all_finite(pose_b, 7) || !graph_all_finite(Saa, 36) || !graph_all_finite(Sab, 36) ||
+      !graph_all_finite(Sbb, 36))
+    return false;
+  double qa[4], qb[4];
+  for (int side = 0; side < 2; side++) {
+    const double* p = side ? pose_b : pose_a;
+    const double n = std::sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] + p[6] * p[6]);
+    if (!(n > 0.0) || !graph_all_finite(&n, 1)) return false;
+    for (int c = 0; c < 4; c++) (side ? qb : qa)[c] = p[3 + c] / n;
+  }
+  double Ra[9], Rb[9];
+  graph_host_quat_to_R(qa, Ra);
+  graph_host_quat_to_R(qb, Rb);
+  const double u[3] = {pose_b[0] - pose_a[0], pose_b[1] - pose_a[1], pose_b[2] - pose_a[2]};
+  const double ux[9] = {0.0, -u[2], u[1], u[2], 0.0, -u[0], -u[1], u[0], 0.0};
+  double J[6][12], S[12][12];
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 12; j++) J[i][j] = 0.0;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double b = 0.0;
+      for (int m = 0; m < 3; m++) b += Ra[3 * m + i] * ux[3 * m + j];      // R_a^T [u]x
+      J[i][j] = -Ra[3 * j + i]; J[i][3 + j] = b; J[3 + i][3 + j] = -Rb[3 * j + i];
+      J[i][6 + j] = Ra[3 * j + i]; J[3 + i][9 + j] = Rb[3 * j + i];
+    }
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) {
+      S[i][j] = Saa[6 * i + j]; S[i][6 + j] = Sab[6 * i + j]; S[6 + j][i] = Sab[6 * i + j]; S[6 + i][6 + j] = Sbb[6 * i + j];
+    }
+  double JS[6][12], C[36];
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 12; j++) {
+      double s = 0.0;
+      for (int m = 0; m < 12; m++) s += J[i][m] * S[m][j];
+      JS[i][j] = s;
+    }
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) {
+      double s = 0.0;
+      for (int m = 0; m < 12; m++) s += JS[i][m] * J[j][m];
+      C[6 * i + j] = s;
+    }
+  double sym[36];
+  for (int i = 0; i < 6; i++)
+    for (int j = 0; j < 6; j++) sym[6 * i + j] = 0.5 * (C[6 * i + j] + C[6 * j + i]);
+  if (!graph_all_finite(sym, 36)) return false;
+  std::copy(sym, sym + 36, out);
+  return true;
+}
 
 }  // namespace msfl

@@ -10,7 +10,13 @@ block-tridiagonal solve alone is the N-with-0-long-edges row: there every LM ite
 right-hand-side passes.  Yardstick in the same process: scipy's sparse LU (SuperLU, one thread) of the same damped normal equations at
 the start poses, factorisation + solve, median of 3.  --info: the same graph with its long edges (closures), or all its edges (all), handed
 over as information edges with the isotropic L of the same cost (tests/graph_info_numpy.isotropic_L); with MSFL_LIB set to another
-build of the library the plain rows (--info none) compare the two builds.  No acceptance threshold hangs on these numbers."""
+build of the library the plain rows (--info none) compare the two builds.  No acceptance threshold hangs on these numbers.
+
+    python tools/graph_throughput.py --marginals [--sizes 1000 10000] [--long 0 10] [--nodes 1 16] [--repeats 5]
+
+writes profiles/graph_marginals.json instead: the time of one msfl_graph_marginals call for the marginals of `nodes` nodes spread over the
+chain, at the start poses, warm (median of `repeats`), and of the same nodes asked one call each.  Yardstick in the same process:
+scipy's sparse LU of the same undamped H = J^T J, factorisation + solve with the same 6 x nodes unit right-hand sides, median of 3."""
 import argparse
 import json
 import os
@@ -56,6 +62,61 @@ def scipy_step_seconds(prob):
     return float(np.median(ts))
 
 
+def scipy_marginals_seconds(prob, nodes):
+    import scipy.sparse.linalg as spl
+    _, _, J = gn.evaluate_sparse(prob, prob["poses"], gn.Options)
+    H = (J.T @ J).tocsc()
+    E = np.zeros((H.shape[0], 6 * len(nodes)))
+    for q, k in enumerate(nodes):
+        E[6 * k + np.arange(6), 6 * q + np.arange(6)] = 1.0
+    ts = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        spl.splu(H).solve(E)
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts))
+
+
+def marginals(args):
+    rows = []
+    for n in args.sizes:
+        for k in args.long:
+            prob = make(n, k)
+            g = capi.PoseGraph(0, max_nodes=n, max_edges=n + k, max_fixes=n // 50 + 2)
+            g.add_nodes(torch.from_numpy(np.ascontiguousarray(prob["poses"])).cuda())
+            g.add_edges(g.edges(prob["ei"], prob["ej"], prob["ez"], prob["esr"], prob["est"]))
+            g.add_fixes(g.fixes(prob["fi"], prob["fj"], prob["ft"], prob["fp"], prob["fst"]))
+            for m in args.nodes:
+                nodes = np.unique(np.round(np.linspace(0, n - 1, m)).astype(int))
+                pairs = np.stack([nodes, nodes], -1)
+                _, sm = g.marginals(pairs)
+                one, each = [], []
+                for _ in range(args.repeats):
+                    t0 = time.perf_counter()
+                    _, sm = g.marginals(pairs)
+                    one.append(time.perf_counter() - t0)
+                    t0 = time.perf_counter()
+                    for p in pairs:
+                        g.marginals(p[None])
+                    each.append(time.perf_counter() - t0)
+                row = dict(n=n, long_edges=k, nodes=len(nodes), build=args.label, columns=sm.n_columns, cg_iterations=sm.cg_iterations,
+                           cg_unconverged=sm.cg_unconverged, singular=sm.singular, min_pivot_ratio=sm.min_pivot_ratio,
+                           one_call_ms=1e3 * float(np.median(one)), one_call_ms_min=1e3 * min(one), one_call_ms_max=1e3 * max(one),
+                           one_call_per_node_ms=1e3 * float(np.median(each)), one_call_per_node_ms_min=1e3 * min(each), one_call_per_node_ms_max=1e3 * max(each),
+                           scipy_splu_ms=None if args.no_scipy else 1e3 * scipy_marginals_seconds(prob, nodes))
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+            g.close()
+    out = dict(device=torch.cuda.get_device_name(0), host_threads_scipy=1, host_cpus=os.cpu_count(), repeats=args.repeats, rows=rows)
+    path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "graph_marginals.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "graph_throughput.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", type=int, nargs="+", default=[1000, 10000, 100000])
@@ -64,8 +125,16 @@ def main():
     ap.add_argument("--info", nargs="+", default=["none"], choices=["none", "closures", "all"])
     ap.add_argument("--label", default="this", help="names the build in every row (A/B runs with MSFL_LIB)")
     ap.add_argument("--no-scipy", action="store_true", help="skip the host yardstick")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "graph_throughput.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--marginals", action="store_true", help="time msfl_graph_marginals instead (profiles/graph_marginals.json)")
+    ap.add_argument("--nodes", type=int, nargs="+", default=[1, 16], help="marginals: requested nodes per call")
     args = ap.parse_args()
+    if args.marginals:
+        if args.sizes == [1000, 10000, 100000]:
+            args.sizes = [1000, 10000]
+        if args.long == [0, 10, 100]:
+            args.long = [0, 10]
+        return marginals(args)
     rows = []
     for n in args.sizes:
         for k in args.long:
