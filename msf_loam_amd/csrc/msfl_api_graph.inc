@@ -86,6 +86,12 @@ size_t graph_state_bytes(const msfl_graph* g) {
   return sizeof(GraphState) + (n + 1) * sizeof(double) + ((n + 1) & ~size_t(1)) * sizeof(int);
 }
 
+// hands out consecutive pieces of a work area
+struct GraphCarve {
+  double* w;
+  double* operator()(size_t n) { double* p = w; w += n; return p; }
+};
+
 // Builds the device copy of the structure and carves the work area; nothing to do while the structure is unchanged.
 msfl_status graph_prepare(msfl_graph* g) {
   if (!g->dirty) return MSFL_OK;
@@ -155,8 +161,7 @@ msfl_status graph_prepare(msfl_graph* g) {
   d.fac_ij = ip + at[6];
   d.fac_data = g->data.as<double>();
   d.x = g->x.as<double>(); d.cand = g->cand.as<double>();
-  double* w = g->work.as<double>();
-  auto carve = [&w](size_t n) { double* p = w; w += n; return p; };
+  GraphCarve carve{g->work.as<double>()};
   d.J = carve(nfz * kGraphJ); d.fcost = carve(nfz); d.fmodel = carve(nfz);
   d.H = carve(Fz * 36); d.Lb = carve(Fz * 36); d.g = carve(Fz * 6); d.scale = carve(Fz * 6);
   d.nxx = carve(Fz); d.ngmax = carve(Fz); d.nstep = carve(Fz);
@@ -172,31 +177,51 @@ msfl_status graph_prepare(msfl_graph* g) {
   return MSFL_OK;
 }
 
+// one lane per item; ny: the grid's y (the marginals' column nodes)
+template <class K, class... A>
+void graph_launch_y(hipStream_t st, K kernel, int items, int block, int ny, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1, div_up(items, block)), (unsigned)ny), dim3(block), 0, st, args...);
+}
 template <class K, class... A>
 void graph_launch(hipStream_t st, K kernel, int items, int block, A... args) {
-  hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1, div_up(items, block))), dim3(block), 0, st, args...);
+  graph_launch_y(st, kernel, items, block, 1, args...);
 }
+
+// The pieces of the launch pattern that msfl_graph_optimize and msfl_graph_marginals share.  They take the stream and the GraphDev to
+// run on: the marginals run on a copy whose `st` is a state record of their own.
 
 // the factor kernels: the plain kinds and, only when the graph holds one, the information kinds
-void graph_enqueue_linearize(msfl_graph* g, double huber) {
-  const GraphDev& d = g->dev;
-  if (d.n_plain) graph_launch(g->stream, graph_linearize_kernel, d.n_plain, kGraphBlock, d, huber);
-  if (d.n_factors > d.n_plain) graph_launch(g->stream, graph_linearize_info_kernel, d.n_factors - d.n_plain, kGraphBlock, d, huber);
+void graph_enqueue_linearize(hipStream_t st, const GraphDev& d, double huber) {
+  if (d.n_plain) graph_launch(st, graph_linearize_kernel, d.n_plain, kGraphBlock, d, huber);
+  if (d.n_factors > d.n_plain) graph_launch(st, graph_linearize_info_kernel, d.n_factors - d.n_plain, kGraphBlock, d, huber);
 }
 template <bool kModel>
-void graph_enqueue_cost(msfl_graph* g, const double* x, double huber) {
-  const GraphDev& d = g->dev;
-  if (d.n_plain) graph_launch(g->stream, graph_cost_kernel<kModel>, d.n_plain, kGraphBlock, d, x, huber);
-  if (d.n_factors > d.n_plain) graph_launch(g->stream, graph_cost_info_kernel<kModel>, d.n_factors - d.n_plain, kGraphBlock, d, x, huber);
+void graph_enqueue_cost(hipStream_t st, const GraphDev& d, const double* x, double huber) {
+  if (d.n_plain) graph_launch(st, graph_cost_kernel<kModel>, d.n_plain, kGraphBlock, d, x, huber);
+  if (d.n_factors > d.n_plain) graph_launch(st, graph_cost_info_kernel<kModel>, d.n_factors - d.n_plain, kGraphBlock, d, x, huber);
 }
 
-// z = T^-1 r: the right-hand-side half of the cyclic reduction
-void graph_enqueue_solve(msfl_graph* g) {
-  hipStream_t st = g->stream;
-  const GraphLevels& v = g->lv;
-  for (int l = 0; l < v.tail; l++) graph_launch(st, graph_cr_rhs_kernel, v.n[l + 1], kGraphVec, g->dev, v, l);
-  graph_launch(st, graph_cr_tail_kernel, 1, kGraphVec, g->dev, v);
-  for (int l = v.tail - 1; l >= 0; l--) graph_launch(st, graph_cr_back_kernel, v.n[l], kGraphVec, g->dev, v, l);
+// workgroups of the invert launch of level l: with kPivot each leaves one partial minimum in M.piv
+int graph_invert_groups(const GraphLevels& v, int l) { return std::max(1, div_up(v.n[l] / 2, kGraphBlock)); }
+
+// the factor half of the cyclic reduction of d.D / d.L; with kPivot also the pivot test into M.st (M is not looked at otherwise)
+template <bool kPivot>
+void graph_enqueue_factor(hipStream_t st, const GraphDev& d, const GraphLevels& v, const GraphMarg& M, double min_ratio) {
+  int n_piv = 0;
+  for (int l = 0; l < v.tail; l++) {
+    graph_launch(st, graph_cr_invert_kernel<kPivot>, v.n[l] / 2, kGraphBlock, d, v, l, M, n_piv);
+    n_piv += graph_invert_groups(v, l);
+    graph_launch(st, graph_cr_reduce_kernel, v.n[l + 1], kGraphBlock, d, v, l);
+  }
+  graph_launch(st, graph_cr_factor_tail_kernel<kPivot>, 1, kGraphVec, d, v, M, n_piv, min_ratio);
+}
+
+// x0 = T^-1 y0, the right-hand-side half of the cyclic reduction, for the columns of `cols` over a grid of ny in y
+template <class C>
+void graph_enqueue_solve(hipStream_t st, const GraphDev& d, const GraphLevels& v, int ny, const C& cols) {
+  for (int l = 0; l < v.tail; l++) graph_launch_y(st, graph_cr_rhs_kernel<C>, v.n[l + 1], C::kLanes, ny, d, v, l, cols);
+  graph_launch_y(st, graph_cr_tail_kernel<C>, 1, kGraphVec, ny, d, v, cols);
+  for (int l = v.tail - 1; l >= 0; l--) graph_launch_y(st, graph_cr_back_kernel<C>, v.n[l], C::kLanes, ny, d, v, l, cols);
 }
 
 msfl_status graph_read_state(msfl_graph* g, GraphState* out) {
@@ -204,6 +229,32 @@ msfl_status graph_read_state(msfl_graph* g, GraphState* out) {
   HIPCHK(g, hipStreamSynchronize(g->stream));
   std::memcpy(out, g->readback.p, sizeof(GraphState));
   return MSFL_OK;
+}
+
+// The checked append behind the four msfl_graph_add_*: nothing is stored unless the whole batch passes.  `held` counts what already
+// stands against `cap` (a kind and its information sibling together), `fits` is the text after "<who>: " when the batch does not fit,
+// `ok` the per-record test and `bad` the text when it fails; an information kind also gets room for its L matrices on the device.
+template <class R, class Ok>
+msfl_status graph_append(msfl_graph* g, const std::string& who, std::vector<R>& to, const R* recs, int n, size_t held, int cap, const char* fits,
+                         Ok ok, const char* bad, bool information) {
+  msfl_status s = enter(g); if (s) return s;
+  if (n < 0 || (n > 0 && !recs)) return fail(g, MSFL_BAD_ARG, who + ": null array or negative count");
+  if ((long long)held + n > cap) return fail(g, MSFL_CAPACITY, who + ": " + fits + "; nothing added");
+  for (int k = 0; k < n; k++) {
+    const R& r = recs[k];
+    if (r.i < 0 || r.j < 0 || r.i >= g->n_nodes || r.j >= g->n_nodes || r.i == r.j)
+      return fail(g, MSFL_BAD_ARG, who + ": a node index out of range or i == j; nothing added");
+    if (!ok(r)) return fail(g, MSFL_BAD_ARG, who + ": " + bad + "; nothing added");
+  }
+  if (n == 0) return MSFL_OK;
+  if (information) HIPCHK(g, g->linfo.reserve(36 * sizeof(double) * (g->edges_info.size() + g->fixes_info.size() + (size_t)n)));
+  to.insert(to.end(), recs, recs + n);
+  g->dirty = true;
+  return MSFL_OK;
+}
+
+bool graph_fix_point_ok(double t, const double* p) {
+  return std::isfinite(t) && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && t >= 0.0 && t <= 1.0;
 }
 
 }  // namespace
@@ -311,77 +362,35 @@ msfl_status msfl_graph_add_nodes(msfl_graph* g, const double* poses, int n, msfl
 }
 
 msfl_status msfl_graph_add_edges(msfl_graph* g, const msfl_graph_edge* edges, int n) {
-  msfl_status s = enter(g); if (s) return s;
-  if (n < 0 || (n > 0 && !edges)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges: null array or negative count");
-  if ((long long)g->edges.size() + (long long)g->edges_info.size() + n > g->cfg.max_edges)
-    return fail(g, MSFL_CAPACITY, "msfl_graph_add_edges: the batch does not fit max_edges; nothing added");
-  for (int k = 0; k < n; k++) {
-    const msfl_graph_edge& e = edges[k];
-    if (e.i < 0 || e.j < 0 || e.i >= g->n_nodes || e.j >= g->n_nodes || e.i == e.j)
-      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges: a node index out of range or i == j; nothing added");
-    if (!graph_pose_ok(e.z) || !std::isfinite(e.sr) || !std::isfinite(e.st) || !(e.sr > 0.0) || !(e.st > 0.0))
-      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges: a non-finite value, a zero quaternion or sr, st <= 0; nothing added");
-  }
-  g->edges.insert(g->edges.end(), edges, edges + n);
-  if (n) g->dirty = true;
-  return MSFL_OK;
+  if (!g) return MSFL_BAD_ARG;
+  return graph_append(g, "msfl_graph_add_edges", g->edges, edges, n, g->edges.size() + g->edges_info.size(), g->cfg.max_edges,
+                      "the batch does not fit max_edges",
+                      [](const msfl_graph_edge& e) { return graph_pose_ok(e.z) && std::isfinite(e.sr) && std::isfinite(e.st) && e.sr > 0.0 && e.st > 0.0; },
+                      "a non-finite value, a zero quaternion or sr, st <= 0", false);
 }
 
 msfl_status msfl_graph_add_fixes(msfl_graph* g, const msfl_graph_fix* fixes, int n) {
-  msfl_status s = enter(g); if (s) return s;
-  if (n < 0 || (n > 0 && !fixes)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes: null array or negative count");
-  if ((long long)g->fixes.size() + (long long)g->fixes_info.size() + n > g->cfg.max_fixes)
-    return fail(g, MSFL_CAPACITY, "msfl_graph_add_fixes: the batch does not fit max_fixes; nothing added");
-  for (int k = 0; k < n; k++) {
-    const msfl_graph_fix& f = fixes[k];
-    if (f.i < 0 || f.j < 0 || f.i >= g->n_nodes || f.j >= g->n_nodes || f.i == f.j)
-      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes: a node index out of range or i == j; nothing added");
-    if (!std::isfinite(f.t) || !std::isfinite(f.p[0]) || !std::isfinite(f.p[1]) || !std::isfinite(f.p[2]) || !std::isfinite(f.st) || !(f.st > 0.0) ||
-        !(f.t >= 0.0 && f.t <= 1.0))
-      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes: a non-finite value, st <= 0 or t outside [0, 1]; nothing added");
-  }
-  g->fixes.insert(g->fixes.end(), fixes, fixes + n);
-  if (n) g->dirty = true;
-  return MSFL_OK;
+  if (!g) return MSFL_BAD_ARG;
+  return graph_append(g, "msfl_graph_add_fixes", g->fixes, fixes, n, g->fixes.size() + g->fixes_info.size(), g->cfg.max_fixes,
+                      "the batch does not fit max_fixes",
+                      [](const msfl_graph_fix& f) { return graph_fix_point_ok(f.t, f.p) && std::isfinite(f.st) && f.st > 0.0; },
+                      "a non-finite value, st <= 0 or t outside [0, 1]", false);
 }
 
 msfl_status msfl_graph_add_edges_info(msfl_graph* g, const msfl_graph_edge_info* edges, int n) {
-  msfl_status s = enter(g); if (s) return s;
-  if (n < 0 || (n > 0 && !edges)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges_info: null array or negative count");
-  if ((long long)g->edges.size() + (long long)g->edges_info.size() + n > g->cfg.max_edges)
-    return fail(g, MSFL_CAPACITY, "msfl_graph_add_edges_info: plain and information edges together do not fit max_edges; nothing added");
-  for (int k = 0; k < n; k++) {
-    const msfl_graph_edge_info& e = edges[k];
-    if (e.i < 0 || e.j < 0 || e.i >= g->n_nodes || e.j >= g->n_nodes || e.i == e.j)
-      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges_info: a node index out of range or i == j; nothing added");
-    if (!graph_pose_ok(e.z) || !graph_sqrt_information_ok(e.sqrt_information, 36))
-      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_edges_info: a non-finite value, a zero quaternion or an all-zero sqrt_information; nothing added");
-  }
-  if (n == 0) return MSFL_OK;
-  HIPCHK(g, g->linfo.reserve(36 * sizeof(double) * (g->edges_info.size() + g->fixes_info.size() + (size_t)n)));
-  g->edges_info.insert(g->edges_info.end(), edges, edges + n);
-  g->dirty = true;
-  return MSFL_OK;
+  if (!g) return MSFL_BAD_ARG;
+  return graph_append(g, "msfl_graph_add_edges_info", g->edges_info, edges, n, g->edges.size() + g->edges_info.size(), g->cfg.max_edges,
+                      "plain and information edges together do not fit max_edges",
+                      [](const msfl_graph_edge_info& e) { return graph_pose_ok(e.z) && graph_sqrt_information_ok(e.sqrt_information, 36); },
+                      "a non-finite value, a zero quaternion or an all-zero sqrt_information", true);
 }
 
 msfl_status msfl_graph_add_fixes_info(msfl_graph* g, const msfl_graph_fix_info* fixes, int n) {
-  msfl_status s = enter(g); if (s) return s;
-  if (n < 0 || (n > 0 && !fixes)) return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes_info: null array or negative count");
-  if ((long long)g->fixes.size() + (long long)g->fixes_info.size() + n > g->cfg.max_fixes)
-    return fail(g, MSFL_CAPACITY, "msfl_graph_add_fixes_info: plain and information fixes together do not fit max_fixes; nothing added");
-  for (int k = 0; k < n; k++) {
-    const msfl_graph_fix_info& f = fixes[k];
-    if (f.i < 0 || f.j < 0 || f.i >= g->n_nodes || f.j >= g->n_nodes || f.i == f.j)
-      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes_info: a node index out of range or i == j; nothing added");
-    if (!std::isfinite(f.t) || !std::isfinite(f.p[0]) || !std::isfinite(f.p[1]) || !std::isfinite(f.p[2]) || !(f.t >= 0.0 && f.t <= 1.0) ||
-        !graph_sqrt_information_ok(f.sqrt_information, 9))
-      return fail(g, MSFL_BAD_ARG, "msfl_graph_add_fixes_info: a non-finite value, t outside [0, 1] or an all-zero sqrt_information; nothing added");
-  }
-  if (n == 0) return MSFL_OK;
-  HIPCHK(g, g->linfo.reserve(36 * sizeof(double) * (g->edges_info.size() + g->fixes_info.size() + (size_t)n)));
-  g->fixes_info.insert(g->fixes_info.end(), fixes, fixes + n);
-  g->dirty = true;
-  return MSFL_OK;
+  if (!g) return MSFL_BAD_ARG;
+  return graph_append(g, "msfl_graph_add_fixes_info", g->fixes_info, fixes, n, g->fixes.size() + g->fixes_info.size(), g->cfg.max_fixes,
+                      "plain and information fixes together do not fit max_fixes",
+                      [](const msfl_graph_fix_info& f) { return graph_fix_point_ok(f.t, f.p) && graph_sqrt_information_ok(f.sqrt_information, 9); },
+                      "a non-finite value, t outside [0, 1] or an all-zero sqrt_information", true);
 }
 
 // pure host arithmetic (msfl_graph_host.h): no graph object, no GPU call
@@ -440,7 +449,7 @@ msfl_status msfl_graph_cost(msfl_graph* g, double* cost) {
   if (g->dev.n_factors == 0) return MSFL_OK;
   hipStream_t st = g->stream;
   double* d_out = g->dev.tr_cost + std::max(1, g->cfg.max_num_iterations);
-  graph_enqueue_cost<false>(g, g->dev.x, g->cfg.huber_delta);
+  graph_enqueue_cost<false>(st, g->dev, g->dev.x, g->cfg.huber_delta);
   graph_launch(st, graph_cost_total_kernel, 1, kGraphVec, g->dev, d_out);
   HIPCHK(g, hipGetLastError());
   HIPCHK(g, hipMemcpyAsync(g->readback.p, d_out, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -489,28 +498,24 @@ msfl_status msfl_graph_optimize(msfl_graph* g, msfl_graph_summary* summary) {
   GraphState now{};
   for (int it = 0;; it++) {
     graph_launch(st, graph_commit_kernel, d.n_nodes * 7, kGraphVec, d);
-    graph_enqueue_linearize(g, o.huber);
+    graph_enqueue_linearize(st, d, o.huber);
     graph_launch(st, graph_assemble_kernel, F, kGraphBlock, d);
     if (it == 0) graph_launch(st, graph_scale_kernel, F * 6, kGraphVec, d, o.jacobi);
     graph_launch(st, graph_tr_begin_kernel, 1, kGraphVec, d, o);
     if (it < o.max_iter) {
       graph_launch(st, graph_damp_kernel, F, kGraphVec, d, o);
-      for (int l = 0; l < v.tail; l++) {
-        graph_launch(st, graph_cr_invert_kernel, v.n[l] / 2, kGraphBlock, d, v, l);
-        graph_launch(st, graph_cr_reduce_kernel, v.n[l + 1], kGraphBlock, d, v, l);
-      }
-      graph_launch(st, graph_cr_factor_tail_kernel, 1, kGraphVec, d, v);
-      graph_enqueue_solve(g);
+      graph_enqueue_factor<false>(st, d, v, GraphMarg{}, 0.0);
+      graph_enqueue_solve(st, d, v, 1, GraphSolveCols{});
       graph_launch(st, graph_dot_kernel, F, kGraphVec, d, n_part);
       for (int c = 0; c < cap; c++) {
         graph_launch(st, graph_matvec_kernel, F, kGraphVec, d, c, n_part, o.cg_tol, direct);
         graph_launch(st, graph_cg_update_kernel, F, kGraphVec, d, c, n_part);
-        graph_enqueue_solve(g);
+        graph_enqueue_solve(st, d, v, 1, GraphSolveCols{});
         graph_launch(st, graph_dot_kernel, F, kGraphVec, d, n_part);
       }
       graph_launch(st, graph_cg_end_kernel, 1, kGraphVec, d, n_part, o.cg_tol, direct);
       graph_launch(st, graph_plus_kernel, F, kGraphVec, d);
-      graph_enqueue_cost<true>(g, d.cand, o.huber);
+      graph_enqueue_cost<true>(st, d, d.cand, o.huber);
       graph_launch(st, graph_tr_kernel, 1, kGraphVec, d, o);
     }
     HIPCHK(g, hipGetLastError());
@@ -608,7 +613,7 @@ msfl_status msfl_graph_marginals_with(msfl_graph* g, const int* pairs, int n_pai
   const size_t per_col = ((size_t)6 * F + 2 * upper) * 36 + (size_t)12 * n_part;             // doubles per column node
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_cols), (size_t)opt.scratch_bytes / (per_col * sizeof(double))));
   int n_piv = 0;
-  for (int l = 0; l < v.tail; l++) n_piv += std::max(1, div_up(v.n[l] / 2, kGraphBlock));
+  for (int l = 0; l < v.tail; l++) n_piv += graph_invert_groups(v, l);
   const size_t state_bytes = sizeof(GraphState) + sizeof(GraphMargState) + (size_t)std::max(1, n_cols) * 6 * sizeof(GraphMargCol);
   HIPCHK(g, g->marg_work.reserve(((size_t)chunk * per_col + (size_t)std::max(1, n_piv)) * sizeof(double)));
   HIPCHK(g, g->marg_state.reserve(state_bytes));
@@ -627,8 +632,7 @@ msfl_status msfl_graph_marginals_with(msfl_graph* g, const int* pairs, int n_pai
   const int* d_pair_fa = d_ints + n_cols; const int* d_pair_col = d_pair_fa + n_pairs;
   double* d_out = out_mem == MSFL_MEM_HOST ? g->marg_out.as<double>() : out;
   auto carve_for = [&](int nc) {                           // the work area for a chunk of nc column nodes
-    double* w = g->marg_work.as<double>();
-    auto carve = [&w](size_t n) { double* p = w; w += n; return p; };
+    GraphCarve carve{g->marg_work.as<double>()};
     M.piv = carve((size_t)std::max(1, n_piv));
     const size_t blk = (size_t)nc * F * 36;
     M.X = carve(blk); M.R = carve(blk); M.Z = carve(blk); M.P[0] = carve(blk); M.P[1] = carve(blk); M.Q = carve(blk);
@@ -638,17 +642,10 @@ msfl_status msfl_graph_marginals_with(msfl_graph* g, const int* pairs, int n_pai
   };
   carve_for(0);
   // 1. linearise and assemble at the current poses, 2. the undamped level 0, 3. the factor half with the pivot test
-  const double huber = g->cfg.huber_delta;
-  if (d.n_plain) graph_launch(st, graph_linearize_kernel, d.n_plain, kGraphBlock, d, huber);
-  if (d.n_factors > d.n_plain) graph_launch(st, graph_linearize_info_kernel, d.n_factors - d.n_plain, kGraphBlock, d, huber);
+  graph_enqueue_linearize(st, d, g->cfg.huber_delta);
   graph_launch(st, graph_assemble_kernel, F, kGraphBlock, d);
   graph_launch(st, graph_marg_setup_kernel, F, kGraphVec, d);
-  for (int l = 0, first = 0; l < v.tail; l++) {
-    graph_launch(st, graph_marg_invert_kernel, v.n[l] / 2, kGraphBlock, d, v, l, M, first);
-    first += std::max(1, div_up(v.n[l] / 2, kGraphBlock));
-    graph_launch(st, graph_cr_reduce_kernel, v.n[l + 1], kGraphBlock, d, v, l);
-  }
-  graph_launch(st, graph_marg_factor_tail_kernel, 1, kGraphVec, d, v, M, n_piv, opt.min_pivot_ratio);
+  graph_enqueue_factor<true>(st, d, v, M, opt.min_pivot_ratio);
   HIPCHK(g, hipGetLastError());
   HIPCHK(g, hipMemcpyAsync(g->marg_read.p, M.st, sizeof(GraphMargState), hipMemcpyDeviceToHost, st));
   HIPCHK(g, hipStreamSynchronize(st));
@@ -661,30 +658,22 @@ msfl_status msfl_graph_marginals_with(msfl_graph* g, const int* pairs, int n_pai
     const int direct = g->gs.n_long == 0;
     const int cap = opt.max_cg_iterations > 0 ? opt.max_cg_iterations : 16 * g->gs.n_long + 8;
     const double tol = g->cfg.cg_tolerance;
-    auto launch2 = [&](auto kernel, int items, int block, int ny, auto... args) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)std::max(1, div_up(items, block)), (unsigned)ny), dim3(block), 0, st, args...);
-    };
-    auto solve = [&](const double* y0, double* x0) {      // x0 = T^-1 y0 for every column node of the chunk
-      for (int l = 0; l < v.tail; l++) launch2(graph_marg_rhs_kernel, v.n[l + 1], kGraphBlock, M.n_cols, d, v, l, M, y0);
-      launch2(graph_marg_tail_kernel, 1, kGraphVec, M.n_cols, d, v, M, y0, x0);
-      for (int l = v.tail - 1; l >= 0; l--) launch2(graph_marg_back_kernel, v.n[l], kGraphBlock, M.n_cols, d, v, l, M, y0, x0);
-    };
     if (n_cols == 0) graph_launch(st, graph_marg_gather_kernel, gather_items, kGraphVec, d, M, d_pair_fa, d_pair_col, n_pairs, 0, 0, d_out);
     for (int first = 0; first < n_cols; first += chunk) {
       carve_for(std::min(chunk, n_cols - first));
       M.col_free = d_ints + first; M.col = cols + (size_t)first * 6;
-      launch2(graph_marg_init_kernel, F * 36, kGraphVec, M.n_cols, d, M);
+      graph_launch_y(st, graph_marg_init_kernel, F * 36, kGraphVec, M.n_cols, d, M);
       if (direct) {
-        solve(M.R, M.X);
+        graph_enqueue_solve(st, d, v, M.n_cols, GraphMargCols{M, M.R, M.X});
       } else {
-        solve(M.R, M.Z);
-        launch2(graph_marg_dot_kernel, F, kGraphBlock, M.n_cols, d, M);
+        graph_enqueue_solve(st, d, v, M.n_cols, GraphMargCols{M, M.R, M.Z});
+        graph_launch_y(st, graph_marg_dot_kernel, F, kGraphBlock, M.n_cols, d, M);
         for (int it = 0; it < cap;) {                      // slices of at most 32 iterations, one small read between them
           for (const int end = std::min(cap, it + 32); it < end; it++) {
-            launch2(graph_marg_matvec_kernel, F, kGraphBlock, M.n_cols, d, M, it, tol);
-            launch2(graph_marg_update_kernel, F, kGraphBlock, M.n_cols, d, M, it);
-            solve(M.R, M.Z);
-            launch2(graph_marg_dot_kernel, F, kGraphBlock, M.n_cols, d, M);
+            graph_launch_y(st, graph_marg_matvec_kernel, F, kGraphBlock, M.n_cols, d, M, it, tol);
+            graph_launch_y(st, graph_marg_update_kernel, F, kGraphBlock, M.n_cols, d, M, it);
+            graph_enqueue_solve(st, d, v, M.n_cols, GraphMargCols{M, M.R, M.Z});
+            graph_launch_y(st, graph_marg_dot_kernel, F, kGraphBlock, M.n_cols, d, M);
           }
           graph_launch(st, graph_marg_check_kernel, M.n_cols * kGraphBlock, kGraphBlock, M, it, tol);
           HIPCHK(g, hipGetLastError());

@@ -3,12 +3,17 @@
 // exact solve of the block-tridiagonal part T (block cyclic reduction); long edges enter through the mat-vec only.
 //
 // Rules every kernel here keeps:
-//   - no floating-point atomics: factors are gathered per node in adjacency order, sums over nodes / factors go through
-//     graph_block_sum (a fixed LDS tree) into one partial per workgroup and graph_total (the same tree over the partials);
+//   - no floating-point atomics: factors are gathered per node in adjacency order, sums (maxima, minima) over nodes / factors go
+//     through graph_block_reduce (a fixed LDS tree) into one partial per workgroup and graph_total (the same tree over the partials);
 //   - no grid-wide barrier: a reduction level is a launch, the tail of the reduction is one workgroup;
 //   - a kernel that finds GraphState::done (or cg_done) set returns at once: the host enqueues a fixed launch pattern.
 // One lane owns one factor or one node; 6 x 6 blocks live in registers (fully unrolled loops), so the block kernels run 64 lanes
 // per workgroup and take what VGPRs they need.
+//
+// The solve (one right-hand side: the step) and the marginals (six per requested node: unit columns) share every body of the cyclic
+// reduction and the mat-vec's operator.  The bodies are templates over the column count W of a node's 6 x W right-hand side (1 or 6)
+// and over kPivot (the marginals' pivot test in the factor half); a small column-set type (GraphSolveCols, GraphMargCols) says where
+// the levels live and when the kernel may return.  What differs stays apart: the two CG state machines and their kernels.
 //
 // Factors are numbered edges, fixes, information edges, information fixes.  The first two kinds (k < n_plain) are the reference's and
 // keep their kernels; the information kinds (a full square-root information matrix L per factor) have kernels of their own over
@@ -61,15 +66,30 @@ struct GraphDev {
   const double* fac_L;               // [information factors x 36]: L row-major (6 x 6; a fix's 3 x 3 in the first 9); their fac_data: edge z[7]; fix t, p[3]
 };
 
-// ---- sums with one stated order --------------------------------------------------------------------------------------
-template <int kThreads, bool kMax>
-__device__ __forceinline__ double graph_block_sum(double v, double* lds) {
+// msfl_graph_marginals (section "marginals" below)
+struct GraphMargCol { double rz[2], rz0; int it, done; };
+struct GraphMargState { double min_pivot; int singular, pad; };
+struct GraphMarg {
+  int n_cols, n_part;                // column nodes of this chunk; workgroups per column node of the node-per-lane kernels
+  const int* col_free;               // [n_cols]: free index of the column node
+  double* X; double* R; double* Z; double* P[2]; double* Q;   // [n_cols x free x 36]
+  double* rhs; double* sol;          // [n_cols x (blocks - free) x 36]: levels 1.. of the reduction
+  double* part;                      // [2 x n_cols x 6 x n_part]: partials of p . q, then of r . z
+  GraphMargCol* col;                 // [n_cols x 6]
+  GraphMargState* st;
+  double* piv;                       // one partial minimum per workgroup of the invert launches, level after level
+};
+
+// ---- sums, maxima and minima with one stated order -------------------------------------------------------------------------
+enum { kGraphSum, kGraphMax, kGraphMin };
+template <int kThreads, int kOp>
+__device__ __forceinline__ double graph_block_reduce(double v, double* lds) {
   const int t = (int)threadIdx.x;
   lds[t] = v;
   __syncthreads();
 #pragma unroll
   for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] = kMax ? fmax(lds[t], lds[t + s]) : lds[t] + lds[t + s];
+    if (t < s) lds[t] = kOp == kGraphMax ? fmax(lds[t], lds[t + s]) : kOp == kGraphMin ? fmin(lds[t], lds[t + s]) : lds[t] + lds[t + s];
     __syncthreads();
   }
   const double out = lds[0];
@@ -77,11 +97,12 @@ __device__ __forceinline__ double graph_block_sum(double v, double* lds) {
   return out;
 }
 // every lane of the workgroup gets the total of a[0 .. n): lane t adds a[t], a[t + kThreads], ... in that order, then the tree
-template <int kThreads, bool kMax>
+template <int kThreads, int kOp>
 __device__ __forceinline__ double graph_total(const double* __restrict__ a, int n, double* lds) {
+  static_assert(kOp != kGraphMin, "a minimum has no neutral start here");
   double v = 0.0;
-  for (int i = (int)threadIdx.x; i < n; i += kThreads) v = kMax ? fmax(v, a[i]) : v + a[i];
-  return graph_block_sum<kThreads, kMax>(v, lds);
+  for (int i = (int)threadIdx.x; i < n; i += kThreads) v = kOp == kGraphMax ? fmax(v, a[i]) : v + a[i];
+  return graph_block_reduce<kThreads, kOp>(v, lds);
 }
 
 // ---- quaternions [x y z w] and 6 x 6 blocks (row-major) ------------------------------------------------------------------
@@ -117,45 +138,69 @@ __device__ __forceinline__ void graph_plus(const double* x, const double* d, dou
   }
 }
 
+template <int kN = 36>
 __device__ __forceinline__ void g6_load(const double* __restrict__ p, double* a) {
 #pragma unroll
-  for (int i = 0; i < 36; i++) a[i] = p[i];
+  for (int i = 0; i < kN; i++) a[i] = p[i];
 }
+template <int kN = 36>
 __device__ __forceinline__ void g6_store(double* __restrict__ p, const double* a) {
 #pragma unroll
-  for (int i = 0; i < 36; i++) p[i] = a[i];
+  for (int i = 0; i < kN; i++) p[i] = a[i];
 }
-// y (+)= A x, y (+)= A^T x
-template <bool kAcc, bool kTrans>
-__device__ __forceinline__ void g6_mv(const double* A, const double* x, double* y) {
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double s = kAcc ? y[i] : 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) s += (kTrans ? A[k * 6 + i] : A[i * 6 + k]) * x[k];
-    y[i] = s;
-  }
-}
-// C += sign * op(A) op(B): kTA / kTB transpose the operand
-template <bool kTA, bool kTB>
-__device__ __forceinline__ void g6_mma(const double* A, const double* B, double* Cm, double sign) {
+// The one block product: Y (6 x W, row-major) from op(A) (6 x 6) and op(X) (6 x W; kTX needs W = 6).  How the six-term sum s of an
+// entry meets Y is the caller's choice, because it rounds differently: kG6Set Y = s; kG6Chain the sum starts at Y and goes on term by
+// term; kG6Add Y += sign * s.
+enum { kG6Set, kG6Chain, kG6Add };
+template <int W, int kForm, bool kTA, bool kTX = false>
+__device__ __forceinline__ void g6_mul(const double* A, const double* X, double* Y, double sign = 1.0) {
+  static_assert(!kTX || W == 6, "only a square block can be transposed");
 #pragma unroll
   for (int i = 0; i < 6; i++)
 #pragma unroll
-    for (int j = 0; j < 6; j++) {
-      double s = 0.0;
+    for (int j = 0; j < W; j++) {
+      double s = kForm == kG6Chain ? Y[i * W + j] : 0.0;
 #pragma unroll
-      for (int k = 0; k < 6; k++) s += (kTA ? A[k * 6 + i] : A[i * 6 + k]) * (kTB ? B[j * 6 + k] : B[k * 6 + j]);
-      Cm[i * 6 + j] += sign * s;
+      for (int k = 0; k < 6; k++) s += (kTA ? A[k * 6 + i] : A[i * 6 + k]) * (kTX ? X[j * 6 + k] : X[k * W + j]);
+      if (kForm == kG6Add) Y[i * W + j] += sign * s;
+      else Y[i * W + j] = s;
     }
 }
-// inverse of a symmetric positive definite block through its Cholesky factor (a block that is not gives NaN: an invalid step)
-__device__ __forceinline__ void g6_inv_spd(double* a) {
+// y (+)= A x, y (+)= A^T x
+template <bool kAcc, bool kTrans>
+__device__ __forceinline__ void g6_mv(const double* A, const double* x, double* y) { g6_mul<1, kAcc ? kG6Chain : kG6Set, kTrans>(A, x, y); }
+// C += sign * op(A) op(B): kTA / kTB transpose the operand
+template <bool kTA, bool kTB>
+__device__ __forceinline__ void g6_mma(const double* A, const double* B, double* Cm, double sign) { g6_mul<6, kG6Add, kTA, kTB>(A, B, Cm, sign); }
+// In the bodies shared by the solve (W = 1) and the marginals (W = 6) the two column counts do not use the same form, and must not be
+// given the same one: the results of both paths are pinned to the bit (tests/golden/graph_parent_v1.npz and the byte tests).
+//   T = op(A) X:   W = 1 overwrites; W = 6 adds the sum to zero (a sum of -0.0 becomes +0.0);
+//   Q += op(A) X:  W = 1 continues Q's sum term by term; W = 6 adds the finished sum.
+// Q -= op(A) X is kG6Add with sign -1 for both: Q + (-1 s) and Q - s are the same operation.
+template <int W, bool kTA>
+__device__ __forceinline__ void g6_fresh(const double* A, const double* X, double* T) {
+  if (W == 1) { g6_mul<W, kG6Set, kTA>(A, X, T); return; }
+#pragma unroll
+  for (int i = 0; i < 6 * W; i++) T[i] = 0.0;
+  g6_mul<W, kG6Add, kTA>(A, X, T);
+}
+template <int W, bool kTA>
+__device__ __forceinline__ void g6_accum(const double* A, const double* X, double* Q) { g6_mul<W, W == 1 ? kG6Chain : kG6Add, kTA>(A, X, Q); }
+// inverse of a symmetric positive definite block through its Cholesky factor (a block that is not gives NaN: an invalid step).  With
+// kPivot it returns the block's smallest pivot^2 / a_jj (-1 when one is not finite); without, 1.
+template <bool kPivot>
+__device__ __forceinline__ double g6_inv_spd(double* a) {
+  double ratio = 1.0;
 #pragma unroll
   for (int j = 0; j < 6; j++) {                    // A = C C^T, C lower, in place
-    double d = a[j * 6 + j];
+    const double ajj = a[j * 6 + j];
+    double d = ajj;
 #pragma unroll
     for (int k = 0; k < j; k++) d -= a[j * 6 + k] * a[j * 6 + k];
+    if (kPivot) {
+      const double q = d / ajj;
+      ratio = fmin(ratio, isfinite(q) ? q : -1.0);
+    }
     d = sqrt(d);
     a[j * 6 + j] = d;
 #pragma unroll
@@ -191,6 +236,7 @@ __device__ __forceinline__ void g6_inv_spd(double* a) {
       for (int k = i; k < 6; k++) s += w[k * 6 + i] * w[k * 6 + j];
       a[i * 6 + j] = s; a[j * 6 + i] = s;
     }
+  return ratio;
 }
 
 // ---- factors -----------------------------------------------------------------------------------------------------------
@@ -291,17 +337,8 @@ __global__ __launch_bounds__(kGraphBlock) void graph_linearize_kernel(GraphDev G
   G.fcost[k] = hr;
 }
 
-// cost of every plain block at `x` into fcost; with kModel also the block's share of -m . (r + m / 2), m = Js step
-template <bool kModel>
-__global__ __launch_bounds__(kGraphBlock) void graph_cost_kernel(GraphDev G, const double* __restrict__ x, double huber) {
-  if (kModel && G.st->done) return;
-  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k >= G.n_plain) return;
-  double r[6], hr;
-  graph_factor<false>(G, x, k, r, nullptr, nullptr);
-  (void)graph_huber(r, huber, &hr);
-  G.fcost[k] = hr;
-  if (!kModel) return;
+// factor k's share of the model cost change -m . (r + m / 2), m = Js step, from its linearised record
+__device__ __forceinline__ double graph_model_share(const GraphDev& G, int k) {
   const double* Jk = G.J + (size_t)k * kGraphJ;
   double m[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -316,7 +353,21 @@ __global__ __launch_bounds__(kGraphBlock) void graph_cost_kernel(GraphDev G, con
   double s = 0.0;
 #pragma unroll
   for (int c = 0; c < 6; c++) s += m[c] * (Jk[72 + c] + 0.5 * m[c]);
-  G.fmodel[k] = -s;
+  return -s;
+}
+
+// cost of every plain block at `x` into fcost; with kModel also the block's share of the model cost change
+template <bool kModel>
+__global__ __launch_bounds__(kGraphBlock) void graph_cost_kernel(GraphDev G, const double* __restrict__ x, double huber) {
+  if (kModel && G.st->done) return;
+  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (k >= G.n_plain) return;
+  double r[6], hr;
+  graph_factor<false>(G, x, k, r, nullptr, nullptr);
+  (void)graph_huber(r, huber, &hr);
+  G.fcost[k] = hr;
+  if (!kModel) return;
+  G.fmodel[k] = graph_model_share(G, k);
 }
 
 // ---- information factors (docs/kernels/graph.md): r = L e with a full square-root information matrix per factor -----------------------
@@ -447,26 +498,6 @@ __global__ __launch_bounds__(kGraphBlock) void graph_linearize_info_kernel(Graph
   G.fcost[k] = hr;
 }
 
-// factor k's share of the model cost change, as graph_cost_kernel<true> computes it from the linearised record (that kernel keeps its
-// own copy: calling this from it moves its register allocation from 104 to 106 VGPRs)
-__device__ __forceinline__ double graph_model_share(const GraphDev& G, int k) {
-  const double* Jk = G.J + (size_t)k * kGraphJ;
-  double m[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int side = 0; side < 2; side++) {
-    const int f = G.free_of[G.fac_ij[2 * k + side]];
-    if (f < 0) continue;
-    double sx[6];
-#pragma unroll
-    for (int c = 0; c < 6; c++) sx[c] = G.scale[(size_t)f * 6 + c] * G.xs[(size_t)f * 6 + c];
-    g6_mv<true, false>(Jk + 36 * side, sx, m);
-  }
-  double s = 0.0;
-#pragma unroll
-  for (int c = 0; c < 6; c++) s += m[c] * (Jk[72 + c] + 0.5 * m[c]);
-  return -s;
-}
-
 // graph_cost_kernel for the information factors
 template <bool kModel>
 __global__ __launch_bounds__(kGraphBlock) void graph_cost_info_kernel(GraphDev G, const double* __restrict__ x, double huber) {
@@ -543,9 +574,9 @@ __global__ __launch_bounds__(kGraphVec) void graph_tr_begin_kernel(GraphDev G, G
   __shared__ double lds[kGraphVec];
   GraphState* s = G.st;
   if (s->done) return;
-  const double xx = graph_total<kGraphVec, false>(G.nxx, G.n_free, lds);
-  const double gmax = graph_total<kGraphVec, true>(G.ngmax, G.n_free, lds);
-  const double cost = s->first ? graph_total<kGraphVec, false>(G.fcost, G.n_factors, lds) : 0.0;
+  const double xx = graph_total<kGraphVec, kGraphSum>(G.nxx, G.n_free, lds);
+  const double gmax = graph_total<kGraphVec, kGraphMax>(G.ngmax, G.n_free, lds);
+  const double cost = s->first ? graph_total<kGraphVec, kGraphSum>(G.fcost, G.n_factors, lds) : 0.0;
   if (threadIdx.x != 0) return;
   s->commit = 0;
   s->x_norm = sqrt(xx); s->gmax = gmax;
@@ -582,12 +613,15 @@ __global__ __launch_bounds__(kGraphVec) void graph_damp_kernel(GraphDev G, Graph
 }
 
 // ---- block cyclic reduction of T x = y: level l keeps its even blocks; odd block k is x_k = D_k^-1 (y_k - L_k x_k-1 - L_k+1^T x_k+1) ----
-__device__ __forceinline__ void graph_cr_invert_node(const GraphDev& G, const GraphLevels& V, int l, int j) {
+// inverts odd block 2 j + 1 of level l; returns g6_inv_spd's pivot ratio
+template <bool kPivot>
+__device__ __forceinline__ double graph_cr_invert_node(const GraphDev& G, const GraphLevels& V, int l, int j) {
   const int k = V.n[l] == 1 ? 0 : 2 * j + 1;       // the last level's single block is inverted too
   double a[36];
   g6_load(G.D + (size_t)(V.off[l] + k) * 36, a);
-  g6_inv_spd(a);
+  const double ratio = g6_inv_spd<kPivot>(a);
   g6_store(G.Dinv + (size_t)(V.ioff[l] + j) * 36, a);
+  return ratio;
 }
 // block m of level l + 1 from block k = 2 m of level l:
 //   D' = D_k - L_k Dinv_k-1 L_k^T - L_k+1^T Dinv_k+1 L_k+1,   L' = -L_k Dinv_k-1 L_k-1
@@ -622,105 +656,148 @@ __device__ __forceinline__ void graph_cr_reduce_node(const GraphDev& G, const Gr
   g6_store(G.D + (size_t)(V.off[l + 1] + m) * 36, Dn);
   g6_store(G.L + (size_t)(V.off[l + 1] + m) * 36, Ln);
 }
-// right-hand side of block m of level l + 1: y' = y_k - L_k Dinv_k-1 y_k-1 - L_k+1^T Dinv_k+1 y_k+1
+// right-hand side (6 x W per block) of block m of level l + 1: y' = y_k - L_k Dinv_k-1 y_k-1 - L_k+1^T Dinv_k+1 y_k+1
+template <int W>
 __device__ __forceinline__ void graph_cr_rhs_node(const GraphDev& G, const GraphLevels& V, int l, int m, const double* __restrict__ y,
                                                   double* __restrict__ yn) {
   const int k = 2 * m, n = V.n[l];
   const double* Ll = G.L + (size_t)V.off[l] * 36; const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
-  double o[6], t[6], u[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++) o[i] = y[(size_t)k * 6 + i];
+  double o[6 * W], t[6 * W];
+  g6_load<6 * W>(y + (size_t)k * 6 * W, o);
   if (k >= 1) {
-    g6_mv<false, false>(Il + (size_t)(m - 1) * 36, y + (size_t)(k - 1) * 6, t);
-    g6_mv<false, false>(Ll + (size_t)k * 36, t, u);
-#pragma unroll
-    for (int i = 0; i < 6; i++) o[i] -= u[i];
+    g6_fresh<W, false>(Il + (size_t)(m - 1) * 36, y + (size_t)(k - 1) * 6 * W, t);
+    g6_mul<W, kG6Add, false>(Ll + (size_t)k * 36, t, o, -1.0);
   }
   if (k + 1 < n) {
-    g6_mv<false, false>(Il + (size_t)m * 36, y + (size_t)(k + 1) * 6, t);
-    g6_mv<false, true>(Ll + (size_t)(k + 1) * 36, t, u);
-#pragma unroll
-    for (int i = 0; i < 6; i++) o[i] -= u[i];
+    g6_fresh<W, false>(Il + (size_t)m * 36, y + (size_t)(k + 1) * 6 * W, t);
+    g6_mul<W, kG6Add, true>(Ll + (size_t)(k + 1) * 36, t, o, -1.0);
   }
-#pragma unroll
-  for (int i = 0; i < 6; i++) yn[(size_t)m * 6 + i] = o[i];
+  g6_store<6 * W>(yn + (size_t)m * 6 * W, o);
 }
 // solution of block k of level l from the solution xn of level l + 1 (even blocks copy, odd blocks substitute)
+template <int W>
 __device__ __forceinline__ void graph_cr_back_node(const GraphDev& G, const GraphLevels& V, int l, int k, const double* __restrict__ y,
                                                    const double* __restrict__ xn, double* __restrict__ x) {
   const int n = V.n[l], m = k >> 1;
+  double t[6 * W], b[6 * W];
   if (!(k & 1)) {
-#pragma unroll
-    for (int i = 0; i < 6; i++) x[(size_t)k * 6 + i] = xn[(size_t)m * 6 + i];
+    g6_load<6 * W>(xn + (size_t)m * 6 * W, t);
+    g6_store<6 * W>(x + (size_t)k * 6 * W, t);
     return;
   }
   const double* Ll = G.L + (size_t)V.off[l] * 36; const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
-  double t[6], o[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++) t[i] = y[(size_t)k * 6 + i];
-  g6_mv<false, false>(Ll + (size_t)k * 36, xn + (size_t)m * 6, o);
-#pragma unroll
-  for (int i = 0; i < 6; i++) t[i] -= o[i];
-  if (k + 1 < n) {
-    g6_mv<false, true>(Ll + (size_t)(k + 1) * 36, xn + (size_t)(m + 1) * 6, o);
-#pragma unroll
-    for (int i = 0; i < 6; i++) t[i] -= o[i];
-  }
-  g6_mv<false, false>(Il + (size_t)m * 36, t, o);
-#pragma unroll
-  for (int i = 0; i < 6; i++) x[(size_t)k * 6 + i] = o[i];
+  g6_load<6 * W>(y + (size_t)k * 6 * W, t);
+  g6_mul<W, kG6Add, false>(Ll + (size_t)k * 36, xn + (size_t)m * 6 * W, t, -1.0);
+  if (k + 1 < n) g6_mul<W, kG6Add, true>(Ll + (size_t)(k + 1) * 36, xn + (size_t)(m + 1) * 6 * W, t, -1.0);
+  g6_fresh<W, false>(Il + (size_t)m * 36, t, b);
+  g6_store<6 * W>(x + (size_t)k * 6 * W, b);
 }
-__device__ __forceinline__ const double* graph_level_rhs(const GraphDev& G, const GraphLevels& V, int l) { return l == 0 ? G.r : G.rhs + (size_t)V.off[l] * 6; }
-__device__ __forceinline__ double* graph_level_sol(const GraphDev& G, const GraphLevels& V, int l) { return l == 0 ? G.z : G.sol + (size_t)V.off[l] * 6; }
 
-// the factor half, once per LM iteration: invert the odd blocks of level l, then form level l + 1
-__global__ __launch_bounds__(kGraphBlock) void graph_cr_invert_kernel(GraphDev G, GraphLevels V, int l) {
+// The right-hand sides the kernels of the right-hand-side half work on: W columns, where level l lives, how many lanes the per-level
+// kernels run, and when there is nothing left to do.
+// The solve's one column: r -> z at level 0, levels 1.. in G.rhs / G.sol; returns with the LM loop or the CG.
+struct GraphSolveCols {
+  static constexpr int W = 1, kLanes = kGraphVec;
+  __device__ bool done(const GraphDev& G) const { return G.st->done || G.st->cg_done; }
+  __device__ double* rhs_up(const GraphDev& G, const GraphLevels& V, int l) const { return G.rhs + (size_t)V.off[l] * 6; }
+  __device__ const double* rhs(const GraphDev& G, const GraphLevels& V, int l) const { return l == 0 ? G.r : rhs_up(G, V, l); }
+  __device__ double* sol(const GraphDev& G, const GraphLevels& V, int l) const { return l == 0 ? G.z : G.sol + (size_t)V.off[l] * 6; }
+};
+// the six columns of column node c are all done
+__device__ __forceinline__ bool graph_marg_all_done(const GraphMarg& M, int c) {
+  int d = 1;
+#pragma unroll
+  for (int j = 0; j < 6; j++) d &= M.col[c * 6 + j].done;
+  return d != 0;
+}
+// The marginals' six columns of column node blockIdx.y: y0 -> x0 at level 0 ([n_cols x free x 36]), levels 1.. in M.rhs / M.sol; returns
+// when the node's six CGs are done.  64 lanes: a lane carries 6 x 6 blocks and takes 250 - 256 VGPRs.
+struct GraphMargCols {
+  static constexpr int W = 6, kLanes = kGraphBlock;
+  GraphMarg M; const double* y0; double* x0;
+  __device__ bool done(const GraphDev&) const { return graph_marg_all_done(M, (int)blockIdx.y); }
+  __device__ size_t at(const GraphDev& G, const GraphLevels& V, int l) const {
+    return l == 0 ? (size_t)blockIdx.y * G.n_free * 36 : ((size_t)blockIdx.y * (size_t)(V.off[V.count - 1] + 1 - G.n_free) + (size_t)(V.off[l] - G.n_free)) * 36;
+  }
+  __device__ double* rhs_up(const GraphDev& G, const GraphLevels& V, int l) const { return M.rhs + at(G, V, l); }
+  __device__ const double* rhs(const GraphDev& G, const GraphLevels& V, int l) const { return l == 0 ? y0 + at(G, V, 0) : rhs_up(G, V, l); }
+  __device__ double* sol(const GraphDev& G, const GraphLevels& V, int l) const { return (l == 0 ? x0 : M.sol) + at(G, V, l); }
+};
+
+// the factor half, once per LM iteration: invert the odd blocks of level l, then form level l + 1.  With kPivot (the marginals) the
+// workgroup's smallest pivot ratio goes to M.piv[first + blockIdx.x]; without, M and first are not looked at.
+template <bool kPivot>
+__global__ __launch_bounds__(kGraphBlock) void graph_cr_invert_kernel(GraphDev G, GraphLevels V, int l, GraphMarg M, int first) {
   if (G.st->done) return;
   const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (j < V.n[l] / 2) graph_cr_invert_node(G, V, l, j);
+  double ratio = 1.0;
+  if (j < V.n[l] / 2) ratio = graph_cr_invert_node<kPivot>(G, V, l, j);
+  if constexpr (kPivot) {
+    __shared__ double lds[kGraphBlock];
+    ratio = graph_block_reduce<kGraphBlock, kGraphMin>(ratio, lds);
+    if (threadIdx.x == 0) M.piv[first + blockIdx.x] = ratio;
+  }
 }
 __global__ __launch_bounds__(kGraphBlock) void graph_cr_reduce_kernel(GraphDev G, GraphLevels V, int l) {
   if (G.st->done) return;
   const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (m < V.n[l + 1]) graph_cr_reduce_node(G, V, l, m);
 }
-// one workgroup finishes the factor half from level V.tail on
-__global__ __launch_bounds__(kGraphVec) void graph_cr_factor_tail_kernel(GraphDev G, GraphLevels V) {
+// one workgroup finishes the factor half from level V.tail on.  With kPivot it makes the pivot test: the minimum over its own blocks and
+// the n_piv partials of the launches before it, into M.st.
+template <bool kPivot>
+__global__ __launch_bounds__(kGraphVec) void graph_cr_factor_tail_kernel(GraphDev G, GraphLevels V, GraphMarg M, int n_piv, double min_ratio) {
   if (G.st->done) return;
+  double ratio = 1.0;
   for (int l = V.tail; l < V.count; l++) {
     const int inv = V.n[l] == 1 ? 1 : V.n[l] / 2;
-    for (int j = (int)threadIdx.x; j < inv; j += kGraphVec) graph_cr_invert_node(G, V, l, j);
+    for (int j = (int)threadIdx.x; j < inv; j += kGraphVec) ratio = fmin(ratio, graph_cr_invert_node<kPivot>(G, V, l, j));
     __syncthreads();
     if (l + 1 < V.count)
       for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec) graph_cr_reduce_node(G, V, l, m);
     __syncthreads();
   }
+  if constexpr (kPivot) {
+    __shared__ double lds[kGraphVec];
+    for (int i = (int)threadIdx.x; i < n_piv; i += kGraphVec) ratio = fmin(ratio, M.piv[i]);
+    ratio = graph_block_reduce<kGraphVec, kGraphMin>(ratio, lds);
+    if (threadIdx.x == 0) { M.st->min_pivot = ratio; M.st->singular = ratio >= min_ratio ? 0 : 1; }
+  }
 }
-// the right-hand-side half, once per CG iteration: z = T^-1 r
-__global__ __launch_bounds__(kGraphVec) void graph_cr_rhs_kernel(GraphDev G, GraphLevels V, int l) {
-  if (G.st->done || G.st->cg_done) return;
+// the right-hand-side half, once per CG iteration: x0 = T^-1 y0 for the columns of C
+template <class C>
+__global__ __launch_bounds__(C::kLanes) void graph_cr_rhs_kernel(GraphDev G, GraphLevels V, int l, C cols) {
+  if (cols.done(G)) return;
   const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (m < V.n[l + 1]) graph_cr_rhs_node(G, V, l, m, graph_level_rhs(G, V, l), G.rhs + (size_t)V.off[l + 1] * 6);
+  if (m < V.n[l + 1]) graph_cr_rhs_node<C::W>(G, V, l, m, cols.rhs(G, V, l), cols.rhs_up(G, V, l + 1));
 }
-__global__ __launch_bounds__(kGraphVec) void graph_cr_tail_kernel(GraphDev G, GraphLevels V) {
-  if (G.st->done || G.st->cg_done) return;
+template <class C>
+__global__ __launch_bounds__(kGraphVec) void graph_cr_tail_kernel(GraphDev G, GraphLevels V, C cols) {
+  constexpr int W = C::W;
+  if (cols.done(G)) return;
   const int last = V.count - 1;
   for (int l = V.tail; l < last; l++) {
-    for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec) graph_cr_rhs_node(G, V, l, m, graph_level_rhs(G, V, l), G.rhs + (size_t)V.off[l + 1] * 6);
+    for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec) graph_cr_rhs_node<W>(G, V, l, m, cols.rhs(G, V, l), cols.rhs_up(G, V, l + 1));
     __syncthreads();
   }
-  if (threadIdx.x == 0) g6_mv<false, false>(G.Dinv + (size_t)V.ioff[last] * 36, graph_level_rhs(G, V, last), graph_level_sol(G, V, last));
+  if (threadIdx.x == 0) {
+    double b[6 * W], t[6 * W];
+    g6_load<6 * W>(cols.rhs(G, V, last), b);
+    g6_fresh<W, false>(G.Dinv + (size_t)V.ioff[last] * 36, b, t);
+    g6_store<6 * W>(cols.sol(G, V, last), t);
+  }
   __syncthreads();
   for (int l = last - 1; l >= V.tail; l--) {
     for (int k = (int)threadIdx.x; k < V.n[l]; k += kGraphVec)
-      graph_cr_back_node(G, V, l, k, graph_level_rhs(G, V, l), graph_level_sol(G, V, l + 1), graph_level_sol(G, V, l));
+      graph_cr_back_node<W>(G, V, l, k, cols.rhs(G, V, l), cols.sol(G, V, l + 1), cols.sol(G, V, l));
     __syncthreads();
   }
 }
-__global__ __launch_bounds__(kGraphVec) void graph_cr_back_kernel(GraphDev G, GraphLevels V, int l) {
-  if (G.st->done || G.st->cg_done) return;
+template <class C>
+__global__ __launch_bounds__(C::kLanes) void graph_cr_back_kernel(GraphDev G, GraphLevels V, int l, C cols) {
+  if (cols.done(G)) return;
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k < V.n[l]) graph_cr_back_node(G, V, l, k, graph_level_rhs(G, V, l), graph_level_sol(G, V, l + 1), graph_level_sol(G, V, l));
+  if (k < V.n[l]) graph_cr_back_node<C::W>(G, V, l, k, cols.rhs(G, V, l), cols.sol(G, V, l + 1), cols.sol(G, V, l));
 }
 
 // ---- PCG ---------------------------------------------------------------------------------------------------------------
@@ -732,8 +809,51 @@ __global__ __launch_bounds__(kGraphVec) void graph_dot_kernel(GraphDev G, int n_
   double s = 0.0;
   if (f < G.n_free)
     for (int i = 0; i < 6; i++) s += G.r[(size_t)f * 6 + i] * G.z[(size_t)f * 6 + i];
-  s = graph_block_sum<kGraphVec, false>(s, lds);
+  s = graph_block_reduce<kGraphVec, kGraphSum>(s, lds);
   if (threadIdx.x == 0) G.part[n_part + blockIdx.x] = s;
+}
+
+// the CG direction of free node f over W columns (6 x W): column j is z + beta_j p_old, z alone in the first iteration
+template <int W>
+__device__ __forceinline__ void graph_cg_dir(const double* __restrict__ z, const double* __restrict__ po, int f, const double* beta, bool first, double* p) {
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int j = 0; j < W; j++) p[i * W + j] = z[((size_t)f * 6 + i) * W + j] + (first ? 0.0 : beta[j] * po[((size_t)f * 6 + i) * W + j]);
+}
+// q = A p for free node f and W columns, p = graph_cg_dir (left in pf for f itself): D_f p_f + L_f p_f-1 + L_f+1^T p_f+1, then the long
+// factors in adjacency order, s_f . Jf^T (Jo (s_o . p_o))
+template <int W>
+__device__ __forceinline__ void graph_apply(const GraphDev& G, int f, const double* z, const double* po, const double* beta, bool first, double* pf, double* q) {
+  double pm[6 * W], t[6 * W];
+  graph_cg_dir<W>(z, po, f, beta, first, pf);
+  g6_fresh<W, false>(G.D + (size_t)f * 36, pf, q);
+  if (f > 0) {
+    graph_cg_dir<W>(z, po, f - 1, beta, first, pm);
+    g6_accum<W, false>(G.L + (size_t)f * 36, pm, q);
+  }
+  if (f + 1 < G.n_free) {
+    graph_cg_dir<W>(z, po, f + 1, beta, first, pm);
+    g6_accum<W, true>(G.L + (size_t)(f + 1) * 36, pm, q);
+  }
+  const double* sf = G.scale + (size_t)f * 6;
+  for (int e = G.ladj_off[f]; e < G.ladj_off[f + 1]; e++) {
+    const int k = G.ladj[e] >> 1, side = G.ladj[e] & 1;
+    const int fo = G.free_of[G.fac_ij[2 * k + (side ^ 1)]];
+    const double* Jk = G.J + (size_t)k * kGraphJ;
+    const double* so = G.scale + (size_t)fo * 6;
+    graph_cg_dir<W>(z, po, fo, beta, first, pm);
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = 0; j < W; j++) pm[i * W + j] *= so[i];
+    g6_fresh<W, false>(Jk + 36 * (side ^ 1), pm, t);
+    g6_fresh<W, true>(Jk + 36 * side, t, pm);
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = 0; j < W; j++) q[i * W + j] += sf[i] * pm[i * W + j];
+  }
 }
 
 // CG iteration `it`: the convergence test on r . z, p = z + beta p (written to p[it & 1], read from the other), q = A p, partial p . q
@@ -742,7 +862,7 @@ __global__ __launch_bounds__(kGraphVec) void graph_matvec_kernel(GraphDev G, int
   GraphState* s = G.st;
   if (s->done || s->cg_done) return;
   const int c = it & 1;
-  const double rz = graph_total<kGraphVec, false>(G.part + n_part, n_part, lds);
+  const double rz = graph_total<kGraphVec, kGraphSum>(G.part + n_part, n_part, lds);
   const double rz0 = it == 0 ? rz : s->rz0;
   const bool stop = it == 0 ? !(rz > 0.0) : (!direct && sqrt(rz) <= cg_tol * sqrt(rz0));
   if (stop) {
@@ -755,37 +875,12 @@ __global__ __launch_bounds__(kGraphVec) void graph_matvec_kernel(GraphDev G, int
   const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   double pq = 0.0;
   if (f < G.n_free) {
-    double pf[6], pm[6], q[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) pf[i] = G.z[(size_t)f * 6 + i] + (it == 0 ? 0.0 : beta * po[(size_t)f * 6 + i]);
-    g6_mv<false, false>(G.D + (size_t)f * 36, pf, q);
-    if (f > 0) {
-#pragma unroll
-      for (int i = 0; i < 6; i++) pm[i] = G.z[(size_t)(f - 1) * 6 + i] + (it == 0 ? 0.0 : beta * po[(size_t)(f - 1) * 6 + i]);
-      g6_mv<true, false>(G.L + (size_t)f * 36, pm, q);
-    }
-    if (f + 1 < G.n_free) {
-#pragma unroll
-      for (int i = 0; i < 6; i++) pm[i] = G.z[(size_t)(f + 1) * 6 + i] + (it == 0 ? 0.0 : beta * po[(size_t)(f + 1) * 6 + i]);
-      g6_mv<true, true>(G.L + (size_t)(f + 1) * 36, pm, q);
-    }
-    const double* sf = G.scale + (size_t)f * 6;
-    for (int e = G.ladj_off[f]; e < G.ladj_off[f + 1]; e++) {       // long factors: s_f . Jf^T (Jo (s_o . p_o)), in adjacency order
-      const int k = G.ladj[e] >> 1, side = G.ladj[e] & 1;
-      const int fo = G.free_of[G.fac_ij[2 * k + (side ^ 1)]];
-      const double* Jk = G.J + (size_t)k * kGraphJ;
-      double t[6], u[6];
-#pragma unroll
-      for (int i = 0; i < 6; i++) pm[i] = G.scale[(size_t)fo * 6 + i] * (G.z[(size_t)fo * 6 + i] + (it == 0 ? 0.0 : beta * po[(size_t)fo * 6 + i]));
-      g6_mv<false, false>(Jk + 36 * (side ^ 1), pm, t);
-      g6_mv<false, true>(Jk + 36 * side, t, u);
-#pragma unroll
-      for (int i = 0; i < 6; i++) q[i] += sf[i] * u[i];
-    }
+    double pf[6], q[6];
+    graph_apply<1>(G, f, G.z, po, &beta, it == 0, pf, q);
 #pragma unroll
     for (int i = 0; i < 6; i++) { pn[(size_t)f * 6 + i] = pf[i]; G.q[(size_t)f * 6 + i] = q[i]; pq += pf[i] * q[i]; }
   }
-  pq = graph_block_sum<kGraphVec, false>(pq, lds);
+  pq = graph_block_reduce<kGraphVec, kGraphSum>(pq, lds);
   if (threadIdx.x == 0) G.part[blockIdx.x] = pq;
 }
 
@@ -794,7 +889,7 @@ __global__ __launch_bounds__(kGraphVec) void graph_cg_update_kernel(GraphDev G, 
   __shared__ double lds[kGraphVec];
   GraphState* s = G.st;
   if (s->done || s->cg_done) return;
-  const double pq = graph_total<kGraphVec, false>(G.part, n_part, lds);
+  const double pq = graph_total<kGraphVec, kGraphSum>(G.part, n_part, lds);
   const double alpha = s->rz[it & 1] / pq;
   const double* p = G.p[it & 1];
   const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -811,7 +906,7 @@ __global__ __launch_bounds__(kGraphVec) void graph_cg_end_kernel(GraphDev G, int
   __shared__ double lds[kGraphVec];
   GraphState* s = G.st;
   if (s->done) return;
-  const double rz = graph_total<kGraphVec, false>(G.part + n_part, n_part, lds);
+  const double rz = graph_total<kGraphVec, kGraphSum>(G.part + n_part, n_part, lds);
   if (threadIdx.x != 0) return;
   if (!s->cg_done && !direct && !(sqrt(rz) <= cg_tol * sqrt(s->rz0))) s->cg_unconverged += 1;
   s->cg_total += s->cg_it;
@@ -838,9 +933,9 @@ __global__ __launch_bounds__(kGraphVec) void graph_tr_kernel(GraphDev G, GraphOp
   __shared__ double lds[kGraphVec];
   GraphState* s = G.st;
   if (s->done) return;
-  const double model = graph_total<kGraphVec, false>(G.fmodel, G.n_factors, lds);
-  const double cand_cost = graph_total<kGraphVec, false>(G.fcost, G.n_factors, lds);
-  const double step2 = graph_total<kGraphVec, false>(G.nstep, G.n_free, lds);
+  const double model = graph_total<kGraphVec, kGraphSum>(G.fmodel, G.n_factors, lds);
+  const double cand_cost = graph_total<kGraphVec, kGraphSum>(G.fcost, G.n_factors, lds);
+  const double step2 = graph_total<kGraphVec, kGraphSum>(G.nstep, G.n_free, lds);
   if (threadIdx.x != 0) return;
   const int slot = s->n_trace++;
   const bool valid = isfinite(model) && isfinite(step2) && model > 0.0;
@@ -877,7 +972,7 @@ __global__ __launch_bounds__(kGraphVec) void graph_tr_kernel(GraphDev G, GraphOp
 // msfl_graph_cost: the total of fcost into out[0]
 __global__ __launch_bounds__(kGraphVec) void graph_cost_total_kernel(GraphDev G, double* out) {
   __shared__ double lds[kGraphVec];
-  const double c = graph_total<kGraphVec, false>(G.fcost, G.n_factors, lds);
+  const double c = graph_total<kGraphVec, kGraphSum>(G.fcost, G.n_factors, lds);
   if (threadIdx.x == 0) out[0] = c;
 }
 
@@ -885,87 +980,14 @@ __global__ __launch_bounds__(kGraphVec) void graph_cost_total_kernel(GraphDev G,
 // Sigma = H^-1 at the current poses, H = J^T J undamped.  With the Jacobi scale S of this linearisation Hs = S H S is factored as the
 // solve factors its damped T, and Hs X = E_b is solved for the six unit columns of every requested free column node b by the same PCG
 // (chain part by cyclic reduction, long factors in the mat-vec); Sigma_ab = S_a X_a S_b.  blockIdx.y selects the column node, one lane
-// owns one free node and carries its 6 x 6 block (row = the node's coordinate, column = which of b's six unit vectors) through g6_mma
-// where the single-column kernels use g6_mv, so Dinv and L are loaded once per six columns.  Each of the six columns is a CG of its own
-// (GraphMargCol); sums per (column, workgroup) in index order; a converged column freezes; a workgroup whose six are done returns.
-struct GraphMargCol { double rz[2], rz0; int it, done; };
-struct GraphMargState { double min_pivot; int singular, pad; };
-struct GraphMarg {
-  int n_cols, n_part;                // column nodes of this chunk; workgroups per column node of the node-per-lane kernels
-  const int* col_free;               // [n_cols]: free index of the column node
-  double* X; double* R; double* Z; double* P[2]; double* Q;   // [n_cols x free x 36]
-  double* rhs; double* sol;          // [n_cols x (blocks - free) x 36]: levels 1.. of the reduction
-  double* part;                      // [2 x n_cols x 6 x n_part]: partials of p . q, then of r . z
-  GraphMargCol* col;                 // [n_cols x 6]
-  GraphMargState* st;
-  double* piv;                       // one partial minimum per workgroup of the invert launches, level after level
-};
+// owns one free node and carries its 6 x 6 block (row = the node's coordinate, column = which of b's six unit vectors) through the W = 6
+// instances of the reduction's bodies and of graph_apply, so Dinv and L are loaded once per six columns; the factor half is the solve's
+// with kPivot.  Each of the six columns is a CG of its own (GraphMargCol), so the CG kernels below are the marginals' own: sums per
+// (column, workgroup) in index order; a converged column freezes; a workgroup whose six are done returns.
 
-// g6_inv_spd that also returns the smallest pivot^2 / a_jj of its block (-1 when one is not finite)
-__device__ __forceinline__ double g6_inv_spd_pivot(double* a) {
-  double ratio = 1.0;
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    const double ajj = a[j * 6 + j];
-    double d = ajj;
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= a[j * 6 + k] * a[j * 6 + k];
-    const double q = d / ajj;
-    ratio = fmin(ratio, isfinite(q) ? q : -1.0);
-    d = sqrt(d);
-    a[j * 6 + j] = d;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double s = a[i * 6 + j];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= a[i * 6 + k] * a[j * 6 + k];
-      a[i * 6 + j] = s / d;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    a[j * 6 + j] = 1.0 / a[j * 6 + j];
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double s = 0.0;
-#pragma unroll
-      for (int k = j; k < i; k++) s -= a[i * 6 + k] * (k == j ? a[j * 6 + j] : a[j * 6 + k]);
-      a[j * 6 + i] = s / a[i * 6 + i];
-    }
-  }
-  double w[36];
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-#pragma unroll
-    for (int j = 0; j < 6; j++) w[i * 6 + j] = i == j ? a[i * 6 + i] : (i > j ? a[j * 6 + i] : 0.0);
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-#pragma unroll
-    for (int j = 0; j <= i; j++) {
-      double s = 0.0;
-#pragma unroll
-      for (int k = i; k < 6; k++) s += w[k * 6 + i] * w[k * 6 + j];
-      a[i * 6 + j] = s; a[j * 6 + i] = s;
-    }
-  return ratio;
-}
-// the fixed LDS tree of graph_block_sum, taking the minimum
-template <int kThreads>
-__device__ __forceinline__ double graph_block_min(double v, double* lds) {
-  const int t = (int)threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (t < s) lds[t] = fmin(lds[t], lds[t + s]);
-    __syncthreads();
-  }
-  const double out = lds[0];
-  __syncthreads();
-  return out;
-}
-
-// level 0 of the reduction without the LM diagonal, under the Jacobi scale of this linearisation (written to G.scale for the mat-vec)
+// level 0 of the reduction without the LM diagonal, under the Jacobi scale of this linearisation (written to G.scale for the mat-vec).
+// graph_damp_kernel's two products per entry are not shared: there the scale is read from G.scale inside rolled loops with the LM term
+// between them, here it is computed into registers.
 __global__ __launch_bounds__(kGraphVec) void graph_marg_setup_kernel(GraphDev G) {
   const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (f >= G.n_free) return;
@@ -985,102 +1007,6 @@ __global__ __launch_bounds__(kGraphVec) void graph_marg_setup_kernel(GraphDev G)
     }
 }
 
-__device__ __forceinline__ double graph_marg_invert_node(const GraphDev& G, const GraphLevels& V, int l, int j) {
-  const int k = V.n[l] == 1 ? 0 : 2 * j + 1;
-  double a[36];
-  g6_load(G.D + (size_t)(V.off[l] + k) * 36, a);
-  const double ratio = g6_inv_spd_pivot(a);
-  g6_store(G.Dinv + (size_t)(V.ioff[l] + j) * 36, a);
-  return ratio;
-}
-// graph_cr_invert_kernel that also leaves its workgroup's smallest pivot ratio in piv[first + blockIdx.x]
-__global__ __launch_bounds__(kGraphBlock) void graph_marg_invert_kernel(GraphDev G, GraphLevels V, int l, GraphMarg M, int first) {
-  __shared__ double lds[kGraphBlock];
-  const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  double ratio = 1.0;
-  if (j < V.n[l] / 2) ratio = graph_marg_invert_node(G, V, l, j);
-  ratio = graph_block_min<kGraphBlock>(ratio, lds);
-  if (threadIdx.x == 0) M.piv[first + blockIdx.x] = ratio;
-}
-// graph_cr_factor_tail_kernel with the pivot test: the minimum over its own blocks and the n_piv partials of the launches before it
-__global__ __launch_bounds__(kGraphVec) void graph_marg_factor_tail_kernel(GraphDev G, GraphLevels V, GraphMarg M, int n_piv, double min_ratio) {
-  __shared__ double lds[kGraphVec];
-  double ratio = 1.0;
-  for (int l = V.tail; l < V.count; l++) {
-    const int inv = V.n[l] == 1 ? 1 : V.n[l] / 2;
-    for (int j = (int)threadIdx.x; j < inv; j += kGraphVec) ratio = fmin(ratio, graph_marg_invert_node(G, V, l, j));
-    __syncthreads();
-    if (l + 1 < V.count)
-      for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec) graph_cr_reduce_node(G, V, l, m);
-    __syncthreads();
-  }
-  for (int i = (int)threadIdx.x; i < n_piv; i += kGraphVec) ratio = fmin(ratio, M.piv[i]);
-  ratio = graph_block_min<kGraphVec>(ratio, lds);
-  if (threadIdx.x == 0) { M.st->min_pivot = ratio; M.st->singular = ratio >= min_ratio ? 0 : 1; }
-}
-
-// the six columns of column node c are all done
-__device__ __forceinline__ bool graph_marg_all_done(const GraphMarg& M, int c) {
-  int d = 1;
-#pragma unroll
-  for (int j = 0; j < 6; j++) d &= M.col[c * 6 + j].done;
-  return d != 0;
-}
-__device__ __forceinline__ size_t graph_marg_upper(const GraphDev& G, const GraphLevels& V) { return (size_t)(V.off[V.count - 1] + 1 - G.n_free); }
-// level l of column node c: right-hand side / solution blocks (level 0: y0 / x0, [n_cols x free x 36])
-__device__ __forceinline__ const double* graph_marg_level_rhs(const GraphDev& G, const GraphLevels& V, const GraphMarg& M, int c, int l, const double* y0) {
-  return l == 0 ? y0 + (size_t)c * G.n_free * 36 : M.rhs + ((size_t)c * graph_marg_upper(G, V) + (size_t)(V.off[l] - G.n_free)) * 36;
-}
-__device__ __forceinline__ double* graph_marg_level_sol(const GraphDev& G, const GraphLevels& V, const GraphMarg& M, int c, int l, double* x0) {
-  return l == 0 ? x0 + (size_t)c * G.n_free * 36 : M.sol + ((size_t)c * graph_marg_upper(G, V) + (size_t)(V.off[l] - G.n_free)) * 36;
-}
-// graph_cr_rhs_node over 6 x 6 blocks: Y' = Y_k - L_k Dinv_k-1 Y_k-1 - L_k+1^T Dinv_k+1 Y_k+1
-__device__ __forceinline__ void graph_marg_rhs_node(const GraphDev& G, const GraphLevels& V, int l, int m, const double* __restrict__ y,
-                                                    double* __restrict__ yn) {
-  const int k = 2 * m, n = V.n[l];
-  const double* Ll = G.L + (size_t)V.off[l] * 36; const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
-  double o[36], t[36], b[36];
-  g6_load(y + (size_t)k * 36, o);
-  if (k >= 1) {
-    g6_load(y + (size_t)(k - 1) * 36, b);
-#pragma unroll
-    for (int i = 0; i < 36; i++) t[i] = 0.0;
-    g6_mma<false, false>(Il + (size_t)(m - 1) * 36, b, t, 1.0);
-    g6_mma<false, false>(Ll + (size_t)k * 36, t, o, -1.0);
-  }
-  if (k + 1 < n) {
-    g6_load(y + (size_t)(k + 1) * 36, b);
-#pragma unroll
-    for (int i = 0; i < 36; i++) t[i] = 0.0;
-    g6_mma<false, false>(Il + (size_t)m * 36, b, t, 1.0);
-    g6_mma<true, false>(Ll + (size_t)(k + 1) * 36, t, o, -1.0);
-  }
-  g6_store(yn + (size_t)m * 36, o);
-}
-// graph_cr_back_node over 6 x 6 blocks
-__device__ __forceinline__ void graph_marg_back_node(const GraphDev& G, const GraphLevels& V, int l, int k, const double* __restrict__ y,
-                                                     const double* __restrict__ xn, double* __restrict__ x) {
-  const int n = V.n[l], m = k >> 1;
-  double t[36], b[36];
-  if (!(k & 1)) {
-    g6_load(xn + (size_t)m * 36, t);
-    g6_store(x + (size_t)k * 36, t);
-    return;
-  }
-  const double* Ll = G.L + (size_t)V.off[l] * 36; const double* Il = G.Dinv + (size_t)V.ioff[l] * 36;
-  g6_load(y + (size_t)k * 36, t);
-  g6_load(xn + (size_t)m * 36, b);
-  g6_mma<false, false>(Ll + (size_t)k * 36, b, t, -1.0);
-  if (k + 1 < n) {
-    g6_load(xn + (size_t)(m + 1) * 36, b);
-    g6_mma<true, false>(Ll + (size_t)(k + 1) * 36, b, t, -1.0);
-  }
-#pragma unroll
-  for (int i = 0; i < 36; i++) b[i] = 0.0;
-  g6_mma<false, false>(Il + (size_t)m * 36, t, b, 1.0);
-  g6_store(x + (size_t)k * 36, b);
-}
-
 // X = 0, R = the unit columns of the column node, every column's CG record cleared
 __global__ __launch_bounds__(kGraphVec) void graph_marg_init_kernel(GraphDev G, GraphMarg M) {
   const int c = (int)blockIdx.y;
@@ -1091,44 +1017,6 @@ __global__ __launch_bounds__(kGraphVec) void graph_marg_init_kernel(GraphDev G, 
   const size_t at = (size_t)c * G.n_free * 36 + i;
   M.X[at] = 0.0;
   M.R[at] = (f == M.col_free[c] && e % 7 == 0) ? 1.0 : 0.0;
-}
-
-// z = T^-1 y per column node: the right-hand-side half of the reduction, y0 -> x0 at level 0
-__global__ __launch_bounds__(kGraphBlock) void graph_marg_rhs_kernel(GraphDev G, GraphLevels V, int l, GraphMarg M, const double* y0) {
-  const int c = (int)blockIdx.y;
-  if (graph_marg_all_done(M, c)) return;
-  const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (m < V.n[l + 1]) graph_marg_rhs_node(G, V, l, m, graph_marg_level_rhs(G, V, M, c, l, y0), M.rhs + ((size_t)c * graph_marg_upper(G, V) + (size_t)(V.off[l + 1] - G.n_free)) * 36);
-}
-__global__ __launch_bounds__(kGraphVec) void graph_marg_tail_kernel(GraphDev G, GraphLevels V, GraphMarg M, const double* y0, double* x0) {
-  const int c = (int)blockIdx.y;
-  if (graph_marg_all_done(M, c)) return;
-  const int last = V.count - 1;
-  for (int l = V.tail; l < last; l++) {
-    for (int m = (int)threadIdx.x; m < V.n[l + 1]; m += kGraphVec)
-      graph_marg_rhs_node(G, V, l, m, graph_marg_level_rhs(G, V, M, c, l, y0), M.rhs + ((size_t)c * graph_marg_upper(G, V) + (size_t)(V.off[l + 1] - G.n_free)) * 36);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    double b[36], t[36];
-    g6_load(graph_marg_level_rhs(G, V, M, c, last, y0), b);
-#pragma unroll
-    for (int i = 0; i < 36; i++) t[i] = 0.0;
-    g6_mma<false, false>(G.Dinv + (size_t)V.ioff[last] * 36, b, t, 1.0);
-    g6_store(graph_marg_level_sol(G, V, M, c, last, x0), t);
-  }
-  __syncthreads();
-  for (int l = last - 1; l >= V.tail; l--) {
-    for (int k = (int)threadIdx.x; k < V.n[l]; k += kGraphVec)
-      graph_marg_back_node(G, V, l, k, graph_marg_level_rhs(G, V, M, c, l, y0), graph_marg_level_sol(G, V, M, c, l + 1, x0), graph_marg_level_sol(G, V, M, c, l, x0));
-    __syncthreads();
-  }
-}
-__global__ __launch_bounds__(kGraphBlock) void graph_marg_back_kernel(GraphDev G, GraphLevels V, int l, GraphMarg M, const double* y0, double* x0) {
-  const int c = (int)blockIdx.y;
-  if (graph_marg_all_done(M, c)) return;
-  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k < V.n[l]) graph_marg_back_node(G, V, l, k, graph_marg_level_rhs(G, V, M, c, l, y0), graph_marg_level_sol(G, V, M, c, l + 1, x0), graph_marg_level_sol(G, V, M, c, l, x0));
 }
 
 // partials of r . z, one per (column, workgroup)
@@ -1148,18 +1036,11 @@ __global__ __launch_bounds__(kGraphBlock) void graph_marg_dot_kernel(GraphDev G,
   double* part = M.part + (size_t)M.n_cols * 6 * M.n_part;
 #pragma unroll
   for (int j = 0; j < 6; j++) {
-    const double v = graph_block_sum<kGraphBlock, false>(s[j], lds);
+    const double v = graph_block_reduce<kGraphBlock, kGraphSum>(s[j], lds);
     if (threadIdx.x == 0) part[(size_t)(c * 6 + j) * M.n_part + blockIdx.x] = v;
   }
 }
 
-// block of the direction of free node f: column j is z + beta_j p_old (z alone at iteration 0)
-__device__ __forceinline__ void graph_marg_dir(const double* __restrict__ z, const double* __restrict__ po, const double* beta, bool first, double* p) {
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-#pragma unroll
-    for (int j = 0; j < 6; j++) p[i * 6 + j] = z[i * 6 + j] + (first ? 0.0 : beta[j] * po[i * 6 + j]);
-}
 // graph_matvec_kernel per column node: every column's convergence test on its r . z, p = z + beta p, q = A p, partials of p . q
 __global__ __launch_bounds__(kGraphBlock) void graph_marg_matvec_kernel(GraphDev G, GraphMarg M, int it, double cg_tol) {
   __shared__ double lds[kGraphBlock];
@@ -1173,7 +1054,7 @@ __global__ __launch_bounds__(kGraphBlock) void graph_marg_matvec_kernel(GraphDev
   for (int j = 0; j < 6; j++) {
     GraphMargCol* s = M.col + c * 6 + j;
     done[j] = s->done;
-    const double rz = graph_total<kGraphBlock, false>(part_rz + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
+    const double rz = graph_total<kGraphBlock, kGraphSum>(part_rz + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
     const double rz0 = it == 0 ? rz : s->rz0;
     const bool stop = it == 0 ? !(rz > 0.0) : sqrt(rz) <= cg_tol * sqrt(rz0);
     beta[j] = it == 0 ? 0.0 : rz / s->rz[w ^ 1];
@@ -1190,39 +1071,8 @@ __global__ __launch_bounds__(kGraphBlock) void graph_marg_matvec_kernel(GraphDev
   const int f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   double pq[6] = {0, 0, 0, 0, 0, 0};
   if (f < G.n_free) {
-    double pf[36], pm[36], q[36], t[36];
-    graph_marg_dir(Z + (size_t)f * 36, po + (size_t)f * 36, beta, it == 0, pf);
-#pragma unroll
-    for (int i = 0; i < 36; i++) q[i] = 0.0;
-    g6_mma<false, false>(G.D + (size_t)f * 36, pf, q, 1.0);
-    if (f > 0) {
-      graph_marg_dir(Z + (size_t)(f - 1) * 36, po + (size_t)(f - 1) * 36, beta, it == 0, pm);
-      g6_mma<false, false>(G.L + (size_t)f * 36, pm, q, 1.0);
-    }
-    if (f + 1 < G.n_free) {
-      graph_marg_dir(Z + (size_t)(f + 1) * 36, po + (size_t)(f + 1) * 36, beta, it == 0, pm);
-      g6_mma<true, false>(G.L + (size_t)(f + 1) * 36, pm, q, 1.0);
-    }
-    const double* sf = G.scale + (size_t)f * 6;
-    for (int e = G.ladj_off[f]; e < G.ladj_off[f + 1]; e++) {       // long factors: s_f . Jf^T (Jo (s_o . p_o)), in adjacency order
-      const int k = G.ladj[e] >> 1, side = G.ladj[e] & 1;
-      const int fo = G.free_of[G.fac_ij[2 * k + (side ^ 1)]];
-      const double* Jk = G.J + (size_t)k * kGraphJ;
-      const double* so = G.scale + (size_t)fo * 6;
-      graph_marg_dir(Z + (size_t)fo * 36, po + (size_t)fo * 36, beta, it == 0, pm);
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j < 6; j++) { pm[i * 6 + j] *= so[i]; t[i * 6 + j] = 0.0; }
-      g6_mma<false, false>(Jk + 36 * (side ^ 1), pm, t, 1.0);
-#pragma unroll
-      for (int i = 0; i < 36; i++) pm[i] = 0.0;
-      g6_mma<true, false>(Jk + 36 * side, t, pm, 1.0);
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j < 6; j++) q[i * 6 + j] += sf[i] * pm[i * 6 + j];
-    }
+    double pf[36], q[36];
+    graph_apply<6>(G, f, Z, po, beta, it == 0, pf, q);
 #pragma unroll
     for (int i = 0; i < 6; i++)
 #pragma unroll
@@ -1234,7 +1084,7 @@ __global__ __launch_bounds__(kGraphBlock) void graph_marg_matvec_kernel(GraphDev
   }
 #pragma unroll
   for (int j = 0; j < 6; j++) {
-    const double v = graph_block_sum<kGraphBlock, false>(pq[j], lds);
+    const double v = graph_block_reduce<kGraphBlock, kGraphSum>(pq[j], lds);
     if (threadIdx.x == 0) M.part[(size_t)(c * 6 + j) * M.n_part + blockIdx.x] = v;
   }
 }
@@ -1250,7 +1100,7 @@ __global__ __launch_bounds__(kGraphBlock) void graph_marg_update_kernel(GraphDev
   for (int j = 0; j < 6; j++) {
     GraphMargCol* s = M.col + c * 6 + j;
     done[j] = s->done;
-    const double pq = graph_total<kGraphBlock, false>(M.part + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
+    const double pq = graph_total<kGraphBlock, kGraphSum>(M.part + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
     alpha[j] = s->rz[it & 1] / pq;
   }
   const size_t base = (size_t)c * G.n_free * 36;
@@ -1276,7 +1126,7 @@ __global__ __launch_bounds__(kGraphBlock) void graph_marg_check_kernel(GraphMarg
 #pragma unroll
   for (int j = 0; j < 6; j++) {
     GraphMargCol* s = M.col + c * 6 + j;
-    const double rz = graph_total<kGraphBlock, false>(part_rz + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
+    const double rz = graph_total<kGraphBlock, kGraphSum>(part_rz + (size_t)(c * 6 + j) * M.n_part, M.n_part, lds);
     if (threadIdx.x == 0 && !s->done && sqrt(rz) <= cg_tol * sqrt(s->rz0)) s->done = 1;
   }
 }
