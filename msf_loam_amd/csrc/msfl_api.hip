@@ -266,6 +266,8 @@ struct msfl_handle_s {
   bool odom_force_brute = false;          // MSFL_ODOM_BRUTE=1: stage B plane queries stay on the brute-force kernel (A/B testing)
   int knn_form = 0;                       // MSFL_KNN_FORM: 0 auto (row-parallel latency form for launches of <= kKnnRowsMaxRecords queries),
                                           // 1 "lane" (one lane per query always), 2 "rows" (row-parallel always); results are identical
+  bool knn_defer = true;                  // MSFL_KNN_DEFER=0|1: the whole-batch 5-NN kernel (and the candidate counter) caps every row visit and walks
+                                          // the deferred tails after the ninth row (knn5_grid_k32<.., DEFER>); results are identical
 
   // scratch of the map matchers (scan-to-map, pairs, records): staged feature clouds, offset table, poses, per-registration status and
   // info, association records, deskewed points / host-format records, 5-NN lists.  `poses` also holds msfl_extract_features' extrinsic.
@@ -733,11 +735,14 @@ void s_launch_assoc(msfl_handle* h, const BatchView& bv_all, const double* d_pos
     if (h->timing == 3) {
       unsigned long long* cnt = h->knn_count.as<unsigned long long>();
       if (deskew) launch_knn5(h, knn5_scan2map_kernel<true, true>, grid, block, bv, d_poses, d_status, dv, nn, cnt, nullptr, nullptr);
+      else if (h->knn_defer) launch_knn5(h, knn5_scan2map_kernel<false, true, false, true>, grid, block, bv, d_poses, d_status, dv, nn, cnt + (second_pass ? 1 : 0), nullptr, nullptr);
       else launch_knn5(h, knn5_scan2map_kernel<false, true>, grid, block, bv, d_poses, d_status, dv, nn, cnt + (second_pass ? 1 : 0), nullptr, nullptr);
     } else if (whole_batch) {       // a whole large batch: one body per feature kind (-2 %)
       const int n_s = bv.n_surf_total, n_c = n_rec - n_s;
       const int edge_blocks = div_up(n_c, kAssocBlock), plane_blocks = div_up(n_s, kAssocBlock);
-      launch_knn5(h, knn5_scan2map_split_kernel, dim3(edge_blocks + plane_blocks), block, bv, d_poses, d_status, nn, h->records.as<double>(), edge_blocks);
+      const dim3 blocks(edge_blocks + plane_blocks);
+      if (h->knn_defer) launch_knn5(h, knn5_scan2map_split_kernel<true>, blocks, block, bv, d_poses, d_status, nn, h->records.as<double>(), edge_blocks);
+      else launch_knn5(h, knn5_scan2map_split_kernel<false>, blocks, block, bv, d_poses, d_status, nn, h->records.as<double>(), edge_blocks);
     } else if (!deskew && (h->knn_form == 2 || (h->knn_form == 0 && (n_rec <= kKnnRowsMaxRecords ||
                                                                        // the SLAM step launches over the list CAPACITIES (device-side counts): a 64-beam scan's ~11-17 k
                                                                        // queries sit in a ~150 k-slot launch whose surplus workgroups leave at once
@@ -892,6 +897,7 @@ msfl_status msfl_create(const msfl_params* params, int device, msfl_handle** out
   if (const char* e = std::getenv("MSFL_SOLVE_RECORDS_BLOCK")) h->solve_records_block = std::atoi(e);
   if (const char* e = std::getenv("MSFL_ODOM_BRUTE")) h->odom_force_brute = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_INDEX_SINGLE")) h->index_single = std::atoi(e) != 0;
+  if (const char* e = std::getenv("MSFL_KNN_DEFER")) h->knn_defer = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_KNN_FORM")) h->knn_form = !std::strcmp(e, "lane") ? 1 : !std::strcmp(e, "rows") ? 2 : 0;
   if (const char* e = std::getenv("MSFL_ODOM_WAVE_MAX_TARGETS")) h->odom_wave_max_targets = std::atoll(e);
   if (const char* e = std::getenv("MSFL_VOXEL_GLOBAL")) h->voxel_force_global = std::atoi(e) != 0;

@@ -177,7 +177,9 @@ struct DeskewView {
 #endif
 constexpr int kAssocBlock = MSFL_ASSOC_BLOCK;      // threads per workgroup of the 5-NN and fit kernels
 // PAIRS: scan b is registered against ITS OWN map (msfl_pairs.cuh): descriptor gcp[b] / gsp[b], cell table slice at cbase_*[b]
-template <bool DESKEW, bool COUNT = false, bool PAIRS = false>
+// DEFER: the capped walk of the whole-batch kernel (knn5_grid_k32), only for the counting instantiation: the candidate counter then
+// reports what the timed launch evaluates
+template <bool DESKEW, bool COUNT = false, bool PAIRS = false, bool DEFER = false>
 __global__ void __launch_bounds__(kAssocBlock)
 knn5_scan2map_kernel(BatchView bv, const double* __restrict__ poses, const int* __restrict__ status,
                      const GridDesc* __restrict__ gcp, const float4* __restrict__ map_c, const int* __restrict__ cs_c,
@@ -221,11 +223,11 @@ knn5_scan2map_kernel(BatchView bv, const double* __restrict__ poses, const int* 
   Top5 t;
   int n_cand = 0;
   // the walk on truncated 32-bit keys first (Top6K); a lane it leaves ambiguous is searched again with the exact keys below
-  __shared__ int s_slot[kTopSlots * kAssocBlock];
+  __shared__ int s_slot[(kTopSlots + (DEFER ? kDeferSlots : 0)) * kAssocBlock];
   Top6K tk;
   top_init(tk, max_sq_dist, s_slot + threadIdx.x);
-  if (is_edge) { const GridDesc gc = gcp[PAIRS ? b : 0]; knn5_grid_k32<kAssocBlock>(gc, map_c, cs_c, q, tk, n_cand, PAIRS ? cbase_c[b] : 0); }
-  else { const GridDesc gs = gsp[PAIRS ? b : 0]; knn5_grid_k32<kAssocBlock>(gs, map_s, cs_s, q, tk, n_cand, PAIRS ? cbase_s[b] : 0); }
+  if (is_edge) { const GridDesc gc = gcp[PAIRS ? b : 0]; knn5_grid_k32<kAssocBlock, DEFER>(gc, map_c, cs_c, q, tk, n_cand, PAIRS ? cbase_c[b] : 0); }
+  else { const GridDesc gs = gsp[PAIRS ? b : 0]; knn5_grid_k32<kAssocBlock, DEFER>(gs, map_s, cs_s, q, tk, n_cand, PAIRS ? cbase_s[b] : 0); }
   const bool settled = top_settled(tk, max_sq_dist);
   if (!settled) {
     int n_again = 0;                   // the candidate counter reports the first walk
@@ -268,7 +270,7 @@ __device__ __forceinline__ V uniform_load(const V* p) {
 
 // K4a for a whole large batch of the plain branch: blocks [0, edge_blocks) serve the corner features (corner map index), the rest
 // the surf features, so that a wavefront never holds both kinds and each body knows its map at compile time.
-template <bool EDGE>
+template <bool EDGE, bool DEFER>
 __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double* __restrict__ poses, const int* __restrict__ status,
                                               const GridDesc* __restrict__ gp, const float4* __restrict__ map, const int* __restrict__ cs,
                                               const int* __restrict__ po, float max_sq_dist, int* __restrict__ nn, double* __restrict__ rec, int block, int* s_slot) {
@@ -307,7 +309,7 @@ __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double*
   const GridDesc gd = *gp;
   Top6K tk;
   top_init(tk, max_sq_dist, s_slot + threadIdx.x);
-  knn5_grid_k32<kAssocBlock>(gd, map, cs, q, tk, n_cand);
+  knn5_grid_k32<kAssocBlock, DEFER>(gd, map, cs, q, tk, n_cand);
   if (top_settled(tk, max_sq_dist)) {
     if (top_found(tk)) {                                                              // :128 / :198: the 5th is below the gate (t differs from the gate's)
       put(top_pos<kAssocBlock>(tk, tk.k0), top_pos<kAssocBlock>(tk, tk.k1), top_pos<kAssocBlock>(tk, tk.k2),
@@ -327,15 +329,17 @@ __device__ __forceinline__ void knn5_one_kind(const BatchView& bv, const double*
     put(-1, -1, -1, -1, -1);
   }
 }
+// DEFER: capped row visits, the rest of a long range walked after the ninth row (knn5_grid_k32); the handle picks the form (MSFL_KNN_DEFER)
+template <bool DEFER>
 __global__ void __launch_bounds__(kAssocBlock)
 knn5_scan2map_split_kernel(BatchView bv, const double* __restrict__ poses, const int* __restrict__ status,
                            const GridDesc* __restrict__ gcp, const float4* __restrict__ map_c, const int* __restrict__ cs_c,
                            const GridDesc* __restrict__ gsp, const float4* __restrict__ map_s, const int* __restrict__ cs_s,
                            const int* __restrict__ pos_c, const int* __restrict__ pos_s, float max_sq_dist, int* __restrict__ nn,
                            double* __restrict__ rec, int edge_blocks) {
-  __shared__ int s_slot[kTopSlots * kAssocBlock];        // Top6K's slot table: 6 positions per lane
-  if ((int)blockIdx.x < edge_blocks) knn5_one_kind<true>(bv, poses, status, gcp, map_c, cs_c, pos_c, max_sq_dist, nn, rec, (int)blockIdx.x, s_slot);
-  else knn5_one_kind<false>(bv, poses, status, gsp, map_s, cs_s, pos_s, max_sq_dist, nn, rec, (int)blockIdx.x - edge_blocks, s_slot);
+  __shared__ int s_slot[(kTopSlots + (DEFER ? kDeferSlots : 0)) * kAssocBlock];        // Top6K's slot table: 6 positions per lane; DEFER: the lanes' range stacks
+  if ((int)blockIdx.x < edge_blocks) knn5_one_kind<true, DEFER>(bv, poses, status, gcp, map_c, cs_c, pos_c, max_sq_dist, nn, rec, (int)blockIdx.x, s_slot);
+  else knn5_one_kind<false, DEFER>(bv, poses, status, gsp, map_s, cs_s, pos_s, max_sq_dist, nn, rec, (int)blockIdx.x - edge_blocks, s_slot);
 }
 
 // K4a, latency form: the same exact 5-NN for a launch too small to fill the machine (one scan per call: ~5 000 queries are

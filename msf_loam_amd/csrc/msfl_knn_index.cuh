@@ -574,7 +574,26 @@ __device__ __forceinline__ void top_insert_off(Top6K& t, float d, unsigned int o
   t.k0 = min(t.k0, x);
   t.bound = min(t.k4 | 7u, t.gate);
 }
-template <int STRIDE>
+// DEFER (the whole-batch kernel; docs/kernels/scan2map.md, "Capped row visits"): a row visit walks at most kDeferCaps[position]
+// pair-iterations; the lane pushes the rest of its range, {start, end} as byte offsets, onto a stack of kDeferDepth entries in LDS
+// (layout [entry][word][lane] right after its column of the slot table: t.col + kTopSlots * STRIDE) and goes on to the next row.
+// After the ninth row one loop walks the stored ranges.  A position then costs the wavefront min(longest range, cap) iterations,
+// and the long lanes of different positions, which are different lanes, catch up side by side.  A full stack walks the range in
+// place.  The candidates offered are those of the plain walk or more (a stored range was cut under a bound no smaller than any
+// later one), so the lists are the plain walk's, bit for bit.
+#ifndef MSFL_KNN_DEFER_CAPS
+#define MSFL_KNN_DEFER_CAPS 8, 4, 4, 1, 1, 1, 1, 1, 1
+#endif
+#ifndef MSFL_KNN_DEFER_DEPTH
+#define MSFL_KNN_DEFER_DEPTH 4
+#endif
+#ifndef MSFL_KNN_DEFER_FLAT
+#define MSFL_KNN_DEFER_FLAT 1         // 1: one flat loop over a lane's stored ranges; 0: entry by entry (the k-th range of every lane together)
+#endif
+constexpr int kDeferCaps[9] = {MSFL_KNN_DEFER_CAPS};   // pair-iterations per row position, in visit order
+constexpr int kDeferDepth = MSFL_KNN_DEFER_DEPTH;
+constexpr int kDeferSlots = 2 * kDeferDepth;           // LDS dwords per lane
+template <int STRIDE, bool DEFER = false>
 __device__ __forceinline__ void knn5_grid_k32(const GridDesc& g, const float4* __restrict__ sorted,
                                               const int* __restrict__ cell_start, float3 q, Top6K& t, int& n_cand,
                                               int cell_base = 0) {        // cell_base: this map's slice of a shared cell table (pairs)
@@ -596,7 +615,9 @@ __device__ __forceinline__ void knn5_grid_k32(const GridDesc& g, const float4* _
   const int zstep = g.dy * g.dx;
   const int off_z = sz < 0 ? -zstep : zstep;
   const char* const mapb = (const char*)sorted;
-  auto visit = [&](bool valid, int row, float rowq) __attribute__((always_inline)) {
+  int* const stack = t.col + kTopSlots * STRIDE;         // DEFER: this lane's stack, entry k at stack[2 k STRIDE] (start) and [(2 k + 1) STRIDE] (end)
+  int* sp = stack;                                        // next free entry
+  auto visit = [&](int pos, bool valid, int row, float rowq) __attribute__((always_inline)) {
     const float row2 = rowq * cell2;
     const float d4 = top_d4(t);
     if (!valid || row2 > d4) return;           // d4: the acceptance gate until five neighbours are known, then >= the 5th distance
@@ -607,9 +628,19 @@ __device__ __forceinline__ void knn5_grid_k32(const GridDesc& g, const float4* _
     if (a > b) return;
     const unsigned int s = (unsigned int)cell_start[(unsigned int)(row + a)], e = (unsigned int)cell_start[(unsigned int)(row + b + 1)];
     if (s == e) return;
-    n_cand += (int)(e - s);
     unsigned int off = s << 4;
-    const unsigned int end = e << 4, last = end - 16u;      // last: offset of the range's last point (>= off)
+    unsigned int end = e << 4;
+    if constexpr (DEFER) {
+      const unsigned int cut = off + 32u * (unsigned int)kDeferCaps[pos];
+      if (end > cut && sp < stack + kDeferSlots * STRIDE) {       // longer than the cap and room on the stack: the rest waits
+        sp[0] = (int)cut; sp[STRIDE] = (int)end; sp += 2 * STRIDE;
+        end = cut;
+      }
+      n_cand += (int)((end - off) >> 4);
+    } else {
+      n_cand += (int)(e - s);
+    }
+    const unsigned int last = end - 16u;       // last: offset of the range's last point (>= off)
     for (; off < last; off += 32u) {           // two loads in flight
       float4 m0 = *(const float4*)(mapb + off), m1 = *(const float4*)(mapb + off + 16u);
       asm volatile("" : "+v"(m0.w));           // keep the 16-byte loads (12-byte loads: slower in rounds 1-2, no change in round 4b)
@@ -620,28 +651,65 @@ __device__ __forceinline__ void knn5_grid_k32(const GridDesc& g, const float4* _
     if (off < end) { float4 m = *(const float4*)(mapb + off); asm volatile("" : "+v"(m.w)); top_insert_off<STRIDE>(t, l2_simple_pk(m, qxy, q.z), off); }
   };
   // the row order of grid_walk_exact: centre, near sides (smaller gap first), far sides, near-near, mixed diagonals, far-far
-  visit(v_y1 && v_z1, base0, q_y1 + q_z1);
+  visit(0, v_y1 && v_z1, base0, q_y1 + q_z1);
   {
     const bool va = v_ny && v_z1, vb = v_y1 && v_nz;               // A: near-y side row, B: near-z side row
     const float ra = q_ny + q_z1, rb = q_y1 + q_nz;
-    visit(o.ny_first ? va : vb, base0 + (o.ny_first ? off_y : off_z), o.ny_first ? ra : rb);
-    visit(o.ny_first ? vb : va, base0 + (o.ny_first ? off_z : off_y), o.ny_first ? rb : ra);
+    visit(1, o.ny_first ? va : vb, base0 + (o.ny_first ? off_y : off_z), o.ny_first ? ra : rb);
+    visit(2, o.ny_first ? vb : va, base0 + (o.ny_first ? off_z : off_y), o.ny_first ? rb : ra);
   }
   {
     const bool va = v_fy && v_z1, vb = v_y1 && v_fz;
     const float ra = q_fy + q_z1, rb = q_y1 + q_fz;
-    visit(o.fy_first ? va : vb, base0 - (o.fy_first ? off_y : off_z), o.fy_first ? ra : rb);
-    visit(o.fy_first ? vb : va, base0 - (o.fy_first ? off_z : off_y), o.fy_first ? rb : ra);
+    visit(3, o.fy_first ? va : vb, base0 - (o.fy_first ? off_y : off_z), o.fy_first ? ra : rb);
+    visit(4, o.fy_first ? vb : va, base0 - (o.fy_first ? off_z : off_y), o.fy_first ? rb : ra);
   }
-  visit(v_ny && v_nz, base0 + off_y + off_z, q_ny + q_nz);
+  visit(5, v_ny && v_nz, base0 + off_y + off_z, q_ny + q_nz);
   {
     const bool va = v_ny && v_fz, vb = v_fy && v_nz;               // A: (near y, far z)
     const float ra = q_ny + q_fz, rb = q_fy + q_nz;
     const int oa = off_y - off_z, ob = off_z - off_y;
-    visit(o.e_first ? va : vb, base0 + (o.e_first ? oa : ob), o.e_first ? ra : rb);
-    visit(o.e_first ? vb : va, base0 + (o.e_first ? ob : oa), o.e_first ? rb : ra);
+    visit(6, o.e_first ? va : vb, base0 + (o.e_first ? oa : ob), o.e_first ? ra : rb);
+    visit(7, o.e_first ? vb : va, base0 + (o.e_first ? ob : oa), o.e_first ? rb : ra);
   }
-  visit(v_fy && v_fz, base0 - off_y - off_z, q_fy + q_fz);
+  visit(8, v_fy && v_fz, base0 - off_y - off_z, q_fy + q_fz);
+  if constexpr (DEFER) {
+    // the stored ranges, in stack order
+    if (MSFL_KNN_DEFER_FLAT) {
+      // one loop: a lane that has finished a range takes its next one in the same iteration, so the trip count is the longest lane's SUM.
+      // An odd range's last iteration loads its last point twice and offers the copy with a key that the pre-filter always refuses.
+      unsigned int off = 0, end = 0;
+      for (const int* rp = stack;; off += 32u) {
+        if (off >= end) {
+          if (rp >= sp) break;
+          off = (unsigned int)rp[0]; end = (unsigned int)rp[STRIDE]; rp += 2 * STRIDE;
+          n_cand += (int)((end - off) >> 4);
+        }
+        const bool two = off + 16u < end;
+        const unsigned int off1 = two ? off + 16u : off;
+        float4 m0 = *(const float4*)(mapb + off), m1 = *(const float4*)(mapb + off1);
+        asm volatile("" : "+v"(m0.w));
+        top_insert_off<STRIDE>(t, l2_simple_pk(m0, qxy, q.z), off);
+        asm volatile("" : "+v"(m1.w));
+        top_insert_off<STRIDE>(t, two ? l2_simple_pk(m1, qxy, q.z) : __uint_as_float(0xffffffffu), off1);
+      }
+    } else {
+      // entry by entry: the k-th stored range of every lane together, with the row visit's own loop
+      for (const int* rp = stack; rp < sp; rp += 2 * STRIDE) {
+        unsigned int off = (unsigned int)rp[0];
+        const unsigned int end = (unsigned int)rp[STRIDE], last = end - 16u;
+        n_cand += (int)((end - off) >> 4);
+        for (; off < last; off += 32u) {
+          float4 m0 = *(const float4*)(mapb + off), m1 = *(const float4*)(mapb + off + 16u);
+          asm volatile("" : "+v"(m0.w));
+          top_insert_off<STRIDE>(t, l2_simple_pk(m0, qxy, q.z), off);
+          asm volatile("" : "+v"(m1.w));
+          top_insert_off<STRIDE>(t, l2_simple_pk(m1, qxy, q.z), off + 16u);
+        }
+        if (off < end) { float4 m = *(const float4*)(mapb + off); asm volatile("" : "+v"(m.w)); top_insert_off<STRIDE>(t, l2_simple_pk(m, qxy, q.z), off); }
+      }
+    }
+  }
 }
 
 }  // namespace msfl
