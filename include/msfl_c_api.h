@@ -229,7 +229,7 @@ msfl_status msfl_set_timing(msfl_handle* h, int enabled);
 msfl_status msfl_get_timing(msfl_handle* h, msfl_timing* out, int reset);
 
 /* Uncertainty output, off by default.  out == NULL turns it off.  Otherwise EVERY later matcher call on this handle
-   (msfl_match_scan2map, _batch, both deskew forms, msfl_match_pairs_batch, msfl_solve_records, msfl_match_scan2scan, _batch)
+   (msfl_match_scan2map, _batch, both deskew forms, msfl_match_pairs_batch, msfl_solve_records, _deskew, msfl_match_scan2scan, _batch)
    writes one record per registration into out[0 .. n), in the call's order; a call with more registrations than `capacity`
    returns MSFL_CAPACITY before it stages or launches anything (poses untouched).  A registration whose per-scan status is not 0, or
    whose last solve had nothing to solve, gets an all-zero record (valid = 0); a call that itself fails writes nothing.
@@ -429,6 +429,31 @@ msfl_status msfl_match_scan2map_deskew(msfl_handle* h,
                                        const msfl_point* surf, int n_surf,
                                        const msfl_deskew* deskew,
                                        double pose_io[7], msfl_match_info* info);
+
+/* Kernel-level entry points of the deskew branch (the two halves of one outer iteration of msfl_match_scan2map_deskew),
+   exposed like msfl_associate_scan2map / msfl_solve_records so that parity tests can pin them separately:
+     msfl_associate_scan2map_deskew : one association pass at a fixed pose through the launch pair the deskew matcher takes
+                                      (the counting 5-NN instantiation after msfl_set_timing(h, 3)).  Feature i is searched at
+                                      pose * {q^-1 (V dt_i - G dt_i^2 / 2) + dp_i, dq_i} (:120 / :190).  records_out gets
+                                      (n_corner + n_surf) x 6 doubles {C', N} in feature order (corner first), with
+                                      C' = C - (V dt_i - G dt_i^2 / 2); a rejected feature is all zeros.  points_out gets
+                                      (n_corner + n_surf) x 3 doubles p'_i = dq_i p_i + dp_i, whether accepted or not.
+     msfl_solve_records_deskew      : msfl_solve_records with the residual points given as f64 `points`
+                                      ((n_corner + n_surf) x 3, corner rows first, non-null even for an empty problem): the
+                                      solve, rejection and uncertainty kernels run their deskew branch (no plane cache, points
+                                      from global memory).  MSFL_SOLVE_RECORDS_BLOCK and every registration option apply as for
+                                      msfl_solve_records.  The clouds give the counts only; their xyz are not read by the solve.
+   Host pointers only. */
+msfl_status msfl_associate_scan2map_deskew(msfl_handle* h,
+                                           const msfl_point* corner, int n_corner,
+                                           const msfl_point* surf, int n_surf,
+                                           const msfl_deskew* deskew, const double pose[7],
+                                           double* records_out, double* points_out);
+msfl_status msfl_solve_records_deskew(msfl_handle* h,
+                                      const msfl_point* corner, int n_corner,
+                                      const msfl_point* surf, int n_surf,
+                                      const double* records, const double* points,
+                                      double pose_io[7], msfl_match_info* info);
 
 /* The deskew branch for a batch.  The four per-feature arrays are indexed exactly like the feature arrays
    (corner feature corner_off[b] + k of scan b uses corner_dq[4 * (corner_off[b] + k)] ...), velocity holds

@@ -21,7 +21,7 @@ EXPORTED = [
     "msfl_synchronize", "msfl_status_string", "msfl_last_error", "msfl_set_timing", "msfl_get_timing",
     "msfl_set_map", "msfl_match_scan2map", "msfl_match_scan2map_batch", "msfl_match_pairs_batch", "msfl_match_scan2map_deskew",
     "msfl_match_scan2map_deskew_batch",
-    "msfl_associate_scan2map", "msfl_solve_records",
+    "msfl_associate_scan2map", "msfl_solve_records", "msfl_associate_scan2map_deskew", "msfl_solve_records_deskew",
     "msfl_match_scan2scan", "msfl_match_scan2scan_batch", "msfl_extract_features",
     "msfl_extract_features_batch", "msfl_voxel_downsample", "msfl_voxel_downsample_batch", "msfl_voxel_downsample_batch_pair",
     "msfl_transform_cloud",
@@ -577,6 +577,36 @@ class Handle:
         info = MatchInfo()
         self._check(self.lib.msfl_solve_records(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
                                                 _vp(rec), _vp(pose), C.byref(info)), "msfl_solve_records")
+        return pose, info
+
+    def associate_scan2map_deskew(self, corner, surf, corner_dq, corner_dp, surf_dq, surf_dp, velocity, gravity, pose):
+        """One de-skew association pass at `pose`: ((n, 6) records {C', N}, (n, 3) points p'), corner features first."""
+        corner, surf = _pts(corner), _pts(surf)
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (corner_dq, corner_dp, surf_dq, surf_dp)]
+        d = Deskew()
+        d.corner_dq, d.corner_dp, d.surf_dq, d.surf_dp = (a.ctypes.data for a in arrs)
+        d.velocity = (C.c_double * 3)(*velocity)
+        d.gravity = (C.c_double * 3)(*gravity)
+        n = len(corner) + len(surf)
+        rec, pts = np.zeros((max(n, 1), 6)), np.zeros((max(n, 1), 3))
+        pose = np.ascontiguousarray(pose, dtype=np.float64)
+        self._check(self.lib.msfl_associate_scan2map_deskew(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
+                                                            C.byref(d), _vp(pose), _vp(rec), _vp(pts)), "msfl_associate_scan2map_deskew")
+        return rec[:n], pts[:n]
+
+    def solve_records_deskew(self, corner, surf, records, points, pose):
+        """msfl_solve_records with the residual points given as f64 `points` (n, 3): the solve's de-skew branch."""
+        corner, surf = _pts(corner), _pts(surf)
+        rec = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, 6)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        if len(pts) != len(corner) + len(surf) or len(rec) != len(pts):
+            raise ValueError("records and points need one row per feature")
+        if len(pts) == 0:
+            pts = np.zeros((1, 3))                                # (the entry wants a non-null pointer)
+        pose = np.array(pose, dtype=np.float64)
+        info = MatchInfo()
+        self._check(self.lib.msfl_solve_records_deskew(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
+                                                       _vp(rec), _vp(pts), _vp(pose), C.byref(info)), "msfl_solve_records_deskew")
         return pose, info
 
     def match_scan2map_deskew(self, corner, surf, corner_dq, corner_dp, surf_dq, surf_dp, velocity, gravity, pose):

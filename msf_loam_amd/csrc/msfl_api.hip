@@ -1251,12 +1251,69 @@ msfl_status msfl_associate_scan2map(msfl_handle* h, const msfl_point* corner, in
   return MSFL_OK;
 }
 
+// The de-skew form of msfl_associate_scan2map: the launch pair msfl_match_scan2map_deskew takes, at a fixed pose.  h->pprime holds
+// the {C', N} staging in its first 6 n doubles and p' in the 3 n doubles behind them.
+msfl_status msfl_associate_scan2map_deskew(msfl_handle* h, const msfl_point* corner, int n_corner, const msfl_point* surf,
+                                           int n_surf, const msfl_deskew* deskew, const double pose[7], double* records_out,
+                                           double* points_out) {
+  msfl_status s = enter(h); if (s) return s;
+  if (n_corner < 0 || n_surf < 0 || !pose || !deskew || (n_corner + n_surf > 0 && (!records_out || !points_out)) ||
+      (n_corner && (!corner || !deskew->corner_dq || !deskew->corner_dp)) || (n_surf && (!surf || !deskew->surf_dq || !deskew->surf_dp)))
+    return fail(h, MSFL_BAD_ARG, "msfl_associate_scan2map_deskew: bad argument");
+  s = check_map(h); if (s) return s;
+  const int n = n_corner + n_surf;
+  if (n == 0) return MSFL_OK;
+  BatchView bv;
+  s = stage_single(h, corner, n_corner, surf, n_surf, pose, bv); if (s) return s;
+  DeskewView dv{};
+  s = stage_in(h, h->dk.corner_dq, deskew->corner_dq, (size_t)n_corner * 4, MSFL_MEM_HOST, h->stream, &dv.corner_dq); if (s) return s;
+  s = stage_in(h, h->dk.corner_dp, deskew->corner_dp, (size_t)n_corner * 3, MSFL_MEM_HOST, h->stream, &dv.corner_dp); if (s) return s;
+  s = stage_in(h, h->dk.surf_dq, deskew->surf_dq, (size_t)n_surf * 4, MSFL_MEM_HOST, h->stream, &dv.surf_dq); if (s) return s;
+  s = stage_in(h, h->dk.surf_dp, deskew->surf_dp, (size_t)n_surf * 3, MSFL_MEM_HOST, h->stream, &dv.surf_dp); if (s) return s;
+  s = stage_in(h, h->dk.velocity, deskew->velocity, (size_t)3, MSFL_MEM_HOST, h->stream, &dv.V); if (s) return s;
+  for (int a = 0; a < 3; a++) dv.G[a] = deskew->gravity[a];
+  HIPCHK(h, h->pprime.reserve((size_t)n * 9 * sizeof(double)));
+  double* full = h->pprime.as<double>();
+  dv.pprime = full + 6 * (size_t)n;
+  s_launch_assoc(h, bv, h->poses.as<double>(), h->status.as<int>(), true, dv, n, full);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(records_out, full, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(points_out, dv.pprime, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return MSFL_OK;
+}
+
 }  // extern "C"
 
 namespace {
-// One solve of the records already in h->records, in the workgroup MSFL_SOLVE_RECORDS_BLOCK chose.  Defined at the end of this file:
-// kSlamLmBlock and the SLAM step's <kSlamLmBlock> instantiations, which this only reuses, come with msfl_api_slam.inc.
-msfl_status solve_given_records(msfl_handle* h, const BatchView& bv, const RegSinks& sinks);
+// One solve of the records already in h->records, in the workgroup MSFL_SOLVE_RECORDS_BLOCK chose; pprime: the de-skew branch's f64
+// points (device, n x 3) or null.  Defined at the end of this file: kSlamLmBlock and the SLAM step's <kSlamLmBlock> instantiations,
+// which this only reuses, come with msfl_api_slam.inc.
+msfl_status solve_given_records(msfl_handle* h, const BatchView& bv, const RegSinks& sinks, const double* pprime);
+
+// msfl_solve_records (points == nullptr) and msfl_solve_records_deskew: h->pprime holds the {C, N} staging in its first 6 n doubles
+// and, for the de-skew form, the points in the 3 n doubles behind them.
+msfl_status solve_records_impl(msfl_handle* h, const msfl_point* corner, int n_corner, const msfl_point* surf, int n_surf,
+                               const double* records, const double* points, double pose_io[7], msfl_match_info* info, const char* who) {
+  const int n = n_corner + n_surf;
+  msfl_status s = reg_check(h, 1, who); if (s) return s;
+  BatchView bv;
+  s = stage_single(h, corner, n_corner, surf, n_surf, pose_io, bv); if (s) return s;
+  RegSinks sinks;
+  s = reg_open(h, 1, h->stream, info != nullptr, &sinks); if (s) return s;
+  if (n || points) HIPCHK(h, h->pprime.reserve(std::max<size_t>(1, (size_t)n * (points ? 9 : 6)) * sizeof(double)));
+  // (an empty problem too: the solve kernels take the de-skew branch on the pointer alone)
+  const double* d_points = points ? h->pprime.as<double>() + 6 * (size_t)n : nullptr;
+  if (n) {
+    HIPCHK(h, hipMemcpyAsync(h->pprime.p, records, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (points) HIPCHK(h, hipMemcpyAsync(h->pprime.as<double>() + 6 * (size_t)n, points, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(pack_records_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, bv, (const double*)h->pprime.as<double>(),
+                       h->records.as<double>());
+  }
+  s = solve_given_records(h, bv, sinks, d_points);
+  if (s) return s;
+  return reg_close(h, 1, MSFL_MEM_HOST, pose_io, h->poses.as<double>(), nullptr, nullptr, info, sinks);   // (host memory: always waited for)
+}
 }  // namespace
 
 extern "C" {
@@ -1266,21 +1323,15 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
   msfl_status s = enter(h); if (s) return s;
   if (n_corner < 0 || n_surf < 0 || !pose_io || (n_corner + n_surf > 0 && !records) || (n_corner && !corner) || (n_surf && !surf))
     return fail(h, MSFL_BAD_ARG, "msfl_solve_records: bad argument");
-  const int n = n_corner + n_surf;
-  s = reg_check(h, 1, "msfl_solve_records"); if (s) return s;
-  BatchView bv;
-  s = stage_single(h, corner, n_corner, surf, n_surf, pose_io, bv); if (s) return s;
-  RegSinks sinks;
-  s = reg_open(h, 1, h->stream, info != nullptr, &sinks); if (s) return s;
-  if (n) {
-    HIPCHK(h, h->pprime.reserve((size_t)n * 6 * sizeof(double)));
-    HIPCHK(h, hipMemcpyAsync(h->pprime.p, records, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(pack_records_kernel, dim3(div_up(n, 256)), dim3(256), 0, h->stream, bv, (const double*)h->pprime.as<double>(),
-                       h->records.as<double>());
-  }
-  s = solve_given_records(h, bv, sinks);
-  if (s) return s;
-  return reg_close(h, 1, MSFL_MEM_HOST, pose_io, h->poses.as<double>(), nullptr, nullptr, info, sinks);   // (host memory: always waited for)
+  return solve_records_impl(h, corner, n_corner, surf, n_surf, records, nullptr, pose_io, info, "msfl_solve_records");
+}
+
+msfl_status msfl_solve_records_deskew(msfl_handle* h, const msfl_point* corner, int n_corner, const msfl_point* surf, int n_surf,
+                                      const double* records, const double* points, double pose_io[7], msfl_match_info* info) {
+  msfl_status s = enter(h); if (s) return s;
+  if (n_corner < 0 || n_surf < 0 || !pose_io || !points || (n_corner + n_surf > 0 && !records) || (n_corner && !corner) || (n_surf && !surf))
+    return fail(h, MSFL_BAD_ARG, "msfl_solve_records_deskew: bad argument");
+  return solve_records_impl(h, corner, n_corner, surf, n_surf, records, points, pose_io, info, "msfl_solve_records_deskew");
 }
 
 }  // extern "C"
@@ -1295,12 +1346,12 @@ msfl_status msfl_solve_records(msfl_handle* h, const msfl_point* corner, int n_c
 
 namespace {
 
-msfl_status solve_given_records(msfl_handle* h, const BatchView& bv, const RegSinks& sinks) {
+msfl_status solve_given_records(msfl_handle* h, const BatchView& bv, const RegSinks& sinks, const double* pprime) {
   const auto no_assoc = [](int) { return MSFL_OK; };        // the records are given: nothing to associate
   const SolverParams sp = solver_params(h->prm, 0);
   if (h->solve_records_block == kSlamLmBlock)                // (any other value, kLmBlock included: the default workgroup)
-    return solve_outer<kSlamLmBlock>(h, 1, bv, nullptr, h->poses.as<double>(), h->status.as<int>(), sinks, sp, 1, no_assoc);
-  return solve_outer<kLmBlock>(h, 1, bv, nullptr, h->poses.as<double>(), h->status.as<int>(), sinks, sp, 1, no_assoc);
+    return solve_outer<kSlamLmBlock>(h, 1, bv, pprime, h->poses.as<double>(), h->status.as<int>(), sinks, sp, 1, no_assoc);
+  return solve_outer<kLmBlock>(h, 1, bv, pprime, h->poses.as<double>(), h->status.as<int>(), sinks, sp, 1, no_assoc);
 }
 
 }  // namespace

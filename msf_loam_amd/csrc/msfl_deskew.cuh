@@ -52,7 +52,9 @@ __device__ __forceinline__ DeltaQP delta_qp(const PreintView& pv, double dt) {
   while (lo < hi) { const int mid = (lo + hi) >> 1; if (dt < pv.sum_dt[mid]) hi = mid; else lo = mid + 1; }
   int idx = lo - 1;
   if (idx > pv.n - 2) idx = pv.n - 2;       // dt == back(): the reference indexes one past the end (:37-39); take s = 1 instead
-  const double s = (dt - pv.sum_dt[idx]) / (pv.sum_dt[idx + 1] - pv.sum_dt[idx]);
+  // (a zero-length interval arises only from that clamp, when the last sample times are equal: 0 / 0 there; s = 1 again, the last sample)
+  const double w = pv.sum_dt[idx + 1] - pv.sum_dt[idx];
+  const double s = w > 0.0 ? (dt - pv.sum_dt[idx]) / w : 1.0;
   quat a, b;
   a.x = pv.dq[4 * idx]; a.y = pv.dq[4 * idx + 1]; a.z = pv.dq[4 * idx + 2]; a.w = pv.dq[4 * idx + 3];
   b.x = pv.dq[4 * idx + 4]; b.y = pv.dq[4 * idx + 5]; b.z = pv.dq[4 * idx + 6]; b.w = pv.dq[4 * idx + 7];

@@ -1439,7 +1439,9 @@ int orc_delta_qp(const double* sum_dt, const double* delta_q, const double* delt
   while (lo < hi) { const int mid = (lo + hi) / 2; if (dt < sum_dt[mid]) hi = mid; else lo = mid + 1; }
   int idx = lo - 1;                                                                      /* :35 */
   if (idx > n_samples - 2) idx = n_samples - 2;
-  const double s = (dt - sum_dt[idx]) / (sum_dt[idx + 1] - sum_dt[idx]);                 /* :37 */
+  /* a zero-length interval arises only from the clamp above (equal last sample times, dt == back()): s = 1, the last sample */
+  const double w = sum_dt[idx + 1] - sum_dt[idx];
+  const double s = w > 0.0 ? (dt - sum_dt[idx]) / w : 1.0;                               /* :37 */
   eigen_slerp(delta_q + 4 * idx, delta_q + 4 * idx + 4, s, q_out);                       /* :38 */
   for (int k = 0; k < 3; k++) p_out[k] = (1 - s) * delta_p[3 * idx + k] + s * delta_p[3 * idx + 3 + k];   /* :39 */
   return 0;

@@ -22,8 +22,8 @@ wrong cache slot or counted twice there moves the pose by microns; it moves H an
   both widths     one problem (3 500 planes, 1 100 edges): equal counts (the oracle's), poses within 1e-9 of each other; not
                   bit-equal, the two widths sum in different orders by design
 
-None of the bars comes from what the kernels deliver.  Out of scope: the de-skew branch of evaluate_pass (pprime != nullptr: no
-plane cache, f64 points) -- msfl_solve_records takes no de-skew arrays.
+None of the bars comes from what the kernels deliver.  The de-skew branch of evaluate_pass (pprime != nullptr: no plane cache, an
+edge loop of its own, f64 points) is held to the same bars by tests/test_gpu_lm_deskew.py through msfl_solve_records_deskew.
 """
 import numpy as np
 import pytest
