@@ -2,6 +2,7 @@
 
     python examples/close_loop.py [--scans 151] [--gap 50] [--every 1] [--max-distance 0.1] [--min-fitness 0.99] [--weights scalar|information]
                                   [--gate distance|mahalanobis] [--gate-bound 16.81]
+                                  [--closure-map session|submap] [--submap-half-width 5] [--rebuild-map PATH]
 
 The figure of eight of examples/loop_candidates.py.  Every scan goes through the device-resident SLAM step (keep_clouds) and into a
 capi.Places.  The odometry the graph starts from is made to drift: the session's consecutive relative poses with a yaw bias and
@@ -17,8 +18,13 @@ every closure is printed after the optimisation.  --gate mahalanobis replaces th
 alone first, the joint marginal of the two nodes of a candidate (PoseGraph.marginals) gives the predicted covariance Sigma_rel of their
 relative pose (capi.relative_covariance), and the candidate passes when e^T (Sigma_rel + Sigma_z)^-1 e <= --gate-bound, e being the
 measured relative pose against the predicted one in the edge's tangent and Sigma_z the closure's own covariance (the inverse of the
-weights it would enter the graph with); the distance is printed for every candidate.  A demonstration; the acceptance rule here is the
-example's, not the library's."""
+weights it would enter the graph with); the distance is printed for every candidate.  --closure-map submap measures a closure against
+a submap instead of the session's (drifted) map: every scan becomes a keyframe of a capi.Keyframes, and ALL candidates (k, j) are
+verified by one compose (the keyframes j-w .. j+w, w = --submap-half-width, laid down in j's frame at relative_pose(pose_map[j],
+pose_map[i])) and one match_pairs_batch from the guess Rz(yaw) at the origin, whose result is the measurement itself; the acceptance
+rules are the same, evaluated against the submap.  --rebuild-map PATH lays the keyframes down again at the optimised poses
+(Keyframes.insert into two fresh map stores) and saves them as PATH_corner.npz / PATH_surf.npz (mapio.save_grid).  A demonstration;
+the acceptance rule here is the example's, not the library's."""
 import argparse
 import os
 import sys
@@ -26,7 +32,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
-from msf_loam_amd import capi, synth
+from msf_loam_amd import capi, mapio, synth
 
 
 def figure_of_eight(n):
@@ -105,6 +111,10 @@ def main():
     ap.add_argument("--gate", choices=("distance", "mahalanobis"), default="distance",
                     help="accept a verified candidate within 1.5 m of its guess, or by its Mahalanobis distance against the odometry graph's marginals")
     ap.add_argument("--gate-bound", type=float, default=16.81, help="mahalanobis: the chi-square bound (16.81: 99 %% at 6 degrees of freedom)")
+    ap.add_argument("--closure-map", choices=("session", "submap"), default="session",
+                    help="verify a candidate against the session's whole map, or against the submap of the scans around the matched one")
+    ap.add_argument("--submap-half-width", type=int, default=5, help="submap: the keyframes j-w .. j+w around the matched scan j")
+    ap.add_argument("--rebuild-map", metavar="PATH", default=None, help="rebuild both map stores at the optimised poses: PATH_corner.npz, PATH_surf.npz")
     args = ap.parse_args()
 
     world = synth.World()
@@ -113,11 +123,16 @@ def main():
     slam = capi.Slam(0, max_scan_points=max(len(p) for p, _ in scans), max_rings=16, pose_odom2map=truth[0], keep_clouds=1)
     places = capi.Places(0, capacity=max(args.scans, 1))
     pose_map, candidates = [], []
+    keep = args.closure_map == "submap" or args.rebuild_map is not None
+    hk = capi.Handle(0) if keep else None
+    kf = capi.Keyframes(hk, max_keyframes=args.scans) if keep else None      # every scan a keyframe, filtered at 0.2 / 0.4 m like the map's inserts
     for k, (pts, ring) in enumerate(scans):
         r = slam.add_scan(pts, ring)
         pose_map.append(np.array(r.pose_map[:]))
         cl = slam.clouds(k)
         assert places.add(cl["full_scan"]) == k
+        if kf is not None:
+            assert kf.add(cl["full_scan"], cl["full_scan"], corner_idx=cl["less_sharp"], surf_idx=cl["less_flat"]) == k
         if k > args.gap and k % args.every == 0:
             m = places.query_entries(k, max_index=k - args.gap, k=1)[0, 0]
             if m["index"] >= 0 and m["distance"] <= args.max_distance:
@@ -125,11 +140,33 @@ def main():
 
     rel, drifted = drifting(pose_map, np.random.default_rng(synth.SEED))
     grid_c, grid_s = slam.grids()
-    h = capi.Handle(0)
-    h.set_map(grid_c.dump(), grid_s.dump())
+    submap = args.closure_map == "submap"
+    h = hk if submap else capi.Handle(0)
+    if not submap:
+        h.set_map(grid_c.dump(), grid_s.dump())
     if args.weights == "information":
-        h.set_uncertainty(1, args.min_eigenvalue)
+        h.set_uncertainty(max(len(candidates), 1) if submap else 1, args.min_eigenvalue)
     n = args.scans
+    identity = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0])
+    if submap and candidates:
+        # every candidate at once: submap p = the keyframes around j laid down in j's frame, scan k registered against it from the
+        # guess Rz(yaw) at the origin; the result is the measured T_j^-1 T_k itself
+        w = args.submap_half_width
+        keys, member_off, guesses = [], [0], []
+        for k, m, _, _ in candidates:
+            j = int(m["index"])
+            keys += list(range(max(j - w, 0), min(j + w, n - 1) + 1))
+            member_off.append(len(keys))
+            guesses.append(turned(identity, float(capi.place_yaw(m["shift"], places.n_sector))))
+        member_poses = [capi.relative_pose(pose_map[int(candidates[p][1]["index"])], pose_map[i])
+                        for p in range(len(candidates)) for i in keys[member_off[p]:member_off[p + 1]]]
+        sub_c, sub_co, sub_s, sub_so = kf.compose(member_off, keys, member_poses, 0.2, 0.4)
+        feats = [kf.get(k) for k, _, _, _ in candidates]
+        co = np.cumsum([0] + [len(c) for c, _ in feats]).astype(np.int32)
+        so = np.cumsum([0] + [len(s) for _, s in feats]).astype(np.int32)
+        sub_z, sub_status, _ = h.match_pairs_batch(sub_c, sub_co, sub_s, sub_so, np.concatenate([c for c, _ in feats]), co,
+                                                   np.concatenate([s for _, s in feats]), so, guesses)
+        sub_unc = h.uncertainty(len(candidates)) if args.weights == "information" else None
     g = capi.PoseGraph(0, max_nodes=n, max_edges=n + len(candidates), max_fixes=1)
     g.add_nodes(drifted)
     g.set_fixed(0)
@@ -139,16 +176,23 @@ def main():
         predicted = g.poses()
         print("odometry graph: %s after %d iterations; the gate reads its marginals" % (capi.GRAPH_TERMINATION[s.termination], s.iterations))
     closures = []
-    for k, m, sharp, flat in candidates:
+    for p, (k, m, sharp, flat) in enumerate(candidates):
         j, yaw = int(m["index"]), float(capi.place_yaw(m["shift"], places.n_sector))
-        corner, surf = h.voxel_downsample(sharp, 0.2), h.voxel_downsample(flat, 0.4)
-        guess = turned(pose_map[j], yaw)
-        status, refined, _ = h.match_scan2map(corner, surf, guess)
-        unc = h.uncertainty(1)[0] if args.weights == "information" else None
+        if submap:
+            # the pair's registration ran above; its fitness is scored against its own submap, in j's frame
+            (corner, surf), base, guess = feats[p], identity, guesses[p]
+            status, refined = int(sub_status[p]), sub_z[p]
+            unc = sub_unc[p] if args.weights == "information" else None
+            h.set_map(sub_c[sub_co[p]:sub_co[p + 1]], sub_s[sub_so[p]:sub_so[p + 1]])
+        else:
+            corner, surf = h.voxel_downsample(sharp, 0.2), h.voxel_downsample(flat, 0.4)
+            base, guess = pose_map[j], turned(pose_map[j], yaw)
+            status, refined, _ = h.match_scan2map(corner, surf, guess)
+            unc = h.uncertainty(1)[0] if args.weights == "information" else None
         fit = capi.fitness(h.score_poses(corner, surf, [refined], args.max_dist), len(corner), len(surf))[0]
-        z = capi.relative_pose(pose_map[j], np.asarray(refined))
+        z = capi.relative_pose(base, np.asarray(refined))
         if args.gate == "mahalanobis":
-            info = closure_information(args.weights, j, k, pose_map[j], np.asarray(refined, np.float64), unc) if status == 0 else None
+            info = closure_information(args.weights, j, k, base, np.asarray(refined, np.float64), unc) if status == 0 else None
             d2 = mahalanobis(g, predicted, j, k, z, info) if info is not None else np.inf
             print("scan %3d ~ scan %3d: Mahalanobis distance %.3g against the bound %.3g" % (k, j, d2, args.gate_bound))
             ok = status == 0 and fit >= args.min_fitness and d2 <= args.gate_bound
@@ -158,14 +202,14 @@ def main():
         print("scan %3d ~ scan %3d: distance %.3f, yaw %+6.1f deg, refined fitness %.3f -> %s (measurement off the truth by %.3f m, %.2f deg)"
               % (k, j, m["distance"], np.degrees(yaw), fit, "edge" if ok else "dropped", dt, np.degrees(dr)))
         if ok:
-            closures.append((j, k, z, unc, np.asarray(refined, np.float64)))
+            closures.append((j, k, z, unc, np.asarray(refined, np.float64), base))
 
     if args.gate == "mahalanobis":
         g.set_poses(drifted)
     if closures and args.weights == "scalar":
         g.add_edges(g.edges([c[0] for c in closures], [c[1] for c in closures], np.array([c[2] for c in closures]), sr=0.005, st=0.05))
-    for j, k, _, unc, refined in closures if args.weights == "information" else []:
-        status, rec = capi.edge_from_uncertainty(j, k, pose_map[j], refined, unc, unc["sigma2"] if unc["sigma2"] > 0.0 else 1.0)
+    for j, k, _, unc, refined, base in closures if args.weights == "information" else []:
+        status, rec = capi.edge_from_uncertainty(j, k, base, refined, unc, unc["sigma2"] if unc["sigma2"] > 0.0 else 1.0)
         if status != capi.OK:
             raise SystemExit("scan %d ~ scan %d: the registration left no usable uncertainty record" % (k, j))
         print("scan %3d ~ scan %3d: information edge of rank %d, sigma2 %.3g, sqrt of the kept eigenvalues / sigma2: %s"
@@ -177,9 +221,27 @@ def main():
     print("ATE against the truth: session %.3f m, drifting odometry %.3f m, after the optimisation %.3f m"
           % (ate(pose_map, truth), ate(drifted, truth), ate(g.poses(), truth)))
     if args.weights == "information":
-        for (j, k, _, _, _), c in zip(closures, g.chi2(capi.GRAPH_FACTOR_EDGE_INFO)):
+        for (j, k, _, _, _, _), c in zip(closures, g.chi2(capi.GRAPH_FACTOR_EDGE_INFO)):
             print("closure scan %3d ~ scan %3d: chi-square %.3g (6 degrees of freedom under the model)" % (k, j, c))
+    if args.rebuild_map is not None:
+        # the corrected trajectory gets its map: every keyframe laid down again at its optimised pose, one insert per keyframe
+        new_c, new_s = capi.Grid(hk, 3.0, 0.2), capi.Grid(hk, 3.0, 0.4)
+        status, n_done = kf.insert(np.arange(n), g.poses(), new_c, new_s)
+        for name, grid, old in (("corner", new_c, grid_c), ("surf", new_s, grid_s)):
+            cells, points = mapio.save_grid("%s_%s.npz" % (args.rebuild_map, name), grid)
+            print("rebuilt %s map: %d keyframes, %d cells, %d points (the session's store: %d points) -> %s_%s.npz"
+                  % (name, n_done, cells, points, old.size()[0], args.rebuild_map, name))
+        # and at the session's own poses: is that the session's map?
+        own_c, own_s = capi.Grid(hk, 3.0, 0.2), capi.Grid(hk, 3.0, 0.4)
+        kf.insert(np.arange(n), pose_map, own_c, own_s)
+        for name, grid, old in (("corner", own_c, grid_c), ("surf", own_s, grid_s)):
+            a, b = grid.dump(), old.dump()
+            same_cells = np.array_equal(grid.dump_cells()[:, :3], old.dump_cells()[:, :3])
+            print("rebuilt at the session's own poses, %s: %d points against the session's %d, %s, %s"
+                  % (name, len(a), len(b), "the same cells" if same_cells else "other cells", "equal bit for bit" if np.array_equal(a, b) else "not equal"))
     g.close()
+    if hk is not None and hk is not h:
+        hk.close()
     h.close()
     places.close()
     slam.close()

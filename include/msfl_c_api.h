@@ -1191,6 +1191,65 @@ msfl_status msfl_graph_marginals_with(msfl_graph* g, const int* pairs, int n_pai
 msfl_status msfl_graph_relative_covariance(const double pose_a[7], const double pose_b[7], const double S_aa[36],
                                            const double S_ab[36], const double S_bb[36], double out[36]);
 
+/* ------------------------------------------------------------------------------------------------------------------
+   Keyframe store: the scans themselves (their less-sharp and less-flat lists) kept on the device, and laid down at any poses
+   as submaps (msfl_keyframes_compose) or into map stores (msfl_keyframes_insert).  docs/kernels/keyframes.md holds the full
+   definition.  A store is created on a handle like msfl_grid, works on that handle's stream and must be destroyed before it.
+   Counts are kept on the host: no call reads a size back from the device.
+     add     : a list is corner[corner_idx[i]], i < n_corner (corner_idx == NULL: the array itself) - the shape of
+               msfl_slam_get_clouds: full_scan with less_sharp_idx / less_flat_idx; device pointers are handed over as they are.
+               With a leaf > 0 the stored list is exactly what msfl_voxel_downsample returns for the list; with leaf == 0 the
+               bytes are stored unchanged.  A point with a non-finite x, y, z or t refuses the add (MSFL_BAD_ARG; host lists are
+               checked before staging, device lists on the device), MSFL_CAPACITY when the keyframe count or a pool would be
+               exceeded; in both cases nothing is added.  *index (optional) receives the new keyframe's index.
+     sizes   : the counts of keyframes [first, first + n) into HOST arrays (either may be NULL).
+     get     : one keyframe's lists (a NULL pointer: not wanted); MSFL_CAPACITY if a capacity is below the list's size.
+     compose : n_submaps clouds per kind in one launch.  Submap b has the members m in [member_off[b], member_off[b + 1]); keys[m]
+               and poses[7 m ..] are indexed absolutely (member_off[0] need not be 0).  Each pose [t, qx qy qz qw] maps its keyframe's
+               frame into the submap's.  Per kind, C_b is the concatenation in member order of the keyframe's list transformed
+               exactly as msfl_transform_cloud transforms it; the output for b is C_b (leaf == 0) or msfl_voxel_downsample(C_b, leaf).
+               Outputs are written back to back, out_*_off (HOST, n_submaps + 1) starts at 0.  A key may repeat; a member without
+               points contributes nothing; a submap without members is an empty cloud.  MSFL_BAD_ARG: a key that is no keyframe, a
+               pose with a non-finite entry, decreasing offsets, a negative or non-finite leaf.  MSFL_CAPACITY: cap_kind below the
+               sum of that kind's member counts, or that sum at 2^31 or beyond.  In every refused case nothing is launched and no
+               output is written.  A transformed cloud the batch voxel filter refuses gives that call's status.  With
+               MSFL_MEM_DEVICE the outputs go straight to msfl_match_pairs_batch (n_submaps == 1: msfl_set_map) and, with both
+               leaves 0, the call is asynchronous.  The call uses scratch of its own: a matcher call after it is bit-identical.
+     insert  : for i = 0 .. n-1 in order, keyframe keys[i] transformed by poses[7 i ..] goes through msfl_grid_insert_scan of each
+               given store (either may be NULL): bit for bit the caller's loop of msfl_transform_cloud + msfl_grid_insert_scan.  The
+               first keyframe a store refuses (a point beyond +-8192 cells: MSFL_CAPACITY) ends the call with that status; *n_done
+               is its position, earlier keyframes stay inserted, that keyframe is in neither store.  MSFL_BAD_ARG (nothing
+               inserted): a key that is no keyframe, a non-finite pose entry, a grid of another handle. */
+typedef struct msfl_keyframes_s msfl_keyframes;
+typedef struct msfl_keyframes_config {
+  int   max_keyframes;       /* default 4096 */
+  int   max_corner_points;   /* pool, fixed at creation; default 4 194 304 */
+  int   max_surf_points;     /* default 16 777 216 */
+  float leaf_corner;         /* voxel filter applied by add; default 0.2, 0 = store the list as given */
+  float leaf_surf;           /* default 0.4, 0 = as given */
+} msfl_keyframes_config;
+
+void        msfl_keyframes_default_config(msfl_keyframes_config* c);
+msfl_status msfl_keyframes_create(msfl_handle* h, const msfl_keyframes_config* c /* NULL = defaults */, msfl_keyframes** out);
+void        msfl_keyframes_destroy(msfl_keyframes* k);
+int         msfl_keyframes_size(const msfl_keyframes* k);
+msfl_status msfl_keyframes_add(msfl_keyframes* k,
+                               const msfl_point* corner, const int* corner_idx, int n_corner,
+                               const msfl_point* surf,   const int* surf_idx,   int n_surf,
+                               msfl_mem mem, int* index);
+msfl_status msfl_keyframes_sizes(msfl_keyframes* k, int first, int n, int* n_corner, int* n_surf);   /* HOST arrays */
+msfl_status msfl_keyframes_get(msfl_keyframes* k, int index, msfl_point* corner, int cap_corner,
+                               msfl_point* surf, int cap_surf, msfl_mem mem);
+msfl_status msfl_keyframes_compose(msfl_keyframes* k, int n_submaps,
+                                   const int* member_off /* HOST, n_submaps+1 */, const int* keys /* HOST */,
+                                   const double* poses /* HOST, 7 per member */,
+                                   float leaf_corner, float leaf_surf,
+                                   msfl_point* out_corner, int cap_corner, int* out_corner_off /* HOST, n_submaps+1 */,
+                                   msfl_point* out_surf,   int cap_surf,   int* out_surf_off,
+                                   msfl_mem mem);
+msfl_status msfl_keyframes_insert(msfl_keyframes* k, const int* keys, const double* poses, int n,
+                                  msfl_grid* grid_corner /* may be NULL */, msfl_grid* grid_surf /* may be NULL */, int* n_done);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

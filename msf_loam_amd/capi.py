@@ -45,6 +45,8 @@ EXPORTED = [
     "msfl_graph_add_edges_info", "msfl_graph_add_fixes_info", "msfl_graph_edge_from_uncertainty", "msfl_graph_fix_from_covariance",
     "msfl_graph_factor_chi2",
     "msfl_graph_marginals_default_options", "msfl_graph_marginals", "msfl_graph_marginals_with", "msfl_graph_relative_covariance",
+    "msfl_keyframes_default_config", "msfl_keyframes_create", "msfl_keyframes_destroy", "msfl_keyframes_size", "msfl_keyframes_add",
+    "msfl_keyframes_sizes", "msfl_keyframes_get", "msfl_keyframes_compose", "msfl_keyframes_insert",
 ]
 
 
@@ -1028,6 +1030,151 @@ class _BorrowedGrid(Grid):
 
     def close(self):
         self.g = C.c_void_p()
+
+
+class KeyframesConfig(C.Structure):
+    _fields_ = [("max_keyframes", C.c_int), ("max_corner_points", C.c_int), ("max_surf_points", C.c_int), ("leaf_corner", C.c_float),
+                ("leaf_surf", C.c_float)]
+
+
+class Keyframes:
+    """Device-resident keyframe store (msfl_keyframes_*) over a Handle's stream: the scans' corner / surf lists, laid down at any
+    poses as submaps (compose) or into map stores (insert).  Keyword arguments are the fields of msfl_keyframes_config
+    (max_keyframes, max_corner_points, max_surf_points, leaf_corner, leaf_surf)."""
+
+    def __init__(self, handle, **cfg):
+        self.handle = handle
+        self.lib = handle.lib
+        self.lib.msfl_keyframes_size.argtypes = [C.c_void_p]
+        self.config = KeyframesConfig()
+        self.lib.msfl_keyframes_default_config(C.byref(self.config))
+        for k, v in cfg.items():
+            if k not in dict(KeyframesConfig._fields_):
+                raise TypeError("unknown msfl_keyframes_config field %r" % (k,))
+            setattr(self.config, k, v)
+        self.k = C.c_void_p()
+        handle._check(self.lib.msfl_keyframes_create(handle.h, C.byref(self.config), C.byref(self.k)), "msfl_keyframes_create")
+        if not hasattr(handle, "_grids"):
+            handle._grids = weakref.WeakSet()
+        handle._grids.add(self)                                     # Handle.close() closes what must go before the handle
+
+    def close(self):
+        if self.k:
+            self.lib.msfl_keyframes_destroy(self.k)
+            self.k = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def size(self):
+        return int(self.lib.msfl_keyframes_size(self.k))
+
+    def __len__(self):
+        return self.size()
+
+    @staticmethod
+    def _idx(idx):
+        return None if idx is None else np.ascontiguousarray(idx, np.int32)
+
+    def _add(self, corner, corner_idx, n_corner, surf, surf_idx, n_surf, mem, allow, what):
+        index = C.c_int(-1)
+        s = self.handle._check(self.lib.msfl_keyframes_add(self.k, _vp(corner), _vp(corner_idx), C.c_int(int(n_corner)), _vp(surf), _vp(surf_idx),
+                                                           C.c_int(int(n_surf)), C.c_int(mem), C.byref(index)), what, allow)
+        return index.value if s == OK else s
+
+    def add(self, corner, surf, corner_idx=None, surf_idx=None, allow=()):
+        """Host memory.  With an index list the kind's list is corner[corner_idx] (the shape of Slam.clouds(): full_scan with
+        less_sharp_idx / less_flat_idx).  Returns the new keyframe's index (or the refusing status when it is in `allow`)."""
+        corner, surf = _pts(corner), _pts(surf)
+        ci, si = self._idx(corner_idx), self._idx(surf_idx)
+        return self._add(corner, ci, len(corner) if ci is None else len(ci), surf, si, len(surf) if si is None else len(si), MEM_HOST, allow,
+                         "msfl_keyframes_add")
+
+    def add_device(self, corner, n_corner, surf, n_surf, corner_idx=None, surf_idx=None, allow=()):
+        """Device pointers (torch tensors / raw pointers) of 16-byte points and, optionally, of int32 index lists; n_* are the lists' sizes."""
+        return self._add(corner, corner_idx, n_corner, surf, surf_idx, n_surf, MEM_DEVICE, allow, "msfl_keyframes_add(device)")
+
+    def sizes(self, first=0, n=None):
+        """-> (n_corner, n_surf) int32 arrays of keyframes [first, first + n): host bookkeeping, no device call."""
+        n = self.size() - first if n is None else int(n)
+        nc, ns = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int32)
+        self.handle._check(self.lib.msfl_keyframes_sizes(self.k, C.c_int(int(first)), C.c_int(n), _vp(nc), _vp(ns)), "msfl_keyframes_sizes")
+        return nc, ns
+
+    def get(self, index):
+        """-> (corner, surf) of one keyframe as stored."""
+        nc, ns = self.sizes(index, 1)
+        corner, surf = np.zeros((int(nc[0]), 4), np.float32), np.zeros((int(ns[0]), 4), np.float32)
+        self.handle._check(self.lib.msfl_keyframes_get(self.k, C.c_int(int(index)), _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
+                                                       C.c_int(MEM_HOST)), "msfl_keyframes_get")
+        return corner, surf
+
+    def get_device(self, index, corner, cap_corner, surf, cap_surf):
+        self.handle._check(self.lib.msfl_keyframes_get(self.k, C.c_int(int(index)), _vp(corner), C.c_int(int(cap_corner)), _vp(surf),
+                                                       C.c_int(int(cap_surf)), C.c_int(MEM_DEVICE)), "msfl_keyframes_get(device)")
+
+    @staticmethod
+    def _members(member_off, keys, poses):
+        member_off = np.ascontiguousarray(member_off, np.int32)
+        keys = np.ascontiguousarray(keys, np.int32)
+        poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
+        return member_off, keys, poses
+
+    def member_totals(self, member_off, keys):
+        """Sum of the member counts per kind over members [member_off[0], member_off[-1]): the capacities compose needs."""
+        nc, ns = self.sizes()
+        k = np.asarray(keys, np.int64)[int(member_off[0]):int(member_off[-1])]
+        return int(nc[k].sum()), int(ns[k].sum())
+
+    def _compose(self, member_off, keys, poses, leaf_corner, leaf_surf, out_corner, cap_corner, out_surf, cap_surf, mem, allow, what):
+        B = len(member_off) - 1
+        off_c, off_s = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32)
+        s = self.handle._check(self.lib.msfl_keyframes_compose(self.k, C.c_int(B), _vp(member_off), _vp(keys), _vp(poses), C.c_float(leaf_corner),
+                                                               C.c_float(leaf_surf), _vp(out_corner), C.c_int(int(cap_corner)), _vp(off_c),
+                                                               _vp(out_surf), C.c_int(int(cap_surf)), _vp(off_s), C.c_int(mem)), what, allow)
+        return s, off_c, off_s
+
+    def compose(self, member_off, keys, poses, leaf_corner=0.0, leaf_surf=0.0, allow=(), out_corner=None, out_surf=None, cap_corner=None,
+                cap_surf=None):
+        """Host memory.  Submap b = members [member_off[b], member_off[b + 1]) of keys / poses (absolute positions), each keyframe
+        transformed by its pose [t, qx qy qz qw]; leaf 0: the concatenation, else its voxel filter.  Returns
+        (corner, corner_off, surf, surf_off), or the refusing status when it is in `allow`.  out_* / cap_*: the caller's arrays and
+        the capacities to state (tests of the refusals); by default both come from the member counts."""
+        member_off, keys, poses = self._members(member_off, keys, poses)
+        if out_corner is None or out_surf is None:
+            tc, ts = self.member_totals(member_off, keys)
+            out_corner = np.zeros((max(tc, 1), 4), np.float32) if out_corner is None else out_corner
+            out_surf = np.zeros((max(ts, 1), 4), np.float32) if out_surf is None else out_surf
+        cap_corner = len(out_corner) if cap_corner is None else cap_corner
+        cap_surf = len(out_surf) if cap_surf is None else cap_surf
+        s, off_c, off_s = self._compose(member_off, keys, poses, leaf_corner, leaf_surf, out_corner, cap_corner, out_surf, cap_surf, MEM_HOST, allow,
+                                        "msfl_keyframes_compose")
+        if s != OK:
+            return s
+        return out_corner[:off_c[-1]].copy(), off_c, out_surf[:off_s[-1]].copy(), off_s
+
+    def compose_device(self, member_off, keys, poses, leaf_corner, leaf_surf, out_corner, cap_corner, out_surf, cap_surf, allow=()):
+        """Device outputs (torch tensors / raw pointers with room for cap_* points) -> (corner_off, surf_off) host arrays: what
+        Handle.match_pairs_batch_device takes as the maps' offsets.  Asynchronous when both leaves are 0."""
+        member_off, keys, poses = self._members(member_off, keys, poses)
+        s, off_c, off_s = self._compose(member_off, keys, poses, leaf_corner, leaf_surf, out_corner, cap_corner, out_surf, cap_surf, MEM_DEVICE, allow,
+                                        "msfl_keyframes_compose(device)")
+        return (off_c, off_s) if s == OK else s
+
+    def insert(self, keys, poses, grid_corner=None, grid_surf=None, allow=()):
+        """Keyframes keys[i] at poses[i] into the given map stores (capi.Grid of the same handle; None: that kind is skipped), in
+        order.  Returns (status, n_done)."""
+        keys = np.ascontiguousarray(keys, np.int32)
+        poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
+        n_done = C.c_int(0)
+        s = self.handle._check(self.lib.msfl_keyframes_insert(self.k, _vp(keys), _vp(poses), C.c_int(len(keys)),
+                                                              grid_corner.g if grid_corner is not None else None,
+                                                              grid_surf.g if grid_surf is not None else None, C.byref(n_done)),
+                               "msfl_keyframes_insert", allow)
+        return s, n_done.value
 
 
 class Slam:

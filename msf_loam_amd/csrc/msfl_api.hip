@@ -29,6 +29,7 @@
 #include "msfl_extract.cuh"
 #include "msfl_odom.cuh"
 #include "msfl_grid.cuh"
+#include "msfl_keyframes.cuh"   // includes msfl_keyframes_host.h
 #include "msfl_deskew.cuh"
 #include "msfl_uncertainty.cuh"
 #include "msfl_degeneracy.cuh"
@@ -1356,3 +1357,4 @@ msfl_status solve_given_records(msfl_handle* h, const BatchView& bv, const RegSi
 
 }  // namespace
 #include "msfl_api_graph.inc"
+#include "msfl_api_keyframes.inc"

@@ -136,3 +136,90 @@ def load_places(path, places=None, device=0, capacity=None):
     if len(desc):
         places.add_descriptors(desc)
     return places
+
+
+# ---- keyframe store (capi.Keyframes) ----
+
+KEYFRAMES_FORMAT = 1
+KEYFRAMES_CONFIG_FIELDS = ("max_keyframes", "max_corner_points", "max_surf_points", "leaf_corner", "leaf_surf")
+
+
+def _keyframes_validate(cfg, n_corner, n_surf, corner, surf):
+    """The rules msfl_keyframes_create and msfl_keyframes_add apply, so that a file they would refuse is refused when it is read."""
+    for name, a in (("n_corner", n_corner), ("n_surf", n_surf)):
+        if a.ndim != 1 or a.dtype != np.int32:
+            raise MapFileError("%s: a 1-D int32 array is needed, got %s %s" % (name, a.dtype, a.shape))
+        if (a < 0).any():
+            raise MapFileError("%s: a negative count" % name)
+    if len(n_corner) != len(n_surf):
+        raise MapFileError("n_corner lists %d keyframes, n_surf %d" % (len(n_corner), len(n_surf)))
+    for name, pts, cnt in (("corner", corner, n_corner), ("surf", surf, n_surf)):
+        if pts.ndim != 2 or pts.shape[1] != 4 or pts.dtype != np.float32:
+            raise MapFileError("%s: an (m, 4) float32 array is needed, got %s %s" % (name, pts.dtype, pts.shape))
+        if int(cnt.astype(np.int64).sum()) != len(pts):
+            raise MapFileError("the %s counts sum to %d, the file holds %d points" % (name, int(cnt.astype(np.int64).sum()), len(pts)))
+        if not np.isfinite(pts).all():
+            raise MapFileError("a %s point is not finite" % name)
+    if cfg["max_keyframes"] < 1 or cfg["max_corner_points"] < 0 or cfg["max_surf_points"] < 0:
+        raise MapFileError("max_keyframes < 1 or a negative pool size")
+    for k in ("leaf_corner", "leaf_surf"):
+        if not (np.isfinite(cfg[k]) and cfg[k] >= 0):
+            raise MapFileError("%s is negative or not finite" % k)
+    if len(n_corner) > cfg["max_keyframes"] or len(corner) > cfg["max_corner_points"] or len(surf) > cfg["max_surf_points"]:
+        raise MapFileError("the file holds more than its own config has room for")
+
+
+def write_keyframes(path, cfg, n_corner, n_surf, corner, surf):
+    """One store as `path` (.npz): its config, the counts per keyframe and the points of each kind back to back."""
+    cfg = {k: (int(cfg[k]) if k.startswith("max_") else float(np.float32(cfg[k]))) for k in KEYFRAMES_CONFIG_FIELDS}
+    n_corner, n_surf = np.ascontiguousarray(n_corner), np.ascontiguousarray(n_surf)
+    corner, surf = np.ascontiguousarray(corner), np.ascontiguousarray(surf)
+    _keyframes_validate(cfg, n_corner, n_surf, corner, surf)
+    with open(path, "wb") as f:
+        np.savez(f, keyframes_format=np.int32(KEYFRAMES_FORMAT), n_corner=n_corner, n_surf=n_surf, corner=corner, surf=surf,
+                 **{k: (np.int32(v) if k.startswith("max_") else np.float32(v)) for k, v in cfg.items()})
+
+
+def read_keyframes(path):
+    """-> (config dict, n_corner, n_surf, corner, surf), validated."""
+    keys = ("keyframes_format", "n_corner", "n_surf", "corner", "surf") + KEYFRAMES_CONFIG_FIELDS
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in keys if k not in z.files]
+        if missing:
+            raise MapFileError("not a keyframe file: no %s" % ", ".join(missing))
+        if int(z["keyframes_format"]) != KEYFRAMES_FORMAT:
+            raise MapFileError("keyframe file format %d, this reader knows %d" % (int(z["keyframes_format"]), KEYFRAMES_FORMAT))
+        cfg = {k: (int(z[k]) if k.startswith("max_") else float(z[k])) for k in KEYFRAMES_CONFIG_FIELDS}
+        n_corner, n_surf, corner, surf = z["n_corner"], z["n_surf"], z["corner"], z["surf"]
+    _keyframes_validate(cfg, n_corner, n_surf, corner, surf)
+    return cfg, n_corner, n_surf, np.ascontiguousarray(corner), np.ascontiguousarray(surf)
+
+
+def save_keyframes(path, keyframes):
+    """The config and every keyframe of a capi.Keyframes as one .npz.  Returns the number of keyframes."""
+    n = keyframes.size()
+    n_corner, n_surf = keyframes.sizes()
+    lists = [keyframes.get(i) for i in range(n)]
+    corner = np.concatenate([c for c, _ in lists]) if n else np.zeros((0, 4), np.float32)
+    surf = np.concatenate([s for _, s in lists]) if n else np.zeros((0, 4), np.float32)
+    write_keyframes(path, {k: getattr(keyframes.config, k) for k in KEYFRAMES_CONFIG_FIELDS}, n_corner, n_surf, corner, surf)
+    return n
+
+
+def load_keyframes(path, handle, keyframes=None):
+    """A keyframe file into a capi.Keyframes through msfl_keyframes_add.  The file's lists are stored lists: they must not pass a
+    voxel filter again, so the store they go into has both leaves 0.  keyframes=None creates one on `handle` with the file's pool
+    sizes and leaves 0; an existing one must have leaves 0 itself.  Returns it; the file's config is left in `.file_config`."""
+    from . import capi
+    cfg, n_corner, n_surf, corner, surf = read_keyframes(path)
+    if keyframes is None:
+        keyframes = capi.Keyframes(handle, **dict(cfg, leaf_corner=0.0, leaf_surf=0.0))
+    elif keyframes.config.leaf_corner != 0.0 or keyframes.config.leaf_surf != 0.0:
+        raise MapFileError("the store filters what is added (leaves %g / %g): stored lists need leaves 0" %
+                           (keyframes.config.leaf_corner, keyframes.config.leaf_surf))
+    oc = np.concatenate([[0], np.cumsum(n_corner, dtype=np.int64)])
+    os_ = np.concatenate([[0], np.cumsum(n_surf, dtype=np.int64)])
+    for i in range(len(n_corner)):
+        keyframes.add(corner[oc[i]:oc[i + 1]], surf[os_[i]:os_[i + 1]])
+    keyframes.file_config = cfg
+    return keyframes
