@@ -3,6 +3,7 @@
     python examples/close_loop.py [--scans 151] [--gap 50] [--every 1] [--max-distance 0.1] [--min-fitness 0.99] [--weights scalar|information]
                                   [--gate distance|mahalanobis] [--gate-bound 16.81]
                                   [--closure-map session|submap] [--submap-half-width 5] [--rebuild-map PATH]
+                                  [--closure-loss KIND:A]
 
 The figure of eight of examples/loop_candidates.py.  Every scan goes through the device-resident SLAM step (keep_clouds) and into a
 capi.Places.  The odometry the graph starts from is made to drift: the session's consecutive relative poses with a yaw bias and
@@ -23,7 +24,10 @@ a submap instead of the session's (drifted) map: every scan becomes a keyframe o
 verified by one compose (the keyframes j-w .. j+w, w = --submap-half-width, laid down in j's frame at relative_pose(pose_map[j],
 pose_map[i])) and one match_pairs_batch from the guess Rz(yaw) at the origin, whose result is the measurement itself; the acceptance
 rules are the same, evaluated against the submap.  --rebuild-map PATH lays the keyframes down again at the optimised poses
-(Keyframes.insert into two fresh map stores) and saves them as PATH_corner.npz / PATH_surf.npz (mapio.save_grid).  A demonstration;
+(Keyframes.insert into two fresh map stores) and saves them as PATH_corner.npz / PATH_surf.npz (mapio.save_grid).  --closure-loss KIND:A (geman_mcclure:1, cauchy:1, soft_l_one:2, huber:0.5, none) gives every closure edge a loss of its
+own (PoseGraph.set_losses) while the odometry chain stays at the graph's Huber loss, in both weight modes: a redescending loss switches
+a closure that contradicts the rest off inside the solve, and after the optimisation every closure's weight rho'(|r|^2)
+(PoseGraph.weights; 1: kept, near 0: switched off) is printed next to its chi-square.  A demonstration;
 the acceptance rule here is the example's, not the library's."""
 import argparse
 import os
@@ -115,7 +119,15 @@ def main():
                     help="verify a candidate against the session's whole map, or against the submap of the scans around the matched one")
     ap.add_argument("--submap-half-width", type=int, default=5, help="submap: the keyframes j-w .. j+w around the matched scan j")
     ap.add_argument("--rebuild-map", metavar="PATH", default=None, help="rebuild both map stores at the optimised poses: PATH_corner.npz, PATH_surf.npz")
+    ap.add_argument("--closure-loss", metavar="KIND:A", default=None,
+                    help="the loss of every closure edge, e.g. geman_mcclure:1 (kinds: %s); default: the graph's Huber loss" % ", ".join(capi.GRAPH_LOSS_NAMES[1:]))
     args = ap.parse_args()
+    closure_loss = None
+    if args.closure_loss:
+        kind, _, a = args.closure_loss.partition(":")
+        if kind not in capi.GRAPH_LOSS_NAMES:
+            ap.error("--closure-loss: unknown kind %r" % kind)
+        closure_loss = (capi.GRAPH_LOSS_NAMES.index(kind), float(a or 0.0))
 
     world = synth.World()
     truth = figure_of_eight(args.scans)
@@ -215,12 +227,21 @@ def main():
         print("scan %3d ~ scan %3d: information edge of rank %d, sigma2 %.3g, sqrt of the kept eigenvalues / sigma2: %s"
               % (k, j, 6 - unc["n_degenerate"], unc["sigma2"], np.array2string(np.linalg.norm(rec["sqrt_information"][0], axis=1), precision=1)))
         g.add_edges_info(rec)
+    closure_kind = capi.GRAPH_FACTOR_EDGE_INFO if args.weights == "information" else capi.GRAPH_FACTOR_EDGE
+    first_closure = 0 if args.weights == "information" else n - 1         # scalar closures follow the chain's n - 1 edges
+    if closure_loss and closures:
+        g.set_losses(closure_kind, closure_loss, first=first_closure, n=len(closures))
+        print("%d closure edges under the loss %s; the chain stays at Huber %g" % (len(closures), args.closure_loss, g.config.huber_delta))
     s = g.optimize()
     print("%d closure edges (%d of them long: both ends free, more than one apart); %s after %d iterations (%d CG iterations, %d unconverged); cost %.4g -> %.4g"
           % (len(closures), s.n_long_edges, capi.GRAPH_TERMINATION[s.termination], s.iterations, s.cg_iterations, s.cg_unconverged, s.initial_cost, s.final_cost))
     print("ATE against the truth: session %.3f m, drifting odometry %.3f m, after the optimisation %.3f m"
           % (ate(pose_map, truth), ate(drifted, truth), ate(g.poses(), truth)))
-    if args.weights == "information":
+    if closure_loss and closures:
+        chi, w = g.chi2(closure_kind, first_closure, len(closures)), g.weights(closure_kind, first_closure, len(closures))
+        for (j, k, _, _, _, _), c, wk in zip(closures, chi, w):
+            print("closure scan %3d ~ scan %3d: chi-square %.3g, weight %.3g under %s" % (k, j, c, wk, args.closure_loss))
+    elif args.weights == "information":
         for (j, k, _, _, _, _), c in zip(closures, g.chi2(capi.GRAPH_FACTOR_EDGE_INFO)):
             print("closure scan %3d ~ scan %3d: chi-square %.3g (6 degrees of freedom under the model)" % (k, j, c))
     if args.rebuild_map is not None:

@@ -106,6 +106,23 @@ class PoseGraph {
     Check(msfl_graph_factor_chi2(g_, kind, first, n, out.data()), "msfl_graph_factor_chi2");
     return out;
   }
+  // A loss per factor (msfl_graph_set_losses): factors first .. first + n of one kind get `losses` (n records, or one for all of them);
+  // a closure under MSFL_GRAPH_LOSS_GEMAN_MCCLURE is switched off by the solve when it contradicts the rest.
+  void SetLosses(int factor_kind, int first, int n, const std::vector<msfl_graph_loss>& losses) {
+    Check(msfl_graph_set_losses(g_, factor_kind, first, n, losses.data(), static_cast<int>(losses.size())), "msfl_graph_set_losses");
+  }
+  void SetLosses(int factor_kind, int first, int n, int loss_kind, double a) { SetLosses(factor_kind, first, n, {msfl_graph_loss{loss_kind, 0, a}}); }
+  std::vector<msfl_graph_loss> Losses(int factor_kind, int first, int n) {
+    std::vector<msfl_graph_loss> out(static_cast<std::size_t>(n > 0 ? n : 0));
+    Check(msfl_graph_get_losses(g_, factor_kind, first, n, out.data()), "msfl_graph_get_losses");
+    return out;
+  }
+  // rho'(|r|^2) of the same factors at the current poses, each under its own loss: near 0 for a factor the loss has switched off
+  std::vector<double> FactorWeights(int factor_kind, int first, int n) {
+    std::vector<double> out(static_cast<std::size_t>(n > 0 ? n : 0));
+    Check(msfl_graph_factor_weights(g_, factor_kind, first, n, out.data()), "msfl_graph_factor_weights");
+    return out;
+  }
   // Covariance blocks Sigma_ab of the node pairs at the current poses (Covariance::GetCovarianceBlockInTangentSpace): blocks[k] is
   // row-major 6 x 6 in [dt ; dtheta], world frame, rotation on the left; a == b gives a node's marginal.  summary.singular: all NaN.
   struct MarginalBlocks { std::vector<std::array<double, 36>> blocks; msfl_graph_marginals_summary summary; };

@@ -1148,6 +1148,35 @@ msfl_status msfl_graph_fix_from_covariance(int i, int j, double t, const double 
 enum { MSFL_GRAPH_FACTOR_EDGE = 0, MSFL_GRAPH_FACTOR_FIX = 1, MSFL_GRAPH_FACTOR_EDGE_INFO = 2, MSFL_GRAPH_FACTOR_FIX_INFO = 3 };
 msfl_status msfl_graph_factor_chi2(msfl_graph* g, int kind, int first, int n, double* out /* HOST */);
 
+/* A loss per factor (docs/kernels/graph.md, "A loss per factor"): Ceres gives every residual block a LossFunction of its own, and so
+   does this.  A loop closer leaves the odometry chain at the graph's loss and puts a redescending one on its closures: a wrong
+   closure is then switched off inside the solve, and msfl_graph_factor_weights reads the inlier decision back.  With s = |r|^2,
+   a > 0, b = a^2 (Ceres' forms; every rho' is clamped from below at DBL_MIN):
+     DEFAULT        the graph's huber_delta, what every factor has without a record
+     NONE           rho = s                                  rho' = 1
+     HUBER          rho = s if s <= b, else 2 a sqrt(s) - b  rho' = 1, else a / sqrt(s)
+     SOFT_L_ONE     rho = 2 b (sqrt(1 + s/b) - 1)            rho' = 1 / sqrt(1 + s/b)
+     CAUCHY         rho = b log(1 + s/b)                     rho' = 1 / (1 + s/b)
+     GEMAN_MCCLURE  rho = b s / (b + s)                      rho' = (b / (b + s))^2
+   All have rho'' <= 0: residual and Jacobian rows are scaled by sqrt(rho'), the cost is rho / 2, as for HuberLoss(huber_delta).
+   msfl_graph_cost, msfl_graph_optimize and msfl_graph_marginals all see the records.
+   set_losses gives factors first .. first + n of one factor kind (MSFL_GRAPH_FACTOR_*) the records losses[0 .. n_losses), n_losses
+   = n, or 1 to give them all the same one.  It may be called again at any time for factors that exist (a shrinking-a schedule is a
+   loop of set_losses and optimize in the caller).  `a` of DEFAULT and NONE is not read and is stored as 0.  Factors added later
+   start at DEFAULT; msfl_graph_clear forgets the records.  MSFL_BAD_ARG, nothing set: an unknown factor or loss kind, a <= 0 or a
+   non-finite a on a kind that reads it, a range outside that kind's factors, n_losses neither n nor 1.
+   A graph that never calls set_losses allocates and launches nothing more than before and runs the same kernels. */
+enum { MSFL_GRAPH_LOSS_DEFAULT = 0, MSFL_GRAPH_LOSS_NONE = 1, MSFL_GRAPH_LOSS_HUBER = 2, MSFL_GRAPH_LOSS_SOFT_L_ONE = 3,
+       MSFL_GRAPH_LOSS_CAUCHY = 4, MSFL_GRAPH_LOSS_GEMAN_MCCLURE = 5 };
+typedef struct msfl_graph_loss { int kind; int reserved; double a; } msfl_graph_loss;
+msfl_status msfl_graph_set_losses(msfl_graph* g, int factor_kind, int first, int n, const msfl_graph_loss* losses /* HOST */,
+                                  int n_losses);
+/* the records of factors first .. first + n; a factor that was never given one reports DEFAULT */
+msfl_status msfl_graph_get_losses(msfl_graph* g, int factor_kind, int first, int n, msfl_graph_loss* out /* HOST */);
+/* rho'(|r|^2) of factors first .. first + n at the current poses, each under its own loss: 1 for a factor the loss leaves alone,
+   towards 0 for one it has switched off.  Changes nothing and refuses what msfl_graph_factor_chi2 refuses. */
+msfl_status msfl_graph_factor_weights(msfl_graph* g, int factor_kind, int first, int n, double* out /* HOST */);
+
 /* Marginal and cross covariances of the poses (docs/kernels/graph.md, "Marginals"): what Ceres'
    Covariance::GetCovarianceBlockInTangentSpace gives.  At the current poses every factor is linearised as the solve linearises it
    (HuberLoss corrector at huber_delta applied), H = J^T J over the free nodes' tangent with NO LM diagonal, Sigma = H^-1.

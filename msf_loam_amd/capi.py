@@ -44,6 +44,7 @@ EXPORTED = [
     "msfl_graph_optimize", "msfl_graph_get_trace",
     "msfl_graph_add_edges_info", "msfl_graph_add_fixes_info", "msfl_graph_edge_from_uncertainty", "msfl_graph_fix_from_covariance",
     "msfl_graph_factor_chi2",
+    "msfl_graph_set_losses", "msfl_graph_get_losses", "msfl_graph_factor_weights",
     "msfl_graph_marginals_default_options", "msfl_graph_marginals", "msfl_graph_marginals_with", "msfl_graph_relative_covariance",
     "msfl_keyframes_default_config", "msfl_keyframes_create", "msfl_keyframes_destroy", "msfl_keyframes_size", "msfl_keyframes_add",
     "msfl_keyframes_sizes", "msfl_keyframes_get", "msfl_keyframes_compose", "msfl_keyframes_insert",
@@ -1540,6 +1541,11 @@ GRAPH_EDGE_INFO_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("z", np.flo
 GRAPH_FIX_INFO_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("t", np.float64), ("p", np.float64, (3,)), ("sqrt_information", np.float64, (3, 3))])
 assert GRAPH_EDGE_INFO_DTYPE.itemsize == 352 and GRAPH_FIX_INFO_DTYPE.itemsize == 112
 GRAPH_FACTOR_EDGE, GRAPH_FACTOR_FIX, GRAPH_FACTOR_EDGE_INFO, GRAPH_FACTOR_FIX_INFO = range(4)
+# msfl_graph_loss: the loss of one factor (PoseGraph.set_losses); `a` is read by HUBER and the kinds after it
+GRAPH_LOSS_DEFAULT, GRAPH_LOSS_NONE, GRAPH_LOSS_HUBER, GRAPH_LOSS_SOFT_L_ONE, GRAPH_LOSS_CAUCHY, GRAPH_LOSS_GEMAN_MCCLURE = range(6)
+GRAPH_LOSS_NAMES = ("default", "none", "huber", "soft_l_one", "cauchy", "geman_mcclure")
+GRAPH_LOSS_DTYPE = np.dtype([("kind", np.int32), ("reserved", np.int32), ("a", np.float64)])
+assert GRAPH_LOSS_DTYPE.itemsize == 16
 
 GRAPH_TERMINATION = ("empty", "gradient", "max_iterations", "min_radius", "invalid_steps", "parameter", "function")
 
@@ -1732,6 +1738,43 @@ class PoseGraph:
         out = np.zeros(max(0, int(n)), np.float64)
         s = self._check(self.lib.msfl_graph_factor_chi2(self.p, C.c_int(int(kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(out)),
                         "msfl_graph_factor_chi2", allow)
+        return out if s == OK else s
+
+    @staticmethod
+    def loss_records(kind, a=0.0):
+        """Records of GRAPH_LOSS_DTYPE from loss kinds (GRAPH_LOSS_*) and their parameters, scalars or arrays."""
+        kind = np.atleast_1d(np.asarray(kind, np.int32))
+        rec = np.zeros(len(kind), GRAPH_LOSS_DTYPE)
+        rec["kind"], rec["a"] = kind, a
+        return rec
+
+    def set_losses(self, factor_kind, rec, first=0, n=None, allow=()):
+        """msfl_graph_set_losses: gives factors first .. first + n (default: to the last) of one kind (GRAPH_FACTOR_*) the records `rec`
+        (GRAPH_LOSS_DTYPE, or a (loss kind, a) pair): n of them, or one for all."""
+        if isinstance(rec, tuple):
+            rec = self.loss_records(*rec)
+        rec = np.ascontiguousarray(rec, GRAPH_LOSS_DTYPE)
+        if n is None:
+            n = self._count[int(factor_kind)] - int(first) if 0 <= int(factor_kind) < 4 else len(rec)
+        return self._check(self.lib.msfl_graph_set_losses(self.p, C.c_int(int(factor_kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(rec),
+                                                          C.c_int(len(rec))), "msfl_graph_set_losses", allow)
+
+    def losses(self, factor_kind, first=0, n=None, allow=()):
+        """msfl_graph_get_losses: the records (GRAPH_LOSS_DTYPE) of factors first .. first + n of one kind; DEFAULT where none was set."""
+        if n is None:
+            n = self._count[int(factor_kind)] - int(first)
+        out = np.zeros(max(0, int(n)), GRAPH_LOSS_DTYPE)
+        s = self._check(self.lib.msfl_graph_get_losses(self.p, C.c_int(int(factor_kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(out)),
+                        "msfl_graph_get_losses", allow)
+        return out if s == OK else s
+
+    def weights(self, factor_kind, first=0, n=None, allow=()):
+        """msfl_graph_factor_weights: rho'(|r|^2) of factors first .. first + n of one kind at the current poses, each under its own loss."""
+        if n is None:
+            n = self._count[int(factor_kind)] - int(first)
+        out = np.zeros(max(0, int(n)), np.float64)
+        s = self._check(self.lib.msfl_graph_factor_weights(self.p, C.c_int(int(factor_kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(out)),
+                        "msfl_graph_factor_weights", allow)
         return out if s == OK else s
 
     def marginals(self, pairs, out=None, allow=(), **options):

@@ -9,6 +9,10 @@ static_assert(sizeof(msfl_graph_edge_info) == 352 && sizeof(msfl_graph_fix_info)
 static_assert(sizeof(GraphState) % 8 == 0, "the trace follows the state record");
 static_assert(sizeof(msfl_graph_marginals_summary) == 32 && sizeof(msfl_graph_marginals_options) == 24, "marginals record layout");
 static_assert(sizeof(GraphMargCol) == 32 && sizeof(GraphMargState) == 16, "marginals state records, read back as they are");
+static_assert(sizeof(msfl_graph_loss) == 16, "loss record layout");
+static_assert(MSFL_GRAPH_LOSS_DEFAULT == kGraphLossDefault && MSFL_GRAPH_LOSS_NONE == kGraphLossNone && MSFL_GRAPH_LOSS_HUBER == kGraphLossHuber &&
+              MSFL_GRAPH_LOSS_SOFT_L_ONE == kGraphLossSoftLOne && MSFL_GRAPH_LOSS_CAUCHY == kGraphLossCauchy &&
+              MSFL_GRAPH_LOSS_GEMAN_MCCLURE == kGraphLossGemanMcClure, "the loss kinds of msfl_graph_host.h are the header's");
 
 struct msfl_graph_s {
   int device = 0;
@@ -31,7 +35,13 @@ struct msfl_graph_s {
   DevBuf x, cand;                // double[max_nodes x 7]
   DevBuf ints, data, work;       // structure, factor data, everything the solve works in
   DevBuf linfo;                  // double[information factors x 36]: their L; allocated by the first call that adds one
-  DevBuf chi;                    // msfl_graph_factor_chi2's result before it goes to the host
+  DevBuf chi;                    // msfl_graph_factor_chi2's / msfl_graph_factor_weights' result before it goes to the host
+  // msfl_graph_set_losses; nothing of it exists before the first call
+  bool has_losses = false;       // from the first call to the next clear: every factor has a record, DEFAULT unless set
+  bool loss_dirty = false;       // records changed since the device copy was built
+  std::vector<msfl_graph_loss> losses[4];   // per factor kind, in the order added
+  DevBuf loss;                   // double a[factors] | int kind[factors], in the factor numbering
+  GraphLossDev loss_dev{};
   DevBuf state;                  // GraphState, double[max_iter] candidate costs, one double (msfl_graph_cost), int[max_iter] accept list
   PinRing pin;
   PinBuf readback;
@@ -93,8 +103,9 @@ struct GraphCarve {
 };
 
 // Builds the device copy of the structure and carves the work area; nothing to do while the structure is unchanged.
+msfl_status graph_prepare_losses(msfl_graph* g);
 msfl_status graph_prepare(msfl_graph* g) {
-  if (!g->dirty) return MSFL_OK;
+  if (!g->dirty) return graph_prepare_losses(g);
   hipStream_t st = g->stream;
   const int ne = (int)g->edges.size(), nx = (int)g->fixes.size(), nei = (int)g->edges_info.size(), nxi = (int)g->fixes_info.size();
   const int np = ne + nx, ni = nei + nxi, nf = np + ni;      // factor numbering: edges, fixes, information edges, information fixes
@@ -174,6 +185,25 @@ msfl_status graph_prepare(msfl_graph* g) {
   d.tr_cost = reinterpret_cast<double*>(sp + sizeof(GraphState));
   d.tr_accepted = reinterpret_cast<int*>(sp + sizeof(GraphState) + ((size_t)std::max(1, g->cfg.max_num_iterations) + 1) * sizeof(double));
   g->dirty = false;
+  g->loss_dirty = g->has_losses;
+  return graph_prepare_losses(g);
+}
+
+// the device copy of the loss records, in the factor numbering; nothing to do for a graph without records or while they are unchanged
+msfl_status graph_prepare_losses(msfl_graph* g) {
+  if (!g->loss_dirty) return MSFL_OK;
+  const size_t nf = (size_t)g->dev.n_factors, nfz = std::max<size_t>(1, nf);
+  std::vector<double> a(nfz, 0.0);
+  std::vector<int> kind(nfz, MSFL_GRAPH_LOSS_DEFAULT);
+  size_t k = 0;
+  for (const std::vector<msfl_graph_loss>& v : g->losses)
+    for (const msfl_graph_loss& l : v) { a[k] = l.a; kind[k] = l.kind; k++; }
+  HIPCHK(g, g->loss.reserve(nfz * (sizeof(double) + sizeof(int))));
+  HIPCHK(g, g->pin.upload(g->loss.p, a.data(), nfz * sizeof(double), g->stream));
+  HIPCHK(g, g->pin.upload(g->loss.as<double>() + nfz, kind.data(), nfz * sizeof(int), g->stream));
+  g->loss_dev.a = g->loss.as<double>();
+  g->loss_dev.kind = reinterpret_cast<const int*>(g->loss.as<double>() + nfz);
+  g->loss_dirty = false;
   return MSFL_OK;
 }
 
@@ -191,15 +221,29 @@ void graph_launch(hipStream_t st, K kernel, int items, int block, A... args) {
 // run on: the marginals run on a copy whose `st` is a state record of their own.
 
 // the factor kernels: the plain kinds and, only when the graph holds one, the information kinds
-void graph_enqueue_linearize(hipStream_t st, const GraphDev& d, double huber) {
-  if (d.n_plain) graph_launch(st, graph_linearize_kernel, d.n_plain, kGraphBlock, d, huber);
-  if (d.n_factors > d.n_plain) graph_launch(st, graph_linearize_info_kernel, d.n_factors - d.n_plain, kGraphBlock, d, huber);
+// `L` is null for a graph without loss records (the kernels there always were), else the per-factor arrays (their siblings)
+void graph_enqueue_linearize(hipStream_t st, const GraphDev& d, double huber, const GraphLossDev* L) {
+  const int ni = d.n_factors - d.n_plain;
+  if (!L) {
+    if (d.n_plain) graph_launch(st, graph_linearize_kernel<>, d.n_plain, kGraphBlock, d, huber);
+    if (ni) graph_launch(st, graph_linearize_info_kernel<>, ni, kGraphBlock, d, huber);
+    return;
+  }
+  if (d.n_plain) graph_launch(st, graph_linearize_kernel<GraphLossDev>, d.n_plain, kGraphBlock, d, huber, *L);
+  if (ni) graph_launch(st, graph_linearize_info_kernel<GraphLossDev>, ni, kGraphBlock, d, huber, *L);
 }
 template <bool kModel>
-void graph_enqueue_cost(hipStream_t st, const GraphDev& d, const double* x, double huber) {
-  if (d.n_plain) graph_launch(st, graph_cost_kernel<kModel>, d.n_plain, kGraphBlock, d, x, huber);
-  if (d.n_factors > d.n_plain) graph_launch(st, graph_cost_info_kernel<kModel>, d.n_factors - d.n_plain, kGraphBlock, d, x, huber);
+void graph_enqueue_cost(hipStream_t st, const GraphDev& d, const double* x, double huber, const GraphLossDev* L) {
+  const int ni = d.n_factors - d.n_plain;
+  if (!L) {
+    if (d.n_plain) graph_launch(st, graph_cost_kernel<kModel>, d.n_plain, kGraphBlock, d, x, huber);
+    if (ni) graph_launch(st, graph_cost_info_kernel<kModel>, ni, kGraphBlock, d, x, huber);
+    return;
+  }
+  if (d.n_plain) graph_launch(st, graph_cost_kernel<kModel, GraphLossDev>, d.n_plain, kGraphBlock, d, x, huber, *L);
+  if (ni) graph_launch(st, graph_cost_info_kernel<kModel, GraphLossDev>, ni, kGraphBlock, d, x, huber, *L);
 }
+const GraphLossDev* graph_losses(const msfl_graph* g) { return g->has_losses ? &g->loss_dev : nullptr; }
 
 // workgroups of the invert launch of level l: with kPivot each leaves one partial minimum in M.piv
 int graph_invert_groups(const GraphLevels& v, int l) { return std::max(1, div_up(v.n[l] / 2, kGraphBlock)); }
@@ -236,7 +280,7 @@ msfl_status graph_read_state(msfl_graph* g, GraphState* out) {
 // `ok` the per-record test and `bad` the text when it fails; an information kind also gets room for its L matrices on the device.
 template <class R, class Ok>
 msfl_status graph_append(msfl_graph* g, const std::string& who, std::vector<R>& to, const R* recs, int n, size_t held, int cap, const char* fits,
-                         Ok ok, const char* bad, bool information) {
+                         Ok ok, const char* bad, bool information, int kind) {
   msfl_status s = enter(g); if (s) return s;
   if (n < 0 || (n > 0 && !recs)) return fail(g, MSFL_BAD_ARG, who + ": null array or negative count");
   if ((long long)held + n > cap) return fail(g, MSFL_CAPACITY, who + ": " + fits + "; nothing added");
@@ -249,8 +293,18 @@ msfl_status graph_append(msfl_graph* g, const std::string& who, std::vector<R>& 
   if (n == 0) return MSFL_OK;
   if (information) HIPCHK(g, g->linfo.reserve(36 * sizeof(double) * (g->edges_info.size() + g->fixes_info.size() + (size_t)n)));
   to.insert(to.end(), recs, recs + n);
+  if (g->has_losses) g->losses[kind].resize(to.size(), msfl_graph_loss{MSFL_GRAPH_LOSS_DEFAULT, 0, 0.0});
   g->dirty = true;
   return MSFL_OK;
+}
+
+// kind, first, n name factors the graph holds; *k0: the first one's place in the factor numbering
+bool graph_factor_range(const msfl_graph* g, int kind, int first, int n, int* k0) {
+  const int count[4] = {(int)g->edges.size(), (int)g->fixes.size(), (int)g->edges_info.size(), (int)g->fixes_info.size()};
+  if (kind < 0 || kind > 3 || first < 0 || n < 0 || (long long)first + n > count[kind]) return false;
+  *k0 = first;
+  for (int c = 0; c < kind; c++) *k0 += count[c];
+  return true;
 }
 
 bool graph_fix_point_ok(double t, const double* p) {
@@ -322,6 +376,8 @@ msfl_status msfl_graph_clear(msfl_graph* g) {
   msfl_status s = enter(g); if (s) return s;
   HIPCHK(g, hipStreamSynchronize(g->stream));
   g->n_nodes = 0; g->fixed.clear(); g->edges.clear(); g->fixes.clear(); g->edges_info.clear(); g->fixes_info.clear(); g->tr_accepted.clear(); g->tr_cost.clear();
+  for (std::vector<msfl_graph_loss>& v : g->losses) v.clear();
+  g->has_losses = false; g->loss_dirty = false;
   g->dirty = true;
   return MSFL_OK;
 }
@@ -366,7 +422,7 @@ msfl_status msfl_graph_add_edges(msfl_graph* g, const msfl_graph_edge* edges, in
   return graph_append(g, "msfl_graph_add_edges", g->edges, edges, n, g->edges.size() + g->edges_info.size(), g->cfg.max_edges,
                       "the batch does not fit max_edges",
                       [](const msfl_graph_edge& e) { return graph_pose_ok(e.z) && std::isfinite(e.sr) && std::isfinite(e.st) && e.sr > 0.0 && e.st > 0.0; },
-                      "a non-finite value, a zero quaternion or sr, st <= 0", false);
+                      "a non-finite value, a zero quaternion or sr, st <= 0", false, MSFL_GRAPH_FACTOR_EDGE);
 }
 
 msfl_status msfl_graph_add_fixes(msfl_graph* g, const msfl_graph_fix* fixes, int n) {
@@ -374,7 +430,7 @@ msfl_status msfl_graph_add_fixes(msfl_graph* g, const msfl_graph_fix* fixes, int
   return graph_append(g, "msfl_graph_add_fixes", g->fixes, fixes, n, g->fixes.size() + g->fixes_info.size(), g->cfg.max_fixes,
                       "the batch does not fit max_fixes",
                       [](const msfl_graph_fix& f) { return graph_fix_point_ok(f.t, f.p) && std::isfinite(f.st) && f.st > 0.0; },
-                      "a non-finite value, st <= 0 or t outside [0, 1]", false);
+                      "a non-finite value, st <= 0 or t outside [0, 1]", false, MSFL_GRAPH_FACTOR_FIX);
 }
 
 msfl_status msfl_graph_add_edges_info(msfl_graph* g, const msfl_graph_edge_info* edges, int n) {
@@ -382,7 +438,7 @@ msfl_status msfl_graph_add_edges_info(msfl_graph* g, const msfl_graph_edge_info*
   return graph_append(g, "msfl_graph_add_edges_info", g->edges_info, edges, n, g->edges.size() + g->edges_info.size(), g->cfg.max_edges,
                       "plain and information edges together do not fit max_edges",
                       [](const msfl_graph_edge_info& e) { return graph_pose_ok(e.z) && graph_sqrt_information_ok(e.sqrt_information, 36); },
-                      "a non-finite value, a zero quaternion or an all-zero sqrt_information", true);
+                      "a non-finite value, a zero quaternion or an all-zero sqrt_information", true, MSFL_GRAPH_FACTOR_EDGE_INFO);
 }
 
 msfl_status msfl_graph_add_fixes_info(msfl_graph* g, const msfl_graph_fix_info* fixes, int n) {
@@ -390,7 +446,7 @@ msfl_status msfl_graph_add_fixes_info(msfl_graph* g, const msfl_graph_fix_info* 
   return graph_append(g, "msfl_graph_add_fixes_info", g->fixes_info, fixes, n, g->fixes.size() + g->fixes_info.size(), g->cfg.max_fixes,
                       "plain and information fixes together do not fit max_fixes",
                       [](const msfl_graph_fix_info& f) { return graph_fix_point_ok(f.t, f.p) && graph_sqrt_information_ok(f.sqrt_information, 9); },
-                      "a non-finite value, t outside [0, 1] or an all-zero sqrt_information", true);
+                      "a non-finite value, t outside [0, 1] or an all-zero sqrt_information", true, MSFL_GRAPH_FACTOR_FIX_INFO);
 }
 
 // pure host arithmetic (msfl_graph_host.h): no graph object, no GPU call
@@ -449,7 +505,7 @@ msfl_status msfl_graph_cost(msfl_graph* g, double* cost) {
   if (g->dev.n_factors == 0) return MSFL_OK;
   hipStream_t st = g->stream;
   double* d_out = g->dev.tr_cost + std::max(1, g->cfg.max_num_iterations);
-  graph_enqueue_cost<false>(st, g->dev, g->dev.x, g->cfg.huber_delta);
+  graph_enqueue_cost<false>(st, g->dev, g->dev.x, g->cfg.huber_delta, graph_losses(g));
   graph_launch(st, graph_cost_total_kernel, 1, kGraphVec, g->dev, d_out);
   HIPCHK(g, hipGetLastError());
   HIPCHK(g, hipMemcpyAsync(g->readback.p, d_out, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -460,19 +516,66 @@ msfl_status msfl_graph_cost(msfl_graph* g, double* cost) {
 
 msfl_status msfl_graph_factor_chi2(msfl_graph* g, int kind, int first, int n, double* out) {
   msfl_status s = enter(g); if (s) return s;
-  const int count[4] = {(int)g->edges.size(), (int)g->fixes.size(), (int)g->edges_info.size(), (int)g->fixes_info.size()};
-  if (kind < 0 || kind > 3 || first < 0 || n < 0 || (long long)first + n > count[kind] || (n > 0 && !out))
+  int k0 = 0;
+  if (!graph_factor_range(g, kind, first, n, &k0) || (n > 0 && !out))
     return fail(g, MSFL_BAD_ARG, "msfl_graph_factor_chi2: unknown kind, range outside the factors of that kind or null result");
   if (n == 0) return MSFL_OK;
   s = graph_prepare(g); if (s) return s;
-  int k0 = first;
-  for (int c = 0; c < kind; c++) k0 += count[c];
   hipStream_t st = g->stream;
   HIPCHK(g, g->chi.reserve((size_t)n * sizeof(double)));
   graph_launch(st, graph_chi2_kernel, n, kGraphBlock, g->dev, k0, n, g->chi.as<double>());
   HIPCHK(g, hipGetLastError());
   HIPCHK(g, hipMemcpyAsync(out, g->chi.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(g, hipStreamSynchronize(st));
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_factor_weights(msfl_graph* g, int kind, int first, int n, double* out) {
+  msfl_status s = enter(g); if (s) return s;
+  int k0 = 0;
+  if (!graph_factor_range(g, kind, first, n, &k0) || (n > 0 && !out))
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_factor_weights: unknown kind, range outside the factors of that kind or null result");
+  if (n == 0) return MSFL_OK;
+  s = graph_prepare(g); if (s) return s;
+  hipStream_t st = g->stream;
+  HIPCHK(g, g->chi.reserve((size_t)n * sizeof(double)));
+  if (g->has_losses) graph_launch(st, graph_weights_kernel<GraphLossDev>, n, kGraphBlock, g->dev, k0, n, g->chi.as<double>(), g->cfg.huber_delta, g->loss_dev);
+  else graph_launch(st, graph_weights_kernel<>, n, kGraphBlock, g->dev, k0, n, g->chi.as<double>(), g->cfg.huber_delta);
+  HIPCHK(g, hipGetLastError());
+  HIPCHK(g, hipMemcpyAsync(out, g->chi.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(g, hipStreamSynchronize(st));
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_set_losses(msfl_graph* g, int kind, int first, int n, const msfl_graph_loss* losses, int n_losses) {
+  msfl_status s = enter(g); if (s) return s;
+  int k0 = 0;
+  if (!graph_factor_range(g, kind, first, n, &k0) || (n > 0 && !losses) || (n_losses != n && n_losses != 1))
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_set_losses: unknown factor kind, range outside the factors of that kind, null array or n_losses neither n nor 1; nothing set");
+  for (int k = 0; k < (n > 0 ? n_losses : 0); k++)
+    if (!graph_loss_ok(losses[k].kind, losses[k].a))
+      return fail(g, MSFL_BAD_ARG, "msfl_graph_set_losses: an unknown loss kind, or a <= 0 or not finite on a kind that reads it; nothing set");
+  if (n == 0) return MSFL_OK;
+  const size_t held[4] = {g->edges.size(), g->fixes.size(), g->edges_info.size(), g->fixes_info.size()};
+  HIPCHK(g, g->loss.reserve(std::max<size_t>(1, held[0] + held[1] + held[2] + held[3]) * (sizeof(double) + sizeof(int))));
+  if (!g->has_losses) {
+    for (int c = 0; c < 4; c++) g->losses[c].assign(held[c], msfl_graph_loss{MSFL_GRAPH_LOSS_DEFAULT, 0, 0.0});
+    g->has_losses = true;
+  }
+  for (int k = 0; k < n; k++) {
+    const msfl_graph_loss& l = losses[n_losses == 1 ? 0 : k];
+    g->losses[kind][(size_t)first + k] = msfl_graph_loss{l.kind, 0, l.kind < MSFL_GRAPH_LOSS_HUBER ? 0.0 : l.a};
+  }
+  g->loss_dirty = true;
+  return MSFL_OK;
+}
+
+msfl_status msfl_graph_get_losses(msfl_graph* g, int kind, int first, int n, msfl_graph_loss* out) {
+  if (!g) return MSFL_BAD_ARG;
+  int k0 = 0;
+  if (!graph_factor_range(g, kind, first, n, &k0) || (n > 0 && !out))
+    return fail(g, MSFL_BAD_ARG, "msfl_graph_get_losses: unknown factor kind, range outside the factors of that kind or null result");
+  for (int k = 0; k < n; k++) out[k] = g->has_losses ? g->losses[kind][(size_t)first + k] : msfl_graph_loss{MSFL_GRAPH_LOSS_DEFAULT, 0, 0.0};
   return MSFL_OK;
 }
 
@@ -498,7 +601,7 @@ msfl_status msfl_graph_optimize(msfl_graph* g, msfl_graph_summary* summary) {
   GraphState now{};
   for (int it = 0;; it++) {
     graph_launch(st, graph_commit_kernel, d.n_nodes * 7, kGraphVec, d);
-    graph_enqueue_linearize(st, d, o.huber);
+    graph_enqueue_linearize(st, d, o.huber, graph_losses(g));
     graph_launch(st, graph_assemble_kernel, F, kGraphBlock, d);
     if (it == 0) graph_launch(st, graph_scale_kernel, F * 6, kGraphVec, d, o.jacobi);
     graph_launch(st, graph_tr_begin_kernel, 1, kGraphVec, d, o);
@@ -515,7 +618,7 @@ msfl_status msfl_graph_optimize(msfl_graph* g, msfl_graph_summary* summary) {
       }
       graph_launch(st, graph_cg_end_kernel, 1, kGraphVec, d, n_part, o.cg_tol, direct);
       graph_launch(st, graph_plus_kernel, F, kGraphVec, d);
-      graph_enqueue_cost<true>(st, d, d.cand, o.huber);
+      graph_enqueue_cost<true>(st, d, d.cand, o.huber, graph_losses(g));
       graph_launch(st, graph_tr_kernel, 1, kGraphVec, d, o);
     }
     HIPCHK(g, hipGetLastError());
@@ -642,7 +745,7 @@ msfl_status msfl_graph_marginals_with(msfl_graph* g, const int* pairs, int n_pai
   };
   carve_for(0);
   // 1. linearise and assemble at the current poses, 2. the undamped level 0, 3. the factor half with the pivot test
-  graph_enqueue_linearize(st, d, g->cfg.huber_delta);
+  graph_enqueue_linearize(st, d, g->cfg.huber_delta, graph_losses(g));
   graph_launch(st, graph_assemble_kernel, F, kGraphBlock, d);
   graph_launch(st, graph_marg_setup_kernel, F, kGraphVec, d);
   graph_enqueue_factor<true>(st, d, v, M, opt.min_pivot_ratio);

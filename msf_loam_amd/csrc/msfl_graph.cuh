@@ -315,6 +315,52 @@ __device__ __forceinline__ double graph_huber(const double* r, double a, double*
   *half_rho = 0.5 * sq;
   return 1.0;
 }
+// rho' of the same loss alone (msfl_graph_factor_weights)
+__device__ __forceinline__ double graph_huber_weight(double sq, double a) {
+  return a > 0.0 && sq > a * a ? fmax(2.2250738585072014e-308, a / sqrt(sq)) : 1.0;
+}
+
+// A loss per factor (msfl_graph_set_losses): rho and rho' (clamped) of kind / a at s = |r|^2, b = a^2, in Ceres' forms; all six kinds
+// have rho'' <= 0, so the corrector is graph_huber's.  DEFAULT is HuberLoss(huber), no loss when huber <= 0.  One lane per factor:
+// the lanes of a wavefront branch on their kinds.  msfl_graph_host.h has the host's twin, operation for operation.
+__device__ __forceinline__ double graph_loss_rho(double s, int kind, double a, double huber, double* rho1) {
+  if (kind == kGraphLossDefault) { kind = huber > 0.0 ? kGraphLossHuber : kGraphLossNone; a = huber; }
+  const double b = a * a;
+  double rho = s, w = 1.0;
+  if (kind == kGraphLossHuber) {
+    if (s > b) { const double n = sqrt(s); rho = 2.0 * a * n - b; w = a / n; }
+  } else if (kind == kGraphLossSoftLOne) {
+    const double t = sqrt(1.0 + s / b);
+    rho = 2.0 * b * (t - 1.0); w = 1.0 / t;
+  } else if (kind == kGraphLossCauchy) {
+    const double q = 1.0 + s / b;
+    rho = b * log(q); w = 1.0 / q;
+  } else if (kind == kGraphLossGemanMcClure) {
+    const double q = b / (b + s);
+    rho = q * s; w = q * q;
+  }
+  *rho1 = fmax(2.2250738585072014e-308, w);
+  return rho;
+}
+// The loss of factor k as the factor kernels see it, graph_huber's contract (*half_rho = rho / 2, returns sqrt(rho')) and rho' alone at
+// |r|^2 = sq.  The kernels end in a parameter pack that is empty for the graph that never set a loss (every factor under
+// HuberLoss(huber): the kernels, arguments and instructions there always were) or holds the two per-factor arrays, in the factor
+// numbering (their siblings, launched once msfl_graph_set_losses has allocated the arrays).
+struct GraphLossDev { const int* kind; const double* a; };
+__device__ __forceinline__ double graph_factor_scale(int, const double* r, double huber, double* half_rho) { return graph_huber(r, huber, half_rho); }
+__device__ __forceinline__ double graph_factor_scale(int k, const double* r, double huber, double* half_rho, const GraphLossDev& L) {
+  double sq = 0.0, w;
+#pragma unroll
+  for (int c = 0; c < 6; c++) sq += r[c] * r[c];
+  *half_rho = 0.5 * graph_loss_rho(sq, L.kind[k], L.a[k], huber, &w);
+  return sqrt(w);
+}
+__device__ __forceinline__ double graph_factor_weight(int, double sq, double huber) { return graph_huber_weight(sq, huber); }
+__device__ __forceinline__ double graph_factor_weight(int k, double sq, double huber, const GraphLossDev& L) {
+  double w;
+  (void)graph_loss_rho(sq, L.kind[k], L.a[k], huber, &w);
+  return w;
+}
 
 __global__ __launch_bounds__(kGraphVec) void graph_commit_kernel(GraphDev G) {
   if (!G.st->commit) return;
@@ -322,13 +368,14 @@ __global__ __launch_bounds__(kGraphVec) void graph_commit_kernel(GraphDev G) {
   if (i < G.n_nodes * 7) G.x[i] = G.cand[i];
 }
 
-__global__ __launch_bounds__(kGraphBlock) void graph_linearize_kernel(GraphDev G, double huber) {
+template <class... Loss>
+__global__ __launch_bounds__(kGraphBlock) void graph_linearize_kernel(GraphDev G, double huber, Loss... loss) {
   if (G.st->done) return;
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (k >= G.n_plain) return;
   double r[6], Ji[36], Jj[36], hr;
   graph_factor<true>(G, G.x, k, r, Ji, Jj);
-  const double s = graph_huber(r, huber, &hr);
+  const double s = graph_factor_scale(k, r, huber, &hr, loss...);
   double* o = G.J + (size_t)k * kGraphJ;
 #pragma unroll
   for (int i = 0; i < 36; i++) { o[i] = s * Ji[i]; o[36 + i] = s * Jj[i]; }
@@ -357,14 +404,14 @@ __device__ __forceinline__ double graph_model_share(const GraphDev& G, int k) {
 }
 
 // cost of every plain block at `x` into fcost; with kModel also the block's share of the model cost change
-template <bool kModel>
-__global__ __launch_bounds__(kGraphBlock) void graph_cost_kernel(GraphDev G, const double* __restrict__ x, double huber) {
+template <bool kModel, class... Loss>
+__global__ __launch_bounds__(kGraphBlock) void graph_cost_kernel(GraphDev G, const double* __restrict__ x, double huber, Loss... loss) {
   if (kModel && G.st->done) return;
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (k >= G.n_plain) return;
   double r[6], hr;
   graph_factor<false>(G, x, k, r, nullptr, nullptr);
-  (void)graph_huber(r, huber, &hr);
+  (void)graph_factor_scale(k, r, huber, &hr, loss...);
   G.fcost[k] = hr;
   if (!kModel) return;
   G.fmodel[k] = graph_model_share(G, k);
@@ -445,7 +492,8 @@ __device__ __forceinline__ void graph_info_residual(const GraphDev& G, const dou
 // graph_linearize_kernel for the information factors.  J = L (de/d.) row by row from L's column halves against the 3 x 3 blocks:
 //   Ji row = [-(l Rt), l B - l' M],  Jj row = [l Rt, l' M],  l = L[row][0:3], l' = L[row][3:6];
 // a row is stored as it completes (L is read a second time for that, after the corrector's scale is known).
-__global__ __launch_bounds__(kGraphBlock) void graph_linearize_info_kernel(GraphDev G, double huber) {
+template <class... Loss>
+__global__ __launch_bounds__(kGraphBlock) void graph_linearize_info_kernel(GraphDev G, double huber, Loss... loss) {
   if (G.st->done) return;
   const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (m >= G.n_factors - G.n_plain) return;
@@ -459,7 +507,7 @@ __global__ __launch_bounds__(kGraphBlock) void graph_linearize_info_kernel(Graph
     graph_info_fix_error(G, G.x, k, e);
 #pragma unroll
     for (int i = 0; i < 3; i++) { r[i] = L[i * 3] * e[0] + L[i * 3 + 1] * e[1] + L[i * 3 + 2] * e[2]; r[3 + i] = 0.0; }
-    const double s = graph_huber(r, huber, &hr);
+    const double s = graph_factor_scale(k, r, huber, &hr, loss...);
 #pragma unroll
     for (int i = 0; i < 6; i++) {
 #pragma unroll
@@ -481,7 +529,7 @@ __global__ __launch_bounds__(kGraphBlock) void graph_linearize_info_kernel(Graph
     for (int c = 0; c < 6; c++) a += L[i * 6 + c] * e[c];
     r[i] = a;
   }
-  const double s = graph_huber(r, huber, &hr);
+  const double s = graph_factor_scale(k, r, huber, &hr, loss...);
 #pragma unroll
   for (int i = 0; i < 6; i++) {
     const double l0 = s * L[i * 6], l1 = s * L[i * 6 + 1], l2 = s * L[i * 6 + 2], l3 = s * L[i * 6 + 3], l4 = s * L[i * 6 + 4], l5 = s * L[i * 6 + 5];
@@ -499,15 +547,15 @@ __global__ __launch_bounds__(kGraphBlock) void graph_linearize_info_kernel(Graph
 }
 
 // graph_cost_kernel for the information factors
-template <bool kModel>
-__global__ __launch_bounds__(kGraphBlock) void graph_cost_info_kernel(GraphDev G, const double* __restrict__ x, double huber) {
+template <bool kModel, class... Loss>
+__global__ __launch_bounds__(kGraphBlock) void graph_cost_info_kernel(GraphDev G, const double* __restrict__ x, double huber, Loss... loss) {
   if (kModel && G.st->done) return;
   const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (m >= G.n_factors - G.n_plain) return;
   const int k = G.n_plain + m;
   double r[6], hr;
   graph_info_residual(G, x, m, r);
-  (void)graph_huber(r, huber, &hr);
+  (void)graph_factor_scale(k, r, huber, &hr, loss...);
   G.fcost[k] = hr;
   if (!kModel) return;
   G.fmodel[k] = graph_model_share(G, k);
@@ -524,6 +572,20 @@ __global__ __launch_bounds__(kGraphBlock) void graph_chi2_kernel(GraphDev G, int
 #pragma unroll
   for (int c = 0; c < 6; c++) sq += r[c] * r[c];
   out[i] = sq;
+}
+
+// msfl_graph_factor_weights: rho'(|r|^2) of the same factors under each one's loss; writes nothing else
+template <class... Loss>
+__global__ __launch_bounds__(kGraphBlock) void graph_weights_kernel(GraphDev G, int first, int n, double* __restrict__ out, double huber, Loss... loss) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int k = first + i;
+  double r[6], sq = 0.0;
+  if (k < G.n_plain) graph_factor<false>(G, G.x, k, r, nullptr, nullptr);
+  else graph_info_residual(G, G.x, k - G.n_plain, r);
+#pragma unroll
+  for (int c = 0; c < 6; c++) sq += r[c] * r[c];
+  out[i] = graph_factor_weight(k, sq, huber, loss...);
 }
 
 // one free node per lane: gathers its factors in adjacency order into the unscaled diagonal block, the block towards f - 1 and the gradient

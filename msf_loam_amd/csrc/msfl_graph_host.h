@@ -1,8 +1,8 @@
 // Host-side bookkeeping of the pose graph (msfl_api_graph.inc): free-node numbering, adjacency lists, long / chain classification and
 // the level sizes of the cyclic reduction, and the arithmetic that turns a registration's eigen-decomposition or a 3 x 3 covariance
-// into an information factor, or a joint marginal into the covariance of a relative pose.  Plain C++ over plain arrays, no HIP:
-// tests/cpp/graph_structure_check.cpp, tests/cpp/graph_info_check.cpp and tests/cpp/graph_marginals_check.cpp run it under the host
-// sanitizers.
+// into an information factor, or a joint marginal into the covariance of a relative pose, and the validation and rho / rho' of a
+// factor's loss record.  Plain C++ over plain arrays, no HIP: tests/cpp/graph_structure_check.cpp, tests/cpp/graph_info_check.cpp,
+// tests/cpp/graph_marginals_check.cpp and tests/cpp/graph_loss_check.cpp run it under the host sanitizers.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -188,6 +188,36 @@ inline bool graph_fix_from_covariance(const double* cov, double* L3) {
   if (!graph_all_finite(out, 9)) return false;
   std::copy(out, out + 9, L3);
   return true;
+}
+
+// ---- a loss per factor: the records of msfl_graph_set_losses (MSFL_GRAPH_LOSS_*, the same numbers) ------------------------------
+enum { kGraphLossDefault = 0, kGraphLossNone, kGraphLossHuber, kGraphLossSoftLOne, kGraphLossCauchy, kGraphLossGemanMcClure, kGraphLossKinds };
+constexpr double kGraphDblMin = 2.2250738585072014e-308;
+// a record the graph accepts: a known kind, and on a kind that reads `a` a finite a > 0
+inline bool graph_loss_ok(int kind, double a) {
+  if (kind < 0 || kind >= kGraphLossKinds) return false;
+  return kind < kGraphLossHuber || (graph_all_finite(&a, 1) && a > 0.0);
+}
+// rho(s) and rho'(s) (clamped from below at DBL_MIN) at s = |r|^2, b = a^2.  DEFAULT is HuberLoss(huber), no loss when huber <= 0.
+// The device's graph_loss_rho (msfl_graph.cuh) is this function operation for operation.
+inline double graph_host_loss_rho(double s, int kind, double a, double huber, double* rho1) {
+  if (kind == kGraphLossDefault) { kind = huber > 0.0 ? kGraphLossHuber : kGraphLossNone; a = huber; }
+  const double b = a * a;
+  double rho = s, w = 1.0;
+  if (kind == kGraphLossHuber) {
+    if (s > b) { const double n = std::sqrt(s); rho = 2.0 * a * n - b; w = a / n; }
+  } else if (kind == kGraphLossSoftLOne) {
+    const double t = std::sqrt(1.0 + s / b);
+    rho = 2.0 * b * (t - 1.0); w = 1.0 / t;
+  } else if (kind == kGraphLossCauchy) {
+    const double q = 1.0 + s / b;
+    rho = b * std::log(q); w = 1.0 / q;
+  } else if (kind == kGraphLossGemanMcClure) {
+    const double q = b / (b + s);
+    rho = q * s; w = q * q;
+  }
+  *rho1 = std::max(kGraphDblMin, w);
+  return rho;
 }
 
 // ---- marginals: the arithmetic of msfl_graph_relative_covariance ---------------------------------------------------------------

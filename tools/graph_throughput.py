@@ -10,7 +10,9 @@ block-tridiagonal solve alone is the N-with-0-long-edges row: there every LM ite
 right-hand-side passes.  Yardstick in the same process: scipy's sparse LU (SuperLU, one thread) of the same damped normal equations at
 the start poses, factorisation + solve, median of 3.  --info: the same graph with its long edges (closures), or all its edges (all), handed
 over as information edges with the isotropic L of the same cost (tests/graph_info_numpy.isotropic_L); with MSFL_LIB set to another
-build of the library the plain rows (--info none) compare the two builds.  No acceptance threshold hangs on these numbers.
+build of the library the plain rows (--info none) compare the two builds.  --loss KIND:A (geman_mcclure:1, cauchy:0.5, ...): the same
+graph with every closure under that loss (msfl_graph_set_losses; rows without a long edge are left out), which runs the per-factor-loss
+siblings of the factor kernels; the row says so in `loss`.  No acceptance threshold hangs on these numbers.
 
     python tools/graph_throughput.py --marginals [--sizes 1000 10000] [--long 0 10] [--nodes 1 16] [--repeats 5]
 
@@ -123,6 +125,7 @@ def main():
     ap.add_argument("--long", type=int, nargs="+", default=[0, 10, 100])
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--info", nargs="+", default=["none"], choices=["none", "closures", "all"])
+    ap.add_argument("--loss", default=None, metavar="KIND:A", help="every closure under this loss, e.g. geman_mcclure:1")
     ap.add_argument("--label", default="this", help="names the build in every row (A/B runs with MSFL_LIB)")
     ap.add_argument("--no-scipy", action="store_true", help="skip the host yardstick")
     ap.add_argument("--out", default=DEFAULT_OUT)
@@ -136,11 +139,15 @@ def main():
             args.long = [0, 10]
         return marginals(args)
     rows = []
+    loss = None
+    if args.loss:
+        kind, _, a = args.loss.partition(":")
+        loss = (capi.GRAPH_LOSS_NAMES.index(kind), float(a or 0.0))
     for n in args.sizes:
         for k in args.long:
             prob = make(n, k)
             for mode in args.info:
-                if mode == "closures" and k == 0:
+                if (mode == "closures" or loss) and k == 0:
                     continue
                 start = torch.from_numpy(np.ascontiguousarray(prob["poses"])).cuda()
                 g = capi.PoseGraph(0, max_nodes=n, max_edges=n + k, max_fixes=n // 50 + 2)
@@ -155,6 +162,11 @@ def main():
                 if as_info.any():
                     g.add_edges_info(g.edges_info(e["i"][as_info], e["j"][as_info], e["z"][as_info], gi.isotropic_L(e["sr"][as_info], e["st"][as_info], int(as_info.sum()))))
                 g.add_fixes(g.fixes(prob["fi"], prob["fj"], prob["ft"], prob["fp"], prob["fst"]))
+                if loss:                                         # the closures: the last k edges of their kind
+                    if mode == "none":
+                        g.set_losses(capi.GRAPH_FACTOR_EDGE, loss, first=n - 1, n=k)
+                    else:
+                        g.set_losses(capi.GRAPH_FACTOR_EDGE_INFO, loss, first=int(as_info.sum()) - k, n=k)
                 s = g.optimize()
                 ts = []
                 for _ in range(args.repeats):
@@ -164,7 +176,7 @@ def main():
                     s = g.optimize()
                     ts.append(time.perf_counter() - t0)
                 wall = float(np.median(ts))
-                row = dict(n=n, long_edges=k, build=args.label, information=mode, information_edges=int(as_info.sum()), n_long_counted=s.n_long_edges,
+                row = dict(n=n, long_edges=k, build=args.label, information=mode, information_edges=int(as_info.sum()), loss=args.loss, n_long_counted=s.n_long_edges,
                            termination=capi.GRAPH_TERMINATION[s.termination], iterations=s.iterations,
                            cg_iterations=s.cg_iterations, cg_unconverged=s.cg_unconverged, initial_cost=s.initial_cost, final_cost=s.final_cost,
                            wall_ms=1e3 * wall, wall_ms_min=1e3 * min(ts), wall_ms_max=1e3 * max(ts),
