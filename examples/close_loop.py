@@ -3,7 +3,7 @@
     python examples/close_loop.py [--scans 151] [--gap 50] [--every 1] [--max-distance 0.1] [--min-fitness 0.99] [--weights scalar|information]
                                   [--gate distance|mahalanobis] [--gate-bound 16.81]
                                   [--closure-map session|submap] [--submap-half-width 5] [--rebuild-map PATH]
-                                  [--closure-loss KIND:A]
+                                  [--closure-loss KIND:A] [--closure-yaws N]
 
 The figure of eight of examples/loop_candidates.py.  Every scan goes through the device-resident SLAM step (keep_clouds) and into a
 capi.Places.  The odometry the graph starts from is made to drift: the session's consecutive relative poses with a yaw bias and
@@ -23,7 +23,10 @@ weights it would enter the graph with); the distance is printed for every candid
 a submap instead of the session's (drifted) map: every scan becomes a keyframe of a capi.Keyframes, and ALL candidates (k, j) are
 verified by one compose (the keyframes j-w .. j+w, w = --submap-half-width, laid down in j's frame at relative_pose(pose_map[j],
 pose_map[i])) and one match_pairs_batch from the guess Rz(yaw) at the origin, whose result is the measurement itself; the acceptance
-rules are the same, evaluated against the submap.  --rebuild-map PATH lays the keyframes down again at the optimised poses
+rules are the same, evaluated against the submap: ONE score_pairs call grades every result against its own submap, on the pair
+index the match_pairs_batch left resident.  --closure-yaws N (with --closure-map submap; 0 = off) does not trust the descriptor's yaw
+to its sector: set_pair_maps indexes the submaps once, score_pairs grades N yaws spread over the sector around the descriptor's per
+candidate, the best one becomes the guess and match_pairs_resident registers from it on the same index.  --rebuild-map PATH lays the keyframes down again at the optimised poses
 (Keyframes.insert into two fresh map stores) and saves them as PATH_corner.npz / PATH_surf.npz (mapio.save_grid).  --closure-loss KIND:A (geman_mcclure:1, cauchy:1, soft_l_one:2, huber:0.5, none) gives every closure edge a loss of its
 own (PoseGraph.set_losses) while the odometry chain stays at the graph's Huber loss, in both weight modes: a redescending loss switches
 a closure that contradicts the rest off inside the solve, and after the optimisation every closure's weight rho'(|r|^2)
@@ -119,9 +122,13 @@ def main():
                     help="verify a candidate against the session's whole map, or against the submap of the scans around the matched one")
     ap.add_argument("--submap-half-width", type=int, default=5, help="submap: the keyframes j-w .. j+w around the matched scan j")
     ap.add_argument("--rebuild-map", metavar="PATH", default=None, help="rebuild both map stores at the optimised poses: PATH_corner.npz, PATH_surf.npz")
+    ap.add_argument("--closure-yaws", type=int, default=0,
+                    help="submap: score this many yaws round the descriptor's per candidate against its submap and register from the best (0: off)")
     ap.add_argument("--closure-loss", metavar="KIND:A", default=None,
                     help="the loss of every closure edge, e.g. geman_mcclure:1 (kinds: %s); default: the graph's Huber loss" % ", ".join(capi.GRAPH_LOSS_NAMES[1:]))
     args = ap.parse_args()
+    if args.closure_yaws < 0 or (args.closure_yaws > 0 and args.closure_map != "submap"):
+        ap.error("--closure-yaws: a count >= 0, with --closure-map submap")
     closure_loss = None
     if args.closure_loss:
         kind, _, a = args.closure_loss.partition(":")
@@ -176,9 +183,26 @@ def main():
         feats = [kf.get(k) for k, _, _, _ in candidates]
         co = np.cumsum([0] + [len(c) for c, _ in feats]).astype(np.int32)
         so = np.cumsum([0] + [len(s) for _, s in feats]).astype(np.int32)
-        sub_z, sub_status, _ = h.match_pairs_batch(sub_c, sub_co, sub_s, sub_so, np.concatenate([c for c, _ in feats]), co,
-                                                   np.concatenate([s for _, s in feats]), so, guesses)
+        all_c, all_s = np.concatenate([c for c, _ in feats]), np.concatenate([s for _, s in feats])
+        if args.closure_yaws > 0:
+            # the submaps indexed once; N yaws over the descriptor's sector scored per candidate, the registration starts from the best
+            h.set_pair_maps(sub_c, sub_co, sub_s, sub_so)
+            N, sector = args.closure_yaws, 2.0 * np.pi / places.n_sector
+            offsets = (np.arange(N) - (N - 1) / 2.0) * sector / N
+            lattice = np.array([turned(gs, d) for gs in guesses for d in offsets])
+            rec = h.score_pairs(all_c, co, all_s, so, lattice, np.arange(len(candidates) + 1) * N, args.max_dist)
+            for p, (c, s) in enumerate(feats):
+                fit = capi.fitness(rec[p * N:(p + 1) * N], len(c), len(s))
+                best = int(np.lexsort((np.abs(offsets), -fit))[0])           # the fittest; among equals the one nearest the descriptor's
+                print("scan %3d ~ scan %3d: yaw %+6.1f deg of %d scored (fitness %.3f; the descriptor's own %.3f)"
+                      % (candidates[p][0], int(candidates[p][1]["index"]), np.degrees(offsets[best]), N, fit[best], fit[int(np.argmin(np.abs(offsets)))]))
+                guesses[p] = lattice[p * N + best]
+            sub_z, sub_status, _ = h.match_pairs_resident(all_c, co, all_s, so, guesses)
+        else:
+            sub_z, sub_status, _ = h.match_pairs_batch(sub_c, sub_co, sub_s, sub_so, all_c, co, all_s, so, guesses)
         sub_unc = h.uncertainty(len(candidates)) if args.weights == "information" else None
+        # every result graded against its own submap at once, on the index the registration left resident
+        sub_score = h.score_pairs(all_c, co, all_s, so, sub_z, np.arange(len(candidates) + 1), args.max_dist)
     g = capi.PoseGraph(0, max_nodes=n, max_edges=n + len(candidates), max_fixes=1)
     g.add_nodes(drifted)
     g.set_fixed(0)
@@ -191,17 +215,18 @@ def main():
     for p, (k, m, sharp, flat) in enumerate(candidates):
         j, yaw = int(m["index"]), float(capi.place_yaw(m["shift"], places.n_sector))
         if submap:
-            # the pair's registration ran above; its fitness is scored against its own submap, in j's frame
+            # the pair's registration and its score against its own submap, in j's frame, ran above
             (corner, surf), base, guess = feats[p], identity, guesses[p]
             status, refined = int(sub_status[p]), sub_z[p]
             unc = sub_unc[p] if args.weights == "information" else None
-            h.set_map(sub_c[sub_co[p]:sub_co[p + 1]], sub_s[sub_so[p]:sub_so[p + 1]])
+            score = sub_score[p:p + 1]
         else:
             corner, surf = h.voxel_downsample(sharp, 0.2), h.voxel_downsample(flat, 0.4)
             base, guess = pose_map[j], turned(pose_map[j], yaw)
             status, refined, _ = h.match_scan2map(corner, surf, guess)
             unc = h.uncertainty(1)[0] if args.weights == "information" else None
-        fit = capi.fitness(h.score_poses(corner, surf, [refined], args.max_dist), len(corner), len(surf))[0]
+            score = h.score_poses(corner, surf, [refined], args.max_dist)
+        fit = capi.fitness(score, len(corner), len(surf))[0]
         z = capi.relative_pose(base, np.asarray(refined))
         if args.gate == "mahalanobis":
             info = closure_information(args.weights, j, k, base, np.asarray(refined, np.float64), unc) if status == 0 else None

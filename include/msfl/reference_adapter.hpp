@@ -35,6 +35,8 @@
 //   msfl::adapter::SetOutlierRejection(h, &rejection_record, MSFL_REJECT_THRESHOLD, 0.2)  once;  ClearOutlierRejection(h) to switch it off
 // and, for a health figure of a registration or the verification of a candidate pose against the map of the last MatchScan2Map:
 //   msfl::adapter::ScorePoses(h, scan_curr, poses, max_dist) -> std::vector<PoseScore> (Fitness(n_features), Rmse())
+// and, for P loop-closure candidates against their P submaps, the submaps indexed once:
+//   msfl::adapter::SetPairMaps(h, maps);  ScorePairs(h, scans, poses_per_scan, max_dist);  MatchPairsResident(h, scans, &poses)
 // and, where the reference's src/slam/loop_closure is an empty class: which earlier scan looks like this one, and at which yaw
 //   msfl::PlaceDatabase places;  places.Add(cloud) per scan;  places.Query(cloud, max_index, n_prefilter, k) -> std::vector<PlaceMatch> (Yaw())
 #pragma once
@@ -258,6 +260,62 @@ inline std::vector<PoseScore> ScorePoses(msfl_handle* h, const StampedT& scan, c
   Check(msfl_score_poses(h, c.data(), static_cast<int>(c.size()), s.data(), static_cast<int>(s.size()), v.data(), static_cast<int>(poses.size()),
                          max_dist, out.data(), nullptr, nullptr, MSFL_MEM_HOST), h, "msfl_score_poses");
   return out;
+}
+
+// ---- P (map, scan) pairs with the pairs' maps kept resident (msfl_set_pair_maps, msfl_score_pairs, msfl_match_pairs_resident; not in
+// the reference, which registers one scan against one map per call): loop-closure candidates against their submaps.  `maps` / `scans`
+// are containers (size(), operator[]) of stamped clouds, of which cloud_corner_less_sharp and cloud_surf_less_flat are read.
+template <class StampedVecT>
+inline void PackPairs(const StampedVecT& clouds, std::vector<msfl_point>* corner, std::vector<int>* corner_off, std::vector<msfl_point>* surf,
+                      std::vector<int>* surf_off) {
+  corner->clear(); surf->clear(); corner_off->assign(1, 0); surf_off->assign(1, 0);
+  for (std::size_t p = 0; p < clouds.size(); ++p) {
+    const std::vector<msfl_point> c = Pack(*clouds[p].cloud_corner_less_sharp);
+    const std::vector<msfl_point> s = Pack(*clouds[p].cloud_surf_less_flat);
+    corner->insert(corner->end(), c.begin(), c.end()); surf->insert(surf->end(), s.begin(), s.end());
+    corner_off->push_back(static_cast<int>(corner->size())); surf_off->push_back(static_cast<int>(surf->size()));
+  }
+}
+// The P maps indexed, one grid per pair; they stay resident until the next MatchScan2Map (msfl_set_map) or SetPairMaps.
+template <class StampedVecT>
+inline void SetPairMaps(msfl_handle* h, const StampedVecT& maps) {
+  std::vector<msfl_point> mc, ms; std::vector<int> mco, mso;
+  PackPairs(maps, &mc, &mco, &ms, &mso);
+  Check(msfl_set_pair_maps(h, static_cast<int>(maps.size()), mc.data(), mco.data(), ms.data(), mso.data(), MSFL_MEM_HOST), h, "msfl_set_pair_maps");
+}
+// scans[p] at each of poses[p] (a container of rigids, may be empty) against pair map p: out[p][k] grades poses[p][k].
+template <class StampedVecT, class RigidVecVecT>
+inline std::vector<std::vector<PoseScore>> ScorePairs(msfl_handle* h, const StampedVecT& scans, const RigidVecVecT& poses, double max_dist) {
+  if (poses.size() != scans.size()) throw std::invalid_argument("ScorePairs: one pose list per scan");
+  std::vector<msfl_point> c, s; std::vector<int> co, so, po(1, 0);
+  PackPairs(scans, &c, &co, &s, &so);
+  std::vector<double> v;
+  for (std::size_t p = 0; p < poses.size(); ++p) {
+    for (std::size_t k = 0; k < poses[p].size(); ++k) { v.resize(v.size() + 7); RigidToArray(poses[p][k], v.data() + v.size() - 7); }
+    po.push_back(static_cast<int>(v.size() / 7));
+  }
+  std::vector<PoseScore> flat(v.size() / 7);
+  Check(msfl_score_pairs(h, static_cast<int>(scans.size()), c.data(), co.data(), s.data(), so.data(), v.data(), po.data(), max_dist, flat.data(),
+                         nullptr, nullptr, MSFL_MEM_HOST), h, "msfl_score_pairs");
+  std::vector<std::vector<PoseScore>> out(scans.size());
+  for (std::size_t p = 0; p < scans.size(); ++p) out[p].assign(flat.begin() + po[p], flat.begin() + po[p + 1]);
+  return out;
+}
+// scans[p] registered against pair map p from (*poses)[p], which it replaces; per pair MSFL_OK or MSFL_MAP_TOO_SMALL (pose untouched).
+// The index is not consumed: call it again, or ScorePairs on the result.  `info`: null or one record per pair.
+template <class StampedVecT, class RigidVecT>
+inline std::vector<int> MatchPairsResident(msfl_handle* h, const StampedVecT& scans, RigidVecT* poses, msfl_match_info* info = nullptr) {
+  if (!poses || poses->size() != scans.size()) throw std::invalid_argument("MatchPairsResident: one pose per scan");
+  std::vector<msfl_point> c, s; std::vector<int> co, so;
+  PackPairs(scans, &c, &co, &s, &so);
+  std::vector<double> v(7 * scans.size());
+  for (std::size_t p = 0; p < scans.size(); ++p) RigidToArray((*poses)[p], v.data() + 7 * p);
+  std::vector<int> status(scans.size(), 0);
+  Check(msfl_match_pairs_resident(h, static_cast<int>(scans.size()), c.data(), co.data(), s.data(), so.data(), v.data(), status.data(), info,
+                                  MSFL_MEM_HOST), h, "msfl_match_pairs_resident");
+  using RigidT = typename std::decay<decltype((*poses)[0])>::type;
+  for (std::size_t p = 0; p < scans.size(); ++p) (*poses)[p] = RigidFromArray<RigidT>(v.data() + 7 * p);
+  return status;
 }
 
 // ---- HybridGrid::GetSurroundedCloud / InsertScan (hybrid_grid.cc:462-534; callers laser_mapping.cc:273-278,330-338) on a

@@ -297,6 +297,23 @@ class MappingScanMatcher : public ScanMatcher {
     return adapter::ScorePoses(h_, scan, poses, max_dist);
   }
 
+  // Not in the reference: P (map, scan) pairs with the pairs' maps kept resident (msfl_set_pair_maps, msfl_score_pairs,
+  // msfl_match_pairs_resident).  SetPairMaps indexes maps[p] once (the map of the last MatchScan2Map is replaced); ScorePairs grades
+  // scans[p] at each of poses[p] against map p only; MatchPairsResident registers scans[p] against map p from (*poses)[p] and returns
+  // the per-pair status (MSFL_OK, or MSFL_MAP_TOO_SMALL with the pose untouched).  Neither consumes the index.
+  // (EnableUncertainty's sink holds one record: with it on, register one pair per call.)
+  template <class StampedVecT>
+  void SetPairMaps(const StampedVecT& maps) { adapter::SetPairMaps(h_, maps); }
+  template <class StampedVecT, class RigidVecVecT>
+  std::vector<std::vector<PoseScore>> ScorePairs(const StampedVecT& scans, const RigidVecVecT& poses, double max_dist) {
+    return adapter::ScorePairs(h_, scans, poses, max_dist);
+  }
+  template <class StampedVecT, class RigidVecT>
+  std::vector<int> MatchPairsResident(const StampedVecT& scans, RigidVecT* poses) {
+    unc_ = msfl_match_uncertainty{};
+    return adapter::MatchPairsResident(h_, scans, poses);
+  }
+
  private:
   ImuPresolve imu_presolve_;
 };

@@ -337,7 +337,8 @@ msfl_status msfl_match_scan2map_batch(msfl_handle* h, int n_scans,
                                   than 5 points (the pose guess passes through); the call itself still returns MSFL_OK.
    Results equal P calls of msfl_set_map + msfl_match_scan2map bit for bit.  With MSFL_MEM_DEVICE the clouds, poses_io and
    status are device pointers and the call is asynchronous.  The handle's resident single map (msfl_set_map) is replaced:
-   call msfl_set_map again before the next msfl_match_scan2map*. */
+   call msfl_set_map again before the next msfl_match_scan2map*.  The call is msfl_set_pair_maps followed by
+   msfl_match_pairs_resident (below), and its pair index stays resident like theirs. */
 msfl_status msfl_match_pairs_batch(msfl_handle* h, int n_pairs,
                                    const msfl_point* map_corner, const int* map_corner_off,
                                    const msfl_point* map_surf, const int* map_surf_off,
@@ -391,6 +392,46 @@ msfl_status msfl_score_poses_batch(msfl_handle* h, int n_scans,
                                    const msfl_point* surf, const int* surf_off,
                                    const double* poses, const int* pose_off,
                                    double max_dist, msfl_pose_score* scores, msfl_mem mem);
+
+/* Resident pair maps: the two halves of msfl_match_pairs_batch on their own, and the fitness against the pairs' maps.
+   The index over P maps is most of what a pairs call costs (docs/kernels/pairs.md), and a second registration round, a
+   yaw lattice per candidate and the fitness of the result all want the same index.
+
+   msfl_set_pair_maps: the index half.  Arguments, limits (at most 65 535 pairs, cell-table and 2^28-point capacity) and
+   offset rules (HOST arrays, non-decreasing, need not start at 0) of msfl_match_pairs_batch.  The handle's resident single
+   map is replaced, as there.  With MSFL_MEM_DEVICE the call is asynchronous, and the caller's map arrays are not needed
+   once the stream has passed it: the index holds its own sorted copy.  n_pairs == 0 changes nothing.
+   The pair index stays resident until msfl_set_map, the next msfl_set_pair_maps (also one that fails) or the next
+   msfl_match_pairs_batch, which leaves ITS index resident in the same way.
+
+   msfl_score_pairs: msfl_score_poses_batch with scan p scored at the poses [pose_off[p], pose_off[p+1]) against pair map p
+   only.  Record, arithmetic, tie rule, fixed-point sums, max_dist rules, non-finite handling and memory kinds are the ones
+   described above.  What differs:
+     - d2_out / nn_out are allowed, and ragged: the row of a hypothesis of scan p has F(p) = n_corner(p) + n_surf(p)
+       values (corner features first), rows in hypothesis order, sum over p of n_poses(p) x F(p) values in all.
+     - nn_out holds the position in pair p's OWN map cloud of the feature's kind (what msfl_set_map on that cloud +
+       msfl_score_poses returns).
+     - MSFL_NO_MAP without a resident pair index; MSFL_BAD_ARG when n_pairs differs from the pairs it holds.  A pair
+       whose map side is empty gives zero inliers of that kind, not an error.
+   msfl_score_poses(_batch) keeps answering MSFL_NO_MAP while a pair index is resident.
+
+   msfl_match_pairs_resident: the registration half, against the resident pair index: arguments, per-pair
+   MSFL_MAP_TOO_SMALL preset and every opt-in feature (uncertainty, prior, degeneracy, rejection) as in
+   msfl_match_pairs_batch, whose results msfl_set_pair_maps + this call equal bit for bit.  It does not consume the index
+   and may be called any number of times; msfl_score_pairs calls in between change nothing in it.  MSFL_NO_MAP /
+   MSFL_BAD_ARG as for msfl_score_pairs. */
+msfl_status msfl_set_pair_maps(msfl_handle* h, int n_pairs,
+                               const msfl_point* map_corner, const int* map_corner_off,
+                               const msfl_point* map_surf, const int* map_surf_off, msfl_mem mem);
+msfl_status msfl_score_pairs(msfl_handle* h, int n_pairs,
+                             const msfl_point* corner, const int* corner_off,
+                             const msfl_point* surf, const int* surf_off,
+                             const double* poses, const int* pose_off,
+                             double max_dist, msfl_pose_score* scores, float* d2_out, int* nn_out, msfl_mem mem);
+msfl_status msfl_match_pairs_resident(msfl_handle* h, int n_pairs,
+                                      const msfl_point* corner, const int* corner_off,
+                                      const msfl_point* surf, const int* surf_off,
+                                      double* poses_io, int* status, msfl_match_info* info, msfl_mem mem);
 
 /* Kernel-level entry points (the two halves of one outer iteration), exposed so that parity tests
    can pin the data association and the solver separately:

@@ -35,6 +35,7 @@ EXPORTED = [
     "msfl_set_degeneracy", "msfl_slam_set_degeneracy", "msfl_slam_get_degeneracy",
     "msfl_set_outlier_rejection", "msfl_slam_set_outlier_rejection", "msfl_slam_get_rejection",
     "msfl_score_poses", "msfl_score_poses_batch",
+    "msfl_set_pair_maps", "msfl_score_pairs", "msfl_match_pairs_resident",
     "msfl_places_default_config", "msfl_places_create", "msfl_places_destroy", "msfl_places_set_stream", "msfl_places_synchronize",
     "msfl_places_size", "msfl_places_last_error", "msfl_places_add", "msfl_places_add_descriptors", "msfl_places_get",
     "msfl_places_query", "msfl_places_query_entries",
@@ -760,7 +761,41 @@ class Handle:
                                                     _vp(offs[2]), _vp(d_surf), _vp(offs[3]), _vp(d_poses), _vp(d_status), None, C.c_int(MEM_DEVICE)),
                     "msfl_match_pairs_batch(device)")
 
-    # ---- pose scoring (msfl_score_poses) ----
+    # ---- resident pair maps (msfl_set_pair_maps, msfl_match_pairs_resident; msfl_score_pairs is with the pose scoring below) ----
+    def set_pair_maps(self, map_corner, map_corner_off, map_surf, map_surf_off):
+        """The index half of match_pairs_batch (host memory): the P maps indexed, one grid per pair, and kept resident for
+        score_pairs and match_pairs_resident until set_map, the next set_pair_maps or the next match_pairs_batch."""
+        mc, ms = _pts(map_corner), _pts(map_surf)
+        offs = [np.ascontiguousarray(o, np.int32) for o in (map_corner_off, map_surf_off)]
+        self._check(self.lib.msfl_set_pair_maps(self.h, C.c_int(len(offs[0]) - 1), _vp(mc), _vp(offs[0]), _vp(ms), _vp(offs[1]), C.c_int(MEM_HOST)),
+                    "msfl_set_pair_maps")
+
+    def set_pair_maps_device(self, P, d_map_corner, map_corner_off, d_map_surf, map_surf_off):
+        """The same with device-resident map clouds (torch tensors or raw pointers) and host offset arrays; asynchronous."""
+        offs = [np.ascontiguousarray(o, np.int32) for o in (map_corner_off, map_surf_off)]
+        self._check(self.lib.msfl_set_pair_maps(self.h, C.c_int(int(P)), _vp(d_map_corner), _vp(offs[0]), _vp(d_map_surf), _vp(offs[1]),
+                                                C.c_int(MEM_DEVICE)), "msfl_set_pair_maps(device)")
+
+    def match_pairs_resident(self, corner, corner_off, surf, surf_off, poses, want_info=False):
+        """The registration half of match_pairs_batch against the resident pair index (host memory) -> (poses (P,7), status (P,),
+        info list or None).  The index is not consumed."""
+        c, s_ = _pts(corner), _pts(surf)
+        offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off)]
+        P = len(offs[0]) - 1
+        poses = np.ascontiguousarray(np.array(poses, np.float64).reshape(P, 7))
+        status = np.zeros(P, np.int32)
+        info = (MatchInfo * P)() if want_info else None
+        self._check(self.lib.msfl_match_pairs_resident(self.h, C.c_int(P), _vp(c), _vp(offs[0]), _vp(s_), _vp(offs[1]), _vp(poses), _vp(status), info,
+                                                       C.c_int(MEM_HOST)), "msfl_match_pairs_resident")
+        return poses, status, info
+
+    def match_pairs_resident_device(self, P, d_corner, corner_off, d_surf, surf_off, d_poses, d_status):
+        """The same with device-resident clouds / poses / status and host offset arrays; asynchronous."""
+        offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off)]
+        self._check(self.lib.msfl_match_pairs_resident(self.h, C.c_int(int(P)), _vp(d_corner), _vp(offs[0]), _vp(d_surf), _vp(offs[1]), _vp(d_poses),
+                                                       _vp(d_status), None, C.c_int(MEM_DEVICE)), "msfl_match_pairs_resident(device)")
+
+    # ---- pose scoring (msfl_score_poses, msfl_score_pairs) ----
     def score_poses_device(self, corner, n_corner, surf, n_surf, poses, n_poses, max_dist, scores, d2_out=None, nn_out=None):
         """Device-pointer form (torch tensors / raw pointers), asynchronous on the handle's stream: `scores` holds n_poses records of
         POSE_SCORE_DTYPE.itemsize bytes, d2_out / nn_out (optional) n_poses x (n_corner + n_surf) float32 / int32."""
@@ -839,6 +874,45 @@ class Handle:
         self._check(self.lib.msfl_score_poses_batch(self.h, C.c_int(B), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]),
                                                     C.c_double(float(max_dist)), _vp(rec), C.c_int(MEM_HOST)), "msfl_score_poses_batch")
         return rec
+
+    def score_pairs_device(self, n_pairs, corner, corner_off, surf, surf_off, poses, pose_off, max_dist, scores, d2_out=None, nn_out=None):
+        """Device-pointer form of score_pairs, asynchronous; the three offset arrays are host arrays.  d2_out / nn_out (optional):
+        sum over the pairs of poses x features float32 / int32, ragged rows in pose order."""
+        offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off, pose_off)]
+        self._check(self.lib.msfl_score_pairs(self.h, C.c_int(int(n_pairs)), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses),
+                                              _vp(offs[2]), C.c_double(float(max_dist)), _vp(scores), _vp(d2_out), _vp(nn_out),
+                                              C.c_int(MEM_DEVICE)), "msfl_score_pairs(device)")
+
+    def score_pairs(self, corner, corner_off, surf, surf_off, poses, pose_off, max_dist, want_nn=False):
+        """score_poses_batch against the resident PAIR index (set_pair_maps, or what match_pairs_batch left): scan p at the poses
+        [pose_off[p], pose_off[p+1]) against pair map p only; one record of POSE_SCORE_DTYPE per pose.  want_nn: also (d2, nn), flat
+        and ragged: the row of a pose of scan p has that scan's n_corner + n_surf values, rows in pose order; nn is the position in
+        pair p's own map cloud of the feature's kind.  Offsets are host arrays; clouds and poses numpy arrays or, all three, torch
+        device tensors."""
+        offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off, pose_off)]
+        B = len(offs[0]) - 1
+        n_out = int(sum(int(offs[2][b + 1] - offs[2][b]) * int(offs[0][b + 1] - offs[0][b] + offs[1][b + 1] - offs[1][b]) for b in range(B)))
+        if _on_device(corner) or _on_device(surf) or _on_device(poses):
+            import torch
+            corner, surf, poses = self._device_inputs(corner, surf, poses)
+            P = poses.numel() // 7
+            buf = self._device_scores(poses, P)
+            d2 = torch.empty(max(n_out, 1), dtype=torch.float32, device=poses.device) if want_nn else None
+            nn = torch.empty(max(n_out, 1), dtype=torch.int32, device=poses.device) if want_nn else None
+            self.score_pairs_device(B, corner, offs[0], surf, offs[1], poses, offs[2], max_dist, buf, d2, nn)
+            self.synchronize()
+            rec = np.zeros(P, POSE_SCORE_DTYPE)                     # poses outside [pose_off[0], pose_off[B]) keep zero records
+            p0, p1 = (int(offs[2][0]), int(offs[2][-1])) if B > 0 else (0, 0)
+            rec[p0:p1] = self._scores_to_host(buf, P)[p0:p1]
+            return (rec, d2.cpu().numpy()[:n_out], nn.cpu().numpy()[:n_out]) if want_nn else rec
+        corner, surf = _pts(corner), _pts(surf)
+        poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
+        rec = np.zeros(len(poses), POSE_SCORE_DTYPE)
+        d2 = np.zeros(n_out, np.float32) if want_nn else None
+        nn = np.zeros(n_out, np.int32) if want_nn else None
+        self._check(self.lib.msfl_score_pairs(self.h, C.c_int(B), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]),
+                                              C.c_double(float(max_dist)), _vp(rec), _vp(d2), _vp(nn), C.c_int(MEM_HOST)), "msfl_score_pairs")
+        return (rec, d2, nn) if want_nn else rec
 
     def transform_cloud(self, pts, pose7):
         """TransformPointCloud (laser_mapping.cc:24-31)."""

@@ -197,18 +197,21 @@ struct DeskewScratch {       // msfl_match_scan2map_deskew*: the staged msfl_des
   DevBuf corner_dq, corner_dp, surf_dq, surf_dp;   // double[4 n_corner], [3 n_corner], [4 n_surf], [3 n_surf]
   DevBuf velocity;           // double[3 B]
 };
-struct PairScratch {         // msfl_match_pairs_batch: build_pair_index
+struct PairScratch {         // msfl_set_pair_maps / msfl_match_pairs_batch: build_pair_index, and what the host remembers of the index
   DevBuf off_c, base_c;      // int[P + 1] each: corner-map offsets and cell-table bases
   DevBuf off_s, base_s;      // ... of the surf maps
   DevBuf bbox;               // int[6 P]: per-pair bounding boxes (not MapIndex::bbox: that one is the single-map build's)
+  bool resident = false;     // h->map_c / map_s and the four tables above hold a pair index (every other writer of the maps clears it)
+  std::vector<int> n_c, n_s; // its P pairs' map point counts per kind
 };
 struct ScoreScratch {        // msfl_score_poses*: no other call touches these, so a matcher call after it finds the handle as it left it
   DevBuf corner, surf;       // float4: staged clouds (host mode)
   DevBuf poses;              // double[7 H]: staged hypotheses (host mode)
-  DevBuf off;                // int[3 (n_scans + 1)]: [corner | surf | pose] offsets
+  DevBuf off;                // int[3 (n_scans + 1)]: [corner | surf | pose] offsets; msfl_score_pairs: then int[2 P], where the pairs' map clouds begin
   DevBuf rec;                // ScoreRec[H]: staged results (host mode)
   DevBuf d2, nn;             // float / int [H x features]: staged per-feature outputs (host mode, single scan)
   DevBuf scan;               // int[H]: scan of every hypothesis (batch form), written by score_init_kernel
+  DevBuf out0;               // u64[P]: msfl_score_pairs' first d2_out / nn_out element of every pair (ScorePairsView::out0)
 };
 
 enum TimerClass { T_ASSOC = 0, T_SOLVE, T_INDEX, T_EXTRACT, T_ODOM, T_FIT, T_ASSOC_SEEDED /* a subset of T_ASSOC */, T_COUNT };
@@ -1051,6 +1054,7 @@ msfl_status msfl_set_map(msfl_handle* h, const msfl_point* corner, int n_corner,
   if (n_corner < 0 || n_surf < 0 || (n_corner > 0 && !corner) || (n_surf > 0 && !surf))
     return fail(h, MSFL_BAD_ARG, "msfl_set_map: null cloud with positive size");
   h->have_map = false;
+  h->pr.resident = false;                 // the single map takes the arrays a pair index lived in
   const float4* dc = reinterpret_cast<const float4*>(corner);
   const float4* ds = reinterpret_cast<const float4*>(surf);
   if (mem == MSFL_MEM_HOST) {

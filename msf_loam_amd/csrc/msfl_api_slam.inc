@@ -753,7 +753,7 @@ msfl_status slam_enqueue_mapping(msfl_slam* s, const SlamJob& jb) {
   // ---- surf side (mapping stream): GetSurroundedCloud (:276-278), index (:70-72)
   SCHK(s, hm, grid_surround_enqueue(s->gs, cur.map_lf.as<float4>(), nullptr, cap_lf, cnt + SC_USE_LF, pose_map,
                                     s->map_s.as<float4>(), (int)std::min<long long>(cap_s, INT32_MAX), meta + META_NMS));
-  hm->have_map = false;
+  hm->have_map = false; hm->pr.resident = false;
   SCHK(s, hm, build_index(hm, s->map_s.as<float4>(), (int)std::min<long long>(cap_s, INT32_MAX), hm->map_s, meta + META_NMS));
   hm->have_map = true;
   seg("surf surround + index");

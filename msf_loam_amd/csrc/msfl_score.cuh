@@ -3,7 +3,8 @@
 //   score_init_kernel    one record per hypothesis: all zero, status = MSFL_BAD_ARG for a pose with a non-finite entry; and the
 //                        hypothesis' scan in a batch call
 //   score_poses_kernel   one lane per (hypothesis, feature): transform, nearest map point of the feature's kind within the
-//                        threshold, then an integer reduction into the hypothesis' record
+//                        threshold, then an integer reduction into the hypothesis' record.  <false>: every scan against the
+//                        resident single map; <true> (msfl_score_pairs): scan b against pair b of the resident pair index
 //
 // The walk is grid_walk_exact (msfl_knn_index.cuh), the one knn5_grid takes: nine (y, z) rows centre-first in the per-query
 // near-side order, x ends trimmed on the per-side lower bounds.  Its state is
@@ -41,6 +42,15 @@ struct ScoreJob {
   ScoreRec* rec;
   float thr;
   float* d2_out; int* nn_out;
+};
+
+// What the PAIRS instantiation reads besides: the pair index's cell-table bases, and for d2_out / nn_out (whose rows are
+// ragged there: F(b) values per hypothesis of scan b) the first output element of every scan's first hypothesis and where
+// pair b's map clouds begin in the concatenated clouds the index words count in.
+struct ScorePairsView {
+  const int* cbase_c; const int* cbase_s;   // n_scans + 1 each (PairScratch::base_c / base_s)
+  const int* map_c0; const int* map_s0;     // n_scans each
+  const unsigned long long* out0;           // n_scans
 };
 
 __global__ void __launch_bounds__(256) score_init_kernel(ScoreJob j, int n, int bad_status) {
@@ -84,10 +94,14 @@ __device__ __forceinline__ void nn1_grid(const GridDesc& g, const float4* __rest
 }
 
 // grid: x = workgroups of one hypothesis (its scan's corner features first, then its surf features; a workgroup holds one
-// kind), y = hypothesis row0 + blockIdx.y of the call.
+// kind), y = hypothesis row0 + blockIdx.y of the call.  PAIRS: b is also the hypothesis' pair, as in
+// knn5_scan2map_kernel<.., true>: descriptor b, the cell table from cell_base[b] on; b is uniform over the workgroup, so
+// both are scalar loads, one per kind.
+template <bool PAIRS>
 __global__ void __launch_bounds__(kScoreBlock) score_poses_kernel(ScoreJob j, int row0,
                                                                    const GridDesc* __restrict__ gcp, const float4* __restrict__ map_c, const int* __restrict__ cs_c,
-                                                                   const GridDesc* __restrict__ gsp, const float4* __restrict__ map_s, const int* __restrict__ cs_s) {
+                                                                   const GridDesc* __restrict__ gsp, const float4* __restrict__ map_s, const int* __restrict__ cs_s,
+                                                                   ScorePairsView pv) {
   __shared__ unsigned long long s_sum[kScoreBlock / 64];
   __shared__ int s_cnt[kScoreBlock / 64];
   const int hyp = row0 + (int)blockIdx.y;
@@ -112,17 +126,20 @@ __global__ void __launch_bounds__(kScoreBlock) score_poses_kernel(ScoreJob j, in
     if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z)) {
       const float3 q = transform_point_f32(T, p.x, p.y, p.z);
       if (isfinite(q.x) && isfinite(q.y) && isfinite(q.z)) {
-        if (kind) { const GridDesc g = *gsp; nn1_grid(g, map_s, cs_s, q, best); }
-        else { const GridDesc g = *gcp; nn1_grid(g, map_c, cs_c, q, best); }
+        if (kind) { const GridDesc g = gsp[PAIRS ? b : 0]; nn1_grid(g, map_s, cs_s + (PAIRS ? pv.cbase_s[b] : 0), q, best); }
+        else { const GridDesc g = gcp[PAIRS ? b : 0]; nn1_grid(g, map_c, cs_c + (PAIRS ? pv.cbase_c[b] : 0), q, best); }
       }
     }
   }
   const bool found = (unsigned int)best != kScoreNoIndex;
   const float d2 = __uint_as_float((unsigned int)(best >> 32));
   if (live && (j.d2_out || j.nn_out)) {
-    const size_t o = (size_t)hyp * (size_t)(n_c + n_s) + (size_t)(kind ? n_c + f : f);
+    // PAIRS: the row starts behind those of the scans before b and of b's earlier hypotheses; the index word counts in the
+    // concatenated map clouds, the caller gets the position in pair b's own cloud
+    const size_t row = PAIRS ? (size_t)pv.out0[b] + (size_t)(hyp - j.pose_off[b]) * (size_t)(n_c + n_s) : (size_t)hyp * (size_t)(n_c + n_s);
+    const size_t o = row + (size_t)(kind ? n_c + f : f);
     if (j.d2_out) j.d2_out[o] = found ? d2 : INFINITY;
-    if (j.nn_out) j.nn_out[o] = found ? (int)(unsigned int)best : -1;
+    if (j.nn_out) j.nn_out[o] = found ? (int)(unsigned int)best - (PAIRS ? (kind ? pv.map_s0[b] : pv.map_c0[b]) : 0) : -1;
   }
   // d2 <= 64 (host check), so d2 * 2^32 <= 2^38: the scaling is exact and rintf (nearest-even) only acts below 2^23
   unsigned long long sum = found ? (unsigned long long)rintf(d2 * 4294967296.0f) : 0ull;
