@@ -615,7 +615,10 @@ msfl_status msfl_extract_features_batch(msfl_handle* h, int n_scans,
    compaction followed by the same filter.  (For a cloud flagged dense PCL does not look and its
    result is undefined; the reference's clouds never hold such a point, msf_loam_node.cc:85-111.)
    The batch forms below REFUSE a cloud with a non-finite point (MSFL_BAD_ARG): their inputs are
-   the extraction's own outputs. */
+   the extraction's own outputs.
+   MSFL_CAPACITY, *n_out = 0: the leaf is too small for the cloud's extent -- its bounding box holds
+   more than 2^31 - 1 voxels, or a voxel coordinate floor(p / leaf) reaches 1e9 in magnitude
+   (pcl::VoxelGrid warns "leaf size is too small" and does not filter such a cloud). */
 msfl_status msfl_voxel_downsample(msfl_handle* h,
                                   const msfl_point* pts, int n, float leaf,
                                   msfl_point* out, int* n_out, msfl_mem mem);
@@ -629,7 +632,10 @@ msfl_status msfl_voxel_downsample(msfl_handle* h,
    count / out follow `mem`.  The filtered clouds are written back to back into `out` (capacity
    off[n]-off[0] points) and out_off (HOST, n_clouds+1) receives their boundaries; the call
    synchronises once to deliver them.  A cloud holding a non-finite point makes the call return
-   MSFL_BAD_ARG (the clouds before it are still delivered). */
+   MSFL_BAD_ARG (the clouds before it are still delivered).  A cloud whose leaf is too small for
+   its extent (see msfl_voxel_downsample) makes the call return MSFL_CAPACITY: that cloud's output
+   range is empty (out_off[b] == out_off[b+1]) and every other cloud of the batch is delivered.
+   msfl_voxel_downsample_batch_pair reports it the same way, per list: the other list is unaffected. */
 msfl_status msfl_voxel_downsample_batch(msfl_handle* h, int n_clouds,
                                         const msfl_point* pts, const int* idx, const int* off,
                                         const int* count, float leaf,

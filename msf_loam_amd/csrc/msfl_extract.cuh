@@ -1083,8 +1083,12 @@ __global__ void __launch_bounds__(kVoxDescThreads) voxel_batch_desc_kernel(Voxel
       float lo = s_mn[0][a], hi = s_mx[0][a];
       for (int w = 1; w < kVoxDescThreads / 64; w++) { lo = fminf(lo, s_mn[w][a]); hi = fmaxf(hi, s_mx[w][a]); }
       if (!(lo <= hi)) { d.min_b[a] = 0; d.div_b[a] = 1; if (n > 0) d.bad = 2; continue; }       // no finite point
-      d.min_b[a] = (int)floorf(lo * v.inv_leaf);
-      d.div_b[a] = (int)floorf(hi * v.inv_leaf) - d.min_b[a] + 1;
+      // voxel coordinates an int cannot hold (x = 1e10 at leaf 0.5) used to saturate in the casts below: div_b wrapped negative, the
+      // cell count with it, and the cloud was filtered with a one-bit key.  The same line as the per-scan chain's vox_big_bbox_kernel
+      const float flo = floorf(lo * v.inv_leaf), fhi = floorf(hi * v.inv_leaf);
+      if (!(fabsf(flo) < 1e9f && fabsf(fhi) < 1e9f)) { d.min_b[a] = 0; d.div_b[a] = 1; d.bad = 1; continue; }
+      d.min_b[a] = (int)flo;
+      d.div_b[a] = (int)fhi - d.min_b[a] + 1;
       cells *= d.div_b[a];
       if (cells > 0x7fffffffLL) d.bad = 1;            // leaf too small for the extent (PCL would skip filtering)
     }
