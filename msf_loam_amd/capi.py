@@ -16,40 +16,40 @@ LIB_PATH = os.environ.get("MSFL_LIB") or os.path.join(_HERE, "libmsfl_hip.so")
 OK, TOO_FEW_CORRESPONDENCES, MAP_TOO_SMALL, BAD_ARG, HIP_ERROR, BAD_RING, NO_MAP, CAPACITY = range(8)
 MEM_HOST, MEM_DEVICE = 0, 1
 
-EXPORTED = [
-    "msfl_default_params", "msfl_api_version", "msfl_create", "msfl_destroy", "msfl_set_stream", "msfl_reset_stream",
-    "msfl_synchronize", "msfl_status_string", "msfl_last_error", "msfl_set_timing", "msfl_get_timing",
-    "msfl_set_map", "msfl_match_scan2map", "msfl_match_scan2map_batch", "msfl_match_pairs_batch", "msfl_match_scan2map_deskew",
-    "msfl_match_scan2map_deskew_batch",
-    "msfl_associate_scan2map", "msfl_solve_records", "msfl_associate_scan2map_deskew", "msfl_solve_records_deskew",
-    "msfl_match_scan2scan", "msfl_match_scan2scan_batch", "msfl_extract_features",
-    "msfl_extract_features_batch", "msfl_voxel_downsample", "msfl_voxel_downsample_batch", "msfl_voxel_downsample_batch_pair",
-    "msfl_transform_cloud",
-    "msfl_delta_qp", "msfl_deskew_cloud", "msfl_undistort_cloud",
-    "msfl_grid_create", "msfl_grid_destroy", "msfl_grid_insert_scan", "msfl_grid_get_surrounded", "msfl_grid_size", "msfl_grid_dump",
-    "msfl_grid_crop", "msfl_grid_crop_tiles", "msfl_grid_load_cells", "msfl_grid_dump_cells", "msfl_grid_stats", "msfl_slam_set_map_window", "msfl_slam_get_map_window",
-    "msfl_slam_default_config", "msfl_slam_create", "msfl_slam_destroy", "msfl_slam_add_scan", "msfl_slam_add_scan_imu", "msfl_slam_get_result", "msfl_slam_grids",
-    "msfl_slam_last_error", "msfl_slam_get_clouds",
-    "msfl_set_uncertainty", "msfl_slam_set_uncertainty", "msfl_slam_get_uncertainty",
-    "msfl_set_pose_prior", "msfl_slam_set_next_prior",
-    "msfl_set_degeneracy", "msfl_slam_set_degeneracy", "msfl_slam_get_degeneracy",
-    "msfl_set_outlier_rejection", "msfl_slam_set_outlier_rejection", "msfl_slam_get_rejection",
-    "msfl_score_poses", "msfl_score_poses_batch",
-    "msfl_set_pair_maps", "msfl_score_pairs", "msfl_match_pairs_resident",
-    "msfl_places_default_config", "msfl_places_create", "msfl_places_destroy", "msfl_places_set_stream", "msfl_places_synchronize",
-    "msfl_places_size", "msfl_places_last_error", "msfl_places_add", "msfl_places_add_descriptors", "msfl_places_get",
-    "msfl_places_query", "msfl_places_query_entries",
-    "msfl_graph_default_config", "msfl_graph_create", "msfl_graph_destroy", "msfl_graph_set_stream", "msfl_graph_synchronize",
-    "msfl_graph_last_error", "msfl_graph_clear", "msfl_graph_num_nodes", "msfl_graph_add_nodes", "msfl_graph_add_edges",
-    "msfl_graph_add_fixes", "msfl_graph_set_fixed", "msfl_graph_set_poses", "msfl_graph_get_poses", "msfl_graph_cost",
-    "msfl_graph_optimize", "msfl_graph_get_trace",
-    "msfl_graph_add_edges_info", "msfl_graph_add_fixes_info", "msfl_graph_edge_from_uncertainty", "msfl_graph_fix_from_covariance",
-    "msfl_graph_factor_chi2",
-    "msfl_graph_set_losses", "msfl_graph_get_losses", "msfl_graph_factor_weights",
-    "msfl_graph_marginals_default_options", "msfl_graph_marginals", "msfl_graph_marginals_with", "msfl_graph_relative_covariance",
-    "msfl_keyframes_default_config", "msfl_keyframes_create", "msfl_keyframes_destroy", "msfl_keyframes_size", "msfl_keyframes_add",
-    "msfl_keyframes_sizes", "msfl_keyframes_get", "msfl_keyframes_compose", "msfl_keyframes_insert",
-]
+# One prototype per function of include/msfl_c_api.h, in the header's order: name=return:parameters.  Returns: i msfl_status / int,
+# v void, z const char*.  Parameters: p any pointer or array (c_void_p), i int / msfl_mem, d double, f float.  load() applies them all;
+# tests/test_capi_symbols.py holds the table against the header.  (The msfl_debug_* exports of profile builds stay undeclared.)
+_CTYPE = {"i": C.c_int, "v": None, "z": C.c_char_p, "p": C.c_void_p, "d": C.c_double, "f": C.c_float}
+PROTOTYPES = dict(t.split("=") for t in """
+    msfl_default_params=v:p msfl_api_version=i: msfl_create=i:pip msfl_destroy=v:p msfl_set_stream=i:pp msfl_reset_stream=i:p msfl_synchronize=i:p
+    msfl_status_string=z:i msfl_last_error=z:p msfl_set_timing=i:pi msfl_get_timing=i:ppi msfl_set_uncertainty=i:ppiid msfl_set_pose_prior=i:ppii
+    msfl_set_degeneracy=i:pidpii msfl_set_outlier_rejection=i:pppii msfl_set_map=i:ppipii msfl_match_scan2map=i:ppipippi
+    msfl_match_scan2map_batch=i:pipppppppi msfl_match_pairs_batch=i:pipppppppppppi msfl_score_poses=i:ppipipidpppi
+    msfl_score_poses_batch=i:pippppppdpi msfl_set_pair_maps=i:pippppi msfl_score_pairs=i:pippppppdpppi msfl_match_pairs_resident=i:pipppppppi
+    msfl_associate_scan2map=i:ppipipp msfl_solve_records=i:ppipippp msfl_match_scan2map_deskew=i:ppipippp msfl_associate_scan2map_deskew=i:ppipipppp
+    msfl_solve_records_deskew=i:ppipipppp msfl_match_scan2map_deskew_batch=i:pippppppppi msfl_match_scan2scan=i:pppppppi
+    msfl_match_scan2scan_batch=i:pipppppppi msfl_extract_features=i:pppippi msfl_extract_features_batch=i:pipppppi msfl_voxel_downsample=i:ppifppi
+    msfl_voxel_downsample_batch=i:pippppfppi msfl_voxel_downsample_batch_pair=i:pippppfppppfppi msfl_transform_cloud=i:ppippi msfl_delta_qp=i:pppippi
+    msfl_deskew_cloud=i:pppipppi msfl_undistort_cloud=i:pppii msfl_grid_create=i:pffp msfl_grid_destroy=v:p msfl_grid_insert_scan=i:ppii
+    msfl_grid_get_surrounded=i:ppippipi msfl_grid_size=i:ppp msfl_grid_dump=i:ppipi msfl_grid_dump_cells=i:ppip msfl_grid_stats=i:pp
+    msfl_grid_crop=i:ppppiip msfl_grid_crop_tiles=i:ppppipiip msfl_grid_load_cells=i:ppipiipp msfl_slam_default_config=v:p msfl_slam_create=i:ppip
+    msfl_slam_destroy=v:p msfl_slam_add_scan=i:pppiip msfl_slam_add_scan_imu=i:pppiipp msfl_slam_get_result=i:pip msfl_slam_set_uncertainty=i:pid
+    msfl_slam_get_uncertainty=i:pipp msfl_slam_set_degeneracy=i:piidd msfl_slam_get_degeneracy=i:pipp msfl_slam_set_outlier_rejection=i:ppp
+    msfl_slam_get_rejection=i:pipp msfl_slam_set_next_prior=i:ppp msfl_slam_set_map_window=i:ppi msfl_slam_get_map_window=i:pipp
+    msfl_slam_get_clouds=i:pipi msfl_slam_grids=i:ppp msfl_slam_last_error=z:p msfl_places_default_config=v:p msfl_places_create=i:pip
+    msfl_places_destroy=v:p msfl_places_set_stream=i:pp msfl_places_synchronize=i:p msfl_places_size=i:p msfl_places_last_error=z:p
+    msfl_places_add=i:pppiip msfl_places_add_descriptors=i:ppiip msfl_places_get=i:piippi msfl_places_query=i:pppipiipi
+    msfl_places_query_entries=i:ppipiipi msfl_graph_default_config=v:p msfl_graph_create=i:pip msfl_graph_destroy=v:p msfl_graph_set_stream=i:pp
+    msfl_graph_synchronize=i:p msfl_graph_last_error=z:p msfl_graph_clear=i:p msfl_graph_num_nodes=i:p msfl_graph_add_nodes=i:ppiip
+    msfl_graph_add_edges=i:ppi msfl_graph_add_fixes=i:ppi msfl_graph_set_fixed=i:pii msfl_graph_set_poses=i:piipi msfl_graph_get_poses=i:piipi
+    msfl_graph_cost=i:pp msfl_graph_optimize=i:pp msfl_graph_get_trace=i:pppip msfl_graph_add_edges_info=i:ppi msfl_graph_add_fixes_info=i:ppi
+    msfl_graph_edge_from_uncertainty=i:iipppdp msfl_graph_fix_from_covariance=i:iidppp msfl_graph_factor_chi2=i:piiip msfl_graph_set_losses=i:piiipi
+    msfl_graph_get_losses=i:piiip msfl_graph_factor_weights=i:piiip msfl_graph_marginals_default_options=v:p msfl_graph_marginals=i:ppipip
+    msfl_graph_marginals_with=i:ppipipp msfl_graph_relative_covariance=i:pppppp msfl_keyframes_default_config=v:p msfl_keyframes_create=i:ppp
+    msfl_keyframes_destroy=v:p msfl_keyframes_size=i:p msfl_keyframes_add=i:pppippiip msfl_keyframes_sizes=i:piipp msfl_keyframes_get=i:pipipii
+    msfl_keyframes_compose=i:pipppffpippipi msfl_keyframes_insert=i:pppippp
+""".split())
+EXPORTED = list(PROTOTYPES)
 
 
 class Preintegration(C.Structure):
@@ -321,15 +321,16 @@ def load():
             raise RuntimeError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        lib.msfl_status_string.restype = C.c_char_p
-        lib.msfl_last_error.restype = C.c_char_p
-        lib.msfl_last_error.argtypes = [C.c_void_p]
+        for name, sig in PROTOTYPES.items():                        # a missing export raises here, by name
+            ret, params = sig.split(":")
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[k] for k in params]
         _lib = lib
     return _lib
 
 
 def status_string(s):
-    return load().msfl_status_string(C.c_int(int(s))).decode()
+    return load().msfl_status_string(int(s)).decode()
 
 
 def default_params():
@@ -355,22 +356,25 @@ def _pts(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, 4))
 
 
-class Handle:
-    """Owns one msfl_handle (one HIP stream + device scratch)."""
+class _Owner:
+    """What the six owners share: `lib`, one opaque pointer (the attribute _PTR names), the function that destroys it and the one
+    that delivers its error text (_ERROR None: the text is the parent handle's)."""
+    _PTR = _DESTROY = _ERROR = None
+    _dependents = ()                                                # objects to close before this one (Handle)
 
-    def __init__(self, device=0, params=None):
-        self.lib = load()
-        self.h = C.c_void_p()
-        s = self.lib.msfl_create(C.byref(params) if params is not None else None, C.c_int(device), C.byref(self.h))
-        if s != OK:
-            raise MsflError(s, "msfl_create", "(no GPU / HIP runtime? there is no CPU fallback)")
+    def _own(self, lib):
+        """Starts with a null pointer; returns the reference msfl_*_create fills."""
+        self.lib = lib
+        setattr(self, self._PTR, C.c_void_p())
+        return C.byref(getattr(self, self._PTR))
 
     def close(self):
-        if self.h:
-            for g in list(getattr(self, "_grids", ())):           # a grid must be destroyed before its handle (msfl_c_api.h)
-                g.close()
-            self.lib.msfl_destroy(self.h)
-            self.h = C.c_void_p()
+        p = getattr(self, self._PTR)
+        if p:
+            for d in list(self._dependents):                        # a grid must be destroyed before its handle (msfl_c_api.h)
+                d.close()
+            getattr(self.lib, self._DESTROY)(p)
+            setattr(self, self._PTR, C.c_void_p())
 
     def __del__(self):
         try:
@@ -378,14 +382,53 @@ class Handle:
         except Exception:
             pass
 
-    def _check(self, s, what, allow=()):
-        if s != OK and s not in allow:
-            raise MsflError(s, what, self.lib.msfl_last_error(self.h).decode())
-        return s
+    def last_error(self):
+        if self._ERROR is None:
+            return self.handle.last_error()
+        return (getattr(self.lib, self._ERROR)(getattr(self, self._PTR)) or b"").decode()
+
+    def _check(self, status, what, allow=()):
+        if status != OK and status not in allow:
+            raise MsflError(status, what, self.last_error())
+        return status
+
+
+class Handle(_Owner):
+    """Owns one msfl_handle (one HIP stream + device scratch)."""
+    _PTR, _DESTROY, _ERROR = "h", "msfl_destroy", "msfl_last_error"
+    # the record sinks: attribute of the host buffer, its dtype, what reading says when there is none
+    _SINKS = {"uncertainty": ("_unc", UNCERTAINTY_DTYPE, "uncertainty output is off: call set_uncertainty(n) first"),
+              "degeneracy": ("_degen", DEGENERACY_DTYPE, "no degeneracy record sink: call set_degeneracy(min_eigenvalue, n) first"),
+              "rejection": ("_reject", REJECTION_DTYPE, "no rejection record sink: call set_outlier_rejection(..., n=n) first")}
+
+    def __init__(self, device=0, params=None):
+        self._dependents = weakref.WeakSet()                        # the open Grid / Keyframes objects on this handle
+        self._unc = self._degen = self._reject = self._prior = None
+        ref = self._own(load())
+        s = self.lib.msfl_create(C.byref(params) if params is not None else None, device, ref)
+        if s != OK:
+            raise MsflError(s, "msfl_create", "(no GPU / HIP runtime? there is no CPU fallback)")
+
+    def _set_sink(self, kind, call, what, ptr=None, capacity=0, mem=MEM_HOST):
+        """Points one record sink somewhere: call(ptr, capacity, mem) is the msfl_set_* call with its other arguments bound.  Host
+        memory with a capacity: a fresh structured array that this object keeps (what _records reads); a device pointer or no sink
+        drops it.  The old array goes only once the library has taken the new sink."""
+        capacity = int(capacity or 0)
+        buf = np.zeros(capacity, self._SINKS[kind][1]) if mem == MEM_HOST and capacity else None
+        self._check(call(_vp(ptr if buf is None else buf), capacity, mem), what)
+        setattr(self, self._SINKS[kind][0], buf)
+
+    def _records(self, kind, n):
+        """The first `n` records (default: all) the last matcher call wrote into the kept host sink, as a copy."""
+        attr, _, missing = self._SINKS[kind]
+        buf = getattr(self, attr)
+        if buf is None:
+            raise RuntimeError(missing)
+        return buf[:len(buf) if n is None else int(n)].copy()
 
     # ---- plumbing ----
     def set_stream(self, stream_ptr):
-        self._check(self.lib.msfl_set_stream(self.h, C.c_void_p(stream_ptr)), "msfl_set_stream")
+        self._check(self.lib.msfl_set_stream(self.h, stream_ptr), "msfl_set_stream")
 
     def reset_stream(self):
         self._check(self.lib.msfl_reset_stream(self.h), "msfl_reset_stream")
@@ -394,59 +437,46 @@ class Handle:
         self._check(self.lib.msfl_synchronize(self.h), "msfl_synchronize")
 
     def set_timing(self, on=True):
-        self._check(self.lib.msfl_set_timing(self.h, C.c_int(int(on))), "msfl_set_timing")
+        self._check(self.lib.msfl_set_timing(self.h, int(on)), "msfl_set_timing")
 
     def get_timing(self, reset=True):
         t = Timing()
-        self._check(self.lib.msfl_get_timing(self.h, C.byref(t), C.c_int(int(reset))), "msfl_get_timing")
+        self._check(self.lib.msfl_get_timing(self.h, C.byref(t), int(reset)), "msfl_get_timing")
         return t
 
     # ---- uncertainty output (msfl_set_uncertainty) ----
     def set_uncertainty(self, n, min_eigenvalue=0.0):
         """Every later matcher call writes one msfl_match_uncertainty per registration into a host buffer of `n` records
         owned by this object (read it with uncertainty()).  n = 0 / None turns the feature off."""
-        if not n:
-            self._check(self.lib.msfl_set_uncertainty(self.h, None, C.c_int(0), C.c_int(MEM_HOST), C.c_double(0.0)), "msfl_set_uncertainty")
-            self._unc = None
-            return
-        buf = np.zeros(int(n), UNCERTAINTY_DTYPE)
-        self._check(self.lib.msfl_set_uncertainty(self.h, _vp(buf), C.c_int(int(n)), C.c_int(MEM_HOST), C.c_double(float(min_eigenvalue))),
-                    "msfl_set_uncertainty")
-        self._unc = buf
+        eig = min_eigenvalue if n else 0.0
+        self._set_sink("uncertainty", lambda p, cap, mem: self.lib.msfl_set_uncertainty(self.h, p, cap, mem, eig), "msfl_set_uncertainty",
+                       capacity=n)
 
     def uncertainty(self, n=None):
         """The first `n` records (default: all) the last matcher call wrote, as a copy of the numpy structured array."""
-        buf = getattr(self, "_unc", None)
-        if buf is None:
-            raise RuntimeError("uncertainty output is off: call set_uncertainty(n) first")
-        return buf[:len(buf) if n is None else int(n)].copy()
+        return self._records("uncertainty", n)
 
     def set_uncertainty_device(self, ptr, capacity, min_eigenvalue=0.0):
         """Device-pointer variant for the *_device calls: `ptr` (torch tensor / raw pointer / None = off) holds `capacity` records of
         UNCERTAINTY_DTYPE.itemsize bytes; written asynchronously on the handle's stream."""
-        self._unc = None
-        self._check(self.lib.msfl_set_uncertainty(self.h, _vp(ptr), C.c_int(int(capacity) if ptr is not None else 0), C.c_int(MEM_DEVICE),
-                                                  C.c_double(float(min_eigenvalue))), "msfl_set_uncertainty(device)")
+        self._set_sink("uncertainty", lambda p, cap, mem: self.lib.msfl_set_uncertainty(self.h, p, cap, mem, min_eigenvalue),
+                       "msfl_set_uncertainty(device)", ptr, capacity if ptr is not None else 0, MEM_DEVICE)
 
     # ---- degeneracy-aware solve (msfl_set_degeneracy) ----
     def set_degeneracy(self, min_eigenvalue, n=0):
         """Every later solve holds the eigen-directions of its entry matrix below `min_eigenvalue` at the guess.  n > 0: one
         msfl_degeneracy_record per registration goes to a host buffer of `n` records owned by this object (read it with degeneracy())."""
-        buf = np.zeros(int(n), DEGENERACY_DTYPE) if n else None
-        self._check(self.lib.msfl_set_degeneracy(self.h, C.c_int(1), C.c_double(float(min_eigenvalue)), _vp(buf), C.c_int(int(n) if n else 0),
-                                                 C.c_int(MEM_HOST)), "msfl_set_degeneracy")
-        self._degen = buf
+        self._set_sink("degeneracy", lambda p, cap, mem: self.lib.msfl_set_degeneracy(self.h, 1, min_eigenvalue, p, cap, mem),
+                       "msfl_set_degeneracy", capacity=n)
 
     def set_degeneracy_device(self, min_eigenvalue, ptr, capacity):
         """Device-pointer sink: `ptr` (torch tensor / raw pointer) holds `capacity` records of DEGENERACY_DTYPE.itemsize bytes, written
         asynchronously on the handle's stream."""
-        self._check(self.lib.msfl_set_degeneracy(self.h, C.c_int(1), C.c_double(float(min_eigenvalue)), _vp(ptr), C.c_int(int(capacity)),
-                                                 C.c_int(MEM_DEVICE)), "msfl_set_degeneracy(device)")
-        self._degen = None
+        self._set_sink("degeneracy", lambda p, cap, mem: self.lib.msfl_set_degeneracy(self.h, 1, min_eigenvalue, p, cap, mem),
+                       "msfl_set_degeneracy(device)", ptr, capacity, MEM_DEVICE)
 
     def clear_degeneracy(self):
-        self._check(self.lib.msfl_set_degeneracy(self.h, C.c_int(0), C.c_double(0.0), None, C.c_int(0), C.c_int(MEM_HOST)), "msfl_set_degeneracy")
-        self._degen = None
+        self._set_sink("degeneracy", lambda p, cap, mem: self.lib.msfl_set_degeneracy(self.h, 0, 0.0, p, cap, mem), "msfl_set_degeneracy")
 
     # ---- outlier rejection in front of the solve (msfl_set_outlier_rejection) ----
     def set_outlier_rejection(self, threshold=None, fraction=None, which=REJECT_LAST_OUTER, n=0):
@@ -454,53 +484,44 @@ class Handle:
         `threshold`, or the ceil(n * fraction) largest of each scan.  n > 0: one msfl_rejection_record per registration goes to a host
         buffer of `n` records owned by this object (read it with rejection())."""
         cfg = outlier_rejection(threshold, fraction, which)
-        buf = np.zeros(int(n), REJECTION_DTYPE) if n else None
-        self._check(self.lib.msfl_set_outlier_rejection(self.h, C.byref(cfg), _vp(buf), C.c_int(int(n) if n else 0), C.c_int(MEM_HOST)),
-                    "msfl_set_outlier_rejection")
-        self._reject = buf
+        self._set_sink("rejection", lambda p, cap, mem: self.lib.msfl_set_outlier_rejection(self.h, C.byref(cfg), p, cap, mem),
+                       "msfl_set_outlier_rejection", capacity=n)
 
     def set_outlier_rejection_device(self, ptr, capacity, threshold=None, fraction=None, which=REJECT_LAST_OUTER):
         """Device-pointer sink: `ptr` (torch tensor / raw pointer) holds `capacity` records of REJECTION_DTYPE.itemsize bytes, written
         asynchronously on the handle's stream."""
         cfg = outlier_rejection(threshold, fraction, which)
-        self._check(self.lib.msfl_set_outlier_rejection(self.h, C.byref(cfg), _vp(ptr), C.c_int(int(capacity)), C.c_int(MEM_DEVICE)),
-                    "msfl_set_outlier_rejection(device)")
-        self._reject = None
+        self._set_sink("rejection", lambda p, cap, mem: self.lib.msfl_set_outlier_rejection(self.h, C.byref(cfg), p, cap, mem),
+                       "msfl_set_outlier_rejection(device)", ptr, capacity, MEM_DEVICE)
 
     def clear_outlier_rejection(self):
-        self._check(self.lib.msfl_set_outlier_rejection(self.h, None, None, C.c_int(0), C.c_int(MEM_HOST)), "msfl_set_outlier_rejection")
-        self._reject = None
+        self._set_sink("rejection", lambda p, cap, mem: self.lib.msfl_set_outlier_rejection(self.h, None, p, cap, mem),
+                       "msfl_set_outlier_rejection")
 
     def rejection(self, n=None):
         """The first `n` records (default: all) the last matcher call wrote, as a copy of the numpy structured array."""
-        buf = getattr(self, "_reject", None)
-        if buf is None:
-            raise RuntimeError("no rejection record sink: call set_outlier_rejection(..., n=n) first")
-        return buf[:len(buf) if n is None else int(n)].copy()
+        return self._records("rejection", n)
 
     def degeneracy(self, n=None):
         """The first `n` records (default: all) the last matcher call wrote, as a copy of the numpy structured array."""
-        buf = getattr(self, "_degen", None)
-        if buf is None:
-            raise RuntimeError("no degeneracy record sink: call set_degeneracy(min_eigenvalue, n) first")
-        return buf[:len(buf) if n is None else int(n)].copy()
+        return self._records("degeneracy", n)
 
     # ---- pose priors (msfl_set_pose_prior) ----
     def set_pose_prior(self, poses, sqrt_info):
         """priors[b] = (poses[b], sqrt_info[b]) joins the problem of registration b of every later matcher call.  The records
         live in a host buffer owned by this object (the library reads it at each call)."""
         rec = pose_priors(poses, sqrt_info)
-        self._check(self.lib.msfl_set_pose_prior(self.h, _vp(rec), C.c_int(len(rec)), C.c_int(MEM_HOST)), "msfl_set_pose_prior")
+        self._check(self.lib.msfl_set_pose_prior(self.h, _vp(rec), len(rec), MEM_HOST), "msfl_set_pose_prior")
         self._prior = rec
 
     def set_pose_prior_device(self, ptr, count):
         """Device-pointer variant: `ptr` (torch tensor / raw pointer) holds `count` records of POSE_PRIOR_DTYPE.itemsize bytes, read on
         the handle's stream at each matcher call."""
-        self._check(self.lib.msfl_set_pose_prior(self.h, _vp(ptr), C.c_int(int(count)), C.c_int(MEM_DEVICE)), "msfl_set_pose_prior(device)")
+        self._check(self.lib.msfl_set_pose_prior(self.h, _vp(ptr), int(count), MEM_DEVICE), "msfl_set_pose_prior(device)")
         self._prior = ptr
 
     def clear_pose_prior(self):
-        self._check(self.lib.msfl_set_pose_prior(self.h, None, C.c_int(0), C.c_int(MEM_HOST)), "msfl_set_pose_prior")
+        self._check(self.lib.msfl_set_pose_prior(self.h, None, 0, MEM_HOST), "msfl_set_pose_prior")
         self._prior = None
 
     # ---- stage C ----
@@ -509,15 +530,14 @@ class Handle:
             corner, surf = _pts(corner), _pts(surf)
             n_corner, n_surf = len(corner), len(surf)
             self._keep = (corner, surf)
-        self._check(self.lib.msfl_set_map(self.h, _vp(corner), C.c_int(n_corner), _vp(surf), C.c_int(n_surf),
-                                          C.c_int(mem)), "msfl_set_map")
+        self._check(self.lib.msfl_set_map(self.h, _vp(corner), n_corner, _vp(surf), n_surf, mem), "msfl_set_map")
 
     def match_scan2map(self, corner, surf, pose, want_info=True, allow=()):
         corner, surf = _pts(corner), _pts(surf)
         pose = np.array(pose, dtype=np.float64)
         info = MatchInfo()
-        s = self.lib.msfl_match_scan2map(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
-                                         _vp(pose), C.byref(info) if want_info else None, C.c_int(MEM_HOST))
+        s = self.lib.msfl_match_scan2map(self.h, _vp(corner), len(corner), _vp(surf), len(surf), _vp(pose), C.byref(info) if want_info else None,
+                                         MEM_HOST)
         self._check(s, "msfl_match_scan2map", allow)
         return s, pose, info
 
@@ -530,8 +550,7 @@ class Handle:
         B = len(poses)
         status = np.zeros(B, np.int32)
         info = (MatchInfo * B)() if want_info else None
-        s = self.lib.msfl_match_scan2map_batch(self.h, C.c_int(B), _vp(corner), _vp(co), _vp(surf), _vp(so), _vp(poses),
-                                               _vp(status), info, C.c_int(MEM_HOST))
+        s = self.lib.msfl_match_scan2map_batch(self.h, B, _vp(corner), _vp(co), _vp(surf), _vp(so), _vp(poses), _vp(status), info, MEM_HOST)
         self._check(s, "msfl_match_scan2map_batch")
         return poses, status, info
 
@@ -539,8 +558,8 @@ class Handle:
         """Device-resident batch (asynchronous on the handle's stream). Offsets are host arrays."""
         co = np.ascontiguousarray(corner_off, dtype=np.int32)
         so = np.ascontiguousarray(surf_off, dtype=np.int32)
-        s = self.lib.msfl_match_scan2map_batch(self.h, C.c_int(B), _vp(corner_ptr), _vp(co), _vp(surf_ptr), _vp(so),
-                                               _vp(poses_ptr), _vp(status_ptr), None, C.c_int(MEM_DEVICE))
+        s = self.lib.msfl_match_scan2map_batch(self.h, B, _vp(corner_ptr), _vp(co), _vp(surf_ptr), _vp(so), _vp(poses_ptr), _vp(status_ptr), None,
+                                               MEM_DEVICE)
         self._check(s, "msfl_match_scan2map_batch(device)")
 
     def match_scan2map_deskew_batch(self, corner, corner_off, surf, surf_off, corner_dq, corner_dp, surf_dq, surf_dp,
@@ -560,8 +579,8 @@ class Handle:
             keep = [corner_dq, corner_dp, surf_dq, surf_dp, velocity]
         d.corner_dq, d.corner_dp, d.surf_dq, d.surf_dp, d.velocity = (_vp(a).value for a in keep)
         d.gravity = (C.c_double * 3)(*[float(g) for g in gravity])
-        s = self.lib.msfl_match_scan2map_deskew_batch(self.h, C.c_int(B), _vp(corner), _vp(co), _vp(surf), _vp(so), C.byref(d),
-                                                      _vp(poses), _vp(status), None, C.c_int(mem))
+        s = self.lib.msfl_match_scan2map_deskew_batch(self.h, B, _vp(corner), _vp(co), _vp(surf), _vp(so), C.byref(d), _vp(poses), _vp(status), None,
+                                                      mem)
         self._check(s, "msfl_match_scan2map_deskew_batch")
         return poses, status
 
@@ -570,8 +589,8 @@ class Handle:
         corner, surf = _pts(corner), _pts(surf)
         rec = np.zeros((max(len(corner) + len(surf), 1), 6))
         pose = np.ascontiguousarray(pose, dtype=np.float64)
-        self._check(self.lib.msfl_associate_scan2map(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf),
-                                                     C.c_int(len(surf)), _vp(pose), _vp(rec)), "msfl_associate_scan2map")
+        self._check(self.lib.msfl_associate_scan2map(self.h, _vp(corner), len(corner), _vp(surf), len(surf), _vp(pose), _vp(rec)),
+                    "msfl_associate_scan2map")
         return rec[:len(corner) + len(surf)]
 
     def solve_records(self, corner, surf, records, pose):
@@ -579,8 +598,8 @@ class Handle:
         rec = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, 6)
         pose = np.array(pose, dtype=np.float64)
         info = MatchInfo()
-        self._check(self.lib.msfl_solve_records(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
-                                                _vp(rec), _vp(pose), C.byref(info)), "msfl_solve_records")
+        self._check(self.lib.msfl_solve_records(self.h, _vp(corner), len(corner), _vp(surf), len(surf), _vp(rec), _vp(pose), C.byref(info)),
+                    "msfl_solve_records")
         return pose, info
 
     def associate_scan2map_deskew(self, corner, surf, corner_dq, corner_dp, surf_dq, surf_dp, velocity, gravity, pose):
@@ -594,8 +613,8 @@ class Handle:
         n = len(corner) + len(surf)
         rec, pts = np.zeros((max(n, 1), 6)), np.zeros((max(n, 1), 3))
         pose = np.ascontiguousarray(pose, dtype=np.float64)
-        self._check(self.lib.msfl_associate_scan2map_deskew(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
-                                                            C.byref(d), _vp(pose), _vp(rec), _vp(pts)), "msfl_associate_scan2map_deskew")
+        self._check(self.lib.msfl_associate_scan2map_deskew(self.h, _vp(corner), len(corner), _vp(surf), len(surf), C.byref(d), _vp(pose), _vp(rec),
+                                                            _vp(pts)), "msfl_associate_scan2map_deskew")
         return rec[:n], pts[:n]
 
     def solve_records_deskew(self, corner, surf, records, points, pose):
@@ -609,8 +628,8 @@ class Handle:
             pts = np.zeros((1, 3))                                # (the entry wants a non-null pointer)
         pose = np.array(pose, dtype=np.float64)
         info = MatchInfo()
-        self._check(self.lib.msfl_solve_records_deskew(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
-                                                       _vp(rec), _vp(pts), _vp(pose), C.byref(info)), "msfl_solve_records_deskew")
+        self._check(self.lib.msfl_solve_records_deskew(self.h, _vp(corner), len(corner), _vp(surf), len(surf), _vp(rec), _vp(pts), _vp(pose),
+                                                       C.byref(info)), "msfl_solve_records_deskew")
         return pose, info
 
     def match_scan2map_deskew(self, corner, surf, corner_dq, corner_dp, surf_dq, surf_dp, velocity, gravity, pose):
@@ -622,8 +641,7 @@ class Handle:
         d.gravity = (C.c_double * 3)(*gravity)
         pose = np.array(pose, dtype=np.float64)
         info = MatchInfo()
-        s = self.lib.msfl_match_scan2map_deskew(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
-                                                C.byref(d), _vp(pose), C.byref(info))
+        s = self.lib.msfl_match_scan2map_deskew(self.h, _vp(corner), len(corner), _vp(surf), len(surf), C.byref(d), _vp(pose), C.byref(info))
         self._check(s, "msfl_match_scan2map_deskew")
         return s, pose, info
 
@@ -640,8 +658,8 @@ class Handle:
             clouds.append(rc)
         pose = np.array(pose, dtype=np.float64)
         info = MatchInfo()
-        s = self.lib.msfl_match_scan2scan(self.h, C.byref(clouds[0]), C.byref(clouds[1]), C.byref(clouds[2]),
-                                          C.byref(clouds[3]), _vp(pose), C.byref(info), C.c_int(MEM_HOST))
+        s = self.lib.msfl_match_scan2scan(self.h, C.byref(clouds[0]), C.byref(clouds[1]), C.byref(clouds[2]), C.byref(clouds[3]), _vp(pose),
+                                          C.byref(info), MEM_HOST)
         self._check(s, "msfl_match_scan2scan", allow)
         return s, pose, info
 
@@ -661,9 +679,8 @@ class Handle:
         B = len(poses)
         status = np.zeros(B, np.int32)
         info = (MatchInfo * B)() if want_info else None
-        s = self.lib.msfl_match_scan2scan_batch(self.h, C.c_int(B), C.byref(structs[0]), C.byref(structs[1]),
-                                                C.byref(structs[2]), C.byref(structs[3]), _vp(poses), _vp(status), info,
-                                                C.c_int(MEM_HOST))
+        s = self.lib.msfl_match_scan2scan_batch(self.h, B, C.byref(structs[0]), C.byref(structs[1]), C.byref(structs[2]), C.byref(structs[3]),
+                                                _vp(poses), _vp(status), info, MEM_HOST)
         self._check(s, "msfl_match_scan2scan_batch")
         return poses, status, info
 
@@ -679,7 +696,7 @@ class Handle:
         f.full_pts, f.full_ring, f.curvature, f.label = (out[k].ctypes.data for k in ("full", "ring", "curvature", "label"))
         f.sharp_idx, f.less_sharp_idx, f.flat_idx, f.less_flat_idx = (out[k].ctypes.data for k in ("sharp", "less_sharp", "flat", "less_flat"))
         ext = np.ascontiguousarray(extrinsic, dtype=np.float64) if extrinsic is not None else None
-        s = self.lib.msfl_extract_features(self.h, _vp(pts), _vp(ring), C.c_int(len(pts)), _vp(ext), C.byref(f), C.c_int(MEM_HOST))
+        s = self.lib.msfl_extract_features(self.h, _vp(pts), _vp(ring), len(pts), _vp(ext), C.byref(f), MEM_HOST)
         self._check(s, "msfl_extract_features", allow)
         nf = f.n_full
         return dict(rc=s, full=out["full"][:nf], ring=out["ring"][:nf], curvature=out["curvature"][:nf],
@@ -703,8 +720,7 @@ class Handle:
         f.sharp_idx, f.less_sharp_idx, f.flat_idx, f.less_flat_idx = (out[k].ctypes.data for k in ("sharp", "less_sharp", "flat", "less_flat"))
         f.n_full, f.n_sharp, f.n_less_sharp, f.n_flat, f.n_less_flat = (cnt[k].ctypes.data for k in ("n_full", "n_sharp", "n_less_sharp", "n_flat", "n_less_flat"))
         status = np.zeros(max(B, 1), np.int32)
-        s = self.lib.msfl_extract_features_batch(self.h, C.c_int(B), _vp(pts), _vp(ring), _vp(off), C.byref(f), _vp(status),
-                                                 C.c_int(MEM_HOST))
+        s = self.lib.msfl_extract_features_batch(self.h, B, _vp(pts), _vp(ring), _vp(off), C.byref(f), _vp(status), MEM_HOST)
         self._check(s, "msfl_extract_features_batch")
         res = []
         for b in range(B):
@@ -722,8 +738,7 @@ class Handle:
         pts = _pts(pts)
         out = np.zeros((max(len(pts), 1), 4), np.float32)
         n_out = C.c_int(0)
-        self._check(self.lib.msfl_voxel_downsample(self.h, _vp(pts), C.c_int(len(pts)), C.c_float(leaf), _vp(out),
-                                                   C.byref(n_out), C.c_int(MEM_HOST)), "msfl_voxel_downsample")
+        self._check(self.lib.msfl_voxel_downsample(self.h, _vp(pts), len(pts), leaf, _vp(out), C.byref(n_out), MEM_HOST), "msfl_voxel_downsample")
         return out[:n_out.value].copy()
 
     def voxel_downsample_batch(self, pts, off, leaf, idx=None, count=None):
@@ -735,9 +750,9 @@ class Handle:
         out_off = np.zeros(B + 1, np.int32)
         idx_a = None if idx is None else np.ascontiguousarray(idx, np.int32)
         cnt_a = None if count is None else np.ascontiguousarray(count, np.int32)
-        self._check(self.lib.msfl_voxel_downsample_batch(self.h, C.c_int(B), _vp(pts), _vp(idx_a) if idx_a is not None else None, _vp(off),
-                                                         _vp(cnt_a) if cnt_a is not None else None, C.c_float(leaf), _vp(out), _vp(out_off),
-                                                         C.c_int(MEM_HOST)), "msfl_voxel_downsample_batch")
+        self._check(self.lib.msfl_voxel_downsample_batch(self.h, B, _vp(pts), _vp(idx_a) if idx_a is not None else None, _vp(off),
+                                                         _vp(cnt_a) if cnt_a is not None else None, leaf, _vp(out), _vp(out_off), MEM_HOST),
+                    "msfl_voxel_downsample_batch")
         return out[:out_off[-1]].copy(), out_off
 
     def match_pairs_batch(self, map_corner, map_corner_off, map_surf, map_surf_off, corner, corner_off, surf, surf_off, poses, want_info=False):
@@ -748,8 +763,8 @@ class Handle:
         poses = np.ascontiguousarray(np.array(poses, np.float64).reshape(P, 7))
         status = np.zeros(P, np.int32)
         info = (MatchInfo * P)() if want_info else None
-        self._check(self.lib.msfl_match_pairs_batch(self.h, C.c_int(P), _vp(mc), _vp(offs[0]), _vp(ms), _vp(offs[1]), _vp(c), _vp(offs[2]),
-                                                    _vp(s_), _vp(offs[3]), _vp(poses), _vp(status), info, C.c_int(MEM_HOST)), "msfl_match_pairs_batch")
+        self._check(self.lib.msfl_match_pairs_batch(self.h, P, _vp(mc), _vp(offs[0]), _vp(ms), _vp(offs[1]), _vp(c), _vp(offs[2]), _vp(s_),
+                                                    _vp(offs[3]), _vp(poses), _vp(status), info, MEM_HOST), "msfl_match_pairs_batch")
         return poses, status, info
 
     def match_pairs_batch_device(self, P, d_map_corner, map_corner_off, d_map_surf, map_surf_off, d_corner, corner_off, d_surf, surf_off,
@@ -757,8 +772,8 @@ class Handle:
         """The same with device-resident clouds / poses / status (torch tensors or raw pointers) and host offset arrays; asynchronous."""
         offs = [np.ascontiguousarray(o, np.int32) for o in (map_corner_off, map_surf_off, corner_off, surf_off)]
         self._keep_offs = offs
-        self._check(self.lib.msfl_match_pairs_batch(self.h, C.c_int(P), _vp(d_map_corner), _vp(offs[0]), _vp(d_map_surf), _vp(offs[1]), _vp(d_corner),
-                                                    _vp(offs[2]), _vp(d_surf), _vp(offs[3]), _vp(d_poses), _vp(d_status), None, C.c_int(MEM_DEVICE)),
+        self._check(self.lib.msfl_match_pairs_batch(self.h, P, _vp(d_map_corner), _vp(offs[0]), _vp(d_map_surf), _vp(offs[1]), _vp(d_corner),
+                                                    _vp(offs[2]), _vp(d_surf), _vp(offs[3]), _vp(d_poses), _vp(d_status), None, MEM_DEVICE),
                     "msfl_match_pairs_batch(device)")
 
     # ---- resident pair maps (msfl_set_pair_maps, msfl_match_pairs_resident; msfl_score_pairs is with the pose scoring below) ----
@@ -767,14 +782,14 @@ class Handle:
         score_pairs and match_pairs_resident until set_map, the next set_pair_maps or the next match_pairs_batch."""
         mc, ms = _pts(map_corner), _pts(map_surf)
         offs = [np.ascontiguousarray(o, np.int32) for o in (map_corner_off, map_surf_off)]
-        self._check(self.lib.msfl_set_pair_maps(self.h, C.c_int(len(offs[0]) - 1), _vp(mc), _vp(offs[0]), _vp(ms), _vp(offs[1]), C.c_int(MEM_HOST)),
+        self._check(self.lib.msfl_set_pair_maps(self.h, len(offs[0]) - 1, _vp(mc), _vp(offs[0]), _vp(ms), _vp(offs[1]), MEM_HOST),
                     "msfl_set_pair_maps")
 
     def set_pair_maps_device(self, P, d_map_corner, map_corner_off, d_map_surf, map_surf_off):
         """The same with device-resident map clouds (torch tensors or raw pointers) and host offset arrays; asynchronous."""
         offs = [np.ascontiguousarray(o, np.int32) for o in (map_corner_off, map_surf_off)]
-        self._check(self.lib.msfl_set_pair_maps(self.h, C.c_int(int(P)), _vp(d_map_corner), _vp(offs[0]), _vp(d_map_surf), _vp(offs[1]),
-                                                C.c_int(MEM_DEVICE)), "msfl_set_pair_maps(device)")
+        self._check(self.lib.msfl_set_pair_maps(self.h, int(P), _vp(d_map_corner), _vp(offs[0]), _vp(d_map_surf), _vp(offs[1]), MEM_DEVICE),
+                    "msfl_set_pair_maps(device)")
 
     def match_pairs_resident(self, corner, corner_off, surf, surf_off, poses, want_info=False):
         """The registration half of match_pairs_batch against the resident pair index (host memory) -> (poses (P,7), status (P,),
@@ -785,30 +800,28 @@ class Handle:
         poses = np.ascontiguousarray(np.array(poses, np.float64).reshape(P, 7))
         status = np.zeros(P, np.int32)
         info = (MatchInfo * P)() if want_info else None
-        self._check(self.lib.msfl_match_pairs_resident(self.h, C.c_int(P), _vp(c), _vp(offs[0]), _vp(s_), _vp(offs[1]), _vp(poses), _vp(status), info,
-                                                       C.c_int(MEM_HOST)), "msfl_match_pairs_resident")
+        self._check(self.lib.msfl_match_pairs_resident(self.h, P, _vp(c), _vp(offs[0]), _vp(s_), _vp(offs[1]), _vp(poses), _vp(status), info,
+                                                       MEM_HOST), "msfl_match_pairs_resident")
         return poses, status, info
 
     def match_pairs_resident_device(self, P, d_corner, corner_off, d_surf, surf_off, d_poses, d_status):
         """The same with device-resident clouds / poses / status and host offset arrays; asynchronous."""
         offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off)]
-        self._check(self.lib.msfl_match_pairs_resident(self.h, C.c_int(int(P)), _vp(d_corner), _vp(offs[0]), _vp(d_surf), _vp(offs[1]), _vp(d_poses),
-                                                       _vp(d_status), None, C.c_int(MEM_DEVICE)), "msfl_match_pairs_resident(device)")
+        self._check(self.lib.msfl_match_pairs_resident(self.h, int(P), _vp(d_corner), _vp(offs[0]), _vp(d_surf), _vp(offs[1]), _vp(d_poses),
+                                                       _vp(d_status), None, MEM_DEVICE), "msfl_match_pairs_resident(device)")
 
     # ---- pose scoring (msfl_score_poses, msfl_score_pairs) ----
     def score_poses_device(self, corner, n_corner, surf, n_surf, poses, n_poses, max_dist, scores, d2_out=None, nn_out=None):
         """Device-pointer form (torch tensors / raw pointers), asynchronous on the handle's stream: `scores` holds n_poses records of
         POSE_SCORE_DTYPE.itemsize bytes, d2_out / nn_out (optional) n_poses x (n_corner + n_surf) float32 / int32."""
-        self._check(self.lib.msfl_score_poses(self.h, _vp(corner), C.c_int(int(n_corner)), _vp(surf), C.c_int(int(n_surf)), _vp(poses),
-                                              C.c_int(int(n_poses)), C.c_double(float(max_dist)), _vp(scores), _vp(d2_out), _vp(nn_out),
-                                              C.c_int(MEM_DEVICE)), "msfl_score_poses(device)")
+        self._check(self.lib.msfl_score_poses(self.h, _vp(corner), int(n_corner), _vp(surf), int(n_surf), _vp(poses), int(n_poses), max_dist,
+                                              _vp(scores), _vp(d2_out), _vp(nn_out), MEM_DEVICE), "msfl_score_poses(device)")
 
     def score_poses_batch_device(self, n_scans, corner, corner_off, surf, surf_off, poses, pose_off, max_dist, scores):
         """Device-pointer batch form, asynchronous; the three offset arrays are host arrays."""
         offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off, pose_off)]
-        self._check(self.lib.msfl_score_poses_batch(self.h, C.c_int(int(n_scans)), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses),
-                                                    _vp(offs[2]), C.c_double(float(max_dist)), _vp(scores), C.c_int(MEM_DEVICE)),
-                    "msfl_score_poses_batch(device)")
+        self._check(self.lib.msfl_score_poses_batch(self.h, int(n_scans), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses),
+                                                    _vp(offs[2]), max_dist, _vp(scores), MEM_DEVICE), "msfl_score_poses_batch(device)")
 
     def _device_scores(self, like, n):
         import torch
@@ -849,8 +862,8 @@ class Handle:
         rec = np.zeros(P, POSE_SCORE_DTYPE)
         d2 = np.zeros((P, F), np.float32) if want_nn else None
         nn = np.zeros((P, F), np.int32) if want_nn else None
-        self._check(self.lib.msfl_score_poses(self.h, _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)), _vp(poses), C.c_int(P),
-                                              C.c_double(float(max_dist)), _vp(rec), _vp(d2), _vp(nn), C.c_int(MEM_HOST)), "msfl_score_poses")
+        self._check(self.lib.msfl_score_poses(self.h, _vp(corner), len(corner), _vp(surf), len(surf), _vp(poses), P, max_dist, _vp(rec), _vp(d2),
+                                              _vp(nn), MEM_HOST), "msfl_score_poses")
         return (rec, d2, nn) if want_nn else rec
 
     def score_poses_batch(self, corner, corner_off, surf, surf_off, poses, pose_off, max_dist):
@@ -871,17 +884,16 @@ class Handle:
         corner, surf = _pts(corner), _pts(surf)
         poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
         rec = np.zeros(len(poses), POSE_SCORE_DTYPE)
-        self._check(self.lib.msfl_score_poses_batch(self.h, C.c_int(B), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]),
-                                                    C.c_double(float(max_dist)), _vp(rec), C.c_int(MEM_HOST)), "msfl_score_poses_batch")
+        self._check(self.lib.msfl_score_poses_batch(self.h, B, _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]), max_dist,
+                                                    _vp(rec), MEM_HOST), "msfl_score_poses_batch")
         return rec
 
     def score_pairs_device(self, n_pairs, corner, corner_off, surf, surf_off, poses, pose_off, max_dist, scores, d2_out=None, nn_out=None):
         """Device-pointer form of score_pairs, asynchronous; the three offset arrays are host arrays.  d2_out / nn_out (optional):
         sum over the pairs of poses x features float32 / int32, ragged rows in pose order."""
         offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off, pose_off)]
-        self._check(self.lib.msfl_score_pairs(self.h, C.c_int(int(n_pairs)), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses),
-                                              _vp(offs[2]), C.c_double(float(max_dist)), _vp(scores), _vp(d2_out), _vp(nn_out),
-                                              C.c_int(MEM_DEVICE)), "msfl_score_pairs(device)")
+        self._check(self.lib.msfl_score_pairs(self.h, int(n_pairs), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]),
+                                              max_dist, _vp(scores), _vp(d2_out), _vp(nn_out), MEM_DEVICE), "msfl_score_pairs(device)")
 
     def score_pairs(self, corner, corner_off, surf, surf_off, poses, pose_off, max_dist, want_nn=False):
         """score_poses_batch against the resident PAIR index (set_pair_maps, or what match_pairs_batch left): scan p at the poses
@@ -910,8 +922,8 @@ class Handle:
         rec = np.zeros(len(poses), POSE_SCORE_DTYPE)
         d2 = np.zeros(n_out, np.float32) if want_nn else None
         nn = np.zeros(n_out, np.int32) if want_nn else None
-        self._check(self.lib.msfl_score_pairs(self.h, C.c_int(B), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]),
-                                              C.c_double(float(max_dist)), _vp(rec), _vp(d2), _vp(nn), C.c_int(MEM_HOST)), "msfl_score_pairs")
+        self._check(self.lib.msfl_score_pairs(self.h, B, _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]), max_dist,
+                                              _vp(rec), _vp(d2), _vp(nn), MEM_HOST), "msfl_score_pairs")
         return (rec, d2, nn) if want_nn else rec
 
     def transform_cloud(self, pts, pose7):
@@ -919,8 +931,7 @@ class Handle:
         pts = _pts(pts)
         pose7 = np.ascontiguousarray(pose7, np.float64)
         out = np.zeros_like(pts)
-        self._check(self.lib.msfl_transform_cloud(self.h, _vp(pts), C.c_int(len(pts)), _vp(pose7), _vp(out), C.c_int(MEM_HOST)),
-                    "msfl_transform_cloud")
+        self._check(self.lib.msfl_transform_cloud(self.h, _vp(pts), len(pts), _vp(pose7), _vp(out), MEM_HOST), "msfl_transform_cloud")
         return out
 
     @staticmethod
@@ -936,7 +947,7 @@ class Handle:
         pts = _pts(pts)
         pre, keep = self._preintegration(sum_dt, delta_q, delta_p)
         dq, dp = np.zeros((len(pts), 4)), np.zeros((len(pts), 3))
-        s = self.lib.msfl_delta_qp(self.h, C.byref(pre), _vp(pts), C.c_int(len(pts)), _vp(dq), _vp(dp), C.c_int(MEM_HOST))
+        s = self.lib.msfl_delta_qp(self.h, C.byref(pre), _vp(pts), len(pts), _vp(dq), _vp(dp), MEM_HOST)
         return s, dq, dp
 
     def deskew_cloud(self, sum_dt, delta_q, delta_p, pts, rot_odom_xyzw, velocity, gravity):
@@ -944,49 +955,34 @@ class Handle:
         pts = _pts(pts).copy()
         pre, keep = self._preintegration(sum_dt, delta_q, delta_p)
         r, v, g = (np.ascontiguousarray(a, np.float64) for a in (rot_odom_xyzw, velocity, gravity))
-        s = self.lib.msfl_deskew_cloud(self.h, C.byref(pre), _vp(pts), C.c_int(len(pts)), _vp(r), _vp(v), _vp(g), C.c_int(MEM_HOST))
+        s = self.lib.msfl_deskew_cloud(self.h, C.byref(pre), _vp(pts), len(pts), _vp(r), _vp(v), _vp(g), MEM_HOST)
         return s, pts
 
     def undistort_cloud(self, sum_dt, delta_q, delta_p, pts):
         """UndistortScanInternal (scan_undistortion.cc:5-19) -> (status, points)."""
         pts = _pts(pts).copy()
         pre, keep = self._preintegration(sum_dt, delta_q, delta_p)
-        s = self.lib.msfl_undistort_cloud(self.h, C.byref(pre), _vp(pts), C.c_int(len(pts)), C.c_int(MEM_HOST))
+        s = self.lib.msfl_undistort_cloud(self.h, C.byref(pre), _vp(pts), len(pts), MEM_HOST)
         return s, pts
 
 
-class Grid:
+class Grid(_Owner):
     """Device-resident local map store (HybridGrid): msfl_grid_* over a Handle's stream."""
+    _PTR, _DESTROY = "g", "msfl_grid_destroy"
 
     def __init__(self, handle, resolution=3.0, leaf=0.2):
         self.handle = handle
-        self.lib = handle.lib
         self.resolution, self.leaf = float(resolution), float(leaf)          # what the store was created with (mapio.save_grid)
-        self.g = C.c_void_p()
-        handle._check(self.lib.msfl_grid_create(handle.h, C.c_float(resolution), C.c_float(leaf), C.byref(self.g)), "msfl_grid_create")
-        if not hasattr(handle, "_grids"):
-            handle._grids = weakref.WeakSet()
-        handle._grids.add(self)                                     # Handle.close() closes the grids that are still open first
-
-    def close(self):
-        if self.g:
-            self.lib.msfl_grid_destroy(self.g)
-            self.g = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check(handle.lib.msfl_grid_create(handle.h, resolution, leaf, self._own(handle.lib)), "msfl_grid_create")
+        handle._dependents.add(self)                                # Handle.close() closes the grids that are still open first
 
     def insert_scan(self, pts, allow=()):
         pts = _pts(pts)
-        return self.handle._check(self.lib.msfl_grid_insert_scan(self.g, _vp(pts), C.c_int(len(pts)), C.c_int(MEM_HOST)),
-                                  "msfl_grid_insert_scan", allow)
+        return self._check(self.lib.msfl_grid_insert_scan(self.g, _vp(pts), len(pts), MEM_HOST), "msfl_grid_insert_scan", allow)
 
     def size(self):
         a, b = C.c_int(0), C.c_int(0)
-        self.handle._check(self.lib.msfl_grid_size(self.g, C.byref(a), C.byref(b)), "msfl_grid_size")
+        self._check(self.lib.msfl_grid_size(self.g, C.byref(a), C.byref(b)), "msfl_grid_size")
         return a.value, b.value
 
     def get_surrounded(self, scan, pose):
@@ -995,23 +991,23 @@ class Grid:
         out = np.zeros((cap, 4), np.float32)
         n_out = C.c_int(0)
         pose = np.ascontiguousarray(pose, dtype=np.float64)
-        self.handle._check(self.lib.msfl_grid_get_surrounded(self.g, _vp(scan), C.c_int(len(scan)), _vp(pose), _vp(out), C.c_int(cap),
-                                                             C.byref(n_out), C.c_int(MEM_HOST)), "msfl_grid_get_surrounded")
+        self._check(self.lib.msfl_grid_get_surrounded(self.g, _vp(scan), len(scan), _vp(pose), _vp(out), cap, C.byref(n_out), MEM_HOST),
+                    "msfl_grid_get_surrounded")
         return out[:n_out.value].copy()
 
     def get_surrounded_device(self, scan_ptr, n, pose, out_ptr, capacity):
         """Device-resident variant: returns the number of points written at out_ptr."""
         n_out = C.c_int(0)
         pose = np.ascontiguousarray(pose, dtype=np.float64)
-        self.handle._check(self.lib.msfl_grid_get_surrounded(self.g, _vp(scan_ptr), C.c_int(n), _vp(pose), _vp(out_ptr), C.c_int(capacity),
-                                                             C.byref(n_out), C.c_int(MEM_DEVICE)), "msfl_grid_get_surrounded(device)")
+        self._check(self.lib.msfl_grid_get_surrounded(self.g, _vp(scan_ptr), n, _vp(pose), _vp(out_ptr), capacity, C.byref(n_out), MEM_DEVICE),
+                    "msfl_grid_get_surrounded(device)")
         return n_out.value
 
     def dump(self):
         cap = max(self.size()[0], 1)
         out = np.zeros((cap, 4), np.float32)
         n_out = C.c_int(0)
-        self.handle._check(self.lib.msfl_grid_dump(self.g, _vp(out), C.c_int(cap), C.byref(n_out), C.c_int(MEM_HOST)), "msfl_grid_dump")
+        self._check(self.lib.msfl_grid_dump(self.g, _vp(out), cap, C.byref(n_out), MEM_HOST), "msfl_grid_dump")
         return out[:n_out.value].copy()
 
     def dump_cells(self):
@@ -1019,13 +1015,13 @@ class Grid:
         cap = max(self.size()[1], 1)
         out = np.zeros((cap, 4), np.int32)
         n_out = C.c_int(0)
-        self.handle._check(self.lib.msfl_grid_dump_cells(self.g, _vp(out), C.c_int(cap), C.byref(n_out)), "msfl_grid_dump_cells")
+        self._check(self.lib.msfl_grid_dump_cells(self.g, _vp(out), cap, C.byref(n_out)), "msfl_grid_dump_cells")
         return out[:n_out.value].copy()
 
     def stats(self):
         """dict of msfl_grid_stats: n_points, n_cells, pool_top, pool_capacity_points, cell_capacity, device_bytes."""
         out = (C.c_longlong * 6)()
-        self.handle._check(self.lib.msfl_grid_stats(self.g, out), "msfl_grid_stats")
+        self._check(self.lib.msfl_grid_stats(self.g, out), "msfl_grid_stats")
         return dict(zip(GRID_STATS, (int(v) for v in out)))
 
     def crop(self, center, half_cells, keep_evicted=False, capacity=None, allow=()):
@@ -1039,8 +1035,7 @@ class Grid:
         if keep_evicted:
             cap = self.size()[0] if capacity is None else int(capacity)
             ev = np.zeros((max(cap, 1), 4), np.float32)
-        info.status = self.handle._check(self.lib.msfl_grid_crop(self.g, center, half, _vp(ev), C.c_int(cap), C.c_int(MEM_HOST), C.byref(info)),
-                                         "msfl_grid_crop", allow)
+        info.status = self._check(self.lib.msfl_grid_crop(self.g, center, half, _vp(ev), cap, MEM_HOST, C.byref(info)), "msfl_grid_crop", allow)
         if not keep_evicted:
             return info
         return info, ev[:info.n_points_evicted if info.applied else 0].copy()
@@ -1050,8 +1045,8 @@ class Grid:
         center = (C.c_double * 3)(*[float(v) for v in center])
         half = (C.c_int * 3)(*[int(v) for v in half_cells])
         info = GridCropInfo()
-        info.status = self.handle._check(self.lib.msfl_grid_crop(self.g, center, half, _vp(evicted_ptr), C.c_int(int(capacity)), C.c_int(MEM_DEVICE),
-                                                                 C.byref(info)), "msfl_grid_crop(device)", allow)
+        info.status = self._check(self.lib.msfl_grid_crop(self.g, center, half, _vp(evicted_ptr), int(capacity), MEM_DEVICE, C.byref(info)),
+                                  "msfl_grid_crop(device)", allow)
         return info
 
     def crop_tiles(self, center, half_cells, capacity=None, cell_capacity=None, allow=()):
@@ -1065,8 +1060,8 @@ class Grid:
         cap = n_pts if capacity is None else int(capacity)
         ccap = n_cells if cell_capacity is None else int(cell_capacity)
         ev, cells = np.zeros((max(cap, 1), 4), np.float32), np.zeros((max(ccap, 1), 4), np.int32)
-        info.status = self.handle._check(self.lib.msfl_grid_crop_tiles(self.g, center, half, _vp(ev), C.c_int(cap), _vp(cells), C.c_int(ccap),
-                                                                       C.c_int(MEM_HOST), C.byref(info)), "msfl_grid_crop_tiles", allow)
+        info.status = self._check(self.lib.msfl_grid_crop_tiles(self.g, center, half, _vp(ev), cap, _vp(cells), ccap, MEM_HOST, C.byref(info)),
+                                  "msfl_grid_crop_tiles", allow)
         ok = info.applied and info.status == OK
         return info, cells[:info.n_cells_evicted if ok else 0].copy(), ev[:info.n_points_evicted if ok else 0].copy()
 
@@ -1074,8 +1069,8 @@ class Grid:
         cells = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 4))
         info = GridLoadInfo()
         conflict = np.zeros(max(len(cells), 1), np.int32) if want_conflicts else None
-        info.status = self.handle._check(self.lib.msfl_grid_load_cells(self.g, _vp(cells), C.c_int(len(cells)), pts_ptr, C.c_int(int(n_points)),
-                                                                       C.c_int(mem), _vp(conflict), C.byref(info)), what, allow)
+        info.status = self._check(self.lib.msfl_grid_load_cells(self.g, _vp(cells), len(cells), pts_ptr, int(n_points), mem, _vp(conflict),
+                                                                C.byref(info)), what, allow)
         return (info, conflict[:len(cells)]) if want_conflicts else info
 
     def load_cells(self, cells, pts, allow=(), want_conflicts=False):
@@ -1094,14 +1089,9 @@ class _BorrowedGrid(Grid):
     """A map store owned by a Slam pipeline (never destroyed from here)."""
 
     def __init__(self, lib, g, err, resolution=None, leaf=None):
-        self.lib, self.g, self._err = lib, g, err
+        self.lib, self.g, self.last_error = lib, g, err             # err: the owning pipeline's last_error
         self.resolution, self.leaf = resolution, leaf
         self.handle = self
-
-    def _check(self, status, what, allow=()):
-        if status != OK and status not in allow:
-            raise MsflError(status, what, self._err())
-        return status
 
     def close(self):
         self.g = C.c_void_p()
@@ -1112,37 +1102,23 @@ class KeyframesConfig(C.Structure):
                 ("leaf_surf", C.c_float)]
 
 
-class Keyframes:
+class Keyframes(_Owner):
     """Device-resident keyframe store (msfl_keyframes_*) over a Handle's stream: the scans' corner / surf lists, laid down at any
     poses as submaps (compose) or into map stores (insert).  Keyword arguments are the fields of msfl_keyframes_config
     (max_keyframes, max_corner_points, max_surf_points, leaf_corner, leaf_surf)."""
+    _PTR, _DESTROY = "k", "msfl_keyframes_destroy"
 
     def __init__(self, handle, **cfg):
         self.handle = handle
-        self.lib = handle.lib
-        self.lib.msfl_keyframes_size.argtypes = [C.c_void_p]
+        ref = self._own(handle.lib)
         self.config = KeyframesConfig()
         self.lib.msfl_keyframes_default_config(C.byref(self.config))
         for k, v in cfg.items():
             if k not in dict(KeyframesConfig._fields_):
                 raise TypeError("unknown msfl_keyframes_config field %r" % (k,))
             setattr(self.config, k, v)
-        self.k = C.c_void_p()
-        handle._check(self.lib.msfl_keyframes_create(handle.h, C.byref(self.config), C.byref(self.k)), "msfl_keyframes_create")
-        if not hasattr(handle, "_grids"):
-            handle._grids = weakref.WeakSet()
-        handle._grids.add(self)                                     # Handle.close() closes what must go before the handle
-
-    def close(self):
-        if self.k:
-            self.lib.msfl_keyframes_destroy(self.k)
-            self.k = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check(self.lib.msfl_keyframes_create(handle.h, C.byref(self.config), ref), "msfl_keyframes_create")
+        handle._dependents.add(self)                                # Handle.close() closes what must go before the handle
 
     def size(self):
         return int(self.lib.msfl_keyframes_size(self.k))
@@ -1156,8 +1132,8 @@ class Keyframes:
 
     def _add(self, corner, corner_idx, n_corner, surf, surf_idx, n_surf, mem, allow, what):
         index = C.c_int(-1)
-        s = self.handle._check(self.lib.msfl_keyframes_add(self.k, _vp(corner), _vp(corner_idx), C.c_int(int(n_corner)), _vp(surf), _vp(surf_idx),
-                                                           C.c_int(int(n_surf)), C.c_int(mem), C.byref(index)), what, allow)
+        s = self._check(self.lib.msfl_keyframes_add(self.k, _vp(corner), _vp(corner_idx), int(n_corner), _vp(surf), _vp(surf_idx), int(n_surf), mem,
+                                                    C.byref(index)), what, allow)
         return index.value if s == OK else s
 
     def add(self, corner, surf, corner_idx=None, surf_idx=None, allow=()):
@@ -1176,20 +1152,19 @@ class Keyframes:
         """-> (n_corner, n_surf) int32 arrays of keyframes [first, first + n): host bookkeeping, no device call."""
         n = self.size() - first if n is None else int(n)
         nc, ns = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int32)
-        self.handle._check(self.lib.msfl_keyframes_sizes(self.k, C.c_int(int(first)), C.c_int(n), _vp(nc), _vp(ns)), "msfl_keyframes_sizes")
+        self._check(self.lib.msfl_keyframes_sizes(self.k, int(first), n, _vp(nc), _vp(ns)), "msfl_keyframes_sizes")
         return nc, ns
 
     def get(self, index):
         """-> (corner, surf) of one keyframe as stored."""
         nc, ns = self.sizes(index, 1)
         corner, surf = np.zeros((int(nc[0]), 4), np.float32), np.zeros((int(ns[0]), 4), np.float32)
-        self.handle._check(self.lib.msfl_keyframes_get(self.k, C.c_int(int(index)), _vp(corner), C.c_int(len(corner)), _vp(surf), C.c_int(len(surf)),
-                                                       C.c_int(MEM_HOST)), "msfl_keyframes_get")
+        self._check(self.lib.msfl_keyframes_get(self.k, int(index), _vp(corner), len(corner), _vp(surf), len(surf), MEM_HOST), "msfl_keyframes_get")
         return corner, surf
 
     def get_device(self, index, corner, cap_corner, surf, cap_surf):
-        self.handle._check(self.lib.msfl_keyframes_get(self.k, C.c_int(int(index)), _vp(corner), C.c_int(int(cap_corner)), _vp(surf),
-                                                       C.c_int(int(cap_surf)), C.c_int(MEM_DEVICE)), "msfl_keyframes_get(device)")
+        self._check(self.lib.msfl_keyframes_get(self.k, int(index), _vp(corner), int(cap_corner), _vp(surf), int(cap_surf), MEM_DEVICE),
+                    "msfl_keyframes_get(device)")
 
     @staticmethod
     def _members(member_off, keys, poses):
@@ -1207,9 +1182,8 @@ class Keyframes:
     def _compose(self, member_off, keys, poses, leaf_corner, leaf_surf, out_corner, cap_corner, out_surf, cap_surf, mem, allow, what):
         B = len(member_off) - 1
         off_c, off_s = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32)
-        s = self.handle._check(self.lib.msfl_keyframes_compose(self.k, C.c_int(B), _vp(member_off), _vp(keys), _vp(poses), C.c_float(leaf_corner),
-                                                               C.c_float(leaf_surf), _vp(out_corner), C.c_int(int(cap_corner)), _vp(off_c),
-                                                               _vp(out_surf), C.c_int(int(cap_surf)), _vp(off_s), C.c_int(mem)), what, allow)
+        s = self._check(self.lib.msfl_keyframes_compose(self.k, B, _vp(member_off), _vp(keys), _vp(poses), leaf_corner, leaf_surf, _vp(out_corner),
+                                                        int(cap_corner), _vp(off_c), _vp(out_surf), int(cap_surf), _vp(off_s), mem), what, allow)
         return s, off_c, off_s
 
     def compose(self, member_off, keys, poses, leaf_corner=0.0, leaf_surf=0.0, allow=(), out_corner=None, out_surf=None, cap_corner=None,
@@ -1245,20 +1219,18 @@ class Keyframes:
         keys = np.ascontiguousarray(keys, np.int32)
         poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
         n_done = C.c_int(0)
-        s = self.handle._check(self.lib.msfl_keyframes_insert(self.k, _vp(keys), _vp(poses), C.c_int(len(keys)),
-                                                              grid_corner.g if grid_corner is not None else None,
-                                                              grid_surf.g if grid_surf is not None else None, C.byref(n_done)),
-                               "msfl_keyframes_insert", allow)
+        s = self._check(self.lib.msfl_keyframes_insert(self.k, _vp(keys), _vp(poses), len(keys), grid_corner.g if grid_corner is not None else None,
+                                                       grid_surf.g if grid_surf is not None else None, C.byref(n_done)), "msfl_keyframes_insert",
+                        allow)
         return s, n_done.value
 
 
-class Slam:
+class Slam(_Owner):
     """Device-resident per-scan SLAM step (msfl_slam_*): raw scan in, poses out, everything in between stays in HBM."""
+    _PTR, _DESTROY, _ERROR = "s", "msfl_slam_destroy", "msfl_slam_last_error"
 
     def __init__(self, device=0, max_scan_points=28800, max_rings=16, pose_odom2map=None, params=None, **cfg):
-        self.lib = load()
-        self.lib.msfl_slam_last_error.restype = C.c_char_p
-        self.lib.msfl_slam_last_error.argtypes = [C.c_void_p]
+        ref = self._own(load())
         c = SlamConfig()
         self.lib.msfl_slam_default_config(C.byref(c))
         c.max_scan_points, c.max_rings = int(max_scan_points), int(max_rings)
@@ -1269,25 +1241,10 @@ class Slam:
         for k, v in cfg.items():
             setattr(c, k, v)
         self._grid_shape = (float(c.map_resolution), float(c.leaf_corner), float(c.leaf_surf))
-        self.s = C.c_void_p()
-        st = self.lib.msfl_slam_create(C.byref(params) if params is not None else None, C.byref(c), C.c_int(device), C.byref(self.s))
+        st = self.lib.msfl_slam_create(C.byref(params) if params is not None else None, C.byref(c), device, ref)
         if st != OK:
             raise MsflError(st, "msfl_slam_create", "no GPU / HIP runtime available (there is no CPU fallback)" if st == HIP_ERROR else "")
         self.n_scans = 0
-
-    def _err(self):
-        return (self.lib.msfl_slam_last_error(self.s) or b"").decode()
-
-    def close(self):
-        if self.s:
-            self.lib.msfl_slam_destroy(self.s)
-            self.s = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @staticmethod
     def make_imu(sum_dt, delta_q, delta_p, is_initialized=False, velocity=(0, 0, 0), gravity=(0, 0, 0), presolved_pose=None):
@@ -1313,100 +1270,76 @@ class Slam:
         ring = np.ascontiguousarray(ring, dtype=np.uint16)
         r = SlamResult() if wait else None
         if imu is None:
-            st = self.lib.msfl_slam_add_scan(self.s, _vp(pts), _vp(ring), C.c_int(len(pts)), C.c_int(MEM_HOST), C.byref(r) if wait else None)
+            st = self.lib.msfl_slam_add_scan(self.s, _vp(pts), _vp(ring), len(pts), MEM_HOST, C.byref(r) if wait else None)
         else:
             im, keep = self.make_imu(**imu)
-            st = self.lib.msfl_slam_add_scan_imu(self.s, _vp(pts), _vp(ring), C.c_int(len(pts)), C.c_int(MEM_HOST), C.byref(im),
-                                                 C.byref(r) if wait else None)
+            st = self.lib.msfl_slam_add_scan_imu(self.s, _vp(pts), _vp(ring), len(pts), MEM_HOST, C.byref(im), C.byref(r) if wait else None)
             del keep
-        if st != OK:
-            raise MsflError(st, "msfl_slam_add_scan", self._err())
+        self._check(st, "msfl_slam_add_scan")
         self.n_scans += 1
         return r
 
     def add_scan_device(self, pts_ptr, ring_ptr, n, wait=True):
         r = SlamResult() if wait else None
-        st = self.lib.msfl_slam_add_scan(self.s, _vp(pts_ptr), _vp(ring_ptr), C.c_int(int(n)), C.c_int(MEM_DEVICE), C.byref(r) if wait else None)
-        if st != OK:
-            raise MsflError(st, "msfl_slam_add_scan(device)", self._err())
+        self._check(self.lib.msfl_slam_add_scan(self.s, _vp(pts_ptr), _vp(ring_ptr), int(n), MEM_DEVICE, C.byref(r) if wait else None),
+                    "msfl_slam_add_scan(device)")
         self.n_scans += 1
         return r
 
     def result(self, scan_index):
         r = SlamResult()
-        st = self.lib.msfl_slam_get_result(self.s, C.c_int(int(scan_index)), C.byref(r))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_get_result", self._err())
+        self._check(self.lib.msfl_slam_get_result(self.s, int(scan_index), C.byref(r)), "msfl_slam_get_result")
         return r
 
     def set_uncertainty(self, enabled=True, min_eigenvalue=0.0):
-        st = self.lib.msfl_slam_set_uncertainty(self.s, C.c_int(1 if enabled else 0), C.c_double(float(min_eigenvalue)))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_set_uncertainty", self._err())
+        self._check(self.lib.msfl_slam_set_uncertainty(self.s, 1 if enabled else 0, min_eigenvalue), "msfl_slam_set_uncertainty")
 
     def set_degeneracy(self, odometry=None, mapping=None):
         """Degeneracy-aware solve of every scan fed from now on: `odometry` / `mapping` is the eigenvalue threshold of that matcher,
         None leaves it off."""
-        st = self.lib.msfl_slam_set_degeneracy(self.s, C.c_int(odometry is not None), C.c_int(mapping is not None),
-                                               C.c_double(0.0 if odometry is None else float(odometry)),
-                                               C.c_double(0.0 if mapping is None else float(mapping)))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_set_degeneracy", self._err())
+        self._check(self.lib.msfl_slam_set_degeneracy(self.s, odometry is not None, mapping is not None, odometry or 0.0, mapping or 0.0),
+                    "msfl_slam_set_degeneracy")
 
     def set_outlier_rejection(self, odometry=None, mapping=None):
         """Outlier rejection of every scan fed from now on: `odometry` / `mapping` is that matcher's OutlierRejection
         (capi.outlier_rejection(...)), None leaves it off."""
-        st = self.lib.msfl_slam_set_outlier_rejection(self.s, None if odometry is None else C.byref(odometry),
-                                                      None if mapping is None else C.byref(mapping))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_set_outlier_rejection", self._err())
+        self._check(self.lib.msfl_slam_set_outlier_rejection(self.s, None if odometry is None else C.byref(odometry),
+                                                             None if mapping is None else C.byref(mapping)), "msfl_slam_set_outlier_rejection")
 
     def get_rejection(self, scan_index):
         """(odometry, mapping) records of REJECTION_DTYPE of one of the last four scans fed (waits for it)."""
         out = np.zeros(2, REJECTION_DTYPE)
-        st = self.lib.msfl_slam_get_rejection(self.s, C.c_int(int(scan_index)), C.c_void_p(out[0:1].ctypes.data), C.c_void_p(out[1:2].ctypes.data))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_get_rejection", self._err())
+        self._check(self.lib.msfl_slam_get_rejection(self.s, int(scan_index), _vp(out[0:1]), _vp(out[1:2])), "msfl_slam_get_rejection")
         return out[0], out[1]
 
     def get_degeneracy(self, scan_index):
         """(odometry, mapping) records of DEGENERACY_DTYPE of one of the last four scans fed (waits for it)."""
         out = np.zeros(2, DEGENERACY_DTYPE)
-        st = self.lib.msfl_slam_get_degeneracy(self.s, C.c_int(int(scan_index)), C.c_void_p(out[0:1].ctypes.data), C.c_void_p(out[1:2].ctypes.data))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_get_degeneracy", self._err())
+        self._check(self.lib.msfl_slam_get_degeneracy(self.s, int(scan_index), _vp(out[0:1]), _vp(out[1:2])), "msfl_slam_get_degeneracy")
         return out[0], out[1]
 
     def set_next_prior(self, odometry=None, mapping=None):
         """Pose priors for the NEXT add_scan only: each a (pose7, sqrt_information 6 x 6) pair or None.  `odometry` joins that scan's
         scan-to-scan solve (relative pose), `mapping` its scan-to-map solve (world pose)."""
         rec = [None if p is None else pose_priors(p[0], [p[1]]) for p in (odometry, mapping)]
-        st = self.lib.msfl_slam_set_next_prior(self.s, _vp(rec[0]), _vp(rec[1]))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_set_next_prior", self._err())
+        self._check(self.lib.msfl_slam_set_next_prior(self.s, _vp(rec[0]), _vp(rec[1])), "msfl_slam_set_next_prior")
 
     def get_uncertainty(self, scan_index):
         """(odometry, mapping) records of one of the last four scans fed: a numpy structured array of two UNCERTAINTY_DTYPE records."""
         out = np.zeros(2, UNCERTAINTY_DTYPE)
-        st = self.lib.msfl_slam_get_uncertainty(self.s, C.c_int(int(scan_index)), C.c_void_p(out[0:1].ctypes.data), C.c_void_p(out[1:2].ctypes.data))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_get_uncertainty", self._err())
+        self._check(self.lib.msfl_slam_get_uncertainty(self.s, int(scan_index), _vp(out[0:1]), _vp(out[1:2])), "msfl_slam_get_uncertainty")
         return out
 
     def set_map_window(self, half_cells, every_n_scans=1):
         """Crop both map stores to +-half_cells cells around pose_map after the inserts of every every_n_scans-th scan fed from
         now on (msfl_slam_set_map_window); half_cells=None turns the window off."""
         half = None if half_cells is None else (C.c_int * 3)(*[int(v) for v in half_cells])
-        st = self.lib.msfl_slam_set_map_window(self.s, half, C.c_int(int(every_n_scans)))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_set_map_window", self._err())
+        self._check(self.lib.msfl_slam_set_map_window(self.s, half, int(every_n_scans)), "msfl_slam_set_map_window")
 
     def get_map_window(self, scan_index):
         """(corner, surf) GridCropInfo of one of the last four scans fed; all zero where no crop ran."""
         a, b = GridCropInfo(), GridCropInfo()
-        st = self.lib.msfl_slam_get_map_window(self.s, C.c_int(int(scan_index)), C.byref(a), C.byref(b))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_get_map_window", self._err())
+        self._check(self.lib.msfl_slam_get_map_window(self.s, int(scan_index), C.byref(a), C.byref(b)), "msfl_slam_get_map_window")
         return a, b
 
     def clouds(self, scan_index):
@@ -1419,62 +1352,39 @@ class Slam:
         c = SlamClouds()
         c.full_scan, c.full_map, c.ring = full_scan.ctypes.data, full_map.ctypes.data, ring.ctypes.data
         c.sharp_idx, c.less_sharp_idx, c.flat_idx, c.less_flat_idx = (a.ctypes.data for a in idx)
-        st = self.lib.msfl_slam_get_clouds(self.s, C.c_int(int(scan_index)), C.byref(c), C.c_int(MEM_HOST))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_get_clouds", self._err())
+        self._check(self.lib.msfl_slam_get_clouds(self.s, int(scan_index), C.byref(c), MEM_HOST), "msfl_slam_get_clouds")
         return dict(full_scan=full_scan[:c.n_full], full_map=full_map[:c.n_full], ring=ring[:c.n_full], sharp=idx[0][:c.n_sharp],
                     less_sharp=idx[1][:c.n_less_sharp], flat=idx[2][:c.n_flat], less_flat=idx[3][:c.n_less_flat])
 
     def grids(self):
         a, b = C.c_void_p(), C.c_void_p()
-        st = self.lib.msfl_slam_grids(self.s, C.byref(a), C.byref(b))
-        if st != OK:
-            raise MsflError(st, "msfl_slam_grids", self._err())
+        self._check(self.lib.msfl_slam_grids(self.s, C.byref(a), C.byref(b)), "msfl_slam_grids")
         res, leaf_c, leaf_s = self._grid_shape
-        return _BorrowedGrid(self.lib, a, self._err, res, leaf_c), _BorrowedGrid(self.lib, b, self._err, res, leaf_s)
+        return _BorrowedGrid(self.lib, a, self.last_error, res, leaf_c), _BorrowedGrid(self.lib, b, self.last_error, res, leaf_s)
 
 
-class Places:
+class Places(_Owner):
     """Owns one msfl_places: a device-resident database of polar scan descriptors (msfl_places_*), independent of any Handle.
     Keyword arguments are the fields of msfl_place_config (n_ring, n_sector, min_range, max_range, height_offset, capacity)."""
+    _PTR, _DESTROY, _ERROR = "p", "msfl_places_destroy", "msfl_places_last_error"
 
     def __init__(self, device=0, **cfg):
-        self.lib = load()
-        self.lib.msfl_places_last_error.restype = C.c_char_p
-        self.lib.msfl_places_last_error.argtypes = [C.c_void_p]
-        self.lib.msfl_places_size.argtypes = [C.c_void_p]
+        ref = self._own(load())
         self.config = PlaceConfig()
         self.lib.msfl_places_default_config(C.byref(self.config))
         for k, v in cfg.items():
             if k not in dict(PlaceConfig._fields_):
                 raise TypeError("unknown msfl_place_config field %r" % (k,))
             setattr(self.config, k, v)
-        self.p = C.c_void_p()
-        s = self.lib.msfl_places_create(C.byref(self.config), C.c_int(device), C.byref(self.p))
+        s = self.lib.msfl_places_create(C.byref(self.config), device, ref)
         if s != OK:
             raise MsflError(s, "msfl_places_create", "(a config outside its limits, or no GPU: there is no CPU fallback)")
 
     n_ring = property(lambda self: self.config.n_ring)
     n_sector = property(lambda self: self.config.n_sector)
 
-    def close(self):
-        if self.p:
-            self.lib.msfl_places_destroy(self.p)
-            self.p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, s, what, allow=()):
-        if s != OK and s not in allow:
-            raise MsflError(s, what, (self.lib.msfl_places_last_error(self.p) or b"").decode())
-        return s
-
     def set_stream(self, stream_ptr):
-        self._check(self.lib.msfl_places_set_stream(self.p, C.c_void_p(stream_ptr)), "msfl_places_set_stream")
+        self._check(self.lib.msfl_places_set_stream(self.p, stream_ptr), "msfl_places_set_stream")
 
     def synchronize(self):
         self._check(self.lib.msfl_places_synchronize(self.p), "msfl_places_synchronize")
@@ -1504,16 +1414,15 @@ class Places:
         index of the first new entry (or the refusing status when it is in `allow`)."""
         pts, off = self._scans(scans, off)
         first = C.c_int(-1)
-        s = self._check(self.lib.msfl_places_add(self.p, _vp(pts), _vp(off), C.c_int(len(off) - 1), C.c_int(MEM_HOST), C.byref(first)),
-                        "msfl_places_add", allow)
+        s = self._check(self.lib.msfl_places_add(self.p, _vp(pts), _vp(off), len(off) - 1, MEM_HOST, C.byref(first)), "msfl_places_add", allow)
         return first.value if s == OK else s
 
     def add_device(self, pts, off, allow=()):
         """Device-pointer form (torch tensor / raw pointer of 16-byte points), asynchronous on the object's stream; `off` is a host array."""
         off = np.ascontiguousarray(off, np.int32)
         first = C.c_int(-1)
-        s = self._check(self.lib.msfl_places_add(self.p, _vp(pts), _vp(off), C.c_int(len(off) - 1), C.c_int(MEM_DEVICE), C.byref(first)),
-                        "msfl_places_add(device)", allow)
+        s = self._check(self.lib.msfl_places_add(self.p, _vp(pts), _vp(off), len(off) - 1, MEM_DEVICE, C.byref(first)), "msfl_places_add(device)",
+                        allow)
         return first.value if s == OK else s
 
     def _desc(self, desc):
@@ -1524,13 +1433,12 @@ class Places:
         """Appends ready descriptors (n, n_ring, n_sector) float32 - what get() delivered; keys and norms are recomputed."""
         d = self._desc(desc)
         first = C.c_int(-1)
-        s = self._check(self.lib.msfl_places_add_descriptors(self.p, _vp(d), C.c_int(len(d)), C.c_int(MEM_HOST), C.byref(first)),
-                        "msfl_places_add_descriptors", allow)
+        s = self._check(self.lib.msfl_places_add_descriptors(self.p, _vp(d), len(d), MEM_HOST, C.byref(first)), "msfl_places_add_descriptors", allow)
         return first.value if s == OK else s
 
     def add_descriptors_device(self, desc, n, allow=()):
         first = C.c_int(-1)
-        s = self._check(self.lib.msfl_places_add_descriptors(self.p, _vp(desc), C.c_int(int(n)), C.c_int(MEM_DEVICE), C.byref(first)),
+        s = self._check(self.lib.msfl_places_add_descriptors(self.p, _vp(desc), int(n), MEM_DEVICE, C.byref(first)),
                         "msfl_places_add_descriptors(device)", allow)
         return first.value if s == OK else s
 
@@ -1539,12 +1447,11 @@ class Places:
         n = self.size() - first if n is None else int(n)
         d = np.zeros((max(n, 0), self.n_ring, self.n_sector), np.float32)
         rk = np.zeros((max(n, 0), self.n_ring), np.int32) if want_ring_key else None
-        self._check(self.lib.msfl_places_get(self.p, C.c_int(int(first)), C.c_int(n), _vp(d), _vp(rk), C.c_int(MEM_HOST)), "msfl_places_get")
+        self._check(self.lib.msfl_places_get(self.p, int(first), n, _vp(d), _vp(rk), MEM_HOST), "msfl_places_get")
         return (d, rk) if want_ring_key else d
 
     def get_device(self, first, n, desc_out, ring_key_out=None):
-        self._check(self.lib.msfl_places_get(self.p, C.c_int(int(first)), C.c_int(int(n)), _vp(desc_out), _vp(ring_key_out), C.c_int(MEM_DEVICE)),
-                    "msfl_places_get(device)")
+        self._check(self.lib.msfl_places_get(self.p, int(first), int(n), _vp(desc_out), _vp(ring_key_out), MEM_DEVICE), "msfl_places_get(device)")
 
     @staticmethod
     def _max_index(max_index, n):
@@ -1560,31 +1467,30 @@ class Places:
         Q = len(off) - 1
         out = np.zeros((max(Q, 0), max(int(k), 0)), PLACE_MATCH_DTYPE)
         mi = self._max_index(max_index, Q)
-        s = self._check(self.lib.msfl_places_query(self.p, _vp(pts), _vp(off), C.c_int(Q), _vp(mi), C.c_int(int(n_prefilter)), C.c_int(int(k)),
-                                                   _vp(out), C.c_int(MEM_HOST)), "msfl_places_query", allow)
+        s = self._check(self.lib.msfl_places_query(self.p, _vp(pts), _vp(off), Q, _vp(mi), int(n_prefilter), int(k), _vp(out), MEM_HOST),
+                        "msfl_places_query", allow)
         return out if s == OK else s
 
     def query_device(self, pts, off, out, max_index=None, n_prefilter=0, k=1, allow=()):
         """Device-pointer form, asynchronous: `out` holds Q x k records of 24 bytes on the device; off / max_index are host arrays."""
         off = np.ascontiguousarray(off, np.int32)
         mi = self._max_index(max_index, len(off) - 1)
-        return self._check(self.lib.msfl_places_query(self.p, _vp(pts), _vp(off), C.c_int(len(off) - 1), _vp(mi), C.c_int(int(n_prefilter)),
-                                                      C.c_int(int(k)), _vp(out), C.c_int(MEM_DEVICE)), "msfl_places_query(device)", allow)
+        return self._check(self.lib.msfl_places_query(self.p, _vp(pts), _vp(off), len(off) - 1, _vp(mi), int(n_prefilter), int(k), _vp(out),
+                                                      MEM_DEVICE), "msfl_places_query(device)", allow)
 
     def query_entries(self, entries, max_index=None, n_prefilter=0, k=1, allow=()):
         """As query(), for entries that are stored already (e.g. entry i against max_index = i - 50: the loop-closure search)."""
         e = np.ascontiguousarray(np.atleast_1d(np.asarray(entries, np.int32)))
         out = np.zeros((len(e), max(int(k), 0)), PLACE_MATCH_DTYPE)
         mi = self._max_index(max_index, len(e))
-        s = self._check(self.lib.msfl_places_query_entries(self.p, _vp(e), C.c_int(len(e)), _vp(mi), C.c_int(int(n_prefilter)), C.c_int(int(k)),
-                                                           _vp(out), C.c_int(MEM_HOST)), "msfl_places_query_entries", allow)
+        s = self._check(self.lib.msfl_places_query_entries(self.p, _vp(e), len(e), _vp(mi), int(n_prefilter), int(k), _vp(out), MEM_HOST),
+                        "msfl_places_query_entries", allow)
         return out if s == OK else s
 
     def query_entries_device(self, entries, out, max_index=None, n_prefilter=0, k=1, allow=()):
         e = np.ascontiguousarray(np.atleast_1d(np.asarray(entries, np.int32)))
         mi = self._max_index(max_index, len(e))
-        return self._check(self.lib.msfl_places_query_entries(self.p, _vp(e), C.c_int(len(e)), _vp(mi), C.c_int(int(n_prefilter)),
-                                                              C.c_int(int(k)), _vp(out), C.c_int(MEM_DEVICE)),
+        return self._check(self.lib.msfl_places_query_entries(self.p, _vp(e), len(e), _vp(mi), int(n_prefilter), int(k), _vp(out), MEM_DEVICE),
                            "msfl_places_query_entries(device)", allow)
 
 
@@ -1674,7 +1580,7 @@ def edge_from_uncertainty(i, j, pose_i, pose_j, unc, scale, out=None):
         u = np.ascontiguousarray(np.asarray(unc, UNCERTAINTY_DTYPE).reshape(1))
         unc = MatchUncertainty.from_buffer_copy(u.tobytes())
     pi, pj = (np.ascontiguousarray(np.asarray(p, np.float64).reshape(7)) for p in (pose_i, pose_j))
-    s = lib.msfl_graph_edge_from_uncertainty(C.c_int(int(i)), C.c_int(int(j)), _vp(pi), _vp(pj), C.byref(unc), C.c_double(float(scale)), _vp(rec))
+    s = lib.msfl_graph_edge_from_uncertainty(int(i), int(j), _vp(pi), _vp(pj), C.byref(unc), scale, _vp(rec))
     return int(s), rec
 
 
@@ -1685,52 +1591,30 @@ def fix_from_covariance(i, j, t, p, covariance, out=None):
     rec = np.zeros(1, GRAPH_FIX_INFO_DTYPE) if out is None else out
     pp = np.ascontiguousarray(np.asarray(p, np.float64).reshape(3))
     cov = np.ascontiguousarray(np.asarray(covariance, np.float64).reshape(9))
-    s = lib.msfl_graph_fix_from_covariance(C.c_int(int(i)), C.c_int(int(j)), C.c_double(float(t)), _vp(pp), _vp(cov), _vp(rec))
+    s = lib.msfl_graph_fix_from_covariance(int(i), int(j), t, _vp(pp), _vp(cov), _vp(rec))
     return int(s), rec
 
 
-class PoseGraph:
+class PoseGraph(_Owner):
     """Owns one msfl_graph: poses on the device, relative-pose edges and position fixes, and the trust-region solve over them
     (msfl_graph_*), independent of any Handle.  Keyword arguments are the fields of msfl_graph_config."""
+    _PTR, _DESTROY, _ERROR = "p", "msfl_graph_destroy", "msfl_graph_last_error"
 
     def __init__(self, device=0, **cfg):
-        self.lib = load()
-        self.lib.msfl_graph_last_error.restype = C.c_char_p
-        self.lib.msfl_graph_last_error.argtypes = [C.c_void_p]
-        self.lib.msfl_graph_num_nodes.argtypes = [C.c_void_p]
+        ref = self._own(load())
         self.config = GraphConfig()
         self.lib.msfl_graph_default_config(C.byref(self.config))
         for k, v in cfg.items():
             if k not in dict(GraphConfig._fields_):
                 raise TypeError("unknown msfl_graph_config field %r" % (k,))
             setattr(self.config, k, v)
-        self.p = C.c_void_p()
         self._count = [0, 0, 0, 0]               # factors per kind (GRAPH_FACTOR_*), for chi2's default range
-        s = self.lib.msfl_graph_create(C.byref(self.config), C.c_int(device), C.byref(self.p))
+        s = self.lib.msfl_graph_create(C.byref(self.config), device, ref)
         if s != OK:
             raise MsflError(s, "msfl_graph_create", "(a config outside its limits, or no GPU: there is no CPU fallback)")
 
-    def close(self):
-        if self.p:
-            self.lib.msfl_graph_destroy(self.p)
-            self.p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, s, what, allow=()):
-        if s != OK and s not in allow:
-            raise MsflError(s, what, (self.lib.msfl_graph_last_error(self.p) or b"").decode())
-        return s
-
-    def last_error(self):
-        return (self.lib.msfl_graph_last_error(self.p) or b"").decode()
-
     def set_stream(self, stream_ptr):
-        self._check(self.lib.msfl_graph_set_stream(self.p, C.c_void_p(stream_ptr)), "msfl_graph_set_stream")
+        self._check(self.lib.msfl_graph_set_stream(self.p, stream_ptr), "msfl_graph_set_stream")
 
     def synchronize(self):
         self._check(self.lib.msfl_graph_synchronize(self.p), "msfl_graph_synchronize")
@@ -1750,11 +1634,11 @@ class PoseGraph:
         (or the refusing status when it is in `allow`)."""
         first = C.c_int(-1)
         if _on_device(poses):
-            n, ptr, mem = int(poses.numel() // 7), C.c_void_p(poses.data_ptr()), MEM_DEVICE
+            n, ptr, mem = int(poses.numel() // 7), poses.data_ptr(), MEM_DEVICE
         else:
             poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
             n, ptr, mem = len(poses), _vp(poses), MEM_HOST
-        s = self._check(self.lib.msfl_graph_add_nodes(self.p, ptr, C.c_int(n), C.c_int(mem), C.byref(first)), "msfl_graph_add_nodes", allow)
+        s = self._check(self.lib.msfl_graph_add_nodes(self.p, ptr, n, mem, C.byref(first)), "msfl_graph_add_nodes", allow)
         return first.value if s == OK else s
 
     @staticmethod
@@ -1793,14 +1677,14 @@ class PoseGraph:
 
     def add_edges_info(self, rec, allow=()):
         rec = np.ascontiguousarray(rec, GRAPH_EDGE_INFO_DTYPE)
-        s = self._check(self.lib.msfl_graph_add_edges_info(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_edges_info", allow)
+        s = self._check(self.lib.msfl_graph_add_edges_info(self.p, _vp(rec), len(rec)), "msfl_graph_add_edges_info", allow)
         if s == OK:
             self._count[GRAPH_FACTOR_EDGE_INFO] += len(rec)
         return s
 
     def add_fixes_info(self, rec, allow=()):
         rec = np.ascontiguousarray(rec, GRAPH_FIX_INFO_DTYPE)
-        s = self._check(self.lib.msfl_graph_add_fixes_info(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_fixes_info", allow)
+        s = self._check(self.lib.msfl_graph_add_fixes_info(self.p, _vp(rec), len(rec)), "msfl_graph_add_fixes_info", allow)
         if s == OK:
             self._count[GRAPH_FACTOR_FIX_INFO] += len(rec)
         return s
@@ -1810,8 +1694,7 @@ class PoseGraph:
         if n is None:
             n = self._count[int(kind)] - int(first)
         out = np.zeros(max(0, int(n)), np.float64)
-        s = self._check(self.lib.msfl_graph_factor_chi2(self.p, C.c_int(int(kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(out)),
-                        "msfl_graph_factor_chi2", allow)
+        s = self._check(self.lib.msfl_graph_factor_chi2(self.p, int(kind), int(first), int(n), _vp(out)), "msfl_graph_factor_chi2", allow)
         return out if s == OK else s
 
     @staticmethod
@@ -1830,16 +1713,15 @@ class PoseGraph:
         rec = np.ascontiguousarray(rec, GRAPH_LOSS_DTYPE)
         if n is None:
             n = self._count[int(factor_kind)] - int(first) if 0 <= int(factor_kind) < 4 else len(rec)
-        return self._check(self.lib.msfl_graph_set_losses(self.p, C.c_int(int(factor_kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(rec),
-                                                          C.c_int(len(rec))), "msfl_graph_set_losses", allow)
+        return self._check(self.lib.msfl_graph_set_losses(self.p, int(factor_kind), int(first), int(n), _vp(rec), len(rec)), "msfl_graph_set_losses",
+                           allow)
 
     def losses(self, factor_kind, first=0, n=None, allow=()):
         """msfl_graph_get_losses: the records (GRAPH_LOSS_DTYPE) of factors first .. first + n of one kind; DEFAULT where none was set."""
         if n is None:
             n = self._count[int(factor_kind)] - int(first)
         out = np.zeros(max(0, int(n)), GRAPH_LOSS_DTYPE)
-        s = self._check(self.lib.msfl_graph_get_losses(self.p, C.c_int(int(factor_kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(out)),
-                        "msfl_graph_get_losses", allow)
+        s = self._check(self.lib.msfl_graph_get_losses(self.p, int(factor_kind), int(first), int(n), _vp(out)), "msfl_graph_get_losses", allow)
         return out if s == OK else s
 
     def weights(self, factor_kind, first=0, n=None, allow=()):
@@ -1847,8 +1729,8 @@ class PoseGraph:
         if n is None:
             n = self._count[int(factor_kind)] - int(first)
         out = np.zeros(max(0, int(n)), np.float64)
-        s = self._check(self.lib.msfl_graph_factor_weights(self.p, C.c_int(int(factor_kind)), C.c_int(int(first)), C.c_int(int(n)), _vp(out)),
-                        "msfl_graph_factor_weights", allow)
+        s = self._check(self.lib.msfl_graph_factor_weights(self.p, int(factor_kind), int(first), int(n), _vp(out)), "msfl_graph_factor_weights",
+                        allow)
         return out if s == OK else s
 
     def marginals(self, pairs, out=None, allow=(), **options):
@@ -1866,49 +1748,48 @@ class PoseGraph:
             setattr(opt, k, v)
         sm = GraphMarginalsSummary()
         if out is not None and _on_device(out):
-            ptr, mem, res = C.c_void_p(out.data_ptr()), MEM_DEVICE, out
+            ptr, mem, res = out.data_ptr(), MEM_DEVICE, out
         else:
             res = np.zeros((n, 6, 6), np.float64) if out is None else out      # a C-contiguous float64 array of n x 36 values
             ptr, mem = _vp(res), MEM_HOST
         call = self.lib.msfl_graph_marginals_with if options else self.lib.msfl_graph_marginals
-        args = (self.p, _vp(pairs), C.c_int(n), ptr, C.c_int(mem)) + ((C.byref(opt),) if options else ()) + (C.byref(sm),)
+        args = (self.p, _vp(pairs), n, ptr, mem) + ((C.byref(opt),) if options else ()) + (C.byref(sm),)
         s = self._check(call(*args), "msfl_graph_marginals", allow)
         return (res, sm) if s == OK else s
 
     def add_edges(self, rec, allow=()):
         rec = np.ascontiguousarray(rec, GRAPH_EDGE_DTYPE)
-        s = self._check(self.lib.msfl_graph_add_edges(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_edges", allow)
+        s = self._check(self.lib.msfl_graph_add_edges(self.p, _vp(rec), len(rec)), "msfl_graph_add_edges", allow)
         if s == OK:
             self._count[GRAPH_FACTOR_EDGE] += len(rec)
         return s
 
     def add_fixes(self, rec, allow=()):
         rec = np.ascontiguousarray(rec, GRAPH_FIX_DTYPE)
-        s = self._check(self.lib.msfl_graph_add_fixes(self.p, _vp(rec), C.c_int(len(rec))), "msfl_graph_add_fixes", allow)
+        s = self._check(self.lib.msfl_graph_add_fixes(self.p, _vp(rec), len(rec)), "msfl_graph_add_fixes", allow)
         if s == OK:
             self._count[GRAPH_FACTOR_FIX] += len(rec)
         return s
 
     def set_fixed(self, node, flag=True, allow=()):
-        return self._check(self.lib.msfl_graph_set_fixed(self.p, C.c_int(int(node)), C.c_int(1 if flag else 0)), "msfl_graph_set_fixed", allow)
+        return self._check(self.lib.msfl_graph_set_fixed(self.p, int(node), 1 if flag else 0), "msfl_graph_set_fixed", allow)
 
     def set_poses(self, poses, first=0, allow=()):
         if _on_device(poses):
-            n, ptr, mem = int(poses.numel() // 7), C.c_void_p(poses.data_ptr()), MEM_DEVICE
+            n, ptr, mem = int(poses.numel() // 7), poses.data_ptr(), MEM_DEVICE
         else:
             poses = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
             n, ptr, mem = len(poses), _vp(poses), MEM_HOST
-        return self._check(self.lib.msfl_graph_set_poses(self.p, C.c_int(int(first)), C.c_int(n), ptr, C.c_int(mem)), "msfl_graph_set_poses", allow)
+        return self._check(self.lib.msfl_graph_set_poses(self.p, int(first), n, ptr, mem), "msfl_graph_set_poses", allow)
 
     def poses(self, first=0, n=None, out=None):
         """(n, 7) poses from node `first` on; `out`: a CUDA float64 tensor to fill on the device instead (asynchronous)."""
         n = self.num_nodes() - int(first) if n is None else int(n)
         if out is not None:
-            self._check(self.lib.msfl_graph_get_poses(self.p, C.c_int(int(first)), C.c_int(n), C.c_void_p(out.data_ptr()), C.c_int(MEM_DEVICE)),
-                        "msfl_graph_get_poses(device)")
+            self._check(self.lib.msfl_graph_get_poses(self.p, int(first), n, out.data_ptr(), MEM_DEVICE), "msfl_graph_get_poses(device)")
             return out
         a = np.zeros((n, 7), np.float64)
-        self._check(self.lib.msfl_graph_get_poses(self.p, C.c_int(int(first)), C.c_int(n), _vp(a), C.c_int(MEM_HOST)), "msfl_graph_get_poses")
+        self._check(self.lib.msfl_graph_get_poses(self.p, int(first), n, _vp(a), MEM_HOST), "msfl_graph_get_poses")
         return a
 
     def cost(self):
@@ -1926,5 +1807,5 @@ class PoseGraph:
         """(accept list, candidate costs) of the last optimize, one entry per LM iteration."""
         cap = max(1, int(self.config.max_num_iterations))
         acc, cost, n = np.zeros(cap, np.int32), np.zeros(cap, np.float64), C.c_int(0)
-        self._check(self.lib.msfl_graph_get_trace(self.p, _vp(acc), _vp(cost), C.c_int(cap), C.byref(n)), "msfl_graph_get_trace")
+        self._check(self.lib.msfl_graph_get_trace(self.p, _vp(acc), _vp(cost), cap, C.byref(n)), "msfl_graph_get_trace")
         return acc[:n.value].copy(), cost[:n.value].copy()

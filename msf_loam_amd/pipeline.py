@@ -38,24 +38,19 @@ class BatchPipeline:
         self.f = f
         self.d_poses = self.d_mstat = None
 
-    def _check(self, s, what):
-        if s != 0:
-            raise capi.MsflError(s, what, self.lib.msfl_last_error(self.h.h).decode())
-
     def extract(self):
-        vp = C.c_void_p
-        self._check(self.lib.msfl_extract_features_batch(self.h.h, C.c_int(self.B), vp(self.d_pts.data_ptr()), vp(self.d_ring.data_ptr()),
-                                                         self.off.ctypes.data_as(vp), C.byref(self.f), vp(self.d_status.data_ptr()),
-                                                         C.c_int(capi.MEM_DEVICE)), "msfl_extract_features_batch")
+        vp = capi._vp
+        self.h._check(self.lib.msfl_extract_features_batch(self.h.h, self.B, vp(self.d_pts), vp(self.d_ring), vp(self.off), C.byref(self.f),
+                                                           vp(self.d_status), capi.MEM_DEVICE), "msfl_extract_features_batch")
 
     def voxel(self, leaf_corner=0.2, leaf_surf=0.4):
         """corner and surf lists in one call: both filters are enqueued before the one synchronisation."""
-        vp = C.c_void_p
-        self._check(self.lib.msfl_voxel_downsample_batch_pair(
-            self.h.h, C.c_int(self.B), vp(self.d_full.data_ptr()), self.off.ctypes.data_as(vp),
-            vp(self.d_idx[1].data_ptr()), vp(self.d_cnt[2].data_ptr()), C.c_float(leaf_corner), vp(self.d_corner.data_ptr()), self.corner_off.ctypes.data_as(vp),
-            vp(self.d_idx[3].data_ptr()), vp(self.d_cnt[4].data_ptr()), C.c_float(leaf_surf), vp(self.d_surf.data_ptr()), self.surf_off.ctypes.data_as(vp),
-            C.c_int(capi.MEM_DEVICE)), "msfl_voxel_downsample_batch_pair")
+        vp = capi._vp
+        self.h._check(self.lib.msfl_voxel_downsample_batch_pair(
+            self.h.h, self.B, vp(self.d_full), vp(self.off),
+            vp(self.d_idx[1]), vp(self.d_cnt[2]), leaf_corner, vp(self.d_corner), vp(self.corner_off),
+            vp(self.d_idx[3]), vp(self.d_cnt[4]), leaf_surf, vp(self.d_surf), vp(self.surf_off),
+            capi.MEM_DEVICE), "msfl_voxel_downsample_batch_pair")
 
     def set_map(self, map_corner, map_surf):
         self.d_map_c = torch.from_numpy(np.ascontiguousarray(map_corner, dtype=np.float32)).to(self.dev)

@@ -1,31 +1,135 @@
-"""CPU: the C-ABI shared library loads and exports every symbol include/msfl_c_api.h declares
-(no compute calls: there is no GPU here)."""
+"""CPU: the C-ABI shared library loads and exports every symbol include/msfl_c_api.h declares, and the ctypes binding
+declares every one of them with the header's prototype (no compute calls: there is no GPU here).  One small GPU test
+passes bare 64-bit device addresses through a declared prototype."""
 import ctypes
 import os
 import re
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+RETURNS = {"msfl_status": "i", "int": "i", "void": "v", "const char*": "z"}
+SCALARS = {"int": "i", "msfl_mem": "i", "msfl_status": "i", "double": "d", "float": "f"}
+CTYPES = {"i": ctypes.c_int, "v": None, "z": ctypes.c_char_p, "p": ctypes.c_void_p, "d": ctypes.c_double, "f": ctypes.c_float}
 
-def _declared():
+
+def _header():
     text = open(os.path.join(ROOT, "include", "msfl_c_api.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(msfl_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"//[^\n]*", "", text)
 
 
-def test_library_exports_every_declared_symbol():
+def _declared():
+    return sorted(set(re.findall(r"\b(msfl_[a-z0-9_]+)\s*\(", _header())))
+
+
+def _prototypes():
+    """Every `ret msfl_*(params);` of the header as {name: "r:kinds"}: r one of i (msfl_status / int), v (void), z (const char*);
+    one kind per parameter: p (anything with * or []), i (int, msfl_mem, msfl_status), d (double), f (float).  A return or a
+    scalar parameter of any other type fails here, by name."""
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?\**)\s*\b(msfl_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header()):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        assert ret in RETURNS, "%s: return type %r is not classified" % (name, ret)
+        kinds = ""
+        for prm in ([] if params.strip() in ("", "void") else params.split(",")):
+            prm = " ".join(prm.split())
+            if "*" in prm or "[" in prm:
+                kinds += "p"
+                continue
+            ty = re.sub(r"\bconst\b", "", prm).split()
+            assert len(ty) == 2 and ty[0] in SCALARS, "%s: scalar parameter %r is not classified" % (name, prm)
+            kinds += SCALARS[ty[0]]
+        assert name not in protos, "declared twice: " + name
+        protos[name] = RETURNS[ret] + ":" + kinds
+    return protos
+
+
+def _lib():
     from msf_loam_amd import capi
     if not os.path.exists(capi.LIB_PATH):
         import __graft_entry__
         __graft_entry__.build()
+    return capi
+
+
+def test_library_exports_every_declared_symbol():
+    capi = _lib()
     lib = ctypes.CDLL(capi.LIB_PATH)
     names = _declared()
     assert len(names) >= 20
     for n in names:
         assert hasattr(lib, n), "missing export: " + n
     assert sorted(capi.EXPORTED) == names, "capi.EXPORTED out of sync with the header"
+
+
+def test_prototype_table_matches_the_header():
+    """Function by function and parameter by parameter, nothing missing and nothing extra (no library needed)."""
+    from msf_loam_amd import capi
+    header = _prototypes()
+    assert sorted(header) == _declared()                         # the declaration parser saw every function the name scan sees
+    table = dict(capi.PROTOTYPES)
+    assert sorted(set(header) - set(table)) == [], "declared in the header, missing from capi.PROTOTYPES"
+    assert sorted(set(table) - set(header)) == [], "in capi.PROTOTYPES, not declared in the header"
+    for name, sig in header.items():
+        assert table[name].split(":")[0] == sig.split(":")[0], "%s: return kind %r, the header says %r" % (name, table[name], sig)
+        got, want = table[name].split(":")[1], sig.split(":")[1]
+        assert len(got) == len(want), "%s: %d parameters, the header has %d" % (name, len(got), len(want))
+        for k, (g, w) in enumerate(zip(got, want)):
+            assert g == w, "%s: parameter %d is %r, the header says %r" % (name, k, g, w)
+    assert list(capi.EXPORTED) == list(capi.PROTOTYPES)          # one list, not two
+
+
+def test_load_applies_every_prototype():
+    capi = _lib()
+    lib = capi.load()
+    for name, sig in _prototypes().items():
+        fn = getattr(lib, name)
+        ret, kinds = sig.split(":")
+        assert fn.restype is CTYPES[ret], name
+        assert fn.argtypes is not None and len(fn.argtypes) == len(kinds), name
+        for k, (a, w) in enumerate(zip(fn.argtypes, kinds)):
+            assert a is CTYPES[w], "%s: parameter %d" % (name, k)
+
+
+def test_declared_prototypes_refuse_wrong_types():
+    capi = _lib()
+    lib = capi.load()
+    with pytest.raises(ctypes.ArgumentError):
+        lib.msfl_status_string(1.5)                               # a float where an int is declared
+    with pytest.raises(ctypes.ArgumentError):
+        lib.msfl_last_error(np.zeros(4))                          # a bare ndarray where a pointer is declared (capi._vp is the way)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.msfl_set_timing(None, 1.0)
+    # a null handle is refused by the library itself; the 64-bit stream value converts without error
+    assert lib.msfl_set_stream(None, 1 << 40) == capi.BAD_ARG
+    assert lib.msfl_status_string(capi.BAD_ARG) == b"BAD_ARG"
+
+
+@pytest.mark.gpu
+def test_bare_device_addresses_pass_whole(gpu):
+    """msfl_transform_cloud called raw with tensor.data_ptr() integers: the declared c_void_p carries all 64 bits of a device
+    address, so the result equals Handle.transform_cloud's bit for bit."""
+    import torch
+    from msf_loam_amd import capi
+    fn = gpu.lib.msfl_transform_cloud
+    assert fn.argtypes is not None and len(fn.argtypes) == 6                 # checked first: an undeclared call would cut the pointers
+    assert [fn.argtypes[k] for k in (0, 1, 3, 4)] == [ctypes.c_void_p] * 4 and fn.restype is ctypes.c_int
+    rng = np.random.default_rng(5)
+    pts = rng.uniform(-20.0, 20.0, (8, 4)).astype(np.float32)
+    q = rng.normal(size=4)
+    pose = np.concatenate([[1.5, -2.25, 0.75], q / np.linalg.norm(q)])
+    want = gpu.transform_cloud(pts, pose)
+    d_in = torch.from_numpy(pts).to("cuda:0")
+    d_out = torch.zeros((8, 4), dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    assert isinstance(d_in.data_ptr(), int) and isinstance(d_out.data_ptr(), int)
+    s = fn(gpu.h, d_in.data_ptr(), 8, pose.ctypes.data, d_out.data_ptr(), capi.MEM_DEVICE)
+    assert s == capi.OK
+    gpu.synchronize()
+    assert d_out.cpu().numpy().tobytes() == want.tobytes()
 
 
 def test_params_struct_matches_header_defaults():
