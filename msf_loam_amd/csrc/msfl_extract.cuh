@@ -2,7 +2,10 @@
 //
 // Replaces RealHandleLaserCloudMessage (msf_loam_node.cc:160-378).  Four kernels per batch (round 2: the sector sort is gone):
 //   extract_prepare_kernel    one 1024-thread workgroup per scan: invalid-point removal (:85-111),
-//                             relative time (:128-156), stable split into rings + concat (:188-195)
+//                             relative time (:128-156), stable split into rings + concat (:188-195); a call of few
+//                             scans runs extract_prepare_count / scatter / finish_kernel instead, several workgroups per
+//                             scan.  Both forms call one copy of each slice pass (prep_pass_a, prep_early_wraps,
+//                             prep_pass_b, prep_ring_tail), so they write the same bytes
 //   extract_curvature_kernel  one thread per point: 11-tap curvature (:213-240) + neighbour-gap flags
 //   extract_pick_kernel       one wavefront per (scan, ring): the serial sharp / less-sharp / flat pick
 //                             (:263-344) as repeated wave-wide arg-max / arg-min over the sector's
@@ -80,15 +83,213 @@ __device__ __forceinline__ unsigned long long same_ring_lanes(bool valid, int r,
   return m;
 }
 
-// Each of the 16 wavefronts owns a CONTIGUOUS slice of the driver-order cloud, so the stable ring
-// split needs no per-chunk workgroup barriers: pass A counts (wave, ring) populations, one scan
-// turns them into write cursors, pass B re-walks the slice and scatters with wave-local ranks
-// (ballot per distinct ring; the cursors of a wave are touched by that wave only).
+// ---------------------------------------------------------------------------------------------------------------------------
+// The stable ring split.  Every wavefront owns a CONTIGUOUS slice of the driver-order cloud, so the split needs no
+// per-chunk workgroup barriers: pass A counts (slice, ring) populations, one scan turns them into write cursors, pass B
+// re-walks the slice and scatters with wave-local ranks (ballot per ring bit; the cursors of a slice are touched by its
+// wavefront only).  Two launch forms run these passes, extract_prepare_kernel (one workgroup per scan, 16 slices) and the
+// count / scatter / finish kernels below it (G workgroups, 16 G slices): what follows is what they share, written once.
+// ---------------------------------------------------------------------------------------------------------------------------
+#ifndef MSFL_PREP_GROUPS
+#define MSFL_PREP_GROUPS 4
+#endif
+// 64-point groups per iteration of a slice pass, their loads issued up front: one workgroup per CU keeps 16 wavefronts
+// there, and one 16-byte load per lane in flight is far from what HBM needs to stay busy
+constexpr int kPrepGroups = MSFL_PREP_GROUPS;
+constexpr double kPrepTwoPi = 2 * 3.14159265358979323846;
+
+// slice [w0, w1) number sl of S: slices are multiples of 64 points, so a 64-point group never straddles two wavefronts
+__device__ __forceinline__ void prep_slice_bounds(int n, int S, int sl, int& w0, int& w1) {
+  const int slice = ((n + S - 1) / S + 63) & ~63;
+  w0 = (int)min((long long)sl * slice, (long long)n); w1 = min(w0 + slice, n);
+}
+
+// relative angle of a point (:139-142): fmod(a, 2 pi) with a = ori - start_ori + 2 pi in [0, 4 pi]: fmod is exact and so is
+// a - 2 pi for 2 pi <= a <= 4 pi (Sterbenz), so two conditional subtractions give the same bits
+__device__ __forceinline__ double prep_rel_angle(const float4 p, double start_ori) {
+  const double ori = -atan2((double)p.y, (double)p.x);
+  double a = ori - start_ori + kPrepTwoPi;
+  if (a >= kPrepTwoPi) a -= kPrepTwoPi;
+  if (a >= kPrepTwoPi) a -= kPrepTwoPi;
+  return a;
+}
+
+// ---- pass A over the slice [w0, w1) of one wavefront: populations of its rings into `cur` (the wavefront's row of the LDS
+//      table, zeroed), and its report head[0..2] = first valid point, bad ring seen, highest ring id ----
+__device__ __forceinline__ void prep_pass_a(const float4* in, const uint16_t* in_ring, int w0, int w1, int lane,
+                                            float min_range_sq, int* cur, int* head) {
+  int first = 0x7fffffff, bad = 0, rmax = 0;
+  for (int g0 = w0; g0 < w1; g0 += 64 * kPrepGroups) {
+    float4 pp[kPrepGroups]; int rr[kPrepGroups];
+#pragma unroll
+    for (int u = 0; u < kPrepGroups; u++) {
+      const int i = g0 + 64 * u + lane;
+      pp[u] = make_float4(0, 0, 0, 0); rr[u] = 0;
+      if (i < w1) { pp[u] = in[i]; rr[u] = in_ring[i]; }
+    }
+#pragma unroll
+    for (int u = 0; u < kPrepGroups; u++) {
+      const int g = g0 + 64 * u;
+      if (g >= w1) break;
+      const int i = g + lane;
+      bool valid = false;
+      int r = -1;
+      if (i < w1) {
+        valid = point_valid(pp[u], min_range_sq);
+        if (valid) { r = rr[u]; if (r >= kMaxRings) { bad = 1; valid = false; } }   // CHECK_LT(point.ring, 128), :136
+      }
+      const unsigned long long any_valid = __ballot(valid);
+      if (any_valid && first == 0x7fffffff) first = g + (__ffsll((long long)any_valid) - 1);
+      if (valid) { atomicAdd(&cur[r], 1); rmax = max(rmax, r); }               // LDS atomic: one instruction instead of the ballot match
+    }
+  }
+  bad = __any(bad) ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rmax = max(rmax, __shfl_xor(rmax, o));
+  if (lane == 0) { head[0] = first; head[1] = bad; head[2] = rmax; }
+}
+
+// n such reports, `stride` ints apart, merged into one: a workgroup's 16 wavefronts, then a scan's G workgroups
+__device__ __forceinline__ void prep_head_merge(const int* head, int n, int stride, int* out) {
+  int f = 0x7fffffff, bd = 0, rm = 0;
+  for (int k = 0; k < n; k++) { f = min(f, head[stride * k]); bd |= head[stride * k + 1]; rm = max(rm, head[stride * k + 2]); }
+  out[0] = f; out[1] = bd; out[2] = rm;
+}
+// the verdict of pass A over the whole scan: [0] first valid point, [1] bad ring, [2] bits of the highest ring id present
+__device__ __forceinline__ void prep_head_reduce(const int* head, int n, int stride, int* s_flag) {
+  prep_head_merge(head, n, stride, s_flag);
+  s_flag[2] = 32 - __clz(s_flag[2] | 1);
+}
+// whether that verdict refuses the scan, the same in every thread; the workgroup that reports it (`report`) leaves what a
+// refused scan leaves behind: status, the five counts, a zeroed ring table
+__device__ __forceinline__ bool prep_refused(const ExtractView& v, int b, int tid, const int* s_flag, bool report) {
+  if (!(s_flag[1] || s_flag[0] == 0x7fffffff)) return false;
+  if (report) {
+    if (tid == 0) {
+      v.status[b] = s_flag[1] ? 5 /*MSFL_BAD_RING*/ : 3 /*MSFL_BAD_ARG: empty valid cloud, CHECK :186,:200*/;
+      v.n_full[b] = 0; v.n_sharp[b] = 0; v.n_less_sharp[b] = 0; v.n_flat[b] = 0; v.n_less_flat[b] = 0;
+    }
+    if (tid <= kMaxRings) v.ring_tab[b * (kMaxRings + 1) + tid] = 0;
+  }
+  return true;
+}
+
+// ---- early wraps, by one wavefront over the cloud's first pre_end (<= 256) points.  A ring whose first point lies just
+//      BEHIND the cloud's first point in azimuth starts at an angle just below 2 pi and wraps at its second point: that is
+//      about half the rings of a spinning lidar, and every point of such a ring takes the +2 pi time.  Found after the
+//      scatter, that meant rewriting the time word of half the cloud (a 4-byte write into a 16-byte point = a
+//      read-modify-write of the whole line, plus the parked candidates).  So the wrap test runs over the cloud's head first,
+//      with exactly the arithmetic of pass B; pass B then stores the final time for everything behind a wrap point found
+//      here (s_early: its output index, INT_MAX = none), and the fix-up only serves later wraps.  Any prefix of the cloud
+//      gives the same outputs.  s_pre_last (NaN) / s_pre_cnt (0): the ring's last angle / points so far ----
+__device__ __forceinline__ void prep_early_wraps(const float4* in, const uint16_t* in_ring, int pre_end, int lane,
+                                                 float min_range_sq, int ring_bits, double start_ori, const int* s_off,
+                                                 double* s_pre_last, int* s_pre_cnt, int* s_early) {
+  for (int g = 0; g < pre_end; g += 64) {
+    const int i = g + lane;
+    float4 p = make_float4(0, 0, 0, 0);
+    int r = -1;
+    bool valid = false;
+    if (i < pre_end) { p = in[i]; valid = point_valid(p, min_range_sq); if (valid) r = in_ring[i]; }
+    const unsigned long long m = same_ring_lanes(valid, r, ring_bits);
+    const unsigned long long below = m & ((1ull << lane) - 1ull);
+    const double a = valid ? prep_rel_angle(p, start_ori) : 0.0;
+    const int pl = below ? 63 - __clzll((long long)below) : lane;
+    double a_prev = __shfl(a, pl);
+    if (valid) {
+      const int seen = s_pre_cnt[r];                         // every lane of a ring reads before its last lane writes
+      bool has_prev = below != 0;
+      if (!has_prev) { a_prev = s_pre_last[r]; has_prev = !isnan(a_prev); }
+      if ((m >> lane) == 1ull) { s_pre_last[r] = a; s_pre_cnt[r] = seen + __popcll(m); }
+      if (has_prev && a < a_prev) atomicMin(&s_early[r], s_off[r] + seen + __popcll(below));
+    }
+  }
+}
+
+// ---- pass B over the slice [w0, w1) of one wavefront: stable split into rings, driver order.  The wrap test of the reference
+//      (`relative_angle < last_relative_angles[ring]`, :145-149: from the first such point on a ring gets +2 pi) compares a
+//      point with its predecessor ON ITS RING, which is the previous same-ring lane of the group, or the last same-ring
+//      point this wavefront has seen (LDS), or the last one of an earlier slice (the callers' test after the pass): the f64
+//      raw angles never go to memory.  cur / lasta (NaN = none yet) / firsta: the wavefront's rows of the write cursors and of
+//      the raw angles of the last / first point of (slice, ring); s_wrap: the ring's smallest wrap index so far ----
+__device__ __forceinline__ void prep_pass_b(const float4* in, const uint16_t* in_ring, int w0, int w1, int lane,
+                                            float min_range_sq, int ring_bits, double start_ori, double scan_period,
+                                            int* cur, double* lasta, double* firsta, int* s_wrap, const int* s_early, float4* out_pts) {
+  for (int g0 = w0; g0 < w1; g0 += 64 * kPrepGroups) {
+    float4 pp[kPrepGroups]; int rr[kPrepGroups];
+#pragma unroll
+    for (int u = 0; u < kPrepGroups; u++) {
+      const int i = g0 + 64 * u + lane;
+      pp[u] = make_float4(0, 0, 0, 0); rr[u] = 0;
+      if (i < w1) { pp[u] = in[i]; rr[u] = in_ring[i]; }
+    }
+#pragma unroll
+    for (int u = 0; u < kPrepGroups; u++) {
+      const int g = g0 + 64 * u;
+      if (g >= w1) break;
+      const int i = g + lane;
+      const float4 p = pp[u];
+      int r = -1;
+      bool valid = false;
+      if (i < w1) {
+        valid = point_valid(p, min_range_sq);
+        if (valid) r = rr[u];
+      }
+      int dst = 0;
+      const unsigned long long m = same_ring_lanes(valid, r, ring_bits);
+      const unsigned long long below = m & ((1ull << lane) - 1ull);
+      double a = 0.0;
+      if (valid) {
+        const int c = cur[r];                                  // every lane of a ring reads the cursor ...
+        dst = c + __popcll(below);
+        if (below == 0) cur[r] = c + __popcll(m);              // ... before its leader advances it
+        a = prep_rel_angle(p, start_ori);
+      }
+      // predecessor on the ring inside this group: the highest same-ring lane below this one
+      const int pl = below ? 63 - __clzll((long long)below) : lane;
+      double a_prev = __shfl(a, pl);
+      if (valid) {
+        bool has_prev = below != 0;
+        if (!has_prev) {                                       // leader of its ring in this group: what the wavefront saw before
+          a_prev = lasta[r];
+          has_prev = !isnan(a_prev);
+          if (!has_prev) firsta[r] = a;
+        }
+        if ((m >> lane) == 1ull) lasta[r] = a;                 // last lane of the ring in this group (after the leader's read)
+        if (has_prev && a < a_prev) atomicMin(&s_wrap[r], dst);
+        // :151; behind a wrap point the angle carries +2 pi.  No ring id is stored here: a ring's ids are one constant over its
+        // output range (filled by prep_ring_tail with full-width stores; 2-byte stores scattered over 16 ring ranges were
+        // written to memory as partial lines, PMC: 0.83 GB written per 1 024 scans for 0.43 GB of output)
+        const double aw = dst >= s_early[r] ? a + kPrepTwoPi : a;
+        out_pts[dst] = make_float4(p.x, p.y, p.z, (float)(aw / kPrepTwoPi * scan_period));
+      }
+    }
+  }
+}
+
+// ---- a ring's tail work, by one wavefront: r's output range is [r0, r1).  The ring ids, one constant run.  Then relative
+//      time (stored in both `time` and `intensity`, :152-153): from a ring's wrap point on, the +2 pi candidate.  What lies
+//      behind an EARLY wrap point has it already, so [lo, hi) = [wrap index, min(early wrap index, r1)) is empty then, and
+//      without a wrap (lo = INT_MAX); a later wrap (the sweep passing the start direction again at the end of the scan)
+//      re-derives the angle of the few points behind it from their coordinates, which are stored unchanged, with the
+//      arithmetic of pass B ----
+__device__ __forceinline__ void prep_ring_tail(float4* out_pts, uint16_t* out_ring, int r, int r0, int r1, int lo, int hi, int lane,
+                                               double start_ori, double scan_period) {
+  for (int i = r0 + lane; i < r1; i += 64) out_ring[i] = (uint16_t)r;
+  if (lo < hi) {
+    for (int i = lo + lane; i < hi; i += 64) {
+      const float4 p = out_pts[i];
+      out_pts[i].w = (float)((prep_rel_angle(p, start_ori) + kPrepTwoPi) / kPrepTwoPi * scan_period);
+    }
+  }
+}
+
+// The one-workgroup form: one 1024-thread workgroup per scan, 16 slices.
 __global__ void __launch_bounds__(1024) extract_prepare_kernel(ExtractView v, ExtractParams prm) {
   __shared__ int s_off[kMaxRings + 1];
   __shared__ int s_wrap[kMaxRings];
   __shared__ int s_cur[16][kMaxRings];      // pass A: population of (wave, ring); pass B: write cursor
-  __shared__ int s_first[16], s_badw[16], s_rmax[16];
+  __shared__ int s_head[16 * 3];            // pass A's report of every wavefront
   __shared__ int s_flag[3];
   __shared__ double s_start_ori;
   __shared__ double s_lasta[16][kMaxRings];   // pass B: raw angle of the last point of (wave, ring) so far; NaN = none yet
@@ -103,50 +304,11 @@ __global__ void __launch_bounds__(1024) extract_prepare_kernel(ExtractView v, Ex
   const uint16_t* in_ring = v.in_ring + o;
   for (int k = tid; k < 16 * kMaxRings; k += 1024) { (&s_cur[0][0])[k] = 0; (&s_lasta[0][0])[k] = __longlong_as_double(0x7ff8000000000000ll); }
   __syncthreads();
-  const int slice = ((n + 15) / 16 + 63) & ~63;            // multiple of 64: a 64-point group never straddles two waves
-  const int w0 = min(wave * slice, n), w1 = min(w0 + slice, n);
-  // ---- pass A: populations, first valid point, ring check ----
-  int first = 0x7fffffff, bad = 0, rmax = 0;
-  // four 64-point groups per iteration with their loads issued up front: one workgroup per CU keeps 16 wavefronts
-  // there, and one 16-byte load per lane in flight is far from what HBM needs to stay busy
-#ifndef MSFL_PREP_GROUPS
-#define MSFL_PREP_GROUPS 4
-#endif
-  constexpr int kGroups = MSFL_PREP_GROUPS;
-  for (int g0 = w0; g0 < w1; g0 += 64 * kGroups) {
-    float4 pp[kGroups]; int rr[kGroups];
-#pragma unroll
-    for (int u = 0; u < kGroups; u++) {
-      const int i = g0 + 64 * u + lane;
-      pp[u] = make_float4(0, 0, 0, 0); rr[u] = 0;
-      if (i < w1) { pp[u] = in[i]; rr[u] = in_ring[i]; }
-    }
-#pragma unroll
-    for (int u = 0; u < kGroups; u++) {
-      const int g = g0 + 64 * u;
-      if (g >= w1) break;
-      const int i = g + lane;
-      bool valid = false;
-      int r = -1;
-      if (i < w1) {
-        valid = point_valid(pp[u], prm.min_range_sq);
-        if (valid) { r = rr[u]; if (r >= kMaxRings) { bad = 1; valid = false; } }   // CHECK_LT(point.ring, 128), :136
-      }
-      const unsigned long long any_valid = __ballot(valid);
-      if (any_valid && first == 0x7fffffff) first = g + (__ffsll((long long)any_valid) - 1);
-      if (valid) { atomicAdd(&s_cur[wave][r], 1); rmax = max(rmax, r); }       // LDS atomic: one instruction instead of the ballot match
-    }
-  }
-  bad = __any(bad) ? 1 : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rmax = max(rmax, __shfl_xor(rmax, o));
-  if (lane == 0) { s_first[wave] = first; s_badw[wave] = bad; s_rmax[wave] = rmax; }
+  int w0, w1;
+  prep_slice_bounds(n, 16, wave, w0, w1);
+  prep_pass_a(in, in_ring, w0, w1, lane, prm.min_range_sq, s_cur[wave], s_head + 3 * wave);
   __syncthreads();
-  if (tid == 0) {
-    int f = 0x7fffffff, bd = 0, rm = 0;
-    for (int w = 0; w < 16; w++) { f = min(f, s_first[w]); bd |= s_badw[w]; rm = max(rm, s_rmax[w]); }
-    s_flag[0] = f; s_flag[1] = bd; s_flag[2] = 32 - __clz(rm | 1);          // bits of the highest ring id present
-  }
+  if (tid == 0) prep_head_reduce(s_head, 16, 3, s_flag);
   // ring totals -> s_off (exclusive), then (wave, ring) cursors
   if (tid < kMaxRings) {
     int t = 0;
@@ -155,14 +317,7 @@ __global__ void __launch_bounds__(1024) extract_prepare_kernel(ExtractView v, Ex
     s_wrap[tid] = t;                                          // borrowed as the ring total
   }
   __syncthreads();
-  if (s_flag[1] || s_flag[0] == 0x7fffffff) {
-    if (tid == 0) {
-      v.status[b] = s_flag[1] ? 5 /*MSFL_BAD_RING*/ : 3 /*MSFL_BAD_ARG: empty valid cloud, CHECK :186,:200*/;
-      v.n_full[b] = 0; v.n_sharp[b] = 0; v.n_less_sharp[b] = 0; v.n_flat[b] = 0; v.n_less_flat[b] = 0;
-    }
-    if (tid <= kMaxRings) v.ring_tab[b * (kMaxRings + 1) + tid] = 0;
-    return;
-  }
+  if (prep_refused(v, b, tid, s_flag, true)) return;
   if (tid == 0) {
     int run = 0;
     for (int r = 0; r < kMaxRings; r++) { s_off[r] = run; run += s_wrap[r]; }
@@ -179,111 +334,23 @@ __global__ void __launch_bounds__(1024) extract_prepare_kernel(ExtractView v, Ex
     s_wrap[tid] = 0x7fffffff;
   }
   __syncthreads();
-  const int N = s_off[kMaxRings];
   const int ring_bits = __builtin_amdgcn_readfirstlane(s_flag[2]);
   const double start_ori = s_start_ori;
-  const double two_pi = 2 * 3.14159265358979323846;
   float4* out_pts = v.full_pts + o;
   uint16_t* out_ring = v.full_ring + o;
-  // relative angle of a point (:139-142): fmod(a, 2 pi) with a = ori - start_ori + 2 pi in [0, 4 pi]: fmod is exact and so is
-  // a - 2 pi for 2 pi <= a <= 4 pi (Sterbenz), so two conditional subtractions give the same bits
-  auto rel_angle = [&](const float4 p) __attribute__((always_inline)) {
-    const double ori = -atan2((double)p.y, (double)p.x);
-    double a = ori - start_ori + two_pi;
-    if (a >= two_pi) a -= two_pi;
-    if (a >= two_pi) a -= two_pi;
-    return a;
-  };
-  // ---- early wraps.  A ring whose first point lies just BEHIND the cloud's first point in azimuth starts at an angle just
-  //      below 2 pi and wraps at its second point: that is about half the rings of a spinning lidar, and every point of such a
-  //      ring takes the +2 pi time.  Found after the scatter, that meant rewriting the time word of half the cloud (a 4-byte
-  //      write into a 16-byte point = a read-modify-write of the whole line, plus the parked candidates).  So wavefront 0 runs
-  //      the wrap test over the first 256 points of the cloud first, with exactly the arithmetic of the pass below; pass B
-  //      then stores the final time for everything behind a wrap point found here, and the fix-up only serves later wraps ----
   if (tid < kMaxRings) { s_pre_last[tid] = __longlong_as_double(0x7ff8000000000000ll); s_pre_cnt[tid] = 0; s_early[tid] = 0x7fffffff; }
   __syncthreads();
-  if (wave == 0) {
+  if (wave == 0) {                                           // the pre-pass ends with wavefront 0's slice here
     const int pre_end = min(w1, 256);
-    for (int g = 0; g < pre_end; g += 64) {
-      const int i = g + lane;
-      float4 p = make_float4(0, 0, 0, 0);
-      int r = -1;
-      bool valid = false;
-      if (i < pre_end) { p = in[i]; valid = point_valid(p, prm.min_range_sq); if (valid) r = in_ring[i]; }
-      const unsigned long long m = same_ring_lanes(valid, r, ring_bits);
-      const unsigned long long below = m & ((1ull << lane) - 1ull);
-      const double a = valid ? rel_angle(p) : 0.0;
-      const int pl = below ? 63 - __clzll((long long)below) : lane;
-      double a_prev = __shfl(a, pl);
-      if (valid) {
-        const int seen = s_pre_cnt[r];                         // every lane of a ring reads before its last lane writes
-        bool has_prev = below != 0;
-        if (!has_prev) { a_prev = s_pre_last[r]; has_prev = !isnan(a_prev); }
-        if ((m >> lane) == 1ull) { s_pre_last[r] = a; s_pre_cnt[r] = seen + __popcll(m); }
-        if (has_prev && a < a_prev) atomicMin(&s_early[r], s_off[r] + seen + __popcll(below));
-      }
-    }
+    prep_early_wraps(in, in_ring, pre_end, lane, prm.min_range_sq, ring_bits, start_ori, s_off, s_pre_last, s_pre_cnt, s_early);
   }
   __syncthreads();
-  // ---- pass B: stable split into rings, every wave in its own slice, driver order.  The wrap test of the reference
-  //      (`relative_angle < last_relative_angles[ring]`, :145-149: from the first such point on a ring gets +2 pi) compares a
-  //      point with its predecessor ON ITS RING, which is the previous same-ring lane of the group, or the last same-ring
-  //      point this wave has seen (LDS), or the last one of an earlier wave (fixed up after the pass): the f64 raw angles
-  //      never go to memory ----
-  for (int g0 = w0; g0 < w1; g0 += 64 * kGroups) {
-    float4 pp[kGroups]; int rr[kGroups];
-#pragma unroll
-    for (int u = 0; u < kGroups; u++) {
-      const int i = g0 + 64 * u + lane;
-      pp[u] = make_float4(0, 0, 0, 0); rr[u] = 0;
-      if (i < w1) { pp[u] = in[i]; rr[u] = in_ring[i]; }
-    }
-#pragma unroll
-    for (int u = 0; u < kGroups; u++) {
-    const int g = g0 + 64 * u;
-    if (g >= w1) break;
-    const int i = g + lane;
-    const float4 p = pp[u];
-    int r = -1;
-    bool valid = false;
-    if (i < w1) {
-      valid = point_valid(p, prm.min_range_sq);
-      if (valid) r = rr[u];
-    }
-    int dst = 0;
-    const unsigned long long m = same_ring_lanes(valid, r, ring_bits);
-    const unsigned long long below = m & ((1ull << lane) - 1ull);
-    double a = 0.0;
-    if (valid) {
-      const int cur = s_cur[wave][r];                        // every lane of a ring reads the cursor ...
-      dst = cur + __popcll(below);
-      if (below == 0) s_cur[wave][r] = cur + __popcll(m);    // ... before its leader advances it
-      a = rel_angle(p);
-    }
-    // predecessor on the ring inside this group: the highest same-ring lane below this one
-    const int pl = below ? 63 - __clzll((long long)below) : lane;
-    double a_prev = __shfl(a, pl);
-    if (valid) {
-      bool has_prev = below != 0;
-      if (!has_prev) {                                       // leader of its ring in this group: what the wave saw before
-        a_prev = s_lasta[wave][r];
-        has_prev = !isnan(a_prev);
-        if (!has_prev) s_firsta[wave][r] = a;
-      }
-      if ((m >> lane) == 1ull) s_lasta[wave][r] = a;         // last lane of the ring in this group (after the leader's read)
-      if (has_prev && a < a_prev) atomicMin(&s_wrap[r], dst);
-      // :151; behind a wrap point the angle carries +2 pi.  No ring id is stored here: a ring's ids are one constant over its
-      // output range (filled below with full-width stores; 2-byte stores scattered over 16 ring ranges were written to
-      // memory as partial lines, PMC: 0.83 GB written per 1 024 scans for 0.43 GB of output)
-      const double aw = dst >= s_early[r] ? a + two_pi : a;
-      out_pts[dst] = make_float4(p.x, p.y, p.z, (float)(aw / two_pi * prm.scan_period));
-    }
-    }
-  }
+  prep_pass_b(in, in_ring, w0, w1, lane, prm.min_range_sq, ring_bits, start_ori, prm.scan_period,
+              s_cur[wave], s_lasta[wave], s_firsta[wave], s_wrap, s_early, out_pts);
   __syncthreads();
-  // predecessor in an earlier wave: the first point of (wave, ring) against the last point of the nearest earlier wave
+  // predecessor in an earlier slice: the first point of (wave, ring) against the last point of the nearest earlier wave
   // that holds the ring.  The ring's output range is split among the waves in order, so (wave, ring) starts where the
-  // previous wave's cursor ended.
+  // previous wave's cursor ended.  (extract_prepare_finish_kernel makes the same test over S global counts.)
   if (tid < kMaxRings) {
     const int r = tid;
     int base = s_off[r];
@@ -300,22 +367,9 @@ __global__ void __launch_bounds__(1024) extract_prepare_kernel(ExtractView v, Ex
     }
   }
   __syncthreads();
-  // relative time (stored in both `time` and `intensity`, :152-153): from a ring's wrap point on, the +2 pi candidate.  What
-  // lies behind an EARLY wrap point has it already (s_wrap == s_early there); a later wrap (the sweep passing the start
-  // direction again at the end of the scan) re-derives the angle of the few points behind it from their coordinates,
-  // which are stored unchanged, with the same arithmetic as the pass above
-  for (int r = wave; r < kMaxRings; r += 16) {
-    const int lo = s_wrap[r], hi = min(s_early[r], s_off[r + 1]);
-    if (lo >= hi) continue;                                  // no wrap on this ring (lo = INT_MAX), or an early one
-    for (int i = lo + lane; i < hi; i += 64) {
-      const float4 p = out_pts[i];
-      out_pts[i].w = (float)((rel_angle(p) + two_pi) / two_pi * prm.scan_period);
-    }
-  }
-  // ring ids: constant runs
   for (int r = wave; r < kMaxRings; r += 16)
-    for (int i = s_off[r] + lane; i < s_off[r + 1]; i += 64) out_ring[i] = (uint16_t)r;
-  if (tid == 0) v.n_full[b] = N;
+    prep_ring_tail(out_pts, out_ring, r, s_off[r], s_off[r + 1], s_wrap[r], min(s_early[r], s_off[r + 1]), lane, start_ori, prm.scan_period);
+  if (tid == 0) v.n_full[b] = s_off[kMaxRings];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -323,11 +377,11 @@ __global__ void __launch_bounds__(1024) extract_prepare_kernel(ExtractView v, Ex
 // One 64-beam sweep (~130 k points, two f64 atan2 each) kept the single workgroup above busy for 326 us while 255 compute
 // units idled (profiles/r05_slam64_*).  The two slice passes need the populations of ALL slices between them, so the
 // split is three launches on the stream instead of a device-wide barrier inside one:
-//   extract_prepare_count_kernel    pass A of 16 slices per workgroup -> populations of (slice, ring), per-workgroup ring totals
-//   extract_prepare_scatter_kernel  cursors from those, the early-wrap pre-pass (every workgroup repeats it: 256 points), pass B
-//   extract_prepare_finish_kernel   wrap test across slices, late-wrap time fix-up and ring ids of the rings r = g (mod G)
-// A slice is still a contiguous piece of the driver-order cloud walked by one wavefront with the arithmetic of the kernel
-// above, and a wrap point is the ring's smallest output index with a < a_prev whoever finds it: outputs are bit-identical.
+//   extract_prepare_count_kernel    prep_pass_a of 16 slices per workgroup -> populations of (slice, ring), per-workgroup ring totals
+//   extract_prepare_scatter_kernel  cursors from those, prep_early_wraps (every workgroup repeats it: 256 points), prep_pass_b
+//   extract_prepare_finish_kernel   wrap test across slices, prep_ring_tail of the rings r = g (mod G)
+// A slice is still a contiguous piece of the driver-order cloud walked by one wavefront through the very functions the kernel
+// above calls, and a wrap point is the ring's smallest output index with a < a_prev whoever finds it: outputs are bit-identical.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct PrepSplitView {
   int* cnt;            // B x S x kMaxRings: population of (slice, ring)
@@ -363,72 +417,17 @@ inline PrepSplitView prep_split_view(void* base, int B, int G) {
   return sv;
 }
 
-constexpr int kPrepGroups = 4;           // 64-point groups per iteration with their loads issued up front (as above)
-
-// slice [w0, w1) of wavefront `wave` of workgroup g: slices are multiples of 64 points, so a 64-point group never straddles two
-__device__ __forceinline__ void prep_slice_bounds(int n, int S, int sl, int& w0, int& w1) {
-  const int slice = ((n + S - 1) / S + 63) & ~63;
-  w0 = (int)min((long long)sl * slice, (long long)n); w1 = min(w0 + slice, n);
-}
-
-// the verdict of pass A over the whole scan, from the workgroups' reports: [0] first valid point, [1] bad ring, [2] ring-id bits
-__device__ __forceinline__ void prep_head_reduce(const int* __restrict__ head, int G, int* s_flag) {
-  int f = 0x7fffffff, bd = 0, rm = 0;
-  for (int g = 0; g < G; g++) { f = min(f, head[4 * g]); bd |= head[4 * g + 1]; rm = max(rm, head[4 * g + 2]); }
-  s_flag[0] = f; s_flag[1] = bd; s_flag[2] = 32 - __clz(rm | 1);
-}
-
-__device__ __forceinline__ double prep_rel_angle(const float4 p, double start_ori) {
-  // :139-142, see rel_angle in extract_prepare_kernel
-  const double two_pi = 2 * 3.14159265358979323846;
-  const double ori = -atan2((double)p.y, (double)p.x);
-  double a = ori - start_ori + two_pi;
-  if (a >= two_pi) a -= two_pi;
-  if (a >= two_pi) a -= two_pi;
-  return a;
-}
-
 __global__ void __launch_bounds__(1024) extract_prepare_count_kernel(ExtractView v, ExtractParams prm, PrepSplitView sv) {
   __shared__ int s_cur[16][kMaxRings];
-  __shared__ int s_first[16], s_badw[16], s_rmax[16];
+  __shared__ int s_head[16 * 3];
   const int g = blockIdx.x, b = blockIdx.y, G = sv.G, S = 16 * G, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int o = v.off[b];
   const int n = v.off[b + 1] - o;
-  const float4* in = v.in_pts + o;
-  const uint16_t* in_ring = v.in_ring + o;
   for (int k = tid; k < 16 * kMaxRings; k += 1024) (&s_cur[0][0])[k] = 0;
   __syncthreads();
   int w0, w1;
   prep_slice_bounds(n, S, 16 * g + wave, w0, w1);
-  int first = 0x7fffffff, bad = 0, rmax = 0;
-  for (int g0 = w0; g0 < w1; g0 += 64 * kPrepGroups) {
-    float4 pp[kPrepGroups]; int rr[kPrepGroups];
-#pragma unroll
-    for (int u = 0; u < kPrepGroups; u++) {
-      const int i = g0 + 64 * u + lane;
-      pp[u] = make_float4(0, 0, 0, 0); rr[u] = 0;
-      if (i < w1) { pp[u] = in[i]; rr[u] = in_ring[i]; }
-    }
-#pragma unroll
-    for (int u = 0; u < kPrepGroups; u++) {
-      const int gq = g0 + 64 * u;
-      if (gq >= w1) break;
-      const int i = gq + lane;
-      bool valid = false;
-      int r = -1;
-      if (i < w1) {
-        valid = point_valid(pp[u], prm.min_range_sq);
-        if (valid) { r = rr[u]; if (r >= kMaxRings) { bad = 1; valid = false; } }   // CHECK_LT(point.ring, 128), :136
-      }
-      const unsigned long long any_valid = __ballot(valid);
-      if (any_valid && first == 0x7fffffff) first = gq + (__ffsll((long long)any_valid) - 1);
-      if (valid) { atomicAdd(&s_cur[wave][r], 1); rmax = max(rmax, r); }
-    }
-  }
-  bad = __any(bad) ? 1 : 0;
-#pragma unroll
-  for (int o2 = 32; o2 > 0; o2 >>= 1) rmax = max(rmax, __shfl_xor(rmax, o2));
-  if (lane == 0) { s_first[wave] = first; s_badw[wave] = bad; s_rmax[wave] = rmax; }
+  prep_pass_a(v.in_pts + o, v.in_ring + o, w0, w1, lane, prm.min_range_sq, s_cur[wave], s_head + 3 * wave);
   __syncthreads();
   int* cnt = sv.cnt + ((size_t)b * S + 16 * g) * kMaxRings;
   for (int k = tid; k < 16 * kMaxRings; k += 1024) cnt[k] = (&s_cur[0][0])[k];
@@ -439,10 +438,9 @@ __global__ void __launch_bounds__(1024) extract_prepare_count_kernel(ExtractView
     sv.wg_tot[((size_t)b * G + g) * kMaxRings + tid] = t;
   }
   if (tid == 0) {
-    int f = 0x7fffffff, bd = 0, rm = 0;
-    for (int w = 0; w < 16; w++) { f = min(f, s_first[w]); bd |= s_badw[w]; rm = max(rm, s_rmax[w]); }
     int* head = sv.head + ((size_t)b * G + g) * 4;
-    head[0] = f; head[1] = bd; head[2] = rm; head[3] = 0;
+    prep_head_merge(s_head, 16, 3, head);
+    head[3] = 0;
   }
 }
 
@@ -462,7 +460,7 @@ __global__ void __launch_bounds__(1024) extract_prepare_scatter_kernel(ExtractVi
   const int n = v.off[b + 1] - o;
   const float4* in = v.in_pts + o;
   const uint16_t* in_ring = v.in_ring + o;
-  if (tid == 0) prep_head_reduce(sv.head + (size_t)b * G * 4, G, s_flag);
+  if (tid == 0) prep_head_reduce(sv.head + (size_t)b * G * 4, G, 4, s_flag);
   for (int k = tid; k < 16 * kMaxRings; k += 1024) (&s_lasta[0][0])[k] = __longlong_as_double(0x7ff8000000000000ll);
   // ring totals of the scan and what the workgroups in front of this one hold of each ring: at most 16 + 16 independent loads
   if (tid < kMaxRings) {
@@ -477,16 +475,7 @@ __global__ void __launch_bounds__(1024) extract_prepare_scatter_kernel(ExtractVi
     s_wrap[tid] = total;                                      // borrowed as the ring total
   }
   __syncthreads();
-  if (s_flag[1] || s_flag[0] == 0x7fffffff) {
-    if (g == 0) {
-      if (tid == 0) {
-        v.status[b] = s_flag[1] ? 5 /*MSFL_BAD_RING*/ : 3 /*MSFL_BAD_ARG: empty valid cloud, CHECK :186,:200*/;
-        v.n_full[b] = 0; v.n_sharp[b] = 0; v.n_less_sharp[b] = 0; v.n_flat[b] = 0; v.n_less_flat[b] = 0;
-      }
-      if (tid <= kMaxRings) v.ring_tab[b * (kMaxRings + 1) + tid] = 0;
-    }
-    return;
-  }
+  if (prep_refused(v, b, tid, s_flag, g == 0)) return;
   if (tid == 0) {
     int run = 0;
     for (int r = 0; r < kMaxRings; r++) { s_off[r] = run; run += s_wrap[r]; }
@@ -506,81 +495,15 @@ __global__ void __launch_bounds__(1024) extract_prepare_scatter_kernel(ExtractVi
   __syncthreads();
   const int ring_bits = __builtin_amdgcn_readfirstlane(s_flag[2]);
   const double start_ori = s_start_ori;
-  const double two_pi = 2 * 3.14159265358979323846;
-  float4* out_pts = v.full_pts + o;
-  // ---- early wraps over the first 256 points of the CLOUD (see the kernel above; any prefix gives the same outputs) ----
-  if (wave == 0) {
+  if (wave == 0) {                                           // every workgroup repeats the pre-pass over the CLOUD's head
     const int pre_end = min(n, 256);
-    for (int gq = 0; gq < pre_end; gq += 64) {
-      const int i = gq + lane;
-      float4 p = make_float4(0, 0, 0, 0);
-      int r = -1;
-      bool valid = false;
-      if (i < pre_end) { p = in[i]; valid = point_valid(p, prm.min_range_sq); if (valid) r = in_ring[i]; }
-      const unsigned long long m = same_ring_lanes(valid, r, ring_bits);
-      const unsigned long long below = m & ((1ull << lane) - 1ull);
-      const double a = valid ? prep_rel_angle(p, start_ori) : 0.0;
-      const int pl = below ? 63 - __clzll((long long)below) : lane;
-      double a_prev = __shfl(a, pl);
-      if (valid) {
-        const int seen = s_pre_cnt[r];
-        bool has_prev = below != 0;
-        if (!has_prev) { a_prev = s_pre_last[r]; has_prev = !isnan(a_prev); }
-        if ((m >> lane) == 1ull) { s_pre_last[r] = a; s_pre_cnt[r] = seen + __popcll(m); }
-        if (has_prev && a < a_prev) atomicMin(&s_early[r], s_off[r] + seen + __popcll(below));
-      }
-    }
+    prep_early_wraps(in, in_ring, pre_end, lane, prm.min_range_sq, ring_bits, start_ori, s_off, s_pre_last, s_pre_cnt, s_early);
   }
   __syncthreads();
-  // ---- pass B over this wavefront's slice ----
   int w0, w1;
   prep_slice_bounds(n, S, 16 * g + wave, w0, w1);
-  for (int g0 = w0; g0 < w1; g0 += 64 * kPrepGroups) {
-    float4 pp[kPrepGroups]; int rr[kPrepGroups];
-#pragma unroll
-    for (int u = 0; u < kPrepGroups; u++) {
-      const int i = g0 + 64 * u + lane;
-      pp[u] = make_float4(0, 0, 0, 0); rr[u] = 0;
-      if (i < w1) { pp[u] = in[i]; rr[u] = in_ring[i]; }
-    }
-#pragma unroll
-    for (int u = 0; u < kPrepGroups; u++) {
-      const int gq = g0 + 64 * u;
-      if (gq >= w1) break;
-      const int i = gq + lane;
-      const float4 p = pp[u];
-      int r = -1;
-      bool valid = false;
-      if (i < w1) {
-        valid = point_valid(p, prm.min_range_sq);
-        if (valid) r = rr[u];
-      }
-      int dst = 0;
-      const unsigned long long m = same_ring_lanes(valid, r, ring_bits);
-      const unsigned long long below = m & ((1ull << lane) - 1ull);
-      double a = 0.0;
-      if (valid) {
-        const int cur = s_cur[wave][r];
-        dst = cur + __popcll(below);
-        if (below == 0) s_cur[wave][r] = cur + __popcll(m);
-        a = prep_rel_angle(p, start_ori);
-      }
-      const int pl = below ? 63 - __clzll((long long)below) : lane;
-      double a_prev = __shfl(a, pl);
-      if (valid) {
-        bool has_prev = below != 0;
-        if (!has_prev) {
-          a_prev = s_lasta[wave][r];
-          has_prev = !isnan(a_prev);
-          if (!has_prev) s_firsta[wave][r] = a;
-        }
-        if ((m >> lane) == 1ull) s_lasta[wave][r] = a;
-        if (has_prev && a < a_prev) atomicMin(&s_wrap[r], dst);
-        const double aw = dst >= s_early[r] ? a + two_pi : a;
-        out_pts[dst] = make_float4(p.x, p.y, p.z, (float)(aw / two_pi * prm.scan_period));
-      }
-    }
-  }
+  prep_pass_b(in, in_ring, w0, w1, lane, prm.min_range_sq, ring_bits, start_ori, prm.scan_period,
+              s_cur[wave], s_lasta[wave], s_firsta[wave], s_wrap, s_early, v.full_pts + o);
   __syncthreads();
   double* firsta = sv.firsta + ((size_t)b * S + 16 * g) * kMaxRings;
   double* lasta = sv.lasta + ((size_t)b * S + 16 * g) * kMaxRings;
@@ -598,9 +521,9 @@ __global__ void __launch_bounds__(1024) extract_prepare_finish_kernel(ExtractVie
   __shared__ int s_flag[3];
   const int g = blockIdx.x, b = blockIdx.y, G = sv.G, S = 16 * G, own = kMaxRings / G, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int o = v.off[b];
-  if (tid == 0) prep_head_reduce(sv.head + (size_t)b * G * 4, G, s_flag);
+  if (tid == 0) prep_head_reduce(sv.head + (size_t)b * G * 4, G, 4, s_flag);
   __syncthreads();
-  if (s_flag[1] || s_flag[0] == 0x7fffffff) return;          // the scatter kernel reported it
+  if (prep_refused(v, b, tid, s_flag, false)) return;        // the scatter kernel reported it
   const int* cnt = sv.cnt + (size_t)b * S * kMaxRings;
   for (int k = tid; k < own * S; k += 1024) { const int j = k / S, sl = k - j * S; s_cnt[k] = cnt[sl * kMaxRings + g + G * j]; }
   if (tid < own) {
@@ -610,6 +533,7 @@ __global__ void __launch_bounds__(1024) extract_prepare_finish_kernel(ExtractVie
   }
   __syncthreads();
   // predecessor in an earlier slice: the first point of (slice, ring) against the last point of the nearest earlier slice that holds the ring
+  // (extract_prepare_kernel makes the same test over its 16 LDS cursor ends)
   const double* firsta = sv.firsta + (size_t)b * S * kMaxRings;
   const double* lasta = sv.lasta + (size_t)b * S * kMaxRings;
   const int* start = sv.start + (size_t)b * S * kMaxRings;
@@ -623,19 +547,9 @@ __global__ void __launch_bounds__(1024) extract_prepare_finish_kernel(ExtractVie
   __syncthreads();
   const int* tab = v.ring_tab + b * (kMaxRings + 1);
   const double start_ori = sv.start_ori[b];
-  const double two_pi = 2 * 3.14159265358979323846;
-  float4* out_pts = v.full_pts + o;
-  uint16_t* out_ring = v.full_ring + o;
   for (int j = wave; j < own; j += 16) {
     const int r = g + G * j, r0 = tab[r], r1 = tab[r + 1];
-    const int lo = s_wrap[j], hi = min(sv.early[(size_t)b * kMaxRings + r], r1);
-    if (lo < hi) {                                           // a late wrap: the +2 pi time for what lies behind it (lo = INT_MAX: none)
-      for (int i = lo + lane; i < hi; i += 64) {
-        const float4 p = out_pts[i];
-        out_pts[i].w = (float)((prep_rel_angle(p, start_ori) + two_pi) / two_pi * prm.scan_period);
-      }
-    }
-    for (int i = r0 + lane; i < r1; i += 64) out_ring[i] = (uint16_t)r;
+    prep_ring_tail(v.full_pts + o, v.full_ring + o, r, r0, r1, s_wrap[j], min(sv.early[(size_t)b * kMaxRings + r], r1), lane, start_ori, prm.scan_period);
   }
   if (g == 0 && tid == 0) v.n_full[b] = tab[kMaxRings];
 }

@@ -52,11 +52,22 @@ def test_the_figures_are_the_kernels_constants():
     assert "constboolin_lds=cnt<=kPickSector;" in cuh
     assert "constintstart=s+5,end=s+len-6;" in cuh and "(end-start>=6)" in cuh
     assert "constintsp=start+(end-start)*j/prm.sectors;" in cuh and "constintep=start+(end-start)*(j+1)/prm.sectors-1;" in cuh
-    # the early-wrap pre-pass: the cloud's first 256 points, in both forms
+    # the early-wrap pre-pass: the cloud's first 256 points, in both forms, through the one body
     assert cuh.count("constintpre_end=min(w1,256);") == 1 and cuh.count("constintpre_end=min(n,256);") == 1
-    # slices: multiples of 64, 16 per workgroup; four 64-point groups per iteration
-    assert "constintslice=((n+15)/16+63)&~63;" in cuh and "constintslice=((n+S-1)/S+63)&~63;" in cuh and "S=16*G" in cuh
-    assert "#defineMSFL_PREP_GROUPS4" in cuh and "constexprintkPrepGroups=4;" in cuh
+    assert cuh.count("pre_end=") == 2 and cuh.count("prep_early_wraps(in,in_ring,pre_end,lane,") == 2
+    assert cuh.count("atomicMin(&s_early[r],s_off[r]+seen+__popcll(below));") == 1
+    # slices: multiples of 64, 16 per workgroup, one rule for both forms; four 64-point groups per iteration, one knob
+    assert cuh.count("constintslice=") == 1 and cuh.count("constintslice=((n+S-1)/S+63)&~63;") == 1 and "S=16*G" in cuh
+    assert cuh.count("prep_slice_bounds(n,16,wave,w0,w1);") == 1 and cuh.count("prep_slice_bounds(n,S,16*g+wave,w0,w1);") == 2
+    assert cuh.count("#ifndefMSFL_PREP_GROUPS#defineMSFL_PREP_GROUPS4#endif") == 1 and cuh.count("#defineMSFL_PREP_GROUPS") == 1
+    assert cuh.count("constexprintkPrepGroups=") == 1 and cuh.count("constexprintkPrepGroups=MSFL_PREP_GROUPS;") == 1
+    assert "kGroups" not in cuh.replace("kPrepGroups", "")
+    # the slice passes and the relative angle are written once: pass A's count, pass B's wrap test and time store
+    assert cuh.count("atomicAdd(&cur[r],1);") == 1 and "atomicAdd(&s_cur" not in cuh
+    assert cuh.count("atomicMin(&s_wrap[r],dst);") == 1
+    assert cuh.count("out_pts[dst]=make_float4(p.x,p.y,p.z,(float)(aw/kPrepTwoPi*scan_period));") == 1 and cuh.count("out_pts[dst]=") == 1
+    assert cuh.count("doublea=ori-start_ori+kPrepTwoPi;if(a>=kPrepTwoPi)a-=kPrepTwoPi;if(a>=kPrepTwoPi)a-=kPrepTwoPi;") == 1
+    assert cuh.count("-atan2((double)p.y,(double)p.x)") == 1 and "rel_angle=[" not in cuh
     # the curvature tile and its halo
     assert "__shared__float4s_p[256+10];" in cuh and "constintg0=o+(int)blockIdx.x*256;" in cuh and "div_up(longest,256)" in host
     assert "if(i>=5&&i<N-5){" in cuh
