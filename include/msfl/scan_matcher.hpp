@@ -414,6 +414,26 @@ class HybridGrid {
     return info;
   }
 
+  // Not in the reference (its HybridGrid never removes a point): remove every stored point that `scan` (sensor frame), taken at the
+  // map pose `pose`, sees through (msfl_grid_carve; config == nullptr: msfl_carve_default_config).  removed != nullptr receives the
+  // removed points, cells ascending and in stored order inside a cell, as msfl_grid_dump would have delivered them.
+  msfl_grid_carve_info Carve(const std::shared_ptr<const PointCloud<PointType>>& scan, const Rigid3d& pose, const msfl_carve_config* config = nullptr,
+                             std::vector<msfl_point>* removed = nullptr) {
+    msfl_grid_carve_info info{};
+    const std::vector<msfl_point> in = adapter::Pack(*scan);
+    double v[7];
+    adapter::RigidToArray(pose, v);
+    int n_points = 0;
+    if (removed) {
+      detail::Check(msfl_grid_size(g_, &n_points, nullptr), h_, "msfl_grid_size");
+      removed->resize(static_cast<std::size_t>(n_points) + 1);
+    }
+    detail::Check(msfl_grid_carve(g_, in.data(), static_cast<int>(in.size()), v, config, removed ? removed->data() : nullptr, n_points, MSFL_MEM_HOST,
+                                  &info), h_, "msfl_grid_carve");
+    if (removed) removed->resize(static_cast<std::size_t>(info.n_points_removed));
+    return info;
+  }
+
  private:
   msfl_handle* h_ = nullptr;
   msfl_grid* g_ = nullptr;

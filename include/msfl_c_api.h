@@ -803,6 +803,58 @@ typedef struct msfl_grid_load_info {
 msfl_status msfl_grid_load_cells(msfl_grid* g, const int* cells, int n_cells, const msfl_point* pts, int n_points, msfl_mem mem,
                                  int* conflict, msfl_grid_load_info* info);
 
+/* Carve: remove the points a later scan sees through (docs/kernels/grid_store.md, "Carve", has the definition in full).
+   HybridGrid never removes a point, so whatever stood somewhere once (a parked car, a person, a closed door) stays in a resident
+   map for good.  msfl_grid_carve takes one scan in the sensor frame and the sensor's map pose: a stored point that lies on a ray
+   along which the scan measured a return well beyond it is not there any more and leaves the store.
+     range image : n_row x n_col pixels over the elevations [elev_low_deg, elev_high_deg) and the full turn; a point's pixel is found by
+                   bisection over f32 compares against the host-built tables below (no atan2).  near[pixel] = minimum range r of the
+                   scan's points there, +inf when empty.  A point has no pixel when it is not finite, lies on the sensor's axis
+                   (x*x + y*y == 0), outside the elevations, or !(r >= min_range) || r > max_range.
+     limit image : lim[pixel] = 0 where near[pixel] is empty (no evidence), else the minimum of near over rows +-window_row (clamped
+                   to the image) and columns +-window_col (wrapping round the turn).
+     the test    : a stored point p goes through the inverse of pose7 exactly as msfl_transform_cloud transforms; it is removed iff
+                   it has a pixel and (r * (1 + margin_rel)) + margin_abs < lim[pixel], all in f32.
+     the store   : a cell keeps its surviving points in stored order; a cell left with none leaves the table; every other cell, the
+                   surround stamps and the order of the table stay as they are.  The pool is not compacted.
+     removed     : NULL, or `capacity` points (host or device memory as `mem` says) that receive the removed points in the order of
+                   msfl_grid_dump (cells ascending, stored order inside a cell).  More of them than `capacity` refuses the call as a
+                   whole exactly like msfl_grid_crop: map unchanged bit for bit, info->applied = 0, the counts are filled, MSFL_CAPACITY.
+     scan, pose7 : host or device memory as `mem` says.  n == 0 is a scan that saw nothing: nothing is removed.
+     cfg         : NULL = msfl_carve_default_config.
+   MSFL_BAD_ARG: info or pose7 NULL, n < 0, scan NULL with n > 0, removed with a negative capacity, a configuration outside
+   n_col even in [2, 2048], n_row in [1, 128], -90 < elev_low_deg < elev_high_deg < 90, 0 <= min_range < max_range, margins >= 0,
+   windows in [0, 4], everything finite; a pose that is not finite (a device-resident one is refused on the device: map unchanged,
+   info->applied = 0, the same status). */
+typedef struct msfl_carve_config {
+  int n_col, n_row;                        /* columns of the full turn (even), rows between the two elevations */
+  float elev_low_deg, elev_high_deg;       /* row k spans the elevations [e_k, e_k+1), e_k = low + (high - low) k / n_row */
+  float min_range, max_range;              /* metres; scan points and stored points outside have no pixel */
+  float margin_abs, margin_rel;            /* how far beyond a stored point the scan must have seen */
+  int window_col, window_row;              /* half widths of the limit image's window */
+} msfl_carve_config;
+
+/* The 16-beam sensor of the synthetic worlds (-15 .. +15 degrees, 2 degrees apart): 720 x 16 pixels, one beam per row and the rows
+   centred on the beams (-16 .. +16 degrees), 0.3 .. 100 m, margins 0.3 m + 2 %, a window of 1 x 1 pixels. */
+void msfl_carve_default_config(msfl_carve_config* cfg);
+
+/* The tables the kernels bisect over, built in double and rounded to f32 (pure host function, no handle):
+     cc[k], cs[k] = cos, sin(2 pi k / n_col), k < n_col / 2;   ec[k], es[k] = cos, sin(e_k in radians), k <= n_row.
+   cc, cs: n_col / 2 floats each; ec, es: n_row + 1 floats each.  MSFL_BAD_ARG: a null pointer, a configuration outside the limits. */
+msfl_status msfl_carve_tables(const msfl_carve_config* cfg, float* cc, float* cs, float* ec, float* es);
+
+typedef struct msfl_grid_carve_info {
+  int n_points_removed, n_cells_emptied;   /* what this call removed (full counts, also when it was refused) */
+  int n_cells, n_points;                   /* live sizes after the call */
+  int n_tested;                            /* stored points that had a pixel */
+  int n_pixels;                            /* non-empty pixels of the scan's range image */
+  int applied;                             /* 1, or 0 when the call was refused: map unchanged */
+  int reserved_;
+} msfl_grid_carve_info;
+
+msfl_status msfl_grid_carve(msfl_grid* g, const msfl_point* scan, int n, const double pose7[7], const msfl_carve_config* cfg,
+                            msfl_point* removed, int capacity, msfl_mem mem, msfl_grid_carve_info* info);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* The per-scan SLAM step, device-resident (BASELINE configs[2]: sequential odometry + mapping).*/

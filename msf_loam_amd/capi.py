@@ -32,7 +32,8 @@ PROTOTYPES = dict(t.split("=") for t in """
     msfl_voxel_downsample_batch=i:pippppfppi msfl_voxel_downsample_batch_pair=i:pippppfppppfppi msfl_transform_cloud=i:ppippi msfl_delta_qp=i:pppippi
     msfl_deskew_cloud=i:pppipppi msfl_undistort_cloud=i:pppii msfl_grid_create=i:pffp msfl_grid_destroy=v:p msfl_grid_insert_scan=i:ppii
     msfl_grid_get_surrounded=i:ppippipi msfl_grid_size=i:ppp msfl_grid_dump=i:ppipi msfl_grid_dump_cells=i:ppip msfl_grid_stats=i:pp
-    msfl_grid_crop=i:ppppiip msfl_grid_crop_tiles=i:ppppipiip msfl_grid_load_cells=i:ppipiipp msfl_slam_default_config=v:p msfl_slam_create=i:ppip
+    msfl_grid_crop=i:ppppiip msfl_grid_crop_tiles=i:ppppipiip msfl_grid_load_cells=i:ppipiipp msfl_carve_default_config=v:p msfl_carve_tables=i:ppppp
+    msfl_grid_carve=i:ppipppiip msfl_slam_default_config=v:p msfl_slam_create=i:ppip
     msfl_slam_destroy=v:p msfl_slam_add_scan=i:pppiip msfl_slam_add_scan_imu=i:pppiipp msfl_slam_get_result=i:pip msfl_slam_set_uncertainty=i:pid
     msfl_slam_get_uncertainty=i:pipp msfl_slam_set_degeneracy=i:piidd msfl_slam_get_degeneracy=i:pipp msfl_slam_set_outlier_rejection=i:ppp
     msfl_slam_get_rejection=i:pipp msfl_slam_set_next_prior=i:ppp msfl_slam_set_map_window=i:ppi msfl_slam_get_map_window=i:pipp
@@ -270,6 +271,45 @@ class GridLoadInfo(C.Structure):
 
     def as_tuple(self):
         return (self.n_cells_loaded, self.n_points_loaded, self.n_cells, self.n_points, self.n_conflicts, self.n_bad_points, self.applied)
+
+
+class CarveConfig(C.Structure):
+    """msfl_carve_config (include/msfl_c_api.h, "Carve")."""
+    _fields_ = [("n_col", C.c_int), ("n_row", C.c_int), ("elev_low_deg", C.c_float), ("elev_high_deg", C.c_float),
+                ("min_range", C.c_float), ("max_range", C.c_float), ("margin_abs", C.c_float), ("margin_rel", C.c_float),
+                ("window_col", C.c_int), ("window_row", C.c_int)]
+
+
+def carve_config(**kw):
+    """msfl_carve_default_config with the given fields replaced."""
+    c = CarveConfig()
+    load().msfl_carve_default_config(C.byref(c))
+    for k, v in kw.items():
+        if k not in dict(CarveConfig._fields_):
+            raise TypeError("msfl_carve_config has no field " + k)
+        setattr(c, k, v)
+    return c
+
+
+def carve_tables(config=None):
+    """msfl_carve_tables: (cc, cs, ec, es) as f32 arrays, the tables msfl_grid_carve bisects over (a pure host call)."""
+    c = config if config is not None else carve_config()
+    cc, cs = np.zeros(max(c.n_col // 2, 1), np.float32), np.zeros(max(c.n_col // 2, 1), np.float32)
+    ec, es = np.zeros(max(c.n_row + 1, 1), np.float32), np.zeros(max(c.n_row + 1, 1), np.float32)
+    s = load().msfl_carve_tables(C.byref(c), _vp(cc), _vp(cs), _vp(ec), _vp(es))
+    if s != OK:
+        raise MsflError(s, "msfl_carve_tables")
+    return cc, cs, ec, es
+
+
+class GridCarveInfo(C.Structure):
+    """msfl_grid_carve_info; `status` (a Python attribute) is the msfl_status of the call that filled it."""
+    _fields_ = [("n_points_removed", C.c_int), ("n_cells_emptied", C.c_int), ("n_cells", C.c_int), ("n_points", C.c_int),
+                ("n_tested", C.c_int), ("n_pixels", C.c_int), ("applied", C.c_int), ("reserved_", C.c_int)]
+    status = OK
+
+    def as_tuple(self):
+        return (self.n_points_removed, self.n_cells_emptied, self.n_cells, self.n_points, self.n_tested, self.n_pixels, self.applied)
 
 
 GRID_STATS = ("n_points", "n_cells", "pool_top", "pool_capacity_points", "cell_capacity", "device_bytes")
@@ -1083,6 +1123,35 @@ class Grid(_Owner):
     def load_cells_device(self, cells, pts_ptr, n_points, allow=(), want_conflicts=False):
         """msfl_grid_load_cells with the points in device memory (`cells` stays a host array)."""
         return self._load(cells, _vp(pts_ptr), n_points, MEM_DEVICE, allow, want_conflicts, "msfl_grid_load_cells(device)")
+
+
+    def carve(self, scan, pose, config=None, keep_removed=False, capacity=None, allow=()):
+        """msfl_grid_carve: remove every stored point that `scan` (sensor frame), taken at the map pose `pose`, sees through.
+        Returns (GridCarveInfo, removed): the removed points in dump() order with keep_removed, else None.  capacity: room for them
+        (default: every live point).  A refused call raises unless its status is in `allow` (then info.applied == 0 and the array
+        is empty)."""
+        scan = _pts(scan)
+        pose = np.ascontiguousarray(pose, dtype=np.float64)
+        info = GridCarveInfo()
+        rm, cap = None, 0
+        if keep_removed:
+            cap = self.size()[0] if capacity is None else int(capacity)
+            rm = np.zeros((max(cap, 1), 4), np.float32)
+        cfg = C.byref(config) if config is not None else None
+        info.status = self._check(self.lib.msfl_grid_carve(self.g, _vp(scan), len(scan), _vp(pose), cfg, _vp(rm), cap, MEM_HOST, C.byref(info)),
+                                  "msfl_grid_carve", allow)
+        if not keep_removed:
+            return info, None
+        return info, rm[:info.n_points_removed if info.applied else 0].copy()
+
+    def carve_device(self, scan_ptr, n, pose_ptr, config=None, removed_ptr=None, capacity=0, allow=()):
+        """msfl_grid_carve with the scan, the pose (7 doubles) and the buffer for the removed points in device memory; returns the
+        GridCarveInfo."""
+        info = GridCarveInfo()
+        cfg = C.byref(config) if config is not None else None
+        info.status = self._check(self.lib.msfl_grid_carve(self.g, _vp(scan_ptr), int(n), _vp(pose_ptr), cfg, _vp(removed_ptr), int(capacity),
+                                                           MEM_DEVICE, C.byref(info)), "msfl_grid_carve(device)", allow)
+        return info
 
 
 class _BorrowedGrid(Grid):

@@ -29,6 +29,7 @@
 #include "msfl_extract.cuh"
 #include "msfl_odom.cuh"
 #include "msfl_grid.cuh"
+#include "msfl_carve.cuh"
 #include "msfl_keyframes.cuh"   // includes msfl_keyframes_host.h
 #include "msfl_deskew.cuh"
 #include "msfl_uncertainty.cuh"

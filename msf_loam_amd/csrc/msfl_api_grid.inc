@@ -18,6 +18,11 @@ struct msfl_grid_s {
   DevBuf crop;                                    // crop scratch: keep flag and rank per cell (cnt / off hold the evicted counts and offsets)
   DevBuf crop_cells;                              // msfl_grid_crop_tiles: {ix, iy, iz, count} of the evicted cells
   DevBuf load;                                    // load scratch: the staged cell list, then key, position, conflict flag, count and slab offset per listed cell
+  // carve scratch, allocated by the first msfl_grid_carve: the range and limit images, keep flag / rank / removed count / offset per
+  // cell, the bisection tables of carve_cfg (rebuilt when the configuration changes), the counters of the call in flight
+  DevBuf carve_img, carve_cells, carve_tab, carve_ctr;
+  msfl_carve_config carve_cfg{};
+  bool carve_tab_valid = false;
   PinBuf report;                                  // int[8] read-back: {points, cells, pool_top, bad, overflow, touched, work, surround_total}, then the int[8] crop info
   // What the host knows: exact sizes as of the newest insert whose report it has seen, plus the inserts enqueued since
   // (sequence number, point capacity).  Every launch bound and capacity decision derives from these upper bounds, so
@@ -365,9 +370,162 @@ msfl_status grid_surround_enqueue(msfl_grid* g, const float4* d_scan, const int*
   return MSFL_OK;
 }
 
+// ---- Carve (msfl_carve.cuh) -----------------------------------------------------------------------------------------------------
+
+bool carve_config_ok(const msfl_carve_config& c) {
+  const float f[6] = {c.elev_low_deg, c.elev_high_deg, c.min_range, c.max_range, c.margin_abs, c.margin_rel};
+  for (float v : f) if (!std::isfinite(v)) return false;
+  return c.n_col >= 2 && c.n_col <= kCarveMaxCol && (c.n_col & 1) == 0 && c.n_row >= 1 && c.n_row <= kCarveMaxRow &&
+         c.elev_low_deg > -90.f && c.elev_low_deg < c.elev_high_deg && c.elev_high_deg < 90.f && c.min_range >= 0.f && c.min_range < c.max_range &&
+         c.margin_abs >= 0.f && c.margin_rel >= 0.f && c.window_col >= 0 && c.window_col <= kCarveMaxWindow && c.window_row >= 0 &&
+         c.window_row <= kCarveMaxWindow;
+}
+
+// the tables in double, rounded to f32 (docs/kernels/grid_store.md states the two formulas)
+void carve_build_tables(const msfl_carve_config& c, float* cc, float* cs, float* ec, float* es) {
+  const double pi = 3.14159265358979323846;
+  for (int k = 0; k < c.n_col / 2; k++) {
+    const double a = 2.0 * pi * (double)k / (double)c.n_col;
+    cc[k] = (float)std::cos(a); cs[k] = (float)std::sin(a);
+  }
+  for (int k = 0; k <= c.n_row; k++) {
+    const double deg = (double)c.elev_low_deg + ((double)c.elev_high_deg - (double)c.elev_low_deg) * (double)k / (double)c.n_row;
+    const double e = deg * pi / 180.0;
+    ec[k] = (float)std::cos(e); es[k] = (float)std::sin(e);
+  }
+}
+
+// Stream-ordered carve with the scan `d_scan` (device, n points, sensor frame) taken at the device-resident `d_pose` (7 doubles).
+// d_removed: device buffer of `capacity` points for the removed points, or null (dropped).  info_dst: device int[8]
+// (msfl_grid_carve_info).  report_dst as in grid_insert_enqueue.  Takes a sequence number and flips the table parity like a crop:
+// the bounds come down when the report is applied.  The pool is not touched: a carved slab's tail is garbage for the next grid_pack.
+msfl_status grid_carve_enqueue(msfl_grid* g, const float4* d_scan, int n, const double* d_pose, const msfl_carve_config& cfg, float4* d_removed,
+                               int capacity, int* info_dst, int* report_dst = nullptr) {
+  msfl_handle* h = g->h;
+  hipStream_t st = h->stream;
+  GridState* gs = g->state.as<GridState>();
+  const int npix = cfg.n_col * cfg.n_row, half = cfg.n_col / 2;
+  if (!g->carve_ctr.p) {
+    HIPCHK(h, g->carve_ctr.reserve(CARVE_CTR_WORDS * sizeof(int)));
+    HIPCHK(h, hipMemsetAsync(g->carve_ctr.p, 0, CARVE_CTR_WORDS * sizeof(int), st));
+  }
+  if (!g->carve_tab_valid || std::memcmp(&g->carve_cfg, &cfg, sizeof(cfg)) != 0) {
+    float tab[kCarveMaxTab];
+    carve_build_tables(cfg, tab, tab + half, tab + 2 * half, tab + 2 * half + cfg.n_row + 1);
+    HIPCHK(h, g->carve_tab.reserve(kCarveMaxTab * sizeof(float)));
+    HIPCHK(h, h->pin.upload(g->carve_tab.p, tab, (size_t)carve_tab_size(cfg.n_col, cfg.n_row) * sizeof(float), st));
+    g->carve_cfg = cfg; g->carve_tab_valid = true;
+  }
+  HIPCHK(h, g->carve_img.reserve(2 * (size_t)npix * sizeof(float)));
+  unsigned* near_img = g->carve_img.as<unsigned>();
+  float* lim = g->carve_img.as<float>() + npix;
+  int* ctr = g->carve_ctr.as<int>();
+  const CarveCfg c{cfg.n_col, cfg.n_row, cfg.window_col, cfg.window_row, cfg.min_range, cfg.max_range, cfg.margin_abs, cfg.margin_rel,
+                   (const float*)g->carve_tab.as<float>()};
+  HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)near_img, (int)kCarveEmpty, (size_t)npix, st));
+  if (n > 0) hipLaunchKernelGGL(carve_fill_kernel, dim3(std::min(div_up(n, kCarveBlock), 1024)), dim3(kCarveBlock), 0, st, c, d_scan, n, near_img);
+  hipLaunchKernelGGL(carve_limit_kernel, dim3(div_up(npix, kCarveBlock)), dim3(kCarveBlock), 0, st, c, (const unsigned*)near_img, lim, ctr);
+  const int bound = (int)std::min<long long>(g->ub_cells, g->cell_cap);
+  int *keep = nullptr, *rank = nullptr, *rcnt = nullptr, *roff = nullptr;
+  if (bound > 0) {
+    const int cur = g->cur_tab, nxt = 1 - cur;
+    HIPCHK(h, g->carve_cells.reserve(4 * (size_t)bound * sizeof(int)));
+    keep = g->carve_cells.as<int>(); rank = keep + bound; rcnt = rank + bound; roff = rcnt + bound;
+    const unsigned long long* keys = g->ckey[cur].as<unsigned long long>();
+    const int* cstart = g->cstart[cur].as<int>();
+    const int* ccnt = g->ccnt[cur].as<int>();
+    float4* pool = g->pool[g->cur_pool].as<float4>();
+    hipLaunchKernelGGL(carve_count_kernel, dim3(std::min(bound, 4096)), dim3(kCarveBlock), 0, st, c, d_pose, (const float*)lim, keys, cstart, ccnt,
+                       (const float4*)pool, bound, g->d.resolution, keep, rcnt, ctr, (const GridState*)gs);
+    if (bound <= kGridOneBlockMax) {
+      hipLaunchKernelGGL(carve_scan_kernel, dim3(1), dim3(1024), 0, st, (const int*)keep, (const int*)rcnt, bound, rank, roff, (const GridState*)gs);
+    } else {
+      size_t tb = 0;
+      HIPCHK(h, rocprim::exclusive_scan(nullptr, tb, keep, rank, 0, (size_t)bound, rocprim::plus<int>(), st));
+      HIPCHK(h, h->idx_cub.reserve(tb));
+      HIPCHK(h, rocprim::exclusive_scan(h->idx_cub.p, tb, keep, rank, 0, (size_t)bound, rocprim::plus<int>(), st));
+      HIPCHK(h, rocprim::exclusive_scan(h->idx_cub.p, tb, rcnt, roff, 0, (size_t)bound, rocprim::plus<int>(), st));
+    }
+    hipLaunchKernelGGL(carve_apply_kernel, dim3(std::min(bound, 4096)), dim3(kCarveBlock), 0, st, c, d_pose, (const float*)lim, keys, cstart, ccnt,
+                       (const int*)g->cstamp[cur].as<int>(), g->ckey[nxt].as<unsigned long long>(), g->cstart[nxt].as<int>(), g->ccnt[nxt].as<int>(),
+                       g->cstamp[nxt].as<int>(), pool, (const int*)keep, (const int*)rank, (const int*)rcnt, (const int*)roff, bound, d_removed,
+                       capacity, (const GridState*)gs);
+    g->cur_tab = nxt;
+  }
+  hipLaunchKernelGGL(carve_finish_kernel, dim3(1), dim3(1), 0, st, gs, d_pose, (const int*)keep, (const int*)rank, (const int*)rcnt, (const int*)roff, bound,
+                     d_removed ? 1 : 0, capacity, ctr, info_dst, report_dst ? report_dst : g->report_dev.as<int>());
+  HIPCHK(h, hipGetLastError());
+  if (!report_dst) { HIPCHK(h, hipMemcpyAsync(g->report.p, g->report_dev.p, 16 * sizeof(int), hipMemcpyDeviceToHost, st)); g->pending = true; }
+  g->last_seq = g->next_seq++;
+  g->inflight.emplace_back(g->last_seq, 0);
+  return MSFL_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void msfl_carve_default_config(msfl_carve_config* cfg) {
+  if (!cfg) return;
+  cfg->n_col = 720; cfg->n_row = 16;
+  cfg->elev_low_deg = -16.f; cfg->elev_high_deg = 16.f;
+  cfg->min_range = 0.3f; cfg->max_range = 100.f;
+  cfg->margin_abs = 0.3f; cfg->margin_rel = 0.02f;
+  cfg->window_col = 1; cfg->window_row = 1;
+}
+
+msfl_status msfl_carve_tables(const msfl_carve_config* cfg, float* cc, float* cs, float* ec, float* es) {
+  if (!cfg || !cc || !cs || !ec || !es || !carve_config_ok(*cfg)) return MSFL_BAD_ARG;
+  carve_build_tables(*cfg, cc, cs, ec, es);
+  return MSFL_OK;
+}
+
+// Remove the points the scan sees through (msfl_c_api.h)
+msfl_status msfl_grid_carve(msfl_grid* g, const msfl_point* scan, int n, const double pose7[7], const msfl_carve_config* cfg, msfl_point* removed,
+                            int capacity, msfl_mem mem, msfl_grid_carve_info* info) {
+  if (!g) return MSFL_BAD_ARG;
+  msfl_handle* h = g->h;
+  msfl_status s = enter(h); if (s) return s;
+  msfl_carve_config c;
+  if (cfg) c = *cfg; else msfl_carve_default_config(&c);
+  if (!info || !pose7 || n < 0 || (n > 0 && !scan) || (removed && capacity < 0)) return fail(h, MSFL_BAD_ARG, "msfl_grid_carve: bad argument");
+  if (!carve_config_ok(c)) return fail(h, MSFL_BAD_ARG, "msfl_grid_carve: configuration outside its limits");
+  if (mem == MSFL_MEM_HOST)
+    for (int k = 0; k < 7; k++) if (!std::isfinite(pose7[k])) return fail(h, MSFL_BAD_ARG, "msfl_grid_carve: a pose that is not finite");
+  hipStream_t st = h->stream;
+  if (g->pending) { HIPCHK(h, hipStreamSynchronize(st)); (void)grid_read_report(g); }
+  const double* d_pose = pose7;
+  if (mem == MSFL_MEM_HOST) {
+    HIPCHK(h, g->pose.reserve(8 * sizeof(double)));
+    HIPCHK(h, h->pin.upload(g->pose.p, pose7, 7 * sizeof(double), st));
+    d_pose = g->pose.as<double>();
+  }
+  // staging of a host call: the scan, then room for the removed points (no more than the live points can go)
+  const float4* d_scan = reinterpret_cast<const float4*>(scan);
+  float4* d_rm = reinterpret_cast<float4*>(removed);
+  if (mem == MSFL_MEM_HOST) {
+    const long long stage_cap = removed ? std::min<long long>(capacity, g->ub_points) : 0;
+    HIPCHK(h, g->stage.reserve(((size_t)n + (size_t)std::max<long long>(stage_cap, 1)) * sizeof(float4)));
+    if (n > 0) HIPCHK(h, hipMemcpyAsync(g->stage.p, scan, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, st));
+    d_scan = g->stage.as<float4>();
+    if (removed) d_rm = g->stage.as<float4>() + n;
+  }
+  int* d_info = g->report_dev.as<int>() + 8;
+  s = grid_carve_enqueue(g, d_scan, n, d_pose, c, d_rm, capacity, d_info); if (s) return s;
+  HIPCHK(h, hipStreamSynchronize(st));
+  s = grid_read_report(g); if (s) return s;
+  static_assert(sizeof(msfl_grid_carve_info) == CARVE_WORDS * sizeof(int), "msfl_grid_carve_info is the device record");
+  std::memcpy(info, g->report.as<int>() + 8, sizeof(*info));
+  if (!info->applied) {
+    if (removed && info->n_points_removed > capacity) return fail(h, MSFL_CAPACITY, "msfl_grid_carve: more removed points than `capacity`; map unchanged");
+    return fail(h, MSFL_BAD_ARG, "msfl_grid_carve: a pose that is not finite; map unchanged");
+  }
+  if (removed && mem == MSFL_MEM_HOST && info->n_points_removed > 0) {
+    HIPCHK(h, hipMemcpyAsync(removed, d_rm, (size_t)info->n_points_removed * sizeof(float4), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+  }
+  return MSFL_OK;
+}
 
 msfl_status msfl_grid_create(msfl_handle* h, float resolution, float leaf, msfl_grid** out) {
   msfl_status s = enter(h); if (s) return s;
@@ -620,7 +778,8 @@ msfl_status msfl_grid_stats(msfl_grid* g, long long out[6]) {
   }
   const DevBuf* bufs[] = {&g->state, &g->pool[0], &g->pool[1], &g->ckey[0], &g->ckey[1], &g->cstart[0], &g->cstart[1], &g->ccnt[0], &g->ccnt[1],
                           &g->cstamp[0], &g->cstamp[1], &g->keys, &g->keys_s, &g->vals, &g->vals_s, &g->head, &g->tpos, &g->xf, &g->xs, &g->t_key, &g->t_ns,
-                          &g->t_old, &g->t_woff, &g->t_rank, &g->t_cnt, &g->cnt, &g->off, &g->stage, &g->pose, &g->report_dev, &g->crop, &g->crop_cells, &g->load};
+                          &g->t_old, &g->t_woff, &g->t_rank, &g->t_cnt, &g->cnt, &g->off, &g->stage, &g->pose, &g->report_dev, &g->crop, &g->crop_cells, &g->load,
+                          &g->carve_img, &g->carve_cells, &g->carve_tab, &g->carve_ctr};
   long long bytes = 0;
   for (auto* b : bufs) bytes += (long long)b->cap;
   out[0] = g->n_points; out[1] = g->n_cells; out[2] = g->pool_top; out[3] = (long long)pool_capacity(g); out[4] = g->cell_cap; out[5] = bytes;
