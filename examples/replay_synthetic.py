@@ -223,7 +223,7 @@ def world_drive(world, kind, n):
 
 def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=False, maps_out=None, quirks=False, imu=None, clouds_out=None,
              uncertainty=None, unc_out=None, priors=None, map_window=None, window_out=None, slam_hook=None, load_map=None, save_map=None,
-             degeneracy=None, degen_out=None, reject=None, reject_out=None):
+             degeneracy=None, degen_out=None, reject=None, reject_out=None, start_pose=None):
     """The same loop through the device-resident SLAM step (msfl_slam_add_scan): raw scan in, pose out, one
     synchronisation per scan (pipelined=False) or none until the record is fetched one scan later (pipelined=True: the
     odometry chain of scan k + 1 runs under the mapping chain of scan k, like the reference's two threads).
@@ -238,7 +238,7 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     records of msfl_slam_get_map_window.  slam_hook(slam, k): called before scan k is fed.
     load_map: PREFIX -> PREFIX.corner.npz / PREFIX.surf.npz (msf_loam_amd/mapio.py) are loaded into the session's two stores before the
     first scan (msfl_grid_load_cells: the stores hold the saved cells bit for bit, and scan 0 is registered against them); poses_true[0]
-    is then the pose of the first scan in the saved map's frame.  save_map: PREFIX -> the two stores are written there after the run.
+    is then the pose of the first scan in the saved map's frame, unless start_pose (relocalize_start) gives it.  save_map: PREFIX -> the two stores are written there after the run.
     Returns (poses, records, wall-clock ms per scan over the scans after the second)."""
     from msf_loam_amd import capi
     n = len(poses_true)
@@ -248,7 +248,7 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     rings = int(max(r.max() for _, r in scans)) + 1
     if os.environ.get("MSFL_REPLAY_DEFAULT_CAPS") == "1":          # msfl_slam_default_config's launch bounds (200 000 points, 128 rings) instead of tight ones
         cap, rings = 200000, 128
-    slam = capi.Slam(device, max_scan_points=cap, max_rings=rings, pose_odom2map=poses_true[0],
+    slam = capi.Slam(device, max_scan_points=cap, max_rings=rings, pose_odom2map=poses_true[0] if start_pose is None else start_pose,
                      reference_quirks=1 if quirks else 0, keep_clouds=1 if clouds_out is not None else 0)
     if uncertainty is not None:
         slam.set_uncertainty(True, uncertainty)
@@ -334,6 +334,33 @@ def ate(est, truth):
     return float(np.sqrt(np.mean(np.sum((est[:, :3] - truth[:, :3]) ** 2, axis=1))))
 
 
+def relocalize_start(prefix, scan, truth0, offset=(1.2, -0.9), yaw_deg=34.0, device=0):
+    """The pose of `scan` in the saved map PREFIX.corner.npz / PREFIX.surf.npz, found by msfl_relocalize from a guess `offset` metres
+    and yaw_deg degrees off truth0: features through the product's extraction and voxel filter, the map files' points as the
+    resident map, the default 13 x 13 x 24 lattice."""
+    from msf_loam_amd import capi, mapio
+    mc, ms = (mapio.read_map("%s.%s.npz" % (prefix, side))[3] for side in ("corner", "surf"))
+    h = capi.Handle(device)
+    f = h.extract_features(*scan)
+    corner = h.voxel_downsample(f["full"][f["less_sharp"]], 0.2)
+    surf = h.voxel_downsample(f["full"][f["less_flat"]], 0.4)
+    guess = np.array(truth0, np.float64)
+    guess[0] += offset[0]; guess[1] += offset[1]
+    hy = -np.deg2rad(yaw_deg) / 2.0
+    q = synth.quat_mul(np.array([0.0, 0.0, np.sin(hy), np.cos(hy)]), guess[3:])
+    guess[3:] = q / np.linalg.norm(q)
+    reach = float(np.ceil(np.percentile(np.linalg.norm(np.concatenate([corner, surf])[:, :3], axis=1), 99)))
+    h.set_map(mc, ms)
+    res = h.relocalize(corner, surf, guess, capi.SearchConfig(range=reach), n_candidates=16, max_dist=1.0, n_refine=5, min_fitness=0.5)
+    h.close()
+    if len(res) == 0 or not res[0]["accepted"]:
+        raise SystemExit("--relocalize: no candidate reached the fitness 0.5")
+    dt, dr = synth.pose_error(res[0]["pose"], truth0)
+    print("relocalised scan 0 from a guess %.2f m / %.0f deg off: %.3f m / %.2f deg from the truth, fitness %.3f"
+          % (np.hypot(*offset), yaw_deg, dt, np.rad2deg(dr), capi.fitness(res["refined"][:1], len(corner), len(surf))[0]), file=sys.stderr)
+    return np.array(res[0]["pose"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scans", type=int, default=300)
@@ -364,9 +391,14 @@ def main():
     ap.add_argument("--load-map", default=None, metavar="PREFIX",
                     help="before the first scan load PREFIX.corner.npz / PREFIX.surf.npz into the session's stores (msfl_grid_load_cells): "
                          "localise in a saved map; the first true pose anchors the session in the saved map's frame")
+    ap.add_argument("--relocalize", action="store_true",
+                    help="with --load-map: the session is not anchored at the first true pose but at what msfl_relocalize finds for scan 0 "
+                         "in the saved map from a guess 1.5 m and 34 degrees off (examples/relocalize.py shows the search on its own)")
     args = ap.parse_args()
     if args.mode == "staged" and (args.save_map or args.load_map):
         ap.error("--save-map / --load-map need the slam modes")
+    if args.relocalize and not args.load_map:
+        ap.error("--relocalize needs --load-map")
     map_window = None
     if args.map_window:
         w = [int(v) for v in args.map_window.split(",")]
@@ -404,7 +436,8 @@ def main():
     import gc
     gc.collect(); gc.disable()
     unc, degen, rejected = [], [], []
-    est, recs, ms = run_slam(world, truth, pipelined=args.mode == "slam-pipelined", scans=scans, quirks=args.reference_quirks,
+    start_pose = relocalize_start(args.load_map, scans[0], truth[0]) if args.relocalize else None
+    est, recs, ms = run_slam(world, truth, pipelined=args.mode == "slam-pipelined", scans=scans, quirks=args.reference_quirks, start_pose=start_pose,
                              imu=synthetic_imu(truth) if args.imu else None, clouds_out=[] if args.keep_clouds else None,
                              uncertainty=args.uncertainty, unc_out=unc, map_window=map_window, load_map=args.load_map, save_map=args.save_map,
                              degeneracy=degeneracy, degen_out=degen, reject=reject, reject_out=rejected)

@@ -1,6 +1,7 @@
 """Score a position x yaw lattice of pose hypotheses for one scan against a resident map (msfl_score_poses), and optionally
-refine the best few with the matcher.  A demonstration of how the scoring primitive composes; it is not a relocaliser (no
-lattice generator, top-k or acceptance policy lives in the library).
+refine the best few with the matcher.  A demonstration of how the scoring primitive composes; it is not a relocaliser: the
+library's own lattice search, top-k and acceptance are msfl_search_poses / msfl_relocalize (examples/relocalize.py,
+docs/kernels/search.md), whose coarse stage ranks such a lattice at a fraction of this exact walk's time.
 
     python examples/score_lattice.py [--world room|outdoor|corridor] [--half 3.0] [--step 0.5] [--yaws 24] [--refine 5]
 

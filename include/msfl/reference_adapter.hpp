@@ -262,6 +262,44 @@ inline std::vector<PoseScore> ScorePoses(msfl_handle* h, const StampedT& scan, c
   return out;
 }
 
+// ---- where in the resident map is this scan, given only a rough guess (msfl_search_poses, msfl_relocalize; not in the reference,
+// whose matcher needs a guess inside its basin).  SearchPoses: the best `capacity` peaks of the hit-count lattice round `guess`,
+// best first.  Relocalize: those candidates scored exactly, the best n_refine registered and scored again, best first; a record's
+// `accepted` says whether its refined inlier fraction reaches min_fitness.  Call them after MatchScan2Map (its map is resident).
+inline msfl_search_config SearchDefaultConfig() {
+  msfl_search_config c;
+  msfl_search_default_config(&c);
+  return c;
+}
+template <class StampedT, class RigidT>
+inline std::vector<msfl_pose_candidate> SearchPoses(msfl_handle* h, const StampedT& scan, const RigidT& guess, const msfl_search_config& cfg,
+                                                    int capacity) {
+  const std::vector<msfl_point> c = Pack(*scan.cloud_corner_less_sharp);
+  const std::vector<msfl_point> s = Pack(*scan.cloud_surf_less_flat);
+  double g[7];
+  RigidToArray(guess, g);
+  std::vector<msfl_pose_candidate> out(static_cast<std::size_t>(capacity > 0 ? capacity : 0));
+  int n = 0;
+  Check(msfl_search_poses(h, c.data(), static_cast<int>(c.size()), s.data(), static_cast<int>(s.size()), g, &cfg, out.data(), capacity, &n, nullptr,
+                          MSFL_MEM_HOST), h, "msfl_search_poses");
+  out.resize(static_cast<std::size_t>(n));
+  return out;
+}
+template <class StampedT, class RigidT>
+inline std::vector<msfl_reloc_result> Relocalize(msfl_handle* h, const StampedT& scan, const RigidT& guess, const msfl_search_config& cfg,
+                                                 int n_candidates, double max_dist, int n_refine, double min_fitness) {
+  const std::vector<msfl_point> c = Pack(*scan.cloud_corner_less_sharp);
+  const std::vector<msfl_point> s = Pack(*scan.cloud_surf_less_flat);
+  double g[7];
+  RigidToArray(guess, g);
+  std::vector<msfl_reloc_result> out(static_cast<std::size_t>(n_refine > 0 ? n_refine : 0));
+  int n = 0;
+  Check(msfl_relocalize(h, c.data(), static_cast<int>(c.size()), s.data(), static_cast<int>(s.size()), g, &cfg, n_candidates, max_dist, n_refine,
+                        min_fitness, out.data(), n_refine, &n, MSFL_MEM_HOST), h, "msfl_relocalize");
+  out.resize(static_cast<std::size_t>(n));
+  return out;
+}
+
 // ---- P (map, scan) pairs with the pairs' maps kept resident (msfl_set_pair_maps, msfl_score_pairs, msfl_match_pairs_resident; not in
 // the reference, which registers one scan against one map per call): loop-closure candidates against their submaps.  `maps` / `scans`
 // are containers (size(), operator[]) of stamped clouds, of which cloud_corner_less_sharp and cloud_surf_less_flat are read.

@@ -297,6 +297,20 @@ class MappingScanMatcher : public ScanMatcher {
     return adapter::ScorePoses(h_, scan, poses, max_dist);
   }
 
+  // Not in the reference: where in the map of the last MatchScan2Map `scan` is, given only a rough guess (msfl_search_poses,
+  // msfl_relocalize; adapter::SearchDefaultConfig() gives the lattice's defaults).  SearchPoses: the best `capacity` peaks of the
+  // hit-count lattice round the guess, best first.  Relocalize: those scored exactly, the best n_refine registered and scored again,
+  // best first; use the first record if its `accepted` is set.
+  template <class StampedT, class RigidT>
+  std::vector<msfl_pose_candidate> SearchPoses(const StampedT& scan, const RigidT& guess, const msfl_search_config& cfg, int capacity) {
+    return adapter::SearchPoses(h_, scan, guess, cfg, capacity);
+  }
+  template <class StampedT, class RigidT>
+  std::vector<msfl_reloc_result> Relocalize(const StampedT& scan, const RigidT& guess, const msfl_search_config& cfg, int n_candidates,
+                                            double max_dist, int n_refine, double min_fitness) {
+    return adapter::Relocalize(h_, scan, guess, cfg, n_candidates, max_dist, n_refine, min_fitness);
+  }
+
   // Not in the reference: P (map, scan) pairs with the pairs' maps kept resident (msfl_set_pair_maps, msfl_score_pairs,
   // msfl_match_pairs_resident).  SetPairMaps indexes maps[p] once (the map of the last MatchScan2Map is replaced); ScorePairs grades
   // scans[p] at each of poses[p] against map p only; MatchPairsResident registers scans[p] against map p from (*poses)[p] and returns

@@ -433,6 +433,109 @@ msfl_status msfl_match_pairs_resident(msfl_handle* h, int n_pairs,
                                       const msfl_point* surf, const int* surf_off,
                                       double* poses_io, int* status, msfl_match_info* info, msfl_mem mem);
 
+/* Pose search: where in the resident map is this scan, given only a rough guess?  A lattice of yaw x position hypotheses
+   round the guess is scored by a HIT COUNT against a bit-per-voxel occupancy volume of the map, the peaks of the score are
+   the candidates, and msfl_relocalize finishes them with the exact score and the matcher.  docs/kernels/search.md has the
+   definition in full; in short:
+     hypothesis  h = ((a nz + kz') ny + ky') nx + kx', n = 2 half + 1 per axis, k = k' - half;
+                 pose(a, k): q = normalised(qz(yaw_min + a yaw_step) * q_guess), t = t_guess + step * k, in double.
+     volume      one bit per voxel of pitch `step` and feature kind, over the box msfl_search_geometry reports.  A finite map
+                 point inside the box sets the voxel (int)floorf((x - origin.x) * inv_step) (f32, per axis) of its kind's
+                 volume; with dilate = 1 every voxel of the box within Chebyshev distance 1 of a set one is set too.
+     count       for yaw sample a and feature p, v = voxel of transform_point_f32(pose(a, 0), p).  The feature HITS at
+                 (a, k) when v + k lies inside the box and that bit is set in the volume of its kind.  The integer shift IS
+                 the definition (it is not the voxel of the point transformed by pose(a, k)).  hits[kind][h] counts the hit
+                 features; a non-finite feature or transformed point never hits.
+     peaks       order: (hits[0] + hits[1] descending, h ascending).  h is a peak when no OTHER hypothesis within nms_cells
+                 (Chebyshev, on k) and nms_yaws (on a; cyclic when yaw_wraps) precedes it.  Windows 0 / 0: every h is a peak.
+     candidates  the first `capacity` peaks in that order. */
+typedef struct msfl_search_config {
+  double step;                 /* lattice AND voxel pitch, metres, > 0 */
+  int half[3];                 /* lattice half-extents in cells, >= 0 */
+  int n_yaw;                   /* >= 1 */
+  double yaw_min, yaw_step;    /* yaw sample a = yaw_min + a * yaw_step, radians */
+  int yaw_wraps;               /* 0 / 1: the samples close a full turn (for the peak window only) */
+  int dilate;                  /* 0 / 1 */
+  double range;                /* features are expected within this distance of the sensor; it sizes the volume */
+  int nms_cells, nms_yaws;     /* peak windows, >= 0 */
+  long long max_volume_bytes;  /* per kind; a larger volume is MSFL_CAPACITY */
+} msfl_search_config;
+
+/* step 0.5, half {6, 6, 0}, 24 yaws from 0 in steps of 2 pi / 24, wraps 1, dilate 1, range 100, windows 1 / 1, 64 MiB. */
+void msfl_search_default_config(msfl_search_config* cfg);
+
+typedef struct msfl_search_geom {
+  float origin[3];             /* low corner of the box: (float)((floor(t_guess / step) - ext) * step), in double until the cast */
+  float inv_step;              /* (float)(1 / step) */
+  int dims[3];                 /* 2 ext + 1 voxels per axis, ext = half + ceil(range / step) + dilate + 1 */
+  int words_per_row;           /* 64-bit words of one x row: ceil(dims[0] / 64) + 1 (the last one stays zero) */
+  int n[3];                    /* lattice positions per axis */
+  int n_yaw;
+  long long n_hypotheses;      /* H = n_yaw n[2] n[1] n[0] */
+  long long volume_bytes;      /* one volume of one kind */
+  long long scratch_bytes;     /* device scratch msfl_search_poses needs for n_corner + n_surf features (staging of host arrays aside) */
+} msfl_search_geom;
+
+/* The geometry rule, on the host alone (no handle, no GPU): what msfl_search_poses will use for this guess and config.
+   MSFL_BAD_ARG: null pointer, non-finite guess, step or range not finite and positive, a negative half or window, n_yaw < 1,
+   non-finite yaw_min / yaw_step, dilate / yaw_wraps not 0 / 1, negative counts, max_volume_bytes <= 0.
+   MSFL_CAPACITY (out is still filled where it can be): a volume above max_volume_bytes, a dimension above 2^20 voxels,
+   more than 2^24 hypotheses, 2^24 features or more of a kind, or more than 2^26 (yaw, feature) table entries. */
+msfl_status msfl_search_geometry(const double guess[7], const msfl_search_config* cfg, int n_corner, int n_surf,
+                                 msfl_search_geom* out);
+
+typedef struct msfl_pose_candidate {
+  double pose[7];              /* pose(a, k) */
+  int h;                       /* hypothesis index */
+  int a, kx, ky, kz;           /* lattice coordinates, k in [-half, half] */
+  int hits[2];                 /* corner, surf */
+  int reserved_;
+} msfl_pose_candidate;
+
+/* The search itself.
+     corner/surf : the scan's features, sensor frame, as in msfl_score_poses.
+     candidates  : `capacity` records, 1 <= capacity <= 1024; *n_out of them are written (fewer when there are fewer peaks).
+                   In device memory the slots past *n_out are written too, all zero; in host memory they are left alone.
+     hits_out    : optional (NULL: not wanted), 2 x H int32: hits[kind][h] over the WHOLE lattice.
+   guess and cfg are HOST data in both memory kinds.  With MSFL_MEM_DEVICE corner, surf, candidates, n_out and hits_out are
+   device pointers and the call is asynchronous on the handle's stream, ordered after a preceding asynchronous msfl_set_map.
+   Refusals, all before anything is staged or launched: MSFL_NO_MAP without a resident single map (also while a pair index is
+   resident); MSFL_BAD_ARG / MSFL_CAPACITY as for msfl_search_geometry; MSFL_BAD_ARG for a capacity outside 1 .. 1024.
+   An empty map side gives zero hits of that kind.  The call works in scratch of its own and reads the map's point arrays
+   only: a matcher or scoring call after it is bit-identical to one without it. */
+msfl_status msfl_search_poses(msfl_handle* h,
+                              const msfl_point* corner, int n_corner,
+                              const msfl_point* surf, int n_surf,
+                              const double guess[7], const msfl_search_config* cfg,
+                              msfl_pose_candidate* candidates, int capacity, int* n_out, int* hits_out, msfl_mem mem);
+
+typedef struct msfl_reloc_result {
+  double pose[7];                  /* the refined pose */
+  msfl_pose_candidate candidate;   /* where it started */
+  msfl_pose_score coarse;          /* msfl_score_poses at the candidate's pose */
+  msfl_pose_score refined;         /* msfl_score_poses at the refined pose */
+  int status;                      /* per-scan status of the registration */
+  int accepted;                    /* (refined.inliers[0] + refined.inliers[1]) / (n_corner + n_surf) >= min_fitness */
+} msfl_reloc_result;
+
+/* Search, verify, refine, verify again: a composition of public calls and no arithmetic of its own.
+     1. msfl_search_poses for n_candidates candidates;
+     2. msfl_score_poses(max_dist) at their poses; order: exact inliers (both kinds) descending, fixed-point sum (both kinds)
+        ascending, candidate order;
+     3. msfl_match_scan2map_batch of the first n_refine in that order, each from its candidate pose;
+     4. msfl_score_poses(max_dist) at the refined poses; the records leave sorted by rule 2 on the refined scores (ties: step 2's order).
+   *n_out = min(n_refine, candidates found) records are written; every byte equals what a caller chaining the four calls gets.
+   `mem` says where corner / surf live; guess, cfg, results and n_out are host data and the call returns when it is done.
+   MSFL_BAD_ARG besides the rules of the four calls: n_candidates outside 1 .. 1024, n_refine outside 1 .. n_candidates,
+   capacity < n_refine, a NaN min_fitness.  Towards the handle's state (record sinks, pose priors, timing, the poses and
+   records a matcher call leaves behind) the call counts as ONE msfl_match_scan2map_batch call of *n_out registrations. */
+msfl_status msfl_relocalize(msfl_handle* h,
+                            const msfl_point* corner, int n_corner,
+                            const msfl_point* surf, int n_surf,
+                            const double guess[7], const msfl_search_config* cfg, int n_candidates,
+                            double max_dist, int n_refine, double min_fitness,
+                            msfl_reloc_result* results, int capacity, int* n_out, msfl_mem mem);
+
 /* Kernel-level entry points (the two halves of one outer iteration), exposed so that parity tests
    can pin the data association and the solver separately:
      msfl_associate_scan2map : mapping_scan_matcher.cc:109-246 at a fixed pose.  records_out gets

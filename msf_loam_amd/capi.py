@@ -26,6 +26,7 @@ PROTOTYPES = dict(t.split("=") for t in """
     msfl_set_degeneracy=i:pidpii msfl_set_outlier_rejection=i:pppii msfl_set_map=i:ppipii msfl_match_scan2map=i:ppipippi
     msfl_match_scan2map_batch=i:pipppppppi msfl_match_pairs_batch=i:pipppppppppppi msfl_score_poses=i:ppipipidpppi
     msfl_score_poses_batch=i:pippppppdpi msfl_set_pair_maps=i:pippppi msfl_score_pairs=i:pippppppdpppi msfl_match_pairs_resident=i:pipppppppi
+    msfl_search_default_config=v:p msfl_search_geometry=i:ppiip msfl_search_poses=i:ppipipppippi msfl_relocalize=i:ppipippididpipi
     msfl_associate_scan2map=i:ppipipp msfl_solve_records=i:ppipippp msfl_match_scan2map_deskew=i:ppipippp msfl_associate_scan2map_deskew=i:ppipipppp
     msfl_solve_records_deskew=i:ppipipppp msfl_match_scan2map_deskew_batch=i:pippppppppi msfl_match_scan2scan=i:pppppppi
     msfl_match_scan2scan_batch=i:pipppppppi msfl_extract_features=i:pppippi msfl_extract_features_batch=i:pipppppi msfl_voxel_downsample=i:ppifppi
@@ -171,6 +172,45 @@ def rmse(scores):
     inl = scores["inliers"].sum(-1).astype(np.float64)
     tot = scores["sum_sq_q32"].astype(np.float64).sum(-1) / 4294967296.0     # (each sum is below 2^63; the float64 rounding is 2^-53 relative)
     return np.sqrt(np.divide(tot, inl, out=np.full(np.shape(inl), np.nan), where=inl > 0))
+
+
+class SearchConfig(C.Structure):
+    """msfl_search_config: the yaw x position lattice, the voxel pitch and the peak windows of Handle.search_poses.  Built with the
+    library's defaults (msfl_search_default_config); keywords override fields (half: three ints)."""
+    _fields_ = [("step", C.c_double), ("half", C.c_int * 3), ("n_yaw", C.c_int), ("yaw_min", C.c_double), ("yaw_step", C.c_double),
+                ("yaw_wraps", C.c_int), ("dilate", C.c_int), ("range", C.c_double), ("nms_cells", C.c_int), ("nms_yaws", C.c_int),
+                ("max_volume_bytes", C.c_longlong)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        load().msfl_search_default_config(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("SearchConfig has no field " + k)
+            setattr(self, k, (C.c_int * 3)(*[int(x) for x in v]) if k == "half" else v)
+
+
+class SearchGeom(C.Structure):
+    """msfl_search_geom: the box, the lattice and the scratch of one search (capi.search_geometry)."""
+    _fields_ = [("origin", C.c_float * 3), ("inv_step", C.c_float), ("dims", C.c_int * 3), ("words_per_row", C.c_int), ("n", C.c_int * 3),
+                ("n_yaw", C.c_int), ("n_hypotheses", C.c_longlong), ("volume_bytes", C.c_longlong), ("scratch_bytes", C.c_longlong)]
+
+
+POSE_CANDIDATE_DTYPE = np.dtype([("pose", np.float64, (7,)), ("h", np.int32), ("a", np.int32), ("kx", np.int32), ("ky", np.int32),
+                                 ("kz", np.int32), ("hits", np.int32, (2,)), ("reserved_", np.int32)])
+RELOC_RESULT_DTYPE = np.dtype([("pose", np.float64, (7,)), ("candidate", POSE_CANDIDATE_DTYPE), ("coarse", POSE_SCORE_DTYPE),
+                               ("refined", POSE_SCORE_DTYPE), ("status", np.int32), ("accepted", np.int32)])
+assert POSE_CANDIDATE_DTYPE.itemsize == 88 and RELOC_RESULT_DTYPE.itemsize == 216 and C.sizeof(SearchConfig) == 72
+
+
+def search_geometry(guess, config, n_corner=0, n_surf=0, allow=()):
+    """msfl_search_geometry, on the host alone (no handle, no GPU): (status, SearchGeom).  A status outside `allow` raises."""
+    guess = np.ascontiguousarray(np.asarray(guess, np.float64).reshape(7))
+    g = SearchGeom()
+    s = load().msfl_search_geometry(_vp(guess), C.byref(config), int(n_corner), int(n_surf), C.byref(g))
+    if s != OK and s not in allow:
+        raise MsflError(s, "msfl_search_geometry")
+    return s, g
 
 
 class PlaceConfig(C.Structure):
@@ -965,6 +1005,65 @@ class Handle(_Owner):
         self._check(self.lib.msfl_score_pairs(self.h, B, _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(poses), _vp(offs[2]), max_dist,
                                               _vp(rec), _vp(d2), _vp(nn), MEM_HOST), "msfl_score_pairs")
         return (rec, d2, nn) if want_nn else rec
+
+    # ---- pose search (msfl_search_poses, msfl_relocalize) ----
+    def search_poses_device(self, corner, n_corner, surf, n_surf, guess, config, candidates, capacity, n_out, hits_out=None):
+        """Device-pointer form, asynchronous on the handle's stream: `candidates` holds capacity records of POSE_CANDIDATE_DTYPE.itemsize
+        bytes, n_out one int32, hits_out (optional) 2 x H int32; guess (7 doubles) and config are host data."""
+        guess = np.ascontiguousarray(np.asarray(guess, np.float64).reshape(7))
+        self._check(self.lib.msfl_search_poses(self.h, _vp(corner), int(n_corner), _vp(surf), int(n_surf), _vp(guess), C.byref(config),
+                                               _vp(candidates), int(capacity), _vp(n_out), _vp(hits_out), MEM_DEVICE), "msfl_search_poses(device)")
+
+    def search_poses(self, corner, surf, guess, config=None, capacity=16, want_hits=False):
+        """The best `capacity` peaks of the hit-count lattice round `guess` (include/msfl_c_api.h, docs/kernels/search.md): records of
+        POSE_CANDIDATE_DTYPE, best first.  want_hits: also hits (2, H) int32 over the whole lattice.  numpy clouds go through host
+        memory, torch device tensors (float32 (n, 4)) through the device form."""
+        config = SearchConfig() if config is None else config
+        guess = np.ascontiguousarray(np.asarray(guess, np.float64).reshape(7))
+        if _on_device(corner) or _on_device(surf):
+            import torch
+            if not (_on_device(corner) and _on_device(surf)) or corner.dtype != torch.float32 or surf.dtype != torch.float32:
+                raise TypeError("search_poses: both clouds must be float32 device tensors, or neither")
+            corner, surf = corner.contiguous(), surf.contiguous()
+            nc, ns = corner.numel() // 4, surf.numel() // 4
+            _, geom = search_geometry(guess, config, nc, ns, allow=(BAD_ARG, CAPACITY))     # (the call itself refuses those)
+            cand = torch.zeros(max(int(capacity), 1) * POSE_CANDIDATE_DTYPE.itemsize, dtype=torch.uint8, device=corner.device)
+            n_out = torch.zeros(1, dtype=torch.int32, device=corner.device)
+            hits = torch.zeros((2, max(int(geom.n_hypotheses), 1)), dtype=torch.int32, device=corner.device) if want_hits else None
+            self.search_poses_device(corner, nc, surf, ns, guess, config, cand, capacity, n_out, hits)
+            self.synchronize()
+            rec = cand.cpu().numpy().view(POSE_CANDIDATE_DTYPE)[:int(n_out.item())].copy()
+            return (rec, hits.cpu().numpy()[:, :int(geom.n_hypotheses)]) if want_hits else rec
+        corner, surf = _pts(corner), _pts(surf)
+        _, geom = search_geometry(guess, config, len(corner), len(surf), allow=(BAD_ARG, CAPACITY))
+        cand = np.zeros(max(int(capacity), 1), POSE_CANDIDATE_DTYPE)
+        n_out = np.zeros(1, np.int32)
+        hits = np.zeros((2, max(int(geom.n_hypotheses), 1)), np.int32) if want_hits else None
+        self._check(self.lib.msfl_search_poses(self.h, _vp(corner), len(corner), _vp(surf), len(surf), _vp(guess), C.byref(config), _vp(cand),
+                                               int(capacity), _vp(n_out), _vp(hits), MEM_HOST), "msfl_search_poses")
+        rec = cand[:int(n_out[0])].copy()
+        return (rec, hits[:, :int(geom.n_hypotheses)]) if want_hits else rec
+
+    def relocalize(self, corner, surf, guess, config=None, n_candidates=16, max_dist=1.0, n_refine=5, min_fitness=0.5):
+        """msfl_relocalize: search, exact score, registration of the best n_refine, exact score again.  Records of RELOC_RESULT_DTYPE,
+        best first (refined inliers descending, fixed-point sum ascending).  Clouds: numpy arrays, or both torch device tensors."""
+        config = SearchConfig() if config is None else config
+        guess = np.ascontiguousarray(np.asarray(guess, np.float64).reshape(7))
+        mem = MEM_HOST
+        if _on_device(corner) or _on_device(surf):
+            import torch
+            if not (_on_device(corner) and _on_device(surf)) or corner.dtype != torch.float32 or surf.dtype != torch.float32:
+                raise TypeError("relocalize: both clouds must be float32 device tensors, or neither")
+            corner, surf = corner.contiguous(), surf.contiguous()
+            nc, ns, mem = corner.numel() // 4, surf.numel() // 4, MEM_DEVICE
+        else:
+            corner, surf = _pts(corner), _pts(surf)
+            nc, ns = len(corner), len(surf)
+        out = np.zeros(max(int(n_refine), 1), RELOC_RESULT_DTYPE)
+        n_out = np.zeros(1, np.int32)
+        self._check(self.lib.msfl_relocalize(self.h, _vp(corner), nc, _vp(surf), ns, _vp(guess), C.byref(config), int(n_candidates), float(max_dist),
+                                             int(n_refine), float(min_fitness), _vp(out), len(out), _vp(n_out), mem), "msfl_relocalize")
+        return out[:int(n_out[0])].copy()
 
     def transform_cloud(self, pts, pose7):
         """TransformPointCloud (laser_mapping.cc:24-31)."""

@@ -214,6 +214,17 @@ struct ScoreScratch {        // msfl_score_poses*: no other call touches these, 
   DevBuf scan;               // int[H]: scan of every hypothesis (batch form), written by score_init_kernel
   DevBuf out0;               // u64[P]: msfl_score_pairs' first d2_out / nn_out element of every pair (ScorePairsView::out0)
 };
+struct SearchScratch {       // msfl_search_poses / msfl_relocalize: no other call touches these
+  DevBuf corner, surf;       // float4: staged clouds (host mode)
+  DevBuf vol;                // u64: the raw volumes [corner | surf], then with dilate = 1 the dilated ones
+  DevBuf tab;                // int4[n_yaw x features]: voxel of every feature at every yaw sample
+  DevBuf hits;               // int[2 H]: the counts when the caller gave no device array for them
+  DevBuf peaks;              // u64[H]: keys of the peaks
+  DevBuf ctr;                // int[2]: peaks appended, candidates written
+  DevBuf qtab;               // double[4 n_yaw + 7]: the yaw samples' quaternions, then the guess
+  DevBuf cand;               // SearchCand[1024]: the select kernel's records
+  DevBuf rl_cand, rl_poses, rl_scores, rl_status, rl_corner, rl_surf;   // msfl_relocalize on device clouds: what its chained calls read and write
+};
 
 enum TimerClass { T_ASSOC = 0, T_SOLVE, T_INDEX, T_EXTRACT, T_ODOM, T_FIT, T_ASSOC_SEEDED /* a subset of T_ASSOC */, T_COUNT };
 
@@ -289,6 +300,7 @@ struct msfl_handle_s {
   PointPassScratch pp;
   PairScratch pr;
   ScoreScratch sc;
+  SearchScratch se;
 
   // msfl_set_uncertainty / msfl_set_degeneracy / msfl_set_outlier_rejection: the knobs, and where every matcher call writes one
   // record per registration.  The uncertainty feature is on while its sink is set; a degeneracy or rejection sink is optional and
@@ -1348,6 +1360,7 @@ msfl_status msfl_solve_records_deskew(msfl_handle* h, const msfl_point* corner, 
 #include "msfl_api_slam.inc"
 #include "msfl_api_pairs.inc"
 #include "msfl_api_score.inc"
+#include "msfl_api_search.inc"
 #include "msfl_api_place.inc"
 
 namespace {
