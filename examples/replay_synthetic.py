@@ -330,6 +330,35 @@ def run_slam(world, poses_true, pipelined=False, device=0, scans=None, verbose=F
     return est, recs, 1e3 * wall / max(n - 2, 1)
 
 
+def run_slam_segmented(poses_true, scans, device=0, config=None):
+    """--segment: every sweep goes to the device once; msfl_segment_scan masks it there (ground and range-image clusters, the rest
+    set to NaN) and msfl_slam_add_scan takes the masked device cloud, so no cloud comes back to the host.  The session runs on a
+    stream of its own: the read-back of the class counts is the one wait between the handle's stream and the session's.
+    Returns (poses, records, ms per scan over the scans after the second, class counts)."""
+    import torch
+    from msf_loam_amd import capi
+    dev = "cuda:%d" % device
+    torch.zeros(1, device=dev)
+    h = capi.Handle(device)
+    cap = max(len(p) for p, _ in scans)
+    rings = int(max(r.max() for _, r in scans)) + 1
+    slam = capi.Slam(device, max_scan_points=cap, max_rings=rings, pose_odom2map=poses_true[0])
+    counts = np.zeros(5, np.int64)
+    recs, t_start = [], None
+    for k, (pts, ring) in enumerate(scans):
+        if k == 2:
+            t_start = time.perf_counter()
+        d_pts = torch.from_numpy(np.ascontiguousarray(pts)).to(dev)
+        d_ring = torch.from_numpy(np.ascontiguousarray(ring).view(np.int16)).to(dev)
+        out = h.segment_scan(d_pts, d_ring, config, want_segment=False)
+        counts += out["info"]["n_class"]
+        recs.append(slam.add_scan_device(out["masked"], d_ring, len(pts)))          # waits for the result: the tensors may go after it
+    wall = time.perf_counter() - t_start if t_start is not None else 0.0
+    est = np.array([np.array(r.pose_map[:]) for r in recs])
+    slam.close(); h.close()
+    return est, recs, 1e3 * wall / max(len(scans) - 2, 1), counts
+
+
 def ate(est, truth):
     return float(np.sqrt(np.mean(np.sum((est[:, :3] - truth[:, :3]) ** 2, axis=1))))
 
@@ -394,6 +423,9 @@ def main():
     ap.add_argument("--relocalize", action="store_true",
                     help="with --load-map: the session is not anchored at the first true pose but at what msfl_relocalize finds for scan 0 "
                          "in the saved map from a guess 1.5 m and 34 degrees off (examples/relocalize.py shows the search on its own)")
+    ap.add_argument("--segment", action="store_true",
+                    help="after the run, replay the same scans once more with msfl_segment_scan in front: the masked device cloud goes "
+                         "into msfl_slam_add_scan; the JSON line gains a `segment` record (class counts, ATE, ms per scan)")
     args = ap.parse_args()
     if args.mode == "staged" and (args.save_map or args.load_map):
         ap.error("--save-map / --load-map need the slam modes")
@@ -436,6 +468,9 @@ def main():
     import gc
     gc.collect(); gc.disable()
     unc, degen, rejected = [], [], []
+    if args.segment:                                       # torch holds the segmented replay's device clouds, and has to initialise first
+        import torch
+        torch.zeros(1, device="cuda:0")
     start_pose = relocalize_start(args.load_map, scans[0], truth[0]) if args.relocalize else None
     est, recs, ms = run_slam(world, truth, pipelined=args.mode == "slam-pipelined", scans=scans, quirks=args.reference_quirks, start_pose=start_pose,
                              imu=synthetic_imu(truth) if args.imu else None, clouds_out=[] if args.keep_clouds else None,
@@ -457,7 +492,17 @@ def main():
     last = recs[-1]
     if args.dump_poses:
         np.save(args.dump_poses, est)
-    print(json.dumps({"mode": args.mode, "world": args.world, "beams": args.beams, "keep_clouds": bool(args.keep_clouds), "scans": args.scans, "reference_quirks": bool(args.reference_quirks), "imu": bool(args.imu),
+    extra = {}
+    if args.segment:
+        from msf_loam_amd import capi
+        seg_cfg = capi.SegmentConfig(n_col=1900, n_row=64, elev_low_deg=-24.8, elev_high_deg=2.0, ground_rows=50) if args.beams == 64 else None
+        est_s, recs_s, ms_s, counts = run_slam_segmented(truth, scans, config=seg_cfg)
+        extra["segment"] = {"class_counts": {name: int(c) for name, c in zip(capi.SEG_CLASS_NAMES, counts)}, "n_points": int(sum(len(p) for p, _ in scans)),
+                            "ate_m": ate(est_s, truth), "final_error_m_rad": synth.pose_error(est_s[-1], truth[-1]), "ms_per_scan_end_to_end": ms_s,
+                            "mapping_gate_closed_scans": int(sum(1 for r in recs_s if r.status_mapping != 0)),
+                            "mean_features_after_voxel": [float(np.mean([r.n_corner_ds for r in recs_s])), float(np.mean([r.n_surf_ds for r in recs_s]))],
+                            "note": "the scan goes to the device once (18 B/pt), is masked there and enters msfl_slam_add_scan as device memory"}
+    print(json.dumps({**extra, "mode": args.mode, "world": args.world, "beams": args.beams, "keep_clouds": bool(args.keep_clouds), "scans": args.scans, "reference_quirks": bool(args.reference_quirks), "imu": bool(args.imu),
                       "map_window": args.map_window, "degeneracy": args.degeneracy, "reject": args.reject, "load_map": args.load_map, "save_map": args.save_map,
                       "ate_rmse_m": ate(est, truth),
                       "final_error_m_rad": synth.pose_error(est[-1], truth[-1]), "ms_per_scan_end_to_end": ms,

@@ -151,6 +151,30 @@ inline void Extract(msfl_handle* h, const CloudT& laser_cloud_in, const RigidT& 
   fill(*scan->cloud_surf_less_flat, idx[3].data(), f.n_less_flat);
 }
 
+// ---- scan segmentation in front of Extract (msfl_segment_scan; not in the reference): ground by the slope between neighbouring
+// beams, range-image clusters, the small ones dropped.  classes: one MSFL_SEG_* per point of `cloud`; masked: the cloud with the
+// points outside cfg.keep_classes set to NaN (x, y, z; everything else as it was) -- hand it to Extract, whose invalid-point pass
+// removes them.  Either output may be null.  cfg == nullptr: msfl_segment_default_config.
+template <class CloudT>
+inline msfl_segment_info Segment(msfl_handle* h, const CloudT& cloud, const msfl_segment_config* cfg, std::vector<std::uint8_t>* classes,
+                                 CloudT* masked) {
+  std::vector<msfl_point> p; std::vector<std::uint16_t> r;
+  PackWithRing(cloud, &p, &r);
+  const std::size_t n = p.size();
+  std::vector<std::uint8_t> cls(n + 1);
+  std::vector<msfl_point> m(masked ? n + 1 : 0);
+  msfl_segment_info info{};
+  Check(msfl_segment_scan(h, p.data(), r.data(), static_cast<int>(n), cfg, cls.data(), nullptr, masked ? m.data() : nullptr, &info, MSFL_MEM_HOST), h,
+        "msfl_segment_scan");
+  cls.resize(n);
+  if (masked) {
+    *masked = cloud;
+    for (std::size_t i = 0; i < n; ++i) { auto& q = (*masked)[i]; q.x = m[i].x; q.y = m[i].y; q.z = m[i].z; }
+  }
+  if (classes) classes->swap(cls);
+  return info;
+}
+
 // ---- OdometryScanMatcher::MatchScan2Scan (odometry_scan_matcher.cc:43-285).  Returns false exactly where the reference does
 // (< 10 correspondences, :262-267); the pose then holds the outer iterations completed so far.
 template <class StampedT, class RigidT>

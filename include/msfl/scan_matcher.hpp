@@ -351,6 +351,14 @@ class ScanRegistration {
     return scan;
   }
 
+  // Not in the reference: ground and range-image clusters in front of Extract (msfl_segment_scan, docs/kernels/segment.md).  Returns
+  // the counts; `classes` gets one MSFL_SEG_* per point, `masked` the cloud with the dropped points set to NaN -- Extract(*masked, ...)
+  // then sees the kept points only.  config == nullptr: msfl_segment_default_config.
+  msfl_segment_info Segment(const PointCloud<PointTypeOriginal>& laser_cloud_in, std::vector<std::uint8_t>* classes,
+                            PointCloud<PointTypeOriginal>* masked, const msfl_segment_config* config = nullptr) {
+    return adapter::Segment(h_, laser_cloud_in, config, classes, masked);
+  }
+
  private:
   msfl_handle* h_ = nullptr;
   Rigid3d lidar2imu_;

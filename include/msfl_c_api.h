@@ -960,6 +960,85 @@ msfl_status msfl_grid_carve(msfl_grid* g, const msfl_point* scan, int n, const d
 
 
 /* ------------------------------------------------------------------------------------------ */
+/* Scan segmentation: ground and range-image clusters before extraction (after LeGO-LOAM).      */
+/* ------------------------------------------------------------------------------------------ */
+
+/* msfl_segment_scans lays every sweep of a batch into its range image, takes the ground out by the slope between neighbouring beams,
+   connects the remaining pixels into clusters by an angle test between neighbours and classifies every input point; the masked copy
+   of the cloud (dropped points set to NaN) goes straight into msfl_extract_features* or msfl_slam_add_scan, whose invalid-point pass
+   removes them.  docs/kernels/segment.md has the definition in full; every step is f32 with contraction off against the host-built
+   tables of msfl_segment_tables, and every decision is an integer one after that, so numpy reproduces every output.  In short:
+     pixel      row = the point's ring, column by bisection (column c covers the azimuths [2 pi (c - 1/2) / n_col, 2 pi (c + 1/2) / n_col):
+                the columns are centred on the beams of a spinning sensor).  No pixel (class NONE): a point that is not finite, on the
+                axis (x*x + y*y == 0), with !(r >= min_range) || r > max_range, or with ring >= n_row.  The pixel's winner is the point
+                with the smallest (bits(r), index in its scan); every other point of the pixel is SHADOWED.
+     ground     for every column and every k < ground_rows with pixels (k, col) and (k+1, col) both occupied, d = upper - lower winner:
+                both are GROUND iff v*v <= g2 * n2, v = ((up.x*dx) + (up.y*dy)) + (up.z*dz), n2 = ((dx*dx) + (dy*dy)) + (dz*dz).
+     edges      between occupied pixels that are not ground, 4-neighbourhood, columns wrap, rows do not: with d1 = fmaxf(ra, rb) and
+                d2 = fminf(ra, rb) of the two winners' ranges, connected iff d2 * s > t * (d1 - d2 * c).
+     components the transitive closure of the edges; a component's id is its smallest pixel index row * n_col + col.
+     clusters   a component is valid iff count >= min_points, or count >= min_points_tall and it touches >= min_rows_tall rows.
+     per point  SEGMENT / OUTLIER: the winner of a pixel of a valid / invalid component. */
+enum { MSFL_SEG_NONE = 0, MSFL_SEG_SHADOWED = 1, MSFL_SEG_GROUND = 2, MSFL_SEG_SEGMENT = 3, MSFL_SEG_OUTLIER = 4, MSFL_SEG_CLASSES = 5 };
+
+typedef struct msfl_segment_config {
+  int n_col, n_row;                        /* columns of the full turn (even, 4..2048); rows = rings (2..128) */
+  float elev_low_deg, elev_high_deg;       /* elevation of row 0 and of row n_row - 1, uniform in between: -90 < low < high < 90 */
+  const float* row_elev_deg;               /* NULL, or a HOST array of n_row strictly ascending elevations in (-90, 90): uneven beams */
+  float min_range, max_range;              /* metres, 0 <= min_range < max_range */
+  int ground_rows;                         /* row pairs (k, k+1), k < ground_rows <= n_row - 1, that are tested; 0: no ground step */
+  float ground_angle_deg;                  /* in (0, 90) */
+  float up[3];                             /* the up direction in the sensor frame, a unit vector (|up|^2 within 1e-3 of 1) */
+  float segment_angle_deg;                 /* in (0, 90) */
+  int min_points, min_points_tall, min_rows_tall;   /* the cluster rule, each >= 1 */
+  int keep_classes;                        /* bit (1 << class) set: masked_out keeps the points of that class; 0 .. 31 */
+} msfl_segment_config;
+
+/* The synthetic 16-beam sensor and LeGO-LOAM's published values: 1800 x 16 pixels, -15 .. +15 degrees, 0.3 .. 100 m, 8 ground row
+   pairs, ground angle 10 degrees, up = (0, 0, 1), segment angle 60 degrees, cluster sizes 30 / 5 / 3, keep = GROUND | SEGMENT. */
+void msfl_segment_default_config(msfl_segment_config* cfg);
+
+/* The f32 tables the kernels compare against, built in double and rounded to f32 (pure host function, no handle):
+     cc[k], cs[k] = cos, sin(2 pi (k - 1/2) / n_col), k < n_col / 2       the column boundaries of the half turn
+     vs[k], vc[k] = sin, cos(e[k+1] - e[k]), k < n_row - 1                the elevation step of row pair k, e in radians
+     scalars      = { sin, cos(2 pi / n_col), g2 = sin^2(ground_angle), t = tan(segment_angle) }
+   with e[k] = row_elev_deg[k], or elev_low_deg + (elev_high_deg - elev_low_deg) k / (n_row - 1).
+   MSFL_BAD_ARG: a null pointer, a configuration outside the limits above or with a field that is not finite. */
+msfl_status msfl_segment_tables(const msfl_segment_config* cfg, float* cc, float* cs, float* vs, float* vc, float scalars[4]);
+
+typedef struct msfl_segment_info {
+  int n_class[5];                          /* points per class, MSFL_SEG_NONE .. MSFL_SEG_OUTLIER; their sum is the scan's n */
+  int n_pixels;                            /* occupied pixels */
+  int n_components;                        /* components among the occupied pixels that are not ground */
+  int n_segments;                          /* valid components */
+  int n_kept;                              /* points whose class is in keep_classes */
+  int reserved_;
+} msfl_segment_info;
+
+/* Scan s is the region [off[s], off[s+1]) of pts / ring and of every output (`off`: HOST, n_scans + 1, never descending, off[0] >= 0;
+   a point's index in its scan is its position minus off[s]).
+     pts, ring   : sensor clouds as the driver delivers them (what msfl_extract_features_batch takes).
+     cls_out     : one uint8_t per point, its class.
+     segment_out : NULL, or one int per point: the component id for SEGMENT and OUTLIER, -1 otherwise.
+     masked_out  : NULL, or one point per point: pts[i] when keep_classes has its class, else x = y = z = NaN and the fourth field
+                   untouched.  Must not overlap pts.
+     info        : NULL, or n_scans HOST records.  NULL: the call is stream-ordered and never waits for the device (device memory), so
+                   masked_out can go into the next call as it is.  Non-NULL: the call reads the counts back (it synchronises).
+     cfg         : NULL = msfl_segment_default_config.  HOST data, as is its row_elev_deg.
+   With MSFL_MEM_DEVICE pts, ring and the three outputs are device pointers.  A batch whose images exceed the scratch budget is processed
+   in chunks of scans on the stream; the results do not depend on the chunking.
+   MSFL_BAD_ARG, before anything is staged or launched: n_scans < 0, off NULL or descending or off[0] < 0, pts / ring / cls_out NULL with
+   points to process, masked_out overlapping pts, a configuration outside its limits. */
+msfl_status msfl_segment_scans(msfl_handle* h, int n_scans, const msfl_point* pts, const uint16_t* ring, const int* off,
+                               const msfl_segment_config* cfg, uint8_t* cls_out, int* segment_out, msfl_point* masked_out,
+                               msfl_segment_info* info, msfl_mem mem);
+
+/* The batch call with one scan of n points (info: NULL or one record). */
+msfl_status msfl_segment_scan(msfl_handle* h, const msfl_point* pts, const uint16_t* ring, int n, const msfl_segment_config* cfg,
+                              uint8_t* cls_out, int* segment_out, msfl_point* masked_out, msfl_segment_info* info, msfl_mem mem);
+
+
+/* ------------------------------------------------------------------------------------------ */
 /* The per-scan SLAM step, device-resident (BASELINE configs[2]: sequential odometry + mapping).*/
 /*   replaces, for one incoming scan, the chain the reference runs across its two threads:      */
 /*     RealHandleLaserCloudMessage   feature extraction            msf_loam_node.cc:160-378      */

@@ -34,7 +34,8 @@ PROTOTYPES = dict(t.split("=") for t in """
     msfl_deskew_cloud=i:pppipppi msfl_undistort_cloud=i:pppii msfl_grid_create=i:pffp msfl_grid_destroy=v:p msfl_grid_insert_scan=i:ppii
     msfl_grid_get_surrounded=i:ppippipi msfl_grid_size=i:ppp msfl_grid_dump=i:ppipi msfl_grid_dump_cells=i:ppip msfl_grid_stats=i:pp
     msfl_grid_crop=i:ppppiip msfl_grid_crop_tiles=i:ppppipiip msfl_grid_load_cells=i:ppipiipp msfl_carve_default_config=v:p msfl_carve_tables=i:ppppp
-    msfl_grid_carve=i:ppipppiip msfl_slam_default_config=v:p msfl_slam_create=i:ppip
+    msfl_grid_carve=i:ppipppiip msfl_segment_default_config=v:p msfl_segment_tables=i:pppppp msfl_segment_scans=i:pippppppppi
+    msfl_segment_scan=i:pppipppppi msfl_slam_default_config=v:p msfl_slam_create=i:ppip
     msfl_slam_destroy=v:p msfl_slam_add_scan=i:pppiip msfl_slam_add_scan_imu=i:pppiipp msfl_slam_get_result=i:pip msfl_slam_set_uncertainty=i:pid
     msfl_slam_get_uncertainty=i:pipp msfl_slam_set_degeneracy=i:piidd msfl_slam_get_degeneracy=i:pipp msfl_slam_set_outlier_rejection=i:ppp
     msfl_slam_get_rejection=i:pipp msfl_slam_set_next_prior=i:ppp msfl_slam_set_map_window=i:ppi msfl_slam_get_map_window=i:pipp
@@ -350,6 +351,52 @@ class GridCarveInfo(C.Structure):
 
     def as_tuple(self):
         return (self.n_points_removed, self.n_cells_emptied, self.n_cells, self.n_points, self.n_tested, self.n_pixels, self.applied)
+
+
+SEG_NONE, SEG_SHADOWED, SEG_GROUND, SEG_SEGMENT, SEG_OUTLIER = range(5)      # MSFL_SEG_*: the classes of msfl_segment_scans
+SEG_CLASS_NAMES = ("none", "shadowed", "ground", "segment", "outlier")
+
+
+class SegmentConfig(C.Structure):
+    """msfl_segment_config (include/msfl_c_api.h, docs/kernels/segment.md), built with the library's defaults
+    (msfl_segment_default_config); keywords override fields.  up: three floats; row_elev_deg: None or n_row ascending elevations
+    (the array is kept alive by this object)."""
+    _fields_ = [("n_col", C.c_int), ("n_row", C.c_int), ("elev_low_deg", C.c_float), ("elev_high_deg", C.c_float),
+                ("row_elev_deg", C.c_void_p), ("min_range", C.c_float), ("max_range", C.c_float), ("ground_rows", C.c_int),
+                ("ground_angle_deg", C.c_float), ("up", C.c_float * 3), ("segment_angle_deg", C.c_float), ("min_points", C.c_int),
+                ("min_points_tall", C.c_int), ("min_rows_tall", C.c_int), ("keep_classes", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        load().msfl_segment_default_config(C.byref(self))
+        self._rows = None
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("SegmentConfig has no field " + k)
+            if k == "row_elev_deg":
+                self._rows = None if v is None else np.ascontiguousarray(v, dtype=np.float32)
+                v = None if v is None else self._rows.ctypes.data
+            elif k == "up":
+                v = (C.c_float * 3)(*[float(x) for x in v])
+            setattr(self, k, v)
+
+
+SEGMENT_INFO_DTYPE = np.dtype([("n_class", np.int32, (5,)), ("n_pixels", np.int32), ("n_components", np.int32), ("n_segments", np.int32),
+                               ("n_kept", np.int32), ("reserved_", np.int32)])
+assert SEGMENT_INFO_DTYPE.itemsize == 40 and C.sizeof(SegmentConfig) == 72
+
+
+def segment_tables(config=None):
+    """msfl_segment_tables: (cc, cs, vs, vc, scalars) as f32 arrays, the tables msfl_segment_scans compares against (a pure host
+    call).  scalars = [sin, cos of one column, sin^2(ground angle), tan(segment angle)]."""
+    c = config if config is not None else SegmentConfig()
+    cc, cs = np.zeros(max(c.n_col // 2, 1), np.float32), np.zeros(max(c.n_col // 2, 1), np.float32)
+    vs, vc = np.zeros(max(c.n_row - 1, 1), np.float32), np.zeros(max(c.n_row - 1, 1), np.float32)
+    scalars = np.zeros(4, np.float32)
+    s = load().msfl_segment_tables(C.byref(c), _vp(cc), _vp(cs), _vp(vs), _vp(vc), _vp(scalars))
+    if s != OK:
+        raise MsflError(s, "msfl_segment_tables")
+    return cc, cs, vs, vc, scalars
 
 
 GRID_STATS = ("n_points", "n_cells", "pool_top", "pool_capacity_points", "cell_capacity", "device_bytes")
@@ -1064,6 +1111,58 @@ class Handle(_Owner):
         self._check(self.lib.msfl_relocalize(self.h, _vp(corner), nc, _vp(surf), ns, _vp(guess), C.byref(config), int(n_candidates), float(max_dist),
                                              int(n_refine), float(min_fitness), _vp(out), len(out), _vp(n_out), mem), "msfl_relocalize")
         return out[:int(n_out[0])].copy()
+
+    # ---- scan segmentation (msfl_segment_scans) ----
+    def segment_scans_device(self, pts, ring, off, config, cls_out, segment_out=None, masked_out=None, info=None):
+        """Device-pointer form: pts, ring and the three outputs are device memory (tensors or addresses), `off` (n_scans + 1) and
+        `info` (None, or n_scans records of SEGMENT_INFO_DTYPE) host arrays.  Without `info` the call only enqueues."""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        cfg = C.byref(config) if config is not None else None
+        self._check(self.lib.msfl_segment_scans(self.h, len(off) - 1, _vp(pts), _vp(ring), _vp(off), cfg, _vp(cls_out), _vp(segment_out),
+                                                _vp(masked_out), _vp(info), MEM_DEVICE), "msfl_segment_scans(device)")
+
+    def segment_scans(self, pts, ring, off, config=None, want_segment=True, want_masked=True, want_info=True):
+        """msfl_segment_scans (include/msfl_c_api.h, docs/kernels/segment.md): scan b is pts[off[b]:off[b + 1]].  Returns a dict:
+        cls (uint8 per point: SEG_NONE .. SEG_OUTLIER), segment (int32 component id or -1), masked (the cloud with the dropped
+        points set to NaN: hand it to extract_features* or Slam.add_scan), info (records of SEGMENT_INFO_DTYPE, one per scan);
+        the want_* switches leave an output out (None).  numpy arrays go through host memory; torch device tensors (pts float32
+        (n, 4), ring a 16-bit integer type) through the device form, whose outputs are tensors and which does not wait for the
+        device when want_info is off."""
+        off = np.ascontiguousarray(off, dtype=np.int32)
+        B = len(off) - 1
+        info = np.zeros(max(B, 1), SEGMENT_INFO_DTYPE) if want_info else None
+        if _on_device(pts) or _on_device(ring):
+            import torch
+            if not (_on_device(pts) and _on_device(ring)) or pts.dtype != torch.float32 or ring.element_size() != 2:
+                raise TypeError("segment_scans: pts must be a float32 and ring a 16-bit device tensor, or both numpy arrays")
+            pts, ring = pts.contiguous(), ring.contiguous()
+            n = pts.numel() // 4
+            cls = torch.zeros(max(n, 1), dtype=torch.uint8, device=pts.device)
+            seg = torch.zeros(max(n, 1), dtype=torch.int32, device=pts.device) if want_segment else None
+            masked = torch.zeros((max(n, 1), 4), dtype=torch.float32, device=pts.device) if want_masked else None
+            self.segment_scans_device(pts, ring, off, config, cls, seg, masked, info)
+            self._seg_keep = (pts, ring)                             # the inputs of an enqueued call stay alive until the next one
+            return dict(cls=cls[:n], segment=None if seg is None else seg[:n], masked=None if masked is None else masked[:n],
+                        info=None if info is None else info[:B])
+        pts = _pts(pts)
+        ring = np.ascontiguousarray(ring, dtype=np.uint16)
+        n = len(pts)
+        cls = np.zeros(max(n, 1), np.uint8)
+        seg = np.zeros(max(n, 1), np.int32) if want_segment else None
+        masked = np.zeros((max(n, 1), 4), np.float32) if want_masked else None
+        cfg = C.byref(config) if config is not None else None
+        self._check(self.lib.msfl_segment_scans(self.h, B, _vp(pts), _vp(ring), _vp(off), cfg, _vp(cls), _vp(seg), _vp(masked), _vp(info),
+                                                MEM_HOST), "msfl_segment_scans")
+        return dict(cls=cls[:n], segment=None if seg is None else seg[:n], masked=None if masked is None else masked[:n],
+                    info=None if info is None else info[:B])
+
+    def segment_scan(self, pts, ring, config=None, **kw):
+        """msfl_segment_scan: one scan; segment_scans' dict with `info` one record."""
+        n = (pts.numel() // 4) if _on_device(pts) else len(_pts(pts))
+        out = self.segment_scans(pts, ring, [0, n], config, **kw)
+        if out["info"] is not None:
+            out["info"] = out["info"][0]
+        return out
 
     def transform_cloud(self, pts, pose7):
         """TransformPointCloud (laser_mapping.cc:24-31)."""

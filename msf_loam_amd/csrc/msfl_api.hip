@@ -225,6 +225,15 @@ struct SearchScratch {       // msfl_search_poses / msfl_relocalize: no other ca
   DevBuf cand;               // SearchCand[1024]: the select kernel's records
   DevBuf rl_cand, rl_poses, rl_scores, rl_status, rl_corner, rl_surf;   // msfl_relocalize on device clouds: what its chained calls read and write
 };
+struct SegmentScratch {      // msfl_segment_scan*: allocated by the first call, no other call touches these
+  DevBuf in_pts, in_ring;    // float4[n_total], u16[n_total]: staged sensor clouds (host mode)
+  DevBuf out_cls, out_seg, out_masked;   // u8 / int / float4 [n_total]: the outputs before they go back (host mode)
+  DevBuf off;                // int[n_scans + 1]: scan offsets into the arrays the kernels see
+  DevBuf tab;                // float: cc, cs [n_col / 2 each], vs, vc [n_row - 1 each] (msfl_segment_tables)
+  DevBuf img;                // the images of one chunk of scans (SegImages; kSegPixelBytes per pixel)
+  DevBuf ctr;                // int[SEG_CTR_WORDS x chunk scans]: the counters of the chunk in flight
+  DevBuf info;               // int[SEG_INFO_WORDS x n_scans]: the info records before they are read back
+};
 
 enum TimerClass { T_ASSOC = 0, T_SOLVE, T_INDEX, T_EXTRACT, T_ODOM, T_FIT, T_ASSOC_SEEDED /* a subset of T_ASSOC */, T_COUNT };
 
@@ -301,6 +310,8 @@ struct msfl_handle_s {
   PairScratch pr;
   ScoreScratch sc;
   SearchScratch se;
+  SegmentScratch sg;
+  int seg_chunk_scans = 0;                // MSFL_SEG_CHUNK_SCANS: scans per chunk of msfl_segment_scans (0 = what the scratch budget holds)
 
   // msfl_set_uncertainty / msfl_set_degeneracy / msfl_set_outlier_rejection: the knobs, and where every matcher call writes one
   // record per registration.  The uncertainty feature is on while its sink is set; a degeneracy or rejection sink is optional and
@@ -920,6 +931,7 @@ msfl_status msfl_create(const msfl_params* params, int device, msfl_handle** out
   if (const char* e = std::getenv("MSFL_VOXEL_GLOBAL")) h->voxel_force_global = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_VOXEL_NO_BIG")) h->voxel_no_big = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_ODOM_BIN_SPLIT")) h->odom_bin_split = std::atoi(e) != 0 ? 1 : 0;
+  if (const char* e = std::getenv("MSFL_SEG_CHUNK_SCANS")) { const int c = std::atoi(e); if (c >= 1) h->seg_chunk_scans = c; }
   if (const char* e = std::getenv("MSFL_PREP_SPLIT")) { const int g = std::atoi(e); if (g == 1 || g == 2 || g == 4 || g == 8 || g == 16) h->prep_split = g; }
   *out = h;
   return MSFL_OK;
@@ -1361,6 +1373,7 @@ msfl_status msfl_solve_records_deskew(msfl_handle* h, const msfl_point* corner, 
 #include "msfl_api_pairs.inc"
 #include "msfl_api_score.inc"
 #include "msfl_api_search.inc"
+#include "msfl_api_segment.inc"
 #include "msfl_api_place.inc"
 
 namespace {
