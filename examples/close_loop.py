@@ -3,7 +3,7 @@
     python examples/close_loop.py [--scans 151] [--gap 50] [--every 1] [--max-distance 0.1] [--min-fitness 0.99] [--weights scalar|information]
                                   [--gate distance|mahalanobis] [--gate-bound 16.81]
                                   [--closure-map session|submap] [--submap-half-width 5] [--rebuild-map PATH]
-                                  [--closure-loss KIND:A] [--closure-yaws N]
+                                  [--closure-loss KIND:A] [--closure-yaws N | --closure-search [HALF_WIDTH PITCH]]
 
 The figure of eight of examples/loop_candidates.py.  Every scan goes through the device-resident SLAM step (keep_clouds) and into a
 capi.Places.  The odometry the graph starts from is made to drift: the session's consecutive relative poses with a yaw bias and
@@ -26,7 +26,13 @@ pose_map[i])) and one match_pairs_batch from the guess Rz(yaw) at the origin, wh
 rules are the same, evaluated against the submap: ONE score_pairs call grades every result against its own submap, on the pair
 index the match_pairs_batch left resident.  --closure-yaws N (with --closure-map submap; 0 = off) does not trust the descriptor's yaw
 to its sector: set_pair_maps indexes the submaps once, score_pairs grades N yaws spread over the sector around the descriptor's per
-candidate, the best one becomes the guess and match_pairs_resident registers from it on the same index.  --rebuild-map PATH lays the keyframes down again at the optimised poses
+candidate, the best one becomes the guess and match_pairs_resident registers from it on the same index.  --closure-search [HALF_WIDTH
+PITCH] (with --closure-map submap, not with --closure-yaws; default 2 m at 0.5 m) does not trust the zero translation between the two
+visits either: set_pair_maps indexes the submaps once, ONE search_pairs call counts hits over a position x yaw lattice round Rz(yaw)
+at the origin per candidate (+-HALF_WIDTH in x and y at PITCH, five yaws over the descriptor's sector), ONE score_pairs call grades all
+lattice candidates of all pairs exactly (a ragged pose_off), the best per pair by msfl_relocalize's order (exact inliers descending,
+fixed-point sum ascending, candidate order) becomes the guess, and match_pairs_resident registers from it on the same index; the
+1.5 m rule then compares against the searched guess.  The library has no msfl_relocalize over pairs: this is the chain.  --rebuild-map PATH lays the keyframes down again at the optimised poses
 (Keyframes.insert into two fresh map stores) and saves them as PATH_corner.npz / PATH_surf.npz (mapio.save_grid).  --closure-loss KIND:A (geman_mcclure:1, cauchy:1, soft_l_one:2, huber:0.5, none) gives every closure edge a loss of its
 own (PoseGraph.set_losses) while the odometry chain stays at the graph's Huber loss, in both weight modes: a redescending loss switches
 a closure that contradicts the rest off inside the solve, and after the optimisation every closure's weight rho'(|r|^2)
@@ -124,11 +130,19 @@ def main():
     ap.add_argument("--rebuild-map", metavar="PATH", default=None, help="rebuild both map stores at the optimised poses: PATH_corner.npz, PATH_surf.npz")
     ap.add_argument("--closure-yaws", type=int, default=0,
                     help="submap: score this many yaws round the descriptor's per candidate against its submap and register from the best (0: off)")
+    ap.add_argument("--closure-search", type=float, nargs="*", default=None, metavar="M",
+                    help="submap: search a position x yaw lattice per candidate first (search_pairs): half-width and pitch in metres (default 2 0.5)")
     ap.add_argument("--closure-loss", metavar="KIND:A", default=None,
                     help="the loss of every closure edge, e.g. geman_mcclure:1 (kinds: %s); default: the graph's Huber loss" % ", ".join(capi.GRAPH_LOSS_NAMES[1:]))
     args = ap.parse_args()
     if args.closure_yaws < 0 or (args.closure_yaws > 0 and args.closure_map != "submap"):
         ap.error("--closure-yaws: a count >= 0, with --closure-map submap")
+    if args.closure_search is not None:
+        if args.closure_map != "submap" or args.closure_yaws > 0:
+            ap.error("--closure-search: with --closure-map submap, and not with --closure-yaws")
+        if len(args.closure_search) not in (0, 2) or any(not v > 0.0 for v in args.closure_search):
+            ap.error("--closure-search: no value, or a positive half-width and a positive pitch")
+        args.closure_search = tuple(args.closure_search) or (2.0, 0.5)
     closure_loss = None
     if args.closure_loss:
         kind, _, a = args.closure_loss.partition(":")
@@ -197,6 +211,31 @@ def main():
                 print("scan %3d ~ scan %3d: yaw %+6.1f deg of %d scored (fitness %.3f; the descriptor's own %.3f)"
                       % (candidates[p][0], int(candidates[p][1]["index"]), np.degrees(offsets[best]), N, fit[best], fit[int(np.argmin(np.abs(offsets)))]))
                 guesses[p] = lattice[p * N + best]
+            sub_z, sub_status, _ = h.match_pairs_resident(all_c, co, all_s, so, guesses)
+        elif args.closure_search:
+            # the submaps indexed once; one lattice search over all pairs, one exact score of all its candidates, the registration
+            # starts from each pair's best (msfl_relocalize's chain, over pairs)
+            h.set_pair_maps(sub_c, sub_co, sub_s, sub_so)
+            half_width, pitch = args.closure_search
+            N, sector = 5, 2.0 * np.pi / places.n_sector
+            reach = np.concatenate([np.linalg.norm(all_c[:, :3], axis=1), np.linalg.norm(all_s[:, :3], axis=1)])
+            cells = int(np.ceil(half_width / pitch))
+            cfg = capi.SearchConfig(step=pitch, half=(cells, cells, 0), n_yaw=N, yaw_min=-(N - 1) / 2.0 * sector / N, yaw_step=sector / N, yaw_wraps=0,
+                                    range=float(np.percentile(reach[np.isfinite(reach)], 99)))
+            found = h.search_pairs(all_c, co, all_s, so, guesses, cfg, capacity=8)
+            pose_off = np.cumsum([0] + [len(f) for f in found]).astype(np.int32)
+            rec = h.score_pairs(all_c, co, all_s, so, np.concatenate([f["pose"] for f in found]).reshape(-1, 7), pose_off, args.max_dist)
+            for p, (c, s) in enumerate(feats):
+                r, f = rec[pose_off[p]:pose_off[p + 1]], found[p]
+                if len(f) == 0:
+                    print("scan %3d ~ scan %3d: search found no peak, the descriptor's guess stays" % (candidates[p][0], int(candidates[p][1]["index"])))
+                    continue
+                best = int(np.lexsort((np.arange(len(r)), r["sum_sq_q32"].sum(1), -r["inliers"].sum(1).astype(np.int64)))[0])
+                fit = capi.fitness(r, len(c), len(s))
+                print("scan %3d ~ scan %3d: search node (%+d, %+d) x %.2f m, yaw %+5.1f deg, %d hits, candidate %d of %d (fitness %.3f; the first one's %.3f)"
+                      % (candidates[p][0], int(candidates[p][1]["index"]), f["kx"][best], f["ky"][best], pitch,
+                         np.degrees(cfg.yaw_min + f["a"][best] * cfg.yaw_step), f["hits"][best].sum(), best, len(f), fit[best], fit[0]))
+                guesses[p] = f["pose"][best].copy()
             sub_z, sub_status, _ = h.match_pairs_resident(all_c, co, all_s, so, guesses)
         else:
             sub_z, sub_status, _ = h.match_pairs_batch(sub_c, sub_co, sub_s, sub_so, all_c, co, all_s, so, guesses)

@@ -363,6 +363,25 @@ inline std::vector<std::vector<PoseScore>> ScorePairs(msfl_handle* h, const Stam
   for (std::size_t p = 0; p < scans.size(); ++p) out[p].assign(flat.begin() + po[p], flat.begin() + po[p + 1]);
   return out;
 }
+// SearchPoses against the pair index: scans[p] round guesses[p] against pair map p, all pairs in one call (msfl_search_pairs);
+// out[p]: the best `capacity` peaks of pair p's lattice, best first.  One cfg serves all pairs (a pair's yaw goes into its guess).
+template <class StampedVecT, class RigidVecT>
+inline std::vector<std::vector<msfl_pose_candidate>> SearchPairs(msfl_handle* h, const StampedVecT& scans, const RigidVecT& guesses,
+                                                                 const msfl_search_config& cfg, int capacity) {
+  if (guesses.size() != scans.size()) throw std::invalid_argument("SearchPairs: one guess per scan");
+  std::vector<msfl_point> c, s; std::vector<int> co, so;
+  PackPairs(scans, &c, &co, &s, &so);
+  std::vector<double> g(7 * scans.size());
+  for (std::size_t p = 0; p < scans.size(); ++p) RigidToArray(guesses[p], g.data() + 7 * p);
+  const std::size_t K = static_cast<std::size_t>(capacity > 0 ? capacity : 0);
+  std::vector<msfl_pose_candidate> flat(K * scans.size());
+  std::vector<int> n(scans.size(), 0);
+  Check(msfl_search_pairs(h, static_cast<int>(scans.size()), c.data(), co.data(), s.data(), so.data(), g.data(), &cfg, flat.data(), capacity, n.data(),
+                          nullptr, MSFL_MEM_HOST), h, "msfl_search_pairs");
+  std::vector<std::vector<msfl_pose_candidate>> out(scans.size());
+  for (std::size_t p = 0; p < scans.size(); ++p) out[p].assign(flat.begin() + p * K, flat.begin() + p * K + n[p]);
+  return out;
+}
 // scans[p] registered against pair map p from (*poses)[p], which it replaces; per pair MSFL_OK or MSFL_MAP_TOO_SMALL (pose untouched).
 // The index is not consumed: call it again, or ScorePairs on the result.  `info`: null or one record per pair.
 template <class StampedVecT, class RigidVecT>

@@ -322,6 +322,12 @@ class MappingScanMatcher : public ScanMatcher {
   std::vector<std::vector<PoseScore>> ScorePairs(const StampedVecT& scans, const RigidVecVecT& poses, double max_dist) {
     return adapter::ScorePairs(h_, scans, poses, max_dist);
   }
+  // SearchPoses against the pair index (msfl_search_pairs): scans[p] round guesses[p] against map p, out[p] best first.
+  template <class StampedVecT, class RigidVecT>
+  std::vector<std::vector<msfl_pose_candidate>> SearchPairs(const StampedVecT& scans, const RigidVecT& guesses, const msfl_search_config& cfg,
+                                                            int capacity) {
+    return adapter::SearchPairs(h_, scans, guesses, cfg, capacity);
+  }
   template <class StampedVecT, class RigidVecT>
   std::vector<int> MatchPairsResident(const StampedVecT& scans, RigidVecT* poses) {
     unc_ = msfl_match_uncertainty{};

@@ -536,6 +536,37 @@ msfl_status msfl_relocalize(msfl_handle* h,
                             double max_dist, int n_refine, double min_fitness,
                             msfl_reloc_result* results, int capacity, int* n_out, msfl_mem mem);
 
+/* The search against the resident PAIR index (msfl_set_pair_maps / msfl_match_pairs_batch): scan p round guess p against pair
+   map p, all n_pairs searches in one chain of launches.  No new arithmetic: for every pair p the candidates (row p of
+   `candidates`), n_out[p], the counts and, in device memory, the all-zero slots past n_out[p] are byte for byte what
+   msfl_set_map(pair p's corner map, pair p's surf map) followed by msfl_search_poses(scan p, guesses + 7 p, cfg, ..., capacity,
+   ...) writes.  The geometry of pair p is msfl_search_geometry(guesses + 7 p, cfg, n_corner(p), n_surf(p)); with the one shared
+   cfg only `origin` differs between pairs, and the yaw lattice of pair p is round guess p's quaternion.
+     corner/surf, corner_off/surf_off : the concatenated scans and their n_pairs + 1 prefix offsets (HOST arrays), by the
+                   offset rules of msfl_score_pairs.
+     guesses     : 7 x n_pairs doubles; guesses and cfg are HOST data in both memory kinds.
+     candidates  : n_pairs x capacity records, row p = pair p; 1 <= capacity <= 1024.  n_out: n_pairs counts.
+     hits_out    : optional, n_pairs x 2 x H int32, [p][kind][h].
+   With MSFL_MEM_DEVICE corner, surf, candidates, n_out and hits_out are device pointers, and the call is asynchronous on the
+   handle's stream, ordered after an asynchronous msfl_set_pair_maps; it never waits for the device.  With host memory the
+   slots past n_out[p] are left alone.
+   Refusals, all before anything is staged or launched, in this order: MSFL_BAD_ARG for an unknown memory kind, negative
+   counts, null pointers, bad offsets or a capacity outside 1 .. 1024; what msfl_search_geometry answers for the first pair it
+   refuses (msfl_last_error names the pair); MSFL_NO_MAP without a resident pair index (also while a single map is resident),
+   MSFL_BAD_ARG when n_pairs is not the number of pairs it holds.  msfl_search_poses and msfl_relocalize keep answering
+   MSFL_NO_MAP while a pair index is resident.  A pair with an empty map side or no features of a kind has zero hits of that
+   kind.  n_pairs == 0 is refused or accepted as by msfl_score_pairs.
+   The pairs are processed in chunks that fit a fixed scratch budget (MSFL_SEARCH_CHUNK_PAIRS in the environment forces the
+   chunk size); the results do not depend on the chunking.  The call works in the search scratch only and reads the pair
+   index's point arrays and cell tables: msfl_match_pairs_resident and msfl_score_pairs after it are bit-identical to the same
+   calls without it.  Not provided: a msfl_relocalize over pairs (examples/close_loop.py chains the calls), and a batched
+   search of many scans against the single map. */
+msfl_status msfl_search_pairs(msfl_handle* h, int n_pairs,
+                              const msfl_point* corner, const int* corner_off,
+                              const msfl_point* surf, const int* surf_off,
+                              const double* guesses, const msfl_search_config* cfg,
+                              msfl_pose_candidate* candidates, int capacity, int* n_out, int* hits_out, msfl_mem mem);
+
 /* Kernel-level entry points (the two halves of one outer iteration), exposed so that parity tests
    can pin the data association and the solver separately:
      msfl_associate_scan2map : mapping_scan_matcher.cc:109-246 at a fixed pose.  records_out gets

@@ -27,6 +27,7 @@ PROTOTYPES = dict(t.split("=") for t in """
     msfl_match_scan2map_batch=i:pipppppppi msfl_match_pairs_batch=i:pipppppppppppi msfl_score_poses=i:ppipipidpppi
     msfl_score_poses_batch=i:pippppppdpi msfl_set_pair_maps=i:pippppi msfl_score_pairs=i:pippppppdpppi msfl_match_pairs_resident=i:pipppppppi
     msfl_search_default_config=v:p msfl_search_geometry=i:ppiip msfl_search_poses=i:ppipipppippi msfl_relocalize=i:ppipippididpipi
+    msfl_search_pairs=i:pipppppppippi
     msfl_associate_scan2map=i:ppipipp msfl_solve_records=i:ppipippp msfl_match_scan2map_deskew=i:ppipippp msfl_associate_scan2map_deskew=i:ppipipppp
     msfl_solve_records_deskew=i:ppipipppp msfl_match_scan2map_deskew_batch=i:pippppppppi msfl_match_scan2scan=i:pppppppi
     msfl_match_scan2scan_batch=i:pipppppppi msfl_extract_features=i:pppippi msfl_extract_features_batch=i:pipppppi msfl_voxel_downsample=i:ppifppi
@@ -1090,6 +1091,55 @@ class Handle(_Owner):
                                                int(capacity), _vp(n_out), _vp(hits), MEM_HOST), "msfl_search_poses")
         rec = cand[:int(n_out[0])].copy()
         return (rec, hits[:, :int(geom.n_hypotheses)]) if want_hits else rec
+
+    def search_pairs_device(self, n_pairs, corner, corner_off, surf, surf_off, guesses, config, candidates, capacity, n_out, hits_out=None):
+        """Device-pointer form of search_pairs, asynchronous on the handle's stream: `candidates` holds n_pairs x capacity records of
+        POSE_CANDIDATE_DTYPE.itemsize bytes, n_out n_pairs int32, hits_out (optional) n_pairs x 2 x H int32; the offset arrays, the
+        guesses (n_pairs x 7 doubles) and config are host data."""
+        offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off)]
+        guesses = np.ascontiguousarray(np.asarray(guesses, np.float64).reshape(-1, 7))
+        self._check(self.lib.msfl_search_pairs(self.h, int(n_pairs), _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(guesses), C.byref(config),
+                                               _vp(candidates), int(capacity), _vp(n_out), _vp(hits_out), MEM_DEVICE), "msfl_search_pairs(device)")
+
+    def search_pairs(self, corner, corner_off, surf, surf_off, guesses, config=None, capacity=16, want_hits=False):
+        """search_poses against the resident PAIR index (set_pair_maps, or what match_pairs_batch left): scan p round guesses[p] against
+        pair map p only, all pairs in one call.  Returns a list of P arrays of POSE_CANDIDATE_DTYPE, best first; want_hits: also hits
+        (P, 2, H) int32.  Offsets and guesses are host arrays; numpy clouds go through host memory, torch device tensors (float32
+        (n, 4)) through the device form."""
+        config = SearchConfig() if config is None else config
+        offs = [np.ascontiguousarray(o, np.int32) for o in (corner_off, surf_off)]
+        P = len(offs[0]) - 1
+        guesses = np.ascontiguousarray(np.asarray(guesses, np.float64).reshape(-1, 7))
+        if len(guesses) != P or len(offs[1]) != P + 1:
+            raise ValueError("search_pairs: %d corner offsets, %d surf offsets, %d guesses" % (len(offs[0]), len(offs[1]), len(guesses)))
+        K = max(int(capacity), 1)
+        # (H depends on the config only; the call itself refuses what the geometry rule refuses)
+        _, geom = search_geometry(guesses[0] if P else np.array([0, 0, 0, 0, 0, 0, 1.0]), config, 0, 0, allow=(BAD_ARG, CAPACITY))
+        H = max(int(geom.n_hypotheses), 0) if want_hits else 0
+        if H * max(P, 1) > (1 << 31):
+            raise ValueError("search_pairs: want_hits asks for %d x 2 x %d counts" % (P, H))
+        if _on_device(corner) or _on_device(surf):
+            import torch
+            if not (_on_device(corner) and _on_device(surf)) or corner.dtype != torch.float32 or surf.dtype != torch.float32:
+                raise TypeError("search_pairs: both clouds must be float32 device tensors, or neither")
+            corner, surf = corner.contiguous(), surf.contiguous()
+            cand = torch.zeros(max(P, 1) * K * POSE_CANDIDATE_DTYPE.itemsize, dtype=torch.uint8, device=corner.device)
+            n_out = torch.zeros(max(P, 1), dtype=torch.int32, device=corner.device)
+            hits = torch.zeros((max(P, 1), 2, max(H, 1)), dtype=torch.int32, device=corner.device) if want_hits else None
+            self.search_pairs_device(P, corner, offs[0], surf, offs[1], guesses, config, cand, capacity, n_out, hits)
+            self.synchronize()
+            cand = cand.cpu().numpy().view(POSE_CANDIDATE_DTYPE).reshape(max(P, 1), K)
+            n_out = n_out.cpu().numpy()
+            hits = hits.cpu().numpy() if want_hits else None
+        else:
+            corner, surf = _pts(corner), _pts(surf)
+            cand = np.zeros((max(P, 1), K), POSE_CANDIDATE_DTYPE)
+            n_out = np.zeros(max(P, 1), np.int32)
+            hits = np.zeros((max(P, 1), 2, max(H, 1)), np.int32) if want_hits else None
+            self._check(self.lib.msfl_search_pairs(self.h, P, _vp(corner), _vp(offs[0]), _vp(surf), _vp(offs[1]), _vp(guesses), C.byref(config),
+                                                   _vp(cand), int(capacity), _vp(n_out), _vp(hits), MEM_HOST), "msfl_search_pairs")
+        recs = [cand[p, :int(n_out[p])].copy() for p in range(P)]
+        return (recs, hits[:P, :, :H]) if want_hits else recs
 
     def relocalize(self, corner, surf, guess, config=None, n_candidates=16, max_dist=1.0, n_refine=5, min_fitness=0.5):
         """msfl_relocalize: search, exact score, registration of the best n_refine, exact score again.  Records of RELOC_RESULT_DTYPE,

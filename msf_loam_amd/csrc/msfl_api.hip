@@ -214,7 +214,8 @@ struct ScoreScratch {        // msfl_score_poses*: no other call touches these, 
   DevBuf scan;               // int[H]: scan of every hypothesis (batch form), written by score_init_kernel
   DevBuf out0;               // u64[P]: msfl_score_pairs' first d2_out / nn_out element of every pair (ScorePairsView::out0)
 };
-struct SearchScratch {       // msfl_search_poses / msfl_relocalize: no other call touches these
+struct SearchScratch {       // msfl_search_poses / msfl_search_pairs / msfl_relocalize: no other call touches these.  msfl_search_pairs holds
+                             // every array below C times, C the pairs of one chunk (SearchPairsView), and qtab for all its pairs
   DevBuf corner, surf;       // float4: staged clouds (host mode)
   DevBuf vol;                // u64: the raw volumes [corner | surf], then with dilate = 1 the dilated ones
   DevBuf tab;                // int4[n_yaw x features]: voxel of every feature at every yaw sample
@@ -223,6 +224,7 @@ struct SearchScratch {       // msfl_search_poses / msfl_relocalize: no other ca
   DevBuf ctr;                // int[2]: peaks appended, candidates written
   DevBuf qtab;               // double[4 n_yaw + 7]: the yaw samples' quaternions, then the guess
   DevBuf cand;               // SearchCand[1024]: the select kernel's records
+  DevBuf pair;               // SearchPair[P]: msfl_search_pairs' per-pair table
   DevBuf rl_cand, rl_poses, rl_scores, rl_status, rl_corner, rl_surf;   // msfl_relocalize on device clouds: what its chained calls read and write
 };
 struct SegmentScratch {      // msfl_segment_scan*: allocated by the first call, no other call touches these
@@ -312,6 +314,7 @@ struct msfl_handle_s {
   SearchScratch se;
   SegmentScratch sg;
   int seg_chunk_scans = 0;                // MSFL_SEG_CHUNK_SCANS: scans per chunk of msfl_segment_scans (0 = what the scratch budget holds)
+  int search_chunk_pairs = 0;             // MSFL_SEARCH_CHUNK_PAIRS: pairs per chunk of msfl_search_pairs (0 = what the scratch budget holds)
 
   // msfl_set_uncertainty / msfl_set_degeneracy / msfl_set_outlier_rejection: the knobs, and where every matcher call writes one
   // record per registration.  The uncertainty feature is on while its sink is set; a degeneracy or rejection sink is optional and
@@ -932,6 +935,7 @@ msfl_status msfl_create(const msfl_params* params, int device, msfl_handle** out
   if (const char* e = std::getenv("MSFL_VOXEL_NO_BIG")) h->voxel_no_big = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSFL_ODOM_BIN_SPLIT")) h->odom_bin_split = std::atoi(e) != 0 ? 1 : 0;
   if (const char* e = std::getenv("MSFL_SEG_CHUNK_SCANS")) { const int c = std::atoi(e); if (c >= 1) h->seg_chunk_scans = c; }
+  if (const char* e = std::getenv("MSFL_SEARCH_CHUNK_PAIRS")) { const int c = std::atoi(e); if (c >= 1) h->search_chunk_pairs = c; }
   if (const char* e = std::getenv("MSFL_PREP_SPLIT")) { const int g = std::atoi(e); if (g == 1 || g == 2 || g == 4 || g == 8 || g == 16) h->prep_split = g; }
   *out = h;
   return MSFL_OK;

@@ -1,5 +1,5 @@
 // Pose search over the resident single map — C-ABI entry points msfl_search_default_config, msfl_search_geometry, msfl_search_poses
-// and msfl_relocalize.  Included at the end of msfl_api.hip (shares its handle, DevBuf, PinRing and helper macros); kernels:
+// and msfl_relocalize — and over the resident pair index, scan p round guess p against pair map p — msfl_search_pairs.  Included at the end of msfl_api.hip (shares its handle, DevBuf, PinRing and helper macros); kernels:
 // msfl_search.cuh.  The search stages into scratch of its own (h->se) and reads only the sorted point arrays of the map index: a
 // matcher or scoring call after it finds the handle as it left it.  msfl_relocalize is a chain of the public calls.
 
@@ -79,16 +79,22 @@ void search_yaw_quat(const double* guess, double yaw, double* q) {
   if (n > 0.0) { q[0] = x / n; q[1] = y / n; q[2] = z / n; q[3] = w / n; }
 }
 
-// The search on the stream: candidates in h->se.cand (device), their count in h->se.ctr[1]; d_n_out / d_hits: device pointers the
-// kernels also write (null: none; without d_hits the counts live in h->se.hits).  corner / surf are device pointers.
-msfl_status search_run(msfl_handle* h, const float4* d_corner, int n_corner, const float4* d_surf, int n_surf, const double* guess,
-                       const msfl_search_config* c, const msfl_search_geom& gm, int K, int* d_n_out, int* d_hits, int** hits_used) {
-  hipStream_t st = h->stream;
+// what the kernels take of the geometry
+SearchGeom search_kernel_geom(const msfl_search_geom& gm, const msfl_search_config* c) {
   SearchGeom g{};
   g.ox = gm.origin[0]; g.oy = gm.origin[1]; g.oz = gm.origin[2]; g.inv = gm.inv_step;
   g.dx = gm.dims[0]; g.dy = gm.dims[1]; g.dz = gm.dims[2]; g.W = gm.words_per_row;
   g.nx = gm.n[0]; g.ny = gm.n[1]; g.nz = gm.n[2]; g.n_yaw = gm.n_yaw;
   g.hx = c->half[0]; g.hy = c->half[1]; g.hz = c->half[2];
+  return g;
+}
+
+// The search on the stream: candidates in h->se.cand (device), their count in h->se.ctr[1]; d_n_out / d_hits: device pointers the
+// kernels also write (null: none; without d_hits the counts live in h->se.hits).  corner / surf are device pointers.
+msfl_status search_run(msfl_handle* h, const float4* d_corner, int n_corner, const float4* d_surf, int n_surf, const double* guess,
+                       const msfl_search_config* c, const msfl_search_geom& gm, int K, int* d_n_out, int* d_hits, int** hits_used) {
+  hipStream_t st = h->stream;
+  const SearchGeom g = search_kernel_geom(gm, c);
   const int H = (int)gm.n_hypotheses, F = n_corner + n_surf;
   const size_t vol_words = (size_t)gm.volume_bytes / 8;
   const size_t all_words = 2 * (size_t)(1 + c->dilate) * vol_words;
@@ -112,7 +118,7 @@ msfl_status search_run(msfl_handle* h, const float4* d_corner, int n_corner, con
   unsigned long long *use_c = raw_c, *use_s = raw_s;
   int* ctr = h->se.ctr.as<int>();
   hipLaunchKernelGGL(search_clear_kernel, dim3((unsigned)((std::max<size_t>(all_words, 2) + kSearchBlock - 1) / kSearchBlock)), dim3(kSearchBlock), 0, st,
-                     raw_c, all_words, ctr);
+                     raw_c, all_words, ctr, 2);
   const int n_mc = h->map_c.n_input, n_ms = h->map_s.n_input;
   if (n_mc > 0)
     hipLaunchKernelGGL(search_fill_kernel, dim3(div_up(n_mc, kSearchBlock)), dim3(kSearchBlock), 0, st, g, (const GridDesc*)h->map_c.gdesc.as<GridDesc>(),
@@ -153,6 +159,115 @@ msfl_status search_check(msfl_handle* h, const std::string& w, const void* corne
   if (s) return fail(h, s, w + ": " + why);
   if (!h->have_map || h->pr.resident)
     return fail(h, MSFL_NO_MAP, w + ": no resident single map (msfl_set_map has not been called, or a pair index replaced it)");
+  return MSFL_OK;
+}
+
+// msfl_search_pairs: device scratch the pairs of one chunk may take together (volumes, table, counts, keys, records).  A pair
+// needs 2 (1 + dilate) volume_bytes + 16 n_yaw F + 16 H + 88 K; one pair always runs, whatever it needs (max_volume_bytes bounds it).
+constexpr long long kSearchPairsBudget = 256ll << 20;
+constexpr int kSearchPairsMaxChunk = 65535;          // gridDim.y
+
+// The P searches on the stream, chunk by chunk.  Checked arguments; gms[p]: the geometry of pair p (they differ in origin only);
+// co / so: P + 1 offsets into d_corner / d_surf.  Host memory: every chunk is waited for and its results copied out.
+msfl_status search_pairs_run(msfl_handle* h, int P, const float4* d_corner, const int* co, const float4* d_surf, const int* so, const double* guesses,
+                             const msfl_search_config* c, const std::vector<msfl_search_geom>& gms, int K, msfl_pose_candidate* candidates, int* n_out,
+                             int* hits_out, bool dev) {
+  hipStream_t st = h->stream;
+  const msfl_search_geom& gm = gms[0];
+  const SearchGeom g = search_kernel_geom(gm, c);              // (the origin is pair 0's: the pairs kernels take theirs from the table)
+  const int H = (int)gm.n_hypotheses, n_yaw = gm.n_yaw;
+  const size_t vol_words = (size_t)gm.volume_bytes / 8;
+  const size_t pair_words = 2 * (size_t)(1 + c->dilate) * vol_words;
+  const size_t q_stride = 4 * (size_t)n_yaw + 7;
+  int f_max = 0;
+  for (int p = 0; p < P; p++) f_max = std::max(f_max, (co[p + 1] - co[p]) + (so[p + 1] - so[p]));
+  const long long per_pair = (long long)pair_words * 8 + 16ll * n_yaw * f_max + 16ll * H + (long long)sizeof(SearchCand) * K + 8;
+  long long C_ll = h->search_chunk_pairs > 0 ? h->search_chunk_pairs : std::max<long long>(1, kSearchPairsBudget / per_pair);
+  const int C = (int)std::min<long long>(std::min<long long>(C_ll, kSearchPairsMaxChunk), P);
+
+  // the tables of all P pairs, uploaded once: yaw quaternions and guess, origin, feature ranges, table offsets (inside the pair's chunk)
+  std::vector<double> qt((size_t)P * q_stride);
+  std::vector<SearchPair> pt((size_t)P);
+  size_t tab_max = 1;
+  for (int p0 = 0; p0 < P; p0 += C) {
+    size_t at = 0;
+    for (int p = p0; p < std::min(P, p0 + C); p++) {
+      const double* guess = guesses + 7 * (size_t)p;
+      double* q = &qt[(size_t)p * q_stride];
+      for (int a = 0; a < n_yaw; a++) search_yaw_quat(guess, c->yaw_min + (double)a * c->yaw_step, q + 4 * (size_t)a);
+      for (int k = 0; k < 7; k++) q[4 * (size_t)n_yaw + k] = guess[k];
+      SearchPair& e = pt[p];
+      e.ox = gms[p].origin[0]; e.oy = gms[p].origin[1]; e.oz = gms[p].origin[2];
+      e.n_corner = co[p + 1] - co[p]; e.n_surf = so[p + 1] - so[p];
+      e.corner0 = co[p]; e.surf0 = so[p];
+      e.reserved_ = 0;
+      e.tab0 = at;
+      at += (size_t)n_yaw * (size_t)(e.n_corner + e.n_surf);
+    }
+    tab_max = std::max(tab_max, at);
+  }
+  const bool own_hits = !(dev && hits_out);
+  HIPCHK(h, h->se.vol.reserve((size_t)C * pair_words * 8));
+  HIPCHK(h, h->se.tab.reserve(tab_max * sizeof(int4)));
+  if (own_hits) HIPCHK(h, h->se.hits.reserve(2 * (size_t)C * H * sizeof(int)));
+  HIPCHK(h, h->se.peaks.reserve((size_t)C * H * sizeof(unsigned long long)));
+  if (!dev) HIPCHK(h, h->se.cand.reserve((size_t)C * K * sizeof(SearchCand)));
+  HIPCHK(h, h->se.ctr.reserve(2 * (size_t)C * sizeof(int)));
+  HIPCHK(h, h->se.qtab.reserve(qt.size() * sizeof(double)));
+  HIPCHK(h, h->se.pair.reserve(pt.size() * sizeof(SearchPair)));
+  HIPCHK(h, h->pin.upload(h->se.qtab.p, qt.data(), qt.size() * sizeof(double), st));
+  HIPCHK(h, h->pin.upload(h->se.pair.p, pt.data(), pt.size() * sizeof(SearchPair), st));
+  std::vector<SearchCand> got;                                  // host memory: a chunk's records before the first n of every pair go out
+  if (!dev) { got.resize((size_t)C * K); HIPCHK(h, h->readback.reserve(2 * (size_t)C * sizeof(int))); }
+
+  const int chunks = div_up(g.nx, 64);
+  for (int p0 = 0; p0 < P; p0 += C) {
+    const int n = std::min(C, P - p0);
+    SearchPairsView v{};
+    v.pair = h->se.pair.as<SearchPair>() + p0;
+    v.qtab = h->se.qtab.as<double>() + (size_t)p0 * q_stride;
+    v.vol = h->se.vol.as<unsigned long long>(); v.vol_words = vol_words;
+    v.tab = h->se.tab.as<int4>();
+    v.hits = own_hits ? h->se.hits.as<int>() : hits_out + 2 * (size_t)p0 * H;
+    v.peaks = h->se.peaks.as<unsigned long long>();
+    v.ctr = h->se.ctr.as<int>();
+    v.cand = dev ? reinterpret_cast<SearchCand*>(candidates) + (size_t)p0 * K : h->se.cand.as<SearchCand>();
+    v.n_out = dev ? n_out + p0 : nullptr;
+    v.n_pairs = n; v.dilate = c->dilate; v.H = H; v.K = K;
+    int map_c = 0, map_s = 0, f_most = 0;                       // the chunk's longest map of each kind, its scan with the most features
+    for (int p = p0; p < p0 + n; p++) {
+      map_c = std::max(map_c, h->pr.n_c[p]); map_s = std::max(map_s, h->pr.n_s[p]);
+      f_most = std::max(f_most, pt[p].n_corner + pt[p].n_surf);
+    }
+    const size_t all_words = (size_t)n * pair_words;
+    hipLaunchKernelGGL(search_clear_kernel, dim3((unsigned)((std::max<size_t>(all_words, 2 * (size_t)n) + kSearchBlock - 1) / kSearchBlock)), dim3(kSearchBlock), 0,
+                       st, v.vol, all_words, v.ctr, 2 * n);
+    if (map_c > 0)
+      hipLaunchKernelGGL(search_fill_pairs_kernel, dim3(div_up(map_c, kSearchBlock), n), dim3(kSearchBlock), 0, st, g, v, 0, (const int*)h->map_c.cell_start.as<int>(),
+                         (const int*)h->pr.base_c.as<int>() + p0, (const float4*)h->map_c.sorted.as<float4>());
+    if (map_s > 0)
+      hipLaunchKernelGGL(search_fill_pairs_kernel, dim3(div_up(map_s, kSearchBlock), n), dim3(kSearchBlock), 0, st, g, v, 1, (const int*)h->map_s.cell_start.as<int>(),
+                         (const int*)h->pr.base_s.as<int>() + p0, (const float4*)h->map_s.sorted.as<float4>());
+    if (c->dilate)
+      hipLaunchKernelGGL(search_dilate_pairs_kernel, dim3((unsigned)((2 * (size_t)n * vol_words + kSearchBlock - 1) / kSearchBlock)), dim3(kSearchBlock), 0, st, g, v);
+    if (f_most > 0)
+      hipLaunchKernelGGL(search_table_pairs_kernel, dim3((unsigned)(((size_t)n_yaw * f_most + kSearchBlock - 1) / kSearchBlock), n), dim3(kSearchBlock), 0, st, g, v,
+                         d_corner, d_surf);
+    hipLaunchKernelGGL(search_correlate_pairs_kernel, dim3((unsigned)((size_t)n_yaw * g.nz * g.ny * chunks), n), dim3(64), 0, st, g, v, chunks);
+    hipLaunchKernelGGL(search_peaks_pairs_kernel, dim3(div_up(H, kSearchBlock), n), dim3(kSearchBlock), 0, st, g, v, c->nms_cells, c->nms_yaws, c->yaw_wraps);
+    hipLaunchKernelGGL(search_select_pairs_kernel, dim3(1, n), dim3(kSearchSelectBlock), 0, st, g, v, c->step);
+    HIPCHK(h, hipGetLastError());
+    if (dev) continue;
+    HIPCHK(h, hipMemcpyAsync(h->readback.p, v.ctr, 2 * (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (hits_out) HIPCHK(h, hipMemcpyAsync(hits_out + 2 * (size_t)p0 * H, v.hits, 2 * (size_t)n * H * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(got.data(), v.cand, (size_t)n * K * sizeof(SearchCand), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    for (int p = 0; p < n; p++) {
+      const int k = h->readback.as<int>()[2 * p + 1];
+      if (k > 0) std::memcpy(candidates + (size_t)(p0 + p) * K, &got[(size_t)p * K], (size_t)k * sizeof(SearchCand));
+      n_out[p0 + p] = k;
+    }
+  }
   return MSFL_OK;
 }
 
@@ -321,6 +436,47 @@ msfl_status msfl_relocalize(msfl_handle* h, const msfl_point* corner, int n_corn
     results[i] = o;
   }
   *n_out = R;
+  return MSFL_OK;
+}
+
+msfl_status msfl_search_pairs(msfl_handle* h, int n_pairs, const msfl_point* corner, const int* corner_off, const msfl_point* surf, const int* surf_off,
+                              const double* guesses, const msfl_search_config* cfg, msfl_pose_candidate* candidates, int capacity, int* n_out,
+                              int* hits_out, msfl_mem mem) {
+  msfl_status s = enter(h); if (s) return s;
+  const std::string w("msfl_search_pairs");
+  const int P = n_pairs;
+  // 1. the arguments
+  if (mem != MSFL_MEM_HOST && mem != MSFL_MEM_DEVICE) return fail(h, MSFL_BAD_ARG, w + ": unknown memory kind");
+  if (P < 0 || (P > 0 && (!corner_off || !surf_off || !guesses || !cfg || !candidates || !n_out))) return fail(h, MSFL_BAD_ARG, w + ": negative count or null argument");
+  if (capacity < 1 || capacity > kSearchMaxK) return fail(h, MSFL_BAD_ARG, w + ": the candidate capacity must be 1 .. 1024");
+  std::vector<int> co((size_t)P + 1, 0), so((size_t)P + 1, 0);
+  if (P > 0) {
+    const int c0 = corner_off[0], s0 = surf_off[0];
+    if (c0 < 0 || s0 < 0) return fail(h, MSFL_BAD_ARG, w + ": negative offset");
+    for (int p = 0; p <= P; p++) {
+      co[p] = corner_off[p] - c0; so[p] = surf_off[p] - s0;
+      if (p > 0 && (co[p] < co[p - 1] || so[p] < so[p - 1])) return fail(h, MSFL_BAD_ARG, w + ": offset arrays must be non-decreasing");
+    }
+    if ((co[P] > 0 && !corner) || (so[P] > 0 && !surf)) return fail(h, MSFL_BAD_ARG, w + ": null cloud");
+  }
+  // 2. the geometry rule, pair by pair (with one cfg the results differ in origin only)
+  std::vector<msfl_search_geom> gms((size_t)P);
+  for (int p = 0; p < P; p++) {
+    std::string why;
+    s = search_geometry(guesses + 7 * (size_t)p, cfg, co[p + 1] - co[p], so[p + 1] - so[p], &gms[p], &why);
+    if (s) return fail(h, s, w + ": pair " + std::to_string(p) + ": " + why);
+  }
+  // 3. the pair index
+  s = pairs_resident(h, w, P); if (s) return s;
+  if (P == 0) return MSFL_OK;
+  hipStream_t st = h->stream;
+  const bool dev = mem == MSFL_MEM_DEVICE;
+  // (both memory kinds read from the first used element on: the offsets are relative to it)
+  const float4 *d_corner, *d_surf;
+  s = stage_in(h, h->se.corner, co[P] ? corner + corner_off[0] : corner, (size_t)co[P], mem, st, &d_corner); if (s) return s;
+  s = stage_in(h, h->se.surf, so[P] ? surf + surf_off[0] : surf, (size_t)so[P], mem, st, &d_surf); if (s) return s;
+  s = search_pairs_run(h, P, d_corner, co.data(), d_surf, so.data(), guesses, cfg, gms, capacity, candidates, n_out, hits_out, dev); if (s) return s;
+  // host clouds were staged with asynchronous copies from pageable memory; every chunk was waited for
   return MSFL_OK;
 }
 

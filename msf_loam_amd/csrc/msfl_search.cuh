@@ -13,6 +13,10 @@
 //   search_peaks_kernel      one lane per hypothesis: the key ((0xffffffff - total) << 32) | h, the peak test, peaks appended
 //   search_select_kernel     ONE workgroup: exact radix select of the K smallest keys, bitonic sort, candidate records
 //
+// Every kernel is a thin wrapper round a __device__ body, and has a second wrapper, <name>_pairs_kernel, for msfl_search_pairs:
+// blockIdx.y is the pair inside the chunk of pairs in flight, blockIdx.x what it is in the single form (a pair's surplus
+// workgroups leave at once).  All pairs share one SearchGeom but the box origin; what differs sits in a SearchPair table.
+//
 // Volume layout: bit x & 63 of word [(z * dims.y + y) * W + (x >> 6)], W = ceil(dims.x / 64) + 1.  Bits at x >= dims.x and the last
 // word of every row stay zero; a window that hangs over either end of a row reads zero words there (range checks, no over-read).
 #pragma once
@@ -40,20 +44,49 @@ struct SearchCand {                              // msfl_pose_candidate
   int reserved_;
 };
 
-// words: 2 volumes (x 2 when dilated) back to back.  ctr: [0] peaks appended, [1] candidates written (the kernel's own n_out)
-__global__ void __launch_bounds__(kSearchBlock) search_clear_kernel(unsigned long long* __restrict__ words, size_t n, int* __restrict__ ctr) {
+// ---- the pairs form: C pairs in flight, every per-pair array a dense [C] x (the single form's array) -------------------------------
+struct SearchPair {                              // one pair of msfl_search_pairs, host-built
+  float ox, oy, oz;                              // its box origin; the rest of SearchGeom is the call's
+  int n_corner, n_surf;
+  int corner0, surf0;                            // its first feature in the call's scan clouds
+  int reserved_;
+  unsigned long long tab0;                       // its first entry in the chunk's table
+};
+struct SearchPairsView {
+  const SearchPair* pair;                        // [C]
+  const double* qtab;                            // [C] x (4 n_yaw quaternion entries, then the pair's guess)
+  unsigned long long* vol;                       // raw volumes [C][kind], then with dilate = 1 the dilated ones [C][kind]
+  size_t vol_words;                              // words of one volume
+  int4* tab;
+  int* hits;                                     // [C][kind][H]
+  unsigned long long* peaks;                     // [C][H]
+  int* ctr;                                      // [C][2]
+  SearchCand* cand;                              // [C][K]
+  int* n_out;                                    // [C], or null
+  int n_pairs, dilate, H, K;
+};
+// (flat offsets over a chunk go through size_t: C x H passes 2^31 quickly; what is indexed inside a pair stays 32-bit)
+__device__ __forceinline__ SearchGeom search_pair_geom(SearchGeom g, const SearchPair& p) { g.ox = p.ox; g.oy = p.oy; g.oz = p.oz; return g; }
+__device__ __forceinline__ const double* search_pair_qtab(const SearchPairsView& v, const SearchGeom& g, int p) {
+  return v.qtab + (size_t)p * (4 * (size_t)g.n_yaw + 7);
+}
+__device__ __forceinline__ const unsigned long long* search_pair_vol(const SearchPairsView& v, int p, int kind) {
+  return v.vol + ((v.dilate ? 2 * (size_t)v.n_pairs : 0) + 2 * (size_t)p + kind) * v.vol_words;
+}
+
+// words: 2 volumes (x 2 when dilated) back to back, of every pair in flight.  ctr, per pair: [0] peaks appended, [1] candidates written (the kernel's own n_out)
+__global__ void __launch_bounds__(kSearchBlock) search_clear_kernel(unsigned long long* __restrict__ words, size_t n, int* __restrict__ ctr, int n_ctr) {
   const size_t i = (size_t)blockIdx.x * kSearchBlock + threadIdx.x;
   if (i < n) words[i] = 0ull;
-  if (i < 2) ctr[i] = 0;
+  if (i < (size_t)n_ctr) ctr[i] = 0;                       // 2 per pair
 }
 
 // voxel coordinate of one axis as a float: the two f32 operations of the definition (the library is built without contraction)
 __device__ __forceinline__ float search_voxel(float x, float o, float inv) { return floorf((x - o) * inv); }
 
-__global__ void __launch_bounds__(kSearchBlock) search_fill_kernel(SearchGeom g, const GridDesc* __restrict__ gd,
-                                                                    const float4* __restrict__ pts, unsigned long long* __restrict__ vol) {
-  const int i = blockIdx.x * kSearchBlock + threadIdx.x;
-  if (i >= gd->n_pts) return;                              // the index's sorted copy holds the map's finite points
+// point i of the n finite points of one map
+__device__ __forceinline__ void search_fill_body(const SearchGeom& g, int n, const float4* __restrict__ pts, unsigned long long* __restrict__ vol, int i) {
+  if (i >= n) return;
   const float4 p = pts[i];
   const float fx = search_voxel(p.x, g.ox, g.inv), fy = search_voxel(p.y, g.oy, g.inv), fz = search_voxel(p.z, g.oz, g.inv);
   // (a NaN fails every comparison)
@@ -61,11 +94,23 @@ __global__ void __launch_bounds__(kSearchBlock) search_fill_kernel(SearchGeom g,
   const int x = (int)fx, y = (int)fy, z = (int)fz;
   atomicOr(&vol[((size_t)z * g.dy + y) * g.W + (x >> 6)], 1ull << (x & 63));
 }
+__global__ void __launch_bounds__(kSearchBlock) search_fill_kernel(SearchGeom g, const GridDesc* __restrict__ gd,
+                                                                    const float4* __restrict__ pts, unsigned long long* __restrict__ vol) {
+  search_fill_body(g, gd->n_pts, pts, vol, blockIdx.x * kSearchBlock + threadIdx.x);   // the index's sorted copy holds the map's finite points
+}
+// The pair index keeps no point count in GridDesc[p]; a pair's finite points are what its slice of the cell table holds, the
+// positions [cell_start[cell_base[p]], cell_start[cell_base[p + 1]]) of the concatenated sorted copy.
+__global__ void __launch_bounds__(kSearchBlock) search_fill_pairs_kernel(SearchGeom g, SearchPairsView v, int kind, const int* __restrict__ cell_start,
+                                                                          const int* __restrict__ cell_base, const float4* __restrict__ sorted) {
+  const int p = blockIdx.y;
+  const int lo = cell_start[cell_base[p]], n = cell_start[cell_base[p + 1]] - lo;
+  if ((int)blockIdx.x * kSearchBlock >= n) return;
+  search_fill_body(search_pair_geom(g, v.pair[p]), n, sorted + lo, v.vol + (2 * (size_t)p + kind) * v.vol_words, blockIdx.x * kSearchBlock + threadIdx.x);
+}
 
-__global__ void __launch_bounds__(kSearchBlock) search_dilate_kernel(SearchGeom g, const unsigned long long* __restrict__ in,
-                                                                      unsigned long long* __restrict__ out) {
+// word i of one volume
+__device__ __forceinline__ void search_dilate_body(const SearchGeom& g, const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out, size_t i) {
   const size_t n = (size_t)g.dz * g.dy * g.W;
-  const size_t i = (size_t)blockIdx.x * kSearchBlock + threadIdx.x;
   if (i >= n) return;
   const int w = (int)(i % g.W);
   const size_t row = i / g.W;
@@ -90,15 +135,25 @@ __global__ void __launch_bounds__(kSearchBlock) search_dilate_kernel(SearchGeom 
   else if (first < g.dx) keep = (1ull << (g.dx - first)) - 1ull;
   out[i] = acc & keep;
 }
+__global__ void __launch_bounds__(kSearchBlock) search_dilate_kernel(SearchGeom g, const unsigned long long* __restrict__ in,
+                                                                      unsigned long long* __restrict__ out) {
+  search_dilate_body(g, in, out, (size_t)blockIdx.x * kSearchBlock + threadIdx.x);
+}
+// flat over the 2 C equal-sized raw volumes of the chunk (the origin plays no part)
+__global__ void __launch_bounds__(kSearchBlock) search_dilate_pairs_kernel(SearchGeom g, SearchPairsView v) {
+  const size_t i = (size_t)blockIdx.x * kSearchBlock + threadIdx.x;
+  const size_t vi = i / v.vol_words;
+  if (vi >= 2 * (size_t)v.n_pairs) return;
+  const unsigned long long* in = v.vol + vi * v.vol_words;
+  search_dilate_body(g, in, v.vol + (2 * (size_t)v.n_pairs + vi) * v.vol_words, i - vi * v.vol_words);
+}
 
 // qtab: n_yaw x 4 doubles, the normalised quaternion of every yaw sample (host-computed: the device copies, it does not redo
 // the trigonometry); guess: the guess pose (its translation is that of pose(a, 0)).  tab[a * F + f], corner features first.
-__global__ void __launch_bounds__(kSearchBlock) search_table_kernel(SearchGeom g, const float4* __restrict__ corner, int n_corner,
-                                                                     const float4* __restrict__ surf, int n_surf,
-                                                                     const double* __restrict__ qtab, const double* __restrict__ guess,
-                                                                     int4* __restrict__ tab) {
+__device__ __forceinline__ void search_table_body(const SearchGeom& g, const float4* __restrict__ corner, int n_corner,
+                                                  const float4* __restrict__ surf, int n_surf, const double* __restrict__ qtab,
+                                                  const double* __restrict__ guess, int4* __restrict__ tab, size_t i) {
   const int F = n_corner + n_surf;
-  const size_t i = (size_t)blockIdx.x * kSearchBlock + threadIdx.x;
   if (i >= (size_t)g.n_yaw * F) return;
   const int a = (int)(i / F), f = (int)(i % F);
   const int kind = f < n_corner ? 0 : 1;
@@ -116,12 +171,28 @@ __global__ void __launch_bounds__(kSearchBlock) search_table_kernel(SearchGeom g
   }
   tab[(size_t)a * F + f] = e;
 }
+__global__ void __launch_bounds__(kSearchBlock) search_table_kernel(SearchGeom g, const float4* __restrict__ corner, int n_corner,
+                                                                     const float4* __restrict__ surf, int n_surf,
+                                                                     const double* __restrict__ qtab, const double* __restrict__ guess,
+                                                                     int4* __restrict__ tab) {
+  search_table_body(g, corner, n_corner, surf, n_surf, qtab, guess, tab, (size_t)blockIdx.x * kSearchBlock + threadIdx.x);
+}
+// ragged: grid.x serves the pair with the most features
+__global__ void __launch_bounds__(kSearchBlock) search_table_pairs_kernel(SearchGeom g, SearchPairsView v, const float4* __restrict__ corner,
+                                                                           const float4* __restrict__ surf) {
+  const int p = blockIdx.y;
+  const SearchPair pr = v.pair[p];
+  if ((size_t)blockIdx.x * kSearchBlock >= (size_t)g.n_yaw * (pr.n_corner + pr.n_surf)) return;
+  const double* qt = search_pair_qtab(v, g, p);
+  search_table_body(search_pair_geom(g, pr), corner + pr.corner0, pr.n_corner, surf + pr.surf0, pr.n_surf, qt, qt + 4 * (size_t)g.n_yaw, v.tab + pr.tab0,
+                    (size_t)blockIdx.x * kSearchBlock + threadIdx.x);
+}
 
 // grid.x = ((a * nz + kz') * ny + ky') * chunks + chunk; one wavefront.  Lane t owns x-shift kx' = 64 chunk + t.
-__global__ void __launch_bounds__(64) search_correlate_kernel(SearchGeom g, const int4* __restrict__ tab, int n_corner, int n_surf,
-                                                               const unsigned long long* __restrict__ vol_c,
-                                                               const unsigned long long* __restrict__ vol_s, int chunks,
-                                                               int* __restrict__ hits, int H) {
+__device__ __forceinline__ void search_correlate_body(const SearchGeom& g, const int4* __restrict__ tab, int n_corner, int n_surf,
+                                                      const unsigned long long* __restrict__ vol_c,
+                                                      const unsigned long long* __restrict__ vol_s, int chunks,
+                                                      int* __restrict__ hits, int H) {
   const int lane = threadIdx.x;
   int b = blockIdx.x;
   const int chunk = b % chunks; b /= chunks;
@@ -180,15 +251,28 @@ __global__ void __launch_bounds__(64) search_correlate_kernel(SearchGeom g, cons
     if (kxp < g.nx) hits[(size_t)kind * H + h0 + lane] = count;
   }
 }
+__global__ void __launch_bounds__(64) search_correlate_kernel(SearchGeom g, const int4* __restrict__ tab, int n_corner, int n_surf,
+                                                               const unsigned long long* __restrict__ vol_c,
+                                                               const unsigned long long* __restrict__ vol_s, int chunks,
+                                                               int* __restrict__ hits, int H) {
+  search_correlate_body(g, tab, n_corner, n_surf, vol_c, vol_s, chunks, hits, H);
+}
+// grid (the single form's grid.x, C): workgroups are handed out x first, so those of one pair are neighbours in dispatch order and
+// its two volumes stay in the reach of few L2s -- a guess about placement, not a measured fact
+__global__ void __launch_bounds__(64) search_correlate_pairs_kernel(SearchGeom g, SearchPairsView v, int chunks) {
+  const int p = blockIdx.y;
+  const SearchPair pr = v.pair[p];
+  search_correlate_body(g, v.tab + pr.tab0, pr.n_corner, pr.n_surf, search_pair_vol(v, p, 0), search_pair_vol(v, p, 1), chunks,
+                        v.hits + 2 * (size_t)p * v.H, v.H);
+}
 
 __device__ __forceinline__ unsigned long long search_key(int total, int h) {
   return ((unsigned long long)(0xffffffffu - (unsigned)total) << 32) | (unsigned)h;
 }
 
 // peaks: keys of the peaks, appended in no particular order (they are unique, the select orders them); ctr[0] counts them
-__global__ void __launch_bounds__(kSearchBlock) search_peaks_kernel(SearchGeom g, const int* __restrict__ hits, int H, int nms_cells,
-                                                                     int nms_yaws, int wraps, unsigned long long* __restrict__ peaks,
-                                                                     int* __restrict__ ctr) {
+__device__ __forceinline__ void search_peaks_body(const SearchGeom& g, const int* __restrict__ hits, int H, int nms_cells, int nms_yaws,
+                                                  int wraps, unsigned long long* __restrict__ peaks, int* __restrict__ ctr) {
   const int h = blockIdx.x * kSearchBlock + threadIdx.x;
   bool peak = false;
   unsigned long long key = 0ull;
@@ -220,14 +304,23 @@ __global__ void __launch_bounds__(kSearchBlock) search_peaks_kernel(SearchGeom g
   base = __shfl(base, __ffsll((long long)m) - 1);
   if (peak) peaks[base + __popcll(m & ((1ull << lane) - 1ull))] = key;
 }
+__global__ void __launch_bounds__(kSearchBlock) search_peaks_kernel(SearchGeom g, const int* __restrict__ hits, int H, int nms_cells,
+                                                                     int nms_yaws, int wraps, unsigned long long* __restrict__ peaks,
+                                                                     int* __restrict__ ctr) {
+  search_peaks_body(g, hits, H, nms_cells, nms_yaws, wraps, peaks, ctr);
+}
+// pair p appends into its own key range with its own counter
+__global__ void __launch_bounds__(kSearchBlock) search_peaks_pairs_kernel(SearchGeom g, SearchPairsView v, int nms_cells, int nms_yaws, int wraps) {
+  const int p = blockIdx.y;
+  search_peaks_body(g, v.hits + 2 * (size_t)p * v.H, v.H, nms_cells, nms_yaws, wraps, v.peaks + (size_t)p * v.H, v.ctr + 2 * p);
+}
 
 // ONE workgroup.  The K smallest of the ctr[0] peak keys (exact radix select, 8 bits per pass from the top, the pattern of
 // place_prefilter_kernel; keys are unique), sorted, as candidate records; ctr[1] = n_out = records written.
-__global__ void __launch_bounds__(kSearchSelectBlock) search_select_kernel(SearchGeom g, const unsigned long long* __restrict__ peaks,
-                                                                            int* __restrict__ ctr, int K, const int* __restrict__ hits,
-                                                                            int H, const double* __restrict__ qtab,
-                                                                            const double* __restrict__ guess, double step,
-                                                                            SearchCand* __restrict__ out, int* __restrict__ n_out) {
+__device__ __forceinline__ void search_select_body(const SearchGeom& g, const unsigned long long* __restrict__ peaks, int* __restrict__ ctr, int K,
+                                                   const int* __restrict__ hits, int H, const double* __restrict__ qtab,
+                                                   const double* __restrict__ guess, double step, SearchCand* __restrict__ out,
+                                                   int* __restrict__ n_out) {
   __shared__ int s_hist[256];
   __shared__ int s_bin, s_left, s_fill;
   __shared__ unsigned long long s_key[kSearchMaxK];
@@ -314,6 +407,20 @@ __global__ void __launch_bounds__(kSearchSelectBlock) search_select_kernel(Searc
     c.h = 0; c.a = 0; c.kx = 0; c.ky = 0; c.kz = 0; c.hits[0] = 0; c.hits[1] = 0; c.reserved_ = 0;
     out[tid] = c;
   }
+}
+__global__ void __launch_bounds__(kSearchSelectBlock) search_select_kernel(SearchGeom g, const unsigned long long* __restrict__ peaks,
+                                                                            int* __restrict__ ctr, int K, const int* __restrict__ hits,
+                                                                            int H, const double* __restrict__ qtab,
+                                                                            const double* __restrict__ guess, double step,
+                                                                            SearchCand* __restrict__ out, int* __restrict__ n_out) {
+  search_select_body(g, peaks, ctr, K, hits, H, qtab, guess, step, out, n_out);
+}
+// one workgroup per pair
+__global__ void __launch_bounds__(kSearchSelectBlock) search_select_pairs_kernel(SearchGeom g, SearchPairsView v, double step) {
+  const int p = blockIdx.y;
+  const double* qt = search_pair_qtab(v, g, p);
+  search_select_body(g, v.peaks + (size_t)p * v.H, v.ctr + 2 * p, v.K, v.hits + 2 * (size_t)p * v.H, v.H, qt, qt + 4 * (size_t)g.n_yaw, step,
+                     v.cand + (size_t)p * v.K, v.n_out ? v.n_out + p : nullptr);
 }
 
 }  // namespace msfl
