@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdint>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -462,10 +463,60 @@ class HybridGrid {
     return info;
   }
 
+  // Not in the reference: the range image this store predicts for a sensor at the map pose `pose` (msfl_grid_render; config ==
+  // nullptr: msfl_carve_default_config), n_row x n_col floats, +inf where the store holds nothing.  accumulate: the minimum is taken
+  // into the image that `image` holds already (rendered from another store with the same configuration).
+  msfl_grid_render_info Render(const Rigid3d& pose, std::vector<float>* image, const msfl_carve_config* config = nullptr, bool accumulate = false) {
+    msfl_carve_config c;
+    if (config) c = *config; else msfl_carve_default_config(&c);
+    msfl_grid_render_info info{};
+    double v[7];
+    adapter::RigidToArray(pose, v);
+    const std::size_t npix = c.n_col > 0 && c.n_row > 0 ? static_cast<std::size_t>(c.n_col) * static_cast<std::size_t>(c.n_row) : 1;
+    if (!accumulate || image->size() != npix) image->assign(npix, std::numeric_limits<float>::infinity());
+    detail::Check(msfl_grid_render(g_, v, &c, image->data(), accumulate ? 1 : 0, MSFL_MEM_HOST, &info), h_, "msfl_grid_render");
+    return info;
+  }
+
+  msfl_handle* handle() const { return h_; }
+  msfl_grid* grid() const { return g_; }
+
  private:
   msfl_handle* h_ = nullptr;
   msfl_grid* g_ = nullptr;
 };
+
+// What ScanNovelty delivers: one class per scan point (MSFL_NOV_*), the counts, and the cloud with the points of the dropped classes
+// removed (the C call's masked_out sets them to NaN; a PointCloud has no use for those).
+struct ScanNoveltyResult {
+  std::vector<uint8_t> cls;
+  msfl_novelty_info info{};
+  std::shared_ptr<PointCloud<PointType>> kept;
+};
+
+// Not in the reference: label `scan` (sensor frame), taken at the map pose `pose`, against what the stores hold
+// (msfl_grids_scan_novelty; config == nullptr: msfl_novelty_default_config).  The stores are rendered into one range image and every
+// scan point is NONE, UNSEEN, COVERED or IN_FRONT of it.  Every store has its own handle here, so the renders run store by store and
+// the labels on the first store's handle: the chain of public calls that msfl_grids_scan_novelty is defined as.
+inline ScanNoveltyResult ScanNovelty(const std::vector<HybridGrid*>& grids, const std::shared_ptr<const PointCloud<PointType>>& scan, const Rigid3d& pose,
+                                     const msfl_novelty_config* config = nullptr) {
+  msfl_novelty_config c;
+  if (config) c = *config; else msfl_novelty_default_config(&c);
+  if (grids.empty()) throw std::invalid_argument("ScanNovelty: no store");
+  std::vector<float> image;
+  for (std::size_t k = 0; k < grids.size(); ++k) grids[k]->Render(pose, &image, &c.image, k > 0);
+  ScanNoveltyResult out;
+  const std::vector<msfl_point> in = adapter::Pack(*scan);
+  std::vector<msfl_point> masked(in.size() + 1);
+  out.cls.assign(in.size() + 1, 0);
+  detail::Check(msfl_scan_novelty(grids[0]->handle(), in.data(), static_cast<int>(in.size()), image.data(), &c, out.cls.data(), masked.data(), &out.info,
+                                  MSFL_MEM_HOST), grids[0]->handle(), "msfl_scan_novelty");
+  out.cls.resize(in.size());
+  out.kept = std::make_shared<PointCloud<PointType>>();
+  for (std::size_t i = 0; i < in.size(); ++i)
+    if ((c.keep_classes >> out.cls[i]) & 1) out.kept->points.push_back(scan->points[i]);
+  return out;
+}
 
 // LaserOdometry + LaserMapping as one device-resident pipeline (msfl_slam_*): the raw cloud of
 // RealHandleLaserCloudMessage (msf_loam_node.cc:160-167) in, pose_scan2world_ (laser_odometry.cc:79) and

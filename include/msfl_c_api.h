@@ -989,6 +989,77 @@ typedef struct msfl_grid_carve_info {
 msfl_status msfl_grid_carve(msfl_grid* g, const msfl_point* scan, int n, const double pose7[7], const msfl_carve_config* cfg,
                             msfl_point* removed, int capacity, msfl_mem mem, msfl_grid_carve_info* info);
 
+/* Render and scan novelty: the carve's mirror image (docs/kernels/novelty.md has the definition in full).  The carve asks which
+   STORED points a scan sees through; these calls ask which SCAN points stand in space the map saw through.
+     msfl_grid_render   the range image the store predicts for a sensor at pose7: every stored point goes through the inverse of pose7
+                        exactly as the carve's test takes it (the pose inverted in f64, the point f32 -> f64 -> q' p + t' -> f32, the
+                        quaternion as given), then through the carve's pixel rule; range_img[row * n_col + col] is the minimum range of
+                        the points with that pixel, +inf (bits 0x7f800000) where there is none.  accumulate = 0 sets the image to +inf
+                        first; accumulate = 1 takes the minimum into the image that is there, so the corner store and then the surf store
+                        give one image.  The minimum is an unsigned one on the bit patterns: the order of the calls does not matter.
+                        Only n_col, n_row, the elevations and the ranges of cfg matter here.  The store is only read.
+     msfl_scan_novelty  one class per scan point (sensor frame) against such an image.  For the point's pixel (row, col) the window
+                        covers the rows row +- window_row clamped to the image (a repeated edge row is counted again) and the columns
+                        col +- window_col wrapping round the turn; support = the window positions whose map pixel is not +inf, mlim =
+                        the unsigned minimum of the map pixels over the window.  An empty centre pixel does not void the window.
+                          MSFL_NOV_NONE      the point has no pixel
+                          MSFL_NOV_UNSEEN    support < min_support: the map holds no evidence round this ray
+                          MSFL_NOV_IN_FRONT  otherwise, and (r * (1 + margin_rel)) + margin_abs < mlim in f32: everything the map holds
+                                             round this ray lies well beyond the return
+                          MSFL_NOV_COVERED   otherwise
+                        IN_FRONT means new relative to the map, not moving: a newly placed static object is labelled the same way.
+     masked_out  : NULL, or one point per point: scan[i] when keep_classes has bit (1 << class), else x = y = z = NaN and the fourth
+                   field untouched (the contract of msfl_segment_scans: it goes straight into msfl_extract_features* or
+                   msfl_slam_add_scan).  Must not overlap scan.
+     mem         : where pose7, range_img / map_img, scan and the outputs live.  Configurations and info records are HOST data.
+     info        : NULL with device memory: the call only enqueues on the handle's stream and never waits.  Non-NULL: the counts are read
+                   back (the call synchronises).  A host-memory call always waits.
+     cfg         : NULL = msfl_carve_default_config / msfl_novelty_default_config.
+   MSFL_BAD_ARG, before anything is staged or launched: a null g / h / pose7 / range_img / map_img, n < 0, scan or cls_out NULL with
+   n > 0, masked_out overlapping scan, a configuration outside the limits of msfl_carve_config, min_support outside
+   [1, (2 window_col + 1)(2 window_row + 1)], keep_classes outside [0, 15], a host pose that is not finite.  A device-resident pose
+   that is not finite is refused on the device: nothing is rendered (the image is all +inf with accumulate = 0 and untouched with
+   accumulate = 1), info->applied = 0 and the status is MSFL_BAD_ARG when info is read back.  Image values that are neither positive
+   floats nor +inf are the caller's error: they are compared by bit pattern and no index depends on them. */
+typedef struct msfl_grid_render_info {
+  int n_tested;                            /* stored points that had a pixel */
+  int applied;                             /* 1, or 0 when a device-resident pose was refused: nothing rendered */
+} msfl_grid_render_info;
+
+msfl_status msfl_grid_render(msfl_grid* g, const double pose7[7], const msfl_carve_config* cfg, float* range_img, int accumulate,
+                             msfl_mem mem, msfl_grid_render_info* info);
+
+enum { MSFL_NOV_NONE = 0, MSFL_NOV_UNSEEN = 1, MSFL_NOV_COVERED = 2, MSFL_NOV_IN_FRONT = 3, MSFL_NOV_CLASSES = 4 };
+
+typedef struct msfl_novelty_config {
+  msfl_carve_config image;                 /* the image geometry, the two margins and the window */
+  int min_support;                         /* window positions that must hold a map pixel before a point is judged */
+  int keep_classes;                        /* bit (1 << class) set: masked_out keeps the points of that class; 0 .. 15 */
+} msfl_novelty_config;
+
+/* msfl_carve_default_config with a window of 2 x 1 pixels, min_support = 1, keep = NONE | UNSEEN | COVERED. */
+void msfl_novelty_default_config(msfl_novelty_config* cfg);
+
+typedef struct msfl_novelty_info {
+  int n_class[4];                          /* points per class, MSFL_NOV_NONE .. MSFL_NOV_IN_FRONT; their sum is n */
+  int n_map_pixels;                        /* non-empty pixels of the image the labels were taken against */
+  int n_kept;                              /* points whose class is in keep_classes */
+  int applied;                             /* 1; 0 when msfl_grids_scan_novelty's device-resident pose was refused */
+  int reserved_;
+} msfl_novelty_info;
+
+/* n == 0 is a scan that saw nothing: the counts are zero, MSFL_OK. */
+msfl_status msfl_scan_novelty(msfl_handle* h, const msfl_point* scan, int n, const float* map_img, const msfl_novelty_config* cfg,
+                              uint8_t* cls_out, msfl_point* masked_out, msfl_novelty_info* info, msfl_mem mem);
+
+/* The chain in one call: msfl_grid_render of grids[0] with accumulate = 0, of grids[1 .. n_grids - 1] with accumulate = 1, all with
+   cfg->image at pose7, then msfl_scan_novelty against that image; every output byte is what a caller chaining the public calls gets.
+   n_grids in [1, 8], all grids of one handle (anything else: MSFL_BAD_ARG).  map_img_out: NULL, or n_row x n_col floats that receive
+   the image.  A device-resident pose that is not finite: the image is all +inf, every point is MSFL_NOV_NONE, info->applied = 0. */
+msfl_status msfl_grids_scan_novelty(msfl_grid* const* grids, int n_grids, const msfl_point* scan, int n, const double pose7[7],
+                                    const msfl_novelty_config* cfg, uint8_t* cls_out, msfl_point* masked_out, float* map_img_out,
+                                    msfl_novelty_info* info, msfl_mem mem);
+
 
 /* ------------------------------------------------------------------------------------------ */
 /* Scan segmentation: ground and range-image clusters before extraction (after LeGO-LOAM).      */

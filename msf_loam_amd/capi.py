@@ -35,7 +35,8 @@ PROTOTYPES = dict(t.split("=") for t in """
     msfl_deskew_cloud=i:pppipppi msfl_undistort_cloud=i:pppii msfl_grid_create=i:pffp msfl_grid_destroy=v:p msfl_grid_insert_scan=i:ppii
     msfl_grid_get_surrounded=i:ppippipi msfl_grid_size=i:ppp msfl_grid_dump=i:ppipi msfl_grid_dump_cells=i:ppip msfl_grid_stats=i:pp
     msfl_grid_crop=i:ppppiip msfl_grid_crop_tiles=i:ppppipiip msfl_grid_load_cells=i:ppipiipp msfl_carve_default_config=v:p msfl_carve_tables=i:ppppp
-    msfl_grid_carve=i:ppipppiip msfl_segment_default_config=v:p msfl_segment_tables=i:pppppp msfl_segment_scans=i:pippppppppi
+    msfl_grid_carve=i:ppipppiip msfl_grid_render=i:ppppiip msfl_novelty_default_config=v:p msfl_scan_novelty=i:ppipppppi
+    msfl_grids_scan_novelty=i:pipippppppi msfl_segment_default_config=v:p msfl_segment_tables=i:pppppp msfl_segment_scans=i:pippppppppi
     msfl_segment_scan=i:pppipppppi msfl_slam_default_config=v:p msfl_slam_create=i:ppip
     msfl_slam_destroy=v:p msfl_slam_add_scan=i:pppiip msfl_slam_add_scan_imu=i:pppiipp msfl_slam_get_result=i:pip msfl_slam_set_uncertainty=i:pid
     msfl_slam_get_uncertainty=i:pipp msfl_slam_set_degeneracy=i:piidd msfl_slam_get_degeneracy=i:pipp msfl_slam_set_outlier_rejection=i:ppp
@@ -352,6 +353,88 @@ class GridCarveInfo(C.Structure):
 
     def as_tuple(self):
         return (self.n_points_removed, self.n_cells_emptied, self.n_cells, self.n_points, self.n_tested, self.n_pixels, self.applied)
+
+
+NOV_NONE, NOV_UNSEEN, NOV_COVERED, NOV_IN_FRONT = range(4)                   # MSFL_NOV_*: the classes of msfl_scan_novelty
+NOV_CLASS_NAMES = ("none", "unseen", "covered", "in_front")
+
+
+class GridRenderInfo(C.Structure):
+    """msfl_grid_render_info; `status` (a Python attribute) is the msfl_status of the call that filled it."""
+    _fields_ = [("n_tested", C.c_int), ("applied", C.c_int)]
+    status = OK
+
+
+class NoveltyConfig(C.Structure):
+    """msfl_novelty_config (include/msfl_c_api.h, docs/kernels/novelty.md): `image` is a CarveConfig."""
+    _fields_ = [("image", CarveConfig), ("min_support", C.c_int), ("keep_classes", C.c_int)]
+
+
+def novelty_config(**kw):
+    """msfl_novelty_default_config with the given fields replaced; a field of msfl_carve_config goes into `image`."""
+    c = NoveltyConfig()
+    load().msfl_novelty_default_config(C.byref(c))
+    for k, v in kw.items():
+        if k in ("min_support", "keep_classes"):
+            setattr(c, k, v)
+        elif k in dict(CarveConfig._fields_):
+            setattr(c.image, k, v)
+        else:
+            raise TypeError("msfl_novelty_config has no field " + k)
+    return c
+
+
+class NoveltyInfo(C.Structure):
+    """msfl_novelty_info; `status` (a Python attribute) is the msfl_status of the call that filled it."""
+    _fields_ = [("n_class", C.c_int * 4), ("n_map_pixels", C.c_int), ("n_kept", C.c_int), ("applied", C.c_int), ("reserved_", C.c_int)]
+    status = OK
+
+    def as_tuple(self):
+        return (tuple(self.n_class), self.n_map_pixels, self.n_kept, self.applied)
+
+
+def _novelty_host(call, scan, config, want_masked, what, check, allow):
+    """The host-memory half shared by Handle.scan_novelty and grids_scan_novelty: call(scan, n, cfg, cls, masked, info) is the C
+    call with its other arguments bound.  Returns dict(cls, masked, info)."""
+    scan = _pts(scan)
+    n = len(scan)
+    cls = np.zeros(max(n, 1), np.uint8)
+    masked = np.zeros((max(n, 1), 4), np.float32) if want_masked else None
+    info = NoveltyInfo()
+    cfg = C.byref(config) if config is not None else None
+    info.status = check(call(_vp(scan), n, cfg, _vp(cls), _vp(masked), C.byref(info)), what, allow)
+    return dict(cls=cls[:n], masked=None if masked is None else masked[:n], info=info)
+
+
+def grids_scan_novelty(grids, scan, pose, config=None, want_masked=True, want_image=False, allow=()):
+    """msfl_grids_scan_novelty through host memory: render `grids` (Grid objects of one handle) at the map pose `pose` into one image
+    and label `scan` (sensor frame) against it.  Returns dict(cls, masked, info, image): cls uint8 per point (NOV_*), masked the
+    cloud with the dropped points set to NaN, info a NoveltyInfo, image (n_row, n_col) f32 with want_image."""
+    grids = list(grids)
+    cfg = config if config is not None else novelty_config()
+    arr = (C.c_void_p * max(len(grids), 1))(*[g.g.value for g in grids])
+    pose = np.ascontiguousarray(pose, dtype=np.float64)
+    img = np.zeros((cfg.image.n_row, cfg.image.n_col), np.float32) if want_image else None
+    lib, owner = grids[0].lib, grids[0]
+    out = _novelty_host(lambda s, n, c, cls, m, info: lib.msfl_grids_scan_novelty(arr, len(grids), s, n, _vp(pose), c, cls, m, _vp(img), info, MEM_HOST),
+                        scan, cfg, want_masked, "msfl_grids_scan_novelty", owner._check, allow)
+    out["image"] = img
+    return out
+
+
+def grids_scan_novelty_device(grids, scan_ptr, n, pose_ptr, config, cls_ptr, masked_ptr=None, image_ptr=None, want_info=False, allow=()):
+    """msfl_grids_scan_novelty with the scan, the pose (7 doubles) and the outputs in device memory.  Without want_info the call
+    only enqueues and returns None; with it the NoveltyInfo."""
+    grids = list(grids)
+    arr = (C.c_void_p * max(len(grids), 1))(*[g.g.value for g in grids])
+    info = NoveltyInfo() if want_info else None
+    cfg = C.byref(config) if config is not None else None
+    s = grids[0]._check(grids[0].lib.msfl_grids_scan_novelty(arr, len(grids), _vp(scan_ptr), int(n), _vp(pose_ptr), cfg, _vp(cls_ptr), _vp(masked_ptr),
+                                                             _vp(image_ptr), C.byref(info) if want_info else None, MEM_DEVICE),
+                        "msfl_grids_scan_novelty(device)", allow)
+    if want_info:
+        info.status = s
+    return info
 
 
 SEG_NONE, SEG_SHADOWED, SEG_GROUND, SEG_SEGMENT, SEG_OUTLIER = range(5)      # MSFL_SEG_*: the classes of msfl_segment_scans
@@ -1214,6 +1297,27 @@ class Handle(_Owner):
             out["info"] = out["info"][0]
         return out
 
+    # ---- scan novelty (msfl_scan_novelty) ----
+    def scan_novelty(self, scan, map_img, config=None, want_masked=True, allow=()):
+        """msfl_scan_novelty through host memory (docs/kernels/novelty.md): one class per point of `scan` (sensor frame) against the
+        map image `map_img` (n_row x n_col f32, what Grid.render delivers).  Returns dict(cls, masked, info): cls uint8 per point
+        (NOV_NONE .. NOV_IN_FRONT), masked the cloud with the dropped points set to NaN (hand it to extract_features* or
+        Slam.add_scan), info a NoveltyInfo."""
+        img = np.ascontiguousarray(map_img, dtype=np.float32)
+        return _novelty_host(lambda s, n, c, cls, m, info: self.lib.msfl_scan_novelty(self.h, s, n, _vp(img), c, cls, m, info, MEM_HOST),
+                             scan, config, want_masked, "msfl_scan_novelty", self._check, allow)
+
+    def scan_novelty_device(self, scan_ptr, n, map_img_ptr, config, cls_ptr, masked_ptr=None, want_info=False, allow=()):
+        """msfl_scan_novelty with the scan, the image and the outputs in device memory (tensors or addresses).  Without want_info
+        the call only enqueues and returns None; with it the NoveltyInfo."""
+        info = NoveltyInfo() if want_info else None
+        cfg = C.byref(config) if config is not None else None
+        s = self._check(self.lib.msfl_scan_novelty(self.h, _vp(scan_ptr), int(n), _vp(map_img_ptr), cfg, _vp(cls_ptr), _vp(masked_ptr),
+                                                   C.byref(info) if want_info else None, MEM_DEVICE), "msfl_scan_novelty(device)", allow)
+        if want_info:
+            info.status = s
+        return info
+
     def transform_cloud(self, pts, pose7):
         """TransformPointCloud (laser_mapping.cc:24-31)."""
         pts = _pts(pts)
@@ -1399,6 +1503,34 @@ class Grid(_Owner):
         cfg = C.byref(config) if config is not None else None
         info.status = self._check(self.lib.msfl_grid_carve(self.g, _vp(scan_ptr), int(n), _vp(pose_ptr), cfg, _vp(removed_ptr), int(capacity),
                                                            MEM_DEVICE, C.byref(info)), "msfl_grid_carve(device)", allow)
+        return info
+
+    def render(self, pose, config=None, image=None, accumulate=False, allow=()):
+        """msfl_grid_render through host memory: the range image (n_row, n_col) f32 this store predicts for a sensor at the map pose
+        `pose`, +inf where it holds nothing.  accumulate: the minimum is taken into `image` (rendered from another store before) and
+        the result is a new array.  config: a CarveConfig (None: the defaults).  Returns (image, GridRenderInfo)."""
+        cfg = config if config is not None else carve_config()
+        pose = np.ascontiguousarray(pose, dtype=np.float64)
+        if accumulate:
+            img = np.array(image, dtype=np.float32, order="C", copy=True)
+            if img.size != cfg.n_row * cfg.n_col:
+                raise ValueError("render: `image` is not n_row x n_col")
+        else:
+            img = np.zeros(cfg.n_row * cfg.n_col, np.float32)
+        info = GridRenderInfo()
+        info.status = self._check(self.lib.msfl_grid_render(self.g, _vp(pose), C.byref(cfg), _vp(img), int(bool(accumulate)), MEM_HOST, C.byref(info)),
+                                  "msfl_grid_render", allow)
+        return img.reshape(cfg.n_row, cfg.n_col), info
+
+    def render_device(self, pose_ptr, config, image_ptr, accumulate=False, want_info=False, allow=()):
+        """msfl_grid_render with the pose (7 doubles) and the image in device memory.  Without want_info the call only enqueues and
+        returns None; with it the GridRenderInfo."""
+        info = GridRenderInfo() if want_info else None
+        cfg = C.byref(config) if config is not None else None
+        s = self._check(self.lib.msfl_grid_render(self.g, _vp(pose_ptr), cfg, _vp(image_ptr), int(bool(accumulate)), MEM_DEVICE,
+                                                  C.byref(info) if want_info else None), "msfl_grid_render(device)", allow)
+        if want_info:
+            info.status = s
         return info
 
 

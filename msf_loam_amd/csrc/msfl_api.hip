@@ -236,6 +236,16 @@ struct SegmentScratch {      // msfl_segment_scan*: allocated by the first call,
   DevBuf ctr;                // int[SEG_CTR_WORDS x chunk scans]: the counters of the chunk in flight
   DevBuf info;               // int[SEG_INFO_WORDS x n_scans]: the info records before they are read back
 };
+struct NoveltyScratch {      // msfl_grid_render / msfl_scan_novelty / msfl_grids_scan_novelty: allocated by the first call, no other call touches these
+  DevBuf img;                // u32[n_col x n_row]: the map image of a host-memory call, and of a composite call without map_img_out
+  DevBuf win;                // u32 mlim[npix], then int support[npix]: the window's minimum and support per pixel
+  DevBuf tab;                // float: cc, cs [n_col / 2 each], ec, es [n_row + 1 each] (msfl_carve_tables) of tab_cfg
+  DevBuf ctr;                // int[NOV_CTR_WORDS]: msfl_novelty_info, then msfl_grid_render_info, as the kernels count them
+  DevBuf pose;               // double[8]: the pose of a host-memory call
+  DevBuf in_scan, out_cls, out_masked;   // float4 / u8 / float4 [n]: the staged scan and the outputs before they go back (host mode)
+  msfl_carve_config tab_cfg{};           // the configuration `tab` was built from; the tables are rebuilt when the geometry differs
+  bool tab_valid = false;
+};
 
 enum TimerClass { T_ASSOC = 0, T_SOLVE, T_INDEX, T_EXTRACT, T_ODOM, T_FIT, T_ASSOC_SEEDED /* a subset of T_ASSOC */, T_COUNT };
 
@@ -313,6 +323,7 @@ struct msfl_handle_s {
   ScoreScratch sc;
   SearchScratch se;
   SegmentScratch sg;
+  NoveltyScratch nv;
   int seg_chunk_scans = 0;                // MSFL_SEG_CHUNK_SCANS: scans per chunk of msfl_segment_scans (0 = what the scratch budget holds)
   int search_chunk_pairs = 0;             // MSFL_SEARCH_CHUNK_PAIRS: pairs per chunk of msfl_search_pairs (0 = what the scratch budget holds)
 
@@ -1378,6 +1389,7 @@ msfl_status msfl_solve_records_deskew(msfl_handle* h, const msfl_point* corner, 
 #include "msfl_api_score.inc"
 #include "msfl_api_search.inc"
 #include "msfl_api_segment.inc"
+#include "msfl_api_novelty.inc"
 #include "msfl_api_place.inc"
 
 namespace {
